@@ -18,6 +18,10 @@ collective on the data path (weak scaling: pairs per GPU fixed); only the
 timing is reduced (MAX).  One frame = 5 ms of SOURCE audio (240 samples).
 Rank 0 prints one JSON line.
 
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write --dump-outputs, print the
+line.  --full adds everything else the benchmark measures and checks after the timed steps (per-kernel durations,
+roofline, the variants, config 4, the CPU baseline, parity with the CPU chain).
+
 --driver streams is round 3's driver (one stream and one graph per pair; it
 needs GPU_MAX_HW_QUEUES, see below), --driver serial runs one wave of the
 lockstep driver on ONE stream (per-kernel durations as rocprofv3 sees them).
@@ -40,17 +44,50 @@ def _argv_value(flag, default):
 
 # The stream-per-pair drivers (--driver streams, the utterance workloads) only overlap their streams if these land on
 # different hardware queues; the runtime's default of 4 serialises the rest (round 3: 4 queues 1.43 M frames/s, 64:
-# 1.91 M).  The variable must be in the environment before the HIP runtime starts.  The default lockstep driver uses
-# four streams and leaves the environment alone.
+# 1.91 M).  32 is the number of hardware queues the chip has.  The variable must be in the environment before the HIP
+# runtime starts.  The default lockstep driver uses four streams and leaves the environment alone.
 if _argv_value('--driver', 'batch') == 'streams' or (_argv_value('--workload', 'pair') == 'utterance' and
                                                    int(_argv_value('--utterances', '0')) == 0):
-    os.environ.setdefault('GPU_MAX_HW_QUEUES', '64')
+    os.environ.setdefault('GPU_MAX_HW_QUEUES', '32')
 
 FS = 48000
 FRAME_PERIOD = 5.0
 # counter summaries of the current kernels (tools/final_measure.sh + tools/collect_profiles.sh)
 PMC_TRAFFIC, PMC_SQ = 'r5_pmc_traffic.json', 'r5_pmc_sq_summary.json'
 METRIC = 'frames/sec end-to-end analyse->align->convert->synth, 48 kHz 5 ms hop'
+# --dump-outputs: at most DUMP_BUDGET bytes of values in all (below 64 MB with the files' headers); DUMP_SAMPLE
+# positions of every item, seeded with DUMP_SEED
+DUMP_BUDGET = 60 << 20
+DUMP_SAMPLE = 4096
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, outputs):
+    """Write what the timed path computed in its last step: `outputs` = {name: one 1-D device tensor per item (pair or
+    utterance)}.  <name>_sample.npy: every item (rows) at the same DUMP_SAMPLE positions (a fixed seeded choice below
+    the shortest item's length); <name>_<index>.npy: whole items of a fixed seeded choice, as many as fit in the
+    budget the samples leave (shared evenly between the names).  float64, float32 for 16-bit samples."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    outputs = {k: v for k, v in sorted(outputs.items()) if v}
+    rs = np.random.RandomState(DUMP_SEED)
+    dtypes = {k: np.float32 if v[0].dtype == torch.int16 else np.float64 for k, v in outputs.items()}
+    npos = {k: min(DUMP_SAMPLE, min(a.numel() for a in v)) for k, v in outputs.items()}
+    left = DUMP_BUDGET - sum(len(v) * npos[k] * np.dtype(dtypes[k]).itemsize for k, v in outputs.items())
+    share = left // max(1, len(outputs))
+    for name, items in outputs.items():
+        dt = dtypes[name]
+        pos = np.sort(rs.choice(min(a.numel() for a in items), npos[name], replace=False))
+        pos_dev = torch.from_numpy(pos).to(items[0].device)
+        np.save(os.path.join(dirname, f'{name}_sample.npy'),
+                np.stack([a.reshape(-1)[pos_dev].cpu().numpy().astype(dt) for a in items]))
+        used = 0
+        for i in rs.permutation(len(items)):
+            size = items[i].numel() * np.dtype(dt).itemsize
+            if used + size > share:
+                break
+            np.save(os.path.join(dirname, f'{name}_{i:03d}.npy'), items[i].reshape(-1).cpu().numpy().astype(dt))
+            used += size
 
 
 def pair_silence(index, K=1025):
@@ -185,9 +222,11 @@ def config4_seeds(total, rank, world):
     return list(range(rank, total, world))
 
 
-def config4_measure(args, grp, utts, steps, warmup):
+def config4_measure(args, grp, utts, steps, warmup, checks=True):
     """Time `steps` passes of this rank's share of the config-4 batch (analyse + resynthesise every utterance, in
-    lockstep waves of 16 or through a stream pool) under the contract's protocol.  Returns a dict (all ranks)."""
+    lockstep waves of 16 or through a stream pool) under the contract's protocol.  Returns a dict (all ranks); 'first'
+    holds the waveforms of the last timed pass.  checks: also check them for finiteness and run one more pass that
+    must reproduce them bit for bit."""
     import torch
     import torch.distributed as dist
     rank, local_rank, world, dev, rdev = grp
@@ -216,6 +255,9 @@ def config4_measure(args, grp, utts, steps, warmup):
         dist.barrier()
     el = time.perf_counter() - t0
     el, frames_total, ranks_seen, per_rank = reduce_ranks(rank, world, rdev, el, float(frames_step * steps))
+    if not checks:
+        return {'seconds': el, 'frames_total': frames_total, 'ranks_seen': ranks_seen, 'per_rank_frames_per_s': per_rank,
+                'lockstep': lockstep, 'first': out, 'out': out}
     finite = all(bool(torch.isfinite(w).all().item()) for w in out)
     first = [w.clone() for w in out]
     step()
@@ -242,28 +284,12 @@ def main_batch(args):
     grp = init_group(args)
     rank, local_rank, world, dev, rdev = grp
     from kwiiyatta_amd import pipeline as pl
-    m = config4_measure(args, grp, utts, args.steps, args.warmup)
-    el, frames_total, finite, identical, lockstep, first = (m['seconds'], m['frames_total'], m['finite'], m['identical'],
-                                                             m['lockstep'], m['first'])
+    m = config4_measure(args, grp, utts, args.steps, args.warmup, checks=args.full)
+    el, frames_total, lockstep, first = m['seconds'], m['frames_total'], m['lockstep'], m['first']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'wave': first})
     if rank == 0:
-        # the D4C stage (dominant whole-chip kernels) of one utterance alone, HIP events on its stream
-        lone = pl.UtterancePipeline(local_rank, FS, utts[0])
-        lone.run(); lone.sync()
-        lone.profile(True)
-        per = {}
-        for _ in range(7):
-            lone.run(); lone.sync()
-            for nme in ('k_d4c_body', 'k_d4c_bands', 'k_cheaptrick', 'k_syn_pulse'):
-                ms, n = lone.profile_read(nme)
-                if n:
-                    per.setdefault(nme, []).append(ms / n)
-        lone.profile(False)
-        alone = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
-        T, K = lone.T, lone.K
-        hop = FS * FRAME_PERIOD / 1000.0
-        d4c_ms = alone.get('k_d4c_body', float('nan')) + alone.get('k_d4c_bands', float('nan'))
-        bytes_per_launch = T * (hop * 8 + 16 + K * 8)
-        achieved = bytes_per_launch / (d4c_ms * 1e-3) / 1e9
+        T, K = len(utts[0][1]), pl.lib.kwy_cheaptrick_fft_size(FS, 71.0) // 2 + 1
         value = frames_total / el
         res = {
             'metric': METRIC, 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
@@ -286,14 +312,34 @@ def main_batch(args):
                                        else f'utterance-per-stream x{args.batch}, utterance-per-GPU x{world}, no collective')},
             'real_time_factor': value / 200.0,
             'hbm_fraction_whole_path': value / world * 36664 / 8e12,
+        }
+    if rank == 0 and args.full:
+        # the D4C stage (dominant whole-chip kernels) of one utterance alone, HIP events on its stream
+        lone = pl.UtterancePipeline(local_rank, FS, utts[0])
+        lone.run(); lone.sync()
+        lone.profile(True)
+        per = {}
+        for _ in range(7):
+            lone.run(); lone.sync()
+            for nme in ('k_d4c_body', 'k_d4c_bands', 'k_cheaptrick', 'k_syn_pulse'):
+                ms, n = lone.profile_read(nme)
+                if n:
+                    per.setdefault(nme, []).append(ms / n)
+        lone.profile(False)
+        alone = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
+        hop = FS * FRAME_PERIOD / 1000.0
+        d4c_ms = alone.get('k_d4c_body', float('nan')) + alone.get('k_d4c_bands', float('nan'))
+        bytes_per_launch = T * (hop * 8 + 16 + K * 8)
+        achieved = bytes_per_launch / (d4c_ms * 1e-3) / 1e9
+        res.update({
             'kernel_ms_per_launch_alone': alone,
             'roofline': {'bound': 'hbm', 'kernel': 'k_d4c_body+k_d4c_bands', 'achieved': achieved, 'peak': 8000.0,
                          'unit': 'GB/s', 'frac': achieved / 8000.0, 'traffic': None, 'avg_launch_ms': d4c_ms,
                          'algorithmic_bytes_per_launch': bytes_per_launch,
                          'note': 'one utterance alone, HIP events on its stream, median of 7 passes'},
-            'checks': {'all_outputs_finite': finite, 'second_pass_bit_identical': identical},
+            'checks': {'all_outputs_finite': m['finite'], 'second_pass_bit_identical': m['identical']},
             'cpu_baseline': None,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             from oracle import oracle as ko
             x, f0, t = utts[0]
@@ -307,6 +353,7 @@ def main_batch(args):
                                              f'oracle/liboracle.so, 1 thread, {sec:.1f} s'}
             res['parity'] = {'wave_rms_vs_cpu_chain': float(np.sqrt(np.mean((first[0].cpu().numpy() - ref) ** 2))),
                              'tolerance': 1e-4, 'note': 'utterance 0 against the all-oracle analyse -> synthesise chain'}
+    if rank == 0:
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()
@@ -323,7 +370,7 @@ def main_lockstep(args):
     # ---- host-side signal generation first, in fresh worker processes, before this process touches the GPU
     mine = list(range(rank, world * args.batch, world))       # = parallel.shard_indices: pair i belongs to rank i % W
     nbase = min(len(mine), args.distinct)      # distinct host-generated signal pairs (default: every pair of the batch)
-    c4_total = 0 if (serial or args.config4 == 'off') else args.config4_utterances
+    c4_total = 0 if (serial or args.config4 == 'off' or not args.full) else args.config4_utterances
     c4_seeds = config4_seeds(c4_total, rank, world)
     made = host_generate(sum((pair_jobs(mine[i], args.seconds) for i in range(nbase)), []) +
                          [(sd, args.seconds) for sd in c4_seeds])
@@ -397,6 +444,44 @@ def main_lockstep(args):
     el_own = time.perf_counter() - t0
     el, frames_total, ranks_seen, per_rank = reduce_ranks(rank, world, rdev, el_own, float(pipe.frames * args.steps))
     value = frames_total / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'wave': [pipe.wave(k) for k in range(pipe.n_pairs)],
+                                         'pcm16': [pipe.pcm16(k) for k in range(pipe.n_pairs)] if wav else []})
+    head = {
+        'metric': METRIC, 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': 1000.0 * el / args.steps, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+        'config': {
+            'workload': ('config3: 48 kHz source (10 s, T=2001) + target (11 s, T=2201) pairs: ' +
+                         ('f0 by DIO+StoneMask of both (wav in), ' if wav else '') + 'CheapTrick+D4C of '
+                         'both, pad with freshly drawn silent spectra, sp2mc, FastDTW(radius 32) align, GMM(%d comp, '
+                         'D=144)+MLPG convert, mc2sp, WORLD synthesis' % args.components +
+                         (', post-step + int16 (pcm out)' if wav else '')),
+            'pairs_per_gpu': args.batch, 'source_frames_per_pair': pipe.waves[0].T[0],
+            'driver': 'one stream, kernel after kernel (--driver serial)' if serial else
+                      'lockstep: %d waves of <= 16 pairs, two streams per wave, batched entries (one grid per stage and '
+                      'wave)' % len(pipe.waves),
+            'streams_per_gpu': 1 if serial else 2 * len(pipe.waves),
+            'GPU_MAX_HW_QUEUES': os.environ.get('GPU_MAX_HW_QUEUES'),
+            'launch': 'the whole step is one captured HIP graph' if args.graph else 'one host launch per kernel',
+            'pad_spectra': 'drawn INSIDE every step: 4 x 100 x 1025 values per pair from numpy\'s legacy generator '
+                           '(MT19937 + polar Box-Muller) continued on the device, one call per step '
+                           '(kwy_np_normal_blocks_dev); with --full, draws_check compares the generator with numpy '
+                           'afterwards',
+            'gmm_model_prepared': 'once per converter (the per-mixture matrices depend on the GMM only)',
+            'parallelism': f'pairs in lockstep x{args.batch} per GPU, pair-per-GPU x{world}, no collective'},
+        'real_time_factor': value / 200.0,
+        'hbm_fraction_whole_path': value / world * 81000 / 8e12,
+        'distinct_pairs_per_gpu': nbase,
+        'ranks_seen': ranks_seen,
+        'per_rank_frames_per_s': per_rank,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # One more (untimed) pass with the generator's state read before it: numpy, set to that state, must draw the same
     # pads for all pairs and end in the same state.  Pair 0's pads, DTW path and waveform of that pass feed the parity
@@ -590,30 +675,8 @@ def main_lockstep(args):
                     for k in ('k_d4c_body', 'k_d4c_bands') if k in sq}
             except (OSError, KeyError, ValueError):
                 pass
-        out = {
-            'metric': METRIC, 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': 1000.0 * el / args.steps, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {
-                'workload': ('config3: 48 kHz source (10 s, T=2001) + target (11 s, T=2201) pairs: ' +
-                             ('f0 by DIO+StoneMask of both (wav in), ' if wav else '') + 'CheapTrick+D4C of '
-                             'both, pad with freshly drawn silent spectra, sp2mc, FastDTW(radius 32) align, GMM(%d comp, '
-                             'D=144)+MLPG convert, mc2sp, WORLD synthesis' % args.components +
-                             (', post-step + int16 (pcm out)' if wav else '')),
-                'pairs_per_gpu': args.batch, 'source_frames_per_pair': pipe.waves[0].T[0],
-                'driver': 'one stream, kernel after kernel (--driver serial)' if serial else
-                          'lockstep: %d waves of <= 16 pairs, two streams per wave, batched entries (one grid per stage and '
-                          'wave)' % len(pipe.waves),
-                'streams_per_gpu': 1 if serial else 2 * len(pipe.waves),
-                'GPU_MAX_HW_QUEUES': os.environ.get('GPU_MAX_HW_QUEUES'),
-                'launch': 'the whole step is one captured HIP graph' if args.graph else 'one host launch per kernel',
-                'pad_spectra': 'drawn INSIDE every step: 4 x 100 x 1025 values per pair from numpy\'s legacy generator '
-                               '(MT19937 + polar Box-Muller) continued on the device, one call per step '
-                               '(kwy_np_normal_blocks_dev); draws_check compares the generator with numpy afterwards',
-                'gmm_model_prepared': 'once per converter (the per-mixture matrices depend on the GMM only)',
-                'parallelism': f'pairs in lockstep x{args.batch} per GPU, pair-per-GPU x{world}, no collective'},
-            'real_time_factor': value / 200.0,
-            'hbm_fraction_whole_path': value / world * 81000 / 8e12,
+        out = dict(head)
+        out.update({
             'kernel_ms_per_launch': {k: v[0] / v[1] for k, v in sorted(kernel_ms.items())},
             'kernel_ms_per_launch_alone': {k: v for k, v in sorted(alone_ms.items())},
             'roofline': roofline,
@@ -623,12 +686,9 @@ def main_lockstep(args):
             'with_pcie': variants.get('with_pcie'),
             'wav_in_pcm_out': variants.get('wav_in_pcm_out'),
             'parity': None,
-            'distinct_pairs_per_gpu': nbase,
-            'ranks_seen': ranks_seen,
-            'per_rank_frames_per_s': per_rank,
             'config4': config4,
             'cpu_baseline': None,
-        }
+        })
         if not args.no_cpu_baseline and world == 1:
             # the CPU chain on the very pads the device drew for pair 0 in the last timed pass
             src0, tgt0 = base[0]
@@ -700,6 +760,17 @@ def main():
                           'object per convert() call) instead of once per converter')
     ap_.add_argument('--backend', default='nccl', help='torch.distributed backend for N > 1 (nccl = RCCL; gloo lets '
                                                         'several ranks share one GPU when rehearsing the launch)')
+    ap_.add_argument('--full', action='store_true',
+                     help='after the timed steps also measure and check everything beyond the headline: per-kernel '
+                          'durations, roofline, draws check, the variants, config 4 beside config 3, the CPU baseline and '
+                          'the parity against the CPU chain (--no-variants, --config4 off, --no-cpu-baseline and '
+                          '--no-pcie-variant trim this).  Without it a run sets up, warms up, times --steps steps, '
+                          'writes --dump-outputs and prints the headline line')
+    ap_.add_argument('--dump-outputs', metavar='DIR', default=None,
+                     help='write what the timed path computed in its last timed step as DIR/<name>.npy (rank 0\'s '
+                          'items; float64 waveforms, float32 16-bit samples): <name>_sample.npy holds a fixed seeded '
+                          'set of positions of every item, <name>_<index>.npy whole items of a fixed seeded choice; '
+                          f'{DUMP_BUDGET >> 20} MB at most in all')
     args = ap_.parse_args()
     import bench_launch
     bench_launch.maybe_launch(args.gpus)     # --gpus N > 1 outside a rank: become the launcher of N ranks (never returns)
@@ -779,6 +850,52 @@ def main():
         tt = torch.tensor([el], dtype=torch.float64, device=rdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
+    frames_rank = sum(p.frames for p in pipes) * args.steps
+    if world > 1:
+        ft = torch.tensor([frames_rank], dtype=torch.float64, device=rdev)
+        dist.all_reduce(ft, op=dist.ReduceOp.SUM)
+        frames_total = float(ft.item())
+    else:
+        frames_total = float(frames_rank)
+    value = frames_total / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'wave': [p.wave for p in pipes]})
+    # whole-path algorithmic bytes per source frame
+    path_bytes = 36664 if args.workload == 'utterance' else 81000
+    head = {
+        'metric': METRIC, 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': 1000.0 * el / args.steps, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+        'config': {
+            'workload': ('config3: 48 kHz source (10 s, T=2001) + target (11 s, T=2201) pairs: CheapTrick+D4C of '
+                         'both, pad, sp2mc, FastDTW(radius 32) align, GMM(%d comp, D=144)+MLPG convert, mc2sp, '
+                         'WORLD synthesis' % args.components) if args.workload == 'pair' else
+                        'config2: 48 kHz 10 s utterances (T=2001, K=1025): CheapTrick + D4C + WORLD synthesis',
+            'pairs_per_gpu' if args.workload == 'pair' else 'utterances_per_gpu': args.batch,
+            'source_frames_per_pair': pipes[0].frames, 'streams_per_gpu': args.batch,
+            'd4c_on_side_stream': bool(args.side_stream) if args.workload == 'pair' else None,
+            'gmm_model_prepared': ('per pair' if args.gmm_prepare_per_pair else
+                                   'once per converter (the per-mixture matrices depend on the GMM only)')
+            if args.workload == 'pair' else None,
+            'launch': ('one captured HIP graph per pass and stream' +
+                       ('; per-kernel HIP-event durations from the same passes enqueued kernel by kernel right after '
+                        'the timed region' if args.full else '')) if args.graph else
+                      'one host launch per kernel; per-kernel HIP events inside the timed region',
+            'pad_spectra': 'drawn once per pipeline, outside the timed region' +
+                           ('; with_pad_draw times the same steps with fresh pads per pass (device generator / host '
+                            'numpy)' if args.full else '')
+            if args.workload == 'pair' else None,
+            'parallelism': f'utterance-per-stream x{args.batch}, utterance-per-GPU x{world}, no collective'},
+        'real_time_factor': value / 200.0,
+        'hbm_fraction_whole_path': value / world * path_bytes / 8e12,
+        'distinct_pairs_per_gpu': nbase,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head))
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     if args.graph:
         # Per-kernel durations for the roofline object: HIP events cannot be recorded inside a captured graph here
@@ -897,15 +1014,6 @@ def main():
                                'region (np.random.normal from the global legacy generator, one thread) and uploaded; '
                                'never `value`'}
         return res
-
-    frames_rank = sum(p.frames for p in pipes) * args.steps
-    if world > 1:
-        ft = torch.tensor([frames_rank], dtype=torch.float64, device=rdev)
-        dist.all_reduce(ft, op=dist.ReduceOp.SUM)
-        frames_total = float(ft.item())
-    else:
-        frames_total = float(frames_rank)
-    value = frames_total / el
 
     if rank == 0:
         T = pipes[0].frames
@@ -1044,32 +1152,8 @@ def main():
                                'latency of one pair, not the throughput, and has no HBM or MFMA roofline')
                               if top in ('k_dtw_values', 'k_dtw_trace', 'k_syn_phase', 'k_align_project') else
                               'whole-chip kernel'}
-        # whole-path algorithmic bytes per source frame
-        path_bytes = 36664 if args.workload == 'utterance' else 81000
-        out = {
-            'metric': METRIC, 'value': value, 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': 1000.0 * el / args.steps, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {
-                'workload': ('config3: 48 kHz source (10 s, T=2001) + target (11 s, T=2201) pairs: CheapTrick+D4C of '
-                             'both, pad, sp2mc, FastDTW(radius 32) align, GMM(%d comp, D=144)+MLPG convert, mc2sp, '
-                             'WORLD synthesis' % args.components) if args.workload == 'pair' else
-                            'config2: 48 kHz 10 s utterances (T=2001, K=1025): CheapTrick + D4C + WORLD synthesis',
-                'pairs_per_gpu' if args.workload == 'pair' else 'utterances_per_gpu': args.batch,
-                'source_frames_per_pair': T, 'streams_per_gpu': args.batch,
-                'd4c_on_side_stream': bool(args.side_stream) if args.workload == 'pair' else None,
-                'gmm_model_prepared': ('per pair' if args.gmm_prepare_per_pair else
-                                       'once per converter (the per-mixture matrices depend on the GMM only)')
-                if args.workload == 'pair' else None,
-                'launch': ('one captured HIP graph per pass and stream; per-kernel HIP-event durations from the same '
-                           'passes enqueued kernel by kernel right after the timed region') if args.graph else
-                          'one host launch per kernel; per-kernel HIP events inside the timed region',
-                'pad_spectra': 'drawn once per pipeline, outside the timed region; with_pad_draw times the same steps '
-                               'with fresh pads per pass (device generator / host numpy)'
-                if args.workload == 'pair' else None,
-                'parallelism': f'utterance-per-stream x{args.batch}, utterance-per-GPU x{world}, no collective'},
-            'real_time_factor': value / 200.0,
-            'hbm_fraction_whole_path': value / world * path_bytes / 8e12,
+        out = dict(head)
+        out.update({
             'kernel_ms_per_launch': {k: v[0] / v[1] for k, v in sorted(kernel_ms.items())},
             'kernel_ms_per_launch_alone': {k: v for k, v in sorted(alone_ms.items())},
             'roofline': roofline,
@@ -1077,10 +1161,9 @@ def main():
             'with_pcie': None,
             'with_pad_draw': None,
             'parity': None,
-            'distinct_pairs_per_gpu': nbase,
             'largest_summed_kernel': by_sum,
             'cpu_baseline': None,
-        }
+        })
     # the variants come last: every rank takes part, and the per-kernel measurements above are done
     pcie = run_pcie_variant()
     pad = run_pad_variant()

@@ -11,7 +11,7 @@ cp $R/kwiiyatta_amd/libkwy.so $R/scratch/libkwy_tree.so
 for i in 1 2; do
   for v in old new; do
     cp $R/scratch/libkwy_$v.so $R/kwiiyatta_amd/libkwy.so
-    timeout -k 10 300 python $R/bench.py --no-variants --config4 off --no-cpu-baseline > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err || exit 1
+    timeout -k 10 300 python $R/bench.py --full --no-variants --config4 off --no-cpu-baseline > $O/ab_${v}_$i.json 2> $O/ab_${v}_$i.err || exit 1
   done
 done
 cp $R/scratch/libkwy_tree.so $R/kwiiyatta_amd/libkwy.so

@@ -34,7 +34,7 @@ if [ -n "$F" ] && [ -n "$W" ]; then
   cp "$F" $P/${RND}_pmc_fetch_counter_collection.csv
   cp "$W" $P/${RND}_pmc_write_counter_collection.csv
   python $P/make_pmc_traffic.py "$F" "$W" $RND 33616 \
-    "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace (two separate passes) -- python bench.py --driver serial --batch 16 --steps 2 --warmup 1 --no-graph --no-variants --no-cpu-baseline" > /dev/null
+    "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace (two separate passes) -- python bench.py --full --driver serial --batch 16 --steps 2 --warmup 1 --no-graph --no-variants --no-cpu-baseline" > /dev/null
 fi
 [ -f $S/wav_serial_kernel_stats.csv ] && cp $S/wav_serial_kernel_stats.csv $P/${RND}_wav_serial_kernel_stats.csv
 [ -f $S/diff_batch_kernel_stats.csv ] && cp $S/diff_batch_kernel_stats.csv $P/${RND}_diff_batch_kernel_stats.csv

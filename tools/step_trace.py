@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """How busy is the chip during the timed steps of `bench.py` (lockstep driver)?
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --no-variants --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python bench.py --full --no-variants --no-cpu-baseline
     python tools/step_trace.py DIR/*/*_kernel_trace.csv [steps] [warmup]
 
 A step of the lockstep driver starts with ONE k_np_words launch (the generator's head, first kernel of the first wave's
