@@ -233,6 +233,42 @@ int kwy_finish_pcm16_batch_dev(kwy_ctx *ctx, const kwy_finish_job *jobs, int cou
 /* bytes of the context's scratch arena one waveform of that length needs in the call above (kwy_ctx_reserve) */
 int64_t kwy_finish_scratch_bytes(int64_t y_length);
 
+/* ---- f0 conversion ---------------------------------------------------------------- */
+/* The reference synthesises a converted voice on the source's own f0 track (kwiiyatta/convert_voice.py:35-46); its
+ * dialog transposes the key with feature.f0 = feature.f0 * (2.0 ** (transposeKey / 12))
+ * (kwiiyatta/view/qt/kwiieiya.py:152-155).  These entries add the log-Gaussian normalised f0 transform
+ *   log f0' = (log f0 - mu_src) * sigma_tgt / sigma_src + mu_tgt            on voiced frames (f0 > 0)
+ * and the key ratio on top of it.  Moments are (n, mean, M2) of log f0 over the voiced frames of a track, M2 the
+ * sum of squared deviations from the mean; an all-unvoiced track gives (0, 0, 0).  Every reduction has a fixed order:
+ * a track's triple does not depend on the run nor on the other tracks of the call.  The _dev forms allocate nothing
+ * and do not synchronise (legal inside a stream capture); the host forms stage through HBM and synchronise. */
+typedef struct kwy_f0_track {
+  const double *f0;     /* length values */
+  int64_t length;
+} kwy_f0_track;
+/* moments: count x 3 doubles, written */
+int kwy_logf0_moments(kwy_ctx *ctx, const kwy_f0_track *tracks, int count, double *moments);
+int kwy_logf0_moments_batch_dev(kwy_ctx *ctx, const kwy_f0_track *tracks, int count, double *moments);
+/* count triples -> one (Chan's pairwise combination, a left fold in index order): the statistics of a corpus,
+ * bit-equal however its tracks were grouped into calls */
+int kwy_logf0_moments_merge(kwy_ctx *ctx, const double *moments, int count, double *out);
+int kwy_logf0_moments_merge_dev(kwy_ctx *ctx, const double *moments, int count, double *out);
+/* f0_out[i] = exp((log f0 - stats[0]) * stats[3] / stats[1] + stats[2]) * ratio on voiced frames, 0 stays 0.
+ * stats: (mu_src, sigma_src, mu_tgt, sigma_tgt) -- device memory in the _dev form -- or NULL: f0 * ratio on every
+ * frame (the dialog's product, bit for bit).  ratio = 2 ** (key / 12), formed by the caller.  f0_out may equal f0_in.
+ * status: count int32 (or NULL), each set to the number of the track's frames whose input is negative or not finite
+ * or whose output is >= fs / 8: the synthesis plan holds y_length / 8 + 16 pulses (kwy_synth_plan_bytes), which a
+ * track below fs / 8 always fits. */
+typedef struct kwy_f0_map_job {
+  const double *f0_in;  /* length values */
+  int64_t length;
+  double *f0_out;       /* length values, written */
+} kwy_f0_map_job;
+int kwy_f0_map(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, const double *stats, double ratio,
+               int32_t *status);
+int kwy_f0_map_batch_dev(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, const double *stats,
+                         double ratio, int32_t *status);
+
 /* ---- mel-cepstrum ---------------------------------------------------------------- */
 /* pysptk.sp2mc(spec, order, alpha) row-wise          kwiiyatta/vocoder/mcep.py:71
  * sp: T x K (K = fftlen/2+1), mc: T x (order+1). */

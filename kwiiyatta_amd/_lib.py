@@ -91,6 +91,12 @@ SIGNATURES = {
     'kwy_stonemask_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int]),
     'kwy_finish_pcm16_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_dbl, c_int, c_dbl]),
     'kwy_finish_scratch_bytes': (c_i64, [c_i64]),
+    'kwy_logf0_moments': (c_int, [c_vp, c_vp, c_int, c_vp]),
+    'kwy_logf0_moments_batch_dev': (c_int, [c_vp, c_vp, c_int, c_vp]),
+    'kwy_logf0_moments_merge': (c_int, [c_vp, c_vp, c_int, c_vp]),
+    'kwy_logf0_moments_merge_dev': (c_int, [c_vp, c_vp, c_int, c_vp]),
+    'kwy_f0_map': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_dbl, c_vp]),
+    'kwy_f0_map_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_dbl, c_vp]),
     'kwy_synthesize': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl, c_i64,
                                c_vp]),
     'kwy_synthesize_dev': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl,
@@ -240,6 +246,9 @@ MlsaJob = _job_struct('MlsaJob', 'kwy_mlsa_job: one signal through the MLSA filt
                       [('x', c_vp), ('x_length', c_i64), ('mc', c_vp), ('T', c_i64), ('y', c_vp)])
 FinishJob = _job_struct('FinishJob', 'kwy_finish_job: post-step + 16-bit PCM of one synthesised waveform',
                         [('y', c_vp), ('y_length', c_i64), ('frame_len', c_i64), ('pcm', c_vp)])
+F0Track = _job_struct('F0Track', 'kwy_f0_track: one f0 track of a log-f0 moments call', [('f0', c_vp), ('length', c_i64)])
+F0MapJob = _job_struct('F0MapJob', 'kwy_f0_map_job: one f0 track through the f0 map',
+                       [('f0_in', c_vp), ('length', c_i64), ('f0_out', c_vp)])
 SynthPlanJob = _job_struct('SynthPlanJob', 'kwy_synth_plan_job: the pulse placement of one utterance',
                            [('f0', c_vp), ('f0_length', c_i64), ('y_length', c_i64), ('plan', c_vp)])
 

@@ -25,6 +25,22 @@ CONVERTER_OPTIONS = (
 )
 
 
+def transpose_key(text):
+    """--transpose-key: semitones, within the reference dialog's spin box range (view/qt/ui/kwiieiya.ui:262-280)"""
+    try:
+        key = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid semitone value: {text!r}') from None
+    if not -99.99 <= key <= 99.99:
+        raise argparse.ArgumentTypeError(f'{text} semitones is outside [-99.99, 99.99]')
+    return key
+
+
+TRANSPOSE_KEY_OPTION = ('--transpose-key', dict(type=transpose_key, default=0.0, metavar='SEMITONES',
+                                                help='Transpose the synthesised voice by this many semitones '
+                                                     '(f0 * 2 ** (SEMITONES / 12); [-99.99, 99.99])'))
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -41,6 +57,9 @@ class Config:
 
     def add_converter_arguments(self):
         self._declare(CONVERTER_OPTIONS)
+
+    def add_transpose_key_argument(self):
+        self._declare((TRANSPOSE_KEY_OPTION,))
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)
@@ -77,18 +96,27 @@ class Config:
         sides = [k.WavFileDataset(path, Analyzer=analyze) for path in (self.source_path, self.target_path)]
         return k.align(*sides)
 
-    def train_converter(self, **kwargs):
+    def train_converter(self, f0_stats=False, **kwargs):
+        """f0_stats=True: training also computes the f0 statistics (and the model file keeps them); a loaded model
+        without them is a parser error"""
         converter = self.create_converter(**kwargs)
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
-            return converter.load(model)
-        converter = self._train(converter)
+            converter.load(model)
+            if f0_stats and converter.f0_stats is None:
+                self.parser.error(f'{model}: the converter model has no f0 statistics; retrain it with '
+                                  f'--convert-f0 (a new --converter-model file)')
+            return converter
+        converter = self._train(converter, f0_stats=f0_stats)
         if model is not None:
             converter.save(model)
         return converter
 
-    def _train(self, converter):
+    def _train(self, converter, f0_stats=False):
         dataset = self.load_dataset()
         keys = sorted(dataset.keys())[slice(self.skip_files, None)]
-        converter.train(dataset, keys[:self.max_files])
+        if f0_stats:
+            converter.train(dataset, keys[:self.max_files], f0_stats=True)
+        else:
+            converter.train(dataset, keys[:self.max_files])
         return converter

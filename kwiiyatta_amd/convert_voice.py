@@ -4,14 +4,21 @@ for every input <name>.wav a <name>.diff.wav (the input waveform through the dif
 <name>.synth.wav (WORLD synthesis from the converted mel-cepstrum).  Additions: `--no-diffvc` skips the first;
 `--converter-model FILE` keeps the trained converter between runs; `--batch` renders the .synth.wav outputs of all
 input files -- and the .diff.wav outputs -- through the HBM-resident batch path (kwiiyatta_amd.corpus.convert_batch:
-waves of 16 files in lockstep, wav in -> 16-bit PCM out on the device) instead of file by file."""
+waves of 16 files in lockstep, wav in -> 16-bit PCM out on the device) instead of file by file; `--convert-f0`
+synthesises the .synth.wav outputs on the source f0 mapped to the target speaker's voiced log-f0 statistics (trained
+with the converter and kept in its model file), `--transpose-key` transposes them by so many semitones.  The .diff.wav
+output keeps the source's pitch whatever the options: the MLSA filter runs on the input waveform itself."""
 import pathlib
+
+import numpy as np
 
 OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
-def convert(conf, converter, src_path, diffvc=True):
-    """one converted waveform.  The file is analysed afresh per call, as the reference does."""
+def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0):
+    """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
+    transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
+    input waveform filtered, its pitch stays the source's)"""
     import kwiiyatta_amd as k
     source = conf.create_analyzer(src_path, Analyzer=k.analyze_wav)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc)
@@ -19,6 +26,11 @@ def convert(conf, converter, src_path, diffvc=True):
         return k.apply_mlsa_filter(source, converted)
     rendered = k.feature(source)
     rendered.mel_cepstrum = converted                   # takes over from the analysed envelope
+    if convert_f0 or transpose_key != 0:
+        from .backend import f0 as f0map
+        stats = converter.f0_stats if convert_f0 else None          # (converter.convert_f0 without the statistics)
+        rendered.f0 = f0map.map_f0(np.ascontiguousarray(source.f0, dtype=np.float64), rendered.fs, stats=stats,
+                                   key=transpose_key)
     return rendered.synthesize()
 
 
@@ -34,13 +46,14 @@ class _Pcm16:
         wavfile.write(wav, self.fs, self.pcm)
 
 
-def convert_synth_batch(conf, converter, paths, diffvc=False):
+def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: f0 (DIO +
     StoneMask), analysis, conversion, synthesis / the MLSA filter of the differential conversion, the post-step of
     `synthesize` and `save`'s normalisation and 16-bit truncation all run on the GPU
-    (corpus.convert_batch(pcm=True, diff=...)); the host reads the wav files and writes 2 bytes per sample."""
+    (corpus.convert_batch(pcm=True, diff=...)); the host reads the wav files and writes 2 bytes per sample.
+    convert_f0 / transpose_key: the .synth.wav outputs on the mapped f0 (as `convert` does), mapped on the device."""
     import kwiiyatta_amd as k
     from . import corpus
     from .converter.delta import DeltaFeatureConverter
@@ -50,14 +63,16 @@ def convert_synth_batch(conf, converter, paths, diffvc=False):
         a = conf.create_analyzer(path, Analyzer=k.analyze_wav)
         if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or \
                 (period is not None and a.frame_period != period):
-            out[path, False] = convert(conf, converter, path, diffvc=False)
+            out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
+                                       transpose_key=transpose_key)
         else:
             batch.append((path, a))
     if batch:
         fs = batch[0][1].fs
         waves = [a.wavdata.data for _, a in batch]
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
-                                   frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc)
+                                   frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
+                                   f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key)
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -80,11 +95,16 @@ def main():
     conf.add_argument('--no-diffvc', action='store_true', help='Write only the .synth.wav outputs')
     conf.add_argument('--batch', action='store_true',
                       help='Render the outputs of all files through the GPU-resident batch path')
+    conf.add_argument('--convert-f0', action='store_true',
+                      help='Map the f0 of the .synth.wav outputs to the target speaker (log-f0 mean and deviation of '
+                           'the training data, kept in the converter model)')
+    conf.add_transpose_key_argument()
     conf.add_converter_arguments()
     conf.parse_args()
-    converter = conf.train_converter(use_delta=True)
+    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0)
+    pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
-                                  diffvc=not conf.no_diffvc) if conf.batch else {}
+                                  diffvc=not conf.no_diffvc, **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -97,7 +117,7 @@ def main():
             if (wav_path, differential) in batched:
                 batched[wav_path, differential].save(out)
             else:
-                convert(conf, converter, wav_path, diffvc=differential).save(out)
+                convert(conf, converter, wav_path, diffvc=differential, **({} if differential else pitch)).save(out)
 
 
 if __name__ == '__main__':

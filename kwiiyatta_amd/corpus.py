@@ -444,9 +444,13 @@ class ConvertWave:
     `pcm[i]` int16 views, 2 bytes per sample to download.  diff=True (with a GMM): also the DIFFERENTIAL output of
     every file -- the input waveform through the MLSA filter of the differential conversion, convert(diffvc=True),
     /root/reference/kwiiyatta/convert_voice.py:19,39-40, filter/mlsa.py:9-30 -- as `wave_diff[i]` (and `pcm_diff[i]`:
-    Wavdata.save's normalisation only, a filtered waveform has no synthesis post-step)."""
+    Wavdata.save's normalisation only, a filtered waveform has no synthesis post-step).  f0_stats (mu_src, sigma_src,
+    mu_tgt, sigma_tgt: a 4-tuple or 4 doubles on the device) and / or transpose_key != 0: the synthesis runs on the
+    analysed f0 mapped by kwy_f0_map_batch_dev (into `f0_synth`; CheapTrick and D4C keep the analysed track), and
+    `f0_map_status` holds a word per utterance (non-zero: frames out of range, backend.f0.map_f0's limit)."""
 
-    def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False):
+    def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
+                 f0_stats=None, transpose_key=0.0):
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
         self.diff = bool(diff) and gmm is not None
         self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
@@ -494,6 +498,15 @@ class ConvertWave:
                 self.j_fin = _lib.job_array(_lib.FinishJob, [(self.wave[i], self.ylen[i], self.T[i], self.pcm[i])
                                                              for i in range(n)])
             self.plan = [torch.empty(int(lib.kwy_synth_plan_bytes(y)), dtype=torch.uint8, device=dev) for y in self.ylen]
+            self.f0_synth, self.f0_map_status = self.f0, None
+            self.transpose_key = float(transpose_key)
+            if f0_stats is not None or self.transpose_key != 0:
+                self.f0_stats = None if f0_stats is None else torch.as_tensor(
+                    f0_stats if torch.is_tensor(f0_stats) else list(f0_stats), dtype=torch.float64, device=dev)
+                self.f0_synth_all = torch.empty(self.rows, **f64)
+                self.f0_synth = [cut(self.f0_synth_all, off, i) for i in range(n)]
+                self.f0_map_status = torch.zeros(n, dtype=torch.int32, device=dev)
+                self.j_map = _lib.job_array(_lib.F0MapJob, [(self.f0[i], self.T[i], self.f0_synth[i]) for i in range(n)])
             if gmm is not None:
                 assert gmm.D2 == 6 * order
                 self.mc = torch.empty((self.rows, order + 1), **f64)
@@ -501,7 +514,8 @@ class ConvertWave:
             ap = [cut(self.ap_all, off, i) for i in range(n)]
             self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], sp[i]) for i in range(n)])
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], ap[i]) for i in range(n)])
-            self.j_plan = _lib.job_array(_lib.SynthPlanJob, [(self.f0[i], self.T[i], self.ylen[i], self.plan[i]) for i in range(n)])
+            self.j_plan = _lib.job_array(_lib.SynthPlanJob, [(self.f0_synth[i], self.T[i], self.ylen[i], self.plan[i])
+                                                             for i in range(n)])
             if gmm is not None:
                 self.mc_conv = torch.empty((self.rows, order + 1), **f64)
                 self.sp_conv = torch.empty((self.rows, K), **f64)
@@ -540,6 +554,11 @@ class ConvertWave:
         with torch.cuda.stream(ls.side):
             hs = ls.side_ctx.handle
             _lib.check(ls.side_ctx, lib.kwy_d4c_batch_dev(hs, self.j_ap, n, fs, 0.85, fft))
+            if self.f0_map_status is not None:
+                from .backend.f0 import key_ratio
+                _lib.check(ls.side_ctx, lib.kwy_f0_map_batch_dev(
+                    hs, self.j_map, n, fs, None if self.f0_stats is None else self.f0_stats.data_ptr(),
+                    key_ratio(self.transpose_key), self.f0_map_status.data_ptr()))
             _lib.check(ls.side_ctx, lib.kwy_synth_plan_batch_dev(hs, self.j_plan, n, fft, self.frame_period, fs))
         with torch.cuda.stream(ls.main):
             h = ls.ctx.handle
@@ -580,14 +599,16 @@ class ConvertWave:
                                                            PIECE_CEILING))
 
 
-def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False):
+def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
+                    f0_stats=None, transpose_key=0.0):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view[, pcm view]) on the main stream.
-    Bare waveforms get their f0 on the device; the DIO status words of all waves are read back ONCE at the end."""
+    Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map) are read
+    back ONCE at the end."""
     ls = ls if ls is not None else _Lockstep(device_index)
-    held, status, waves_diff = [], [], []
+    held, status, map_status, waves_diff = [], [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
-                         diff=diff, defer_mlsa=diff)
+                         diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key)
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -599,6 +620,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
                     keep(w0 + i, wv.wave[i])
         if wv.f0_status is not None:
             status.append(wv.f0_status)
+        if wv.f0_map_status is not None:
+            map_status.append(wv.f0_map_status)
         if diff:
             waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
         held.append(wv)
@@ -621,9 +644,14 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             for wv in waves_diff:
                 wv.finish_diff(ls.ctx)
     ls.sync()
-    if status and bool(torch.cat(status).any().item()):
-        bad = torch.nonzero(torch.cat(status)).flatten().tolist()
+    words = torch.cat(status + map_status).cpu() if status or map_status else None
+    n_dio = sum(v.numel() for v in status)
+    if status and bool(words[:n_dio].any()):
+        bad = torch.nonzero(words[:n_dio]).flatten().tolist()
         raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
+    if map_status:
+        from .backend.f0 import check_status
+        check_status(words[n_dio:], fs)
     return ls
 
 
@@ -745,20 +773,51 @@ class _upload_ahead:
 
 def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
                           silence_for=None, pool=None, rng=None, pairs_before=0, driver=None, lockstep=None,
-                          wave_pairs=16):
+                          wave_pairs=16, f0_moments=False):
     """driver='lockstep' (default): waves of `wave_pairs` pairs through the batched entries on two streams
     (`TrainWave`; `lockstep`: a _Lockstep to reuse), rows appended behind a device-side cursor, one read-back per wave;
-    driver='streams': round 3's pair-per-stream driver (`TrainPair`, below).  Same matrix either way."""
+    driver='streams': round 3's pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
+    f0_moments=True: a third result, the (2, 3) numpy array of the merged voiced log-f0 moments (n, mean, M2) of the
+    source and of the target side -- each side's trimmed f0 tracks, merged in pair order on the device
+    (MelCepstrumFeatureConverter.train(f0_stats=True)'s statistics; backend.f0.stats_from_moments)."""
     driver = driver or ('streams' if pool is not None else 'lockstep')
+    moments = _PairMoments(len(pairs), device_index) if f0_moments else None
     if driver == 'lockstep':
-        return _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng,
-                                               pairs_before, lockstep, wave_pairs)
-    return _build_training_matrix_streams(pairs, fs, device_index, order, radius, frame_period, streams, silence_for,
-                                          pool, rng, pairs_before)
+        out = _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng,
+                                              pairs_before, lockstep, wave_pairs, moments)
+    else:
+        out = _build_training_matrix_streams(pairs, fs, device_index, order, radius, frame_period, streams, silence_for,
+                                             pool, rng, pairs_before, moments)
+    return out if moments is None else out + (moments.merged(),)
+
+
+class _PairMoments:
+    """per-track voiced log-f0 moments of a corpus's pairs in HBM: row 2 i the source, 2 i + 1 the target of pair i"""
+
+    def __init__(self, n_pairs, device_index):
+        self.dev = torch.device('cuda', device_index)
+        self.rows = torch.empty((2 * n_pairs, 3), dtype=torch.float64, device=self.dev)     # every row is written
+
+    def add(self, ctx, first_pair, tracks):
+        """enqueue (on ctx's stream) the moments of `tracks`: the trimmed source and target f0 of consecutive pairs"""
+        from .backend import f0 as f0map
+        f0map.logf0_moments_batch_dev(ctx, tracks, self.rows[2 * first_pair:2 * first_pair + len(tracks)])
+
+    def merged(self):
+        """(after the streams that ran `add` are synchronised) the merged (source, target) triples"""
+        if len(self.rows) == 0:
+            return np.zeros((2, 3))
+        from .backend import f0 as f0map
+        ctx = _lib.Context(self.dev.index, stream=torch.cuda.current_stream(self.dev).cuda_stream)
+        with torch.cuda.device(self.dev):
+            out = torch.empty((2, 3), dtype=torch.float64, device=self.dev)
+            for side in (0, 1):
+                f0map.merge_moments_dev(ctx, self.rows[side::2].contiguous(), out[side])
+            return out.cpu().numpy()
 
 
 def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng, pairs_before,
-                                    ls, wave_pairs):
+                                    ls, wave_pairs, moments=None):
     dev = torch.device('cuda', device_index)
     ls = ls if ls is not None else _Lockstep(device_index)
     K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
@@ -799,22 +858,24 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
         prev, held = None, []
         worst = torch.zeros(1, dtype=torch.int64, device=dev)      # min over all pairs' n_rows: < 0 = a pair was dropped
 
-        def close(wave):
+        def close(wave, first_pair):
             wave.finish(X, cursor, pads)
             with torch.cuda.stream(ls.main):
                 torch.minimum(worst, wave.n_rows.min().reshape(1), out=worst)
+                if moments is not None:
+                    moments.add(ls.ctx, first_pair, [f[:k] for f, k in zip(wave.f0, wave.keep)])
         for w0 in range(0, len(pairs), wave_pairs):
             chunk = [uploads.get() for _ in range(len(pairs[w0:w0 + wave_pairs]))]
             wave = TrainWave(ls, fs, chunk, order=order, radius=radius, frame_period=frame_period)
             wave.analyse()                     # enqueued BEFORE the host waits for the previous wave's lengths
             if prev is not None:
-                close(prev)
+                close(prev, w0 - wave_pairs)
                 held.append(prev)
             frames += wave.frames
             prev = wave
             while len(held) > 2:
                 held.pop(0)                    # (its buffers: all uses are ordered on the main stream before reuse)
-        close(prev)
+        close(prev, (len(pairs) - 1) // wave_pairs * wave_pairs)
         with torch.cuda.stream(ls.main):
             n_rows, dropped = (int(v) for v in torch.cat((cursor, worst)).tolist())     # ONE read-back
         ls.sync()
@@ -832,7 +893,7 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
 
 
 def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
-                                   silence_for=None, pool=None, rng=None, pairs_before=0):
+                                   silence_for=None, pool=None, rng=None, pairs_before=0, moments=None):
     """pairs: list of ((x, f0, t), (x, f0, t)) numpy triples of THIS rank, in corpus order.  Returns the
     (n, 2*3*order) float64 device tensor of make_dataset_to_array and the number of source frames analysed.
     Pairs are processed `streams` at a time, each on its own stream (`pool`: a StreamPool to use instead of a new one).
@@ -857,11 +918,14 @@ def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=3
     uploads = _upload_ahead(pairs, dev, 2 * len(pool)) if pairs else None
     blocks, frames = [], 0
 
-    def finish(wave):
+    def finish(wave, first_pair):
         """the host-dependent half of a wave: trim lengths back, alignment and row extraction enqueued, rows collected"""
         nonlocal frames
-        for p in wave:
+        for k, p in enumerate(wave):
             p.align()
+            if moments is not None:
+                with torch.cuda.stream(p.stream):
+                    moments.add(p.ctx, first_pair + k, [p.src.f0[:p.src.n], p.tgt.f0[:p.tgt.n]])
         for p in wave:
             blocks.append(p.rows().clone())  # enqueued on the default stream after rows() has synchronised
             frames += p.frames
@@ -892,10 +956,10 @@ def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=3
             for p in wave:
                 p.analyse()
             if prev is not None:
-                finish(prev)
+                finish(prev, w0 - len(pool))
             prev = wave
         if prev is not None:
-            finish(prev)
+            finish(prev, (len(pairs) - 1) // len(pool) * len(pool))
         torch.cuda.synchronize(dev)
     finally:
         if ahead is not None:
@@ -951,14 +1015,16 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
 
 
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
-                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False):
+                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
     diff=True appends the differential outputs (the inputs through the MLSA filter of the differential conversion,
     convert_voice.py's .diff.wav): (waveforms, pcm or None, diff waveforms, diff pcm or None).
     driver='lockstep' (default): waves of 16 utterances through the batched entries on two streams (`ConvertWave`);
-    'streams': round 3's utterance-per-stream driver, see `_stream_batch` for its scheduling."""
+    'streams': round 3's utterance-per-stream driver, see `_stream_batch` for its scheduling.
+    f0_stats / transpose_key (lockstep driver): the waveforms are synthesised on the mapped f0 (ConvertWave); a frame
+    out of the map's range raises ValueError after the batch."""
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
@@ -968,12 +1034,15 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
 
         def keep_view(i, w, p=None, wd=None, pd=None):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
-        _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff)
+        _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
+                        f0_stats=f0_stats, transpose_key=transpose_key)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
     if pcm or diff or (len(utterances) and not isinstance(utterances[0], (tuple, list))):
         raise ValueError('convert_batch: wav-in utterances and pcm=True need the lockstep driver')
+    if f0_stats is not None or transpose_key != 0:
+        raise ValueError('convert_batch: f0_stats and transpose_key need the lockstep driver')
     if pool is None:
         pool = StreamPool(device_index, streams)
 

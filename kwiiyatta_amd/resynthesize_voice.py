@@ -2,7 +2,9 @@
 sampling rate (--result-fs), or on the timing and f0 of a second recording (--carrier; with --diffvc the carrier's
 own waveform is filtered towards the source's spectrum instead of being re-synthesised).  Command line of the
 reference's kwiiyatta/resynthesize_voice.py; its Qt dialog (started when no source file is given) is not part of
-this build."""
+this build, but its key transposition is: --transpose-key SEMITONES multiplies the f0 by 2 ** (SEMITONES / 12)
+after the carrier and --mcep steps (kwiiyatta/view/qt/kwiieiya.py:152-155).  --diffvc returns before that step in
+the dialog, so the two together are refused."""
 import copy
 import pathlib
 
@@ -23,6 +25,11 @@ def render(conf, source):
     if conf.mcep:
         picture.extract_mel_cepstrum()
         picture.spectrum_envelope = None                 # from here on the mel-cepstrum is the envelope
+    if conf.transpose_key != 0:
+        import numpy as np
+        from .backend import f0 as f0map
+        fs = conf.result_fs if conf.result_fs is not None else picture.fs
+        picture.f0 = f0map.map_f0(np.ascontiguousarray(picture.f0, dtype=np.float64), fs, key=conf.transpose_key)
     if conf.result_fs is not None:
         picture.resample(conf.result_fs)
     return picture.synthesize()
@@ -39,9 +46,13 @@ def main():
     conf.add_argument('--carrier', type=str, help='Wav file to use for carrier')
     conf.add_argument('--diffvc', action='store_true', help='Use difference MelCepstrum synthesis')
     conf.add_argument('--result-fs', type=int, help='Result waveform sampling rate')
+    conf.add_transpose_key_argument()
     conf.parse_args()
     if conf.source is None:
         conf.parser.error('a source wav file is required (the Qt dialog of the reference is not part of this build)')
+    if conf.diffvc and conf.transpose_key != 0:
+        conf.parser.error('--transpose-key cannot be combined with --diffvc (the carrier waveform is filtered, not '
+                          're-synthesised: its pitch stays)')
     source_path = pathlib.Path(conf.source).resolve()
     wav = render(conf, conf.create_analyzer(source_path, Analyzer=k.analyze_wav))
     if not conf.no_save:
