@@ -5,6 +5,8 @@ restatement of the same chain, and against scikit-learn for the fit."""
 import numpy as np
 import pytest
 
+from d4c_cases import AP_ABS
+
 pytestmark = pytest.mark.gpu
 
 FS = 16000
@@ -81,8 +83,9 @@ def test_training_matrix_stages_vs_oracle(corpus):
         f0_pad = np.r_[np.zeros(P), f0[:n], np.zeros(P)]
         voiced = (f0_pad >= FS / ((513 - 1) / 2) + 1.0) & (ap_pad[:, 0] <= 0.999)
         got_v = side.voiced.cpu().numpy()[:n + 2 * P] > 0
-        # D4C differs by <= 1e-4 between oracle and GPU: a frame sitting on the 0.999 edge may flip
-        assert (got_v != voiced).sum() <= 2
+        # the HIP D4C is within AP_ABS of the oracle: only a frame that sits on the 0.999 edge may flip
+        flips = np.flatnonzero(got_v != voiced)
+        assert len(flips) <= 2 and (np.abs(ap_pad[flips, 0] - 0.999) <= AP_ABS).all(), flips
         mc = ko.sp2mc(sp_pad, ORDER, alpha)
         mc_g = side.mc_pad.cpu().numpy()
         assert np.abs(mc_g - mc).max() <= 1e-9 * np.abs(mc).max()

@@ -3,12 +3,15 @@
 CPU half: the oracle still reproduces them (guards the checker against drift; tolerance 1e-9
 relative because libm picks CPU-specific exp/log/cos kernels).  GPU half: the HIP kernels, through
 the C ABI, reproduce them on a box that has neither the reference nor its third-party stack; same
-tolerances as tests/test_world_gpu.py and tests/test_backends_gpu.py.
+tolerances as tests/test_world_gpu.py and tests/test_backends_gpu.py (aperiodicity: the CPU half's 1e-7 plus
+d4c_cases.AP_ABS, the HIP kernels' distance from the oracle).
 """
 import os
 
 import numpy as np
 import pytest
+
+from d4c_cases import AP_ABS
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'golden.npz'))
 FS = int(G['fs'])
@@ -85,8 +88,9 @@ def test_hip_world_vectors():
     sp, ap = kw.cheaptrick(x, G['f0'], t, FS), kw.d4c(x, G['f0'], t, FS)
     spectrum_close(sp[fr], G['sp_rows'])
     assert np.abs(sp.sum(axis=1) - G['sp_sum']).max() <= 1e-8 * G['sp_sum'].max()
-    assert np.abs(ap[fr] - G['ap_rows']).max() <= 1e-4
-    assert np.abs(ap.mean(axis=1) - G['ap_mean']).max() <= 1e-5
+    # within AP_ABS of the oracle, which test_oracle_world_vectors holds within 1e-7 of the file
+    assert np.abs(ap[fr] - G['ap_rows']).max() <= 1e-7 + AP_ABS
+    assert np.abs(ap.mean(axis=1) - G['ap_mean']).max() <= 1e-7 + AP_ABS
     y = kw.synthesize(G['f0'], sp, ap, FS, 5.0)
     assert y.shape == G['y'].shape
     assert np.sqrt(np.mean((y - G['y']) ** 2)) <= 1e-4      # the north-star criterion
