@@ -105,7 +105,7 @@ def dio(x, fs, f0_floor=default_f0_floor, f0_ceil=default_f0_ceil, channels_in_o
         frame_period=default_frame_period, speed=1, allowed_range=0.1, ctx=None):
     x = _lib.as_f64(x)
     ctx = ctx or _lib.default_context()
-    T = lib.kwy_dio_frames(int(fs), len(x), float(frame_period))
+    T = dio_frames(fs, len(x), frame_period)
     f0 = np.empty(T)
     t = np.empty(T)
     _lib.check(ctx, lib.kwy_dio(ctx.handle, ptr(x), len(x), int(fs), float(f0_floor), float(f0_ceil),
@@ -129,6 +129,8 @@ def stonemask(x, f0, temporal_positions, fs, ctx=None):
 
 # ---- the f0 track of a batch of utterances without the host (device tensors; round 5) -------------------------------
 def dio_frames(fs, x_length, frame_period=default_frame_period):
+    if not (int(fs) > 0 and float(frame_period) > 0):      # (the frame count of a period <= 0 is no number)
+        raise ValueError('dio: bad argument')
     return int(lib.kwy_dio_frames(int(fs), int(x_length), float(frame_period)))
 
 

@@ -61,7 +61,7 @@ struct dio_utt {
 struct dio_plan {
   int count, nbands;
   int ny_max, T_max, ntiles_max, cap_max;   // layout extents (ntiles_max: filter blocks of the longest utterance)
-  int cap_block;                            // edges one filter block may leave per engine
+  int cap_block;                            // edges one filter block may leave per engine: the most it can find
   int half, V;                              // Lh + 2 max_hal (the longest combined filter is 2 half taps); outputs per block
   double fs, f0_floor, f0_ceil, frame_period, allowed_range;
   double boundary[DIO_MAX_BANDS];
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(DIO_NT, 4) void k_dio_filter(dio_plan P, const kwy_
       }
       zc[wv][2 * lane] = inc - v0 - v1;
       zc[wv][2 * lane + 1] = inc - v1;
-      if (lane == 63) cnt[(4 * b + wv) * P.ntiles_max + blockIdx.x] = min(inc, P.cap_block);
+      if (lane == 63) cnt[(4 * b + wv) * P.ntiles_max + blockIdx.x] = inc;        // <= cap_block = (V + 1) / 2
     }
     __syncthreads();
     double *lists = P.at<double>(utt, P.off_lists);
@@ -224,12 +224,8 @@ __global__ __launch_bounds__(DIO_NT, 4) void k_dio_filter(dio_plan P, const kwy_
         const unsigned long long m = __ballot(e[kind]);
         if (e[kind]) {
           const int at = zc[kind][j * (NT / 64) + wv] + __popcll(m & below);
-          if (at < P.cap_block) {
-            const double a = dio_sig(fl, kind, li), c = dio_sig(fl, kind, li + 1);
-            lists[((int64_t)(4 * b + kind) * P.ntiles_max + blockIdx.x) * P.cap_block + at] = (i0 + li + 1) - a / (c - a);
-          } else {
-            atomicExch(P.u[utt].status, 1);
-          }
+          const double a = dio_sig(fl, kind, li), c = dio_sig(fl, kind, li + 1);     // (at < cap_block: no two edges adjacent)
+          lists[((int64_t)(4 * b + kind) * P.ntiles_max + blockIdx.x) * P.cap_block + at] = (i0 + li + 1) - a / (c - a);
         }
       }
     }
@@ -779,7 +775,10 @@ static int dio_prepare(kwy_ctx *ctx, int fs, double f0_floor, double f0_ceil, do
   p.ny_max = (int)n_max + 1;
   p.T_max = (int)kwy_dio_frames(fs, n_max, frame_period_ms);
   p.ntiles_max = (p.ny_max + p.V - 1) / p.V;
-  p.cap_block = p.V / 8 + 64;
+  // An engine's edges are negative-going crossings between neighbouring samples, so no two of them are adjacent and
+  // a block holds at most (V + 1) / 2: the lists take whatever a block finds (112 bytes per sample of the longest
+  // utterance at 7 bands).  Only the cap per utterance, (n + 1) / 8 + 64, can set the status word: see ADVICE.md.
+  p.cap_block = (p.V + 1) / 2;
   p.cap_max = p.ny_max / 8 + 64;
   p.scratch = nullptr;
   *block = dio_layout(p);

@@ -4,13 +4,16 @@ f0 front-end (DIO, StoneMask).
 
 Tolerances: mel-cepstrum 1e-12 relative (same algorithm, different summation
 order); FastDTW path and distance bit-exact (integer path, identical distance
-arithmetic); MLPG 1e-10 relative; DIO f0 1e-8 Hz with identical voicing
-decisions (direct FIR instead of FFT filtering); StoneMask 1e-10 relative."""
+arithmetic); MLPG 1e-10 relative; DIO and StoneMask by tests/f0_cases.py
+(identical voicing decisions and F0_ABS in Hz; F0_REL per frame)."""
+import os
+
 import numpy as np
 import pytest
 from scipy.io import wavfile
 
 from conftest import CLB_WAV, SLT_WAV, clb_variant
+from f0_cases import all_frames, assert_f0_close, assert_refined_close
 
 pytestmark = pytest.mark.gpu
 
@@ -272,14 +275,11 @@ def test_gmm_mlpg_errors(clb):
 def test_dio_stonemask(ko, path, frame_period):
     from kwiiyatta_amd.backend import world
     fs, x = load(path)
+    label = f'{os.path.basename(os.path.dirname(os.path.dirname(path)))} {fs} period {frame_period}'
     f0_ref, t_ref = ko.dio(x, fs, frame_period=frame_period)
-    f0_got, t_got = world.dio(x, fs, frame_period=frame_period)
-    assert np.array_equal(t_got, t_ref)
-    assert np.array_equal(f0_got > 0, f0_ref > 0)
-    assert np.abs(f0_got - f0_ref).max() <= 1e-8
+    assert_f0_close(world.dio(x, fs, frame_period=frame_period), (f0_ref, t_ref), all_frames(f0_ref), label)
     s_ref = ko.stonemask(x, f0_ref, t_ref, fs)
-    s_got = world.stonemask(x, f0_ref, t_ref, fs)
-    assert np.abs(s_got - s_ref).max() <= 1e-10 * s_ref.max()
+    assert_refined_close(world.stonemask(x, f0_ref, t_ref, fs), s_ref, label, f0_in=f0_ref)
 
 
 def test_dio_short_and_silent(ko):
@@ -288,13 +288,17 @@ def test_dio_short_and_silent(ko):
     x = np.zeros(3000)
     f0, t = world.dio(x, fs)
     f0r, tr = ko.dio(x, fs)
+    assert_f0_close((f0, t), (f0r, tr), all_frames(f0r), 'silence', f0_abs=0.0)
     assert np.array_equal(f0, f0r) and np.array_equal(t, tr) and not f0.any()
     rng = np.random.default_rng(1)
     x = rng.standard_normal(800) * 0.1      # shorter than the voiced-range minimum
     f0, t = world.dio(x, fs)
     f0r, tr = ko.dio(x, fs)
+    assert_f0_close((f0, t), (f0r, tr), all_frames(f0r), '800 samples of noise', f0_abs=0.0)
     assert np.array_equal(t, tr) and np.array_equal(f0, f0r)
-    assert np.array_equal(world.stonemask(x, f0, t, fs), ko.stonemask(x, f0r, tr, fs))
+    s, sr = world.stonemask(x, f0, t, fs), ko.stonemask(x, f0r, tr, fs)
+    assert_refined_close(s, sr, '800 samples of noise', f0_in=f0r, f0_rel=0.0)
+    assert np.array_equal(s, sr)
 
 
 # ---------------------------------------------------------------- spectral-axis stretch (reshape), SURVEY 8f-3

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import CLB_WAV, CLB_WAV2, SLT_WAV, clb_variant
+from f0_cases import all_frames, assert_f0_close, assert_refined_close
 
 pytestmark = pytest.mark.gpu
 
@@ -60,9 +61,13 @@ def test_f0_batch_equals_host_entries_16k(frame_period):
     assert not status.any()
     for i, x in enumerate(waves):
         f0_h, t_h = world.dio(x, fs, frame_period=frame_period)
+        r_h = world.stonemask(x, f0_h, t_h, fs)
+        assert_f0_close((f0[i], t[i]), (f0_h, t_h), all_frames(f0_h), f'batch 16k member {i} against its host call',
+                        f0_abs=0.0)
+        assert_refined_close(refined[i], r_h, f'batch 16k member {i} against its host call', f0_in=f0_h, f0_rel=0.0)
         assert np.array_equal(t[i], t_h), i
         assert np.array_equal(f0[i], f0_h), i
-        assert np.array_equal(refined[i], world.stonemask(x, f0_h, t_h, fs)), i
+        assert np.array_equal(refined[i], r_h), i
 
 
 @pytest.mark.parametrize('suffix', ['22', '48', '96'])
@@ -76,8 +81,12 @@ def test_f0_batch_equals_host_entries_other_rates(suffix):
     assert not status.any()
     for i, x in enumerate(waves):
         f0_h, t_h = world.dio(x, fs)
+        r_h = world.stonemask(x, f0_h, t_h, fs)
+        assert_f0_close((f0[i], t[i]), (f0_h, t_h), all_frames(f0_h), f'batch {fs} member {i} against its host call',
+                        f0_abs=0.0)
+        assert_refined_close(refined[i], r_h, f'batch {fs} member {i} against its host call', f0_in=f0_h, f0_rel=0.0)
         assert np.array_equal(t[i], t_h) and np.array_equal(f0[i], f0_h), i
-        assert np.array_equal(refined[i], world.stonemask(x, f0_h, t_h, fs)), i
+        assert np.array_equal(refined[i], r_h), i
 
 
 def test_f0_batch_synthetic_48k_vs_oracle():
@@ -92,12 +101,9 @@ def test_f0_batch_synthetic_48k_vs_oracle():
     assert not status.any()
     for i, x in enumerate(waves):
         f0_ref, t_ref = ko.dio(x, fs)
-        assert np.array_equal(t[i], t_ref)
-        assert np.array_equal(f0[i] > 0, f0_ref > 0)
-        assert np.abs(f0[i] - f0_ref).max() <= 1e-8
+        assert_f0_close((f0[i], t[i]), (f0_ref, t_ref), all_frames(f0_ref), f'synthetic 48k member {i}')
         s_ref = ko.stonemask(x, f0[i], t_ref, fs)          # the oracle's refinement of the device's own DIO track
-        assert np.array_equal(refined[i] > 0, s_ref > 0)
-        assert np.abs(refined[i] - s_ref).max() <= 1e-10 * s_ref.max()
+        assert_refined_close(refined[i], s_ref, f'synthetic 48k member {i}', f0_in=f0[i])
 
 
 def test_dio_dev_single_and_status_word():
