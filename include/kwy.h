@@ -269,6 +269,50 @@ int kwy_f0_map(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, cons
 int kwy_f0_map_batch_dev(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, const double *stats,
                          double ratio, int32_t *status);
 
+/* ---- global variance ---------------------------------------------------------------- */
+/* The reference has no counterpart (kwiiyatta/convert_voice.py:35-46 synthesises the converter's output as it is):
+ * these entries add the global-variance postfilter of Toda et al. (2007) for the over-smoothed trajectories of a
+ * GMM / MLPG conversion.  For a row-major (rows, cols) matrix x, per column d >= first_col
+ *   m_d = mean of x[:, d],   v_d = M2_d / rows (variance, ddof 0),   r_d = sqrt(gv_d / v_d)
+ *   out[t, d] = base[t, d] + strength * (r_d - 1) * (x[t, d] - m_d)
+ * evaluated operation by operation as written; columns below first_col are copied from base.  base == x is the plain
+ * filter (variance gv_d at strength 1), base == the differential conversion the differential one.  A column with
+ * v_d == 0 (a constant column, rows <= 1) or strength * (r_d - 1) == 0 is copied from base; so is a column whose v_d
+ * is not finite or whose gv_d is not finite or <= 0, and those are counted in the matrix's status word.
+ * Column moments are (n, mean, M2) per column, cols x 3 doubles per matrix: n = rows, M2 the sum of squared deviations
+ * from the mean, in two passes; a column whose values all equal its first one has that value as its mean and M2 == 0
+ * exactly.  Every reduction has a fixed order: a matrix's moments depend on the matrix alone, not on the run nor on
+ * the other matrices of the call.  cols <= 64.  The _dev forms allocate nothing and do not synchronise (legal inside
+ * a stream capture); the host forms stage through HBM and synchronise. */
+typedef struct kwy_gv_matrix {
+  const double *x;      /* rows x cols values */
+  int64_t rows;
+} kwy_gv_matrix;
+/* moments: count x cols x 3 doubles, written */
+int kwy_column_moments(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols, double *moments);
+int kwy_column_moments_dev(kwy_ctx *ctx, const double *x, int64_t rows, int cols, double *moments);
+int kwy_column_moments_batch_dev(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols, double *moments);
+/* gv[d] = the mean over the matrices with n > 0 of M2 / n (a left fold in index order, then one division): the
+ * statistic of a corpus, bit-equal however its matrices were grouped into calls; 0 when no matrix has rows.
+ * moments: count x cols x 3; gv: cols doubles, written */
+int kwy_gv_from_moments(kwy_ctx *ctx, const double *moments, int count, int cols, double *gv);
+int kwy_gv_from_moments_dev(kwy_ctx *ctx, const double *moments, int count, int cols, double *gv);
+typedef struct kwy_gv_job {
+  const double *x;        /* rows x cols: the matrix the moments were taken from */
+  int64_t rows;
+  const double *moments;  /* cols x 3, of x (the host form computes them itself and ignores this field) */
+  const double *base;     /* rows x cols (may equal x) */
+  double *out;            /* rows x cols, written (may equal base) */
+} kwy_gv_job;
+/* gv: cols doubles -- device memory in the _dev forms; strength in [0, 1]; status: one int32 per matrix (or NULL),
+ * set to the number of columns >= first_col that were copied because v_d or gv_d is unusable */
+int kwy_gv_postfilter(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col, const double *gv,
+                      double strength, int32_t *status);
+int kwy_gv_postfilter_dev(kwy_ctx *ctx, const double *x, int64_t rows, int cols, int first_col, const double *moments,
+                          const double *gv, double strength, const double *base, double *out, int32_t *status);
+int kwy_gv_postfilter_batch_dev(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col,
+                                const double *gv, double strength, int32_t *status);
+
 /* ---- mel-cepstrum ---------------------------------------------------------------- */
 /* pysptk.sp2mc(spec, order, alpha) row-wise          kwiiyatta/vocoder/mcep.py:71
  * sp: T x K (K = fftlen/2+1), mc: T x (order+1). */

@@ -97,6 +97,14 @@ SIGNATURES = {
     'kwy_logf0_moments_merge_dev': (c_int, [c_vp, c_vp, c_int, c_vp]),
     'kwy_f0_map': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_dbl, c_vp]),
     'kwy_f0_map_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_dbl, c_vp]),
+    'kwy_column_moments': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
+    'kwy_column_moments_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
+    'kwy_column_moments_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
+    'kwy_gv_from_moments': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
+    'kwy_gv_from_moments_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
+    'kwy_gv_postfilter': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
+    'kwy_gv_postfilter_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp]),
+    'kwy_gv_postfilter_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
     'kwy_synthesize': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl, c_i64,
                                c_vp]),
     'kwy_synthesize_dev': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl,
@@ -249,6 +257,9 @@ FinishJob = _job_struct('FinishJob', 'kwy_finish_job: post-step + 16-bit PCM of 
 F0Track = _job_struct('F0Track', 'kwy_f0_track: one f0 track of a log-f0 moments call', [('f0', c_vp), ('length', c_i64)])
 F0MapJob = _job_struct('F0MapJob', 'kwy_f0_map_job: one f0 track through the f0 map',
                        [('f0_in', c_vp), ('length', c_i64), ('f0_out', c_vp)])
+GvMatrix = _job_struct('GvMatrix', 'kwy_gv_matrix: one matrix of a column moments call', [('x', c_vp), ('rows', c_i64)])
+GvJob = _job_struct('GvJob', 'kwy_gv_job: one matrix through the global-variance postfilter',
+                    [('x', c_vp), ('rows', c_i64), ('moments', c_vp), ('base', c_vp), ('out', c_vp)])
 SynthPlanJob = _job_struct('SynthPlanJob', 'kwy_synth_plan_job: the pulse placement of one utterance',
                            [('f0', c_vp), ('f0_length', c_i64), ('y_length', c_i64), ('plan', c_vp)])
 

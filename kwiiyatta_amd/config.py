@@ -41,6 +41,23 @@ TRANSPOSE_KEY_OPTION = ('--transpose-key', dict(type=transpose_key, default=0.0,
                                                      '(f0 * 2 ** (SEMITONES / 12); [-99.99, 99.99])'))
 
 
+def gv_strength(text):
+    """--gv: the strength of the global-variance postfilter, within [0, 1]"""
+    try:
+        strength = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid strength: {text!r}') from None
+    if not 0.0 <= strength <= 1.0:
+        raise argparse.ArgumentTypeError(f'{text} is outside [0, 1]')
+    return strength
+
+
+GV_OPTION = ('--gv', dict(type=gv_strength, nargs='?', const=1.0, default=0.0, metavar='STRENGTH',
+                          help='Global-variance postfilter on the converted mel-cepstrum: stretch every trajectory '
+                               'about its mean towards the variance of the target speaker (kept in the converter '
+                               'model); STRENGTH within [0, 1], 1 when omitted'))
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -60,6 +77,9 @@ class Config:
 
     def add_transpose_key_argument(self):
         self._declare((TRANSPOSE_KEY_OPTION,))
+
+    def add_gv_argument(self):
+        self._declare((GV_OPTION,))
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)
@@ -96,9 +116,9 @@ class Config:
         sides = [k.WavFileDataset(path, Analyzer=analyze) for path in (self.source_path, self.target_path)]
         return k.align(*sides)
 
-    def train_converter(self, f0_stats=False, **kwargs):
-        """f0_stats=True: training also computes the f0 statistics (and the model file keeps them); a loaded model
-        without them is a parser error"""
+    def train_converter(self, f0_stats=False, gv_stats=False, **kwargs):
+        """f0_stats=True / gv_stats=True: training also computes the f0 statistics / the target's global variance (and
+        the model file keeps them); a loaded model without them is a parser error"""
         converter = self.create_converter(**kwargs)
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
@@ -106,17 +126,20 @@ class Config:
             if f0_stats and converter.f0_stats is None:
                 self.parser.error(f'{model}: the converter model has no f0 statistics; retrain it with '
                                   f'--convert-f0 (a new --converter-model file)')
+            if gv_stats and converter.gv_stats is None:
+                self.parser.error(f'{model}: the converter model has no global variance statistics; retrain it with '
+                                  f'--gv (a new --converter-model file)')
             return converter
-        converter = self._train(converter, f0_stats=f0_stats)
+        converter = self._train(converter, f0_stats=f0_stats, gv_stats=gv_stats)
         if model is not None:
             converter.save(model)
         return converter
 
-    def _train(self, converter, f0_stats=False):
+    def _train(self, converter, f0_stats=False, gv_stats=False):
         dataset = self.load_dataset()
         keys = sorted(dataset.keys())[slice(self.skip_files, None)]
-        if f0_stats:
-            converter.train(dataset, keys[:self.max_files], f0_stats=True)
-        else:
-            converter.train(dataset, keys[:self.max_files])
+        extra = dict(f0_stats=True) if f0_stats else {}
+        if gv_stats:
+            extra['gv_stats'] = True
+        converter.train(dataset, keys[:self.max_files], **extra)
         return converter

@@ -7,7 +7,11 @@ input files -- and the .diff.wav outputs -- through the HBM-resident batch path 
 waves of 16 files in lockstep, wav in -> 16-bit PCM out on the device) instead of file by file; `--convert-f0`
 synthesises the .synth.wav outputs on the source f0 mapped to the target speaker's voiced log-f0 statistics (trained
 with the converter and kept in its model file), `--transpose-key` transposes them by so many semitones.  The .diff.wav
-output keeps the source's pitch whatever the options: the MLSA filter runs on the input waveform itself."""
+output keeps the source's pitch whatever the options: the MLSA filter runs on the input waveform itself.
+`--gv [STRENGTH]` runs the global-variance postfilter on the converted mel-cepstrum of both outputs: a GMM conversion
+averages, its trajectories vary about 0.6 times as much as the target speaker's and the voice sounds muffled; the
+filter stretches every coefficient's trajectory about its own mean until its variance is the one the target's training
+utterances have (learnt with the converter, kept in its model file), or STRENGTH of the way there."""
 import pathlib
 
 import numpy as np
@@ -15,13 +19,14 @@ import numpy as np
 OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
-def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0):
+def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
-    input waveform filtered, its pitch stays the source's)"""
+    input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
+    global-variance postfilter of that strength (converter.convert(gv=...), either output)"""
     import kwiiyatta_amd as k
     source = conf.create_analyzer(src_path, Analyzer=k.analyze_wav)
-    converted = converter.convert(source.mel_cepstrum, diff=diffvc)
+    converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}))
     if diffvc:
         return k.apply_mlsa_filter(source, converted)
     rendered = k.feature(source)
@@ -46,14 +51,15 @@ class _Pcm16:
         wavfile.write(wav, self.fs, self.pcm)
 
 
-def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0):
+def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: f0 (DIO +
     StoneMask), analysis, conversion, synthesis / the MLSA filter of the differential conversion, the post-step of
     `synthesize` and `save`'s normalisation and 16-bit truncation all run on the GPU
     (corpus.convert_batch(pcm=True, diff=...)); the host reads the wav files and writes 2 bytes per sample.
-    convert_f0 / transpose_key: the .synth.wav outputs on the mapped f0 (as `convert` does), mapped on the device."""
+    convert_f0 / transpose_key: the .synth.wav outputs on the mapped f0 (as `convert` does), mapped on the device.
+    gv > 0: both outputs from the postfiltered mel-cepstra (as `convert` does), filtered on the device."""
     import kwiiyatta_amd as k
     from . import corpus
     from .converter.delta import DeltaFeatureConverter
@@ -64,7 +70,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
         if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or \
                 (period is not None and a.frame_period != period):
             out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
-                                       transpose_key=transpose_key)
+                                       transpose_key=transpose_key, gv=gv)
         else:
             batch.append((path, a))
     if batch:
@@ -72,7 +78,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
         waves = [a.wavdata.data for _, a in batch]
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
                                    frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
-                                   f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key)
+                                   f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key,
+                                   **(dict(gv_stats=converter.gv_stats, gv_strength=gv) if gv > 0 else {}))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -99,12 +106,13 @@ def main():
                       help='Map the f0 of the .synth.wav outputs to the target speaker (log-f0 mean and deviation of '
                            'the training data, kept in the converter model)')
     conf.add_transpose_key_argument()
+    conf.add_gv_argument()
     conf.add_converter_arguments()
     conf.parse_args()
-    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0)
+    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0)
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
-                                  diffvc=not conf.no_diffvc, **pitch) if conf.batch else {}
+                                  diffvc=not conf.no_diffvc, gv=conf.gv, **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -117,7 +125,8 @@ def main():
             if (wav_path, differential) in batched:
                 batched[wav_path, differential].save(out)
             else:
-                convert(conf, converter, wav_path, diffvc=differential, **({} if differential else pitch)).save(out)
+                convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv,
+                        **({} if differential else pitch)).save(out)
 
 
 if __name__ == '__main__':

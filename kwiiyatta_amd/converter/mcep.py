@@ -33,15 +33,19 @@ class MelCepstrumDataset(abc.MapDataset):
         return record.data[:, 1:]
 
 
-def _f0_tracks(dataset, keys):
-    """(source tracks, target tracks) of `keys` in sorted order: the f0 of the frames TrimmedDataset keeps, before
-    alignment (the items of the dataset itself when its chain has no TrimmedDataset)"""
+def _trimmed_stage(dataset):
+    """the TrimmedDataset of the dataset's chain (the dataset itself when its chain has none)"""
     from .dataset import TrimmedDataset
     stage = dataset
     while not isinstance(stage, TrimmedDataset) and isinstance(stage, abc.MapDataset):
         stage = stage.base
-    if not isinstance(stage, TrimmedDataset):
-        stage = dataset
+    return stage if isinstance(stage, TrimmedDataset) else dataset
+
+
+def _f0_tracks(dataset, keys):
+    """(source tracks, target tracks) of `keys` in sorted order: the f0 of the frames TrimmedDataset keeps, before
+    alignment (the items of the dataset itself when its chain has no TrimmedDataset)"""
+    stage = _trimmed_stage(dataset)
     sides = ([], [])
     for key in sorted(keys):
         for side, feature in zip(sides, stage[key]):
@@ -49,14 +53,30 @@ def _f0_tracks(dataset, keys):
     return sides
 
 
+def _target_mel_cepstra(dataset, keys, order, fs):
+    """the target side's mel-cepstra (frames, order + 1) of `keys` in sorted order, at the given order and sampling
+    rate: the frames `_f0_tracks` takes, c0 included"""
+    stage = _trimmed_stage(dataset)
+    mats = []
+    for key in sorted(keys):
+        snap = _pkg().feature(stage[key][1])
+        snap.mel_cepstrum_order = order
+        record = snap.mel_cepstrum if snap.fs == fs else snap.resample_mel_cepstrum(fs)
+        mats.append(np.ascontiguousarray(record.data, dtype=np.float64))
+    return mats
+
+
 class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
     def __init__(self, base, mcep_fs=None):
         super().__init__(base)
         self.mcep_fs = mcep_fs
         self.f0_stats = None
+        self.gv_stats = None
 
-    def train(self, dataset, keys, f0_stats=False, **kwargs):
-        """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`)"""
+    def train(self, dataset, keys, f0_stats=False, gv_stats=False, **kwargs):
+        """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`).
+        gv_stats=True: also the target side's global variance (`gv_stats`, order + 1 values: per coefficient the mean
+        over the training utterances of its variance within the utterance; used by `convert(gv=...)`)"""
         coefficients = MelCepstrumDataset(dataset, mcep_fs=self.mcep_fs)
         self.base.train(coefficients, keys, **kwargs)
         self.order, self.fs = coefficients.order, coefficients.fs
@@ -68,6 +88,13 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 raise ValueError('f0 statistics: no training files')
             self.f0_stats = f0map.stats_from_moments(f0map.merge_moments(f0map.logf0_moments(source)),
                                                      f0map.merge_moments(f0map.logf0_moments(target)))
+        self.gv_stats = None
+        if gv_stats:
+            from ..backend import gv as gvfilter
+            mats = _target_mel_cepstra(dataset, keys, self.order, self.fs)
+            if not mats:
+                raise ValueError('global variance statistics: no training files')
+            self.gv_stats = gvfilter.gv_from_moments(gvfilter.column_moments(mats))
 
     def convert_f0(self, f0, key=0.0, fs=None):
         """the f0 track for synthesising a converted voice: voiced frames through the log-Gaussian transform of
@@ -82,17 +109,21 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
 
     def save(self, path):
         """the trained stack as one .npz: the mixture's parameters and what the outer stages learnt from the
-        training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics when there are any)"""
+        training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics and the global variance when
+        there are any)"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
+            if self.gv_stats is not None:
+                extra['gv_stats'] = np.array(self.gv_stats, dtype=np.float64)
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      weights=gmm.weights_, means=gmm.means_, covariances=gmm.covariances_, **extra)
 
     def load(self, path):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
-        the file.  `f0_stats` is None for a file without them (written without f0 statistics, or before they existed)"""
+        the file.  `f0_stats` / `gv_stats` are None for a file without them (written without these statistics, or before
+        they existed)"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
@@ -111,13 +142,32 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             gmm.n_components = len(gmm.weights_)
             gmm.converged_ = True
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
+            self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None
         return self
 
-    def convert(self, mel_cepstrum, **kwargs):
-        """a MelCepstrum at the converter's sampling rate: c0 of the input, c1..cN converted"""
+    def convert(self, mel_cepstrum, gv=0.0, **kwargs):
+        """a MelCepstrum at the converter's sampling rate: c0 of the input, c1..cN converted.
+        gv > 0 (a strength within [0, 1]; needs `gv_stats`): the converted c1..cN through the global-variance
+        postfilter, each trajectory stretched about its own mean towards the target's variance.  With diff=True the
+        filter's change of the NON-differential conversion is added to the differential one, which costs one more
+        conversion (MLPG) of the same input."""
         if mel_cepstrum.order != self.order:
             raise ValueError(f'order is expected to {self.order!s} but {mel_cepstrum.order!s}')
+        if not 0.0 <= gv <= 1.0:
+            raise ValueError(f'global variance: strength {gv!r} is outside [0, 1]')
+        if gv > 0 and self.gv_stats is None:
+            raise ValueError('global variance: the converter has no statistics (train it with gv_stats=True)')
         out = copy.copy(mel_cepstrum) if mel_cepstrum.fs == self.fs else _pkg().resample(mel_cepstrum, self.fs)
         power, shape = out.data[:, :1], out.data[:, 1:]
-        out.data = np.hstack((power, super().convert(shape, raw=mel_cepstrum, **kwargs)))
+        converted = super().convert(shape, raw=mel_cepstrum, **kwargs)
+        if gv > 0:
+            from ..backend import gv as gvfilter
+            as_f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+            target = as_f64(self.gv_stats[1:])
+            if kwargs.get('diff'):
+                plain = super().convert(shape, raw=mel_cepstrum, **dict(kwargs, diff=False))
+                converted = gvfilter.postfilter(as_f64(plain), target, gv, base=as_f64(converted), first_col=0)
+            else:
+                converted = gvfilter.postfilter(as_f64(converted), target, gv, first_col=0)
+        out.data = np.hstack((power, converted))
         return out

@@ -447,10 +447,15 @@ class ConvertWave:
     Wavdata.save's normalisation only, a filtered waveform has no synthesis post-step).  f0_stats (mu_src, sigma_src,
     mu_tgt, sigma_tgt: a 4-tuple or 4 doubles on the device) and / or transpose_key != 0: the synthesis runs on the
     analysed f0 mapped by kwy_f0_map_batch_dev (into `f0_synth`; CheapTrick and D4C keep the analysed track), and
-    `f0_map_status` holds a word per utterance (non-zero: frames out of range, backend.f0.map_f0's limit)."""
+    `f0_map_status` holds a word per utterance (non-zero: frames out of range, backend.f0.map_f0's limit).
+    gv_strength > 0 (with a GMM and gv_stats, the order + 1 values of MelCepstrumFeatureConverter.gv_stats as an array
+    or on the device): the converted mel-cepstra through the global-variance postfilter right after the conversion
+    (kwy_column_moments_batch_dev, kwy_gv_postfilter_batch_dev on c1..cN, in place); with diff=True the differential
+    conversion then runs early and takes the filter's change of the plain conversion BEFORE that one is filtered in
+    place.  `gv_status` holds a word per utterance (non-zero: coefficients left unfiltered, backend.gv.postfilter)."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
-                 f0_stats=None, transpose_key=0.0):
+                 f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0):
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
         self.diff = bool(diff) and gmm is not None
         self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
@@ -540,6 +545,25 @@ class ConvertWave:
                     self.pcm_diff = [cut(self.pcm_diff_all, xo, i) for i in range(n)]
                     self.j_fin_diff = _lib.job_array(_lib.FinishJob, [(self.wave_diff[i], self.x[i].numel(), 0, self.pcm_diff[i])
                                                                       for i in range(n)])
+            self.gv_status, self.gv_strength = None, float(gv_strength)
+            if not 0.0 <= self.gv_strength <= 1.0:
+                raise ValueError(f'global variance: strength {gv_strength!r} is outside [0, 1]')
+            if self.gv_strength > 0 and gmm is not None:
+                if gv_stats is None:
+                    raise ValueError('global variance: gv_strength > 0 needs gv_stats')
+                self.gv = (gv_stats if torch.is_tensor(gv_stats) else
+                           torch.from_numpy(np.ascontiguousarray(gv_stats, dtype=np.float64))).to(dev)
+                if self.gv.shape != (order + 1,) or self.gv.dtype != torch.float64:
+                    raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
+                self.gv_moments = torch.empty((n, order + 1, 3), **f64)
+                self.gv_status = torch.zeros(n, dtype=torch.int32, device=dev)
+                conv = [cut(self.mc_conv, off, i) for i in range(n)]
+                self.j_gv_mom = _lib.job_array(_lib.GvMatrix, [(conv[i], self.T[i]) for i in range(n)])
+                self.j_gv = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], conv[i], conv[i])
+                                                        for i in range(n)])
+                if self.diff:
+                    self.j_gv_diff = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], self.mc_diff_rows[i],
+                                                                  self.mc_diff_rows[i]) for i in range(n)])
             self.j_render = _lib.synth_job_array([(self.plan[i], sp[i], ap[i], self.wave[i]) for i in range(n)])
         self.frames = int(sum(self.T))
 
@@ -568,6 +592,17 @@ class ConvertWave:
             else:
                 chk(lib.kwy_cheaptrick_mcep_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs), order, self.alpha))
                 chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv, n, order, self.gmm.M, _p(self.model)))
+                if self.gv_status is not None:
+                    cols = order + 1
+                    chk(lib.kwy_column_moments_batch_dev(h, self.j_gv_mom, n, cols, _p(self.gv_moments)))
+                    if self.diff:
+                        # the differential coefficients take the filter's change of the plain conversion, which the
+                        # filter of the plain conversion (in place) then overwrites: this order, on one stream
+                        chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
+                        chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv_diff, n, cols, 1, _p(self.gv), self.gv_strength,
+                                                            None))
+                    chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv, n, cols, 1, _p(self.gv), self.gv_strength,
+                                                        _p(self.gv_status)))
                 chk(lib.kwy_mc2sp_dev(h, _p(self.mc_conv), self.rows, order, self.alpha, fft, _p(self.sp_conv)))
             ls.main.wait_stream(ls.side)
             chk(lib.kwy_synth_render_batch_dev(h, self.j_render, n, fft, self.frame_period, fs, float(fs)))
@@ -577,7 +612,8 @@ class ConvertWave:
             if self.diff:
                 # the differential conversion of the same mel-cepstra, its filter over the INPUT waveforms: all
                 # utterances' recursions side by side (one wavefront each)
-                chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
+                if self.gv_status is None:           # (with the postfilter it ran above)
+                    chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
                 if not self.defer_mlsa:
                     self.run_mlsa(ls.ctx)
 
@@ -600,15 +636,16 @@ class ConvertWave:
 
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
-                    f0_stats=None, transpose_key=0.0):
+                    f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view[, pcm view]) on the main stream.
-    Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map) are read
-    back ONCE at the end."""
+    Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
+    global-variance postfilter) are read back ONCE at the end."""
     ls = ls if ls is not None else _Lockstep(device_index)
-    held, status, map_status, waves_diff = [], [], [], []
+    held, status, map_status, gv_status, waves_diff = [], [], [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
-                         diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key)
+                         diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key,
+                         **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}))
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -622,6 +659,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             status.append(wv.f0_status)
         if wv.f0_map_status is not None:
             map_status.append(wv.f0_map_status)
+        if wv.gv_status is not None:
+            gv_status.append(wv.gv_status)
         if diff:
             waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
         held.append(wv)
@@ -644,14 +683,18 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             for wv in waves_diff:
                 wv.finish_diff(ls.ctx)
     ls.sync()
-    words = torch.cat(status + map_status).cpu() if status or map_status else None
+    words = torch.cat(status + map_status + gv_status).cpu() if status or map_status or gv_status else None
     n_dio = sum(v.numel() for v in status)
+    n_map = sum(v.numel() for v in map_status)
     if status and bool(words[:n_dio].any()):
         bad = torch.nonzero(words[:n_dio]).flatten().tolist()
         raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
     if map_status:
         from .backend.f0 import check_status
-        check_status(words[n_dio:], fs)
+        check_status(words[n_dio:n_dio + n_map], fs)
+    if gv_status:
+        from .backend import gv as gvfilter
+        gvfilter.check_status(words[n_dio + n_map:])
     return ls
 
 
@@ -773,22 +816,28 @@ class _upload_ahead:
 
 def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
                           silence_for=None, pool=None, rng=None, pairs_before=0, driver=None, lockstep=None,
-                          wave_pairs=16, f0_moments=False):
+                          wave_pairs=16, f0_moments=False, gv_moments=False):
     """driver='lockstep' (default): waves of `wave_pairs` pairs through the batched entries on two streams
     (`TrainWave`; `lockstep`: a _Lockstep to reuse), rows appended behind a device-side cursor, one read-back per wave;
     driver='streams': round 3's pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
     f0_moments=True: a third result, the (2, 3) numpy array of the merged voiced log-f0 moments (n, mean, M2) of the
     source and of the target side -- each side's trimmed f0 tracks, merged in pair order on the device
-    (MelCepstrumFeatureConverter.train(f0_stats=True)'s statistics; backend.f0.stats_from_moments)."""
+    (MelCepstrumFeatureConverter.train(f0_stats=True)'s statistics; backend.f0.stats_from_moments).
+    gv_moments=True: a further result (after the f0 moments when both are asked for), the numpy vector of order + 1
+    values of the target side's global variance -- the column moments of every pair's trimmed target mel-cepstra as
+    the matrix path computes them, folded in pair order on the device (train(gv_stats=True)'s statistic)."""
     driver = driver or ('streams' if pool is not None else 'lockstep')
     moments = _PairMoments(len(pairs), device_index) if f0_moments else None
+    gv = _PairGV(len(pairs), order, device_index) if gv_moments else None
     if driver == 'lockstep':
         out = _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng,
-                                              pairs_before, lockstep, wave_pairs, moments)
+                                              pairs_before, lockstep, wave_pairs, moments, gv)
     else:
         out = _build_training_matrix_streams(pairs, fs, device_index, order, radius, frame_period, streams, silence_for,
-                                             pool, rng, pairs_before, moments)
-    return out if moments is None else out + (moments.merged(),)
+                                             pool, rng, pairs_before, moments, gv)
+    if moments is not None:
+        out = out + (moments.merged(),)
+    return out if gv is None else out + (gv.statistic(),)
 
 
 class _PairMoments:
@@ -811,13 +860,43 @@ class _PairMoments:
         ctx = _lib.Context(self.dev.index, stream=torch.cuda.current_stream(self.dev).cuda_stream)
         with torch.cuda.device(self.dev):
             out = torch.empty((2, 3), dtype=torch.float64, device=self.dev)
+            # for the null stream the context runs a stream of its own: torch's copies are finished before it starts, and
+            # it is finished before torch reads the result
+            sides = [self.rows[side::2].contiguous() for side in (0, 1)]
+            torch.cuda.current_stream(self.dev).synchronize()
             for side in (0, 1):
-                f0map.merge_moments_dev(ctx, self.rows[side::2].contiguous(), out[side])
+                f0map.merge_moments_dev(ctx, sides[side], out[side])
+            ctx.sync()
+            return out.cpu().numpy()
+
+
+class _PairGV:
+    """column moments of the trimmed target mel-cepstra of a corpus's pairs in HBM, one (order + 1, 3) block per pair"""
+
+    def __init__(self, n_pairs, order, device_index):
+        self.dev = torch.device('cuda', device_index)
+        self.rows = torch.empty((n_pairs, order + 1, 3), dtype=torch.float64, device=self.dev)      # every block is written
+
+    def add(self, ctx, first_pair, mats):
+        """enqueue (on ctx's stream) the moments of `mats`: the trimmed target mel-cepstra of consecutive pairs"""
+        from .backend import gv as gvfilter
+        gvfilter.column_moments_batch_dev(ctx, mats, self.rows[first_pair:first_pair + len(mats)])
+
+    def statistic(self):
+        """(after the streams that ran `add` are synchronised) the global variance, order + 1 values"""
+        if len(self.rows) == 0:
+            return np.zeros(self.rows.shape[1])
+        from .backend import gv as gvfilter
+        ctx = _lib.Context(self.dev.index, stream=torch.cuda.current_stream(self.dev).cuda_stream)
+        with torch.cuda.device(self.dev):
+            out = torch.empty(self.rows.shape[1], dtype=torch.float64, device=self.dev)
+            gvfilter.gv_from_moments_dev(ctx, self.rows, out)
+            ctx.sync()            # (for the null stream the context runs a stream of its own, which .cpu() does not wait for)
             return out.cpu().numpy()
 
 
 def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng, pairs_before,
-                                    ls, wave_pairs, moments=None):
+                                    ls, wave_pairs, moments=None, gv=None):
     dev = torch.device('cuda', device_index)
     ls = ls if ls is not None else _Lockstep(device_index)
     K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
@@ -864,6 +943,9 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
                 torch.minimum(worst, wave.n_rows.min().reshape(1), out=worst)
                 if moments is not None:
                     moments.add(ls.ctx, first_pair, [f[:k] for f, k in zip(wave.f0, wave.keep)])
+                if gv is not None:
+                    gv.add(ls.ctx, first_pair, [wave.reg(wave.mc_pad, 2 * k + 1)[PAD_LEN:PAD_LEN + wave.keep[2 * k + 1]]
+                                                for k in range(wave.n)])
         for w0 in range(0, len(pairs), wave_pairs):
             chunk = [uploads.get() for _ in range(len(pairs[w0:w0 + wave_pairs]))]
             wave = TrainWave(ls, fs, chunk, order=order, radius=radius, frame_period=frame_period)
@@ -893,7 +975,7 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
 
 
 def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
-                                   silence_for=None, pool=None, rng=None, pairs_before=0, moments=None):
+                                   silence_for=None, pool=None, rng=None, pairs_before=0, moments=None, gv=None):
     """pairs: list of ((x, f0, t), (x, f0, t)) numpy triples of THIS rank, in corpus order.  Returns the
     (n, 2*3*order) float64 device tensor of make_dataset_to_array and the number of source frames analysed.
     Pairs are processed `streams` at a time, each on its own stream (`pool`: a StreamPool to use instead of a new one).
@@ -926,6 +1008,9 @@ def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=3
             if moments is not None:
                 with torch.cuda.stream(p.stream):
                     moments.add(p.ctx, first_pair + k, [p.src.f0[:p.src.n], p.tgt.f0[:p.tgt.n]])
+            if gv is not None:
+                with torch.cuda.stream(p.stream):
+                    gv.add(p.ctx, first_pair + k, [p.tgt.mc_pad[PAD_LEN:PAD_LEN + p.tgt.n]])
         for p in wave:
             blocks.append(p.rows().clone())  # enqueued on the default stream after rows() has synchronised
             frames += p.frames
@@ -1015,7 +1100,8 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
 
 
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
-                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0):
+                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
+                  gv_stats=None, gv_strength=0.0):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1024,7 +1110,9 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     driver='lockstep' (default): waves of 16 utterances through the batched entries on two streams (`ConvertWave`);
     'streams': round 3's utterance-per-stream driver, see `_stream_batch` for its scheduling.
     f0_stats / transpose_key (lockstep driver): the waveforms are synthesised on the mapped f0 (ConvertWave); a frame
-    out of the map's range raises ValueError after the batch."""
+    out of the map's range raises ValueError after the batch.
+    gv_stats / gv_strength (lockstep driver): gv_strength > 0 runs the global-variance postfilter on the converted
+    mel-cepstra of both outputs (ConvertWave); a coefficient it cannot filter raises ValueError after the batch."""
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
@@ -1035,7 +1123,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         def keep_view(i, w, p=None, wd=None, pd=None):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
-                        f0_stats=f0_stats, transpose_key=transpose_key)
+                        f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
@@ -1043,6 +1131,8 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         raise ValueError('convert_batch: wav-in utterances and pcm=True need the lockstep driver')
     if f0_stats is not None or transpose_key != 0:
         raise ValueError('convert_batch: f0_stats and transpose_key need the lockstep driver')
+    if gv_stats is not None or gv_strength != 0:
+        raise ValueError('convert_batch: gv_stats and gv_strength need the lockstep driver')
     if pool is None:
         pool = StreamPool(device_index, streams)
 
