@@ -29,7 +29,8 @@ struct ct_view {
 // the mel-cepstrum form (k_cheaptrick<.., true> + k_cep2mc): the liftered cepstra of all frames of the launch
 struct ct_mcep {
   double *cep;           // (frames of the launch) x ncs, in workgroup order
-  int ncut, ncs;         // cepstral coefficients the frequency transform reads; row length (ncut rounded up to 4)
+  int ncut, ncs;         // cepstral coefficients the frequency transform reads (<= N: beyond N / 2 they are the
+                         // mirrored half of the symmetric cepstrum); row length (ncut rounded up to 4)
 };
 typedef kwy_batch<ct_view> ct_batch;
 
@@ -292,7 +293,14 @@ __global__ __launch_bounds__(KWY_THREADS, LOG2N <= 11 ? 5 : 4) void k_cheaptrick
     }
   }
   if constexpr (MCEP) {
-    for (int k = H + 1 + tid; k < mcep.ncs; k += KWY_THREADS) mcep.cep[(size_t)blockIdx.x * mcep.ncs + k] = 0.0;   // row padding
+    // pysptk transforms the whole symmetric cepstrum, c[N - k] = c[k]: a short transform with a large alpha and a high
+    // order reads beyond N / 2 (512 points, alpha 0.7, order 63: 4e-4 of the coefficients).  Rare: the row is mirrored
+    // from what the workgroup has just stored; the same stores are the row's padding.
+    if (mcep.ncs > H + 1) {
+      __syncthreads();
+      double *crow = mcep.cep + (size_t)blockIdx.x * mcep.ncs;
+      for (int k = H + 1 + tid; k < mcep.ncs; k += KWY_THREADS) crow[k] = k >= mcep.ncut ? 0.0 : crow[N - k];
+    }
     return;
   }
   kwy_irfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twb, twN);
@@ -371,13 +379,28 @@ static size_t ct_scratch_bytes(int64_t T) {
 // (mc_order + 1)); the arena then also holds the launch's cepstra (ct_mcep_bytes).
 static size_t ct_mcep_bytes(int64_t frames, int ncs) { return kwy_pad(sizeof(double) * (size_t)frames * ncs); }
 
-static int cheaptrick_core(kwy_ctx *ctx, ct_batch &b, int fs, double q1, int fft_size, double out_div, int mc_order = -1,
-                           double mc_alpha = 0.0) {
+// the transform lengths the kernels are built for; the window of a frame analysed with the 500 Hz default
+// (2 round(1.5 fs / 500) + 1 samples: every frame at or below the effective floor) has to fit as well
+static int ct_fft_check(kwy_ctx *ctx, int fs, int fft_size) {
   const int log2n = kwy_ilog2(fft_size);
   if ((1 << log2n) != fft_size || log2n < 9 || log2n > 12) {
     ctx->err = "cheaptrick: fft_size must be a power of two in [512, 4096]";
     return KWY_EINVAL;
   }
+  if (2 * (int)(1.5 * fs / CT_DEFAULT_F0 + 0.5) + 1 > fft_size) {
+    ctx->err = "cheaptrick: fft_size too short for the sampling rate (the window of the 500 Hz default does not fit)";
+    return KWY_EINVAL;
+  }
+  return KWY_OK;
+}
+
+// rows of the cepstral scratch of the mel-cepstrum form
+static int ct_mcep_row(int ncut, int fft_size) { return ((ncut < fft_size ? ncut : fft_size) + 3) & ~3; }
+
+static int cheaptrick_core(kwy_ctx *ctx, ct_batch &b, int fs, double q1, int fft_size, double out_div, int mc_order = -1,
+                           double mc_alpha = 0.0) {
+  KWY_TRY(ct_fft_check(ctx, fs, fft_size));
+  const int log2n = kwy_ilog2(fft_size);
   const int K = fft_size / 2 + 1;
   const double floor_eff = 3.0 * fs / (fft_size - 3.0);
   b.start[0] = 0;
@@ -400,8 +423,8 @@ static int cheaptrick_core(kwy_ctx *ctx, ct_batch &b, int fs, double q1, int fft
   const double *F;
   ct_mcep mcep;
   KWY_TRY(kwy_get_sp2mc_matrix(ctx, fft_size, mc_order, mc_alpha, &F, &mcep.ncut));
-  if (mcep.ncut > K) mcep.ncut = K;
-  mcep.ncs = (mcep.ncut + 3) & ~3;
+  if (mcep.ncut > fft_size) mcep.ncut = fft_size;
+  mcep.ncs = ct_mcep_row(mcep.ncut, fft_size);
   mcep.cep = kwy_arena<double>(ctx, (size_t)b.start[b.n] * mcep.ncs);
   if (!mcep.cep) { ctx->err = "cheaptrick: scratch arena too small"; return KWY_ENOMEM; }
   switch (log2n) {
@@ -497,8 +520,13 @@ extern "C" int kwy_cheaptrick_mcep_batch_dev(kwy_ctx *ctx, const kwy_utterance *
   }
   if (frames > 0x7fffffff) { ctx->err = "cheaptrick_mcep_batch: too many frames"; return KWY_EINVAL; }
   KWY_HIP(hipSetDevice(ctx->device));
-  // (the cepstra rows are at most K + 3 doubles; the passes of a call run one after the other but keep their own rows)
-  KWY_TRY(kwy_arena_begin(ctx, scratch + ct_mcep_bytes(frames, fft_size / 2 + 4) + 4096 * ((count + KWY_BATCH_MAX - 1) / KWY_BATCH_MAX)));
+  KWY_TRY(ct_fft_check(ctx, fs, fft_size));
+  const double *F;
+  int ncut;
+  KWY_TRY(kwy_get_sp2mc_matrix(ctx, fft_size, order, alpha, &F, &ncut));
+  // (the cepstra rows are at least K + 3 doubles; the passes of a call run one after the other but keep their own rows)
+  const int row = ct_mcep_row(ncut, fft_size) > fft_size / 2 + 4 ? ct_mcep_row(ncut, fft_size) : fft_size / 2 + 4;
+  KWY_TRY(kwy_arena_begin(ctx, scratch + ct_mcep_bytes(frames, row) + 4096 * ((count + KWY_BATCH_MAX - 1) / KWY_BATCH_MAX)));
   for (int i0 = 0; i0 < count; i0 += KWY_BATCH_MAX) {
     ct_batch b;
     b.n = count - i0 < KWY_BATCH_MAX ? count - i0 : KWY_BATCH_MAX;

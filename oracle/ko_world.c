@@ -317,6 +317,8 @@ int ko_cheaptrick(const double *x, int64_t x_length, int fs, const double *t,
                   const double *f0, int64_t f0_length, double q1,
                   double f0_floor, int fft_size, double *out) {
   if (fft_size <= 0) fft_size = ko_cheaptrick_fft_size(fs, f0_floor);
+  /* the window of a frame analysed with kDefaultF0 must fit the transform (WORLD itself overruns its buffer) */
+  if (2 * matlab_round(1.5 * fs / kDefaultF0) + 1 > fft_size) return -1;
   int half = fft_size / 2;
   ko_rng rng; ko_rng_seed(&rng);
   double floor_eff = ko_cheaptrick_f0_floor(fs, fft_size);

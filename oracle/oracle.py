@@ -170,8 +170,10 @@ def cheaptrick(x, f0, temporal_positions, fs, q1=-0.15, f0_floor=default_f0_floo
     if fft_size is None:
         fft_size = get_cheaptrick_fft_size(fs, f0_floor)
     out = np.zeros((len(f0), fft_size // 2 + 1))
-    lib().ko_cheaptrick(_dp(x), len(x), int(fs), _dp(t), _dp(f0), len(f0), q1,
-                        f0_floor, int(fft_size), _dp(out))
+    rc = lib().ko_cheaptrick(_dp(x), len(x), int(fs), _dp(t), _dp(f0), len(f0), q1,
+                             f0_floor, int(fft_size), _dp(out))
+    if rc != 0:
+        raise ValueError('oracle cheaptrick: fft_size too short for the 500 Hz default window at this rate')
     return out
 
 

@@ -100,14 +100,15 @@ MUTANTS = [
 ]
 
 
-def load_mutant(tmp_path, name, text, replacement):
-    """A copy of oracle/ with one edit of ko_world.c, built by its own Makefile and loaded as a module of its own."""
+def load_mutant(tmp_path, name, text, replacement, file='ko_world.c'):
+    """A copy of oracle/ with one edit of ko_world.c (or of another `file` of it), built by its own Makefile and
+    loaded as a module of its own."""
     src = os.path.join(ROOT, 'oracle')
     dst = tmp_path / 'oracle'
     shutil.copytree(src, dst, ignore=shutil.ignore_patterns('*.so', '__pycache__', '_ref'))
-    c = (dst / 'ko_world.c').read_text()
+    c = (dst / file).read_text()
     assert c.count(text) == 1, name
-    (dst / 'ko_world.c').write_text(c.replace(text, replacement))
+    (dst / file).write_text(c.replace(text, replacement))
     subprocess.run(['make', '-C', str(dst), '-s'], check=True, capture_output=True)
     spec = importlib.util.spec_from_file_location(f'mutant_oracle_{abs(hash(name))}', dst / 'oracle.py')
     mod = importlib.util.module_from_spec(spec)

@@ -2,12 +2,14 @@
 (libkwy.so via ctypes), against the CPU oracle on identical inputs.
 
 Tolerances (float64 path; north_star: output within 1e-4 RMS of the CPU path):
-  * spectral envelope: max |d| / max|ref| per utterance <= 1e-8, and the
-    log-spectral distance per bin <= 1e-3 on bins that are within 100 dB of the
-    frame maximum, and sum|d| / sum|ref| <= 1e-9.  (CheapTrick's linear smoothing differences two cumulative
-    sums; bins far below the frame's total power are conditioned like
-    eps * total / local in ANY summation order, CPU included, so elementwise
-    agreement on dead bins is not a meaningful target.)
+  * spectral envelope: tests/ct_cases.assert_sp_close -- per frame max |d| <= SP_FRAME_REL of the frame's own maximum
+    and |d log| <= SP_LOG on every bin of every frame, no bin left out (10x the worst seen on an MI355X, see
+    ct_cases.py).  CheapTrick's linear smoothing differences two cumulative sums, so bins far below the frame's total
+    power are conditioned like eps * total / local in ANY summation order, CPU included: recordings have such bins
+    (the Nyquist bin at 16 kHz; everything above 8 kHz in those resampled up from 16 kHz) and are held to the
+    _RECORDED and _UPSAMPLED pairs, which are the oracle's own running-sum error, and beside them to what every
+    envelope was held to before: max |d| <= 1e-8 of the utterance's maximum, sum|d| / sum|ref| <= 1e-9, and
+    |d log| <= 1e-3 on the bins within 100 dB of their frame's maximum (sp_close below).
   * aperiodicity: tests/d4c_cases.assert_ap_close -- the same frames pass the LoveTrain gate, the others are
     bit-equal, and on the gated ones max abs <= AP_ABS and max |dB| <= AP_DB (10x the worst seen on an MI355X;
     the recordings resampled up from 16 kHz: AP_ABS_UPSAMPLED / AP_DB_UPSAMPLED, see d4c_cases.py)
@@ -21,6 +23,7 @@ import pytest
 from scipy.io import wavfile
 
 from conftest import CLB_WAV, SLT_WAV, clb_variant
+from ct_cases import assert_sp_close
 from d4c_cases import RATES, UNGATED, assert_ap_close, batch_cases, edge_case
 
 pytestmark = pytest.mark.gpu
@@ -53,14 +56,18 @@ def f0_track(ko, x, fs):
     return ko.stonemask(x, f0, t, fs), t
 
 
-def check_spectrum(got, ref):
-    assert got.shape == ref.shape
-    assert np.isfinite(got).all()
-    assert np.abs(got - ref).max() / np.abs(ref).max() <= 1e-8
-    assert np.abs(got - ref).sum() / np.abs(ref).sum() <= 1e-9
+def sp_close(got, ref, label, fs=None):
+    """assert_sp_close (fs: the rate of a recording, which picks its pair of bounds), and beside it what the check it
+    replaces asked and the recordings' pairs do not: 1e-8 of the utterance's maximum, 1e-9 of its sum, 1e-3 in log on
+    the bins within 100 dB of their frame's maximum."""
+    assert_sp_close(got, ref, label, None if fs is None else 'upsampled' if fs > 16000 else 'native')
+    e_max = np.abs(got - ref).max() / np.abs(ref).max()
+    assert e_max <= 1e-8, f'{label}: max |d| / max |ref| {e_max:.3e} > 1e-8'
+    e_sum = np.abs(got - ref).sum() / np.abs(ref).sum()
+    assert e_sum <= 1e-9, f'{label}: sum |d| / sum |ref| {e_sum:.3e} > 1e-9'
     live = ref >= ref.max(axis=1, keepdims=True) * 1e-10
-    lsd = np.abs(np.log(got[live]) - np.log(ref[live]))
-    assert lsd.max() <= 1e-3, lsd.max()
+    e_live = np.abs(np.log(got[live]) - np.log(ref[live])).max()
+    assert e_live <= 1e-3, f'{label}: max |d log| on live bins {e_live:.3e} > 1e-3'
 
 
 CASES = [CLB_WAV, SLT_WAV, clb_variant('22'), clb_variant('44'), clb_variant('48'), clb_variant('96')]
@@ -70,7 +77,7 @@ CASES = [CLB_WAV, SLT_WAV, clb_variant('22'), clb_variant('44'), clb_variant('48
 def test_cheaptrick_parity(ko, kw, path):
     fs, x = load(path)
     f0, t = f0_track(ko, x, fs)
-    check_spectrum(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs))
+    sp_close(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs), tag(path), fs)
 
 
 @pytest.mark.parametrize('path', CASES)
@@ -276,7 +283,7 @@ def test_frame_periods(ko, kw, frame_period):
     fs, x = load(CLB_WAV)
     f0, t = ko.dio(x, fs, frame_period=frame_period)
     f0 = ko.stonemask(x, f0, t, fs)
-    check_spectrum(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs))
+    sp_close(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs), f'{tag(CLB_WAV)} frame period {frame_period}', fs)
     sp, ap = ko.cheaptrick(x, f0, t, fs), ko.d4c(x, f0, t, fs)
     got = kw.synthesize(f0, sp, ap, fs, float(frame_period))
     ref = ko.synthesize(f0, sp, ap, fs, float(frame_period))
@@ -292,7 +299,7 @@ def test_low_sampling_rates(ko, kw, fs, up, down):
     _, x16 = load(CLB_WAV)
     x = np.ascontiguousarray(ss.resample_poly(x16, up, down))
     f0, t = f0_track(ko, x, fs)
-    check_spectrum(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs))
+    sp_close(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs), f'clb resampled to {fs}', fs)
     ref = ko.d4c(x, f0, t, fs)
     assert_ap_close(kw.d4c(x, f0, t, fs), ref, f'clb resampled to {fs}')
     sp, ap = ko.cheaptrick(x, f0, t, fs), ref
@@ -304,8 +311,8 @@ def test_options(ko, kw):
     tests/kwiiyatta/test_vocoder.py:429-430, view/qt/kwiieiya.py:84)."""
     fs, x = load(CLB_WAV)
     f0, t = f0_track(ko, x, fs)
-    check_spectrum(kw.cheaptrick(x, f0, t, fs, q1=-0.09, fft_size=2048),
-                   ko.cheaptrick(x, f0, t, fs, q1=-0.09, fft_size=2048))
+    sp_close(kw.cheaptrick(x, f0, t, fs, q1=-0.09, fft_size=2048), ko.cheaptrick(x, f0, t, fs, q1=-0.09, fft_size=2048),
+             f'{tag(CLB_WAV)} q1 -0.09 fft_size 2048', fs)
     for thr in (0.0, 0.5, 0.95):
         assert_ap_close(kw.d4c(x, f0, t, fs, threshold=thr), ko.d4c(x, f0, t, fs, threshold=thr),
                         f'{tag(CLB_WAV)} threshold {thr}')
@@ -343,18 +350,19 @@ def test_edge_inputs(ko, kw):
     x = rng.standard_normal(4000) * 0.01
     f0 = np.zeros(51)
     t = np.arange(51) * 0.005
-    check_spectrum(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs))
+    sp_close(kw.cheaptrick(x, f0, t, fs), ko.cheaptrick(x, f0, t, fs), 'edge inputs: unvoiced noise')
     assert np.array_equal(kw.d4c(x, f0, t, fs), ko.d4c(x, f0, t, fs))
     xs = np.zeros(4000)
     got, ref = kw.cheaptrick(xs, f0, t, fs), ko.cheaptrick(xs, f0, t, fs)
     assert np.abs(np.log(got) - np.log(ref)).max() <= 1e-6   # spectrum of the noise floor itself
+    sp_close(got, ref, 'edge inputs: digital silence')
     sp = ko.cheaptrick(x, f0, t, fs)
     ap = ko.d4c(x, f0, t, fs)
     assert np.sqrt(np.mean((kw.synthesize(f0, sp, ap, fs) - ko.synthesize(f0, sp, ap, fs)) ** 2)) <= 1e-12
     # very short signal, frames beyond the end of x
     x1 = rng.standard_normal(90) * 0.1
     f01 = np.array([0.0, 120.0, 0.0]); t1 = np.arange(3) * 0.005
-    check_spectrum(kw.cheaptrick(x1, f01, t1, fs), ko.cheaptrick(x1, f01, t1, fs))
+    sp_close(kw.cheaptrick(x1, f01, t1, fs), ko.cheaptrick(x1, f01, t1, fs), 'edge inputs: 90 samples, 3 frames')
 
 
 def test_contiguity_contract(kw):
@@ -384,7 +392,7 @@ def test_full_size_config2(ko, kw):
     sp, ap = kw.cheaptrick(x, f0, t, fs), kw.d4c(x, f0, t, fs)
     assert sp.shape == (2001, 1025) and ap.shape == (2001, 1025)
     sp_ref, ap_ref = ko.cheaptrick(x, f0, t, fs), ko.d4c(x, f0, t, fs)
-    check_spectrum(sp, sp_ref)
+    sp_close(sp, sp_ref, 'config 2: make_utterance(seed=1234) 48 kHz 10 s')
     assert_ap_close(ap, ap_ref, 'config 2: make_utterance(seed=1234) 48 kHz 10 s')
     y = kw.synthesize(f0, sp, ap, fs, 5.0)
     assert len(y) == 480240
@@ -452,7 +460,7 @@ def test_jump_ahead_beyond_the_table_gives_the_same_bits(ko, kw, path, limit):
         out.append((sp, ap, y))
     for a, b in zip(*out):
         assert np.array_equal(a, b)
-    check_spectrum(out[1][0], ko.cheaptrick(x, f0, t, fs))
+    sp_close(out[1][0], ko.cheaptrick(x, f0, t, fs), f'{tag(path)} 1.2 s, randn table cut at {limit}', fs)
     assert_ap_close(out[1][1], ko.d4c(x, f0, t, fs), f'{tag(path)} 1.2 s, randn table cut at {limit}',
                     upsampled=fs > 16000)
 
