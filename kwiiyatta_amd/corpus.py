@@ -11,10 +11,11 @@ What the reference does for `kwiiyatta --source A --target B files...`
   fit         GaussianMixture(n_components, covariance_type='full', max_iter=100, random_state=seed)
   per file    analyse; convert the mel-cepstrum (delta + GMM posterior + MLPG, c0 kept); synthesise
 
-Here every pair runs on its own HIP stream (`TrainPair`), ranks take contiguous blocks of pairs (the global
+Here waves of up to 16 pairs run in lockstep through the batched entries on two HIP streams (`TrainWave`; the
+pair-per-stream driver `TrainPair` remains as driver='streams'), ranks take contiguous blocks of pairs (the global
 row order is the pair order whatever the number of ranks), the rows land in one device tensor that
-`GaussianMixtureHIP.fit` uses as its shard, and the fitted model converts utterances stream-parallel
-(`ConvertPipeline`).  The only collectives are those of the fit.
+`GaussianMixtureHIP.fit` uses as its shard, and the fitted model converts utterances wave by wave (`ConvertWave`;
+stream-parallel with `ConvertPipeline`).  The only collectives are those of the fit.
 
 The silence padding of `align_even` draws from numpy's GLOBAL legacy generator in the reference
 (kwiiyatta/vocoder/world.py:158-161, quirk kept): the draws are made on the host, in the reference's order
@@ -25,37 +26,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, c_vp
-from .pipeline import (PAD_LEN, POWER_THRESHOLD, POWER_WEIGHT, SAFE_GUARD_MINIMUM, VUV_WEIGHT, DeviceGMM, _Graphed,
-                       draw_silence)
+from ._blocks import Ragged, p as _p, to_device
+from ._lib import lib
+from .pipeline import (PAD_LEN, PIECE_CEILING, POWER_THRESHOLD, POWER_WEIGHT, SAFE_GUARD_MINIMUM, VUV_WEIGHT, DeviceGMM,
+                       _Graphed, _Side, draw_silence, f0_jobs)
 
 TRIM_EPS = 1e-7       # nnmnkwii trim_zeros_frames / remove_zeros_frames
-
-
-def _p(t):
-    return c_vp(t.data_ptr())
-
-
-class _TrainSide:
-    def __init__(self, x, f0, t, fs, K, order, dev):
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.N, self.T = len(x), len(f0)
-        up = lambda a: a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
-        self.x, self.f0, self.t = up(x), up(f0), up(t)
-        Tp = self.T + 2 * PAD_LEN
-        self.sp_pad = torch.empty((Tp, K), **f64)
-        self.ap_pad = torch.full((Tp, K), 1 - SAFE_GUARD_MINIMUM, **f64)
-        self.f0_pad = torch.zeros(Tp, **f64)
-        self.n_keep_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.n = None          # frames kept by TrimmedDataset (host int, after analyse + sync)
-
-    @property
-    def sp(self):
-        return self.sp_pad[PAD_LEN:PAD_LEN + self.T]
-
-    @property
-    def ap(self):
-        return self.ap_pad[PAD_LEN:PAD_LEN + self.T]
 
 
 class TrainPair:
@@ -82,12 +58,14 @@ class TrainPair:
         if silence is None:        # the reference's order of draws: source head, source tail, target head, tail
             silence = [draw_silence(self.fs, self.K) for _ in range(4)]
         with torch.cuda.stream(self.stream):
-            self.src = _TrainSide(*source, self.fs, self.K, order, self.dev)
-            self.tgt = _TrainSide(*target, self.fs, self.K, order, self.dev)
+            # (align() writes all rows of the padded envelope it reads, and fills f0_pad's middle at the trimmed length)
+            self.src, self.tgt = (_Side(*u, self.K, self.dev, sp_alloc=torch.empty) for u in (source, target))
+            for s in (self.src, self.tgt):
+                s.n_keep_dev = torch.zeros(1, dtype=torch.int64, device=self.dev)
+                s.n = None          # frames kept by TrimmedDataset (host int, after analyse + sync)
             if silence_ready is not None:
                 self.stream.wait_event(silence_ready)
-            self.silence = [s if torch.is_tensor(s) else torch.from_numpy(np.ascontiguousarray(s)).to(self.dev)
-                            for s in silence]
+            self.silence = [to_device(s, self.dev) for s in silence]
             # tensors made on other streams (the upload helper's, the generator's) are used on this one: the allocator
             # must not hand their memory out again while this stream's work on them is still queued
             for t_ in (self.src.x, self.src.f0, self.src.t, self.tgt.x, self.tgt.f0, self.tgt.t, *self.silence):
@@ -116,15 +94,13 @@ class TrainPair:
             keep = torch.cat((self.src.n_keep_dev, self.tgt.n_keep_dev)).cpu().tolist()   # waits for the analysis
             for s, n, sil in ((self.src, keep[0], self.silence[:2]), (self.tgt, keep[1], self.silence[2:])):
                 s.n = int(n)
-                s.Tp = s.n + 2 * P
+                s.feature_rows(s.n + 2 * P, order)       # (the side's Tp is the trimmed one from here on)
                 # pad_silence on the first n frames (TrimmedDataset keeps feature[:n])
                 s.sp_pad[:P].copy_(sil[0])
                 s.sp_pad[P + s.n:s.Tp].copy_(sil[1])
                 s.ap_pad[P + s.n:s.Tp].fill_(1 - SAFE_GUARD_MINIMUM)
                 s.f0_pad[P:P + s.n].copy_(s.f0[:s.n])
                 s.voiced = torch.empty(s.Tp, **f64)
-                s.mc_pad = torch.empty((s.Tp, order + 1), **f64)
-                s.feat = torch.empty((s.Tp, order + 2), **f64)
                 self._chk(lib.kwy_is_voiced_dev(h, _p(s.f0_pad), _p(s.ap_pad), s.Tp, K, fs, _p(s.voiced)))
                 self._chk(lib.kwy_sp2mc_dev(h, _p(s.sp_pad), s.Tp, K, order, self.alpha, _p(s.mc_pad)))
                 # make_feature(vuv='voiced', power='binalize', power_pivot='max')
@@ -178,17 +154,6 @@ class _Lockstep:
         self.side.synchronize()
 
 
-def _resident(side, dev, streams):
-    """(x, f0, t) as device tensors that the given streams may use after the caller has dropped them"""
-    out = []
-    for a in side:
-        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        for s_ in streams:
-            t.record_stream(s_)
-        out.append(t)
-    return out
-
-
 class TrainWave:
     """<= 16 parallel pairs -> their rows of the training matrix, in lockstep through the batched entries of
     include/kwy.h (what TrainPair does pair by pair on a stream each):
@@ -210,14 +175,14 @@ class TrainWave:
         f64 = dict(dtype=torch.float64, device=dev)
         P = PAD_LEN
         with torch.cuda.stream(ls.main):
-            sides = [_resident(s, dev, (ls.main, ls.side)) for pair in pairs for s in pair]
+            # (x, f0, t) of every side: both streams may use them after the caller has dropped them
+            sides = [[to_device(a, dev, (ls.main, ls.side)) for a in s] for pair in pairs for s in pair]
             self.x, self.f0, self.t = ([s[k] for s in sides] for k in range(3))
             self.N = [len(v) for v in self.x]
             self.T = [len(v) for v in self.f0]
-            off = np.concatenate(([0], np.cumsum([t + 2 * P for t in self.T]))).astype(np.int64)
-            self.off = off
-            rows = int(off[-1])
-            self.rows = rows
+            layout = Ragged([t + 2 * P for t in self.T])
+            self.reg = layout.view          # reg(block, i): the padded rows of side i in one of the blocks below
+            self.rows = rows = layout.total
             self.sp_pad = torch.empty((rows, K), **f64)
             self.ap_pad = torch.full((rows, K), 1 - SAFE_GUARD_MINIMUM, **f64)
             self.f0_pad = torch.empty(rows, **f64)
@@ -227,10 +192,7 @@ class TrainWave:
             ns = len(sides)
             self.keep_dev = torch.zeros(ns, dtype=torch.int64, device=dev)
             self.keep_host = torch.zeros(ns, dtype=torch.int64).pin_memory()
-            reg = lambda a, i: a[int(off[i]):int(off[i + 1])]  # noqa: E731
-            self.sp = [reg(self.sp_pad, i)[P:P + self.T[i]] for i in range(ns)]
-            self.ap = [reg(self.ap_pad, i)[P:P + self.T[i]] for i in range(ns)]
-            self.reg = reg
+            self.sp, self.ap = layout.views(self.sp_pad, P, P), layout.views(self.ap_pad, P, P)
             self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], self.sp[i]) for i in range(ns)])
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], self.ap[i]) for i in range(ns)])
             self.j_trim = _lib.job_array(_lib.TrimJob, [(self.sp[i], self.T[i], self.keep_dev[i:i + 1]) for i in range(ns)])
@@ -324,11 +286,9 @@ class ConvertPipeline(_Graphed):
         self.mcep_fs = int(mcep_fs) if mcep_fs is not None and int(mcep_fs) != self.fs else None
         self.rng = rng
         with torch.cuda.stream(self.stream):
-            for a in (x, f0, t):
-                if torch.is_tensor(a):
-                    a.record_stream(self.stream)        # (cloned below on this stream; the caller may drop it)
-            self.x, self.f0, self.t = (a.clone() if torch.is_tensor(a) else
-                                       torch.from_numpy(np.ascontiguousarray(a)).to(self.dev) for a in (x, f0, t))
+            # (a caller's tensor is cloned on this stream, and recorded: the caller may drop it while the clone is queued)
+            self.x, self.f0, self.t = (to_device(a, self.dev, (self.stream,)).clone() if torch.is_tensor(a) else
+                                       to_device(a, self.dev) for a in (x, f0, t))
             self.sp = torch.empty((self.T, self.K), **f64)
             self.ap = torch.empty((self.T, self.K), **f64)
             self.mc = torch.empty((self.T, order + 1), **f64)
@@ -367,10 +327,8 @@ class ConvertPipeline(_Graphed):
             raise ValueError('ConvertPipeline.load: shape differs from the pipeline\'s')
         with torch.cuda.stream(self.stream):
             for dst, src in ((self.x, x), (self.f0, f0), (self.t, t)):
-                if torch.is_tensor(src):
-                    src.record_stream(self.stream)      # (the caller may drop it while the copy is still queued)
-                dst.copy_(src if torch.is_tensor(src) else torch.from_numpy(np.ascontiguousarray(src)),
-                          non_blocking=True)
+                # (a caller's tensor is recorded: it may be dropped while the copy is still queued)
+                dst.copy_(to_device(src, None, (self.stream,)), non_blocking=True)
 
     def _convert_across_rates(self, chk, h):
         """self.mc (utterance rate) -> self.mc_conv (utterance rate) through the converter's rate"""
@@ -470,36 +428,33 @@ class ConvertWave:
         f64 = dict(dtype=torch.float64, device=dev)
         with torch.cuda.stream(ls.main):
             self.model = gmm.model(diff=False) if gmm is not None else None
-            cut = lambda a, o, i: a[int(o[i]):int(o[i + 1])]  # noqa: E731
+            both = (ls.main, ls.side)           # the inputs: both streams may use them after the caller has dropped them
             if self.wav_in:
-                self.x = [_resident((u,), dev, (ls.main, ls.side))[0] for u in utterances]
+                self.x = [to_device(u, dev, both) for u in utterances]
                 self.T = [int(lib.kwy_dio_frames(self.fs, v.numel(), self.frame_period)) for v in self.x]
-                off = np.concatenate(([0], np.cumsum(self.T))).astype(np.int64)
-                blocks = [torch.empty(int(off[-1]), **f64) for _ in range(3)]
-                self.t, self.f0_dio, self.f0 = ([cut(b, off, i) for i in range(n)] for b in blocks)
+                rows = Ragged(self.T)           # the layout of every per-frame block: the utterances' frames end to end
+                self.t, self.f0_dio, self.f0 = (rows.views(torch.empty(rows.total, **f64)) for _ in range(3))
                 self.f0_status = torch.zeros(n, dtype=torch.int32, device=dev)
-                self.j_dio = _lib.job_array(_lib.F0Job, [(self.x[i], self.x[i].numel(), self.t[i], self.f0_dio[i],
-                                                          self.f0_status[i:i + 1]) for i in range(n)])
-                self.j_sm = _lib.utterance_array([(self.x[i], self.t[i], self.f0_dio[i], self.f0[i]) for i in range(n)])
+                self.j_dio, self.j_sm = f0_jobs(self.x, self.t, self.f0_dio, self.f0, self.f0_status)
             else:
-                us = [_resident(u, dev, (ls.main, ls.side)) for u in utterances]
+                us = [[to_device(a, dev, both) for a in u] for u in utterances]
                 self.x, self.f0, self.t = ([u[k] for u in us] for k in range(3))
                 self.T = [len(v) for v in self.f0]
-                off = np.concatenate(([0], np.cumsum(self.T))).astype(np.int64)
+                rows = Ragged(self.T)
                 self.f0_status = None
-            self.rows = int(off[-1])
+            self.rows = rows.total
             # (with a GMM nothing reads the analysed envelopes but sp2mc: CheapTrick hands over mel-cepstra instead,
             # kwy_cheaptrick_mcep_batch_dev)
             self.sp_all = torch.empty((self.rows, K), **f64) if gmm is None else None
             self.ap_all = torch.empty((self.rows, K), **f64)
             self.ylen = [int(lib.kwy_synth_length(t, self.frame_period, self.fs)) for t in self.T]
-            yo = np.concatenate(([0], np.cumsum(self.ylen))).astype(np.int64)
-            self.wave_all = torch.empty(int(yo[-1]), **f64)
-            self.wave = [cut(self.wave_all, yo, i) for i in range(n)]
+            out = Ragged(self.ylen)
+            self.wave_all = torch.empty(out.total, **f64)
+            self.wave = out.views(self.wave_all)
             self.pcm = None
             if pcm:
-                self.pcm_all = torch.zeros(int(yo[-1]), dtype=torch.int16, device=dev)
-                self.pcm = [cut(self.pcm_all, yo, i) for i in range(n)]
+                self.pcm_all = torch.zeros(out.total, dtype=torch.int16, device=dev)
+                self.pcm = out.views(self.pcm_all)
                 self.j_fin = _lib.job_array(_lib.FinishJob, [(self.wave[i], self.ylen[i], self.T[i], self.pcm[i])
                                                              for i in range(n)])
             self.plan = [torch.empty(int(lib.kwy_synth_plan_bytes(y)), dtype=torch.uint8, device=dev) for y in self.ylen]
@@ -509,40 +464,39 @@ class ConvertWave:
                 self.f0_stats = None if f0_stats is None else torch.as_tensor(
                     f0_stats if torch.is_tensor(f0_stats) else list(f0_stats), dtype=torch.float64, device=dev)
                 self.f0_synth_all = torch.empty(self.rows, **f64)
-                self.f0_synth = [cut(self.f0_synth_all, off, i) for i in range(n)]
+                self.f0_synth = rows.views(self.f0_synth_all)
                 self.f0_map_status = torch.zeros(n, dtype=torch.int32, device=dev)
                 self.j_map = _lib.job_array(_lib.F0MapJob, [(self.f0[i], self.T[i], self.f0_synth[i]) for i in range(n)])
             if gmm is not None:
                 assert gmm.D2 == 6 * order
                 self.mc = torch.empty((self.rows, order + 1), **f64)
-            sp = [cut(self.sp_all if gmm is None else self.mc, off, i) for i in range(n)]
-            ap = [cut(self.ap_all, off, i) for i in range(n)]
-            self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], sp[i]) for i in range(n)])
+            # CheapTrick's rows (envelopes, or mel-cepstra for the conversion) and the rows the rendering reads
+            env, ap = rows.views(self.sp_all if gmm is None else self.mc), rows.views(self.ap_all)
+            spec = env
+            self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], env[i]) for i in range(n)])
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], ap[i]) for i in range(n)])
             self.j_plan = _lib.job_array(_lib.SynthPlanJob, [(self.f0_synth[i], self.T[i], self.ylen[i], self.plan[i])
                                                              for i in range(n)])
             if gmm is not None:
                 self.mc_conv = torch.empty((self.rows, order + 1), **f64)
                 self.sp_conv = torch.empty((self.rows, K), **f64)
-                self.j_conv = _lib.job_array(_lib.ConvertJob, [(cut(self.mc, off, i), self.T[i], cut(self.mc_conv, off, i))
-                                                               for i in range(n)])
-                sp = [cut(self.sp_conv, off, i) for i in range(n)]
+                conv, spec = rows.views(self.mc_conv), rows.views(self.sp_conv)
+                self.j_conv = _lib.job_array(_lib.ConvertJob, [(env[i], self.T[i], conv[i]) for i in range(n)])
             if self.diff:
                 self.model_diff = gmm.model(diff=True)
                 self.mc_diff = torch.empty((self.rows, order + 1), **f64)
-                self.j_conv_diff = _lib.job_array(_lib.ConvertJob, [(cut(self.mc, off, i), self.T[i], cut(self.mc_diff, off, i))
-                                                                    for i in range(n)])
-                xo = np.concatenate(([0], np.cumsum([v.numel() for v in self.x]))).astype(np.int64)
-                self.wave_diff_all = torch.empty(int(xo[-1]), **f64)
-                self.wave_diff = [cut(self.wave_diff_all, xo, i) for i in range(n)]
-                self.mc_diff_rows = [cut(self.mc_diff, off, i) for i in range(n)]
+                self.mc_diff_rows = rows.views(self.mc_diff)
+                self.j_conv_diff = _lib.job_array(_lib.ConvertJob, [(env[i], self.T[i], self.mc_diff_rows[i]) for i in range(n)])
+                samples = Ragged([v.numel() for v in self.x])         # the filtered inputs: as long as the inputs
+                self.wave_diff_all = torch.empty(samples.total, **f64)
+                self.wave_diff = samples.views(self.wave_diff_all)
                 self.j_mlsa = _lib.job_array(_lib.MlsaJob, [(self.x[i], self.x[i].numel(), self.mc_diff_rows[i], self.T[i],
                                                             self.wave_diff[i]) for i in range(n)])
                 self.hop = int(self.fs * (self.frame_period * 0.001))
                 self.pcm_diff = None
                 if pcm:
-                    self.pcm_diff_all = torch.zeros(int(xo[-1]), dtype=torch.int16, device=dev)
-                    self.pcm_diff = [cut(self.pcm_diff_all, xo, i) for i in range(n)]
+                    self.pcm_diff_all = torch.zeros(samples.total, dtype=torch.int16, device=dev)
+                    self.pcm_diff = samples.views(self.pcm_diff_all)
                     self.j_fin_diff = _lib.job_array(_lib.FinishJob, [(self.wave_diff[i], self.x[i].numel(), 0, self.pcm_diff[i])
                                                                       for i in range(n)])
             self.gv_status, self.gv_strength = None, float(gv_strength)
@@ -551,20 +505,18 @@ class ConvertWave:
             if self.gv_strength > 0 and gmm is not None:
                 if gv_stats is None:
                     raise ValueError('global variance: gv_strength > 0 needs gv_stats')
-                self.gv = (gv_stats if torch.is_tensor(gv_stats) else
-                           torch.from_numpy(np.ascontiguousarray(gv_stats, dtype=np.float64))).to(dev)
+                self.gv = to_device(gv_stats, dev, dtype=np.float64).to(dev)     # (.to: a tensor may come from the host)
                 if self.gv.shape != (order + 1,) or self.gv.dtype != torch.float64:
                     raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
                 self.gv_moments = torch.empty((n, order + 1, 3), **f64)
                 self.gv_status = torch.zeros(n, dtype=torch.int32, device=dev)
-                conv = [cut(self.mc_conv, off, i) for i in range(n)]
                 self.j_gv_mom = _lib.job_array(_lib.GvMatrix, [(conv[i], self.T[i]) for i in range(n)])
                 self.j_gv = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], conv[i], conv[i])
                                                         for i in range(n)])
                 if self.diff:
                     self.j_gv_diff = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], self.mc_diff_rows[i],
                                                                   self.mc_diff_rows[i]) for i in range(n)])
-            self.j_render = _lib.synth_job_array([(self.plan[i], sp[i], ap[i], self.wave[i]) for i in range(n)])
+            self.j_render = _lib.synth_job_array([(self.plan[i], spec[i], ap[i], self.wave[i]) for i in range(n)])
         self.frames = int(sum(self.T))
 
     def run(self):
@@ -606,7 +558,6 @@ class ConvertWave:
                 chk(lib.kwy_mc2sp_dev(h, _p(self.mc_conv), self.rows, order, self.alpha, fft, _p(self.sp_conv)))
             ls.main.wait_stream(ls.side)
             chk(lib.kwy_synth_render_batch_dev(h, self.j_render, n, fft, self.frame_period, fs, float(fs)))
-            from .pipeline import PIECE_CEILING
             if self.pcm is not None:
                 chk(lib.kwy_finish_pcm16_batch_dev(h, self.j_fin, n, fs, 1, PIECE_CEILING, 1, PIECE_CEILING))
             if self.diff:
@@ -623,13 +574,11 @@ class ConvertWave:
         return [(self.x[i], self.x[i].numel(), self.mc_diff_rows[i], self.T[i], self.wave_diff[i]) for i in range(self.n)]
 
     def run_mlsa(self, ctx):
-        from .pipeline import PIECE_CEILING
         chk = lambda rc: _lib.check(ctx, rc)  # noqa: E731
         chk(lib.kwy_mlsa_filter_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, 4, self.hop, 1))
         self.finish_diff(ctx)
 
     def finish_diff(self, ctx):
-        from .pipeline import PIECE_CEILING
         if self.pcm_diff is not None:
             _lib.check(ctx, lib.kwy_finish_pcm16_batch_dev(ctx.handle, self.j_fin_diff, self.n, self.fs, 0, PIECE_CEILING, 1,
                                                            PIECE_CEILING))
@@ -714,9 +663,8 @@ class StreamPool:
         queues = os.environ.get('GPU_MAX_HW_QUEUES')
         if n > 4 and queues is None:
             warnings.warn(f'{n} streams, but GPU_MAX_HW_QUEUES is not set: the HIP runtime maps all streams onto 4 '
-                          f'hardware queues and most of the overlap between utterances is lost (1.43 M instead of '
-                          f'1.91 M frames/s in bench.py); export it before the first HIP call', RuntimeWarning,
-                          stacklevel=2)
+                          f'hardware queues and most of the overlap between utterances is lost; export it before the '
+                          f'first HIP call', RuntimeWarning, stacklevel=2)
         self.streams = [torch.cuda.Stream(device=self.dev) for _ in range(max(1, n))]
         self.contexts = [_lib.Context(device_index, stream=s.cuda_stream) for s in self.streams]
 
@@ -782,7 +730,7 @@ class _upload_ahead:
         self.halt = threading.Event()
 
         def side_up(side):
-            return tuple(a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in side)
+            return tuple(to_device(a, dev) for a in side)
 
         def hand(item):
             while not self.halt.is_set():
@@ -925,7 +873,7 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
             for k in range(n_pairs):
                 sil = silence_for(done[0] + k) if silence_for is not None else ahead.get()
                 for dst, a in zip(rows[4 * k:4 * k + 4], sil):
-                    dst.copy_(a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a)), non_blocking=True)
+                    dst.copy_(to_device(a, None), non_blocking=True)
         else:
             rng.abs_normal_blocks(scale, rows, ctx=ls.ctx)
         done[0] += n_pairs

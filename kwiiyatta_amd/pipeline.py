@@ -22,23 +22,18 @@ followed by `kwiiyatta`'s conversion):
 
 torch is used for device memory, streams and strided copies only.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, c_vp
+from ._blocks import Ragged, p as _p, to_device
+from ._lib import lib
 
 EPS = 2.220446049250313e-16
 SAFE_GUARD_MINIMUM = 1e-12
 PAD_LEN = 100
 POWER_WEIGHT, POWER_THRESHOLD, VUV_WEIGHT = 9.4, 1.636, 9.0
 PIECE_CEILING = float(np.power(10, -1 / 10))          # normalize_data's default peak_lv = -1 (kwiiyatta/wavfile.py:8-12)
-
-
-def _p(t):
-    return c_vp(t.data_ptr())
 
 
 class DeviceGMM:
@@ -68,24 +63,29 @@ class DeviceGMM:
 
 
 class _Side:
-    """Buffers of one analysed utterance, stored with PAD_LEN silent frames on both ends."""
+    """Buffers of one analysed utterance ((x, f0, t): numpy arrays or device tensors), stored with PAD_LEN silent
+    frames on both ends.  What differs between the conversion pair and the training pair stays with them: PairPipeline
+    copies the f0 track into the padded one and sizes the feature rows for the whole utterance at once; TrainPair
+    (corpus.py) does both in `align()`, at the trimmed length, and adds its trim-length word."""
 
-    def __init__(self, x, f0, t, fs, K, order, dev):
+    def __init__(self, x, f0, t, K, dev, sp_alloc=torch.zeros):
+        """sp_alloc: torch.zeros, or torch.empty where every row of the padded envelope is written before it is read"""
         self.N, self.T = len(x), len(f0)
         self.Tp = self.T + 2 * PAD_LEN
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.x = torch.from_numpy(x).to(dev)
-        self.f0 = torch.from_numpy(f0).to(dev)
-        self.t = torch.from_numpy(t).to(dev)
+        self.f64 = f64 = dict(dtype=torch.float64, device=dev)
+        self.x, self.f0, self.t = (to_device(a, dev) for a in (x, f0, t))
         self.f0_pad = torch.zeros(self.Tp, **f64)
-        self.f0_pad[PAD_LEN:PAD_LEN + self.T] = self.f0
-        self.sp_pad = torch.zeros((self.Tp, K), **f64)
+        self.sp_pad = sp_alloc((self.Tp, K), **f64)
         self.ap_pad = torch.full((self.Tp, K), 1 - SAFE_GUARD_MINIMUM, **f64)
-        self.mc_pad = torch.empty((self.Tp, order + 1), **f64)
-        self.feat = torch.empty((self.Tp, order + 2), **f64)
         # views of the un-padded middle part (the kernels write straight into them)
         self.sp = self.sp_pad[PAD_LEN:PAD_LEN + self.T]
         self.ap = self.ap_pad[PAD_LEN:PAD_LEN + self.T]
+
+    def feature_rows(self, Tp, order):
+        """mel-cepstra and DTW features of the first `Tp` padded rows (henceforth the side's `Tp`)"""
+        self.Tp = Tp
+        self.mc_pad = torch.empty((Tp, order + 1), **self.f64)
+        self.feat = torch.empty((Tp, order + 2), **self.f64)
 
     def silence_rows(self):
         return self.sp_pad[:PAD_LEN], self.sp_pad[PAD_LEN + self.T:]
@@ -187,8 +187,10 @@ class PairPipeline(_Graphed):
         self.gmm_model = gmm.model(diff=False)
         f64 = dict(dtype=torch.float64, device=self.dev)
         with torch.cuda.stream(self.stream):
-            self.src = _Side(*source, self.fs, self.K, order, self.dev)
-            self.tgt = _Side(*target, self.fs, self.K, order, self.dev)
+            self.src, self.tgt = _Side(*source, self.K, self.dev), _Side(*target, self.K, self.dev)
+            for s in (self.src, self.tgt):
+                s.f0_pad[PAD_LEN:PAD_LEN + s.T] = s.f0
+                s.feature_rows(s.Tp, order)
             Tt = self.tgt.T
             cap = self.src.Tp + self.tgt.Tp + 2
             self.path = torch.zeros((cap, 2), dtype=torch.int32, device=self.dev)
@@ -213,7 +215,7 @@ class PairPipeline(_Graphed):
                 silence = [draw_silence(self.fs, self.K) for _ in range(4)]
             rows = self.src.silence_rows() + self.tgt.silence_rows()
             for dst, sil in zip(rows, silence):
-                dst.copy_(torch.from_numpy(np.ascontiguousarray(sil)))
+                dst.copy_(to_device(sil, None))
         self.stream.synchronize()
         self.frames = self.src.T   # the metric counts source frames
 
@@ -301,6 +303,15 @@ class PairPipeline(_Graphed):
         self.ctx.sync()
 
 
+def f0_jobs(x, t, f0_dio, f0, status):
+    """The job arrays of the f0 extraction of a wave of bare waveforms `x` (lists of per-utterance views): DIO's
+    (kwy_dio_batch_dev: frame times into `t`, its track into `f0_dio`, one word of `status` per utterance) and
+    StoneMask's (kwy_stonemask_batch_dev: the refined track into `f0`)"""
+    n = len(x)
+    j_dio = _lib.job_array(_lib.F0Job, [(x[i], x[i].numel(), t[i], f0_dio[i], status[i:i + 1]) for i in range(n)])
+    return j_dio, _lib.utterance_array([(x[i], t[i], f0_dio[i], f0[i]) for i in range(n)])
+
+
 class _Wave:
     """The pairs of one wave of a PairBatchPipeline: two streams with a library context each, and the wave's buffers
     as CONTIGUOUS blocks -- the padded features of all its utterances form one (rows, K) matrix, so the row-wise
@@ -328,16 +339,17 @@ class _Wave:
         self.T = [int(lib.kwy_dio_frames(fs, len(s[0]), owner.frame_period)) for s in sides] if wav_in else \
             [len(s[1]) for s in sides]
         self.Tp = [t + 2 * PAD_LEN for t in self.T]
-        cat = lambda k: torch.from_numpy(np.concatenate([np.ascontiguousarray(s[k], dtype=np.float64)  # noqa: E731
-                                                         for s in sides])).to(dev)
+        # the layouts of the wave's blocks: samples, frames and padded rows per utterance
+        xl, tl, pl = Ragged(self.N), Ragged(self.T), Ragged(self.Tp)
+        cat = lambda k: to_device(np.concatenate([np.asarray(s[k], dtype=np.float64) for s in sides]), dev)  # noqa: E731
         with torch.cuda.stream(self.stream):
             self.x_all = cat(0)
             if wav_in:
-                self.t_all = torch.empty(int(sum(self.T)), **f64)
-                self.f0_all = torch.empty(int(sum(self.T)), **f64)        # DIO's track, before the refinement
+                self.t_all = torch.empty(tl.total, **f64)
+                self.f0_all = torch.empty(tl.total, **f64)        # DIO's track, before the refinement
             else:
                 self.f0_all, self.t_all = cat(1), cat(2)
-            rows = int(sum(self.Tp))
+            rows = pl.total
             fused = owner.fused_mcep
             if not fused:
                 self.sp_pad = torch.zeros((rows, K), **f64)
@@ -345,33 +357,22 @@ class _Wave:
             self.f0_pad = torch.zeros(rows, **f64)
             self.mc_pad = torch.empty((rows, order + 1), **f64)
             self.feat = torch.empty((rows, order + 2), **f64)
-            xo = np.concatenate(([0], np.cumsum(self.N)))
-            to = np.concatenate(([0], np.cumsum(self.T)))
-            po = np.concatenate(([0], np.cumsum(self.Tp)))
-            cut = lambda a, o, i, lo=0, hi=0: a[int(o[i]) + lo:int(o[i + 1]) - hi]  # noqa: E731
             ns = len(sides)
-            self.x = [cut(self.x_all, xo, i) for i in range(ns)]
-            self.f0 = [cut(self.f0_all, to, i) for i in range(ns)]
-            self.t = [cut(self.t_all, to, i) for i in range(ns)]
-            self.ap = [cut(self.ap_pad, po, i, PAD_LEN, PAD_LEN) for i in range(ns)]
+            self.x, self.f0, self.t = xl.views(self.x_all), tl.views(self.f0_all), tl.views(self.t_all)
+            P = PAD_LEN                     # views(block, P, P): the un-padded middle parts
+            self.ap = pl.views(self.ap_pad, P, P)
             if not fused:
-                self.sp = [cut(self.sp_pad, po, i, PAD_LEN, PAD_LEN) for i in range(ns)]      # the un-padded middle parts
-                self.sp_p = [cut(self.sp_pad, po, i) for i in range(ns)]
-            self.ap_p = [cut(self.ap_pad, po, i) for i in range(ns)]
-            self.mc_p = [cut(self.mc_pad, po, i) for i in range(ns)]
-            self.f0_p = [cut(self.f0_pad, po, i) for i in range(ns)]
-            self.feat_p = [cut(self.feat, po, i) for i in range(ns)]
+                self.sp, self.sp_p = pl.views(self.sp_pad, P, P), pl.views(self.sp_pad)
+            self.ap_p, self.mc_p, self.f0_p, self.feat_p = (pl.views(b) for b in (self.ap_pad, self.mc_pad, self.f0_pad,
+                                                                                  self.feat))
             if wav_in:
                 # StoneMask writes the refined track straight into the padded f0 rows; every consumer reads it there
-                self.f0_dio = self.f0
-                self.f0 = [self.f0_p[i][PAD_LEN:PAD_LEN + self.T[i]] for i in range(ns)]
+                self.f0_dio, self.f0 = self.f0, pl.views(self.f0_pad, P, P)
                 self.f0_status = torch.zeros(ns, dtype=torch.int32, device=dev)
-                self.j_dio = _lib.job_array(_lib.F0Job, [(self.x[i], self.N[i], self.t[i], self.f0_dio[i],
-                                                          self.f0_status[i:i + 1]) for i in range(ns)])
-                self.j_sm = _lib.utterance_array([(self.x[i], self.t[i], self.f0_dio[i], self.f0[i]) for i in range(ns)])
+                self.j_dio, self.j_sm = f0_jobs(self.x, self.t, self.f0_dio, self.f0, self.f0_status)
             else:
-                for i in range(ns):
-                    self.f0_p[i][PAD_LEN:PAD_LEN + self.T[i]] = self.f0[i]
+                for dst, f0 in zip(pl.views(self.f0_pad, P, P), self.f0):
+                    dst.copy_(f0)
             # pad rows in the reference's order of draws: source head, source tail, target head, target tail
             if not fused:
                 self.pad_rows = [blk for i in range(ns) for blk in (self.sp_p[i][:PAD_LEN], self.sp_p[i][PAD_LEN + self.T[i]:])]
@@ -379,30 +380,31 @@ class _Wave:
                 # No envelope rows at all: CheapTrick hands over mel-cepstra (kwy_cheaptrick_mcep_batch_dev) straight into
                 # the padded rows' middle parts; the pad SPECTRA live in one block of their own, their mel-cepstra
                 # (sp2mc over 2 x 100 rows per side) are copied to the rows around
-                self.pads_sp = torch.zeros((2 * ns * PAD_LEN, K), **f64)
-                self.pads_mc = torch.empty((2 * ns * PAD_LEN, order + 1), **f64)
-                self.pad_rows = [self.pads_sp[b * PAD_LEN:(b + 1) * PAD_LEN] for b in range(2 * ns)]
+                heads_tails = Ragged([PAD_LEN] * (2 * ns))
+                self.pads_sp = torch.zeros((heads_tails.total, K), **f64)
+                self.pads_mc = torch.empty((heads_tails.total, order + 1), **f64)
+                self.pad_rows = heads_tails.views(self.pads_sp)
                 self.pad_idx = torch.arange(PAD_LEN, dtype=torch.int32, device=dev)
-                pm = lambda b: self.pads_mc[b * PAD_LEN:(b + 1) * PAD_LEN]  # noqa: E731
+                pm = heads_tails.views(self.pads_mc)
                 self.j_padmc = _lib.job_array(_lib.GatherJob, [row for i in range(ns) for row in (
-                    (pm(2 * i), PAD_LEN, self.pad_idx, PAD_LEN, self.mc_p[i][:PAD_LEN]),
-                    (pm(2 * i + 1), PAD_LEN, self.pad_idx, PAD_LEN, self.mc_p[i][PAD_LEN + self.T[i]:]))])
+                    (pm[2 * i], PAD_LEN, self.pad_idx, PAD_LEN, self.mc_p[i][:PAD_LEN]),
+                    (pm[2 * i + 1], PAD_LEN, self.pad_idx, PAD_LEN, self.mc_p[i][PAD_LEN + self.T[i]:]))])
             # per pair, on the target's time axis
             Tt = [self.T[2 * k + 1] for k in range(self.n)]
             self.Tt = Tt
-            ao = np.concatenate(([0], np.cumsum(Tt)))
-            arows = int(ao[-1])
+            al = Ragged(Tt)
+            arows = al.total
             self.ap_al = torch.empty((arows, K), **f64)
             self.mc_al = torch.empty((arows, order + 1), **f64)
             self.mc_conv = torch.empty((arows, order + 1), **f64)
             self.sp_conv = torch.empty((arows, K), **f64)
             self.ylen = [lib.kwy_synth_length(t, owner.frame_period, fs) for t in Tt]
-            yo = np.concatenate(([0], np.cumsum(self.ylen)))
-            self.wave_all = torch.empty(int(yo[-1]), **f64)
-            self.wave = [cut(self.wave_all, yo, k) for k in range(self.n)]
+            self.wave_layout = yl = Ragged(self.ylen)       # (the feeders cut the same block on the host side)
+            self.wave_all = torch.empty(yl.total, **f64)
+            self.wave = yl.views(self.wave_all)
             if owner.pcm:         # the post-step and the 16-bit samples on the device (kwy_finish_pcm16_batch_dev)
-                self.pcm_all = torch.zeros(int(yo[-1]), dtype=torch.int16, device=dev)
-                self.pcm = [cut(self.pcm_all, yo, k) for k in range(self.n)]
+                self.pcm_all = torch.zeros(yl.total, dtype=torch.int16, device=dev)
+                self.pcm = yl.views(self.pcm_all)
                 self.j_fin = _lib.job_array(_lib.FinishJob, [(self.wave[k], self.ylen[k], Tt[k], self.pcm[k])
                                                              for k in range(self.n)])
             cap = [self.Tp[2 * k] + self.Tp[2 * k + 1] + 2 for k in range(self.n)]
@@ -412,25 +414,26 @@ class _Wave:
             self.idx = [torch.zeros(self.Tp[2 * k + 1], dtype=torch.int32, device=dev) for k in range(self.n)]
             self.n_idx = torch.zeros(self.n, dtype=torch.int64, device=dev)
             self.plan = [torch.empty(lib.kwy_synth_plan_bytes(y), dtype=torch.uint8, device=dev) for y in self.ylen]
-            one = lambda a, k: a[k:k + 1]  # noqa: E731
+            # the per-pair words (distance, path length, gathered rows) as one-element views, the aligned blocks per pair
+            dist, path_len, n_idx = (Ragged([1] * self.n).views(a) for a in (self.dist, self.path_len, self.n_idx))
+            ap_al, mc_al, mc_conv, sp_conv = (al.views(b) for b in (self.ap_al, self.mc_al, self.mc_conv, self.sp_conv))
             J = _lib.job_array
             both = range(ns)
-            self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i],
-                                                self.mc_p[i][PAD_LEN:PAD_LEN + self.T[i]] if fused else self.sp[i]) for i in both])
+            env_out = pl.views(self.mc_pad, P, P) if fused else self.sp
+            self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], env_out[i]) for i in both])
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], self.ap[i]) for i in both])
             self.j_feat = J(_lib.AlignJob, [(self.mc_p[i], self.f0_p[i], self.Tp[i], self.feat_p[i]) for i in both])
             self.j_dtw = J(_lib.DtwJob, [(self.feat_p[2 * k], self.Tp[2 * k], self.feat_p[2 * k + 1], self.Tp[2 * k + 1],
-                                          one(self.dist, k), self.path[k], one(self.path_len, k)) for k in range(self.n)])
-            self.j_proj = J(_lib.ProjectJob, [(self.path[k], one(self.path_len, k), self.idx[k], self.Tp[2 * k + 1],
-                                               one(self.n_idx, k)) for k in range(self.n)])
-            self.j_gap = J(_lib.GatherJob, [(self.ap_p[2 * k], self.Tp[2 * k], self.idx[k], Tt[k], cut(self.ap_al, ao, k))
+                                          dist[k], self.path[k], path_len[k]) for k in range(self.n)])
+            self.j_proj = J(_lib.ProjectJob, [(self.path[k], path_len[k], self.idx[k], self.Tp[2 * k + 1], n_idx[k])
+                                              for k in range(self.n)])
+            self.j_gap = J(_lib.GatherJob, [(self.ap_p[2 * k], self.Tp[2 * k], self.idx[k], Tt[k], ap_al[k])
                                             for k in range(self.n)])
-            self.j_gmc = J(_lib.GatherJob, [(self.mc_p[2 * k], self.Tp[2 * k], self.idx[k], Tt[k], cut(self.mc_al, ao, k))
+            self.j_gmc = J(_lib.GatherJob, [(self.mc_p[2 * k], self.Tp[2 * k], self.idx[k], Tt[k], mc_al[k])
                                             for k in range(self.n)])
-            self.j_conv = J(_lib.ConvertJob, [(cut(self.mc_al, ao, k), Tt[k], cut(self.mc_conv, ao, k)) for k in range(self.n)])
+            self.j_conv = J(_lib.ConvertJob, [(mc_al[k], Tt[k], mc_conv[k]) for k in range(self.n)])
             self.j_plan = J(_lib.SynthPlanJob, [(self.f0[2 * k + 1], Tt[k], self.ylen[k], self.plan[k]) for k in range(self.n)])
-            self.j_render = _lib.synth_job_array([(self.plan[k], cut(self.sp_conv, ao, k), cut(self.ap_al, ao, k), self.wave[k])
-                                                  for k in range(self.n)])
+            self.j_render = _lib.synth_job_array([(self.plan[k], sp_conv[k], ap_al[k], self.wave[k]) for k in range(self.n)])
         self.rows, self.arows = rows, arows
         self.frames = sum(self.T[0::2])
 
@@ -457,8 +460,8 @@ class PairBatchPipeline(_Graphed):
     pads are `silence` (4 blocks per pair) or drawn here once from numpy's global generator, as PairPipeline does.
 
     rng_place: where the draw runs -- 'side' (default: at the head of the first wave's side stream, in front of its
-    D4C; measured at 32 pairs: 29.7 ms per step against 29.4 without any draw), 'head' (on the main stream before the
-    fork: 30.0), 'own' (the generator's own stream as a fifth branch of the graph: 31.8).
+    D4C; measured at 32 pairs: 29.7 ms per step against 29.4 without any draw) or 'head' (on the main stream before the
+    fork: 30.0).  (A third place, the generator's own stream as a fifth branch of the graph, took 31.8 ms and is gone.)
     serial: everything on ONE stream, kernel after kernel (for per-kernel timing).
 
     wav_in: the pairs are bare waveforms (or (x, ...) tuples whose f0 is ignored): DIO + StoneMask of both sides run at
@@ -489,6 +492,8 @@ class PairBatchPipeline(_Graphed):
         assert gmm.D2 == 6 * order
         self.gmm_model = gmm.model(diff=False)
         self.rng = rng
+        if rng_place not in ('side', 'head'):
+            raise ValueError(f"PairBatchPipeline: rng_place must be 'side' or 'head', not {rng_place!r}")
         self.rng_place = rng_place
         pairs = list(pairs)
         nw = max(1, min(int(waves), len(pairs)))
@@ -509,7 +514,7 @@ class PairBatchPipeline(_Graphed):
                 silence = [draw_silence(self.fs, self.K) for _ in range(4 * len(pairs))]
             with torch.cuda.stream(self.stream):
                 for dst, sil in zip(self.pad_rows, silence):
-                    dst.copy_(torch.from_numpy(np.ascontiguousarray(sil)))
+                    dst.copy_(to_device(sil, None))
         for wv in self.waves:
             wv.stream.synchronize()
         self.frames = sum(wv.frames for wv in self.waves)
@@ -539,20 +544,14 @@ class PairBatchPipeline(_Graphed):
             for c in (wv.ctx, wv.side_ctx):
                 if not any(c is o for o in cs):
                     cs.append(c)
-        return cs + ([self.rng.ctx] if self.rng is not None and self.rng_place == 'own' else [])
+        return cs
 
     def run(self):
         fs, fft, K, order = self.fs, self.fft, self.K, self.order
         origin = self.stream
         pads = None
         with torch.cuda.stream(origin):
-            if self.rng is not None and self.rng_place == 'own':
-                # ONE draw for the step, on the generator's own stream: the pads are needed first by sp2mc, behind
-                # CheapTrick, which the draw overlaps with
-                self.rng.stream.wait_stream(origin)
-                self.rng.abs_normal_blocks(EPS / fs, self.pad_rows)
-                pads = self.rng.record_event()
-            elif self.rng is not None and self.rng_place == 'head':
+            if self.rng is not None and self.rng_place == 'head':
                 self.rng.abs_normal_blocks(EPS / fs, self.pad_rows, ctx=self.ctx)
             if self.wav_in:
                 # The f0 tracks of ALL waves first, on the origin stream, then the fork.  (With the extraction at the
@@ -609,8 +608,6 @@ class PairBatchPipeline(_Graphed):
             for wv in self.waves:
                 if wv.stream is not origin:
                     origin.wait_stream(wv.stream)
-            if self.rng is not None and self.rng_place == 'own':
-                origin.wait_stream(self.rng.stream)
 
     def sync(self):
         for wv in self.waves:
@@ -650,10 +647,8 @@ class UtterancePipeline(_Graphed):
             raise ValueError('UtterancePipeline.load: shape differs from the pipeline\'s')
         with torch.cuda.stream(self.stream):
             for dst, src in ((self.x, x), (self.f0, f0), (self.t, t)):
-                if torch.is_tensor(src):
-                    src.record_stream(self.stream)      # (the caller may drop it while the copy is still queued)
-                dst.copy_(src if torch.is_tensor(src) else torch.from_numpy(np.ascontiguousarray(src)),
-                          non_blocking=True)
+                # (a caller's tensor is recorded: it may be dropped while the copy is still queued)
+                dst.copy_(to_device(src, None, (self.stream,)), non_blocking=True)
 
     def run(self):
         h, fs, fft = self.ctx.handle, self.fs, self.fft
@@ -692,20 +687,17 @@ class HostFeeder:
         dev = self.pipes[0].dev
         self.up = up if up is not None else torch.cuda.Stream(device=dev)
         self.down = down if down is not None else torch.cuda.Stream(device=dev)
-        n_in = [(p.src.x.numel(), p.tgt.x.numel()) for p in self.pipes]
-        n_out = [p.wave.numel() for p in self.pipes]
-        self.in_off = np.concatenate(([0], np.cumsum([a + b for a, b in n_in]))).astype(np.int64)
-        self.out_off = np.concatenate(([0], np.cumsum(n_out))).astype(np.int64)
+        # the staging blocks: items 2 i and 2 i + 1 of the input are pipeline i's source and target waveform
+        self.lay_in = Ragged([s.x.numel() for p in self.pipes for s in (p.src, p.tgt)])
+        self.lay_out = Ragged([p.wave.numel() for p in self.pipes])
         f64 = dict(dtype=torch.float64)
-        self.host_in = torch.empty(int(self.in_off[-1]), **f64).pin_memory()
-        self.host_out = [torch.empty(int(self.out_off[-1]), **f64).pin_memory() for _ in range(2)]
+        self.host_in = torch.empty(self.lay_in.total, **f64).pin_memory()
+        self.host_out = [torch.empty(self.lay_out.total, **f64).pin_memory() for _ in range(2)]
         for i, p in enumerate(self.pipes):
-            a = int(self.in_off[i])
-            self.host_in[a:a + n_in[i][0]].copy_(p.src.x)
-            self.host_in[a + n_in[i][0]:a + n_in[i][0] + n_in[i][1]].copy_(p.tgt.x)
-        self.n_in = n_in
-        self.slots = [dict(dev_in=torch.empty(int(self.in_off[-1]), device=dev, **f64),
-                           dev_out=torch.empty(int(self.out_off[-1]), device=dev, **f64),
+            self.lay_in.view(self.host_in, 2 * i).copy_(p.src.x)
+            self.lay_in.view(self.host_in, 2 * i + 1).copy_(p.tgt.x)
+        self.slots = [dict(dev_in=torch.empty(self.lay_in.total, device=dev, **f64),
+                           dev_out=torch.empty(self.lay_out.total, device=dev, **f64),
                            taken=[], drained=None) for _ in range(2)]
         self.n = 0
 
@@ -722,12 +714,10 @@ class HostFeeder:
         sl['taken'] = []
         done = []
         for i, p in enumerate(self.pipes):
-            a, (ns, nt) = int(self.in_off[i]), self.n_in[i]
-            o = int(self.out_off[i])
             p.stream.wait_event(arrived)
             with torch.cuda.stream(p.stream):
-                torch.mul(sl['dev_in'][a:a + ns], 1.0, out=p.src.x)
-                torch.mul(sl['dev_in'][a + ns:a + ns + nt], 1.0, out=p.tgt.x)
+                torch.mul(self.lay_in.view(sl['dev_in'], 2 * i), 1.0, out=p.src.x)
+                torch.mul(self.lay_in.view(sl['dev_in'], 2 * i + 1), 1.0, out=p.tgt.x)
                 ev = torch.cuda.Event()
                 ev.record(p.stream)
                 sl['taken'].append(ev)
@@ -735,7 +725,7 @@ class HostFeeder:
             if sl['drained'] is not None:
                 p.stream.wait_event(sl['drained'])        # the download of two steps ago has left this slot
             with torch.cuda.stream(p.stream):
-                torch.mul(p.wave, 1.0, out=sl['dev_out'][o:o + p.wave.numel()])
+                torch.mul(p.wave, 1.0, out=self.lay_out.view(sl['dev_out'], i))
                 ev = torch.cuda.Event()
                 ev.record(p.stream)
                 done.append(ev)
@@ -749,7 +739,7 @@ class HostFeeder:
     def result(self, i):
         """pipeline i's waveform of the last step (pinned host memory; call sync() first)"""
         k = (self.n - 1) & 1
-        return self.host_out[k][int(self.out_off[i]):int(self.out_off[i + 1])]
+        return self.lay_out.view(self.host_out[k], i)
 
     def sync(self):
         for p in self.pipes:
@@ -774,17 +764,15 @@ class BatchHostFeeder:
         self.pipe = pipe
         dev = pipe.dev
         self.up, self.down = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-        n_in = [wv.x_all.numel() for wv in pipe.waves]
-        n_out = [wv.wave_all.numel() for wv in pipe.waves]
-        self.in_off = np.concatenate(([0], np.cumsum(n_in))).astype(np.int64)
-        self.out_off = np.concatenate(([0], np.cumsum(n_out))).astype(np.int64)
+        self.lay_in = Ragged([wv.x_all.numel() for wv in pipe.waves])         # one item per wave, both ways
+        self.lay_out = Ragged([wv.wave_all.numel() for wv in pipe.waves])
         f64 = dict(dtype=torch.float64)
-        self.host_in = torch.empty(int(self.in_off[-1]), **f64).pin_memory()
-        self.host_out = [torch.empty(int(self.out_off[-1]), **f64).pin_memory() for _ in range(2)]
-        for w, wv in enumerate(pipe.waves):
-            self.host_in[int(self.in_off[w]):int(self.in_off[w + 1])].copy_(wv.x_all)
-        self.slots = [dict(dev_in=torch.empty(int(self.in_off[-1]), device=dev, **f64),
-                           dev_out=torch.empty(int(self.out_off[-1]), device=dev, **f64),
+        self.host_in = torch.empty(self.lay_in.total, **f64).pin_memory()
+        self.host_out = [torch.empty(self.lay_out.total, **f64).pin_memory() for _ in range(2)]
+        for src, wv in zip(self.lay_in.views(self.host_in), pipe.waves):
+            src.copy_(wv.x_all)
+        self.slots = [dict(dev_in=torch.empty(self.lay_in.total, device=dev, **f64),
+                           dev_out=torch.empty(self.lay_out.total, device=dev, **f64),
                            taken=None, drained=None) for _ in range(2)]
         self.n = 0
 
@@ -802,7 +790,7 @@ class BatchHostFeeder:
         h = p.ctx.handle
         with torch.cuda.stream(p.stream):
             for w, wv in enumerate(p.waves):
-                _lib.check(p.ctx, lib.kwy_copy_dev(h, _p(wv.x_all), c_vp(sl['dev_in'].data_ptr() + 8 * int(self.in_off[w])),
+                _lib.check(p.ctx, lib.kwy_copy_dev(h, _p(wv.x_all), _p(self.lay_in.view(sl['dev_in'], w)),
                                                    8 * wv.x_all.numel()))
             sl['taken'] = torch.cuda.Event()
             sl['taken'].record(p.stream)
@@ -811,7 +799,7 @@ class BatchHostFeeder:
             p.stream.wait_event(sl['drained'])            # the download of two steps ago has left this slot
         with torch.cuda.stream(p.stream):
             for w, wv in enumerate(p.waves):
-                _lib.check(p.ctx, lib.kwy_copy_dev(h, c_vp(sl['dev_out'].data_ptr() + 8 * int(self.out_off[w])), _p(wv.wave_all),
+                _lib.check(p.ctx, lib.kwy_copy_dev(h, _p(self.lay_out.view(sl['dev_out'], w)), _p(wv.wave_all),
                                                    8 * wv.wave_all.numel()))
             done = torch.cuda.Event()
             done.record(p.stream)
@@ -824,9 +812,8 @@ class BatchHostFeeder:
     def result(self, k):
         """pair k's waveform of the last step (pinned host memory; call sync() first)"""
         w, i = self.pipe.where[k]
-        wv = self.pipe.waves[w]
-        off = int(self.out_off[w]) + int(sum(wv.ylen[:i]))
-        return self.host_out[(self.n - 1) & 1][off:off + wv.ylen[i]]
+        block = self.lay_out.view(self.host_out[(self.n - 1) & 1], w)       # the wave's `wave_all`, cut as the wave cuts it
+        return self.pipe.waves[w].wave_layout.view(block, i)
 
     def sync(self):
         self.pipe.sync()
