@@ -313,6 +313,68 @@ int kwy_gv_postfilter_dev(kwy_ctx *ctx, const double *x, int64_t rows, int cols,
 int kwy_gv_postfilter_batch_dev(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col,
                                 const double *gv, double strength, int32_t *status);
 
+/* ---- objective evaluation ------------------------------------------------------------- */
+/* The reference has no counterpart: it compares features only in its tests (tests/feature.py: calc_feature_diffs).
+ * These entries add the measures voice-conversion work reports on held-out parallel utterances, taken along an
+ * alignment (the index lists of kwy_align_even_dev, or any other):
+ *   mel-cepstral distortion (Kubichek 1993), per selected row t
+ *     mcd[t] = (10 / ln 10) * sqrt(2 * sum_{d = first_col .. cols-1} (a[ia[t], d] - b[ib[t], d])^2)      dB
+ *   f0 error: 1200 * log2(fa / fb) cents over the rows where both tracks are voiced (f0 > 0); its root mean square is
+ *     sqrt(M2 / n + mean^2)
+ *   voicing error: the confusion counts VV, VU, UV, UU (a voiced / b voiced, a voiced / b unvoiced, ...)
+ * Row t of a job reads row idx_a[t] - off_a of a and row idx_b[t] - off_b of b (a NULL list is the identity), so that
+ * indices into a padded block can address an unpadded one; a row that falls outside either side this way is not a
+ * row of the measure and is passed over.  No gathered copies are made.  The row count is `rows`, or
+ * -- _dev forms only -- the device word n_dev[0] clamped to [0, rows] (kwy_align_even_dev's n_out; rows is then the
+ * capacity of the lists).  Moments are (n, mean, M2) over the rows that count, M2 the sum of squared deviations from
+ * the mean in a second pass; no such row gives (0, 0, 0).  Every reduction has a fixed order: a job's result depends
+ * on the job alone, not on the run nor on the other jobs of the call.  The _dev forms allocate nothing and do not
+ * synchronise (legal inside a stream capture); the host forms stage through HBM and synchronise. */
+typedef struct kwy_mcd_job {
+  const double *a;        /* a_rows rows of cols values, a_stride doubles apart (>= cols when there are rows to step over) */
+  int64_t a_rows, a_stride;
+  const double *b;        /* b_rows rows, b_stride doubles apart */
+  int64_t b_rows, b_stride;
+  const int32_t *idx_a;   /* rows indices, or NULL: t */
+  const int32_t *idx_b;
+  int64_t off_a, off_b;
+  int64_t rows;
+  const int64_t *n_dev;   /* device word with the row count, or NULL (always NULL in the host form) */
+  const double *mask;     /* or NULL.  Row t counts when mask[idx_b[t] * mask_stride] > 0: the UNSHIFTED b-side index */
+  int64_t mask_stride, mask_rows;
+  double *per_row;        /* rows values, written (or NULL): mcd[t], NaN for a row that does not count */
+} kwy_mcd_job;
+/* cols <= 64; first_col = 1 leaves the power coefficient out.  moments: count x 3 doubles, written.  status: one int32
+ * per job (or NULL): the rows left out because one of the coefficients first_col .. cols-1 is not finite on either
+ * side; rows whose mask is clear (or whose index lies outside the mask) are not examined. */
+int kwy_mcd(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int cols, int first_col, double *moments,
+            int32_t *status);
+int kwy_mcd_batch_dev(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int cols, int first_col, double *moments,
+                      int32_t *status);
+typedef struct kwy_f0_error_job {
+  const double *f0_a;     /* a_length values: the track under test */
+  int64_t a_length;
+  const double *f0_b;     /* b_length values: the track it is measured against */
+  int64_t b_length;
+  const int32_t *idx_a;   /* as in kwy_mcd_job */
+  const int32_t *idx_b;
+  int64_t off_a, off_b;
+  int64_t rows;
+  const int64_t *n_dev;
+} kwy_f0_error_job;
+/* counts: count x 4 int64 (VV, VU, UV, UU), written; moments: count x 3 doubles, written: the cents over the VV rows.
+ * status: one int32 per job (or NULL): the rows left out of every figure because an f0 value is negative or not
+ * finite.  The four counts and the status add up to the rows that lie inside both tracks. */
+int kwy_f0_error(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int count, int64_t *counts, double *moments,
+                 int32_t *status);
+int kwy_f0_error_batch_dev(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int count, int64_t *counts, double *moments,
+                           int32_t *status);
+/* count rows of width triples -> width triples (width <= 64): per column Chan's pairwise combination, a left fold in
+ * row order that skips n == 0 (kwy_logf0_moments_merge is this with width 1) -- the totals of a corpus, bit-equal
+ * however its utterances were grouped into calls */
+int kwy_moments_merge(kwy_ctx *ctx, const double *moments, int count, int width, double *out);
+int kwy_moments_merge_dev(kwy_ctx *ctx, const double *moments, int count, int width, double *out);
+
 /* ---- mel-cepstrum ---------------------------------------------------------------- */
 /* pysptk.sp2mc(spec, order, alpha) row-wise          kwiiyatta/vocoder/mcep.py:71
  * sp: T x K (K = fftlen/2+1), mc: T x (order+1). */

@@ -17,10 +17,13 @@ from .converter import MelCepstrumConverter, ParallelDataset, WavFileDataset, al
 from .filter import apply_mlsa_filter
 from .align import align
 from .config import Config
+from .evaluate_voice import evaluate, evaluate_pair
 
 name = "kwiiyatta_amd"
 
 __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFileDataset',
            'align_dataset', 'apply_mlsa_filter', 'Analyzer', 'Feature', 'MelCepstrum',
            'Synthesizer', 'align_even', 'analyze_wav', 'feature', 'pad_silence', 'resample',
-           'reshape', 'Wavdata', 'load_wav']
+           'reshape', 'Wavdata', 'load_wav',
+           # additions to the reference's names: objective evaluation of a trained converter (evaluate_voice.py)
+           'evaluate_pair', 'evaluate']

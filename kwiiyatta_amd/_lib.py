@@ -105,6 +105,12 @@ SIGNATURES = {
     'kwy_gv_postfilter': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
     'kwy_gv_postfilter_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp]),
     'kwy_gv_postfilter_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
+    'kwy_mcd': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    'kwy_mcd_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    'kwy_f0_error': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    'kwy_f0_error_batch_dev': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
+    'kwy_moments_merge': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
+    'kwy_moments_merge_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
     'kwy_synthesize': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl, c_i64,
                                c_vp]),
     'kwy_synthesize_dev': (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl,
@@ -260,6 +266,13 @@ F0MapJob = _job_struct('F0MapJob', 'kwy_f0_map_job: one f0 track through the f0 
 GvMatrix = _job_struct('GvMatrix', 'kwy_gv_matrix: one matrix of a column moments call', [('x', c_vp), ('rows', c_i64)])
 GvJob = _job_struct('GvJob', 'kwy_gv_job: one matrix through the global-variance postfilter',
                     [('x', c_vp), ('rows', c_i64), ('moments', c_vp), ('base', c_vp), ('out', c_vp)])
+McdJob = _job_struct('McdJob', 'kwy_mcd_job: one utterance of a mel-cepstral distortion call',
+                     [('a', c_vp), ('a_rows', c_i64), ('a_stride', c_i64), ('b', c_vp), ('b_rows', c_i64), ('b_stride', c_i64),
+                      ('idx_a', c_vp), ('idx_b', c_vp), ('off_a', c_i64), ('off_b', c_i64), ('rows', c_i64), ('n_dev', c_vp),
+                      ('mask', c_vp), ('mask_stride', c_i64), ('mask_rows', c_i64), ('per_row', c_vp)])
+F0ErrorJob = _job_struct('F0ErrorJob', 'kwy_f0_error_job: one pair of f0 tracks of an f0 / voicing error call',
+                         [('f0_a', c_vp), ('a_length', c_i64), ('f0_b', c_vp), ('b_length', c_i64), ('idx_a', c_vp),
+                          ('idx_b', c_vp), ('off_a', c_i64), ('off_b', c_i64), ('rows', c_i64), ('n_dev', c_vp)])
 SynthPlanJob = _job_struct('SynthPlanJob', 'kwy_synth_plan_job: the pulse placement of one utterance',
                            [('f0', c_vp), ('f0_length', c_i64), ('y_length', c_i64), ('plan', c_vp)])
 

@@ -160,8 +160,9 @@ class TrainWave:
 
         w.analyse()   enqueue CheapTrick + D4C of all utterances and their trim lengths; the lengths start their way
                       to the host (ONE read-back per wave)
-        w.finish(X, cursor, pads)   (waits for the lengths) enqueue padding, voicing, sp2mc, DTW features, FastDTW,
-                      strict filter + cut, deltas and the append of the joint rows behind the device-side cursor
+        w.finish(X, cursor, pads)   (waits for the lengths) enqueue padding, voicing, sp2mc, DTW features, FastDTW
+                      (`align`, which `EvalWave` shares), strict filter + cut, deltas and the append of the joint rows
+                      behind the device-side cursor
     """
 
     def __init__(self, ls, fs, pairs, order=24, radius=32, frame_period=5.0):
@@ -221,6 +222,20 @@ class TrainWave:
     def finish(self, X, cursor, pads):
         """pads(rows): fills the wave's pad rows -- a list of 4 n device views (source head, source tail, target
         head, target tail, pair after pair) -- on the main stream"""
+        Tp = self.align(pads)
+        ls, order, reg = self.ls, self.order, self.reg
+        with torch.cuda.stream(ls.main):
+            # dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames, append
+            _lib.check(ls.ctx, lib.kwy_train_rows_batch_dev(
+                ls.ctx.handle,
+                _lib.job_array(_lib.TrainJob, [(self.path[k], self.path_len[k:k + 1], reg(self.feat, 2 * k),
+                                                reg(self.feat, 2 * k + 1), reg(self.mc_pad, 2 * k), reg(self.mc_pad, 2 * k + 1),
+                                                Tp[2 * k], Tp[2 * k + 1], self.n_rows[k:k + 1]) for k in range(self.n)]),
+                self.n, order, 1, 1, 1, PAD_LEN, TRIM_EPS, _p(X), X.shape[0], _p(cursor)))
+
+    def align(self, pads):
+        """(waits for the trim lengths) enqueue padding, voicing, sp2mc, the DTW features and FastDTW of every pair;
+        sets `keep` and returns the padded lengths of the sides"""
         ls, fs, K, order, P, ns = self.ls, self.fs, self.K, self.order, PAD_LEN, 2 * self.n
         self.keep_ready.synchronize()
         keep = [int(v) for v in self.keep_host.tolist()]
@@ -244,13 +259,104 @@ class TrainWave:
                                                               Tp[2 * k + 1], self.dist[k:k + 1], self.path[k],
                                                               self.path_len[k:k + 1]) for k in range(self.n)]),
                                           self.n, order + 2, self.radius))
-            # dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames, append
-            chk(lib.kwy_train_rows_batch_dev(
-                h, J(_lib.TrainJob, [(self.path[k], self.path_len[k:k + 1], reg(self.feat, 2 * k), reg(self.feat, 2 * k + 1),
-                                      reg(self.mc_pad, 2 * k), reg(self.mc_pad, 2 * k + 1), Tp[2 * k], Tp[2 * k + 1],
-                                      self.n_rows[k:k + 1]) for k in range(self.n)]),
-                self.n, order, 1, 1, 1, P, TRIM_EPS, _p(X), X.shape[0], _p(cursor)))
         self.keep = keep
+        return Tp
+
+
+class EvalWave(TrainWave):
+    """<= 16 parallel pairs -> their evaluation figures (kwiiyatta_amd.evaluate_voice), in lockstep: analysed, trimmed,
+    padded and aligned exactly as TrainWave does it (`analyse`, `align`: the same pad rows in the same order), the
+    source's trimmed mel-cepstra converted on their own time axis as ConvertWave converts (the batched GMM + MLPG
+    entry, then the global-variance postfilter when asked for), and measured along the index lists that
+    kwy_align_even_dev leaves on the device (kwy_mcd_batch_dev, kwy_f0_error_batch_dev: no gathered copies, the row
+    counts stay device words).  Nothing is read back here: `measure` writes pair k's figures into row first + k of the
+    caller's tensors."""
+
+    def measure(self, pads, gmm, model, tot, first, frames='speech', gv=None, gv_strength=0.0, f0_stats=None,
+                transpose_key=0.0, per_frame=False):
+        """tot: the _EvalTotals of the corpus; gv / f0_stats: device tensors (order + 1 values / 4 values) or None"""
+        from .backend import distortion as dist
+        Tp = self.align(pads)
+        ls, fs, order, P, n, reg, keep = self.ls, self.fs, self.order, PAD_LEN, self.n, self.reg, self.keep
+        dev, cols = ls.dev, self.order + 1
+        f64 = dict(dtype=torch.float64, device=dev)
+        with torch.cuda.stream(ls.main):
+            h = ls.ctx.handle
+            chk = lambda rc: _lib.check(ls.ctx, rc)  # noqa: E731
+            J = _lib.job_array
+            # dtw_feature(strict=True) + align_even's cut: the index lists and their count stay on the device
+            cap = [self.path[k].shape[0] for k in range(n)]
+            self.idx_x = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
+            self.idx_y = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
+            n_sel = tot.aligned[first:first + n]
+            for k in range(n):
+                chk(lib.kwy_align_even_dev(h, _p(self.path[k]), _p(self.path_len[k:k + 1]), _p(reg(self.feat, 2 * k)),
+                                           _p(reg(self.feat, 2 * k + 1)), order + 2, 1, 1, 1, Tp[2 * k], Tp[2 * k + 1], P,
+                                           _p(self.idx_x[k]), _p(self.idx_y[k]), cap[k], _p(n_sel[k:k + 1])))
+            # the trimmed utterances inside their padded blocks
+            src_mc = [reg(self.mc_pad, 2 * k)[P:P + keep[2 * k]] for k in range(n)]
+            tgt_mc = [reg(self.mc_pad, 2 * k + 1)[P:P + keep[2 * k + 1]] for k in range(n)]
+            src_f0 = [self.f0[2 * k][:keep[2 * k]] for k in range(n)]
+            tgt_f0 = [self.f0[2 * k + 1][:keep[2 * k + 1]] for k in range(n)]
+            own = Ragged(keep[0::2])                    # the sources' own time axes, end to end
+            self.mc_conv = torch.empty((own.total, cols), **f64)
+            conv = own.views(self.mc_conv)
+            chk(lib.kwy_convert_mcep_batch_dev(h, J(_lib.ConvertJob, [(src_mc[k], keep[2 * k], conv[k]) for k in range(n)]),
+                                               n, order, gmm.M, _p(model)))
+            if gv is not None:
+                self.gv_moments = torch.empty((n, cols, 3), **f64)
+                chk(lib.kwy_column_moments_batch_dev(h, J(_lib.GvMatrix, [(conv[k], keep[2 * k]) for k in range(n)]), n,
+                                                     cols, _p(self.gv_moments)))
+                chk(lib.kwy_gv_postfilter_batch_dev(
+                    h, J(_lib.GvJob, [(conv[k], keep[2 * k], self.gv_moments[k], conv[k], conv[k]) for k in range(n)]),
+                    n, cols, 1, _p(gv), float(gv_strength), _p(tot.gv_status[first:first + n])))
+            if f0_stats is not None or transpose_key != 0:
+                from .backend.f0 import key_ratio
+                self.f0_mapped = torch.empty(own.total, **f64)
+                mapped = own.views(self.f0_mapped)
+                chk(lib.kwy_f0_map_batch_dev(h, J(_lib.F0MapJob, [(src_f0[k], keep[2 * k], mapped[k]) for k in range(n)]),
+                                             n, fs, None if f0_stats is None else f0_stats.data_ptr(),
+                                             key_ratio(transpose_key), _p(tot.f0_map_status[first:first + n])))
+                src_f0 = mapped
+            self.mcd_frames = [torch.empty(c, **f64) for c in cap] if per_frame else [None] * n
+            jobs = []
+            for k in range(n):
+                along = dict(idx_a=self.idx_x[k], idx_b=self.idx_y[k], off_a=P, off_b=P, rows=cap[k], n_dev=n_sel[k:k + 1],
+                             mask=reg(self.feat, 2 * k + 1)[:Tp[2 * k + 1], 0] if frames == 'speech' else None)
+                jobs.append(dist.mcd_job(conv[k], tgt_mc[k], per_row=self.mcd_frames[k], **along))
+                jobs.append(dist.mcd_job(src_mc[k], tgt_mc[k], **along))
+            dist.mcd_batch_dev(ls.ctx, jobs, cols, tot.mcd[first:first + n].view(-1, 3),
+                               tot.mcd_status[first:first + n].view(-1))
+            dist.f0_error_batch_dev(ls.ctx, [dist.f0_error_job(src_f0[k], tgt_f0[k], self.idx_x[k], self.idx_y[k], P, P,
+                                                               rows=cap[k], n_dev=n_sel[k:k + 1]) for k in range(n)],
+                                    tot.counts[first:first + n], tot.f0[first:first + n], tot.f0_status[first:first + n])
+
+
+class _EvalTotals:
+    """the figures of a corpus's pairs in HBM, a row per pair: the (n, mean, M2) triples of the distortion (converted,
+    unconverted source) and of the f0 error, the voicing counts, the aligned frames and the status words"""
+
+    def __init__(self, n_pairs, dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.mcd = torch.zeros((n_pairs, 2, 3), **f64)
+        self.f0 = torch.zeros((n_pairs, 3), **f64)
+        self.counts = torch.zeros((n_pairs, 4), dtype=torch.int64, device=dev)
+        self.aligned = torch.zeros(n_pairs, dtype=torch.int64, device=dev)
+        self.mcd_status, self.f0_status = torch.zeros((n_pairs, 2), **i32), torch.zeros(n_pairs, **i32)
+        self.gv_status, self.f0_map_status = torch.zeros(n_pairs, **i32), torch.zeros(n_pairs, **i32)
+
+    def read(self, ctx):
+        """(enqueued behind the waves on ctx's stream) the pooled triples from the merge kernel, then everything to the
+        host: (triples (n_pairs + 1, 3, 3) with the totals last, counts, aligned, status words (n_pairs, 5))"""
+        from .backend import distortion as dist
+        triples = torch.cat((self.mcd, self.f0[:, None]), dim=1).contiguous()
+        both = torch.cat((triples, torch.zeros_like(triples[:1])))
+        dist.merge_moments_dev(ctx, triples, both[-1])
+        status = torch.cat((self.mcd_status, self.f0_status[:, None], self.gv_status[:, None],
+                            self.f0_map_status[:, None]), dim=1)
+        whole = torch.cat((self.counts, self.aligned[:, None]), dim=1)
+        return both.cpu().numpy(), whole[:, :4].cpu().numpy(), whole[:, 4].cpu().numpy(), status.cpu().numpy()
 
 
 class ConvertPipeline(_Graphed):
@@ -1124,3 +1230,92 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
     _stream_batch(lambda u, st, ctx: UtterancePipeline(device_index, fs, u, frame_period=frame_period, stream=st,
                                                        ctx=ctx), utterances, pool, shapes_per_stream, keep)
     return res, frames
+
+
+def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_period=5.0, frames='speech', gv_stats=None,
+                   gv_strength=0.0, f0_stats=None, transpose_key=0.0, per_frame=False, converter_fs=None, lockstep=None,
+                   wave_pairs=16):
+    """Objective evaluation of the fitted mixture on parallel pairs, HBM-resident (what
+    kwiiyatta_amd.evaluate_voice.evaluate does pair by pair through the Python API): waves of `wave_pairs` pairs
+    through `EvalWave`.  pairs: ((x, f0, t), (x, f0, t)) triples as `build_training_matrix` takes them, all at the
+    sampling rate `fs` -- which must be the converter's: converter_fs (when given) != fs raises ValueError, such pairs
+    go through evaluate_voice.evaluate_pair, which resamples.  The silence pads are drawn from numpy's global
+    generator in training's order, so under np.random.seed a pair's alignment is the one training would use.
+    frames='speech': the distortion over the aligned frames whose target-side binarised power term is set; 'all': over
+    every aligned frame inside both utterances.  gv_stats / gv_strength, f0_stats / transpose_key: as in
+    `convert_batch`.  Returns (records, total): a dict per pair and one of the pooled figures -- the triples
+    mcd_moments, source_moments, f0_moments ((n, mean, M2); merged by kwy_moments_merge_dev for the total), counts
+    (VV, VU, UV, UU), aligned (frames of the alignment) and outside (those beyond either utterance) -- read back once,
+    after the last wave.  per_frame=True: a record also holds idx_x, idx_y (frame indices into the trimmed utterances)
+    and mcd_frames (per aligned frame, nan where not selected).  A value that is not finite raises ValueError."""
+    if frames not in ('speech', 'all'):
+        raise ValueError(f"frames must be 'speech' or 'all', not {frames!r}")
+    if converter_fs is not None and int(converter_fs) != int(fs):
+        raise ValueError(f'evaluate_batch: the pairs are at {fs} Hz, the converter at {converter_fs} Hz; pairs of another '
+                         f'sampling rate go through evaluate_voice.evaluate_pair')
+    if not 0.0 <= float(gv_strength) <= 1.0:
+        raise ValueError(f'global variance: strength {gv_strength!r} is outside [0, 1]')
+    if gv_strength > 0 and gv_stats is None:
+        raise ValueError('global variance: gv_strength > 0 needs gv_stats')
+    dev = torch.device('cuda', device_index)
+    zero = dict(mcd_moments=(0.0, 0.0, 0.0), source_moments=(0.0, 0.0, 0.0), f0_moments=(0.0, 0.0, 0.0),
+                counts=(0, 0, 0, 0), aligned=0, outside=0)
+    if not pairs:
+        return [], zero
+    ls = lockstep if lockstep is not None else _Lockstep(device_index)
+    dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
+    assert dg.D2 == 6 * order
+    wave_pairs = max(1, min(16, int(wave_pairs)))
+    K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
+    with torch.cuda.stream(ls.main):
+        model = dg.model(diff=False)
+        tot = _EvalTotals(len(pairs), dev)
+        gv = None
+        if gv_strength > 0:
+            gv = to_device(gv_stats, dev, dtype=np.float64).to(dev)
+            if gv.shape != (order + 1,) or gv.dtype != torch.float64:
+                raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
+        stats = None if f0_stats is None else torch.as_tensor(
+            f0_stats if torch.is_tensor(f0_stats) else list(f0_stats), dtype=torch.float64, device=dev)
+
+    def pads(rows):          # the reference's order of draws: source head, source tail, target head, target tail
+        for dst in rows:
+            dst.copy_(to_device(draw_silence(fs, K), None), non_blocking=True)
+    waves = []
+    for w0 in range(0, len(pairs), wave_pairs):
+        wave = EvalWave(ls, fs, pairs[w0:w0 + wave_pairs], order=order, radius=radius, frame_period=frame_period)
+        wave.analyse()
+        wave.measure(pads, dg, model, tot, w0, frames=frames, gv=gv, gv_strength=gv_strength, f0_stats=stats,
+                     transpose_key=float(transpose_key), per_frame=per_frame)
+        waves.append(wave)
+        if not per_frame:
+            while len(waves) > 2:
+                waves.pop(0)            # (its buffers: all uses are ordered on the main stream before reuse)
+    with torch.cuda.stream(ls.main):
+        triples, counts, aligned, status = tot.read(ls.ctx)
+    ls.sync()
+    if status[:, :3].any():
+        from .backend import distortion as dist
+        dist.check_status(status[:, :3].sum(axis=1), 'evaluation')
+    if gv is not None:
+        from .backend import gv as gvfilter
+        gvfilter.check_status(status[:, 3])
+    if stats is not None or transpose_key != 0:
+        from .backend.f0 import check_status
+        check_status(status[:, 4], fs)
+
+    def record(m, c, n_aligned):
+        c = tuple(int(v) for v in c)
+        return dict(mcd_moments=tuple(m[0].tolist()), source_moments=tuple(m[1].tolist()), f0_moments=tuple(m[2].tolist()),
+                    counts=c,
+                    aligned=int(n_aligned), outside=int(n_aligned) - sum(c))
+    records = [record(triples[i], counts[i], aligned[i]) for i in range(len(pairs))]
+    if per_frame:
+        i = 0
+        for wave in waves:
+            for k in range(wave.n):
+                n = records[i]['aligned']
+                records[i].update(idx_x=wave.idx_x[k][:n].cpu().numpy() - PAD_LEN, idx_y=wave.idx_y[k][:n].cpu().numpy() - PAD_LEN,
+                                  mcd_frames=wave.mcd_frames[k][:n].cpu().numpy())
+                i += 1
+    return records, record(triples[-1], counts.sum(axis=0), aligned.sum())

@@ -10,7 +10,8 @@
 // Reductions are deterministic: one workgroup per track, a thread's frames added in index order, then
 // kwy_block_sum (DPP over the 64 lanes of a wave, the waves' partial sums in wave order through LDS).  A track's
 // triple therefore depends on its own frames only -- not on the run, nor on the other tracks of the launch -- and
-// the corpus merge is a left fold of Chan's pairwise combination in index order on one lane.
+// the corpus merge is a left fold of Chan's pairwise combination in index order on one lane (k_moments_merge,
+// kwy_eval.hip).
 //
 // No kernel here allocates, synchronises or uses the context's arena: the _dev entries are legal inside a stream
 // capture.  The host entries stage through the arena and synchronise, as kwy_synthesize does.
@@ -73,27 +74,6 @@ __global__ __launch_bounds__(KWY_THREADS) void k_logf0_moments(f0m_tracks B) {
   }
 }
 
-// Chan et al.'s pairwise combination, a left fold over `count` triples in index order (one lane)
-__global__ __launch_bounds__(64) void k_logf0_merge(const double *__restrict__ m, int count, double *__restrict__ out) {
-  if (threadIdx.x != 0) return;
-  double n = 0.0, mean = 0.0, m2 = 0.0;
-  for (int i = 0; i < count; ++i) {
-    const double nb = m[3 * i], mb = m[3 * i + 1], m2b = m[3 * i + 2];
-    if (nb == 0.0) continue;
-    if (n == 0.0) {
-      n = nb; mean = mb; m2 = m2b;
-      continue;
-    }
-    const double nn = n + nb, delta = mb - mean;
-    mean = mean + delta * (nb / nn);
-    m2 = (m2 + m2b) + delta * delta * (n * nb / nn);
-    n = nn;
-  }
-  out[0] = n;
-  out[1] = mean;
-  out[2] = m2;
-}
-
 // one workgroup per track; stats == NULL: voiced f0 * ratio (the dialog's product, bit for bit)
 __global__ __launch_bounds__(KWY_THREADS) void k_f0_map(f0m_maps B, const double *__restrict__ stats, double ratio,
                                                          double limit) {
@@ -148,13 +128,9 @@ extern "C" int kwy_logf0_moments_batch_dev(kwy_ctx *ctx, const kwy_f0_track *tra
   return f0m_launch_moments(ctx, tracks, count, moments);
 }
 
+// the corpus merge: kwy_eval.hip's fold (Chan's pairwise combination, left to right) over one column of triples
 extern "C" int kwy_logf0_moments_merge_dev(kwy_ctx *ctx, const double *moments, int count, double *out) {
-  if (!ctx) return KWY_EINVAL;
-  if (!moments || count < 1 || !out) { ctx->err = "logf0_moments_merge: bad argument"; return KWY_EINVAL; }
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_PROF(ctx, "k_logf0_merge", hipLaunchKernelGGL(k_logf0_merge, dim3(1), dim3(64), 0, ctx->stream, moments, count, out));
-  KWY_HIP(hipGetLastError());
-  return KWY_OK;
+  return kwy_moments_merge_dev(ctx, moments, count, 1, out);
 }
 
 extern "C" int kwy_logf0_moments(kwy_ctx *ctx, const kwy_f0_track *tracks, int count, double *moments) {
@@ -179,16 +155,7 @@ extern "C" int kwy_logf0_moments(kwy_ctx *ctx, const kwy_f0_track *tracks, int c
 }
 
 extern "C" int kwy_logf0_moments_merge(kwy_ctx *ctx, const double *moments, int count, double *out) {
-  if (!ctx) return KWY_EINVAL;
-  if (!moments || count < 1 || !out) { ctx->err = "logf0_moments_merge: bad argument"; return KWY_EINVAL; }
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * 3 * (size_t)count) + kwy_pad(sizeof(double) * 3)));
-  double *dm = kwy_arena<double>(ctx, 3 * (size_t)count), *dout = kwy_arena<double>(ctx, 3);
-  KWY_HIP(hipMemcpyAsync(dm, moments, sizeof(double) * 3 * count, hipMemcpyHostToDevice, ctx->stream));
-  KWY_TRY(kwy_logf0_moments_merge_dev(ctx, dm, count, dout));
-  KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * 3, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return kwy_moments_merge(ctx, moments, count, 1, out);
 }
 
 static int f0m_check_maps(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, double ratio) {

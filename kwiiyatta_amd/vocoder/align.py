@@ -112,18 +112,25 @@ def align(feature, target, vuv='f0', strict=False, pad_silence=True, pad_len=100
     return feature[list(project_path_iter(path, trim=pad_silence, trim_len=pad_len))]
 
 
-def align_even(a, b, pad_silence=True, pad_len=100, **kwargs):
-    """both feature sets along the warping path (same length), without the silence pads"""
-    if pad_silence:
-        pad = _pkg().pad_silence
-        a, b = pad(a, pad_len), pad(b, pad_len)
+def even_indices(a, b, pad_len=None, **kwargs):
+    """the x and y index lists of `align_even` for a and b as they are (padded already, if at all): the warping path
+    of `dtw_feature`, cut -- when `pad_len` is given -- to the stretch between the silence pads"""
     _, path = dtw_feature(a, b, **kwargs)
     xs, ys = np.asarray(path).T
-    if pad_silence:
+    if pad_len is not None:
         # from the first cell inside both signals to the first cell inside both trailing pads; argmax of an
         # all-False mask is 0, which the reference's code shares
         inside = (xs >= pad_len) & (ys >= pad_len)
         beyond = (xs >= a.frame_len - pad_len) & (ys >= b.frame_len - pad_len)
         keep = slice(int(np.argmax(inside)), int(np.argmax(beyond)))
         xs, ys = xs[keep], ys[keep]
+    return xs, ys
+
+
+def align_even(a, b, pad_silence=True, pad_len=100, **kwargs):
+    """both feature sets along the warping path (same length), without the silence pads"""
+    if pad_silence:
+        pad = _pkg().pad_silence
+        a, b = pad(a, pad_len), pad(b, pad_len)
+    xs, ys = even_indices(a, b, pad_len if pad_silence else None, **kwargs)
     return a[xs], b[ys]
