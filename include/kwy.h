@@ -313,6 +313,40 @@ int kwy_gv_postfilter_dev(kwy_ctx *ctx, const double *x, int64_t rows, int cols,
 int kwy_gv_postfilter_batch_dev(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col,
                                 const double *gv, double strength, int32_t *status);
 
+/* ---- waveform pitch shift -------------------------------------------------------------- */
+/* The reference has no counterpart: its differential output (kwiiyatta/convert_voice.py:19,39-40) keeps the source's
+ * pitch.  These entries add the waveform pitch shifter GMM voice-conversion recipes run on the source recordings: a
+ * WSOLA time stretch by `rate` followed by resampling back to the input's length, which multiplies every frequency by
+ * `rate`.  x: n samples, xb: x extended with zeros on both sides; rate within [0.5, 2.0]; int64 index arithmetic.
+ *   constants   H = (int)(fs * 0.010), L = 2 H, S = H;  M = floor(n * rate + 0.5);  K = ceil(M / H) frames (0 for M = 0)
+ *   positions   p_0 = 0;  for k = 1 .. K-1:  a_k = (k H n + M / 2) / M  (integer divisions),
+ *               candidates q in [lo, hi], lo = min(max(a_k - S, 0), n - 1), hi = min(a_k + S, n - 1),
+ *               template t[i] = xb[p_{k-1} + H + i], i < L;  d(q) = sum_{i < L} (xb[q + i] - t[i])^2 (any order);
+ *               p_k = the q of the smallest d, ties to the smallest |q - a_k|, then to the smaller q
+ *   stretch     for m < M, k = m / H, i = m % H:  s[m] = xb[i] for k = 0, otherwise a + w_i (b - a) with
+ *               a = xb[p_{k-1} + H + i], b = xb[p_k + i], w_i = 0.5 - 0.5 cos(2 pi i / L)
+ *   resample    M == n: y = s.  Otherwise c = min(1, n / M), W = 32 / c and for every j < n
+ *               base = (j M) / n, frac = ((j M) % n) / n,
+ *               y[j] = sum_i s[base + i] g(frac - i) over the i with 0 <= base + i < M and |frac - i| < W,
+ *               g(t) = c sinc(c t) bh(t / W), sinc(u) = sin(pi u) / (pi u), sinc(0) = 1,
+ *               bh(u) = 0.35875 + 0.48829 cos(pi u) + 0.14128 cos(2 pi u) + 0.01168 cos(3 pi u)
+ * rate == 1 gives p_k = k H and y == x bit for bit.  fs within [100, 128000] (the search window and the template of a
+ * step, 6 H doubles, stay in LDS).  The chain of positions of an utterance is one workgroup; a batch runs all its
+ * utterances side by side in one grid, and every job's result equals the single call's bit for bit. */
+/* M and K of the above; -1 for a bad argument (n < 0, fs or rate out of range or not finite).  No device needed. */
+int64_t kwy_pitch_stretched_length(int64_t n, double rate);
+int64_t kwy_pitch_frames(int64_t n, int fs, double rate);
+/* x, y: n samples (host); positions: kwy_pitch_frames(n, fs, rate) int32 values, written, or NULL */
+int kwy_pitch_shift(kwy_ctx *ctx, const double *x, int64_t n, int fs, double rate, double *y, int32_t *positions);
+typedef struct kwy_pitch_job {
+  const double *x;      /* n samples */
+  int64_t n;
+  double *y;            /* n samples, written (must not overlap x) */
+  int32_t *pos;         /* kwy_pitch_frames(n, fs, rate) positions, written, or NULL */
+} kwy_pitch_job;
+/* device pointers; enqueued on the context's stream, not synchronised (uses the context's scratch arena) */
+int kwy_pitch_shift_batch_dev(kwy_ctx *ctx, const kwy_pitch_job *jobs, int count, int fs, double rate);
+
 /* ---- objective evaluation ------------------------------------------------------------- */
 /* The reference has no counterpart: it compares features only in its tests (tests/feature.py: calc_feature_diffs).
  * These entries add the measures voice-conversion work reports on held-out parallel utterances, taken along an

@@ -19,6 +19,15 @@ from .align import align
 from .config import Config
 from .evaluate_voice import evaluate, evaluate_pair
 
+
+def shift_pitch(wavdata, rate):
+    """a new Wavdata of the same length and sampling rate whose pitch is `rate` (within [0.5, 2.0]) times the
+    input's: a WSOLA time stretch resampled back to the input's length (backend.pitch, kwy_pitch.hip)"""
+    import numpy as np
+    from .backend import pitch
+    return Wavdata(wavdata.fs, pitch.shift_pitch(np.ascontiguousarray(wavdata.data, dtype=np.float64), wavdata.fs, rate))
+
+
 name = "kwiiyatta_amd"
 
 __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFileDataset',
@@ -26,4 +35,6 @@ __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFil
            'Synthesizer', 'align_even', 'analyze_wav', 'feature', 'pad_silence', 'resample',
            'reshape', 'Wavdata', 'load_wav',
            # additions to the reference's names: objective evaluation of a trained converter (evaluate_voice.py)
-           'evaluate_pair', 'evaluate']
+           'evaluate_pair', 'evaluate',
+           # ... and the waveform pitch shifter in front of a differential conversion across genders (backend/pitch.py)
+           'shift_pitch']

@@ -105,6 +105,10 @@ SIGNATURES = {
     'kwy_gv_postfilter': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
     'kwy_gv_postfilter_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp]),
     'kwy_gv_postfilter_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
+    'kwy_pitch_stretched_length': (c_i64, [c_i64, c_dbl]),
+    'kwy_pitch_frames': (c_i64, [c_i64, c_int, c_dbl]),
+    'kwy_pitch_shift': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
+    'kwy_pitch_shift_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl]),
     'kwy_mcd': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     'kwy_mcd_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     'kwy_f0_error': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
@@ -266,6 +270,8 @@ F0MapJob = _job_struct('F0MapJob', 'kwy_f0_map_job: one f0 track through the f0 
 GvMatrix = _job_struct('GvMatrix', 'kwy_gv_matrix: one matrix of a column moments call', [('x', c_vp), ('rows', c_i64)])
 GvJob = _job_struct('GvJob', 'kwy_gv_job: one matrix through the global-variance postfilter',
                     [('x', c_vp), ('rows', c_i64), ('moments', c_vp), ('base', c_vp), ('out', c_vp)])
+PitchJob = _job_struct('PitchJob', 'kwy_pitch_job: one waveform through the pitch shifter',
+                       [('x', c_vp), ('n', c_i64), ('y', c_vp), ('pos', c_vp)])
 McdJob = _job_struct('McdJob', 'kwy_mcd_job: one utterance of a mel-cepstral distortion call',
                      [('a', c_vp), ('a_rows', c_i64), ('a_stride', c_i64), ('b', c_vp), ('b_rows', c_i64), ('b_stride', c_i64),
                       ('idx_a', c_vp), ('idx_b', c_vp), ('off_a', c_i64), ('off_b', c_i64), ('rows', c_i64), ('n_dev', c_vp),

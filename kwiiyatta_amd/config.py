@@ -4,8 +4,11 @@ analyzers and converters are created through it so that frame period, mel-cepstr
 follow the command line."""
 import argparse
 import functools
+import math
 import pathlib
 import sys
+
+import numpy as np
 
 VOCODER_OPTIONS = (
     ('--frame-period', dict(type=int, default=5, help='Frame period milli-seconds of vocoder')),
@@ -22,6 +25,33 @@ CONVERTER_OPTIONS = (
     # an addition to the reference's options: keep the trained converter between runs
     ('--converter-model', dict(type=str, help='File of the trained converter: loaded when it exists (no training, '
                                               '--source/--target not needed), written after training otherwise')),
+)
+
+SOURCE_F0_RATE_RANGE = (0.5, 2.0)
+
+
+def source_f0_rate(text):
+    """--source-f0-rate: 'auto', or a ratio within the pitch shifter's range"""
+    if text == 'auto':
+        return text
+    try:
+        rate = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid f0 ratio: {text!r} (a number or 'auto')") from None
+    lo, hi = SOURCE_F0_RATE_RANGE
+    if not lo <= rate <= hi:                # (false for nan)
+        raise argparse.ArgumentTypeError(f'{text} is outside [{lo}, {hi}]')
+    return rate
+
+
+# an addition to the reference's options, among the converter's: it shapes the training set as well as the conversion
+CONVERTER_OPTIONS += (
+    ('--source-f0-rate', dict(type=source_f0_rate, default=None, metavar='RATE|auto',
+                              help='Shift the pitch of every source waveform by this ratio (WSOLA + resampling, '
+                                   'within [0.5, 2.0]) before it is analysed, in training and in conversion, so that '
+                                   'the differential output takes the target\'s pitch as well; auto: the ratio of the '
+                                   'two speakers\' mean voiced log-f0 over the training files; kept in the converter '
+                                   'model (default 1: no shift)')),
 )
 
 
@@ -109,11 +139,63 @@ class Config:
     source_path = property(lambda self: self._required_dir('source'))
     target_path = property(lambda self: self._required_dir('target'))
 
-    def load_dataset(self):
-        """the aligned parallel training set of --source / --target"""
+    # ---- the source side's pitch shift (--source-f0-rate) ----------------------------------------------------------------
+    def analyze_source(self, path, rate):
+        """the analyzer of a SOURCE-side wav file -- a training file, a file to convert, the source of an evaluated
+        pair -- for a converter of that `source_f0_rate`: at 1 the file as it is, otherwise its waveform through the
+        pitch shifter first"""
         k = _pkg()
+        if rate == 1:
+            return self.create_analyzer(path, Analyzer=k.analyze_wav)
+        return self.create_analyzer(k.shift_pitch(k.load_wav(path), rate), Analyzer=k.vocoder.Analyzer)
+
+    def _training_keys(self, keys):
+        return sorted(keys)[slice(self.skip_files, None)][:self.max_files]
+
+    def auto_source_f0_rate(self):
+        """exp(mean voiced log-f0 of the target - that of the source) over the training files, from the f0 tracks of
+        the unshifted waveforms (DIO + StoneMask only); a parser error outside the shifter's range"""
+        from .backend import f0 as f0map
+        k = _pkg()
+        dirs = (self.source_path, self.target_path)
+        sides = [k.WavFileDataset(path, Analyzer=functools.partial(self.create_analyzer, Analyzer=k.analyze_wav))
+                 for path in dirs]
+        keys = self._training_keys(sides[0].keys() & sides[1].keys())
+        means = []
+        for flag, side in zip(('source', 'target'), sides):
+            tracks = [np.ascontiguousarray(side[key].f0, dtype=np.float64) for key in keys]
+            n, mean, _ = f0map.merge_moments(f0map.logf0_moments(tracks)) if tracks else (0, 0, 0)
+            if not n > 0:
+                self.parser.error(f'--source-f0-rate auto: the training files of --{flag} have no voiced frames')
+            means.append(float(mean))
+        rate = math.exp(means[1] - means[0])
+        lo, hi = SOURCE_F0_RATE_RANGE
+        if not lo <= rate <= hi:
+            self.parser.error(f'--source-f0-rate auto: the speakers\' f0 ratio {rate:.4f} is outside [{lo}, {hi}]')
+        return rate
+
+    def resolve_source_f0_rate(self):
+        """the rate the command line asks for, as a number (`auto` is measured once and remembered)"""
+        asked = getattr(self, 'source_f0_rate', None)
+        if asked is None:
+            return 1.0
+        if asked == 'auto':
+            if getattr(self, '_auto_f0_rate', None) is None:
+                self._auto_f0_rate = self.auto_source_f0_rate()
+            return self._auto_f0_rate
+        return float(asked)
+
+    def load_dataset(self, source_f0_rate=None):
+        """the aligned parallel training set of --source / --target; the source side through `analyze_source` at
+        `source_f0_rate` (default: what the command line asks for, resolved when the first file is analysed -- a
+        converter loaded from a model file in between decides, see train_converter)"""
+        k = _pkg()
+
+        def source(path):
+            rate = source_f0_rate if source_f0_rate is not None else getattr(self, '_model_f0_rate', None)
+            return self.analyze_source(path, self.resolve_source_f0_rate() if rate is None else rate)
         analyze = functools.partial(self.create_analyzer, Analyzer=k.analyze_wav)
-        sides = [k.WavFileDataset(path, Analyzer=analyze) for path in (self.source_path, self.target_path)]
+        sides = [k.WavFileDataset(self.source_path, Analyzer=source), k.WavFileDataset(self.target_path, Analyzer=analyze)]
         return k.align(*sides)
 
     def train_converter(self, f0_stats=False, gv_stats=False, **kwargs):
@@ -123,6 +205,12 @@ class Config:
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
             converter.load(model)
+            asked = getattr(self, 'source_f0_rate', None)
+            if isinstance(asked, float) and asked != converter.source_f0_rate:
+                self.parser.error(f'{model}: the converter model was trained with --source-f0-rate '
+                                  f'{converter.source_f0_rate:g}, not {asked:g}; retrain it with --source-f0-rate '
+                                  f'{asked:g} (a new --converter-model file)')
+            self._model_f0_rate = converter.source_f0_rate          # (a loaded model decides, `auto` included)
             if f0_stats and converter.f0_stats is None:
                 self.parser.error(f'{model}: the converter model has no f0 statistics; retrain it with '
                                   f'--convert-f0 (a new --converter-model file)')
@@ -136,7 +224,8 @@ class Config:
         return converter
 
     def _train(self, converter, f0_stats=False, gv_stats=False):
-        dataset = self.load_dataset()
+        converter.source_f0_rate = self._model_f0_rate = self.resolve_source_f0_rate()
+        dataset = self.load_dataset(converter.source_f0_rate)
         keys = sorted(dataset.keys())[slice(self.skip_files, None)]
         extra = dict(f0_stats=True) if f0_stats else {}
         if gv_stats:

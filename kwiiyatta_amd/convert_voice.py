@@ -6,8 +6,14 @@ for every input <name>.wav a <name>.diff.wav (the input waveform through the dif
 input files -- and the .diff.wav outputs -- through the HBM-resident batch path (kwiiyatta_amd.corpus.convert_batch:
 waves of 16 files in lockstep, wav in -> 16-bit PCM out on the device) instead of file by file; `--convert-f0`
 synthesises the .synth.wav outputs on the source f0 mapped to the target speaker's voiced log-f0 statistics (trained
-with the converter and kept in its model file), `--transpose-key` transposes them by so many semitones.  The .diff.wav
-output keeps the source's pitch whatever the options: the MLSA filter runs on the input waveform itself.
+with the converter and kept in its model file), `--transpose-key` transposes them by so many semitones.  Neither
+reaches the .diff.wav output: the MLSA filter runs on a waveform, whose pitch it keeps.
+`--source-f0-rate RATE|auto` changes the pitch of that waveform instead: every source waveform -- the training set's
+and the files to convert -- goes through the pitch shifter (WSOLA + resampling, backend.pitch) before anything else
+runs, the converter is trained from the shifted source to the target (the shift moves the formants too; the mixture
+learns that), and both outputs start from the shifted waveform.  `auto` takes the ratio of the two speakers' mean
+voiced log-f0 over the training files.  The rate is kept in the converter model; at 1 (the default) the shifter is
+never called.  `--convert-f0` and `--gv` compose with it unchanged: their statistics are those of the shifted source.
 `--gv [STRENGTH]` runs the global-variance postfilter on the converted mel-cepstrum of both outputs: a GMM conversion
 averages, its trajectories vary about 0.6 times as much as the target speaker's and the voice sounds muffled; the
 filter stretches every coefficient's trajectory about its own mean until its variance is the one the target's training
@@ -23,9 +29,10 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
-    global-variance postfilter of that strength (converter.convert(gv=...), either output)"""
+    global-variance postfilter of that strength (converter.convert(gv=...), either output).  A converter trained on
+    pitch-shifted sources (converter.source_f0_rate != 1) gets the file's waveform shifted the same way."""
     import kwiiyatta_amd as k
-    source = conf.create_analyzer(src_path, Analyzer=k.analyze_wav)
+    source = analyze_source(conf, converter, src_path)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}))
     if diffvc:
         return k.apply_mlsa_filter(source, converted)
@@ -37,6 +44,32 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
         rendered.f0 = f0map.map_f0(np.ascontiguousarray(source.f0, dtype=np.float64), rendered.fs, stats=stats,
                                    key=transpose_key)
     return rendered.synthesize()
+
+
+def analyze_source(conf, converter, path):
+    """the analyzer of a file to convert: the file as it is, or -- for a converter trained on pitch-shifted sources --
+    its waveform through the shifter at the converter's rate (Config.analyze_source, which training uses too)"""
+    import kwiiyatta_amd as k
+    rate = getattr(converter, 'source_f0_rate', 1.0)
+    if rate == 1:
+        return conf.create_analyzer(path, Analyzer=k.analyze_wav)
+    return conf.analyze_source(path, rate)
+
+
+def shift_waves_dev(waves, fs, rate, device_index=0):
+    """the waveforms of a batch (numpy arrays) through ONE kwy_pitch_shift_batch_dev call: float64 device tensors, which
+    the corpus drivers take as they are"""
+    import torch
+    from . import _lib
+    from .backend import pitch
+    dev = torch.device('cuda', device_index)
+    xs = [torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(dev) for w in waves]
+    ys = [torch.empty_like(x) for x in xs]
+    torch.cuda.current_stream(dev).synchronize()          # (the uploads, before the library's own stream reads them)
+    ctx = _lib.default_context()
+    pitch.shift_pitch_batch_dev(ctx, xs, ys, fs, rate)
+    ctx.sync()                                            # (the drivers run on streams of their own)
+    return ys
 
 
 class _Pcm16:
@@ -54,7 +87,9 @@ class _Pcm16:
 def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
-    one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: f0 (DIO +
+    one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
+    a converter trained on shifted sources (all files of the batch in one call, the shifted waveforms stay on the
+    device), f0 (DIO +
     StoneMask), analysis, conversion, synthesis / the MLSA filter of the differential conversion, the post-step of
     `synthesize` and `save`'s normalisation and 16-bit truncation all run on the GPU
     (corpus.convert_batch(pcm=True, diff=...)); the host reads the wav files and writes 2 bytes per sample.
@@ -76,6 +111,9 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     if batch:
         fs = batch[0][1].fs
         waves = [a.wavdata.data for _, a in batch]
+        rate = getattr(converter, 'source_f0_rate', 1.0)
+        if rate != 1:
+            waves = shift_waves_dev(waves, fs, rate)
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
                                    frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
                                    f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key,
@@ -107,7 +145,7 @@ def main():
                            'the training data, kept in the converter model)')
     conf.add_transpose_key_argument()
     conf.add_gv_argument()
-    conf.add_converter_arguments()
+    conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0)
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key)

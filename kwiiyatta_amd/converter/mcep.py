@@ -72,6 +72,9 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         self.mcep_fs = mcep_fs
         self.f0_stats = None
         self.gv_stats = None
+        # the pitch ratio the source waveforms were (and are to be) shifted by before analysis (backend.pitch): set by
+        # whoever prepares the training set (Config.train_converter), kept in the model file; 1: no shift
+        self.source_f0_rate = 1.0
 
     def train(self, dataset, keys, f0_stats=False, gv_stats=False, **kwargs):
         """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`).
@@ -110,7 +113,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
     def save(self, path):
         """the trained stack as one .npz: the mixture's parameters and what the outer stages learnt from the
         training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics and the global variance when
-        there are any)"""
+        there are any; the pitch ratio of the source waveforms)"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
@@ -118,12 +121,13 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 extra['gv_stats'] = np.array(self.gv_stats, dtype=np.float64)
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
+                     source_f0_rate=float(self.source_f0_rate),
                      weights=gmm.weights_, means=gmm.means_, covariances=gmm.covariances_, **extra)
 
     def load(self, path):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
         the file.  `f0_stats` / `gv_stats` are None for a file without them (written without these statistics, or before
-        they existed)"""
+        they existed); `source_f0_rate` is 1.0 for a file without it"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
@@ -143,6 +147,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             gmm.converged_ = True
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
             self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None
+            self.source_f0_rate = float(z['source_f0_rate']) if 'source_f0_rate' in z.files else 1.0
         return self
 
     def convert(self, mel_cepstrum, gv=0.0, **kwargs):

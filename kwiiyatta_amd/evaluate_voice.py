@@ -220,7 +220,8 @@ def report(names, results, total, options):
 
 def _evaluate_batched(conf, converter, dataset, keys, options):
     """the pairs at the converter's sampling rate, order and frame period through corpus.evaluate_batch, the others
-    one by one (the batch path has no resampling stage)"""
+    one by one (the batch path has no resampling stage).  For a converter trained on pitch-shifted sources the source
+    waveforms of the batch go through the shifter in one call and are analysed from there on the device"""
     import kwiiyatta_amd as k
     from . import corpus
     from .convert_voice import _stages
@@ -234,7 +235,14 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
                (period is not None and a.frame_period != period) for a in pair):
             results[key] = evaluate_pair(converter, *_trimmed(dataset)[key], **options)
         else:
-            batch.append((key, tuple(_triple(a) for a in pair), float(pair[0].frame_period)))
+            # (the source's f0 track is taken from the shifted waveform below when there is a shift)
+            source = _triple(pair[0]) if getattr(converter, 'source_f0_rate', 1.0) == 1 else \
+                (np.ascontiguousarray(pair[0].wavdata.data, dtype=np.float64),)
+            batch.append((key, (source, _triple(pair[1])), float(pair[0].frame_period)))
+    rate = getattr(converter, 'source_f0_rate', 1.0)
+    if batch and rate != 1:
+        sources = _shifted_triples([pair[0][0] for _, pair, _ in batch], converter.fs, rate, batch[0][2])
+        batch = [(key, (src, pair[1]), period) for (key, pair, period), src in zip(batch, sources)]
     if batch:
         records, _ = corpus.evaluate_batch(
             [p for _, p, _ in batch], converter.fs, converter.gmm, order=converter.order, frame_period=batch[0][2],
@@ -245,6 +253,29 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
             results[key] = Result(rec['mcd_moments'], rec['source_moments'], rec['f0_moments'], rec['counts'],
                                   rec['aligned'], rec['outside'])
     return [results[key] for key in keys]
+
+
+def _shifted_triples(waves, fs, rate, frame_period, group=16):
+    """(x, f0, t) device tensors per waveform: the waveforms through ONE kwy_pitch_shift_batch_dev call
+    (convert_voice.shift_waves_dev), then DIO + StoneMask on the device, as Analyzer.extract_f0 runs them"""
+    import torch
+    from . import _lib
+    from .backend import world
+    from .convert_voice import shift_waves_dev
+    xs = shift_waves_dev(waves, fs, rate)
+    ctx = _lib.default_context()
+    frames = [world.dio_frames(fs, x.numel(), frame_period) for x in xs]
+    ts, coarse, f0 = ([torch.empty(n, dtype=torch.float64, device=xs[0].device) for n in frames] for _ in range(3))
+    status = torch.zeros(len(xs), dtype=torch.int32, device=xs[0].device)
+    torch.cuda.current_stream(xs[0].device).synchronize()
+    for g in range(0, len(xs), group):
+        sl = slice(g, g + group)
+        world.dio_batch_dev(ctx, xs[sl], fs, ts[sl], coarse[sl], status=status[sl], frame_period=frame_period)
+        world.stonemask_batch_dev(ctx, xs[sl], ts[sl], coarse[sl], fs, f0[sl])
+    ctx.sync()
+    if status.any().item():
+        raise RuntimeError('dio: zero-crossing buffer overflow')
+    return list(zip(xs, f0, ts))
 
 
 def _trimmed(dataset):
