@@ -408,6 +408,10 @@ int kwy_f0_error_batch_dev(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int count
  * however its utterances were grouped into calls */
 int kwy_moments_merge(kwy_ctx *ctx, const double *moments, int count, int width, double *out);
 int kwy_moments_merge_dev(kwy_ctx *ctx, const double *moments, int count, int width, double *out);
+/* The monitor of a re-alignment pass: acc[0] += sum_i n_i * mean_i, acc[1] += sum_i n_i over count (n, mean, M2)
+ * triples in row order (kwy_mcd_batch_dev's output for the pairs of a wave): the distortion summed over the cells of
+ * the wave and their number, accumulated across waves in one device block.  No host synchronisation. */
+int kwy_moments_accumulate_dev(kwy_ctx *ctx, const double *moments, int count, double *acc);
 
 /* ---- mel-cepstrum ---------------------------------------------------------------- */
 /* pysptk.sp2mc(spec, order, alpha) row-wise          kwiiyatta/vocoder/mcep.py:71
@@ -535,6 +539,18 @@ typedef struct kwy_convert_job {
 } kwy_convert_job;
 int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *jobs, int count, int d, int M,
                                const double *model);
+/* Re-alignment of the training set (an addition: the reference aligns once): the same batched conversion, with the
+ * converted c1..cd of every job stored straight into columns 2.. of its DTW feature rows (kwy_align_features_dev's
+ * layout, rows d + 2 doubles apart) -- columns 0 and 1, the source's own power and voicing terms, are not touched, and no
+ * T x (d + 1) intermediate is made.  Columns 2.. equal columns 1.. of kwy_convert_mcep_dev's output for the same mc and
+ * model bit for bit.  Any count (KWY_BATCH_MAX = 16 utterances share a pass of launches); no host synchronisation. */
+typedef struct kwy_realign_job {
+  const double *mc;      /* T x (d + 1): the padded source mel-cepstrum */
+  int64_t T;
+  double *feat;          /* T x (d + 2) DTW features, columns 2.. written */
+} kwy_realign_job;
+int kwy_realign_features_batch_dev(kwy_ctx *ctx, const kwy_realign_job *jobs, int count, int d, int M,
+                                   const double *model);
 
 /* ---- cross-rate aperiodicity codec ------------------------------------------------------
  * pyworld.code_aperiodicity(ap, fs) / pyworld.decode_aperiodicity(coded, fs, fft_size)

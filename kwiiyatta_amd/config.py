@@ -55,6 +55,31 @@ CONVERTER_OPTIONS += (
 )
 
 
+ALIGN_ITERATIONS_RANGE = (0, 10)
+
+
+def align_iterations(text):
+    """--align-iterations: how often the training set is aligned again, an integer within [0, 10]"""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid iteration count: {text!r}') from None
+    lo, hi = ALIGN_ITERATIONS_RANGE
+    if not lo <= n <= hi:
+        raise argparse.ArgumentTypeError(f'{text} is outside [{lo}, {hi}]')
+    return n
+
+
+# an addition to the reference's options (it aligns its training set once)
+CONVERTER_OPTIONS += (
+    ('--align-iterations', dict(type=align_iterations, default=None, metavar='N',
+                                help='Align the training set again N times (within [0, 10]): each time every pair is '
+                                     'aligned with the source mel-cepstrum converted by the converter fitted so far, '
+                                     'the joint matrix is rebuilt along the new paths and the mixture refitted; kept '
+                                     'in the converter model (default 0: aligned once, as the reference does)')),
+)
+
+
 def transpose_key(text):
     """--transpose-key: semitones, within the reference dialog's spin box range (view/qt/ui/kwiieiya.ui:262-280)"""
     try:
@@ -211,6 +236,11 @@ class Config:
                                   f'{converter.source_f0_rate:g}, not {asked:g}; retrain it with --source-f0-rate '
                                   f'{asked:g} (a new --converter-model file)')
             self._model_f0_rate = converter.source_f0_rate          # (a loaded model decides, `auto` included)
+            asked = getattr(self, 'align_iterations', None)
+            if asked is not None and asked != converter.align_iterations:
+                self.parser.error(f'{model}: the converter model was trained with --align-iterations '
+                                  f'{converter.align_iterations}, not {asked}; retrain it with --align-iterations '
+                                  f'{asked} (a new --converter-model file)')
             if f0_stats and converter.f0_stats is None:
                 self.parser.error(f'{model}: the converter model has no f0 statistics; retrain it with '
                                   f'--convert-f0 (a new --converter-model file)')
@@ -230,5 +260,7 @@ class Config:
         extra = dict(f0_stats=True) if f0_stats else {}
         if gv_stats:
             extra['gv_stats'] = True
+        if getattr(self, 'align_iterations', None):
+            extra['align_iterations'] = self.align_iterations
         converter.train(dataset, keys[:self.max_files], **extra)
         return converter

@@ -17,7 +17,11 @@ never called.  `--convert-f0` and `--gv` compose with it unchanged: their statis
 `--gv [STRENGTH]` runs the global-variance postfilter on the converted mel-cepstrum of both outputs: a GMM conversion
 averages, its trajectories vary about 0.6 times as much as the target speaker's and the voice sounds muffled; the
 filter stretches every coefficient's trajectory about its own mean until its variance is the one the target's training
-utterances have (learnt with the converter, kept in its model file), or STRENGTH of the way there."""
+utterances have (learnt with the converter, kept in its model file), or STRENGTH of the way there.
+`--align-iterations N` trains with iterative re-alignment: after the first fit every training pair is aligned again, N
+times over, with the source mel-cepstrum converted by the converter fitted so far in its DTW features (the reference
+aligns once, on the two speakers' own coefficients), the joint matrix is rebuilt along the new paths and the mixture
+refitted.  The count is kept in the converter model; 0 (the default) is the reference's training."""
 import pathlib
 
 import numpy as np

@@ -1,7 +1,8 @@
 """Converter layer: datasets of the training path and the converter stack
 (mel-cepstrum stage > delta stage > joint GMM).  Export list of kwiiyatta.converter."""
 from . import abc
-from .dataset import AlignedDataset, ParallelDataset, TrimmedDataset, WavFileDataset, make_dataset_to_array
+from .dataset import (AlignedDataset, PaddedDataset, ParallelDataset, TrimmedDataset, WavFileDataset,
+                      make_dataset_to_array)
 from .delta import DELTA_WINDOWS, DeltaFeatureConverter, DeltaFeatureDataset
 from .gmm import GMMFeatureConverter
 from .mcep import MelCepstrumDataset, MelCepstrumFeatureConverter
@@ -21,5 +22,5 @@ def align_dataset(parallel_dataset):
 
 
 __all__ = ['MelCepstrumConverter', 'align_dataset', 'AlignedDataset', 'ParallelDataset', 'TrimmedDataset',
-           'WavFileDataset', 'make_dataset_to_array', 'GMMFeatureConverter', 'DELTA_WINDOWS',
+           'WavFileDataset', 'PaddedDataset', 'make_dataset_to_array', 'GMMFeatureConverter', 'DELTA_WINDOWS',
            'DeltaFeatureConverter', 'DeltaFeatureDataset', 'MelCepstrumDataset', 'MelCepstrumFeatureConverter']

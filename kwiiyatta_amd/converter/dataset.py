@@ -78,6 +78,49 @@ def AlignedDataset(features, **kwargs):
     return _pkg().align_even(*features, **kwargs)
 
 
+class PaddedSide:
+    """What re-alignment needs of one padded side of a pair, and nothing else: its mel-cepstrum (frames, order + 1) and
+    its voicing decision -- no envelopes.  It answers the questions `vocoder.align.make_feature` asks of a feature set"""
+
+    def __init__(self, feature):
+        record = feature.mel_cepstrum
+        self.fs, self.frame_period, self.order = feature.fs, feature.frame_period, record.order
+        self.mel_cepstrum_data = np.ascontiguousarray(record.data, dtype=np.float64)
+        self.is_voiced = np.array(feature.is_voiced, dtype=bool)
+        self.frame_len = len(self.is_voiced)
+
+    def resample_mel_cepstrum(self, fs):
+        if fs != self.fs:
+            raise ValueError(f'align_iterations: a side at {self.fs} Hz cannot be re-aligned at {fs} Hz '
+                             f'(only its mel-cepstrum at its own sampling rate is kept)')
+        return self
+
+    data = property(lambda self: self.mel_cepstrum_data)
+
+
+class PaddedDataset(abc.MapDataset):
+    """a parallel pair with `pad_len` frames of the vocoder's silence around both sides -- drawn ONCE per key, in
+    align_even's order (source head, source tail, target head, target tail), when the key is first read.  An
+    AlignedDataset on top (with padded=True) therefore gives what one on the unpadded pairs gives, draw for draw.
+    `sides[key]` keeps the pair's `PaddedSide`s: later alignments of the same pads (MelCepstrumFeatureConverter
+    .train(align_iterations=...)) read those; the padded envelopes themselves are not kept"""
+    expand_tuple = False
+    with_key = True
+
+    def __init__(self, base, pad_len=100):
+        super().__init__(base)
+        self.pad_len = pad_len
+        self.sides = {}
+
+    def function(self, features, key):
+        if key in self.sides:
+            raise ValueError(f'PaddedDataset: "{key}" was padded before; its pads are drawn once (read `sides`)')
+        pad = _pkg().pad_silence
+        pair = tuple(pad(f, self.pad_len) for f in features)
+        self.sides[key] = tuple(PaddedSide(f) for f in pair)
+        return pair
+
+
 def make_dataset_to_array(dataset, keys=None):
     """rows of all items under `keys` (default: all, sorted), zero rows removed; a tuple item contributes its
     members side by side.  None for no keys."""

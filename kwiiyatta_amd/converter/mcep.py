@@ -75,14 +75,24 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         # the pitch ratio the source waveforms were (and are to be) shifted by before analysis (backend.pitch): set by
         # whoever prepares the training set (Config.train_converter), kept in the model file; 1: no shift
         self.source_f0_rate = 1.0
+        # the re-alignment passes the training ran (`train(align_iterations=...)`) and its record, a dict per fit
+        self.align_iterations = 0
+        self.align_history = []
 
-    def train(self, dataset, keys, f0_stats=False, gv_stats=False, **kwargs):
+    def train(self, dataset, keys, f0_stats=False, gv_stats=False, align_iterations=0, **kwargs):
         """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`).
         gv_stats=True: also the target side's global variance (`gv_stats`, order + 1 values: per coefficient the mean
-        over the training utterances of its variance within the utterance; used by `convert(gv=...)`)"""
-        coefficients = MelCepstrumDataset(dataset, mcep_fs=self.mcep_fs)
-        self.base.train(coefficients, keys, **kwargs)
-        self.order, self.fs = coefficients.order, coefficients.fs
+        over the training utterances of its variance within the utterance; used by `convert(gv=...)`).
+        align_iterations=N > 0: iterative re-alignment of the training set, see `_train_realigned`"""
+        if isinstance(align_iterations, bool) or int(align_iterations) != align_iterations or align_iterations < 0:
+            raise ValueError(f'align_iterations must be a non-negative integer, not {align_iterations!r}')
+        self.align_iterations, self.align_history = int(align_iterations), []
+        if self.align_iterations > 0:
+            self._train_realigned(dataset, list(keys), self.align_iterations, kwargs)
+        else:
+            coefficients = MelCepstrumDataset(dataset, mcep_fs=self.mcep_fs)
+            self.base.train(coefficients, keys, **kwargs)
+            self.order, self.fs = coefficients.order, coefficients.fs
         self.f0_stats = None
         if f0_stats:
             from ..backend import f0 as f0map
@@ -99,6 +109,86 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 raise ValueError('global variance statistics: no training files')
             self.gv_stats = gvfilter.gv_from_moments(gvfilter.column_moments(mats))
 
+    def _train_realigned(self, dataset, keys, iterations, fit_options):
+        """Iterative re-alignment of the training set (Toda et al.'s joint-feature iterations): fit 0 is the training
+        of align_iterations=0 on the same rows -- every pair trimmed, padded (the pads are drawn ONCE, here, in
+        today's order) and aligned on the two speakers' own DTW features.  Then, `iterations` times over, every pair
+        is aligned again: the same padded pair, the source's DTW features carrying its mel-cepstrum CONVERTED by the
+        mixture fitted last (`convert(..., diff=False)`: deltas, mixture, MLPG; no GV, no f0) in columns 2.. while its
+        power and voicing terms stay its own; the joint rows pair the ORIGINAL source coefficients with the target's
+        along the new path, and the mixture is fitted on them from scratch (same components, random_state, stopping
+        rule).  `align_history` gets one record per fit: rows, em_iterations and mcd, the monitor -- the mean
+        distortion in dB over c1..cN, along the kept path of all pairs, between the target and the source coefficients
+        the path was found with (fit 0: the source's own; fit k: converted by fit k - 1).
+        The dataset must be an AlignedDataset chain with silence pads; pairs whose alignment would not run at the
+        converter's sampling rate raise ValueError (nothing is resampled here)."""
+        from ..backend import distortion as dist
+        from ..backend.mlpg import DELTA_WINDOWS, delta_features
+        from ..vocoder.align import even_indices
+        from .dataset import AlignedDataset, PaddedDataset, remove_zeros_frames
+        from .delta import DeltaFeatureConverter
+        stage = dataset
+        while not isinstance(stage, AlignedDataset) and isinstance(stage, abc.MapDataset):
+            stage = stage.base
+        if not isinstance(stage, AlignedDataset):
+            raise ValueError('align_iterations > 0 needs an aligned dataset (kwiiyatta_amd.align / align_dataset)')
+        options = dict(stage.kwargs)
+        if not options.pop('pad_silence', True) or options.pop('padded', False):
+            raise ValueError('align_iterations > 0 needs an alignment that pads its pairs with silence itself')
+        padded = PaddedDataset(stage.base, pad_len=options.pop('pad_len', 100))
+        delta_stage = self.base
+        while not isinstance(delta_stage, DeltaFeatureConverter) and isinstance(delta_stage, abc.MapFeatureConverter):
+            delta_stage = delta_stage.base
+        if not isinstance(delta_stage, DeltaFeatureConverter):
+            delta_stage = None
+        k = _pkg()
+        self.order, self.fs = None, self.mcep_fs
+        for it in range(iterations + 1):
+            blocks, triples = [], []
+            for key in keys:
+                if it == 0:
+                    padded[key]                      # draws the pair's pads and keeps its `sides`
+                x, y = padded.sides[key]
+                if it == 0:
+                    if self.order is None:
+                        self.order = x.order
+                    if self.fs is None:
+                        self.fs = x.fs
+                    if x.order != self.order or y.order != self.order:
+                        raise ValueError(f'align_iterations: "{key}" has mel-cepstra of order {x.order} and {y.order}, '
+                                         f'the converter of order {self.order}')
+                    if not x.fs == y.fs == self.fs:
+                        raise ValueError(f'align_iterations: "{key}" is aligned at {min(x.fs, y.fs)} Hz (source {x.fs} Hz, '
+                                         f'target {y.fs} Hz) but the converter works at {self.fs} Hz; re-alignment does '
+                                         f'not resample')
+                    if delta_stage is not None:
+                        if key == keys[0]:
+                            delta_stage.frame_period = x.frame_period
+                        for side in (x, y):
+                            if side.frame_period != delta_stage.frame_period:
+                                raise ValueError(f'frame_period of "{key}" is {side.frame_period!r} but others are '
+                                                 f'{delta_stage.frame_period!r}')
+                    mapped = x.data
+                else:
+                    source = k.MelCepstrum(x.fs, x.frame_period, x.data)
+                    mapped = np.ascontiguousarray(self.convert(source, diff=False).data, dtype=np.float64)
+                xs, ys = even_indices(x, y, padded.pad_len, **options,
+                                      **({} if it == 0 else dict(x_mapped=mapped[:, 1:])))
+                sides = [np.ascontiguousarray(side.data[idx][:, 1:]) for side, idx in ((x, xs), (y, ys))]
+                if delta_stage is not None:
+                    sides = [delta_features(m, DELTA_WINDOWS) for m in sides]
+                blocks.append(remove_zeros_frames(np.hstack(sides)))
+                lists = [np.ascontiguousarray(v, dtype=np.int32) for v in (xs, ys)]
+                triples.append(dist.mcd(mapped, y.data, idx_a=lists[0], idx_b=lists[1])[0])
+            matrix = np.concatenate(blocks)
+            self._train(matrix, **fit_options)
+            cells = float(sum(t[0] for t in triples))
+            total = 0.0
+            for t in triples:
+                total += float(t[0]) * float(t[1])
+            self.align_history.append(dict(rows=len(matrix), mcd=total / cells if cells > 0 else float('nan'),
+                                           em_iterations=int(getattr(self.gmm, 'n_iter_', 0))))
+
     def convert_f0(self, f0, key=0.0, fs=None):
         """the f0 track for synthesising a converted voice: voiced frames through the log-Gaussian transform of
         `f0_stats` (when trained with them), then transposed by `key` semitones; unvoiced frames stay 0.  fs: the
@@ -113,7 +203,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
     def save(self, path):
         """the trained stack as one .npz: the mixture's parameters and what the outer stages learnt from the
         training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics and the global variance when
-        there are any; the pitch ratio of the source waveforms)"""
+        there are any; the pitch ratio of the source waveforms; the re-alignment passes of the training as
+        `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`)"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
@@ -122,12 +213,15 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      source_f0_rate=float(self.source_f0_rate),
+                     align_iterations=int(self.align_iterations),
+                     align_mcd=np.array([r['mcd'] for r in self.align_history], dtype=np.float64),
+                     align_rows=np.array([r['rows'] for r in self.align_history], dtype=np.int64),
                      weights=gmm.weights_, means=gmm.means_, covariances=gmm.covariances_, **extra)
 
     def load(self, path):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
         the file.  `f0_stats` / `gv_stats` are None for a file without them (written without these statistics, or before
-        they existed); `source_f0_rate` is 1.0 for a file without it"""
+        they existed); `source_f0_rate` is 1.0 for a file without it, `align_iterations` 0 and `align_history` empty"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
@@ -148,6 +242,11 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
             self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None
             self.source_f0_rate = float(z['source_f0_rate']) if 'source_f0_rate' in z.files else 1.0
+            self.align_iterations = int(z['align_iterations']) if 'align_iterations' in z.files else 0
+            mcd = z['align_mcd'] if 'align_mcd' in z.files else ()
+            rows = z['align_rows'] if 'align_rows' in z.files else [None] * len(mcd)
+            self.align_history = [dict(rows=None if n is None else int(n), mcd=float(v), em_iterations=None)
+                                  for n, v in zip(rows, mcd)]
         return self
 
     def convert(self, mel_cepstrum, gv=0.0, **kwargs):

@@ -181,7 +181,7 @@ class TrainWave:
             self.x, self.f0, self.t = ([s[k] for s in sides] for k in range(3))
             self.N = [len(v) for v in self.x]
             self.T = [len(v) for v in self.f0]
-            layout = Ragged([t + 2 * P for t in self.T])
+            self.layout = layout = Ragged([t + 2 * P for t in self.T])
             self.reg = layout.view          # reg(block, i): the padded rows of side i in one of the blocks below
             self.rows = rows = layout.total
             self.sp_pad = torch.empty((rows, K), **f64)
@@ -219,19 +219,15 @@ class TrainWave:
             self.keep_ready = torch.cuda.Event()
             self.keep_ready.record(ls.main)
 
-    def finish(self, X, cursor, pads):
+    def finish(self, X, cursor, pads, cache=None):
         """pads(rows): fills the wave's pad rows -- a list of 4 n device views (source head, source tail, target
-        head, target tail, pair after pair) -- on the main stream"""
+        head, target tail, pair after pair) -- on the main stream.  cache: a TrainCache that takes over the wave's
+        alignment inputs (and its share of the monitor of this first alignment), or None"""
         Tp = self.align(pads)
-        ls, order, reg = self.ls, self.order, self.reg
-        with torch.cuda.stream(ls.main):
-            # dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames, append
-            _lib.check(ls.ctx, lib.kwy_train_rows_batch_dev(
-                ls.ctx.handle,
-                _lib.job_array(_lib.TrainJob, [(self.path[k], self.path_len[k:k + 1], reg(self.feat, 2 * k),
-                                                reg(self.feat, 2 * k + 1), reg(self.mc_pad, 2 * k), reg(self.mc_pad, 2 * k + 1),
-                                                Tp[2 * k], Tp[2 * k + 1], self.n_rows[k:k + 1]) for k in range(self.n)]),
-                self.n, order, 1, 1, 1, PAD_LEN, TRIM_EPS, _p(X), X.shape[0], _p(cursor)))
+        _train_rows(self.ls, self.order, self.reg, self.n, Tp, self.path, self.path_len, self.feat, self.feat, self.mc_pad,
+                    self.n_rows, X, cursor)
+        if cache is not None:
+            cache.add(self, Tp)
 
     def align(self, pads):
         """(waits for the trim lengths) enqueue padding, voicing, sp2mc, the DTW features and FastDTW of every pair;
@@ -261,6 +257,178 @@ class TrainWave:
                                           self.n, order + 2, self.radius))
         self.keep = keep
         return Tp
+
+
+def _train_rows(ls, order, reg, n, Tp, path, path_len, feat_x, feat_y, mc_pad, n_rows, X, cursor):
+    """enqueue (main stream) dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames and the
+    append behind the cursor for the n pairs of a wave: pair k's source features are item 2 k of `feat_x`, its target
+    features item 2 k + 1 of `feat_y`, the mel-cepstra of both items of `mc_pad`"""
+    with torch.cuda.stream(ls.main):
+        _lib.check(ls.ctx, lib.kwy_train_rows_batch_dev(
+            ls.ctx.handle,
+            _lib.job_array(_lib.TrainJob, [(path[k], path_len[k:k + 1], reg(feat_x, 2 * k), reg(feat_y, 2 * k + 1),
+                                            reg(mc_pad, 2 * k), reg(mc_pad, 2 * k + 1), Tp[2 * k], Tp[2 * k + 1],
+                                            n_rows[k:k + 1]) for k in range(n)]),
+            n, order, 1, 1, 1, PAD_LEN, TRIM_EPS, _p(X), X.shape[0], _p(cursor)))
+
+
+def _monitor_wave(ls, order, reg, n, Tp, path, path_len, feat_x, feat_y, mc_pad, acc):
+    """enqueue (main stream) the monitor of a wave's alignment: along the kept path of every pair (strict filter and
+    cut: the cells kwy_train_rows_batch_dev turns into rows) the distortion in dB over c1..cN between columns 2.. of
+    the source's DTW features -- the coefficients the path was found with -- and the target's mel-cepstrum
+    (kwy_mcd_batch_dev, one workgroup per pair); the cells' sum and count are added to the two device words `acc`
+    (kwy_moments_accumulate_dev)"""
+    from .backend import distortion as dist
+    dev = ls.dev
+    with torch.cuda.stream(ls.main):
+        h = ls.ctx.handle
+        cap = [path[k].shape[0] for k in range(n)]
+        idx_x = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
+        idx_y = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
+        n_sel = torch.zeros(n, dtype=torch.int64, device=dev)
+        moments = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        jobs = []
+        for k in range(n):
+            fx, fy = reg(feat_x, 2 * k)[:Tp[2 * k]], reg(feat_y, 2 * k + 1)[:Tp[2 * k + 1]]
+            _lib.check(ls.ctx, lib.kwy_align_even_dev(h, _p(path[k]), _p(path_len[k:k + 1]), _p(fx), _p(fy), order + 2, 1, 1, 1,
+                                                      Tp[2 * k], Tp[2 * k + 1], PAD_LEN, _p(idx_x[k]), _p(idx_y[k]), cap[k],
+                                                      _p(n_sel[k:k + 1])))
+            # (column 1 of the features, the voicing term, stands where c0 stands in a mel-cepstrum: first_col = 1)
+            jobs.append(dist.mcd_job(fx[:, 1:], reg(mc_pad, 2 * k + 1)[:Tp[2 * k + 1]], idx_a=idx_x[k], idx_b=idx_y[k],
+                                     rows=cap[k], n_dev=n_sel[k:k + 1]))
+        dist.mcd_batch_dev(ls.ctx, jobs, order + 1, moments)
+        _lib.check(ls.ctx, lib.kwy_moments_accumulate_dev(h, _p(moments), n, _p(acc)))
+
+
+class _CachedWave:
+    """the alignment inputs of one wave of pairs: blocks in the wave's ragged layout (item 2 k the source, 2 k + 1 the
+    target of pair k), the padded lengths in use, the frames TrimmedDataset kept and the lengths of the first paths"""
+
+    def __init__(self, wave, Tp):
+        self.n, self.layout, self.Tp, self.keep = wave.n, wave.layout, list(Tp), list(wave.keep)
+        self.mc_pad, self.feat, self.voiced = wave.mc_pad, wave.feat, wave.voiced
+        self.path_cap = [p.shape[0] for p in wave.path]
+        self.path_len = wave.path_len            # cells of the first alignment's FastDTW paths (n device words)
+
+
+class TrainCache:
+    """What a second alignment of the training set needs of the first, kept in HBM: per wave of pairs the padded
+    mel-cepstra `mc_pad`, the DTW features `feat` of the first alignment, the voicing `voiced`, the padded lengths and
+    the kept frames -- ragged blocks in `_blocks.Ragged` layout, the waves' own buffers taken over as they are.  The
+    padded envelopes and aperiodicities (sp_pad, ap_pad: 2 x 1025 doubles per frame at 48 kHz) are NOT kept; without
+    the cache a second pass would have to analyse every pair again.
+    Size: (order + 1) + (order + 2) + 1 doubles per padded frame of both sides -- 416 bytes (0.41 KiB) at order 24;
+    bench_corpus.py's 503 pairs of 5 s (1001 + 200 padded frames a side) take 2 x 1201 x 416 B = 1.0 MB a pair,
+    0.50 GB in all.
+    `monitor`: two device words, sum and count of the first alignment's monitor (see `_monitor_wave`)."""
+
+    def __init__(self, ls, fs, order, radius):
+        self.ls, self.fs, self.order, self.radius = ls, int(fs), int(order), int(radius)
+        self.waves = []
+        self.monitor = torch.zeros(2, dtype=torch.float64, device=ls.dev)
+
+    pairs = property(lambda self: sum(w.n for w in self.waves))
+    frames = property(lambda self: sum(sum(w.Tp) for w in self.waves))
+    nbytes = property(lambda self: sum(t.numel() * 8 for w in self.waves for t in (w.mc_pad, w.feat, w.voiced)))
+
+    def add(self, wave, Tp):
+        self.waves.append(_CachedWave(wave, Tp))
+        # (its scratch is made and dropped on the main stream: reused there only behind the queued work)
+        _monitor_wave(self.ls, self.order, wave.reg, wave.n, Tp, wave.path, wave.path_len, wave.feat, wave.feat, wave.mc_pad,
+                      self.monitor)
+
+
+def realign_training_matrix(cache, gmm, paths=None):
+    """One re-alignment pass over a cached training set with the fitted mixture `gmm`: -> (X, mcd_mean).
+    The mixture is prepared once (kwy_gmm_prepare_dev); then, wave by wave (<= 16 pairs), the sources' padded
+    mel-cepstra are converted -- deltas, mixture, MLPG: `MelCepstrumFeatureConverter.convert(..., diff=False)` -- straight
+    into columns 2.. of a COPY of their DTW features (kwy_realign_features_batch_dev; the cache's first-alignment
+    features stay as they are, power and voicing terms are the source's own), FastDTW runs on them against the targets'
+    unchanged features, and the joint rows of the ORIGINAL mel-cepstra along the new paths go behind a device-side
+    cursor (kwy_train_rows_batch_dev).  mcd_mean: the monitor of this alignment (`_monitor_wave`).  One read-back.
+    paths: a list that receives, pair after pair, the (FastDTW path, its length) device tensors of this pass."""
+    import struct
+    ls, order, dev = cache.ls, cache.order, cache.ls.dev
+    dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
+    if dg.D2 != 6 * order:
+        raise ValueError(f'realign_training_matrix: the mixture has {dg.D2} joint dimensions, the cache order {order}')
+    cap_rows = cache.frames               # a pair yields at most one row per cell of its path
+    J = _lib.job_array
+    with torch.cuda.stream(ls.main):
+        model = dg.model(diff=False)
+        X = torch.empty((cap_rows, 6 * order), dtype=torch.float64, device=dev)
+        cursor = torch.zeros(1, dtype=torch.int64, device=dev)
+        worst = torch.zeros(1, dtype=torch.int64, device=dev)
+        acc = torch.zeros(2, dtype=torch.float64, device=dev)
+        for w in cache.waves:
+            n, reg, Tp = w.n, w.layout.view, w.Tp
+            h = ls.ctx.handle
+            feat = w.feat.clone()                  # the sources' items are rewritten below, the targets' only read
+            path = [torch.zeros((c, 2), dtype=torch.int32, device=dev) for c in w.path_cap]
+            path_len = torch.zeros(n, dtype=torch.int64, device=dev)
+            dist_ = torch.zeros(n, dtype=torch.float64, device=dev)
+            n_rows = torch.zeros(n, dtype=torch.int64, device=dev)
+            _lib.check(ls.ctx, lib.kwy_realign_features_batch_dev(
+                h, J(_lib.RealignJob, [(reg(w.mc_pad, 2 * k), Tp[2 * k], reg(feat, 2 * k)) for k in range(n)]), n, order,
+                dg.M, _p(model)))
+            _lib.check(ls.ctx, lib.kwy_fastdtw_batch_dev(
+                h, J(_lib.DtwJob, [(reg(feat, 2 * k), Tp[2 * k], reg(feat, 2 * k + 1), Tp[2 * k + 1], dist_[k:k + 1], path[k],
+                                    path_len[k:k + 1]) for k in range(n)]), n, order + 2, cache.radius))
+            _train_rows(ls, order, reg, n, Tp, path, path_len, feat, feat, w.mc_pad, n_rows, X, cursor)
+            _monitor_wave(ls, order, reg, n, Tp, path, path_len, feat, feat, w.mc_pad, acc)
+            torch.minimum(worst, n_rows.min().reshape(1), out=worst)
+            # (the wave's scratch -- feat, path, ... -- was made on the main stream: freed here, reused there in order)
+            if paths is not None:
+                paths.extend((path[k], path_len[k:k + 1]) for k in range(n))
+        words = torch.cat((cursor, worst, acc.view(torch.int64))).tolist()     # ONE read-back
+    ls.sync()
+    n_rows, dropped = int(words[0]), int(words[1])
+    total, cells = struct.unpack('<2d', struct.pack('<2q', *words[2:]))
+    if dropped < 0:
+        raise RuntimeError(f'training matrix: a pair of {-1 - dropped} rows did not fit the capacity of {cap_rows}')
+    torch.cuda.current_stream(dev).synchronize()
+    return (X[:n_rows].clone() if n_rows * 4 < cap_rows * 3 else X[:n_rows]), (total / cells if cells > 0 else float('nan'))
+
+
+def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterations=0, max_iter=100, device_index=0,
+                              order=24, radius=32, frame_period=5.0, silence_for=None, rng=None, pairs_before=0,
+                              driver=None, lockstep=None, wave_pairs=16, f0_moments=False, gv_moments=False, verbose=0,
+                              keep_matrices=False):
+    """Training with iterative re-alignment on the device: `build_training_matrix(keep=True)` and `fit_converter`, then
+    `align_iterations` times `realign_training_matrix` with the mixture fitted last and `fit_converter` on its rows,
+    from scratch (same components, seed, stopping rule).  The pads are drawn once -- numpy's global generator or the
+    device-drawn stream (`rng`, `pairs_before`) advance as they do for align_iterations = 0 -- and the f0 / global
+    variance moments are the first pass's.  Returns (mixture, history[, f0 moments][, gv statistic]): history holds a
+    dict per fit -- rows, mcd (the alignment's monitor, `_monitor_wave`), em_iterations -- and with keep_matrices=True
+    its matrix X.  Lockstep driver only."""
+    n_more = int(align_iterations)
+    if n_more < 0:
+        raise ValueError(f'align_iterations {align_iterations!r} is negative')
+    if n_more > 0 and driver not in (None, 'lockstep'):
+        raise ValueError(f"align_iterations > 0 needs the lockstep driver, not driver={driver!r}")
+    out = build_training_matrix(pairs, fs, device_index=device_index, order=order, radius=radius, frame_period=frame_period,
+                                silence_for=silence_for, rng=rng, pairs_before=pairs_before, driver=driver,
+                                lockstep=lockstep, wave_pairs=wave_pairs, f0_moments=f0_moments, gv_moments=gv_moments,
+                                keep=n_more > 0)
+    X, rest = out[0], list(out[2:])
+    cache = rest.pop(0) if n_more > 0 else None
+    history = []
+
+    def fit(X, mcd):
+        g = fit_converter(X, components=components, seed=seed, max_iter=max_iter, device_index=device_index,
+                          verbose=verbose)
+        history.append(dict(rows=int(X.shape[0]), mcd=mcd, em_iterations=int(g.n_iter_),
+                            **(dict(X=X) if keep_matrices else {})))
+        return g
+    first = None
+    if cache is not None:
+        total, cells = cache.monitor.tolist()
+        first = total / cells if cells > 0 else float('nan')
+    g = fit(X, first)
+    for _ in range(n_more):
+        X, mcd = realign_training_matrix(cache, g)
+        g = fit(X, mcd)
+    return (g, history, *rest)
 
 
 class EvalWave(TrainWave):
@@ -870,7 +1038,7 @@ class _upload_ahead:
 
 def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
                           silence_for=None, pool=None, rng=None, pairs_before=0, driver=None, lockstep=None,
-                          wave_pairs=16, f0_moments=False, gv_moments=False):
+                          wave_pairs=16, f0_moments=False, gv_moments=False, keep=False):
     """driver='lockstep' (default): waves of `wave_pairs` pairs through the batched entries on two streams
     (`TrainWave`; `lockstep`: a _Lockstep to reuse), rows appended behind a device-side cursor, one read-back per wave;
     driver='streams': round 3's pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
@@ -879,13 +1047,17 @@ def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_
     (MelCepstrumFeatureConverter.train(f0_stats=True)'s statistics; backend.f0.stats_from_moments).
     gv_moments=True: a further result (after the f0 moments when both are asked for), the numpy vector of order + 1
     values of the target side's global variance -- the column moments of every pair's trimmed target mel-cepstra as
-    the matrix path computes them, folded in pair order on the device (train(gv_stats=True)'s statistic)."""
+    the matrix path computes them, folded in pair order on the device (train(gv_stats=True)'s statistic).
+    keep=True (lockstep driver): a third result right behind (X, frames), the `TrainCache` with the alignment inputs of
+    every pair for `realign_training_matrix`; the default keeps nothing, the waves' buffers go as they went before."""
     driver = driver or ('streams' if pool is not None else 'lockstep')
+    if keep and driver != 'lockstep':
+        raise ValueError(f"build_training_matrix(keep=True) needs the lockstep driver, not driver={driver!r}")
     moments = _PairMoments(len(pairs), device_index) if f0_moments else None
     gv = _PairGV(len(pairs), order, device_index) if gv_moments else None
     if driver == 'lockstep':
         out = _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng,
-                                              pairs_before, lockstep, wave_pairs, moments, gv)
+                                              pairs_before, lockstep, wave_pairs, moments, gv, keep)
     else:
         out = _build_training_matrix_streams(pairs, fs, device_index, order, radius, frame_period, streams, silence_for,
                                              pool, rng, pairs_before, moments, gv)
@@ -950,14 +1122,15 @@ class _PairGV:
 
 
 def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng, pairs_before,
-                                    ls, wave_pairs, moments=None, gv=None):
+                                    ls, wave_pairs, moments=None, gv=None, keep=False):
     dev = torch.device('cuda', device_index)
     ls = ls if ls is not None else _Lockstep(device_index)
+    cache = TrainCache(ls, fs, order, radius) if keep else None
     K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
     scale = 2.220446049250313e-16 / fs
     wave_pairs = max(1, min(16, int(wave_pairs)))
     if not pairs:
-        return torch.empty((0, 6 * order), dtype=torch.float64, device=dev), 0
+        return (torch.empty((0, 6 * order), dtype=torch.float64, device=dev), 0) + ((cache,) if keep else ())
     if rng is not None and pairs_before:
         with torch.cuda.stream(ls.main):
             sink = [torch.empty((PAD_LEN, K), dtype=torch.float64, device=dev) for _ in range(4 * 16)]
@@ -992,7 +1165,7 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
         worst = torch.zeros(1, dtype=torch.int64, device=dev)      # min over all pairs' n_rows: < 0 = a pair was dropped
 
         def close(wave, first_pair):
-            wave.finish(X, cursor, pads)
+            wave.finish(X, cursor, pads, cache)
             with torch.cuda.stream(ls.main):
                 torch.minimum(worst, wave.n_rows.min().reshape(1), out=worst)
                 if moments is not None:
@@ -1025,7 +1198,7 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
         uploads.stop()
     torch.cuda.current_stream(dev).synchronize()
     # (a view would keep the whole capacity block alive: twice the rows actually used, or more)
-    return (X[:n_rows].clone() if n_rows * 4 < cap_rows * 3 else X[:n_rows]), frames
+    return ((X[:n_rows].clone() if n_rows * 4 < cap_rows * 3 else X[:n_rows]), frames) + ((cache,) if keep else ())
 
 
 def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,

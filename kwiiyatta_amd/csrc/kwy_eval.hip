@@ -258,6 +258,21 @@ __global__ __launch_bounds__(EV_MAX_COLS) void k_moments_merge(const double *__r
   out[3 * c + 2] = m2;
 }
 
+// sum and count behind `count` triples, added to acc[0..1] in row order by one lane: the running totals of a
+// re-alignment pass stay on the device from wave to wave
+__global__ void k_eval_accumulate(const double *__restrict__ m, int count, double *__restrict__ acc) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double sum = acc[0], n = acc[1];
+  for (int i = 0; i < count; ++i) {
+    const double ni = m[3 * (int64_t)i];
+    if (ni == 0.0) continue;
+    sum += ni * m[3 * (int64_t)i + 1];
+    n += ni;
+  }
+  acc[0] = sum;
+  acc[1] = n;
+}
+
 // ---- mel-cepstral distortion ------------------------------------------------------------------------------------------
 static int ev_check_mcd(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int cols, int first_col, const double *moments,
                         bool host) {
@@ -466,5 +481,15 @@ extern "C" int kwy_moments_merge(kwy_ctx *ctx, const double *moments, int count,
   KWY_TRY(kwy_moments_merge_dev(ctx, dm, count, width, dout));
   KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
   KWY_HIP(hipStreamSynchronize(ctx->stream));
+  return KWY_OK;
+}
+
+extern "C" int kwy_moments_accumulate_dev(kwy_ctx *ctx, const double *moments, int count, double *acc) {
+  if (!ctx) return KWY_EINVAL;
+  if (!moments || !acc || count < 0) { ctx->err = "moments_accumulate: bad argument"; return KWY_EINVAL; }
+  if (count == 0) return KWY_OK;
+  KWY_HIP(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_eval_accumulate, dim3(1), dim3(64), 0, ctx->stream, moments, count, acc);
+  KWY_HIP(hipGetLastError());
   return KWY_OK;
 }

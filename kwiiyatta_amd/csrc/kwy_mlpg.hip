@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "kwy_internal.hpp"
 
@@ -1019,20 +1020,22 @@ extern "C" int kwy_convert_mcep_dev(kwy_ctx *ctx, const double *mc, int64_t T, i
                    mc_out);
 }
 
-extern "C" int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *jobs, int count, int d, int M,
-                                          const double *model) {
-  if (!ctx) return KWY_EINVAL;
-  if (!jobs || count < 0) { ctx->err = "convert_mcep_batch: bad argument"; return KWY_EINVAL; }
-  if (count == 0) return KWY_OK;
+// a batch of conversions with a prepared model, KWY_BATCH_MAX utterances per pass of launches.  Utterance j reads the
+// d static coefficients of row t at x[j] + t * ldx and gets its trajectory at y[j] + t * ldy: the final store of
+// k_mlpg_finish runs along the coefficient index whatever the row stride, so consecutive lanes write consecutive
+// doubles of a row.  keep_in / keep_out (arrays, or null): one more column copied through (k_delta).
+static int convert_batch_strided(kwy_ctx *ctx, int count, const double *const *x, const int64_t *T, double *const *y,
+                                 const double *const *keep_in, double *const *keep_out, int ldx, int ldy, int d, int M,
+                                 const double *model) {
   size_t bytes = 0;
   for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    int64_t T = 0;
+    int64_t Tsum = 0;
     const int n = std::min(KWY_BATCH_MAX, count - j0);
     for (int j = j0; j < j0 + n; ++j) {
-      KWY_TRY(ml_check(ctx, jobs[j].mc, jobs[j].T, d, M, model, model, model, jobs[j].mc_out));
-      T += jobs[j].T;
+      KWY_TRY(ml_check(ctx, x[j], T[j], d, M, model, model, model, y[j]));
+      Tsum += T[j];
     }
-    bytes += ml_scratch_bytes(T, d, M, n);
+    bytes += ml_scratch_bytes(Tsum, d, M, n);
   }
   KWY_HIP(hipSetDevice(ctx->device));
   KWY_TRY(kwy_arena_begin(ctx, bytes));
@@ -1040,16 +1043,54 @@ extern "C" int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *j
     ml_batch bt;
     int64_t Ts[KWY_BATCH_MAX];
     bt.n = std::min(KWY_BATCH_MAX, count - j0);
-    bt.ldx = bt.ldy = d + 1;
+    bt.ldx = ldx;
+    bt.ldy = ldy;
     for (int k = 0; k < bt.n; ++k) {
-      const kwy_convert_job &q = jobs[j0 + k];
-      bt.u[k].x = q.mc + 1; bt.u[k].y = q.mc_out + 1; bt.u[k].keep_in = q.mc; bt.u[k].keep_out = q.mc_out;
-      Ts[k] = q.T;
+      bt.u[k].x = x[j0 + k]; bt.u[k].y = y[j0 + k];
+      bt.u[k].keep_in = keep_in ? keep_in[j0 + k] : nullptr;
+      bt.u[k].keep_out = keep_out ? keep_out[j0 + k] : nullptr;
+      Ts[k] = T[j0 + k];
     }
     int *status;
     KWY_TRY(mlpg_batch_core(ctx, bt, Ts, d, M, nullptr, nullptr, nullptr, 0, &status, model));
   }
   return KWY_OK;
+}
+
+extern "C" int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *jobs, int count, int d, int M,
+                                          const double *model) {
+  if (!ctx) return KWY_EINVAL;
+  if (!jobs || count < 0) { ctx->err = "convert_mcep_batch: bad argument"; return KWY_EINVAL; }
+  if (count == 0) return KWY_OK;
+  std::vector<const double *> x(count), keep_in(count);
+  std::vector<double *> y(count), keep_out(count);
+  std::vector<int64_t> T(count);
+  for (int j = 0; j < count; ++j) {
+    const kwy_convert_job &q = jobs[j];
+    // (a null matrix stays null for ml_check: no pointer arithmetic on it)
+    x[j] = q.mc ? q.mc + 1 : nullptr; y[j] = q.mc_out ? q.mc_out + 1 : nullptr;
+    keep_in[j] = q.mc; keep_out[j] = q.mc_out; T[j] = q.T;
+  }
+  return convert_batch_strided(ctx, count, x.data(), T.data(), y.data(), keep_in.data(), keep_out.data(), d + 1, d + 1, d,
+                               M, model);
+}
+
+// Re-alignment of a training pair (include/kwy.h): the conversion of kwy_convert_mcep_batch_dev, its trajectories
+// stored straight into columns 2.. of the DTW feature rows (row stride d + 2); columns 0 and 1 (the source's own power
+// and voicing terms) are not touched, and there is no T x (d + 1) intermediate.
+extern "C" int kwy_realign_features_batch_dev(kwy_ctx *ctx, const kwy_realign_job *jobs, int count, int d, int M,
+                                              const double *model) {
+  if (!ctx) return KWY_EINVAL;
+  if (!jobs || count < 0) { ctx->err = "realign_features_batch: bad argument"; return KWY_EINVAL; }
+  if (count == 0) return KWY_OK;
+  std::vector<const double *> x(count);
+  std::vector<double *> y(count);
+  std::vector<int64_t> T(count);
+  for (int j = 0; j < count; ++j) {
+    const kwy_realign_job &q = jobs[j];
+    x[j] = q.mc ? q.mc + 1 : nullptr; y[j] = q.feat ? q.feat + 2 : nullptr; T[j] = q.T;
+  }
+  return convert_batch_strided(ctx, count, x.data(), T.data(), y.data(), nullptr, nullptr, d + 1, d + 2, d, M, model);
 }
 
 extern "C" int kwy_gmm_mlpg(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,

@@ -14,6 +14,8 @@ and is compared frame by frame through the index lists of the alignment.  frames
 frames whose TARGET-side binarised power term is set (column 0 of the DTW feature: c0 within 1.636 of its maximum);
 frames='all' every aligned frame that lies inside both utterances.  The frame selection applies to the distortion;
 the f0 and voicing figures always take every aligned frame (their own voicing decision selects).
+With --align-iterations N the converter is trained with N re-alignment passes (Config), and the report starts with the
+training record: one line per fit with the rows of its joint matrix and the monitor distortion of its alignment.
 The numbers come from the kernels of kwy_eval.hip (backend.distortion); this module is the bookkeeping around them."""
 import json
 import math
@@ -211,6 +213,17 @@ def overlap_warning(trained, evaluated):
             + ', '.join(str(key) for key in both))
 
 
+def training_record_lines(converter):
+    """the record of a training with --align-iterations, a line per fit: the rows of its joint matrix and the monitor,
+    the mean distortion along the training alignment between the target and the source coefficients that alignment was
+    found with (fit 0: the source's own, fit k: converted by fit k - 1).  Nothing for a converter aligned once"""
+    history = getattr(converter, 'align_history', None) or []
+    if not getattr(converter, 'align_iterations', 0):
+        return []
+    return [f'training alignment {it}: rows {"?" if r["rows"] is None else r["rows"]} monitor MCD {r["mcd"]:.3f} dB'
+            for it, r in enumerate(history)]
+
+
 def report(names, results, total, options):
     """the --json document: the options that shape the figures, a record per file, the pooled record"""
     return dict(options=dict(options),
@@ -310,6 +323,8 @@ def main():
         total = pool(results)
     else:
         results, total = evaluate(converter, dataset, keys, **options)
+    for line in training_record_lines(converter):
+        print(line)
     for key, r in zip(keys, results):
         print(r.line(key))
     if total.frames == 0:

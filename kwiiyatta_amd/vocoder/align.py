@@ -62,10 +62,19 @@ def make_feature(f, fs, vuv='voiced', vuv_weight=9.0, power='binalize', power_we
     return rows
 
 
-def dtw_feature(x, y, vuv='voiced', power='binalize', strict=True, radius=32, **kwargs):
-    """(FastDTW distance, path as an (L, 2) integer array) between the DTW features of x and y"""
+def dtw_feature(x, y, vuv='voiced', power='binalize', strict=True, radius=32, x_mapped=None, **kwargs):
+    """(FastDTW distance, path as an (L, 2) integer array) between the DTW features of x and y.
+    x_mapped: a (frames, order) array that takes the place of x's c1..cN in its feature rows (columns 2..) -- x's
+    coefficients mapped towards y's speaker, for the re-alignment of a training set; x's power and voicing terms stay
+    its own"""
     fs = min(x.fs, y.fs)
     x_rows = make_feature(x, fs, vuv=vuv, power=power, **kwargs)
+    if x_mapped is not None:
+        x_mapped = np.asarray(x_mapped)
+        if x_mapped.shape != x_rows[:, 2:].shape:
+            raise ValueError(f'x_mapped is expected to have shape {x_rows[:, 2:].shape} (frames, order) but has '
+                             f'{x_mapped.shape}')
+        x_rows[:, 2:] = x_mapped
     y_rows = make_feature(y, fs, vuv=vuv, power=power, **kwargs)
     dist, cells = fastdtw.fastdtw(x_rows, y_rows, dist=2, radius=radius)
     path = np.array(cells, dtype=int).reshape(-1, 2)
@@ -127,9 +136,11 @@ def even_indices(a, b, pad_len=None, **kwargs):
     return xs, ys
 
 
-def align_even(a, b, pad_silence=True, pad_len=100, **kwargs):
-    """both feature sets along the warping path (same length), without the silence pads"""
-    if pad_silence:
+def align_even(a, b, pad_silence=True, pad_len=100, padded=False, **kwargs):
+    """both feature sets along the warping path (same length), without the silence pads.
+    padded=True: a and b carry their `pad_len` silent frames already (converter.dataset.PaddedDataset), nothing is
+    drawn here.  `x_mapped` (dtw_feature) passes through, as every other option does"""
+    if pad_silence and not padded:
         pad = _pkg().pad_silence
         a, b = pad(a, pad_len), pad(b, pad_len)
     xs, ys = even_indices(a, b, pad_len if pad_silence else None, **kwargs)
