@@ -15,13 +15,18 @@ Here waves of up to 16 pairs run in lockstep through the batched entries on two 
 pair-per-stream driver `TrainPair` remains as driver='streams'), ranks take contiguous blocks of pairs (the global
 row order is the pair order whatever the number of ranks), the rows land in one device tensor that
 `GaussianMixtureHIP.fit` uses as its shard, and the fitted model converts utterances wave by wave (`ConvertWave`;
-stream-parallel with `ConvertPipeline`).  The only collectives are those of the fit.
+stream-parallel with `ConvertPipeline`).  The only collectives are those of the fit.  Training, re-alignment and
+evaluation share the lockstep pair path: a wave hands its `_AlignInputs` to an `_Alignment` (FastDTW, the rows of the
+kept path, its index lists, its monitor), the rows go into a `_RowSink`, and an `_Ahead` thread prepares what the host
+would otherwise wait for.
 
 The silence padding of `align_even` draws from numpy's GLOBAL legacy generator in the reference
 (kwiiyatta/vocoder/world.py:158-161, quirk kept): the draws are made on the host, in the reference's order
 (source head, source tail, target head, target tail, pair after pair), and uploaded once per pair -- so this path
 and the Python API path produce the same matrix under `np.random.seed`.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -160,10 +165,10 @@ class TrainWave:
 
         w.analyse()   enqueue CheapTrick + D4C of all utterances and their trim lengths; the lengths start their way
                       to the host (ONE read-back per wave)
-        w.finish(X, cursor, pads)   (waits for the lengths) enqueue padding, voicing, sp2mc, DTW features, FastDTW
+        w.finish(sink, pads)   (waits for the lengths) enqueue padding, voicing, sp2mc, DTW features, FastDTW
                       (`align`, which `EvalWave` shares), strict filter + cut, deltas and the append of the joint rows
-                      behind the device-side cursor
-    """
+                      behind the sink's device-side cursor
+    `frame_period` is accepted and ignored: the frames come with the f0 tracks."""
 
     def __init__(self, ls, fs, pairs, order=24, radius=32, frame_period=5.0):
         self.ls, self.fs, self.order, self.radius = ls, int(fs), int(order), int(radius)
@@ -179,7 +184,6 @@ class TrainWave:
             # (x, f0, t) of every side: both streams may use them after the caller has dropped them
             sides = [[to_device(a, dev, (ls.main, ls.side)) for a in s] for pair in pairs for s in pair]
             self.x, self.f0, self.t = ([s[k] for s in sides] for k in range(3))
-            self.N = [len(v) for v in self.x]
             self.T = [len(v) for v in self.f0]
             self.layout = layout = Ragged([t + 2 * P for t in self.T])
             self.reg = layout.view          # reg(block, i): the padded rows of side i in one of the blocks below
@@ -197,11 +201,6 @@ class TrainWave:
             self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], self.sp[i]) for i in range(ns)])
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], self.ap[i]) for i in range(ns)])
             self.j_trim = _lib.job_array(_lib.TrimJob, [(self.sp[i], self.T[i], self.keep_dev[i:i + 1]) for i in range(ns)])
-            cap = [self.T[2 * k] + self.T[2 * k + 1] + 4 * P + 2 for k in range(self.n)]
-            self.path = [torch.zeros((c, 2), dtype=torch.int32, device=dev) for c in cap]
-            self.path_len = torch.zeros(self.n, dtype=torch.int64, device=dev)
-            self.dist = torch.zeros(self.n, **f64)
-            self.n_rows = torch.zeros(self.n, dtype=torch.int64, device=dev)
         self.frames = sum(self.T[0::2])
 
     def analyse(self):
@@ -219,22 +218,21 @@ class TrainWave:
             self.keep_ready = torch.cuda.Event()
             self.keep_ready.record(ls.main)
 
-    def finish(self, X, cursor, pads, cache=None):
+    def finish(self, sink, pads, cache=None):
         """pads(rows): fills the wave's pad rows -- a list of 4 n device views (source head, source tail, target
         head, target tail, pair after pair) -- on the main stream.  cache: a TrainCache that takes over the wave's
         alignment inputs (and its share of the monitor of this first alignment), or None"""
-        Tp = self.align(pads)
-        _train_rows(self.ls, self.order, self.reg, self.n, Tp, self.path, self.path_len, self.feat, self.feat, self.mc_pad,
-                    self.n_rows, X, cursor)
+        a = self.align(pads)
+        a.rows_into(sink)
         if cache is not None:
-            cache.add(self, Tp)
+            cache.add(a)
 
     def align(self, pads):
         """(waits for the trim lengths) enqueue padding, voicing, sp2mc, the DTW features and FastDTW of every pair;
-        sets `keep` and returns the padded lengths of the sides"""
+        sets `keep` and `alignment` and returns that `_Alignment`"""
         ls, fs, K, order, P, ns = self.ls, self.fs, self.K, self.order, PAD_LEN, 2 * self.n
         self.keep_ready.synchronize()
-        keep = [int(v) for v in self.keep_host.tolist()]
+        self.keep = keep = [int(v) for v in self.keep_host.tolist()]
         Tp = [k + 2 * P for k in keep]
         reg = self.reg
         with torch.cuda.stream(ls.main):
@@ -251,91 +249,146 @@ class TrainWave:
             chk(lib.kwy_align_features_batch_dev(h, J(_lib.AlignJob, [(reg(self.mc_pad, i), reg(self.voiced, i), Tp[i],
                                                                        reg(self.feat, i)) for i in range(ns)]),
                                                  ns, order + 1, POWER_WEIGHT, POWER_THRESHOLD, VUV_WEIGHT))
-            chk(lib.kwy_fastdtw_batch_dev(h, J(_lib.DtwJob, [(reg(self.feat, 2 * k), Tp[2 * k], reg(self.feat, 2 * k + 1),
-                                                              Tp[2 * k + 1], self.dist[k:k + 1], self.path[k],
-                                                              self.path_len[k:k + 1]) for k in range(self.n)]),
-                                          self.n, order + 2, self.radius))
-        self.keep = keep
-        return Tp
+        inputs = _AlignInputs(self.n, self.layout, Tp, keep, self.mc_pad, self.feat, self.voiced, order)
+        self.alignment = _Alignment(ls, inputs, self.radius)
+        return self.alignment
 
 
-def _train_rows(ls, order, reg, n, Tp, path, path_len, feat_x, feat_y, mc_pad, n_rows, X, cursor):
-    """enqueue (main stream) dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames and the
-    append behind the cursor for the n pairs of a wave: pair k's source features are item 2 k of `feat_x`, its target
-    features item 2 k + 1 of `feat_y`, the mel-cepstra of both items of `mc_pad`"""
-    with torch.cuda.stream(ls.main):
-        _lib.check(ls.ctx, lib.kwy_train_rows_batch_dev(
-            ls.ctx.handle,
-            _lib.job_array(_lib.TrainJob, [(path[k], path_len[k:k + 1], reg(feat_x, 2 * k), reg(feat_y, 2 * k + 1),
-                                            reg(mc_pad, 2 * k), reg(mc_pad, 2 * k + 1), Tp[2 * k], Tp[2 * k + 1],
-                                            n_rows[k:k + 1]) for k in range(n)]),
-            n, order, 1, 1, 1, PAD_LEN, TRIM_EPS, _p(X), X.shape[0], _p(cursor)))
+class _AlignInputs(namedtuple('_AlignInputs', 'n layout Tp keep mc_pad feat voiced order')):
+    """What a wave of `n` pairs hands to an alignment, and all a TrainCache keeps of it: the padded mel-cepstra, the DTW
+    features and the voicing -- blocks in the wave's ragged `layout`, item 2 k the source, 2 k + 1 the target of pair
+    k --, the padded lengths `Tp` in use and the frames `keep` that TrimmedDataset kept"""
+    __slots__ = ()
 
 
-def _monitor_wave(ls, order, reg, n, Tp, path, path_len, feat_x, feat_y, mc_pad, acc):
-    """enqueue (main stream) the monitor of a wave's alignment: along the kept path of every pair (strict filter and
-    cut: the cells kwy_train_rows_batch_dev turns into rows) the distortion in dB over c1..cN between columns 2.. of
-    the source's DTW features -- the coefficients the path was found with -- and the target's mel-cepstrum
-    (kwy_mcd_batch_dev, one workgroup per pair); the cells' sum and count are added to the two device words `acc`
-    (kwy_moments_accumulate_dev)"""
-    from .backend import distortion as dist
-    dev = ls.dev
-    with torch.cuda.stream(ls.main):
-        h = ls.ctx.handle
-        cap = [path[k].shape[0] for k in range(n)]
-        idx_x = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
-        idx_y = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
-        n_sel = torch.zeros(n, dtype=torch.int64, device=dev)
-        moments = torch.zeros((n, 3), dtype=torch.float64, device=dev)
-        jobs = []
-        for k in range(n):
-            fx, fy = reg(feat_x, 2 * k)[:Tp[2 * k]], reg(feat_y, 2 * k + 1)[:Tp[2 * k + 1]]
-            _lib.check(ls.ctx, lib.kwy_align_even_dev(h, _p(path[k]), _p(path_len[k:k + 1]), _p(fx), _p(fy), order + 2, 1, 1, 1,
-                                                      Tp[2 * k], Tp[2 * k + 1], PAD_LEN, _p(idx_x[k]), _p(idx_y[k]), cap[k],
-                                                      _p(n_sel[k:k + 1])))
+class _Alignment:
+    """One FastDTW alignment of a wave's `_AlignInputs`, enqueued on the main stream (the only place the DtwJob array is
+    built): pair k's source features are item 2 k of `feat`, its target's item 2 k + 1 -- the inputs' own features, or
+    the rewritten copy of a re-alignment -- and the mel-cepstra are both items of the inputs' `mc_pad`."""
+
+    def __init__(self, ls, inputs, radius, feat=None):
+        self.ls, self.inputs = ls, inputs
+        self.feat = feat = inputs.feat if feat is None else feat
+        n, off, Tp, reg, dev = inputs.n, inputs.layout.off, inputs.Tp, inputs.layout.view, ls.dev
+        with torch.cuda.stream(ls.main):
+            # (a path's capacity: the cells of both padded items at their untrimmed lengths, + 2)
+            self.path = [torch.zeros((off[2 * k + 2] - off[2 * k] + 2, 2), dtype=torch.int32, device=dev) for k in range(n)]
+            self.path_len = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.dist = torch.zeros(n, dtype=torch.float64, device=dev)
+            _lib.check(ls.ctx, lib.kwy_fastdtw_batch_dev(
+                ls.ctx.handle,
+                _lib.job_array(_lib.DtwJob, [(reg(feat, 2 * k), Tp[2 * k], reg(feat, 2 * k + 1), Tp[2 * k + 1],
+                                             self.dist[k:k + 1], self.path[k], self.path_len[k:k + 1]) for k in range(n)]),
+                n, inputs.order + 2, radius))
+
+    def rows_into(self, sink):
+        """enqueue dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames and the append
+        behind the cursor of the `_RowSink` for every pair; `n_rows`: the pairs' row counts, device words"""
+        ls, inp, feat = self.ls, self.inputs, self.feat
+        Tp, reg = inp.Tp, inp.layout.view
+        with torch.cuda.stream(ls.main):
+            self.n_rows = torch.zeros(inp.n, dtype=torch.int64, device=ls.dev)
+            _lib.check(ls.ctx, lib.kwy_train_rows_batch_dev(
+                ls.ctx.handle,
+                _lib.job_array(_lib.TrainJob, [(self.path[k], self.path_len[k:k + 1], reg(feat, 2 * k), reg(feat, 2 * k + 1),
+                                                reg(inp.mc_pad, 2 * k), reg(inp.mc_pad, 2 * k + 1), Tp[2 * k], Tp[2 * k + 1],
+                                                self.n_rows[k:k + 1]) for k in range(inp.n)]),
+                inp.n, inp.order, 1, 1, 1, PAD_LEN, TRIM_EPS, _p(sink.X), sink.X.shape[0], _p(sink.cursor)))
+
+    def index_lists(self, n_sel=None):
+        """enqueue dtw_feature(strict=True) + align_even's cut of every pair: -> (idx_x, idx_y, cap, n_sel), per pair the
+        kept path's index lists into the two padded items, their capacity and their length (device words: `n_sel`)"""
+        ls, inp, feat = self.ls, self.inputs, self.feat
+        n, Tp, reg, dev = inp.n, inp.Tp, inp.layout.view, ls.dev
+        with torch.cuda.stream(ls.main):
+            cap = [p.shape[0] for p in self.path]
+            idx_x = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
+            idx_y = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
+            if n_sel is None:
+                n_sel = torch.zeros(n, dtype=torch.int64, device=dev)
+            for k in range(n):
+                _lib.check(ls.ctx, lib.kwy_align_even_dev(
+                    ls.ctx.handle, _p(self.path[k]), _p(self.path_len[k:k + 1]), _p(reg(feat, 2 * k)), _p(reg(feat, 2 * k + 1)),
+                    inp.order + 2, 1, 1, 1, Tp[2 * k], Tp[2 * k + 1], PAD_LEN, _p(idx_x[k]), _p(idx_y[k]), cap[k],
+                    _p(n_sel[k:k + 1])))
+        return idx_x, idx_y, cap, n_sel
+
+    def monitor(self, acc):
+        """enqueue the monitor of this alignment: along the kept path of every pair (`index_lists`: the cells that
+        `rows_into` turns into rows) the distortion in dB over c1..cN between columns 2.. of the source's DTW features
+        -- the coefficients the path was found with -- and the target's mel-cepstrum (kwy_mcd_batch_dev, one workgroup
+        per pair); the cells' sum and count are added to the two device words `acc` (kwy_moments_accumulate_dev)"""
+        from .backend import distortion as dist
+        ls, inp = self.ls, self.inputs
+        n, Tp, reg = inp.n, inp.Tp, inp.layout.view
+        with torch.cuda.stream(ls.main):
+            idx_x, idx_y, cap, n_sel = self.index_lists()
+            moments = torch.zeros((n, 3), dtype=torch.float64, device=ls.dev)
             # (column 1 of the features, the voicing term, stands where c0 stands in a mel-cepstrum: first_col = 1)
-            jobs.append(dist.mcd_job(fx[:, 1:], reg(mc_pad, 2 * k + 1)[:Tp[2 * k + 1]], idx_a=idx_x[k], idx_b=idx_y[k],
-                                     rows=cap[k], n_dev=n_sel[k:k + 1]))
-        dist.mcd_batch_dev(ls.ctx, jobs, order + 1, moments)
-        _lib.check(ls.ctx, lib.kwy_moments_accumulate_dev(h, _p(moments), n, _p(acc)))
+            jobs = [dist.mcd_job(reg(self.feat, 2 * k)[:Tp[2 * k], 1:], reg(inp.mc_pad, 2 * k + 1)[:Tp[2 * k + 1]],
+                                 idx_a=idx_x[k], idx_b=idx_y[k], rows=cap[k], n_dev=n_sel[k:k + 1]) for k in range(n)]
+            dist.mcd_batch_dev(ls.ctx, jobs, inp.order + 1, moments)
+            _lib.check(ls.ctx, lib.kwy_moments_accumulate_dev(ls.ctx.handle, _p(moments), n, _p(acc)))
 
 
-class _CachedWave:
-    """the alignment inputs of one wave of pairs: blocks in the wave's ragged layout (item 2 k the source, 2 k + 1 the
-    target of pair k), the padded lengths in use, the frames TrimmedDataset kept and the lengths of the first paths"""
+class _RowSink:
+    """A training matrix being filled on the main stream: the capacity block `X`, the device-side `cursor` that
+    kwy_train_rows_batch_dev appends behind, and `worst`, the minimum over all pairs' row counts (k_tr_rows_place marks
+    a pair that did not fit behind the cursor with -1 - rows and drops it)."""
 
-    def __init__(self, wave, Tp):
-        self.n, self.layout, self.Tp, self.keep = wave.n, wave.layout, list(Tp), list(wave.keep)
-        self.mc_pad, self.feat, self.voiced = wave.mc_pad, wave.feat, wave.voiced
-        self.path_cap = [p.shape[0] for p in wave.path]
-        self.path_len = wave.path_len            # cells of the first alignment's FastDTW paths (n device words)
+    def __init__(self, ls, cap_rows, order):
+        self.ls, self.cap_rows = ls, cap_rows
+        with torch.cuda.stream(ls.main):
+            self.X = torch.empty((cap_rows, 6 * order), dtype=torch.float64, device=ls.dev)
+            self.cursor = torch.zeros(1, dtype=torch.int64, device=ls.dev)
+            self.worst = torch.zeros(1, dtype=torch.int64, device=ls.dev)
+
+    def take(self, n_rows):
+        """enqueue the fold of a wave's row counts into `worst`"""
+        with torch.cuda.stream(self.ls.main):
+            torch.minimum(self.worst, n_rows.min().reshape(1), out=self.worst)
+
+    def close(self, extra=()):
+        """the ONE read-back of a matrix: -> (the rows written, the `extra` int64 device words as host ints)"""
+        cap_rows = self.cap_rows
+        with torch.cuda.stream(self.ls.main):
+            words = torch.cat((self.cursor, self.worst, *extra)).tolist()
+        self.ls.sync()
+        n_rows, dropped = int(words[0]), int(words[1])
+        if dropped < 0:
+            # (the capacity, a row per frame of both sides, bounds every pair's rows: a bug, never a data property)
+            raise RuntimeError(f'training matrix: a pair of {-1 - dropped} rows did not fit the capacity of {cap_rows}')
+        torch.cuda.current_stream(self.ls.dev).synchronize()
+        # (a view would keep the whole capacity block alive: twice the rows actually used, or more)
+        return (self.X[:n_rows].clone() if n_rows * 4 < cap_rows * 3 else self.X[:n_rows]), words[2:]
 
 
 class TrainCache:
     """What a second alignment of the training set needs of the first, kept in HBM: per wave of pairs the padded
     mel-cepstra `mc_pad`, the DTW features `feat` of the first alignment, the voicing `voiced`, the padded lengths and
-    the kept frames -- ragged blocks in `_blocks.Ragged` layout, the waves' own buffers taken over as they are.  The
-    padded envelopes and aperiodicities (sp_pad, ap_pad: 2 x 1025 doubles per frame at 48 kHz) are NOT kept; without
-    the cache a second pass would have to analyse every pair again.
+    the kept frames -- the waves' `_AlignInputs`: ragged blocks in `_blocks.Ragged` layout, the waves' own buffers taken
+    over as they are.  The padded envelopes and aperiodicities (sp_pad, ap_pad: 2 x 1025 doubles per frame at 48 kHz)
+    are NOT kept; without the cache a second pass would have to analyse every pair again.
     Size: (order + 1) + (order + 2) + 1 doubles per padded frame of both sides -- 416 bytes (0.41 KiB) at order 24;
     bench_corpus.py's 503 pairs of 5 s (1001 + 200 padded frames a side) take 2 x 1201 x 416 B = 1.0 MB a pair,
     0.50 GB in all.
-    `monitor`: two device words, sum and count of the first alignment's monitor (see `_monitor_wave`)."""
+    `monitor`: two device words, sum and count of the first alignment's monitor (see `_Alignment.monitor`);
+    `path_len`: per wave the cells of the first alignment's FastDTW paths (n device words)."""
 
     def __init__(self, ls, fs, order, radius):
         self.ls, self.fs, self.order, self.radius = ls, int(fs), int(order), int(radius)
-        self.waves = []
+        self.waves, self.path_len = [], []
         self.monitor = torch.zeros(2, dtype=torch.float64, device=ls.dev)
 
     pairs = property(lambda self: sum(w.n for w in self.waves))
     frames = property(lambda self: sum(sum(w.Tp) for w in self.waves))
     nbytes = property(lambda self: sum(t.numel() * 8 for w in self.waves for t in (w.mc_pad, w.feat, w.voiced)))
 
-    def add(self, wave, Tp):
-        self.waves.append(_CachedWave(wave, Tp))
+    def add(self, alignment):
+        self.waves.append(alignment.inputs)
+        self.path_len.append(alignment.path_len)
         # (its scratch is made and dropped on the main stream: reused there only behind the queued work)
-        _monitor_wave(self.ls, self.order, wave.reg, wave.n, Tp, wave.path, wave.path_len, wave.feat, wave.feat, wave.mc_pad,
-                      self.monitor)
+        alignment.monitor(self.monitor)
 
 
 def realign_training_matrix(cache, gmm, paths=None):
@@ -345,49 +398,33 @@ def realign_training_matrix(cache, gmm, paths=None):
     into columns 2.. of a COPY of their DTW features (kwy_realign_features_batch_dev; the cache's first-alignment
     features stay as they are, power and voicing terms are the source's own), FastDTW runs on them against the targets'
     unchanged features, and the joint rows of the ORIGINAL mel-cepstra along the new paths go behind a device-side
-    cursor (kwy_train_rows_batch_dev).  mcd_mean: the monitor of this alignment (`_monitor_wave`).  One read-back.
+    cursor (kwy_train_rows_batch_dev).  mcd_mean: the monitor of this alignment (`_Alignment.monitor`).  One read-back.
     paths: a list that receives, pair after pair, the (FastDTW path, its length) device tensors of this pass."""
     import struct
     ls, order, dev = cache.ls, cache.order, cache.ls.dev
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     if dg.D2 != 6 * order:
         raise ValueError(f'realign_training_matrix: the mixture has {dg.D2} joint dimensions, the cache order {order}')
-    cap_rows = cache.frames               # a pair yields at most one row per cell of its path
-    J = _lib.job_array
+    sink = _RowSink(ls, cache.frames, order)      # a pair yields at most one row per cell of its path
     with torch.cuda.stream(ls.main):
         model = dg.model(diff=False)
-        X = torch.empty((cap_rows, 6 * order), dtype=torch.float64, device=dev)
-        cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-        worst = torch.zeros(1, dtype=torch.int64, device=dev)
         acc = torch.zeros(2, dtype=torch.float64, device=dev)
         for w in cache.waves:
-            n, reg, Tp = w.n, w.layout.view, w.Tp
-            h = ls.ctx.handle
+            reg = w.layout.view
             feat = w.feat.clone()                  # the sources' items are rewritten below, the targets' only read
-            path = [torch.zeros((c, 2), dtype=torch.int32, device=dev) for c in w.path_cap]
-            path_len = torch.zeros(n, dtype=torch.int64, device=dev)
-            dist_ = torch.zeros(n, dtype=torch.float64, device=dev)
-            n_rows = torch.zeros(n, dtype=torch.int64, device=dev)
             _lib.check(ls.ctx, lib.kwy_realign_features_batch_dev(
-                h, J(_lib.RealignJob, [(reg(w.mc_pad, 2 * k), Tp[2 * k], reg(feat, 2 * k)) for k in range(n)]), n, order,
-                dg.M, _p(model)))
-            _lib.check(ls.ctx, lib.kwy_fastdtw_batch_dev(
-                h, J(_lib.DtwJob, [(reg(feat, 2 * k), Tp[2 * k], reg(feat, 2 * k + 1), Tp[2 * k + 1], dist_[k:k + 1], path[k],
-                                    path_len[k:k + 1]) for k in range(n)]), n, order + 2, cache.radius))
-            _train_rows(ls, order, reg, n, Tp, path, path_len, feat, feat, w.mc_pad, n_rows, X, cursor)
-            _monitor_wave(ls, order, reg, n, Tp, path, path_len, feat, feat, w.mc_pad, acc)
-            torch.minimum(worst, n_rows.min().reshape(1), out=worst)
+                ls.ctx.handle, _lib.job_array(_lib.RealignJob, [(reg(w.mc_pad, 2 * k), w.Tp[2 * k], reg(feat, 2 * k))
+                                                                for k in range(w.n)]), w.n, order, dg.M, _p(model)))
+            a = _Alignment(ls, w, cache.radius, feat=feat)
+            a.rows_into(sink)
+            a.monitor(acc)
+            sink.take(a.n_rows)
             # (the wave's scratch -- feat, path, ... -- was made on the main stream: freed here, reused there in order)
             if paths is not None:
-                paths.extend((path[k], path_len[k:k + 1]) for k in range(n))
-        words = torch.cat((cursor, worst, acc.view(torch.int64))).tolist()     # ONE read-back
-    ls.sync()
-    n_rows, dropped = int(words[0]), int(words[1])
-    total, cells = struct.unpack('<2d', struct.pack('<2q', *words[2:]))
-    if dropped < 0:
-        raise RuntimeError(f'training matrix: a pair of {-1 - dropped} rows did not fit the capacity of {cap_rows}')
-    torch.cuda.current_stream(dev).synchronize()
-    return (X[:n_rows].clone() if n_rows * 4 < cap_rows * 3 else X[:n_rows]), (total / cells if cells > 0 else float('nan'))
+                paths.extend((a.path[k], a.path_len[k:k + 1]) for k in range(w.n))
+    X, words = sink.close(extra=(acc.view(torch.int64),))
+    total, cells = struct.unpack('<2d', struct.pack('<2q', *words))
+    return X, (total / cells if cells > 0 else float('nan'))
 
 
 def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterations=0, max_iter=100, device_index=0,
@@ -399,7 +436,7 @@ def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterati
     from scratch (same components, seed, stopping rule).  The pads are drawn once -- numpy's global generator or the
     device-drawn stream (`rng`, `pairs_before`) advance as they do for align_iterations = 0 -- and the f0 / global
     variance moments are the first pass's.  Returns (mixture, history[, f0 moments][, gv statistic]): history holds a
-    dict per fit -- rows, mcd (the alignment's monitor, `_monitor_wave`), em_iterations -- and with keep_matrices=True
+    dict per fit -- rows, mcd (the alignment's monitor, `_Alignment.monitor`), em_iterations -- and with keep_matrices=True
     its matrix X.  Lockstep driver only."""
     n_more = int(align_iterations)
     if n_more < 0:
@@ -438,13 +475,14 @@ class EvalWave(TrainWave):
     entry, then the global-variance postfilter when asked for), and measured along the index lists that
     kwy_align_even_dev leaves on the device (kwy_mcd_batch_dev, kwy_f0_error_batch_dev: no gathered copies, the row
     counts stay device words).  Nothing is read back here: `measure` writes pair k's figures into row first + k of the
-    caller's tensors."""
+    caller's tensors.  `frame_period` is accepted and ignored, as in TrainWave."""
 
     def measure(self, pads, gmm, model, tot, first, frames='speech', gv=None, gv_strength=0.0, f0_stats=None,
                 transpose_key=0.0, per_frame=False):
         """tot: the _EvalTotals of the corpus; gv / f0_stats: device tensors (order + 1 values / 4 values) or None"""
         from .backend import distortion as dist
-        Tp = self.align(pads)
+        a = self.align(pads)
+        Tp = a.inputs.Tp
         ls, fs, order, P, n, reg, keep = self.ls, self.fs, self.order, PAD_LEN, self.n, self.reg, self.keep
         dev, cols = ls.dev, self.order + 1
         f64 = dict(dtype=torch.float64, device=dev)
@@ -453,14 +491,7 @@ class EvalWave(TrainWave):
             chk = lambda rc: _lib.check(ls.ctx, rc)  # noqa: E731
             J = _lib.job_array
             # dtw_feature(strict=True) + align_even's cut: the index lists and their count stay on the device
-            cap = [self.path[k].shape[0] for k in range(n)]
-            self.idx_x = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
-            self.idx_y = [torch.zeros(c, dtype=torch.int32, device=dev) for c in cap]
-            n_sel = tot.aligned[first:first + n]
-            for k in range(n):
-                chk(lib.kwy_align_even_dev(h, _p(self.path[k]), _p(self.path_len[k:k + 1]), _p(reg(self.feat, 2 * k)),
-                                           _p(reg(self.feat, 2 * k + 1)), order + 2, 1, 1, 1, Tp[2 * k], Tp[2 * k + 1], P,
-                                           _p(self.idx_x[k]), _p(self.idx_y[k]), cap[k], _p(n_sel[k:k + 1])))
+            self.idx_x, self.idx_y, cap, n_sel = a.index_lists(tot.aligned[first:first + n])
             # the trimmed utterances inside their padded blocks
             src_mc = [reg(self.mc_pad, 2 * k)[P:P + keep[2 * k]] for k in range(n)]
             tgt_mc = [reg(self.mc_pad, 2 * k + 1)[P:P + keep[2 * k + 1]] for k in range(n)]
@@ -609,31 +640,31 @@ class ConvertPipeline(_Graphed):
         T, order, fs, fc = self.T, self.order, self.fs, self.mcep_fs
         EPS = 2.220446049250313e-16
         up_first = fc > fs
-        if True:                    # (one block: the order below IS the order of the reference's calls)
-            # MelCepstrum.resample_data(fc): spectrum on our grid, cut / extended, coefficients with the new alpha
-            chk(lib.kwy_mc2sp_dev(h, _p(self.mc), T, order, self.alpha, self.fft, _p(self.spec_u)))
-            if up_first:
-                self.rng.stream.wait_stream(self.stream)
-                self.rng.abs_normal(EPS / fs, out=self.silent)
-                self.stream.wait_event(self.rng.record_event())
-                self.there[:, :self.K].copy_(self.spec_u)
-                self.there[:, self.K:].copy_(self.silent)
-            else:
-                self.there.copy_(self.spec_u[:, :self.n_there])
-            chk(lib.kwy_sp2mc_dev(h, _p(self.there), T, self.n_there, order, self.alpha_c, _p(self.mc_c)))
-            # the conversion itself, at the converter's rate (c0 kept)
-            chk(lib.kwy_convert_mcep_dev(h, _p(self.mc_c), T, order, self.gmm.M, _p(self.gmm_model), _p(self.mc_c2)))
-            # `feature.mel_cepstrum = converted` -> resample_data(fs): back through the converter rate's grid
-            chk(lib.kwy_mc2sp_dev(h, _p(self.mc_c2), T, order, self.alpha_c, 2 * (self.Kc - 1), _p(self.spec_c)))
-            if not up_first:
-                self.rng.stream.wait_stream(self.stream)
-                self.rng.abs_normal(EPS / fc, out=self.silent)
-                self.stream.wait_event(self.rng.record_event())
-                self.back[:, :self.Kc].copy_(self.spec_c)
-                self.back[:, self.Kc:].copy_(self.silent)
-            else:
-                self.back.copy_(self.spec_c[:, :self.n_back])
-            chk(lib.kwy_sp2mc_dev(h, _p(self.back), T, self.n_back, order, self.alpha, _p(self.mc_conv)))
+        # (one block: the order below IS the order of the reference's calls)
+        # MelCepstrum.resample_data(fc): spectrum on our grid, cut / extended, coefficients with the new alpha
+        chk(lib.kwy_mc2sp_dev(h, _p(self.mc), T, order, self.alpha, self.fft, _p(self.spec_u)))
+        if up_first:
+            self.rng.stream.wait_stream(self.stream)
+            self.rng.abs_normal(EPS / fs, out=self.silent)
+            self.stream.wait_event(self.rng.record_event())
+            self.there[:, :self.K].copy_(self.spec_u)
+            self.there[:, self.K:].copy_(self.silent)
+        else:
+            self.there.copy_(self.spec_u[:, :self.n_there])
+        chk(lib.kwy_sp2mc_dev(h, _p(self.there), T, self.n_there, order, self.alpha_c, _p(self.mc_c)))
+        # the conversion itself, at the converter's rate (c0 kept)
+        chk(lib.kwy_convert_mcep_dev(h, _p(self.mc_c), T, order, self.gmm.M, _p(self.gmm_model), _p(self.mc_c2)))
+        # `feature.mel_cepstrum = converted` -> resample_data(fs): back through the converter rate's grid
+        chk(lib.kwy_mc2sp_dev(h, _p(self.mc_c2), T, order, self.alpha_c, 2 * (self.Kc - 1), _p(self.spec_c)))
+        if not up_first:
+            self.rng.stream.wait_stream(self.stream)
+            self.rng.abs_normal(EPS / fc, out=self.silent)
+            self.stream.wait_event(self.rng.record_event())
+            self.back[:, :self.Kc].copy_(self.spec_c)
+            self.back[:, self.Kc:].copy_(self.silent)
+        else:
+            self.back.copy_(self.spec_c[:, :self.n_back])
+        chk(lib.kwy_sp2mc_dev(h, _p(self.back), T, self.n_back, order, self.alpha, _p(self.mc_conv)))
 
     def run(self):
         h, fs, fft, K, order, T = self.ctx.handle, self.fs, self.fft, self.K, self.order, self.T
@@ -660,6 +691,27 @@ class ConvertPipeline(_Graphed):
         if self.mcep_fs is not None and self.rng is not None and self.rng.ctx is not self.ctx:
             cs.append(self.rng.ctx)
         return cs
+
+
+def _gv_on_device(gv_stats, gv_strength, order, dev, on=True):
+    """the options of the global-variance postfilter, checked before anything is put on the device: -> the order + 1
+    statistics as a device tensor, or None when nothing is filtered (strength 0, or on=False: no conversion)"""
+    if not 0.0 <= float(gv_strength) <= 1.0:
+        raise ValueError(f'global variance: strength {gv_strength!r} is outside [0, 1]')
+    if not (on and gv_strength > 0):
+        return None
+    if gv_stats is None:
+        raise ValueError('global variance: gv_strength > 0 needs gv_stats')
+    gv = to_device(gv_stats, dev, dtype=np.float64).to(dev)     # (.to: a tensor may come from the host)
+    if gv.shape != (order + 1,) or gv.dtype != torch.float64:
+        raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
+    return gv
+
+
+def _f0_stats_on_device(f0_stats, dev):
+    """(mu_src, sigma_src, mu_tgt, sigma_tgt) as 4 doubles on the device (a 4-tuple, or such a tensor already), or None"""
+    return None if f0_stats is None else torch.as_tensor(f0_stats if torch.is_tensor(f0_stats) else list(f0_stats),
+                                                         dtype=torch.float64, device=dev)
 
 
 class ConvertWave:
@@ -735,8 +787,7 @@ class ConvertWave:
             self.f0_synth, self.f0_map_status = self.f0, None
             self.transpose_key = float(transpose_key)
             if f0_stats is not None or self.transpose_key != 0:
-                self.f0_stats = None if f0_stats is None else torch.as_tensor(
-                    f0_stats if torch.is_tensor(f0_stats) else list(f0_stats), dtype=torch.float64, device=dev)
+                self.f0_stats = _f0_stats_on_device(f0_stats, dev)
                 self.f0_synth_all = torch.empty(self.rows, **f64)
                 self.f0_synth = rows.views(self.f0_synth_all)
                 self.f0_map_status = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -774,14 +825,8 @@ class ConvertWave:
                     self.j_fin_diff = _lib.job_array(_lib.FinishJob, [(self.wave_diff[i], self.x[i].numel(), 0, self.pcm_diff[i])
                                                                       for i in range(n)])
             self.gv_status, self.gv_strength = None, float(gv_strength)
-            if not 0.0 <= self.gv_strength <= 1.0:
-                raise ValueError(f'global variance: strength {gv_strength!r} is outside [0, 1]')
-            if self.gv_strength > 0 and gmm is not None:
-                if gv_stats is None:
-                    raise ValueError('global variance: gv_strength > 0 needs gv_stats')
-                self.gv = to_device(gv_stats, dev, dtype=np.float64).to(dev)     # (.to: a tensor may come from the host)
-                if self.gv.shape != (order + 1,) or self.gv.dtype != torch.float64:
-                    raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
+            self.gv = _gv_on_device(gv_stats, gv_strength, order, dev, on=gmm is not None)
+            if self.gv is not None:
                 self.gv_moments = torch.empty((n, order + 1, 3), **f64)
                 self.gv_status = torch.zeros(n, dtype=torch.int32, device=dev)
                 self.j_gv_mom = _lib.job_array(_lib.GvMatrix, [(conv[i], self.T[i]) for i in range(n)])
@@ -860,7 +905,8 @@ class ConvertWave:
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
                     f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0):
-    """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view[, pcm view]) on the main stream.
+    """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
+    view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
     global-variance postfilter) are read back ONCE at the end."""
     ls = ls if ls is not None else _Lockstep(device_index)
@@ -872,12 +918,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
-                if diff:
-                    keep(w0 + i, wv.wave[i], wv.pcm[i] if pcm else None, wv.wave_diff[i], wv.pcm_diff[i] if pcm else None)
-                elif pcm:
-                    keep(w0 + i, wv.wave[i], wv.pcm[i])
-                else:
-                    keep(w0 + i, wv.wave[i])
+                keep(w0 + i, wv.wave[i], wv.pcm[i] if pcm else None, wv.wave_diff[i] if wv.diff else None,
+                     wv.pcm_diff[i] if wv.diff and pcm else None)
         if wv.f0_status is not None:
             status.append(wv.f0_status)
         if wv.f0_map_status is not None:
@@ -955,56 +997,16 @@ def shard_block(n_items, rank, world_size):
     return list(range(lo, hi))
 
 
-class _silence_ahead:
-    """The pad spectra of `n_pairs` pairs, drawn by a helper thread in pair order from numpy's global legacy generator
-    (the reference's source, `draw_silence`) while the caller enqueues GPU work: the generator is serial (4.6 ms per
-    pair at 48 kHz) and numpy releases the GIL inside it.  The caller must not use `np.random` between construction
-    and `stop()`; `stop()` (always called by build_training_matrix, also when a pair raises) ends the thread, so a
-    failed run does not leave a thread behind that keeps consuming global draws."""
+class _Ahead:
+    """The items of an iterable, evaluated on a helper thread at most `depth` ahead of the consumer, while the caller
+    enqueues GPU work.  An exception of the producer is handed over: `get()` raises it where the item would have been.
+    `stop()` (the drivers always call it, also when a pair raises) ends the thread: none is left behind producing."""
 
-    def __init__(self, n_pairs, fs, depth):
-        import queue
-        import threading
-        K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
-        self.q = queue.Queue(maxsize=max(1, depth))
-        self.halt = threading.Event()
-
-        def work():
-            for _ in range(n_pairs):
-                item = [draw_silence(fs, K) for _ in range(4)]
-                while not self.halt.is_set():
-                    try:
-                        self.q.put(item, timeout=0.05)
-                        break
-                    except queue.Full:
-                        continue
-                if self.halt.is_set():
-                    return
-        self.thread = threading.Thread(target=work, daemon=True)
-        self.thread.start()
-
-    def get(self):
-        return self.q.get()
-
-    def stop(self):
-        self.halt.set()
-        self.thread.join(timeout=5.0)
-
-
-class _upload_ahead:
-    """The waveforms, f0 tracks and frame times of the pairs as device tensors, uploaded by a helper thread in pair
-    order while the caller enqueues GPU work: a copy from pageable host memory blocks its caller (0.2 ms per 5 s
-    waveform at 48 kHz, six copies per pair: 0.5 ms of the ~1.3 ms of host time a pair costs) and releases the
-    interpreter lock meanwhile.  A copy is complete when the helper hands the tensors over.  `stop()` ends the thread."""
-
-    def __init__(self, pairs, dev, depth):
+    def __init__(self, items, depth):
         import queue
         import threading
         self.q = queue.Queue(maxsize=max(1, depth))
         self.halt = threading.Event()
-
-        def side_up(side):
-            return tuple(to_device(a, dev) for a in side)
 
         def hand(item):
             while not self.halt.is_set():
@@ -1017,10 +1019,10 @@ class _upload_ahead:
 
         def work():
             try:
-                for it in pairs:
-                    if not hand(tuple(side_up(side) for side in it)):
+                for item in items:
+                    if not hand(item):
                         return
-            except Exception as exc:        # handed to the consumer: it raises where the pair would have been built
+            except Exception as exc:
                 hand(exc)
         self.thread = threading.Thread(target=work, daemon=True)
         self.thread.start()
@@ -1036,12 +1038,29 @@ class _upload_ahead:
         self.thread.join(timeout=5.0)
 
 
+def _pair_silences(n_pairs, fs):
+    """the pad spectra of consecutive pairs, drawn from numpy's global legacy generator (the reference's source,
+    `draw_silence`).  On an `_Ahead` thread: the generator is serial (4.6 ms per pair at 48 kHz) and numpy releases the
+    GIL inside it.  The caller must not use `np.random` until `stop()`, after which no global draws are consumed."""
+    K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
+    for _ in range(n_pairs):
+        yield [draw_silence(fs, K) for _ in range(4)]
+
+
+def _pair_uploads(pairs, dev):
+    """the waveforms, f0 tracks and frame times of consecutive pairs as device tensors, each copy complete when handed
+    over.  On an `_Ahead` thread: a copy from pageable host memory blocks its caller (0.2 ms per 5 s waveform at 48 kHz,
+    six copies per pair: 0.5 ms of the ~1.3 ms of host time a pair costs) and releases the interpreter lock meanwhile."""
+    for pair in pairs:
+        yield tuple(tuple(to_device(a, dev) for a in side) for side in pair)
+
+
 def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
                           silence_for=None, pool=None, rng=None, pairs_before=0, driver=None, lockstep=None,
                           wave_pairs=16, f0_moments=False, gv_moments=False, keep=False):
     """driver='lockstep' (default): waves of `wave_pairs` pairs through the batched entries on two streams
     (`TrainWave`; `lockstep`: a _Lockstep to reuse), rows appended behind a device-side cursor, one read-back per wave;
-    driver='streams': round 3's pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
+    driver='streams': the pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
     f0_moments=True: a third result, the (2, 3) numpy array of the merged voiced log-f0 moments (n, mean, M2) of the
     source and of the target side -- each side's trimmed f0 tracks, merged in pair order on the device
     (MelCepstrumFeatureConverter.train(f0_stats=True)'s statistics; backend.f0.stats_from_moments).
@@ -1139,8 +1158,8 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
                 take = min(16, left)
                 rng.abs_normal_blocks(scale, sink[:4 * take], ctx=ls.ctx)
                 left -= take
-    ahead = _silence_ahead(len(pairs), fs, 2 * wave_pairs) if silence_for is None and rng is None else None
-    uploads = _upload_ahead(pairs, dev, 3 * wave_pairs)
+    ahead = _Ahead(_pair_silences(len(pairs), fs), 2 * wave_pairs) if silence_for is None and rng is None else None
+    uploads = _Ahead(_pair_uploads(pairs, dev), 3 * wave_pairs)
     # capacity of the matrix: a pair yields at most one row per path cell of its un-padded stretch
     cap_rows = sum(len(p[0][1]) + len(p[1][1]) for p in pairs)
     frames = 0
@@ -1158,16 +1177,13 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
         done[0] += n_pairs
 
     try:
-        with torch.cuda.stream(ls.main):
-            X = torch.empty((cap_rows, 6 * order), dtype=torch.float64, device=dev)
-            cursor = torch.zeros(1, dtype=torch.int64, device=dev)
-        prev, held = None, []
-        worst = torch.zeros(1, dtype=torch.int64, device=dev)      # min over all pairs' n_rows: < 0 = a pair was dropped
+        matrix = _RowSink(ls, cap_rows, order)
+        prev, held = None, []           # prev: the wave that waits for its trim lengths, and its first pair
 
         def close(wave, first_pair):
-            wave.finish(X, cursor, pads, cache)
+            wave.finish(matrix, pads, cache)
+            matrix.take(wave.alignment.n_rows)
             with torch.cuda.stream(ls.main):
-                torch.minimum(worst, wave.n_rows.min().reshape(1), out=worst)
                 if moments is not None:
                     moments.add(ls.ctx, first_pair, [f[:k] for f, k in zip(wave.f0, wave.keep)])
                 if gv is not None:
@@ -1178,27 +1194,19 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
             wave = TrainWave(ls, fs, chunk, order=order, radius=radius, frame_period=frame_period)
             wave.analyse()                     # enqueued BEFORE the host waits for the previous wave's lengths
             if prev is not None:
-                close(prev, w0 - wave_pairs)
-                held.append(prev)
+                close(*prev)
+                held.append(prev[0])
             frames += wave.frames
-            prev = wave
+            prev = (wave, w0)
             while len(held) > 2:
                 held.pop(0)                    # (its buffers: all uses are ordered on the main stream before reuse)
-        close(prev, (len(pairs) - 1) // wave_pairs * wave_pairs)
-        with torch.cuda.stream(ls.main):
-            n_rows, dropped = (int(v) for v in torch.cat((cursor, worst)).tolist())     # ONE read-back
-        ls.sync()
-        if dropped < 0:
-            # k_tr_rows_place marks a pair that did not fit behind the cursor with -1 - rows and drops it; the capacity
-            # above (one row per frame of both sides) bounds every pair's rows, so this is a bug, never a data property
-            raise RuntimeError(f'training matrix: a pair of {-1 - dropped} rows did not fit the capacity of {cap_rows}')
+        close(*prev)
+        X, _ = matrix.close()
     finally:
         if ahead is not None:
             ahead.stop()
         uploads.stop()
-    torch.cuda.current_stream(dev).synchronize()
-    # (a view would keep the whole capacity block alive: twice the rows actually used, or more)
-    return ((X[:n_rows].clone() if n_rows * 4 < cap_rows * 3 else X[:n_rows]), frames) + ((cache,) if keep else ())
+    return (X, frames) + ((cache,) if keep else ())
 
 
 def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
@@ -1223,8 +1231,8 @@ def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=3
             sink = [torch.empty((PAD_LEN, K), dtype=torch.float64, device=dev) for _ in range(4)]
             for _ in range(pairs_before):
                 rng.abs_normal_blocks(scale, sink)
-    ahead = _silence_ahead(len(pairs), fs, 2 * len(pool)) if silence_for is None and rng is None and pairs else None
-    uploads = _upload_ahead(pairs, dev, 2 * len(pool)) if pairs else None
+    ahead = _Ahead(_pair_silences(len(pairs), fs), 2 * len(pool)) if silence_for is None and rng is None and pairs else None
+    uploads = _Ahead(_pair_uploads(pairs, dev), 2 * len(pool)) if pairs else None
     blocks, frames = [], 0
 
     def finish(wave, first_pair):
@@ -1335,7 +1343,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     diff=True appends the differential outputs (the inputs through the MLSA filter of the differential conversion,
     convert_voice.py's .diff.wav): (waveforms, pcm or None, diff waveforms, diff pcm or None).
     driver='lockstep' (default): waves of 16 utterances through the batched entries on two streams (`ConvertWave`);
-    'streams': round 3's utterance-per-stream driver, see `_stream_batch` for its scheduling.
+    'streams': the utterance-per-stream driver, see `_stream_batch` for its scheduling.
     f0_stats / transpose_key (lockstep driver): the waveforms are synthesised on the mapped f0 (ConvertWave); a frame
     out of the map's range raises ValueError after the batch.
     gv_stats / gv_strength (lockstep driver): gv_strength > 0 runs the global-variance postfilter on the converted
@@ -1347,7 +1355,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     if driver == 'lockstep':
         pcms, dwav, dpcm = ([None] * len(utterances) for _ in range(3))
 
-        def keep_view(i, w, p=None, wd=None, pd=None):
+        def keep_view(i, w, p, wd, pd):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
                         f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength)
@@ -1382,7 +1390,7 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
         frames += len(u[1])
     driver = driver or ('streams' if pool is not None else 'lockstep')
     if driver == 'lockstep':
-        def keep_view(i, w):
+        def keep_view(i, w, *_):
             if out is not None:
                 out[i].copy_(w)
                 res[i] = out[i]
@@ -1426,11 +1434,9 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     if converter_fs is not None and int(converter_fs) != int(fs):
         raise ValueError(f'evaluate_batch: the pairs are at {fs} Hz, the converter at {converter_fs} Hz; pairs of another '
                          f'sampling rate go through evaluate_voice.evaluate_pair')
-    if not 0.0 <= float(gv_strength) <= 1.0:
-        raise ValueError(f'global variance: strength {gv_strength!r} is outside [0, 1]')
-    if gv_strength > 0 and gv_stats is None:
-        raise ValueError('global variance: gv_strength > 0 needs gv_stats')
     dev = torch.device('cuda', device_index)
+    gv = _gv_on_device(gv_stats, gv_strength, order, dev)       # (raises before anything else is put on the device)
+    stats = _f0_stats_on_device(f0_stats, dev)
     zero = dict(mcd_moments=(0.0, 0.0, 0.0), source_moments=(0.0, 0.0, 0.0), f0_moments=(0.0, 0.0, 0.0),
                 counts=(0, 0, 0, 0), aligned=0, outside=0)
     if not pairs:
@@ -1443,13 +1449,6 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     with torch.cuda.stream(ls.main):
         model = dg.model(diff=False)
         tot = _EvalTotals(len(pairs), dev)
-        gv = None
-        if gv_strength > 0:
-            gv = to_device(gv_stats, dev, dtype=np.float64).to(dev)
-            if gv.shape != (order + 1,) or gv.dtype != torch.float64:
-                raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
-        stats = None if f0_stats is None else torch.as_tensor(
-            f0_stats if torch.is_tensor(f0_stats) else list(f0_stats), dtype=torch.float64, device=dev)
 
     def pads(rows):          # the reference's order of draws: source head, source tail, target head, target tail
         for dst in rows:
