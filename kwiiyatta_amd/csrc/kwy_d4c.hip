@@ -1,16 +1,21 @@
 // kwy_d4c.hip -- D4C band aperiodicity (with the "LoveTrain" voicing gate) on gfx950.
 //
 // Replaces pyworld.d4c (reference call site kwiiyatta/vocoder/world.py:55;
-// algorithm: Morise 2016, as shipped with pyworld 0.2.8).  Two frame-parallel
-// kernels, one 256-thread workgroup per frame, everything staged in LDS:
+// algorithm: Morise 2016, as shipped with pyworld 0.2.8).  Three frame-parallel
+// kernels, one workgroup per frame (256 threads; 512 at 96 kHz), everything staged in LDS:
 //
 //   k_d4c_lovetrain : Blackman-windowed frame -> power spectrum -> ratio of the
 //                     cumulative power at 4 kHz / 7.9 kHz  (voicing gate)
 //   k_d4c_body      : for gated frames: 2 temporal centroids (2 FFTs each),
-//                     smoothed power spectrum, static group delay, then per
-//                     3 kHz band a Nuttall-windowed FFT, an in-LDS sort and the
-//                     energy ratio; finally the band values are interpolated to
-//                     the K output bins.  Ungated frames write 1 - 1e-12.
+//                     smoothed power spectrum, static group delay (a row per frame
+//                     in HBM).  Ungated frames write 1 - 1e-12.
+//   k_d4c_bands     : per 3 kHz band a Nuttall-windowed FFT of the group delay, the sum
+//                     of the smallest power bins against the sum of all (a histogram
+//                     select, no sort) and the energy ratio; finally the band values are
+//                     interpolated to the K output bins.
+// The noise of the windows comes from the process-wide randn table (kwy_device.hpp).  The
+// 4096-point frames (32 .. 48 kHz) drain the closing pass of every transform into
+// registers (d4c_drain below).
 //
 // Algorithmic HBM bytes per frame: hop*8 + 16 in, K*8 out.
 #include <math.h>
@@ -274,6 +279,10 @@ __global__ __launch_bounds__(NT) void k_d4c_lovetrain(
     Bd[i] = (i < wl) ? vv[r] - Bd[i] * coef : 0.0;
   }
   __syncthreads();
+  // (The drained closing pass of the body and the band kernel was measured here too and is NOT used: this kernel sums
+  // the powers per thread in the order of the k = tid + NT r mapping, so the drained powers had to travel to their
+  // readers through LDS by bin index, and thread 0's own set of bins ran as a second pass of wavefront 0:
+  // 0.312 ms against 0.303 ms per launch of 33 616 frames.)
   kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
 
   const int boundary0 = (int)ceil(100.0 * N / fs);
@@ -474,6 +483,13 @@ __device__ __forceinline__ kwy_c d4c_opaque(kwy_c v) {
 // 96 kHz (N = 8192): 512 threads and 99 KB, one frame per CU.
 template <int LOG2N>
 struct d4c_nt { static constexpr int value = LOG2N >= 13 ? 512 : 256; };
+// The 4096-point frames (32 .. 48 kHz) end their transforms with kwy_fft_tail4_drain: the closing radix-4 pass leaves
+// the pairs (k, H - k) in the registers of the thread that consumes them instead of storing the transform for a
+// re-read.  The other sizes have another thread / point ratio, a radix-2 tail or none, and keep the stored form.
+template <int LOG2N>
+struct d4c_drain { static constexpr bool value = LOG2N == 12; };
+// the slot twiddles of the drained form: twN[tid] and twN[(NT - tid) mod NT], fetched where they are used
+#define D4C_DRAIN_TWC(twN, NT, tid) (twN)[((NT) - (tid)) & ((NT) - 1)]
 template <int LOG2N>
 static constexpr size_t d4c_body_lds() {
   constexpr int N = 1 << LOG2N, H = N / 2, NT = d4c_nt<LOG2N>::value;
@@ -496,6 +512,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   constexpr int RK = (H + 1 + NT - 1) / NT;  // spectrum bins per thread
   constexpr int HEX = 16 * NT / N;           // 16th-root index step of the bin twiddles
   static_assert(HEX >= 1, "workgroup narrower than N/16");
+  constexpr bool DRAIN = d4c_drain<LOG2N>::value;
 #define D4C_STAMP(n) do { if (dbg && threadIdx.x == 0 && blockIdx.x == (unsigned)dbg[63]) dbg[n] = clock64(); } while (0)
   extern __shared__ double smem[];
   double *tot = smem;                        // NT
@@ -530,6 +547,11 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   D4C_STAMP(0);
   kwy_c tw4[4];   // this thread's factor of every radix-8 pass
   kwy_fft_thread_twiddles<LOG2N - 1, NT>(twH, tw4);
+  // The drained form holds a whole transform's pairs at once where the stored form read them two at a time, so the
+  // pass factors do not stay in registers across those phases: every transform fetches them again (four 16-byte
+  // loads from L1 / L2 through the opaque thread index, as k_d4c_bands does per band).
+#define D4C_BODY_TW4() do { if constexpr (DRAIN) { const int ot = kwy_tid_opaque(); \
+    kwy_fft_thread_twiddles<LOG2N - 1, NT>(twH + (ot - (int)threadIdx.x), tw4); } } while (0)
   // exp(-2 pi i k / N) of "my" spectrum bins k = tid + NT*r is this times a 16th root of unity
   const kwy_c twb = twN[tid];
   // stream positions of the frame's three windows: the body's noise continues where the LoveTrain pass stopped
@@ -567,28 +589,55 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
       }
       __syncthreads();
       D4C_STAMP(2 + which * 2);
-      kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
+      D4C_BODY_TW4();
+      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
       kwy_c Ek[RP], Eh[RP];
+      if constexpr (DRAIN) {
+        // slot r holds the pair of bin p = kwy_drain_bin(r, tid) instead of p = tid + NT r (the centroid sums go to
+        // LDS by bin index further down: which thread forms a bin does not matter)
+        static_assert(RP == 4, "four pairs per thread");
+        kwy_c Em;
+        kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, Ek, Eh, Em);
+        if (tid == 0) { mid[0] = Em.x; mid[1] = Em.y; }
+      } else {
 #pragma unroll
-      for (int r = 0; r < RP; ++r) {
-        const int pp = tid + NT * r;
-        Ek[r] = Eh[r] = kwy_c{0.0, 0.0};
-        if (pp < H / 2) { Ek[r] = B[pp]; Eh[r] = B[(H - pp) & (H - 1)]; }     // (p = 0: E[H] = E[0])
+        for (int r = 0; r < RP; ++r) {
+          const int pp = tid + NT * r;
+          Ek[r] = Eh[r] = kwy_c{0.0, 0.0};
+          if (pp < H / 2) { Ek[r] = B[pp]; Eh[r] = B[(H - pp) & (H - 1)]; }     // (p = 0: E[H] = E[0])
+        }
+        if (tid == 0) { mid[0] = B[H / 2].x; mid[1] = B[H / 2].y; }
       }
-      if (tid == 0) { mid[0] = B[H / 2].x; mid[1] = B[H / 2].y; }
       __syncthreads();
       if (tid & 1) {
 #pragma unroll
         for (int r = 0; r < E; ++r) { const int i = tid + NT * r; Bd[i - 1] = av[r]; Bd[i] = av[r] * (i + 1.0); }
       }
       __syncthreads();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
+      D4C_BODY_TW4();
+      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
+      kwy_c Od[DRAIN ? 4 : 1], Odh[DRAIN ? 4 : 1], twa = {0.0, 0.0}, twc = {0.0, 0.0};
+      if constexpr (DRAIN) {
+        kwy_c Om;
+        kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, Od, Odh, Om);
+        if (tid == 0) { mid[3] = Om.x; mid[4] = Om.y; }     // (parked like E[H/2]: four registers less across the products)
+        // (both twiddle bases are fetched here, through the opaque thread index, instead of living in registers
+        // from the head of the kernel: at this register budget they would be spilled)
+        twa = twN[tid];
+        twc = D4C_DRAIN_TWC(twN, NT, tid);
+      }
 #pragma unroll
       for (int r = 0; r < RP; ++r) {
         const int pp = tid + NT * r;
-        if (pp < H / 2) {
-          const kwy_c w = kwy_tw_hex(d4c_opaque(twb), HEX * r);            // W^p = exp(-2 pi i p / N)
-          const kwy_c Ok = B[pp], Oh = B[(H - pp) & (H - 1)];
+        if (DRAIN || pp < H / 2) {
+          kwy_c w, Ok, Oh;
+          if constexpr (DRAIN) {
+            w = kwy_drain_tw<LOG2N - 1, NT>(r, twa, twc);                  // W^p of the slot's bin
+            Ok = Od[r]; Oh = Odh[r];
+          } else {
+            w = kwy_tw_hex(d4c_opaque(twb), HEX * r);                      // W^p = exp(-2 pi i p / N)
+            Ok = B[pp]; Oh = B[(H - pp) & (H - 1)];
+          }
           const kwy_c t = cmulf(w, Ok);                                     // W^p O[p]
           const kwy_c u = cmulf(kwy_c{-w.x, w.y}, Oh);                      // W^(H-p) O[H-p] = -conj(W^p) O[H-p]
           const kwy_c zp = cadd(Ek[r], t), zhp = csub(Ek[r], t);            // Z[p], Z[H + p]
@@ -601,7 +650,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
         }
       }
       if (tid == 0) {     // bin H/2: W^(H/2) = -i, Z[H/2] = E + t, Z[N - H/2] = Z[H + H/2] = E - t
-        const kwy_c Em = {mid[0], mid[1]}, Om = B[H / 2];
+        const kwy_c Em = {mid[0], mid[1]}, Om = DRAIN ? kwy_c{mid[3], mid[4]} : B[H / 2];
         const kwy_c t = {Om.y, -Om.x};
         const kwy_c za = cadd(Em, t), zb = csub(Em, t);
         const double v = 2.0 * __builtin_fma(za.x, zb.y, za.y * zb.x);
@@ -619,10 +668,36 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
     __syncthreads();
   }
   D4C_STAMP(7);
-  kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
+  D4C_BODY_TW4();
+  kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
   D4C_STAMP(8);
   double pv[RK];
-  {
+  if constexpr (DRAIN) {
+    // the power spectrum from the drained pairs: slot s holds bins k = kwy_drain_bin(s, tid) and H - k, H/2 is thread 0's
+    static_assert(RK == 9, "four pairs per thread and the self-paired bin");
+    const int tid = kwy_tid_opaque();
+    kwy_c lo[4], hi[4], md;
+    kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, lo, hi, md);
+    const kwy_c twa = twN[tid], twc = D4C_DRAIN_TWC(twN, NT, tid);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (s == 0 && tid == 0) kwy_rfft_pair_power2_dc(lo[0], &pv[0], &pv[1]);
+      else kwy_rfft_pair_power2_v(lo[s], hi[s], kwy_drain_tw<LOG2N - 1, NT>(s, twa, twc), &pv[2 * s], &pv[2 * s + 1]);
+    }
+    pv[8] = 0.0;
+    if (tid == 0) {
+      double pm;
+      kwy_rfft_pair_power2_v(md, md, kwy_c{0.0, -1.0}, &pv[8], &pm);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int k = kwy_drain_bin<LOG2N - 1>(s, tid);
+      P[k] = pv[2 * s];
+      P[H - k] = pv[2 * s + 1];
+    }
+    if (tid == 0) P[H / 2] = pv[8];
+  } else {
     // the power spectrum in pairs (k, H - k), k = tid + NT q <= H/2 (kwy_rfft_pair_power2_w), H/2 by thread 0
     constexpr int Q = (H / 2) / NT;
     static_assert(RK == 2 * Q + 1, "pairs per thread");
@@ -651,7 +726,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   // ---- static group delay: the centroid sum moves into A0
 #pragma unroll
   for (int r = 0; r < RP; ++r) {
-    const int pp = tid + NT * r;
+    const int pp = DRAIN ? kwy_drain_bin<LOG2N - 1>(r, tid) : tid + NT * r;
     if (pp < H / 2) { Dv[pp] = cen_lo[r]; Dv[H - pp] = cen_hi[r]; }
   }
   if (tid == 0) Dv[H / 2] = mid[2];
@@ -675,6 +750,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   }
   D4C_STAMP(15);
 #undef D4C_STAMP
+#undef D4C_BODY_TW4
 }
 
 // The band half of D4C, one workgroup per frame: per 3 kHz band a Nuttall-windowed slice of the static group delay
@@ -702,6 +778,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
   constexpr int E = N / NT;
   constexpr int RK = (H + 1 + NT - 1) / NT;
   constexpr int HEX = 16 * NT / N;
+  constexpr bool DRAIN = d4c_drain<LOG2N>::value;
 #define D4C_STAMP(n) do { if (dbg && threadIdx.x == 0 && blockIdx.x == (unsigned)dbg[63]) dbg[n] = clock64(); } while (0)
   extern __shared__ double smem[];
   double *red = smem;                        // 16
@@ -767,7 +844,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
       kwy_c a0 = {c0 * wns[2 * tid], c1 * wns[2 * tid + 1]}, a1 = {0.0, 0.0};
       if (tid == 0 && 2 * (H / 8) < p.window_length) a1.x = Dc[2 * (H / 8)] * nuttall[2 * (H / 8)];
       kwy_fft_pass8_first_sparse_core<LOG2N - 1, NT, false>(B, kwy_tw_reg{tw4[0]}, a0, a1);
-      kwy_fft_inplace_rest_w<LOG2N - 1, NT, false>(B, tw4);
+      kwy_fft_inplace_rest_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
       if (b == 1) D4C_STAMP(18);
     } else {
 #pragma unroll
@@ -776,7 +853,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
         Bd[j] = (r < 4 && j < p.window_length) ? Dc[j] * nutr[r < 4 ? r : 0] : 0.0;
       }
       __syncthreads();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
+      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
     }
     // CPU: power spectrum, sort ascending, cumulative sum, ratio of the (H - boundary) smallest to all
     // bins k and H - k in pairs (k = tid + NT q <= H/2; the self-paired H/2 goes to thread 0): slot 2 q and 2 q + 1 of
@@ -785,20 +862,56 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
     unsigned long long key[RK];
     constexpr int Q = (H / 2) / NT;
     static_assert(RK == 2 * Q + 1, "pairs per thread");
+    if constexpr (DRAIN) {
+      // The pairs come out of the closing pass in registers (kwy_fft_tail4_drain), for the bins k = tid, 2 NT + tid
+      // -- this thread's own slots q = 0 and q = 2 -- and k = 2 NT - tid, 4 NT - tid, which are slots q = 1 and q = 3
+      // of thread NT - tid.  The selection sums a thread's keys in slot order, so the keys stay where they were: those
+      // two pairs of powers change hands through Z[2 NT - tid] and Z[4 NT - tid], two of the points this thread has
+      // just read itself (no barrier in front of the stores) and clear of the select's histogram words.
+      static_assert(Q == 4 && sizeof(uint32_t) * KWY_SELECT_WORDS(NT) <= sizeof(kwy_c) * NT, "exchange clear of the histogram");
+      kwy_c lo[4], hi[4], md;
+      kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, lo, hi, md);
+      const kwy_c twc = D4C_DRAIN_TWC(twN, NT, tid);
+      double pw[8];
 #pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      double pk, pm;
-      kwy_rfft_pair_power2_w<LOG2N - 1>(B, tid + NT * q, kwy_tw_hex(d4c_opaque(twb), HEX * q), &pk, &pm);
-      key[2 * q] = (unsigned long long)__double_as_longlong(pk);
-      key[2 * q + 1] = (unsigned long long)__double_as_longlong(pm);
+      for (int s = 0; s < 4; ++s) {
+        if (s == 0 && tid == 0) kwy_rfft_pair_power2_dc(lo[0], &pw[0], &pw[1]);
+        else kwy_rfft_pair_power2_v(lo[s], hi[s], kwy_drain_tw<LOG2N - 1, NT>(s, d4c_opaque(twb), twc), &pw[2 * s], &pw[2 * s + 1]);
+      }
+      key[2 * Q] = ~0ull;
+      if (tid == 0) {
+        double pk, pm;
+        kwy_rfft_pair_power2_v(md, md, kwy_c{0.0, -1.0}, &pk, &pm);
+        key[2 * Q] = (unsigned long long)__double_as_longlong(pk);
+      } else {
+        B[2 * NT - tid] = kwy_c{pw[4], pw[5]};
+        B[4 * NT - tid] = kwy_c{pw[6], pw[7]};
+      }
+      __syncthreads();
+      if (tid != 0) {       // (thread 0's slots 2 and 3 are its own bins NT and 3 NT)
+        const kwy_c v1 = B[NT + tid], v3 = B[3 * NT + tid];
+        pw[4] = v1.x; pw[5] = v1.y; pw[6] = v3.x; pw[7] = v3.y;
+      }
+      key[0] = (unsigned long long)__double_as_longlong(pw[0]); key[1] = (unsigned long long)__double_as_longlong(pw[1]);
+      key[2] = (unsigned long long)__double_as_longlong(pw[4]); key[3] = (unsigned long long)__double_as_longlong(pw[5]);
+      key[4] = (unsigned long long)__double_as_longlong(pw[2]); key[5] = (unsigned long long)__double_as_longlong(pw[3]);
+      key[6] = (unsigned long long)__double_as_longlong(pw[6]); key[7] = (unsigned long long)__double_as_longlong(pw[7]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        double pk, pm;
+        kwy_rfft_pair_power2_w<LOG2N - 1>(B, tid + NT * q, kwy_tw_hex(d4c_opaque(twb), HEX * q), &pk, &pm);
+        key[2 * q] = (unsigned long long)__double_as_longlong(pk);
+        key[2 * q + 1] = (unsigned long long)__double_as_longlong(pm);
+      }
+      key[2 * Q] = ~0ull;
+      if (tid == 0) {
+        double pk, pm;
+        kwy_rfft_pair_power2_w<LOG2N - 1>(B, H / 2, kwy_c{0.0, -1.0}, &pk, &pm);
+        key[2 * Q] = (unsigned long long)__double_as_longlong(pk);
+      }
+      __syncthreads();
     }
-    key[2 * Q] = ~0ull;
-    if (tid == 0) {
-      double pk, pm;
-      kwy_rfft_pair_power2_w<LOG2N - 1>(B, H / 2, kwy_c{0.0, -1.0}, &pk, &pm);
-      key[2 * Q] = (unsigned long long)__double_as_longlong(pk);
-    }
-    __syncthreads();
     if (b == 1) D4C_STAMP(19);
     double nsmall, nall;
     kwy_block_smallest_sum<RK, NT>(key, H + 1, H - boundary, hist, red, &nsmall, &nall);

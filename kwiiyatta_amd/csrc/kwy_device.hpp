@@ -56,7 +56,10 @@ __device__ __forceinline__ uint32_t kwy_wave_xor_u32(uint32_t v) {
 // Wavefront-cooperative jump: all 64 lanes hold the same state s[4]; on return
 // every lane holds T^steps s.  pow2: [64][128] columns of T^(2^k) (uint4 each).
 __device__ inline void kwy_wave_jump(uint32_t (&s)[4], uint64_t steps, const uint4 *__restrict__ pow2) {
-  const int lane = threadIdx.x & 63;
+  // (behind an optimisation barrier: this is the cold path beyond the randn table, and the table address of the lane
+  // is otherwise formed at the head of the calling kernel and carried -- in k_d4c_body, spilled -- across all of it)
+  int lane = threadIdx.x & 63;
+  asm volatile("" : "+v"(lane));
   for (int k = 0; steps != 0; ++k, steps >>= 1) {
     if (!(steps & 1)) continue;
     // lane l owns state bits l and l+64 (words l>>5 and 2+(l>>5))
@@ -1021,18 +1024,19 @@ __device__ __forceinline__ void kwy_fft_thread_twiddles(const kwy_c *__restrict_
     w[p] = (3 * p + 3 < LOG2H + 0 && ps < (1 << LOG2H) / 8) ? twH[ps] : kwy_c{1.0, 0.0};
   }
 }
-template <int LOG2H, int NT, bool INV>
+// TAIL = false: stop in front of the closing radix-4 / radix-2 pass (the caller runs kwy_fft_tail4_drain instead)
+template <int LOG2H, int NT, bool INV, bool TAIL = true>
 __device__ inline void kwy_fft_inplace_rest_w(kwy_c *z, const kwy_c (&w)[4]) {
   kwy_fft_pass8_core<LOG2H, 3, NT, INV>(z, kwy_tw_reg{w[1]});
   if constexpr (LOG2H >= 9) kwy_fft_pass8_core<LOG2H, 6, NT, INV>(z, kwy_tw_reg{w[2]});
   if constexpr (LOG2H == 12) kwy_fft_pass8_core<LOG2H, 9, NT, INV>(z, kwy_tw_reg{w[3]});
-  if constexpr (LOG2H % 3 != 0) kwy_fft_tail<LOG2H, LOG2H % 3, NT, INV>(z);
+  if constexpr (TAIL && LOG2H % 3 != 0) kwy_fft_tail<LOG2H, LOG2H % 3, NT, INV>(z);
 }
-template <int LOG2H, int NT, bool INV>
+template <int LOG2H, int NT, bool INV, bool TAIL = true>
 __device__ inline void kwy_fft_inplace_w(kwy_c *z, const kwy_c (&w)[4]) {
   static_assert(LOG2H >= 8 && LOG2H <= 12, "unsupported in-place FFT length");
   kwy_fft_pass8_core<LOG2H, 0, NT, INV>(z, kwy_tw_reg{w[0]});
-  kwy_fft_inplace_rest_w<LOG2H, NT, INV>(z, w);
+  kwy_fft_inplace_rest_w<LOG2H, NT, INV, TAIL>(z, w);
 }
 
 // exp(-2 pi i (t + r*NT) / N) from base = exp(-2 pi i t / N): base times a 16th root of unity,
@@ -1170,6 +1174,91 @@ __device__ __forceinline__ void kwy_rfft_pair_power2_w(const kwy_c *z, int k, kw
   *pk = __builtin_fma(xr, xr, xi * xi);
   *pm = __builtin_fma(yr, yr, yi * yi);
 }
+// kwy_rfft_bin2_w (k != 0, H) on the two packed points themselves: A = Z[k], Bz = Z[H - k]
+__device__ __forceinline__ kwy_c kwy_rfft_bin2_v(kwy_c A, kwy_c Bz, kwy_c w) {
+  const kwy_c B = {Bz.x, -Bz.y};
+  const double er = A.x + B.x, ei = A.y + B.y;
+  const double dr = A.x - B.x, di = A.y - B.y;
+  return {__builtin_fma(dr, w.y, __builtin_fma(di, w.x, er)), __builtin_fma(-dr, w.x, __builtin_fma(di, w.y, ei))};
+}
+// kwy_rfft_pair_power2_w on the two packed points themselves (A = Z[k], Bz = Z[H - k], k != 0)
+__device__ __forceinline__ void kwy_rfft_pair_power2_v(kwy_c A, kwy_c Bz, kwy_c w, double *pk, double *pm) {
+  const double er = A.x + Bz.x, ei = A.y - Bz.y;
+  const double dr = A.x - Bz.x, di = A.y + Bz.y;
+  const double pr = __builtin_fma(dr, w.y, di * w.x), pi = __builtin_fma(-dr, w.x, di * w.y);
+  const double xr = er + pr, xi = ei + pi, yr = er - pr, yi = ei - pi;
+  *pk = __builtin_fma(xr, xr, xi * xi);
+  *pm = __builtin_fma(yr, yr, yi * yi);
+}
+// ... and its k = 0 case (DC and Nyquist) on Z[0]
+__device__ __forceinline__ void kwy_rfft_pair_power2_dc(kwy_c Z0, double *pk, double *pm) {
+  const double a = 2.0 * (Z0.x + Z0.y), b = 2.0 * (Z0.x - Z0.y);
+  *pk = a * a; *pm = b * b;
+}
+
+// ------------------------------------------------------- the closing radix-4 pass drained into registers
+// kwy_fft_tail stores the whole transform only for the consumer to read bins k and H - k back: a whole-buffer store
+// (the slow direction of the LDS), a whole-buffer read and a barrier per transform.  Here thread t runs the two
+// radix-4 butterflies whose eight outputs ARE four such pairs, and hands them over in registers.  With Q = H/4
+// butterflies and NT = Q/2 threads:
+//   t >= 1: butterflies j = t and j = Q - t      -> pairs (k, H - k) for k = t, Q + t, Q - t, 2Q - t
+//   t == 0: butterflies j = 0 and j = Q/2        -> k = 0 (X[0] twice: DC / Nyquist), Q, Q/2, 3Q/2, and the
+//                                                    self-paired X[H/2] in `mid` (every thread gets its X[2Q + t])
+// Slot s of thread t holds lo[s] = X[k], hi[s] = X[H - k] with k = kwy_drain_bin(s, t); every k in [0, H/2) belongs
+// to exactly one (t, s).  W^k = exp(-2 pi i k / 2H) of a slot is kwy_drain_tw(): the expression kwy_tw_hex(twN[k mod
+// NT], HEX (k div NT)) that the k = tid + NT q mapping forms, so that the bits of every bin stay what they were.
+// Reads z only; the caller has a barrier in front (the last radix-8 pass ends with one) and puts one behind before
+// anything is stored to z.
+template <int LOG2H, int NT, bool INV>
+__device__ __forceinline__ void kwy_fft_tail4_drain(const kwy_c *z, kwy_c (&lo)[4], kwy_c (&hi)[4], kwy_c &mid) {
+  constexpr int H = 1 << LOG2H, Q = H / 4;
+  static_assert(LOG2H % 3 == 2 && NT == Q / 2, "radix-4 tail, two butterflies per thread");
+  const int t = kwy_tid_opaque();
+  const int jb = t ? Q - t : Q / 2;
+  kwy_c a[4], b[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) { a[m] = z[t + m * Q]; b[m] = z[jb + m * Q]; }
+  {
+    const kwy_c apc = cadd(a[0], a[2]), amc = csub(a[0], a[2]);
+    const kwy_c bpd = cadd(a[1], a[3]), jq = kwy_rot90<INV>(csub(a[1], a[3]));
+    a[0] = cadd(apc, bpd); a[1] = cadd(amc, jq); a[2] = csub(apc, bpd); a[3] = csub(amc, jq);
+  }
+  {
+    const kwy_c apc = cadd(b[0], b[2]), amc = csub(b[0], b[2]);
+    const kwy_c bpd = cadd(b[1], b[3]), jq = kwy_rot90<INV>(csub(b[1], b[3]));
+    b[0] = cadd(apc, bpd); b[1] = cadd(amc, jq); b[2] = csub(apc, bpd); b[3] = csub(amc, jq);
+  }
+  const bool t0 = t == 0;
+  lo[0] = a[0]; hi[0] = t0 ? a[0] : b[3];
+  lo[1] = a[1]; hi[1] = t0 ? a[3] : b[2];
+  lo[2] = b[0]; hi[2] = t0 ? b[3] : a[3];
+  lo[3] = b[1]; hi[3] = t0 ? b[2] : a[2];
+  mid = a[2];
+}
+// the bin k of slot s (see above); Q = H/4
+template <int LOG2H>
+__device__ __forceinline__ int kwy_drain_bin(int s, int t) {
+  constexpr int Q = (1 << LOG2H) / 4;
+  switch (s) {
+    case 0: return t;
+    case 1: return Q + t;
+    case 2: return t ? Q - t : Q / 2;
+    default: return t ? 2 * Q - t : Q + Q / 2;
+  }
+}
+// exp(-2 pi i k / 2H) for k = kwy_drain_bin(s, t); twa = twN[t], twc = twN[(NT - t) & (NT - 1)] (twN: exp(-2 pi i k / 2H))
+template <int LOG2H, int NT>
+__device__ __forceinline__ kwy_c kwy_drain_tw(int s, kwy_c twa, kwy_c twc) {
+  constexpr int HEX = 16 * NT / (2 << LOG2H);
+  static_assert(HEX >= 1, "workgroup narrower than N/16");
+  switch (s) {
+    case 0: return kwy_tw_hex(twa, 0);
+    case 1: return kwy_tw_hex(twa, 2 * HEX);
+    case 2: return kwy_tw_hex(twc, HEX);
+    default: return kwy_tw_hex(twc, 3 * HEX);
+  }
+}
+
 template <int LOG2H>
 __device__ __forceinline__ kwy_c kwy_rfft_bin(const kwy_c *z, int k, const kwy_c *__restrict__ twN) {
   return kwy_rfft_bin_w<LOG2H>(z, k, twN[k & ((2 << LOG2H) - 1)]);

@@ -11,6 +11,11 @@ extern "C" {
 int kwy_debug_smallest_sum_dev(void *stream, const double *values, int problems, int n, int m, double *out);
 /* kwy_log(x) and kwy_sincos_medium(x) of kwy_device.hpp for every element of x (n doubles, device). */
 int kwy_debug_devmath_dev(void *stream, const double *x, int n, double *log_out, double *sin_out, double *cos_out);
+/* The real FFT of rows of 2^log2n samples through both closing passes of the LDS transform: the stored one and the
+ * one drained into registers (kwy_fft_tail4_drain).  x: problems x 2^log2n doubles (device); out_old / out_new:
+ * problems x (2^(log2n-1) + 1) x {re, im} (device), twice the bins 0 .. N/2.  log2n = 12 is the only size with a
+ * drained pass; others return -1.  Synchronises the stream.  Returns 0, -1 (arguments) or -2 (HIP failure). */
+int kwy_debug_rfft_paths_dev(void *stream, const double *x, int problems, int log2n, double *out_old, double *out_new);
 #ifdef __cplusplus
 }
 #endif

@@ -345,6 +345,52 @@ __device__ inline kwy_c *kwy_fft_lds(kwy_c *a, kwy_c *b, int log2H, const kwy_c 
   return src;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The closing radix-4 pass stored and re-read (VAR 5) against drained into registers (VAR 6, kwy_fft_tail4_drain), on
+// one 2048-point transform WITH its consumer -- the pair powers of the bins (k, H - k), as k_d4c_body and k_d4c_bands
+// form them -- because the drained form saves the consumer's reads, not only the pass's stores.  Pass factors in
+// registers (kwy_fft_inplace_w), as in the D4C kernels.  Both end with the barrier that frees the buffer.
+template <int VAR>
+__device__ __forceinline__ double fft_closing_form(kwy_c *A, const kwy_c (&tw4)[4], const kwy_c *__restrict__ tw) {
+  constexpr int LOG2H = 11, NT = 256, H = 1 << LOG2H;
+  const int tid = kwy_tid_opaque();
+  double acc = 0.0;
+  if constexpr (VAR == 5) {
+    kwy_fft_inplace_w<LOG2H, NT, false>(A, tw4);
+    const kwy_c twb = tw[tid];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      double pk, pm;
+      kwy_rfft_pair_power2_w<LOG2H>(A, tid + NT * q, kwy_tw_hex(twb, q), &pk, &pm);
+      acc += pk + pm;
+    }
+    if (tid == 0) {
+      double pk, pm;
+      kwy_rfft_pair_power2_w<LOG2H>(A, H / 2, kwy_c{0.0, -1.0}, &pk, &pm);
+      acc += pk;
+    }
+  } else {
+    kwy_fft_inplace_w<LOG2H, NT, false, false>(A, tw4);
+    kwy_c lo[4], hi[4], md;
+    kwy_fft_tail4_drain<LOG2H, NT, false>(A, lo, hi, md);
+    const kwy_c twa = tw[tid], twc = tw[(NT - tid) & (NT - 1)];
+#pragma unroll
+    for (int s2 = 0; s2 < 4; ++s2) {
+      double pk, pm;
+      if (s2 == 0 && tid == 0) kwy_rfft_pair_power2_dc(lo[0], &pk, &pm);
+      else kwy_rfft_pair_power2_v(lo[s2], hi[s2], kwy_drain_tw<LOG2H, NT>(s2, twa, twc), &pk, &pm);
+      acc += pk + pm;
+    }
+    if (tid == 0) {
+      double pk, pm;
+      kwy_rfft_pair_power2_v(md, md, kwy_c{0.0, -1.0}, &pk, &pm);
+      acc += pk;
+    }
+  }
+  __syncthreads();
+  return acc;
+}
+
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 
 template <int LOG2H, int NT, int VAR>
@@ -363,6 +409,16 @@ __global__ __launch_bounds__(NT) void k_fft(const kwy_c *__restrict__ tw, double
     if constexpr (VAR == 2) { kwy_fftw_2048(A, kwy_fftw_twiddles(tw)); r = A; }
     if constexpr (VAR == 3) { kwy_fftw_1024<false>(A, tw); r = A; }
     if constexpr (VAR == 4) { kwy_fftw_1024<true>(A, tw); r = A; }
+    if constexpr (VAR == 5 || VAR == 6) {
+      kwy_c tw4[4];
+      kwy_fft_thread_twiddles<LOG2H, NT>(tw, tw4);
+      const double a5 = fft_closing_form<VAR>(A, tw4, tw);
+      if (a5 == 12345.678) out[blockIdx.x] = a5;
+      // refill (the next transform's input; the same stores in both variants)
+      for (int i = threadIdx.x; i < H; i += NT) A[i] = {(double)((i * 37 + it) % 101) - 50.0, (double)((i * 11) % 17) - 8.0};
+      __syncthreads();
+      r = A;
+    }
   }
   long long t1 = clock64();
   if (threadIdx.x == 0 && blockIdx.x == 0) cyc[0] = t1 - t0;
@@ -490,6 +546,13 @@ int main() {
   run<11, 256, 2>("wave-local NT256, 2 WG/CU (lds 70K)", tw, 70 * 1024, grid, reps);
   run<11, 256, 2>("wave-local NT256, 3 WG/CU (lds 51K)", tw, 51 * 1024, grid, reps);
   run<11, 256, 2>("wave-local NT256, 4 WG/CU (lds 33K)", tw, sizeof(kwy_c) * KWY_FFTW_ENTRIES + 64, grid, reps);
+  // the closing pass stored against drained, at the occupancies of k_d4c_body (3 / CU) and k_d4c_bands / LoveTrain (4 / CU)
+  for (int rep = 0; rep < 3; ++rep) {
+    run<11, 256, 5>("closing pass stored + pair powers, 3 WG/CU", tw, 51 * 1024, 2304, reps);
+    run<11, 256, 6>("closing pass drained + pair powers, 3 WG/CU", tw, 51 * 1024, 2304, reps);
+    run<11, 256, 5>("closing pass stored + pair powers, 4 WG/CU", tw, one, grid, reps);
+    run<11, 256, 6>("closing pass drained + pair powers, 4 WG/CU", tw, one, grid, reps);
+  }
   run<11, 512, 1>("pingpong r4 NT512, 1 WG/CU (lds 100K)", tw, 100 * 1024, grid, reps);
   run<11, 512, 1>("pingpong r4 NT512, 2 WG/CU (lds 70K)", tw, 70 * 1024, grid, reps);
   run<11, 256, 1>("pingpong r4 NT256, 2 WG/CU (lds 70K)", tw, 70 * 1024, grid, reps);
