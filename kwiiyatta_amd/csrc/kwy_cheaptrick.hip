@@ -65,7 +65,7 @@ __device__ __forceinline__ double ct_interp1q(double x0, double shift, const dou
 template <int LOG2N, bool MCEP>
 __global__ __launch_bounds__(KWY_THREADS, LOG2N <= 11 ? 5 : 4) void k_cheaptrick(
     ct_batch batch, int fs, double q1, double f0_floor_eff, kwy_randn_src rs, const uint4 *__restrict__ poly,
-    const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twN, double out_div, ct_mcep mcep) {
+    const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP, const kwy_c *__restrict__ twN, double out_div, ct_mcep mcep) {
   constexpr int N = 1 << LOG2N;
   constexpr int H = N / 2;
   constexpr int K = H + 1;
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(KWY_THREADS, LOG2N <= 11 ? 5 : 4) void k_cheaptrick
 
   // ---- power spectrum
   __syncthreads();
-  kwy_rfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twb, twN);
+  kwy_rfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twP, twb, twN);
   double *S = (double *)bufA;   // scratch after P is formed (N+2 doubles)
   for (int k = tid; k <= H; k += KWY_THREADS) {
     kwy_c v = bufA[k];
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(KWY_THREADS, LOG2N <= 11 ? 5 : 4) void k_cheaptrick
     if (k >= 1 && k < H) Lg[N - k] = v;
   }
   __syncthreads();
-  kwy_rfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twb, twN);
+  kwy_rfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twP, twb, twN);
   kwy_c *Cx = bufA;
 
   // ---- smoothing + recovery lifter.  The lifters' argument pi cf0 k / fs advances by a constant from one of the
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(KWY_THREADS, LOG2N <= 11 ? 5 : 4) void k_cheaptrick
     }
     return;
   }
-  kwy_irfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twb, twN);
+  kwy_irfft_inplace<LOG2N - 1, KWY_THREADS>(bufA, twl, twP, twb, twN);
   const double *wr = (const double *)bufA;
   double *o = out + frame * K;
   if (out_div == 1.0) {
@@ -355,9 +355,10 @@ template <int LOG2N, bool MCEP>
 static int launch_ct(kwy_ctx *ctx, const ct_batch &b, int fs, double q1, double floor_eff, double out_div, ct_mcep mcep) {
   constexpr int N = 1 << LOG2N, H = N / 2, K = H + 1;
   constexpr int C = (N + K + KWY_THREADS - 1) / KWY_THREADS;
-  const kwy_c *twH, *twN;
+  const kwy_c *twH, *twN, *twP;
   const uint4 *poly;
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N - 1, &twH));
+  KWY_TRY(kwy_get_twiddle_powers(ctx, LOG2N - 1, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
   KWY_TRY(kwy_get_poly_multi(ctx, C, KWY_THREADS, &poly));
   size_t lds = sizeof(kwy_c) * ((H + 1) + (H / 8 > 1 ? H / 8 : 1)) + sizeof(double) * (K + 1 + 8 + KWY_THREADS) +
@@ -365,7 +366,7 @@ static int launch_ct(kwy_ctx *ctx, const ct_batch &b, int fs, double q1, double 
   KWY_HIP(hipFuncSetAttribute((const void *)k_cheaptrick<LOG2N, MCEP>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_PROF(ctx, "k_cheaptrick", hipLaunchKernelGGL((k_cheaptrick<LOG2N, MCEP>), dim3((unsigned)b.start[b.n]), dim3(KWY_THREADS), lds,
-                     ctx->stream, b, fs, q1, floor_eff, kwy_randn(ctx), poly, twH, twN, out_div, mcep));
+                     ctx->stream, b, fs, q1, floor_eff, kwy_randn(ctx), poly, twH, twP, twN, out_div, mcep));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }

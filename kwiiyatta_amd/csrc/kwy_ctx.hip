@@ -253,6 +253,9 @@ void *kwy_arena_alloc(kwy_ctx *ctx, size_t bytes) {
 }
 
 // ================================================================ tables
+// The powers table of the stride-64 pass (kwy_device.hpp: kwy_tw_powers), filled on the device with the expressions the
+// per-lane pass uses, under the same -ffp-contract=off (k_twiddle_powers_fill): entry u holds the bits every lane of a
+// wavefront with j >> 6 == u would form from tw[64 u].
 int kwy_get_twiddles(kwy_ctx *ctx, int log2n, const kwy_c **out) {
   if (log2n < 0 || log2n >= 20) { ctx->err = "fft size out of range"; return KWY_EINVAL; }
   if (!ctx->d_tw[log2n]) {
@@ -267,8 +270,25 @@ int kwy_get_twiddles(kwy_ctx *ctx, int log2n, const kwy_c **out) {
     KWY_HIP(hipMalloc((void **)&d, sizeof(kwy_c) * n));
     KWY_HIP(hipMemcpy(d, h.data(), sizeof(kwy_c) * n, hipMemcpyHostToDevice));
     ctx->d_tw[log2n] = d;
+    // the powers table of this length's stride-64 pass is made with it: never inside a captured region
+    if (log2n >= 10 && log2n <= 12) {
+      const int entries = KWY_TWP_ENTRIES(log2n);
+      kwy_c *t = nullptr;
+      KWY_HIP(hipMalloc((void **)&t, sizeof(kwy_c) * KWY_TWP_ENTRY * entries));
+      hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, ctx->stream, (const kwy_c *)d, t, entries);
+      KWY_HIP(hipGetLastError());
+      KWY_HIP(hipStreamSynchronize(ctx->stream));
+      ctx->d_twp[log2n] = t;
+    }
   }
   *out = ctx->d_tw[log2n];
+  return KWY_OK;
+}
+
+int kwy_get_twiddle_powers(kwy_ctx *ctx, int log2h, const kwy_c **out) {
+  const kwy_c *tw;
+  KWY_TRY(kwy_get_twiddles(ctx, log2h, &tw));
+  *out = ctx->d_twp[log2h];
   return KWY_OK;
 }
 
@@ -414,6 +434,8 @@ void kwy_ctx_destroy(kwy_ctx *ctx) {
   if (ctx->arena) (void)hipFree(ctx->arena);
   if (ctx->d_pow2) (void)hipFree(ctx->d_pow2);
   for (auto &p : ctx->d_tw)
+    if (p) (void)hipFree(p);
+  for (auto &p : ctx->d_twp)
     if (p) (void)hipFree(p);
   for (auto &kv : ctx->d_poly) (void)hipFree(kv.second);
   for (auto &kv : ctx->d_mats) (void)hipFree(kv.second);

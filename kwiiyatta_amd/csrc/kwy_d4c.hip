@@ -13,7 +13,8 @@
 //                     of the smallest power bins against the sum of all (a histogram
 //                     select, no sort) and the energy ratio; finally the band values are
 //                     interpolated to the K output bins.
-// The noise of the windows comes from the process-wide randn table (kwy_device.hpp).  The
+// The stride-64 pass of every transform takes its factors from the context's powers table (twP; kwy_device.hpp:
+// kwy_tw_powers).  The noise of the windows comes from the process-wide randn table (kwy_device.hpp).  The
 // 4096-point frames (32 .. 48 kHz) drain the closing pass of every transform into
 // registers (d4c_drain below).
 //
@@ -194,7 +195,8 @@ __global__ __launch_bounds__(KWY_THREADS) void k_d4c_body_scan(d4c_batch b, int 
 template <int LOG2N, int NT>
 __global__ __launch_bounds__(NT) void k_d4c_lovetrain(
     d4c_batch batch, int fs, kwy_randn_src rs,
-    const uint4 *__restrict__ poly, const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twN) {
+    const uint4 *__restrict__ poly, const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP,
+    const kwy_c *__restrict__ twN) {
   constexpr int N = 1 << LOG2N, H = N / 2;
   constexpr int C = N / NT;
   constexpr int HEX = 16 * NT / N;
@@ -283,7 +285,7 @@ __global__ __launch_bounds__(NT) void k_d4c_lovetrain(
   // the powers per thread in the order of the k = tid + NT r mapping, so the drained powers had to travel to their
   // readers through LDS by bin index, and thread 0's own set of bins ran as a second pass of wavefront 0:
   // 0.312 ms against 0.303 ms per launch of 33 616 frames.)
-  kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
+  kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4, twP);
 
   const int boundary0 = (int)ceil(100.0 * N / fs);
   const int boundary1 = (int)ceil(4000.0 * N / fs);
@@ -504,8 +506,8 @@ static constexpr size_t d4c_body_lds() {
 template <int LOG2N>
 __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d4c_body(
     d4c_batch batch, d4c_params p, kwy_randn_src rs,
-    const uint4 *__restrict__ poly, const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twN,
-    long long *__restrict__ dbg) {
+    const uint4 *__restrict__ poly, const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP,
+    const kwy_c *__restrict__ twN, long long *__restrict__ dbg) {
   constexpr int N = 1 << LOG2N, H = N / 2;
   constexpr int NT = d4c_nt<LOG2N>::value;
   constexpr int E = N / NT;                  // window elements per thread
@@ -548,7 +550,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   kwy_c tw4[4];   // this thread's factor of every radix-8 pass
   kwy_fft_thread_twiddles<LOG2N - 1, NT>(twH, tw4);
   // The drained form holds a whole transform's pairs at once where the stored form read them two at a time, so the
-  // pass factors do not stay in registers across those phases: every transform fetches them again (four 16-byte
+  // pass factors do not stay in registers across those phases: every transform fetches them again (three 16-byte
   // loads from L1 / L2 through the opaque thread index, as k_d4c_bands does per band).
 #define D4C_BODY_TW4() do { if constexpr (DRAIN) { const int ot = kwy_tid_opaque(); \
     kwy_fft_thread_twiddles<LOG2N - 1, NT>(twH + (ot - (int)threadIdx.x), tw4); } } while (0)
@@ -590,7 +592,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
       __syncthreads();
       D4C_STAMP(2 + which * 2);
       D4C_BODY_TW4();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
+      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
       kwy_c Ek[RP], Eh[RP];
       if constexpr (DRAIN) {
         // slot r holds the pair of bin p = kwy_drain_bin(r, tid) instead of p = tid + NT r (the centroid sums go to
@@ -615,7 +617,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
       }
       __syncthreads();
       D4C_BODY_TW4();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
+      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
       kwy_c Od[DRAIN ? 4 : 1], Odh[DRAIN ? 4 : 1], twa = {0.0, 0.0}, twc = {0.0, 0.0};
       if constexpr (DRAIN) {
         kwy_c Om;
@@ -669,7 +671,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   }
   D4C_STAMP(7);
   D4C_BODY_TW4();
-  kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
+  kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
   D4C_STAMP(8);
   double pv[RK];
   if constexpr (DRAIN) {
@@ -771,7 +773,7 @@ static constexpr size_t d4c_bands_lds() {
 // one register budget)
 template <int LOG2N, bool SPARSE>
 __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d4c_bands(
-    d4c_batch batch, d4c_params p, const kwy_c *__restrict__ twH,
+    d4c_batch batch, d4c_params p, const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP,
     const kwy_c *__restrict__ twN, const double *__restrict__ nuttall, long long *__restrict__ dbg) {
   constexpr int N = 1 << LOG2N, H = N / 2;
   constexpr int NT = d4c_nt<LOG2N>::value;
@@ -824,7 +826,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
   double nx1 = (mine1 && p.nbands > 0) ? Dfirst[2 * tid + 1] : 0.0;
   for (int b = 0; b < p.nbands; ++b) {
     const int tid = kwy_tid_opaque();
-    // the thread's pass factors and bin twiddle are fetched again for every band (five 16-byte loads from L1 / L2,
+    // the thread's pass factors and bin twiddle are fetched again for every band (four 16-byte loads from L1 / L2,
     // through the opaque thread index so that they are not hoisted) instead of living in 20 registers across the
     // selection, where the kernel is at its cap of 128
     kwy_c tw4[4];
@@ -844,7 +846,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
       kwy_c a0 = {c0 * wns[2 * tid], c1 * wns[2 * tid + 1]}, a1 = {0.0, 0.0};
       if (tid == 0 && 2 * (H / 8) < p.window_length) a1.x = Dc[2 * (H / 8)] * nuttall[2 * (H / 8)];
       kwy_fft_pass8_first_sparse_core<LOG2N - 1, NT, false>(B, kwy_tw_reg{tw4[0]}, a0, a1);
-      kwy_fft_inplace_rest_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
+      kwy_fft_inplace_rest_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
       if (b == 1) D4C_STAMP(18);
     } else {
 #pragma unroll
@@ -853,7 +855,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
         Bd[j] = (r < 4 && j < p.window_length) ? Dc[j] * nutr[r < 4 ? r : 0] : 0.0;
       }
       __syncthreads();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4);
+      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
     }
     // CPU: power spectrum, sort ascending, cumulative sum, ratio of the (H - boundary) smallest to all
     // bins k and H - k in pairs (k = tid + NT q <= H/2; the self-paired H/2 goes to thread 0): slot 2 q and 2 q + 1 of
@@ -955,9 +957,10 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
 template <int LOG2N>
 static int launch_lt(kwy_ctx *ctx, const d4c_batch &b, int fs) {
   constexpr int N = 1 << LOG2N, H = N / 2;
-  const kwy_c *twH, *twN;
+  const kwy_c *twH, *twN, *twP;
   const uint4 *poly;
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N - 1, &twH));
+  KWY_TRY(kwy_get_twiddle_powers(ctx, LOG2N - 1, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
   constexpr int NT = d4c_nt<LOG2N>::value;
   KWY_TRY(kwy_get_poly_multi(ctx, N / NT, NT, &poly));
@@ -965,7 +968,7 @@ static int launch_lt(kwy_ctx *ctx, const d4c_batch &b, int fs) {
   KWY_HIP(hipFuncSetAttribute((const void *)k_d4c_lovetrain<LOG2N, NT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_PROF(ctx, "k_d4c_lovetrain", hipLaunchKernelGGL((k_d4c_lovetrain<LOG2N, NT>), dim3((unsigned)b.start[b.n]), dim3(NT), lds,
-                     ctx->stream, b, fs, kwy_randn(ctx), poly, twH, twN));
+                     ctx->stream, b, fs, kwy_randn(ctx), poly, twH, twP, twN));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
@@ -973,9 +976,10 @@ static int launch_lt(kwy_ctx *ctx, const d4c_batch &b, int fs) {
 template <int LOG2N>
 static int launch_body(kwy_ctx *ctx, const d4c_batch &b, const d4c_params &p, const double *nuttall) {
   constexpr int N = 1 << LOG2N, H = N / 2;
-  const kwy_c *twH, *twN;
+  const kwy_c *twH, *twN, *twP;
   const uint4 *poly;
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N - 1, &twH));
+  KWY_TRY(kwy_get_twiddle_powers(ctx, LOG2N - 1, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
   constexpr int NT = d4c_nt<LOG2N>::value;
   KWY_TRY(kwy_get_poly_multi(ctx, N / NT, NT, &poly));
@@ -984,18 +988,18 @@ static int launch_body(kwy_ctx *ctx, const d4c_batch &b, const d4c_params &p, co
   KWY_HIP(hipFuncSetAttribute((const void *)k_d4c_body<LOG2N>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_PROF(ctx, "k_d4c_body", hipLaunchKernelGGL(k_d4c_body<LOG2N>, dim3(grid), dim3(NT), lds, ctx->stream, b, p,
-                     kwy_randn(ctx), poly, twH, twN, (long long *)ctx->dbg));
+                     kwy_randn(ctx), poly, twH, twP, twN, (long long *)ctx->dbg));
   const size_t lds_b = d4c_bands_lds<LOG2N>();
   if (p.window_length <= 2 * (H / 8) + 1) {
     KWY_HIP(hipFuncSetAttribute((const void *)k_d4c_bands<LOG2N, true>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
     KWY_PROF(ctx, "k_d4c_bands", hipLaunchKernelGGL((k_d4c_bands<LOG2N, true>), dim3(grid), dim3(NT), lds_b, ctx->stream,
-                       b, p, twH, twN, nuttall, (long long *)ctx->dbg));
+                       b, p, twH, twP, twN, nuttall, (long long *)ctx->dbg));
   } else {
     KWY_HIP(hipFuncSetAttribute((const void *)k_d4c_bands<LOG2N, false>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
     KWY_PROF(ctx, "k_d4c_bands", hipLaunchKernelGGL((k_d4c_bands<LOG2N, false>), dim3(grid), dim3(NT), lds_b, ctx->stream,
-                       b, p, twH, twN, nuttall, (long long *)ctx->dbg));
+                       b, p, twH, twP, twN, nuttall, (long long *)ctx->dbg));
   }
   KWY_HIP(hipGetLastError());
   return KWY_OK;

@@ -855,6 +855,34 @@ struct kwy_tw_table {   // pass factor from a table exp(-2 pi i k / H) (global o
   const kwy_c *tw;
   __device__ __forceinline__ kwy_c operator()(int ps) const { return tw[ps]; }
 };
+// The pass with sub-transform stride 64 (LOG2S == 6): ps = (j >> 6) << 6 is ONE value per wavefront (NT is a multiple of
+// 64), so its factor and the 2nd .. 7th powers come ready-made from the per-context table of kwy_get_twiddle_powers
+// (kwy_ctx.hip): entry u = j >> 6 holds w^1 .. w^7 at [1] .. [7] of 8 complex, w = exp(-2 pi i 64 u / H), formed by
+// the expressions of the per-lane path below, so the bits are the same.  The index goes through readfirstlane and the
+// table is const __restrict__: the factors arrive by scalar loads and feed the products as scalar operands -- no
+// vector instruction forms them and no vector register holds them.  The inverse direction conjugates at use
+// (cmulf of conjugates is exactly the conjugate of cmulf).
+#define KWY_TWP_ENTRY 8                                   // complex per table entry ([0] unused)
+#define KWY_TWP_ENTRIES(LOG2H) ((1 << (LOG2H)) / 512)     // distinct ps of the stride-64 pass of an H-point transform
+struct kwy_tw_powers {
+  const kwy_c *__restrict__ pw;
+};
+// one table entry from w^1, by the per-lane pass's own expressions (the table's fill kernel and the self-test)
+__device__ __forceinline__ void kwy_twiddle_powers(kwy_c w1, kwy_c *o) {
+  const kwy_c w2 = cmulf(w1, w1), w4 = cmulf(w2, w2);
+  const kwy_c w3 = cmulf(w1, w2), w5 = cmulf(w4, w1), w6 = cmulf(w4, w2);
+  const kwy_c w7 = cmulf(w4, w3);
+  o[0] = {1.0, 0.0}; o[1] = w1; o[2] = w2; o[3] = w3; o[4] = w4; o[5] = w5; o[6] = w6; o[7] = w7;
+}
+// fills the table from tw = exp(-2 pi i k / H): one thread per entry, ordinary vector stores (a template so that the
+// library and the self-test library launch the same code)
+template <int = 0>
+__global__ __launch_bounds__(64) void k_twiddle_powers_fill(const kwy_c *__restrict__ tw, kwy_c *__restrict__ tab, int entries) {
+  const int u = threadIdx.x;
+  if (u < entries) kwy_twiddle_powers(tw[64 * u], tab + KWY_TWP_ENTRY * u);
+}
+template <class TW> struct kwy_tw_has_powers { static constexpr bool value = false; };
+template <> struct kwy_tw_has_powers<kwy_tw_powers> { static constexpr bool value = true; };
 struct kwy_tw_reg {     // pass factor held by the thread itself (one butterfly per thread and pass)
   kwy_c w;
   // behind an optimisation barrier: its 2nd..7th powers are formed again in every pass instead of
@@ -884,7 +912,16 @@ __device__ __forceinline__ void kwy_fft_pass8_core(kwy_c *z, TW tw) {
         a[it][m] = z[(LOG2S == 3) ? (idx ^ ((idx >> 3) & 7)) : idx];
       }
       kwy_dft8<INV>(a[it]);
-      if (!LAST) {
+      if constexpr (kwy_tw_has_powers<TW>::value) {
+        static_assert(LOG2S == 6 && !LAST && NT % 64 == 0 && Q % 64 == 0, "the wave-uniform pass");
+        const kwy_c *__restrict__ pw = tw.pw + KWY_TWP_ENTRY * __builtin_amdgcn_readfirstlane(j >> 6);
+#pragma unroll
+        for (int m = 1; m < 8; ++m) {
+          kwy_c w = pw[m];
+          if (INV) w.y = -w.y;
+          a[it][m] = cmulf(w, a[it][m]);
+        }
+      } else if (!LAST) {
         const int ps = (j >> LOG2S) << LOG2S;
         kwy_c w1 = tw(ps);
         if (INV) w1.y = -w1.y;
@@ -917,6 +954,12 @@ __device__ __forceinline__ void kwy_fft_pass8_core(kwy_c *z, TW tw) {
 template <int LOG2H, int LOG2S, int NT, bool INV>
 __device__ __forceinline__ void kwy_fft_pass8(kwy_c *z, const kwy_c *__restrict__ tw) {
   kwy_fft_pass8_core<LOG2H, LOG2S, NT, INV>(z, kwy_tw_table{tw});
+}
+// the stride-64 pass: factors from the powers table where it is not the closing pass (which has none)
+template <int LOG2H, int NT, bool INV>
+__device__ __forceinline__ void kwy_fft_pass8_s64(kwy_c *z, const kwy_c *__restrict__ pw) {
+  if constexpr (LOG2H == 9) kwy_fft_pass8_core<LOG2H, 6, NT, INV>(z, kwy_tw_table{nullptr});
+  else kwy_fft_pass8_core<LOG2H, 6, NT, INV>(z, kwy_tw_powers{pw});
 }
 
 // First radix-8 pass (S = 1) of a transform whose input is zero except for x[0 .. H/8]: thread j
@@ -960,9 +1003,9 @@ __device__ __forceinline__ void kwy_fft_tail(kwy_c *z);
 
 // the remaining passes after kwy_fft_pass8_first_sparse
 template <int LOG2H, int NT, bool INV>
-__device__ inline void kwy_fft_inplace_rest(kwy_c *z, const kwy_c *__restrict__ tw) {
+__device__ inline void kwy_fft_inplace_rest(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw) {
   kwy_fft_pass8<LOG2H, 3, NT, INV>(z, tw);
-  kwy_fft_pass8<LOG2H, 6, NT, INV>(z, tw);
+  kwy_fft_pass8_s64<LOG2H, NT, INV>(z, pw);
   if constexpr (LOG2H == 12) kwy_fft_pass8<LOG2H, 9, NT, INV>(z, tw);
   if constexpr (LOG2H == 11) kwy_fft_tail<LOG2H, 2, NT, INV>(z);
   if constexpr (LOG2H == 10) kwy_fft_tail<LOG2H, 1, NT, INV>(z);
@@ -1000,20 +1043,22 @@ __device__ __forceinline__ void kwy_fft_tail(kwy_c *z) {
 
 // In-place complex FFT of H = 2^LOG2H (512 .. 4096) points in LDS.  The caller
 // has a barrier between filling z and this call; ends with a barrier.
-// tw: exp(-2 pi i k / H), k < H/8 (global or LDS).  Unnormalised in both directions.
+// tw: exp(-2 pi i k / H), k < H/8 (global or LDS); pw: the powers table of the stride-64 pass (global; unused below
+// H = 1024).  Unnormalised in both directions.
 template <int LOG2H, int NT, bool INV>
-__device__ inline void kwy_fft_inplace(kwy_c *z, const kwy_c *__restrict__ tw) {
+__device__ inline void kwy_fft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw) {
   static_assert(LOG2H >= 8 && LOG2H <= 12, "unsupported in-place FFT length");
   kwy_fft_pass8<LOG2H, 0, NT, INV>(z, tw);
   kwy_fft_pass8<LOG2H, 3, NT, INV>(z, tw);
-  if constexpr (LOG2H >= 9) kwy_fft_pass8<LOG2H, 6, NT, INV>(z, tw);
+  if constexpr (LOG2H >= 9) kwy_fft_pass8_s64<LOG2H, NT, INV>(z, pw);
   if constexpr (LOG2H == 12) kwy_fft_pass8<LOG2H, 9, NT, INV>(z, tw);
   if constexpr (LOG2H % 3 != 0) kwy_fft_tail<LOG2H, LOG2H % 3, NT, INV>(z);
 }
 
 // The same transform with the pass factors held by the threads: when a pass has one butterfly
 // per thread (H/8 <= NT), the factor of pass p is the thread constant
-// w[p] = exp(-2 pi i ((tid >> 3p) << 3p) / H)  -- no table at all (kwy_fft_thread_twiddles).
+// w[p] = exp(-2 pi i ((tid >> 3p) << 3p) / H)  -- no table at all (kwy_fft_thread_twiddles).  The stride-64 pass
+// (p = 2) is the exception: its factors are wave-uniform and come from the powers table, w[2] is not fetched.
 template <int LOG2H, int NT>
 __device__ __forceinline__ void kwy_fft_thread_twiddles(const kwy_c *__restrict__ twH, kwy_c (&w)[4]) {
   static_assert((1 << LOG2H) / 8 <= NT, "one butterfly per thread and pass");
@@ -1021,22 +1066,22 @@ __device__ __forceinline__ void kwy_fft_thread_twiddles(const kwy_c *__restrict_
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     const int ps = (j >> (3 * p)) << (3 * p);
-    w[p] = (3 * p + 3 < LOG2H + 0 && ps < (1 << LOG2H) / 8) ? twH[ps] : kwy_c{1.0, 0.0};
+    w[p] = (p != 2 && 3 * p + 3 < LOG2H + 0 && ps < (1 << LOG2H) / 8) ? twH[ps] : kwy_c{1.0, 0.0};
   }
 }
 // TAIL = false: stop in front of the closing radix-4 / radix-2 pass (the caller runs kwy_fft_tail4_drain instead)
 template <int LOG2H, int NT, bool INV, bool TAIL = true>
-__device__ inline void kwy_fft_inplace_rest_w(kwy_c *z, const kwy_c (&w)[4]) {
+__device__ inline void kwy_fft_inplace_rest_w(kwy_c *z, const kwy_c (&w)[4], const kwy_c *__restrict__ pw) {
   kwy_fft_pass8_core<LOG2H, 3, NT, INV>(z, kwy_tw_reg{w[1]});
-  if constexpr (LOG2H >= 9) kwy_fft_pass8_core<LOG2H, 6, NT, INV>(z, kwy_tw_reg{w[2]});
+  if constexpr (LOG2H >= 9) kwy_fft_pass8_s64<LOG2H, NT, INV>(z, pw);
   if constexpr (LOG2H == 12) kwy_fft_pass8_core<LOG2H, 9, NT, INV>(z, kwy_tw_reg{w[3]});
   if constexpr (TAIL && LOG2H % 3 != 0) kwy_fft_tail<LOG2H, LOG2H % 3, NT, INV>(z);
 }
 template <int LOG2H, int NT, bool INV, bool TAIL = true>
-__device__ inline void kwy_fft_inplace_w(kwy_c *z, const kwy_c (&w)[4]) {
+__device__ inline void kwy_fft_inplace_w(kwy_c *z, const kwy_c (&w)[4], const kwy_c *__restrict__ pw) {
   static_assert(LOG2H >= 8 && LOG2H <= 12, "unsupported in-place FFT length");
   kwy_fft_pass8_core<LOG2H, 0, NT, INV>(z, kwy_tw_reg{w[0]});
-  kwy_fft_inplace_rest_w<LOG2H, NT, INV, TAIL>(z, w);
+  kwy_fft_inplace_rest_w<LOG2H, NT, INV, TAIL>(z, w, pw);
 }
 
 // exp(-2 pi i (t + r*NT) / N) from base = exp(-2 pi i t / N): base times a 16th root of unity,
@@ -1065,11 +1110,11 @@ __device__ __forceinline__ kwy_c kwy_tw_hex(kwy_c b, int idx16) {
 // for NT >= N/8 the pair twiddles are twb times 8th roots of unity, else they are read from twN[].
 // Ends with a barrier.
 template <int LOG2H, int NT>
-__device__ inline void kwy_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, kwy_c twb,
+__device__ inline void kwy_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw, kwy_c twb,
                                    const kwy_c *__restrict__ twN = nullptr) {
   constexpr int H = 1 << LOG2H, N = 2 * H;
   constexpr int OCT = 8 * NT / N;  // 0: the workgroup is narrower than N/8, pair twiddles come from twN[]
-  kwy_fft_inplace<LOG2H, NT, false>(z, tw);
+  kwy_fft_inplace<LOG2H, NT, false>(z, tw, pw);
   const int tid = kwy_tid_opaque();
 #pragma unroll
   for (int r = 0; r * NT <= H / 2; ++r) {
@@ -1097,7 +1142,7 @@ __device__ inline void kwy_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, 
 // kwy_irfft_inplace: z[0..H] holds X; on return the first N doubles of z are the signal times N
 // (unnormalised: N times the true inverse).  Ends with a barrier.
 template <int LOG2H, int NT>
-__device__ inline void kwy_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, kwy_c twb,
+__device__ inline void kwy_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw, kwy_c twb,
                                    const kwy_c *__restrict__ twN = nullptr) {
   constexpr int H = 1 << LOG2H, N = 2 * H;
   constexpr int OCT = 8 * NT / N;  // 0: the workgroup is narrower than N/8, pair twiddles come from twN[]
@@ -1124,7 +1169,7 @@ __device__ inline void kwy_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw,
     }
   }
   __syncthreads();
-  kwy_fft_inplace<LOG2H, NT, true>(z, tw);
+  kwy_fft_inplace<LOG2H, NT, true>(z, tw, pw);
 }
 
 // Bin k (0 <= k <= H) of the real FFT of the N = 2H reals whose packed

@@ -114,6 +114,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_dio_sum(dio_plan P) {
 // seg[q] = y[i0 - half + 1 + q], q < N, is transformed once; G_b carries h_b delayed by 2 (max_hal - hal_b), so that
 // for every band output i sits at q = i - i0 + 2 half - 1, free of wrap-around for q >= 2 half - 1.
 __global__ __launch_bounds__(DIO_NT, 4) void k_dio_filter(dio_plan P, const kwy_c *__restrict__ twH,
+                                                         const kwy_c *__restrict__ twP,
                                                          const kwy_c *__restrict__ twN) {
   constexpr int H = DIO_H, N = DIO_N, NT = DIO_NT;
   extern __shared__ double smem[];
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(DIO_NT, 4) void k_dio_filter(dio_plan P, const kwy_
   }
   __syncthreads();
   const kwy_c twb = twN[tid];
-  kwy_rfft_inplace<DIO_LOG2H, NT>(z, twl, twb, twN);
+  kwy_rfft_inplace<DIO_LOG2H, NT>(z, twl, twP, twb, twN);
   kwy_c X[H / NT];
 #pragma unroll
   for (int r = 0; r < H / NT; ++r) X[r] = z[tid + NT * r];
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(DIO_NT, 4) void k_dio_filter(dio_plan P, const kwy_
 #pragma unroll
     for (int r = 0; r < H / NT; ++r) z[tid + NT * r] = cmulf(G[tid + NT * r], X[r]);
     if (tid == 0) z[H] = {G[H].x * xh, 0.0};
-    kwy_irfft_inplace<DIO_LOG2H, NT>(z, twl, twb, twN);
+    kwy_irfft_inplace<DIO_LOG2H, NT>(z, twl, twP, twb, twN);
     // ---- the block's zero crossings, straight from LDS: fl[li] = filtered sample i0 + li, li < V + 2 (the block
     //      OWNS li < V; the two samples behind them are its own values too, so every edge is decided exactly once,
     //      on one set of numbers).  Pass 1 counts per (engine, row, wavefront) by ballots, a scan orders the slots,
@@ -800,8 +801,9 @@ static int dio_pass(kwy_ctx *ctx, const kwy_f0_job *jobs, int count, dio_plan p,
       p.u[u] = dio_utt{nullptr, nullptr, nullptr, nullptr, 0, 0};
     }
   }
-  const kwy_c *twH, *twN;
+  const kwy_c *twH, *twN, *twP;
   KWY_TRY(kwy_get_twiddles(ctx, DIO_LOG2H, &twH));
+  KWY_TRY(kwy_get_twiddle_powers(ctx, DIO_LOG2H, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, DIO_LOG2H + 1, &twN));
   const size_t lds = sizeof(kwy_c) * (DIO_H + 1 + DIO_H / 8) + sizeof(double) * (DIO_PARTS + 8) + sizeof(int) * 4 * 128;
   KWY_HIP(hipFuncSetAttribute((const void *)k_dio_filter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -809,7 +811,7 @@ static int dio_pass(kwy_ctx *ctx, const kwy_f0_job *jobs, int count, dio_plan p,
   const unsigned nblocks = (unsigned)p.ntiles_max;
   hipLaunchKernelGGL(k_dio_sum, dim3(DIO_PARTS, count), dim3(KWY_THREADS), 0, ctx->stream, p);
   KWY_PROF(ctx, "k_dio_filter", hipLaunchKernelGGL(k_dio_filter, dim3(nblocks, count), dim3(DIO_NT), lds, ctx->stream,
-                                                   p, twH, twN));
+                                                   p, twH, twP, twN));
   {
     kwy_prof_scope ps_(ctx, "k_dio_zc");
     hipLaunchKernelGGL(k_dio_zc_scan, dim3(nengines, count), dim3(KWY_THREADS), 0, ctx->stream, p);

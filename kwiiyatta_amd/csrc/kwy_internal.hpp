@@ -28,6 +28,7 @@ struct kwy_ctx {
   const uint32_t *d_randn = nullptr;       // the device's table of WORLD's randn stream (shared by all contexts)
   uint64_t randn_n = 0;                    // draws of it this context uses (kwy_ctx_set_randn_limit lowers it)
   kwy_c *d_tw[20] = {nullptr};             // d_tw[l]: exp(-2 pi i k / 2^l), k < 2^l
+  kwy_c *d_twp[20] = {nullptr};            // d_twp[l]: powers of the stride-64 pass factors of a 2^l-point transform
   std::map<uint64_t, uint4 *> d_poly;      // stride(steps) -> x^(stride*t) mod P, t < 256
   std::map<std::string, double *> d_mats;  // cached host-built matrices (mcep etc.)
   std::map<std::string, int64_t> i_vals;   // small cached integers that go with them
@@ -88,6 +89,10 @@ static inline size_t kwy_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // --- tables -----------------------------------------------------------------
 int kwy_get_twiddles(kwy_ctx *ctx, int log2n, const kwy_c **out);
+// w^1 .. w^7 of every factor w the stride-64 radix-8 pass of a 2^log2h-point LDS transform uses (kwy_device.hpp:
+// kwy_tw_powers), KWY_TWP_ENTRY complex per factor; made together with the twiddles of that length.  Transforms below
+// 1024 points have no such pass: *out = NULL.
+int kwy_get_twiddle_powers(kwy_ctx *ctx, int log2h, const kwy_c **out);
 int kwy_get_poly(kwy_ctx *ctx, uint64_t stride_steps, const uint4 **out);
 // pysptk.sp2mc's frequency transform for transform length N as a matrix [ncut][64] (kwy_mcep.hip): mc[j] = sum_n F[n][j] c[n]
 int kwy_get_sp2mc_matrix(kwy_ctx *ctx, int N, int order, double alpha, const double **out, int *ncut);

@@ -61,6 +61,7 @@ template <int LOG2N>
 __global__ __launch_bounds__(KWY_THREADS) void k_sp2mc(const double *__restrict__ sp, int64_t T, int order,
                                                       const double *__restrict__ F, int ncut,
                                                       const kwy_c *__restrict__ twH,
+                                                      const kwy_c *__restrict__ twP,
                                                       const kwy_c *__restrict__ twN,
                                                       double *__restrict__ mc) {
   constexpr int N = 1 << LOG2N, H = N / 2, K = H + 1;
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_sp2mc(const double *__restrict_
     const double *p = sp + frame * K;
     __syncthreads();
     for (int k = tid; k <= H; k += KWY_THREADS) buf[k] = {log(p[k]), 0.0};
-    kwy_irfft_inplace<LOG2N - 1, KWY_THREADS>(buf, twl, twb, twN);
+    kwy_irfft_inplace<LOG2N - 1, KWY_THREADS>(buf, twl, twP, twb, twN);
     const double *c = (const double *)buf;  // N * cepstrum (unnormalised c2r)
     for (int n = tid; n < ncut; n += KWY_THREADS) {
       double cn = c[n] / N;
@@ -235,14 +236,15 @@ template <int LOG2N>
 static int launch_sp2mc(kwy_ctx *ctx, const double *sp, int64_t T, int order, const double *F, int ncut,
                         double *mc) {
   constexpr int N = 1 << LOG2N, H = N / 2;
-  const kwy_c *twH, *twN;
+  const kwy_c *twH, *twN, *twP;
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N - 1, &twH));
+  KWY_TRY(kwy_get_twiddle_powers(ctx, LOG2N - 1, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
   size_t lds = sizeof(kwy_c) * ((H + 1) + (H / 8 > 1 ? H / 8 : 1)) + sizeof(double) * (size_t)MC_FR * (256 + ncut);
   if (lds > 160 * 1024) { ctx->err = "sp2mc: transform too long for the LDS"; return KWY_EINVAL; }
   KWY_HIP(hipFuncSetAttribute((const void *)k_sp2mc<LOG2N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_PROF(ctx, "k_sp2mc", hipLaunchKernelGGL(k_sp2mc<LOG2N>, dim3((unsigned)((T + MC_FR - 1) / MC_FR)), dim3(KWY_THREADS), lds, ctx->stream, sp, T, order, F,
-                     ncut, twH, twN, mc));
+                     ncut, twH, twP, twN, mc));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }

@@ -16,6 +16,14 @@ int kwy_debug_devmath_dev(void *stream, const double *x, int n, double *log_out,
  * problems x (2^(log2n-1) + 1) x {re, im} (device), twice the bins 0 .. N/2.  log2n = 12 is the only size with a
  * drained pass; others return -1.  Synchronises the stream.  Returns 0, -1 (arguments) or -2 (HIP failure). */
 int kwy_debug_rfft_paths_dev(void *stream, const double *x, int problems, int log2n, double *out_old, double *out_new);
+/* The complex LDS transform of 2^log2h points (10, 11, 12) with nt threads (128 or 256; 256; 512), forward or inverse,
+ * twice: the stride-64 radix-8 pass forms the powers of its factor per lane (out_lane), or takes them from the powers
+ * table by scalar loads (out_table) as every kernel of the library does.  x, out_lane, out_table: problems x 2^log2h x
+ * {re, im} (device).  tab receives the table as the library's fill kernel makes it, tab_ref and tab_ref_conj the
+ * entries recomputed by one thread from w and from conj(w): 8 x 2^log2h / 512 x {re, im} each (device).
+ * Synchronises the stream.  Returns 0, -1 (arguments) or -2 (HIP failure). */
+int kwy_debug_fft_powers_dev(void *stream, const double *x, int problems, int log2h, int nt, int inverse,
+                             double *out_lane, double *out_table, double *tab, double *tab_ref, double *tab_ref_conj);
 #ifdef __cplusplus
 }
 #endif

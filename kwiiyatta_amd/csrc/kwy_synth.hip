@@ -824,11 +824,11 @@ __device__ __forceinline__ kwy_c syn_pair_twiddle(const kwy_c (&base)[V], int r)
 }
 
 template <int LOG2H, int NT, int V>
-__device__ inline void syn_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c (&base)[V],
+__device__ inline void syn_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw, const kwy_c (&base)[V],
                                         const kwy_c *__restrict__ twN) {
   constexpr int H = 1 << LOG2H, N = 2 * H;
   constexpr bool TABLE = 8 * (NT * V) / N < 1;              // the long transforms read the pair twiddles
-  kwy_fft_inplace<LOG2H, NT, false>(z, tw);
+  kwy_fft_inplace<LOG2H, NT, false>(z, tw, pw);
   const int tid = kwy_tid_opaque();
 #pragma unroll
   for (int r = 0; r * NT <= H / 2; ++r) {
@@ -854,7 +854,7 @@ __device__ inline void syn_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, 
 }
 
 template <int LOG2H, int NT, int V>
-__device__ inline void syn_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c (&base)[V],
+__device__ inline void syn_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw, const kwy_c (&base)[V],
                                          const kwy_c *__restrict__ twN) {
   constexpr int H = 1 << LOG2H, N = 2 * H;
   constexpr bool TABLE = 8 * (NT * V) / N < 1;
@@ -880,7 +880,7 @@ __device__ inline void syn_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw,
     }
   }
   __syncthreads();
-  kwy_fft_inplace<LOG2H, NT, true>(z, tw);
+  kwy_fft_inplace<LOG2H, NT, true>(z, tw, pw);
 }
 
 // sum over the workgroup of the V partial sums every thread carries, in the order of a 256-thread workgroup whose
@@ -930,7 +930,7 @@ typedef kwy_batch<syn_view> syn_batch;
 template <int LOG2N, bool DIRECT>
 __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2N == 12 ? 2 : 1)) void k_syn_pulse(
     syn_batch batch, kwy_randn_src rs, const uint4 *__restrict__ poly,
-    const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twN,
+    const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP, const kwy_c *__restrict__ twN,
     const double *__restrict__ dc_remover, long long *__restrict__ dbg) {
   constexpr int NT = syn_pulse_nt<LOG2N>::value, V = KWY_THREADS / NT;
   // diagnostic stamps (tools/syn_pulse_stamps.py): the first voiced pulse that a workgroup from dbg[63] on reaches
@@ -1137,7 +1137,7 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
           }
           __syncthreads();
         }
-        syn_rfft_inplace<LOG2N - 1, NT, V>(buf, twl, twb, twN);
+        syn_rfft_inplace<LOG2N - 1, NT, V>(buf, twl, twP, twb, twN);
         if (it == 1) {
           // (three bins a trip: their exp / sincos chains are independent and fill each other's issue gaps)
           constexpr int G = 3;
@@ -1178,7 +1178,7 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
         }
       }
       SYN_STAMP(3 + 5 * part);
-      syn_irfft_inplace<LOG2N - 1, NT, V>(buf, twl, twb, twN);
+      syn_irfft_inplace<LOG2N - 1, NT, V>(buf, twl, twP, twb, twN);
       SYN_STAMP(4 + 5 * part);
       if (part == 0) {
         const double *w = (const double *)buf;
@@ -1295,10 +1295,11 @@ static int get_dc_remover(kwy_ctx *ctx, int fft_size, const double **out) {
 template <int LOG2N>
 static int launch_pulse(kwy_ctx *ctx, syn_batch &batch) {
   constexpr int N = 1 << LOG2N, H = N / 2, K = H + 1;
-  const kwy_c *twH, *twN;
+  const kwy_c *twH, *twN, *twP;
   const uint4 *poly;
   const double *dcrem;
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N - 1, &twH));
+  KWY_TRY(kwy_get_twiddle_powers(ctx, LOG2N - 1, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
   KWY_TRY(kwy_get_poly(ctx, 12ull * (N / syn_pulse_nt<LOG2N>::value), &poly));
   KWY_TRY(get_dc_remover(ctx, N, &dcrem));
@@ -1316,7 +1317,7 @@ static int launch_pulse(kwy_ctx *ctx, syn_batch &batch) {
   for (int u = 0; u < batch.n; ++u) { batch.start[u] = g; g += std::max(1, std::min(batch.u[u].slots, share)); }
   batch.start[batch.n] = g;
   KWY_PROF(ctx, "k_syn_pulse", hipLaunchKernelGGL((k_syn_pulse<LOG2N, false>), dim3(g), dim3(NT), lds, ctx->stream, batch,
-                     kwy_randn(ctx), poly, twH, twN, dcrem, (long long *)ctx->dbg));
+                     kwy_randn(ctx), poly, twH, twP, twN, dcrem, (long long *)ctx->dbg));
   g = 0;
   for (int u = 0; u < batch.n; ++u) { batch.start[u] = g; g += batch.u[u].nt; }
   batch.start[batch.n] = g;
@@ -1324,7 +1325,7 @@ static int launch_pulse(kwy_ctx *ctx, syn_batch &batch) {
   // pulses beyond the slots (none for speech): one workgroup per utterance, serial, same order
   for (int u = 0; u <= batch.n; ++u) batch.start[u] = u;
   KWY_PROF(ctx, "k_syn_pulse_more", hipLaunchKernelGGL((k_syn_pulse<LOG2N, true>), dim3(batch.n), dim3(NT), lds, ctx->stream,
-                     batch, kwy_randn(ctx), poly, twH, twN, dcrem, (long long *)nullptr));
+                     batch, kwy_randn(ctx), poly, twH, twP, twN, dcrem, (long long *)nullptr));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }

@@ -63,6 +63,7 @@ extern "C" int kwy_debug_devmath_dev(void *stream, const double *x, int n, doubl
 // H/2 from the thread's base factor, the others from the table)
 template <int LOG2N, int NT>
 __global__ __launch_bounds__(NT) void k_rfft_paths_selftest(const double *__restrict__ x, const kwy_c *__restrict__ twH,
+                                                            const kwy_c *__restrict__ twP,
                                                             const kwy_c *__restrict__ twN, kwy_c *__restrict__ out_old,
                                                             kwy_c *__restrict__ out_new) {
   constexpr int N = 1 << LOG2N, H = N / 2, HEX = 16 * NT / N;
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(NT) void k_rfft_paths_selftest(const double *__rest
   // stored form
   for (int i = tid; i < N; i += NT) Bd[i] = row[i];
   __syncthreads();
-  kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4);
+  kwy_fft_inplace_w<LOG2N - 1, NT, false>(B, tw4, twP);
   for (int r = 0; tid + NT * r <= H; ++r) {
     const int k = tid + NT * r;
     const kwy_c w = r < 4 ? kwy_tw_hex(twN[tid], HEX * r) : twN[k];
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(NT) void k_rfft_paths_selftest(const double *__rest
   // drained form
   for (int i = tid; i < N; i += NT) Bd[i] = row[i];
   __syncthreads();
-  kwy_fft_inplace_w<LOG2N - 1, NT, false, false>(B, tw4);
+  kwy_fft_inplace_w<LOG2N - 1, NT, false, false>(B, tw4, twP);
   kwy_c lo[4], hi[4], md;
   kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, lo, hi, md);
   const kwy_c twa = twN[tid], twc = twN[(NT - tid) & (NT - 1)];
@@ -110,7 +111,8 @@ extern "C" int kwy_debug_rfft_paths_dev(void *stream, const double *x, int probl
   if (!x || !out_old || !out_new || problems <= 0) return -1;
   if (log2n != 12) return -1;        // the one size with a drained closing pass
   constexpr int LOG2N = 12, NT = 256, N = 1 << LOG2N, H = N / 2;
-  std::vector<kwy_c> h(H / 8 + N);
+  constexpr int TWP = KWY_TWP_ENTRY * KWY_TWP_ENTRIES(LOG2N - 1);    // the powers table behind the two twiddle tables
+  std::vector<kwy_c> h(H / 8 + N + TWP);
   for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * KWY_PI * k / H; h[k] = {cos(a), sin(a)}; }
   for (int k = 0; k < N; ++k) { const double a = -2.0 * KWY_PI * k / N; h[H / 8 + k] = {cos(a), sin(a)}; }
   kwy_c *tw = nullptr;
@@ -122,11 +124,102 @@ extern "C" int kwy_debug_rfft_paths_dev(void *stream, const double *x, int probl
     auto kern = k_rfft_paths_selftest<LOG2N, NT>;
     if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) rc = -2;
     if (rc == 0) {
-      hipLaunchKernelGGL(kern, dim3(problems), dim3(NT), lds, (hipStream_t)stream, x, tw, tw + H / 8, (kwy_c *)out_old,
+      hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const kwy_c *)tw,
+                         tw + H / 8 + N, KWY_TWP_ENTRIES(LOG2N - 1));
+      hipLaunchKernelGGL(kern, dim3(problems), dim3(NT), lds, (hipStream_t)stream, x, tw, tw + H / 8 + N, tw + H / 8, (kwy_c *)out_old,
                          (kwy_c *)out_new);
       if (hipGetLastError() != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -2;
     }
   }
+  hipFree(tw);
+  return rc;
+}
+
+// ---- diagnostic: the stride-64 radix-8 pass with per-lane powers and with the powers table ----------------------------
+// (one NT-thread workgroup per row of H complex; both paths return the H bins of the complex transform.  The passes
+// around the stride-64 one are the same calls in both paths.)
+template <int LOG2H, int NT, bool INV>
+__global__ __launch_bounds__(NT) void k_fft_powers_selftest(const kwy_c *__restrict__ x, const kwy_c *__restrict__ twH,
+                                                            const kwy_c *__restrict__ twP, kwy_c *__restrict__ out_lane,
+                                                            kwy_c *__restrict__ out_table) {
+  constexpr int H = 1 << LOG2H;
+  extern __shared__ double smem[];
+  kwy_c *B = (kwy_c *)smem;          // H complex
+  const int tid = threadIdx.x;
+  const kwy_c *row = x + (size_t)blockIdx.x * H;
+#pragma nounroll
+  for (int path = 0; path < 2; ++path) {
+    kwy_c *o = (path == 0 ? out_lane : out_table) + (size_t)blockIdx.x * H;
+    for (int i = tid; i < H; i += NT) B[i] = row[i];
+    __syncthreads();
+    kwy_fft_pass8<LOG2H, 0, NT, INV>(B, twH);
+    kwy_fft_pass8<LOG2H, 3, NT, INV>(B, twH);
+    if (path == 0) kwy_fft_pass8<LOG2H, 6, NT, INV>(B, twH);
+    else kwy_fft_pass8_s64<LOG2H, NT, INV>(B, twP);
+    if constexpr (LOG2H == 12) kwy_fft_pass8<LOG2H, 9, NT, INV>(B, twH);
+    if constexpr (LOG2H % 3 != 0) kwy_fft_tail<LOG2H, LOG2H % 3, NT, INV>(B);
+    for (int i = tid; i < H; i += NT) o[i] = B[i];
+    __syncthreads();
+  }
+}
+
+// the table's entries once more, by one thread, from w^1 and from its conjugate (the inverse direction's factor)
+__global__ void k_twiddle_powers_ref(const kwy_c *__restrict__ twH, int entries, kwy_c *__restrict__ ref,
+                                     kwy_c *__restrict__ ref_conj) {
+  for (int u = 0; u < entries; ++u) {
+    for (int c = 0; c < 2; ++c) {
+      kwy_c w1 = twH[64 * u];
+      if (c) w1.y = -w1.y;
+      const kwy_c w2 = cmulf(w1, w1), w4 = cmulf(w2, w2);
+      const kwy_c w3 = cmulf(w1, w2), w5 = cmulf(w4, w1), w6 = cmulf(w4, w2);
+      const kwy_c w7 = cmulf(w4, w3);
+      kwy_c *o = (c ? ref_conj : ref) + KWY_TWP_ENTRY * u;
+      o[0] = {1.0, 0.0}; o[1] = w1; o[2] = w2; o[3] = w3; o[4] = w4; o[5] = w5; o[6] = w6; o[7] = w7;
+    }
+  }
+}
+
+template <int LOG2H, int NT>
+static int fft_powers_launch(hipStream_t stream, const kwy_c *x, int problems, bool inverse, const kwy_c *twH,
+                             const kwy_c *twP, kwy_c *out_lane, kwy_c *out_table) {
+  const size_t lds = sizeof(kwy_c) * (1 << LOG2H);
+  if (hipFuncSetAttribute((const void *)k_fft_powers_selftest<LOG2H, NT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+      hipFuncSetAttribute((const void *)k_fft_powers_selftest<LOG2H, NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return -2;
+  if (inverse) hipLaunchKernelGGL((k_fft_powers_selftest<LOG2H, NT, true>), dim3(problems), dim3(NT), lds, stream, x, twH, twP, out_lane, out_table);
+  else hipLaunchKernelGGL((k_fft_powers_selftest<LOG2H, NT, false>), dim3(problems), dim3(NT), lds, stream, x, twH, twP, out_lane, out_table);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// x: problems rows of 2^log2h complex; out_lane / out_table: the same shape; tab, tab_ref, tab_ref_conj:
+// KWY_TWP_ENTRY * 2^log2h / 512 complex each (the table as the library fills it, and the one-thread recomputations)
+extern "C" int kwy_debug_fft_powers_dev(void *stream, const double *x, int problems, int log2h, int nt, int inverse,
+                                        double *out_lane, double *out_table, double *tab, double *tab_ref,
+                                        double *tab_ref_conj) {
+  if (!x || !out_lane || !out_table || !tab || !tab_ref || !tab_ref_conj || problems <= 0) return -1;
+  if (!((log2h == 10 && (nt == 128 || nt == 256)) || (log2h == 11 && nt == 256) || (log2h == 12 && nt == 512))) return -1;
+  const int H = 1 << log2h, entries = H / 512;
+  std::vector<kwy_c> h(H);
+  for (int k = 0; k < H; ++k) { const double a = -2.0 * M_PI * (double)k / (double)H; h[k] = {cos(a), sin(a)}; }
+  kwy_c *tw = nullptr;
+  if (hipMalloc((void **)&tw, sizeof(kwy_c) * H) != hipSuccess) return -2;
+  int rc = 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * H, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  if (rc == 0) {
+    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, (kwy_c *)tab, entries);
+    hipLaunchKernelGGL(k_twiddle_powers_ref, dim3(1), dim3(1), 0, s, (const kwy_c *)tw, entries, (kwy_c *)tab_ref, (kwy_c *)tab_ref_conj);
+    if (hipGetLastError() != hipSuccess) rc = -2;
+  }
+  if (rc == 0) {
+    const kwy_c *cx = (const kwy_c *)x, *tp = (const kwy_c *)tab;
+    kwy_c *ol = (kwy_c *)out_lane, *ot = (kwy_c *)out_table;
+    if (log2h == 10 && nt == 128) rc = fft_powers_launch<10, 128>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
+    else if (log2h == 10) rc = fft_powers_launch<10, 256>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
+    else if (log2h == 11) rc = fft_powers_launch<11, 256>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
+    else rc = fft_powers_launch<12, 512>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
   hipFree(tw);
   return rc;
 }

@@ -356,7 +356,7 @@ __device__ __forceinline__ double fft_closing_form(kwy_c *A, const kwy_c (&tw4)[
   const int tid = kwy_tid_opaque();
   double acc = 0.0;
   if constexpr (VAR == 5) {
-    kwy_fft_inplace_w<LOG2H, NT, false>(A, tw4);
+    kwy_fft_inplace_w<LOG2H, NT, false>(A, tw4, tw + H);
     const kwy_c twb = tw[tid];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -370,7 +370,7 @@ __device__ __forceinline__ double fft_closing_form(kwy_c *A, const kwy_c (&tw4)[
       acc += pk;
     }
   } else {
-    kwy_fft_inplace_w<LOG2H, NT, false, false>(A, tw4);
+    kwy_fft_inplace_w<LOG2H, NT, false, false>(A, tw4, tw + H);
     kwy_c lo[4], hi[4], md;
     kwy_fft_tail4_drain<LOG2H, NT, false>(A, lo, hi, md);
     const kwy_c twa = tw[tid], twc = tw[(NT - tid) & (NT - 1)];
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(NT) void k_fft(const kwy_c *__restrict__ tw, double
   long long t0 = clock64();
   kwy_c *r = A;
   for (int it = 0; it < reps; ++it) {
-    if (VAR == 0) { kwy_fft_inplace<LOG2H, NT, false>(A, tw); r = A; }
+    if (VAR == 0) { kwy_fft_inplace<LOG2H, NT, false>(A, tw, tw + H); r = A; }
     if (VAR == 1) { r = kwy_fft_lds<false, NT>(A, B2, LOG2H, tw); }
     if constexpr (VAR == 2) { kwy_fftw_2048(A, kwy_fftw_twiddles(tw)); r = A; }
     if constexpr (VAR == 3) { kwy_fftw_1024<false>(A, tw); r = A; }
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256) void k_check(const kwy_c *__restrict__ tw, dou
     B2[kwy_fftw_in(i)] = v;
   }
   __syncthreads();
-  kwy_fft_inplace<11, 256, false>(A, tw);
+  kwy_fft_inplace<11, 256, false>(A, tw, tw + 2048);
   kwy_fftw_2048(B2, kwy_fftw_twiddles(tw));
   double e = 0.0, m = 0.0;
   for (int k = threadIdx.x; k < 2048; k += 256) {
@@ -466,7 +466,7 @@ __global__ __launch_bounds__(256) void k_check1024(const kwy_c *__restrict__ tw,
     B2[i] = v;
   }
   __syncthreads();
-  kwy_fft_inplace<10, 256, INV>(A, tw);
+  kwy_fft_inplace<10, 256, INV>(A, tw, tw + 1024);
   kwy_fftw_1024<INV>(B2, tw);
   double e = 0.0, m = 0.0;
   for (int k = threadIdx.x; k < 1024; k += 256) {
@@ -506,7 +506,9 @@ int main() {
   const int L = 11, H = 1 << L;
   std::vector<kwy_c> h(H);
   for (int k = 0; k < H; ++k) { double a = -2.0 * M_PI * k / H; h[k].x = cos(a); h[k].y = sin(a); }
-  kwy_c *tw; CK(hipMalloc(&tw, sizeof(kwy_c) * H)); CK(hipMemcpy(tw, h.data(), sizeof(kwy_c) * H, hipMemcpyHostToDevice));
+  // every twiddle table is followed by the powers table of its length's stride-64 pass (kwy_device.hpp: kwy_tw_powers)
+  kwy_c *tw; CK(hipMalloc(&tw, sizeof(kwy_c) * (H + KWY_TWP_ENTRY * KWY_TWP_ENTRIES(L)))); CK(hipMemcpy(tw, h.data(), sizeof(kwy_c) * H, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, 0, (const kwy_c *)tw, tw + H, KWY_TWP_ENTRIES(L));
   {
     double *out; CK(hipMalloc(&out, 16 * 4));
     CK(hipFuncSetAttribute((const void *)k_check, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
@@ -518,7 +520,8 @@ int main() {
   {
     std::vector<kwy_c> h10(1024);
     for (int k = 0; k < 1024; ++k) { double a = -2.0 * M_PI * k / 1024; h10[k].x = cos(a); h10[k].y = sin(a); }
-    CK(hipMalloc(&tw10, sizeof(kwy_c) * 1024)); CK(hipMemcpy(tw10, h10.data(), sizeof(kwy_c) * 1024, hipMemcpyHostToDevice));
+    CK(hipMalloc(&tw10, sizeof(kwy_c) * (1024 + KWY_TWP_ENTRY * KWY_TWP_ENTRIES(10)))); CK(hipMemcpy(tw10, h10.data(), sizeof(kwy_c) * 1024, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, 0, (const kwy_c *)tw10, tw10 + 1024, KWY_TWP_ENTRIES(10));
     double *out; CK(hipMalloc(&out, 16 * 4));
     double h8[8];
     CK(hipFuncSetAttribute((const void *)k_check1024<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 40 * 1024));
