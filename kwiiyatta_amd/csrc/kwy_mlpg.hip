@@ -7,10 +7,11 @@
 //
 // Kernels:
 //   k_gmm_prep   one workgroup per mixture: Cholesky of S_xx in LDS, its inverse,
-//                A = S_yx S_xx^-1, diagonal conditional variance, log-normaliser
+//                A = S_yx S_xx^-1 and its transpose, diagonal conditional variance, log-normaliser
 //   k_delta      static + delta + delta-delta features (3-tap correlations)
-//   k_gmm_logp   (frame tile x mixture) workgroups: ||L^-1 (x - mu)||^2 from LDS
-//   k_gmm_cond   per frame: arg-max mixture, conditional mean E and variance D
+//   k_gmm_logp_frag  (frame tile x mixture) workgroups: ||L^-1 (x - mu)||^2 on the f64 MFMA, L^-1 in fragment order in
+//                LDS, the frames in registers (k_gmm_logp: both operands from LDS, for features wider than 96)
+//   k_gmm_cond   four frames per wavefront: arg-max mixture, conditional mean E (from A transposed) and variance D
 //   k_mlpg_build per (frame, dim): the pentadiagonal normal equations W'PW, W'P mu
 //   k_mlpg_chunks / k_mlpg_finish  per static dim: banded Cholesky, partitioned into chunks (nested dissection)
 //
@@ -53,8 +54,10 @@ struct ml_batch {
 // layout of the prepared model (doubles), per mixture m:
 //   Z   [D*D]  lower-triangular inverse of chol(S_xx)   (row j: Z[j][0..j])
 //   A   [D*D]  S_yx S_xx^-1
-//   mux [D], muy [D], dvar [D], cst [1] (+ padding)
-__host__ __device__ static inline size_t ml_model_stride(int D) { return (size_t)2 * D * D + 3 * D + 8; }
+//   mux [D], muy [D], dvar [D], cst [1] (+ padding to 8)
+//   AT  [D*D]  A transposed (AT[k][i] = A[i][k]): what k_gmm_cond reads, consecutive lanes consecutive doubles
+__host__ __device__ static inline size_t ml_model_stride(int D) { return (size_t)3 * D * D + 3 * D + 8; }
+__host__ __device__ static inline size_t ml_model_at(int D) { return (size_t)2 * D * D + 3 * D + 8; }
 
 __global__ __launch_bounds__(KWY_THREADS) void k_gmm_prep(const double *__restrict__ weights,
                                                          const double *__restrict__ means,
@@ -68,6 +71,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_gmm_prep(const double *__restri
   const double *C = covs + (size_t)m * D2 * D2;
   double *out = model + (size_t)m * ml_model_stride(D);
   double *oZ = out, *oA = oZ + D * D, *omux = oA + D * D, *omuy = omux + D, *odv = omuy + D, *ocst = odv + D;
+  double *oAT = out + ml_model_at(D);
 
   auto Sxx = [&](int i, int j) { return C[(size_t)i * D2 + j]; };
   auto Sxy = [&](int i, int j) { return diff ? C[(size_t)i * D2 + D + j] - C[(size_t)i * D2 + j] : C[(size_t)i * D2 + D + j]; };
@@ -119,6 +123,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_gmm_prep(const double *__restri
     double v = 0.0;
     for (int j = c; j < D; ++j) v += W[r * D + j] * Z[j * D + c];
     oA[e] = v;
+    oAT[c * D + r] = v;
     oZ[e] = Z[e];
   }
   for (int i = tid; i < D; i += KWY_THREADS) {
@@ -275,37 +280,181 @@ __global__ __launch_bounds__(64 * NW) void k_gmm_logp(const double *__restrict__
   }
 }
 
+// The same product with the frame operand in registers (the form of k_fit_logprob, kwy_gmmfit.hip): fed from LDS alone
+// the MFMA is LDS-bound.  Z_m is expanded once per workgroup into MFMA-fragment order -- fragment (nb, ks), ks < 4 nb + 4,
+// at 2 nb (nb + 1) + ks holds the 64 lane values of the B operand of column block nb and k-step ks, zeros above the
+// diagonal: one conflict-free 512-byte read per operand, 29 KB for D = 72 instead of 121 KB of rows.  A wavefront takes
+// 32 frames: x - mu_x of two 16-frame sub-tiles goes straight from global memory into the A registers (2 x Kp/4
+// doubles per lane), and every B fragment feeds two independent accumulator chains.  Per logp[t][m] the operations and
+// their order are those of k_gmm_logp: the same k-steps min(Kp/4, 4 (nb + 1)) from a zero accumulator, the squares
+// summed in ascending nb, the same row sum.  NBLK = column blocks (D <= 16 NBLK), NW = wavefronts per workgroup.
+#define ML_FRAG_MAXBLK 6    // D <= 96.  The fragments would fit the LDS up to nine blocks (D = 144, 92 KB), but k_gmm_prep
+                            // holds three D x D matrices in LDS and admits D <= 82: wider instances could not be reached or tested
+template <int NBLK, int NW>
+__global__ __launch_bounds__(64 * NW) void k_gmm_logp_frag(const double *__restrict__ X, ml_dims dm,
+                                                          const double *__restrict__ model,
+                                                          double *__restrict__ logp) {
+  constexpr int KS = 4 * NBLK, NFRAG = 2 * NBLK * (NBLK + 1), TILE = 32 * NW;
+  extern __shared__ double smem[];
+  double *zf = smem;                // NFRAG x 64
+  double *mus = zf + NFRAG * 64;    // 16 NBLK: mu_x, zero beyond D
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, m = blockIdx.y;
+  const int ar = lane & 15, ak = lane >> 4;
+  const int D = dm.D, kp4 = ml_kp(D) / 4;      // 4 (NBLK - 1) < kp4 <= 4 NBLK
+  const double *mod = model + (size_t)m * ml_model_stride(D);
+  const double *mZ = mod, *mux = mod + 2 * D * D;
+  const double cst = mod[2 * D * D + 3 * D];
+  for (int idx = tid; idx < NFRAG * 64; idx += 64 * NW) {
+    const int f = idx >> 6, l = idx & 63;
+    int nb = 0;
+    while (2 * (nb + 1) * (nb + 2) <= f) ++nb;
+    const int ks = f - 2 * nb * (nb + 1);
+    const int j = 16 * nb + (l & 15), i = 4 * ks + (l >> 4);
+    zf[idx] = (j < D && i <= j) ? mZ[j * D + i] : 0.0;
+  }
+  for (int c = tid; c < 16 * NBLK; c += 64 * NW) mus[c] = c < D ? mux[c] : 0.0;
+  __syncthreads();
+  const int64_t ntiles = (dm.T + TILE - 1) / TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {   // (no barrier in this loop)
+    const int64_t t0 = tile * TILE + 32 * wv;
+    if (t0 >= dm.T) break;
+    // rows behind the last frame repeat it (their results are not stored); columns beyond D are zero
+    const double *xa = X + min(t0 + ar, dm.T - 1) * D, *xb = X + min(t0 + 16 + ar, dm.T - 1) * D;
+    double a0[KS], a1[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS - 4; ++ks) {
+      const double mu = mus[4 * ks + ak];
+      a0[ks] = xa[4 * ks + ak] - mu;
+      a1[ks] = xb[4 * ks + ak] - mu;
+    }
+#pragma unroll
+    for (int ks = KS - 4; ks < KS; ++ks) {
+      const int c = 4 * ks + ak, cc = min(c, D - 1);
+      const double mu = mus[cc];
+      const double v0 = xa[cc] - mu, v1 = xb[cc] - mu;
+      a0[ks] = c < D ? v0 : 0.0;
+      a1[ks] = c < D ? v1 : 0.0;
+    }
+    double q0[4] = {0.0, 0.0, 0.0, 0.0}, q1[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb) {
+      ml_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+      const double *frag = zf + (2 * nb * (nb + 1)) * 64 + lane;
+#pragma unroll
+      for (int ks = 0; ks < 4 * nb + 4; ++ks) {
+        // only the last block can end before its diagonal (Kp/4 k-steps), and never before its first k-step
+        if (nb < NBLK - 1 || ks <= 4 * (NBLK - 1) || ks < kp4) {
+          const double b = frag[ks * 64];
+          acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[ks], b, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[ks], b, acc1, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        q0[r] += acc0[r] * acc0[r];
+        q1[r] += acc1[r] * acc1[r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double v = q0[r], w = q1[r];
+      v += kwy_dpp_f64<0x111>(v); w += kwy_dpp_f64<0x111>(w);
+      v += kwy_dpp_f64<0x112>(v); w += kwy_dpp_f64<0x112>(w);
+      v += kwy_dpp_f64<0x114>(v); w += kwy_dpp_f64<0x114>(w);
+      v += kwy_dpp_f64<0x118>(v); w += kwy_dpp_f64<0x118>(w);
+      q0[r] = v; q1[r] = w;
+    }
+    if (ar == 15) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t t = t0 + ak + 4 * r;
+        if (t < dm.T) logp[t * dm.M + m] = cst - 0.5 * q0[r];
+        if (t + 16 < dm.T) logp[(t + 16) * dm.M + m] = cst - 0.5 * q1[r];
+      }
+    }
+  }
+}
+
 // ---- arg-max mixture, conditional mean / variance --------------------------------------------
-__global__ __launch_bounds__(128) void k_gmm_cond(const double *__restrict__ X, ml_dims dm,
-                                                 const double *__restrict__ model,
-                                                 const double *__restrict__ logp,
-                                                 double *__restrict__ E, double *__restrict__ Dv,
-                                                 int *__restrict__ mix) {
-  __shared__ int s_m;
-  __shared__ double dsh[256];
-  const int64_t t = blockIdx.x;
-  const int tid = threadIdx.x, D = dm.D;
-  if (tid == 0) {
-    int bm = 0;
+// A wavefront takes ML_COND_F consecutive frames, a workgroup ML_COND_W wavefronts.  The arg-max is the lowest index
+// among equal maxima (what a serial `lp > best` walk from -inf returns; a frame without any lp > -inf gets mixture 0).
+// Lane i then forms output i as muy[i] + sum_k AT[k][i] (x - mux)[k], k ascending: a load instruction reads one row
+// of AT, consecutive doubles, where a row-major A puts every lane on a cache line of its own.  The kernel is bound by
+// the D x D doubles of A that a frame pulls through L2 (41 KB at D = 72), so where the frames of a wavefront agree on
+// the mixture -- neighbouring frames of speech mostly do -- one load of AT serves all of them; the sums of a frame are
+// the same operations in the same order either way.
+#define ML_COND_F 4
+#define ML_COND_W 4
+__global__ __launch_bounds__(64 * ML_COND_W) void k_gmm_cond(const double *__restrict__ X, ml_dims dm,
+                                                            const double *__restrict__ model,
+                                                            const double *__restrict__ logp,
+                                                            double *__restrict__ E, double *__restrict__ Dv,
+                                                            int *__restrict__ mix) {
+  __shared__ double dsh_all[ML_COND_W][ML_COND_F][192];     // (x - mux) of every frame: D <= 192
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, D = dm.D;
+  const int64_t tb = ((int64_t)blockIdx.x * ML_COND_W + wv) * ML_COND_F;
+  double (*dsh)[192] = dsh_all[wv];
+  const int none = 0x7fffffff;
+  int bms[ML_COND_F];
+#pragma unroll
+  for (int f = 0; f < ML_COND_F; ++f) {
+    const int64_t t = min(tb + f, dm.T - 1);      // frames behind the last one repeat it and store nothing
+    int bm = none;
     double best = -INFINITY;
-    for (int m = 0; m < dm.M; ++m) {
-      double lp = logp[t * dm.M + m];
+    for (int m = lane; m < dm.M; m += 64) {
+      const double lp = logp[t * dm.M + m];
       if (lp > best) { best = lp; bm = m; }
     }
-    s_m = bm;
-    mix[t] = bm;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+      const double ob = __shfl_xor(best, s);
+      const int om = __shfl_xor(bm, s);
+      if (ob > best || (ob == best && om < bm)) { best = ob; bm = om; }
+    }
+    if (bm == none) bm = 0;
+    bm = __builtin_amdgcn_readfirstlane(bm);
+    bms[f] = bm;
+    const double *mux = model + (size_t)bm * ml_model_stride(D) + 2 * D * D;
+    for (int i = lane; i < D; i += 64) dsh[f][i] = X[t * D + i] - mux[i];
+    if (lane == 0 && tb + f < dm.T) mix[t] = bm;
   }
   __syncthreads();
-  const double *mod = model + (size_t)s_m * ml_model_stride(D);
-  const double *A = mod + D * D, *mux = A + D * D, *muy = mux + D, *dvar = muy + D;
-  for (int i = tid; i < D; i += blockDim.x) dsh[i] = X[t * D + i] - mux[i];
-  __syncthreads();
-  for (int i = tid; i < D; i += blockDim.x) {
-    double v = muy[i];
-    const double *ar = A + (size_t)i * D;
-    for (int k = 0; k < D; ++k) v += ar[k] * dsh[k];
-    E[t * D + i] = v;
-    Dv[t * D + i] = dvar[i];
+  bool same = true;                      // (wave-uniform: the mixtures sit in scalar registers)
+#pragma unroll
+  for (int f = 1; f < ML_COND_F; ++f) same = same && bms[f] == bms[0];
+  if (same) {
+    const double *mod = model + (size_t)bms[0] * ml_model_stride(D);
+    const double *muy = mod + 2 * D * D + D, *dvar = muy + D, *AT = mod + ml_model_at(D);
+    for (int i = lane; i < D; i += 64) {
+      double v[ML_COND_F];
+#pragma unroll
+      for (int f = 0; f < ML_COND_F; ++f) v[f] = muy[i];
+      const double *at = AT + i;
+#pragma unroll 4
+      for (int k = 0; k < D; ++k) {
+        const double a = at[(size_t)k * D];
+#pragma unroll
+        for (int f = 0; f < ML_COND_F; ++f) v[f] += a * dsh[f][k];
+      }
+      const double dv = dvar[i];
+#pragma unroll
+      for (int f = 0; f < ML_COND_F; ++f)
+        if (tb + f < dm.T) { E[(tb + f) * D + i] = v[f]; Dv[(tb + f) * D + i] = dv; }
+    }
+  } else {
+    for (int f = 0; f < ML_COND_F; ++f) {
+      if (tb + f >= dm.T) break;
+      const double *mod = model + (size_t)bms[f] * ml_model_stride(D);
+      const double *muy = mod + 2 * D * D + D, *dvar = muy + D, *AT = mod + ml_model_at(D);
+      for (int i = lane; i < D; i += 64) {
+        double v = muy[i];
+        const double *at = AT + i;
+#pragma unroll 8
+        for (int k = 0; k < D; ++k) v += at[(size_t)k * D] * dsh[f][k];
+        E[(tb + f) * D + i] = v;
+        Dv[(tb + f) * D + i] = dvar[i];
+      }
+    }
   }
 }
 
@@ -768,7 +917,45 @@ static int ml_logp_splits(int64_t T, int M, int D) {
   return (int)(s < 1 ? 1 : s);
 }
 
+// the fragment form: eight wavefronts, 256 frames per tile
+#define ML_FRAG_NW 8
+#define ML_FRAG_WGS 1024  // workgroups of a launch: measured 0.341 / 0.306 / 0.296 ms with 256 / 512 / 1024 (D = 72, 35 216 frames)
+static int ml_frag_blocks(int D) { return ml_np(D) / 16; }
+static bool ml_logp_frag(int D) { return ml_frag_blocks(D) <= ML_FRAG_MAXBLK; }
+static size_t ml_frag_lds(int D) {
+  const int nblk = ml_frag_blocks(D);
+  return sizeof(double) * ((size_t)2 * nblk * (nblk + 1) * 64 + 16 * nblk);
+}
+static int ml_frag_splits(int64_t T, int M) {
+  const int64_t ntiles = (T + 32 * ML_FRAG_NW - 1) / (32 * ML_FRAG_NW);
+  int64_t s = (ML_FRAG_WGS + M - 1) / M;
+  if (s > ntiles) s = ntiles;
+  return (int)(s < 1 ? 1 : s);
+}
+
+template <int NBLK>
+static int ml_launch_frag(kwy_ctx *ctx, const double *X, const ml_dims &dm, const double *model, double *logp) {
+  const size_t lds = ml_frag_lds(dm.D);
+  const dim3 grid((unsigned)ml_frag_splits(dm.T, dm.M), dm.M);
+  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_logp_frag<NBLK, ML_FRAG_NW>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  KWY_PROF(ctx, "k_gmm_logp", hipLaunchKernelGGL((k_gmm_logp_frag<NBLK, ML_FRAG_NW>), grid, dim3(64 * ML_FRAG_NW), lds,
+                                                 ctx->stream, X, dm, model, logp));
+  return KWY_OK;
+}
+
 static int ml_launch_logp(kwy_ctx *ctx, const double *X, const ml_dims &dm, const double *model, double *logp) {
+  if (ml_logp_frag(dm.D)) {
+    switch (ml_frag_blocks(dm.D)) {
+      case 1: return ml_launch_frag<1>(ctx, X, dm, model, logp);
+      case 2: return ml_launch_frag<2>(ctx, X, dm, model, logp);
+      case 3: return ml_launch_frag<3>(ctx, X, dm, model, logp);
+      case 4: return ml_launch_frag<4>(ctx, X, dm, model, logp);
+      case 5: return ml_launch_frag<5>(ctx, X, dm, model, logp);
+      default: return ml_launch_frag<6>(ctx, X, dm, model, logp);
+    }
+  }
+  // wider features: rows of Z_m and the frame tile in LDS
   const size_t lds = ml_logp_lds(dm.D);
   const dim3 grid((unsigned)ml_logp_splits(dm.T, dm.M, dm.D), dm.M);
   if (ml_logp_waves(dm.D) == 8) {
@@ -830,7 +1017,7 @@ static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d,
   *status_out = status;
   KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
   size_t lds_prep = sizeof(double) * 3 * D * D;
-  size_t lds_logp = ml_logp_lds(D);
+  size_t lds_logp = ml_logp_frag(D) ? ml_frag_lds(D) : ml_logp_lds(D);
   if (lds_prep > 160 * 1024 || lds_logp > 160 * 1024) { ctx->err = "gmm_mlpg: feature dimension too large"; return KWY_EINVAL; }
   KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
   const int cpw = 64 / d;
@@ -844,7 +1031,7 @@ static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d,
   const unsigned ge = (unsigned)((T * d + 255) / 256);
   hipLaunchKernelGGL(k_delta, dim3(ge), dim3(256), 0, ctx->stream, bt, dm, X);
   KWY_TRY(ml_launch_logp(ctx, X, dm, model, logp));
-  hipLaunchKernelGGL(k_gmm_cond, dim3((unsigned)T), dim3(128), 0, ctx->stream, X, dm, model, logp, E, Dv, mix);
+  hipLaunchKernelGGL(k_gmm_cond, dim3((unsigned)((T + ML_COND_F * ML_COND_W - 1) / (ML_COND_F * ML_COND_W))), dim3(64 * ML_COND_W), 0, ctx->stream, X, dm, model, logp, E, Dv, mix);
   hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, E, Dv, bt, dm, band);
   KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0, ctx->stream,
                                                      band, rhs, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
@@ -884,7 +1071,7 @@ static int soft_core(kwy_ctx *ctx, const double *x, int64_t T, int D, int M, con
   *status_out = status;
   KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
   const size_t lds_prep = sizeof(double) * 3 * D * D;
-  const size_t lds_logp = ml_logp_lds(D);
+  const size_t lds_logp = ml_logp_frag(D) ? ml_frag_lds(D) : ml_logp_lds(D);
   if (lds_prep > 160 * 1024 || lds_logp > 160 * 1024 || D > 192 || M > 256) {
     // (3 D^2 doubles of LDS for the preparation: 160 KB hold D <= 82)
     ctx->err = "gmm_convert_frames: feature dimension (<= 82 per side) or mixture count (<= 256) too large";
