@@ -14,7 +14,10 @@ Tolerances (float64 path; north_star: output within 1e-4 RMS of the CPU path):
     bit-equal, and on the gated ones max abs <= AP_ABS and max |dB| <= AP_DB (10x the worst seen on an MI355X;
     the recordings resampled up from 16 kHz: AP_ABS_UPSAMPLED / AP_DB_UPSAMPLED, see d4c_cases.py)
   * waveform: RMS <= 1e-9 given identical features (pulse positions, noise
-    stream and overlap-add are reproduced exactly; only FFT rounding differs).
+    stream and overlap-add are reproduced exactly; only FFT rounding differs), and beside it
+    tests/synth_cases.assert_wave_close -- in every block of fft_size / 2 samples max |d| <= SYN_LOCAL_REL of the
+    largest |ref| of the block and its neighbours, and max |d| <= SYN_ABS_REL max |ref| (10x the worst seen on an
+    MI355X; recordings: the _RECORDED pair, see synth_cases.py).
 """
 import os
 
@@ -25,6 +28,7 @@ from scipy.io import wavfile
 from conftest import CLB_WAV, SLT_WAV, clb_variant
 from ct_cases import assert_sp_close
 from d4c_cases import RATES, UNGATED, assert_ap_close, batch_cases, edge_case
+from synth_cases import assert_wave_close
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +101,7 @@ def test_synthesis_parity(ko, kw, path):
     rms = np.sqrt(np.mean((got - ref) ** 2))
     assert rms <= 1e-9, rms
     assert np.abs(got - ref).max() <= 1e-8
+    assert_wave_close(got, ref, (sp.shape[1] - 1) * 2, tag(path), recording=True)
 
 
 def test_synthesis_leading_silence(ko, kw):
@@ -219,6 +224,7 @@ def test_synthesis_voicing_patterns(ko, kw):
         assert got.shape == ref.shape
         scale = max(np.sqrt(np.mean(ref ** 2)), 1e-12)
         assert np.sqrt(np.mean((got - ref) ** 2)) <= 1e-9 * max(scale, 1.0) + 1e-12 * scale, (case, fs, T)
+        assert_wave_close(got, ref, (K - 1) * 2, f'voicing pattern {case} at {fs}, {T} frames')
         assert np.array_equal(got, kw.synthesize(f0, sp, ap, fs, 5.0))
 
 
@@ -247,6 +253,7 @@ def test_synthesis_phase_chain_extremes(ko, kw, fs, seconds, f0_hz, lead):
     assert got.shape == ref.shape
     scale = max(np.sqrt(np.mean(ref ** 2)), 1e-12)
     assert np.sqrt(np.mean((got - ref) ** 2)) <= 1e-9 * max(scale, 1.0) + 1e-12 * scale
+    assert_wave_close(got, ref, (K - 1) * 2, f'phase chain {fs} Hz, {seconds} s at {f0_hz} Hz, lead {lead}')
     assert np.array_equal(got, kw.synthesize(f0, sp, ap, fs, 5.0))
 
 
@@ -288,6 +295,7 @@ def test_frame_periods(ko, kw, frame_period):
     got = kw.synthesize(f0, sp, ap, fs, float(frame_period))
     ref = ko.synthesize(f0, sp, ap, fs, float(frame_period))
     assert np.sqrt(np.mean((got - ref) ** 2)) <= 1e-9
+    assert_wave_close(got, ref, (sp.shape[1] - 1) * 2, f'{tag(CLB_WAV)} frame period {frame_period}', recording=True)
 
 
 @pytest.mark.parametrize('fs,up,down', [(8000, 1, 2), (12000, 3, 4)])
@@ -303,7 +311,9 @@ def test_low_sampling_rates(ko, kw, fs, up, down):
     ref = ko.d4c(x, f0, t, fs)
     assert_ap_close(kw.d4c(x, f0, t, fs), ref, f'clb resampled to {fs}')
     sp, ap = ko.cheaptrick(x, f0, t, fs), ref
-    assert np.sqrt(np.mean((kw.synthesize(f0, sp, ap, fs) - ko.synthesize(f0, sp, ap, fs)) ** 2)) <= 1e-9
+    got, ref = kw.synthesize(f0, sp, ap, fs), ko.synthesize(f0, sp, ap, fs)
+    assert np.sqrt(np.mean((got - ref) ** 2)) <= 1e-9
+    assert_wave_close(got, ref, (sp.shape[1] - 1) * 2, f'clb resampled to {fs}', recording=True)
 
 
 def test_options(ko, kw):
@@ -358,7 +368,9 @@ def test_edge_inputs(ko, kw):
     sp_close(got, ref, 'edge inputs: digital silence')
     sp = ko.cheaptrick(x, f0, t, fs)
     ap = ko.d4c(x, f0, t, fs)
-    assert np.sqrt(np.mean((kw.synthesize(f0, sp, ap, fs) - ko.synthesize(f0, sp, ap, fs)) ** 2)) <= 1e-12
+    got, ref = kw.synthesize(f0, sp, ap, fs), ko.synthesize(f0, sp, ap, fs)
+    assert np.sqrt(np.mean((got - ref) ** 2)) <= 1e-12
+    assert_wave_close(got, ref, (sp.shape[1] - 1) * 2, 'edge inputs: unvoiced noise')
     # very short signal, frames beyond the end of x
     x1 = rng.standard_normal(90) * 0.1
     f01 = np.array([0.0, 120.0, 0.0]); t1 = np.arange(3) * 0.005
@@ -421,6 +433,7 @@ def test_synthesis_8192_points(ko, kw):
     got, ref = kw.synthesize(f0, sp8, ap8, fs, 5.0), ko.synthesize(f0, sp8, ap8, fs, 5.0)
     assert got.shape == ref.shape
     assert np.sqrt(np.mean((got - ref) ** 2)) <= 1e-9 * max(1.0, np.abs(ref).max())
+    assert_wave_close(got, ref, 8192, f'{tag(clb_variant("96"))} 120 frames stretched to 8192 points', recording=True)
 
 
 # ---------------------------------------------------------------- the randn table and the jump-ahead path beyond it
