@@ -313,6 +313,53 @@ int kwy_gv_postfilter_dev(kwy_ctx *ctx, const double *x, int64_t rows, int cols,
 int kwy_gv_postfilter_batch_dev(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col,
                                 const double *gv, double strength, int32_t *status);
 
+/* ---- modulation spectrum -------------------------------------------------------------- */
+/* The reference has no counterpart.  These entries add the utterance-level modulation-spectrum postfilter of Takamichi
+ * et al. (2016): the global-variance filter above fixes one number per trajectory, this one every modulation-frequency
+ * bin of it.  For column d of a row-major (T, cols) matrix x and a transform length L in {512, 1024, 2048, 4096, 8192},
+ * T <= L (KWY_EINVAL otherwise, nothing is written):
+ *   m = mean of x[:, d] (as kwy_column_moments defines it),  z[t] = x[t, d] - m for t < T, 0 for T <= t < L
+ *   Z = the real transform of z, bins f = 0 .. L/2,   s[f] = log(max(|Z[f]|^2, DBL_MIN) / T)
+ * s is the log modulation spectrum.  Statistics are (n, mean, M2) per (column, bin), cols x (L/2 + 1) x 3 doubles,
+ * sigma = sqrt(M2 / n); bin 0 carries none (after the mean removal it holds rounding noise) and stays (0, 0, 0).
+ * The filter at strength k in [0, 1], with the statistics G of converted and N of natural speech, for f >= 1:
+ *   s'[f] = (1 - k) s[f] + k (sigmaN[f] / sigmaG[f] (s[f] - muG[f]) + muN[f]),   g[f] = exp((s'[f] - s[f]) / 2),  g[0] = 1
+ *   out[t, d] = base[t, d] + (z'[t] - z[t]),   z' = the inverse transform of g Z, t < T
+ * base == x is the plain filter, base == the differential conversion the differential one.  A bin whose statistics
+ * are unusable (nG < 2, nN < 2, a mean that is not finite, sigmaG not finite or <= 0, sigmaN not finite or < 0) or
+ * whose gain is not finite keeps g = 1 and is counted in the matrix's status word.  Columns below first_col, columns
+ * with T < 2 or M2 == 0, and everything at k == 0 are copied from base bit for bit.
+ * Every reduction has a fixed order: a matrix's result depends on the matrix, the statistics and the shape alone.
+ * cols <= 64.  The _dev forms allocate nothing and do not synchronise once the context holds the tables of the
+ * length (its first call makes them); the host forms stage through HBM and synchronise. */
+/* spectra: count x cols x (L/2 + 1) doubles, written; valid: count x cols int32, written: 1, or 0 for a column with
+ * T < 2 or M2 == 0, whose row of spectra is then zero */
+int kwy_ms_logspectra(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols, int L, double *spectra,
+                      int32_t *valid);
+int kwy_ms_logspectra_batch_dev(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols, int L, double *spectra,
+                                int32_t *valid);
+/* acc: cols x (L/2 + 1) x 3, updated in place by Welford's step over the count matrices in index order, the invalid
+ * columns skipped: bit-equal however a corpus was grouped into calls.  A new accumulator is all zero. */
+int kwy_ms_stats_update(kwy_ctx *ctx, double *acc, const double *spectra, const int32_t *valid, int count, int cols,
+                        int L);
+int kwy_ms_stats_update_dev(kwy_ctx *ctx, double *acc, const double *spectra, const int32_t *valid, int count, int cols,
+                            int L);
+typedef struct kwy_ms_job {
+  const double *x;        /* rows x cols: the matrix whose modulation spectrum is modified */
+  int64_t rows;
+  const double *base;     /* rows x cols (may equal x) */
+  double *out;            /* rows x cols, written (may equal base or x) */
+} kwy_ms_job;
+/* statsG, statsN: cols x (L/2 + 1) x 3 -- device memory in the _dev forms; status: one int32 per matrix (or NULL),
+ * set to the number of bins that kept g = 1 because their statistics or their gain are unusable */
+int kwy_ms_postfilter(kwy_ctx *ctx, const kwy_ms_job *jobs, int count, int cols, int first_col, int L,
+                      const double *statsG, const double *statsN, double strength, int32_t *status);
+int kwy_ms_postfilter_dev(kwy_ctx *ctx, const double *x, int64_t rows, int cols, int first_col, int L,
+                          const double *statsG, const double *statsN, double strength, const double *base, double *out,
+                          int32_t *status);
+int kwy_ms_postfilter_batch_dev(kwy_ctx *ctx, const kwy_ms_job *jobs, int count, int cols, int first_col, int L,
+                                const double *statsG, const double *statsN, double strength, int32_t *status);
+
 /* ---- waveform pitch shift -------------------------------------------------------------- */
 /* The reference has no counterpart: its differential output (kwiiyatta/convert_voice.py:19,39-40) keeps the source's
  * pitch.  These entries add the waveform pitch shifter GMM voice-conversion recipes run on the source recordings: a

@@ -105,6 +105,13 @@ SIGNATURES = {
     'kwy_gv_postfilter': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
     'kwy_gv_postfilter_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp]),
     'kwy_gv_postfilter_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp]),
+    'kwy_ms_logspectra': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    'kwy_ms_logspectra_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    'kwy_ms_stats_update': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int]),
+    'kwy_ms_stats_update_dev': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int]),
+    'kwy_ms_postfilter': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp]),
+    'kwy_ms_postfilter_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp]),
+    'kwy_ms_postfilter_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_dbl, c_vp]),
     'kwy_pitch_stretched_length': (c_i64, [c_i64, c_dbl]),
     'kwy_pitch_frames': (c_i64, [c_i64, c_int, c_dbl]),
     'kwy_pitch_shift': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
@@ -274,6 +281,8 @@ F0MapJob = _job_struct('F0MapJob', 'kwy_f0_map_job: one f0 track through the f0 
 GvMatrix = _job_struct('GvMatrix', 'kwy_gv_matrix: one matrix of a column moments call', [('x', c_vp), ('rows', c_i64)])
 GvJob = _job_struct('GvJob', 'kwy_gv_job: one matrix through the global-variance postfilter',
                     [('x', c_vp), ('rows', c_i64), ('moments', c_vp), ('base', c_vp), ('out', c_vp)])
+MsJob = _job_struct('MsJob', 'kwy_ms_job: one matrix through the modulation-spectrum postfilter',
+                    [('x', c_vp), ('rows', c_i64), ('base', c_vp), ('out', c_vp)])
 PitchJob = _job_struct('PitchJob', 'kwy_pitch_job: one waveform through the pitch shifter',
                        [('x', c_vp), ('n', c_i64), ('y', c_vp), ('pos', c_vp)])
 McdJob = _job_struct('McdJob', 'kwy_mcd_job: one utterance of a mel-cepstral distortion call',

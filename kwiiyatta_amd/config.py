@@ -10,6 +10,8 @@ import sys
 
 import numpy as np
 
+from .backend.ms import LENGTHS as MS_LENGTHS
+
 VOCODER_OPTIONS = (
     ('--frame-period', dict(type=int, default=5, help='Frame period milli-seconds of vocoder')),
     ('--mcep-order', dict(type=int, default=24, help='Mel-cepstrum order for spectrum envelope')),
@@ -80,6 +82,16 @@ CONVERTER_OPTIONS += (
 )
 
 
+# an addition to the reference's options (it has no postfilter)
+CONVERTER_OPTIONS += (
+    ('--ms-length', dict(type=int, choices=MS_LENGTHS, default=None, metavar='L',
+                         help='Transform length of the modulation-spectrum statistics learnt with --ms, in frames (one '
+                              f'of {", ".join(map(str, MS_LENGTHS))}; default 4096); no training or converted utterance '
+                              'may be longer; kept in the converter model, which decides when one is loaded; only '
+                              'convert_voice --ms uses it')),
+)
+
+
 def transpose_key(text):
     """--transpose-key: semitones, within the reference dialog's spin box range (view/qt/ui/kwiieiya.ui:262-280)"""
     try:
@@ -113,6 +125,13 @@ GV_OPTION = ('--gv', dict(type=gv_strength, nargs='?', const=1.0, default=0.0, m
                                'model); STRENGTH within [0, 1], 1 when omitted'))
 
 
+MS_OPTION = ('--ms', dict(type=gv_strength, nargs='?', const=1.0, default=0.0, metavar='STRENGTH',
+                          help='Modulation-spectrum postfilter on the converted mel-cepstrum: move every modulation '
+                               'frequency of every trajectory from the statistics of converted speech to those of the '
+                               'target speaker (both kept in the converter model); runs before --gv; STRENGTH within '
+                               '[0, 1], 1 when omitted'))
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -135,6 +154,9 @@ class Config:
 
     def add_gv_argument(self):
         self._declare((GV_OPTION,))
+
+    def add_ms_argument(self):
+        self._declare((MS_OPTION,))
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)
@@ -223,9 +245,10 @@ class Config:
         sides = [k.WavFileDataset(self.source_path, Analyzer=source), k.WavFileDataset(self.target_path, Analyzer=analyze)]
         return k.align(*sides)
 
-    def train_converter(self, f0_stats=False, gv_stats=False, **kwargs):
-        """f0_stats=True / gv_stats=True: training also computes the f0 statistics / the target's global variance (and
-        the model file keeps them); a loaded model without them is a parser error"""
+    def train_converter(self, f0_stats=False, gv_stats=False, ms_stats=False, **kwargs):
+        """f0_stats=True / gv_stats=True / ms_stats=True: training also computes the f0 statistics / the target's global
+        variance / the modulation-spectrum statistics at --ms-length (and the model file keeps them); a loaded model
+        without them is a parser error"""
         converter = self.create_converter(**kwargs)
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
@@ -247,19 +270,24 @@ class Config:
             if gv_stats and converter.gv_stats is None:
                 self.parser.error(f'{model}: the converter model has no global variance statistics; retrain it with '
                                   f'--gv (a new --converter-model file)')
+            if ms_stats and converter.ms_stats is None:
+                self.parser.error(f'{model}: the converter model has no modulation spectrum statistics; retrain it '
+                                  f'with --ms (a new --converter-model file)')
             return converter
-        converter = self._train(converter, f0_stats=f0_stats, gv_stats=gv_stats)
+        converter = self._train(converter, f0_stats=f0_stats, gv_stats=gv_stats, ms_stats=ms_stats)
         if model is not None:
             converter.save(model)
         return converter
 
-    def _train(self, converter, f0_stats=False, gv_stats=False):
+    def _train(self, converter, f0_stats=False, gv_stats=False, ms_stats=False):
         converter.source_f0_rate = self._model_f0_rate = self.resolve_source_f0_rate()
         dataset = self.load_dataset(converter.source_f0_rate)
         keys = sorted(dataset.keys())[slice(self.skip_files, None)]
         extra = dict(f0_stats=True) if f0_stats else {}
         if gv_stats:
             extra['gv_stats'] = True
+        if ms_stats:
+            extra.update(ms_stats=True, ms_length=getattr(self, 'ms_length', None) or 4096)
         if getattr(self, 'align_iterations', None):
             extra['align_iterations'] = self.align_iterations
         converter.train(dataset, keys[:self.max_files], **extra)

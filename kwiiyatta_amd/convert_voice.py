@@ -18,6 +18,12 @@ never called.  `--convert-f0` and `--gv` compose with it unchanged: their statis
 averages, its trajectories vary about 0.6 times as much as the target speaker's and the voice sounds muffled; the
 filter stretches every coefficient's trajectory about its own mean until its variance is the one the target's training
 utterances have (learnt with the converter, kept in its model file), or STRENGTH of the way there.
+`--ms [STRENGTH]` runs the modulation-spectrum postfilter on the converted mel-cepstrum of both outputs, before `--gv`
+where both are given: the smoothing of GMM + MLPG removes the fast movement of a trajectory (10 - 50 Hz of modulation
+frequency) far more than the slow, which one variance ratio cannot undo; the filter takes the log power spectrum of
+every coefficient's trajectory along time and moves every bin from the statistics of converted speech to those of the
+target speaker's natural speech (both learnt with the converter at `--ms-length` frames and kept in its model file),
+or STRENGTH of the way there, keeping the phase.  No utterance may be longer than that length.
 `--align-iterations N` trains with iterative re-alignment: after the first fit every training pair is aligned again, N
 times over, with the source mel-cepstrum converted by the converter fitted so far in its DTW features (the reference
 aligns once, on the two speakers' own coefficients), the joint matrix is rebuilt along the new paths and the mixture
@@ -29,15 +35,17 @@ import numpy as np
 OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
-def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0):
+def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
-    global-variance postfilter of that strength (converter.convert(gv=...), either output).  A converter trained on
+    global-variance postfilter of that strength (converter.convert(gv=...), either output); ms > 0: through the
+    modulation-spectrum postfilter first (converter.convert(ms=...)).  A converter trained on
     pitch-shifted sources (converter.source_f0_rate != 1) gets the file's waveform shifted the same way."""
     import kwiiyatta_amd as k
     source = analyze_source(conf, converter, src_path)
-    converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}))
+    converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
+                                  **(dict(ms=ms) if ms > 0 else {}))
     if diffvc:
         return k.apply_mlsa_filter(source, converted)
     rendered = k.feature(source)
@@ -88,7 +96,7 @@ class _Pcm16:
         wavfile.write(wav, self.fs, self.pcm)
 
 
-def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0):
+def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -98,18 +106,24 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     `synthesize` and `save`'s normalisation and 16-bit truncation all run on the GPU
     (corpus.convert_batch(pcm=True, diff=...)); the host reads the wav files and writes 2 bytes per sample.
     convert_f0 / transpose_key: the .synth.wav outputs on the mapped f0 (as `convert` does), mapped on the device.
-    gv > 0: both outputs from the postfiltered mel-cepstra (as `convert` does), filtered on the device."""
+    gv > 0 / ms > 0: both outputs from the postfiltered mel-cepstra (as `convert` does), filtered on the device; a file
+    longer than the converter's ms_length goes through `convert`, which names it."""
     import kwiiyatta_amd as k
     from . import corpus
+    from ._lib import lib
     from .converter.delta import DeltaFeatureConverter
     out, batch = {}, []
     period = next((s.frame_period for s in _stages(converter) if isinstance(s, DeltaFeatureConverter)), None)
     for path in paths:
         a = conf.create_analyzer(path, Analyzer=k.analyze_wav)
-        if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or \
+        # (the frame count ConvertWave itself takes for a bare waveform -- the same call on the same number of samples,
+        # which the pitch shifter keeps -- so a file that passes here fits there)
+        too_long = ms > 0 and converter.ms_length is not None and \
+            lib.kwy_dio_frames(int(a.fs), len(a.wavdata.data), float(a.frame_period)) > converter.ms_length
+        if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or too_long or \
                 (period is not None and a.frame_period != period):
             out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
-                                       transpose_key=transpose_key, gv=gv)
+                                       transpose_key=transpose_key, gv=gv, ms=ms)
         else:
             batch.append((path, a))
     if batch:
@@ -121,7 +135,9 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
                                    frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
                                    f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key,
-                                   **(dict(gv_stats=converter.gv_stats, gv_strength=gv) if gv > 0 else {}))
+                                   **(dict(gv_stats=converter.gv_stats, gv_strength=gv) if gv > 0 else {}),
+                                   **(dict(ms_stats=converter.ms_stats, ms_length=converter.ms_length, ms_strength=ms)
+                                      if ms > 0 else {}))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -149,12 +165,14 @@ def main():
                            'the training data, kept in the converter model)')
     conf.add_transpose_key_argument()
     conf.add_gv_argument()
+    conf.add_ms_argument()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
-    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0)
+    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
+                                     ms_stats=conf.ms > 0)
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
-                                  diffvc=not conf.no_diffvc, gv=conf.gv, **pitch) if conf.batch else {}
+                                  diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -167,7 +185,7 @@ def main():
             if (wav_path, differential) in batched:
                 batched[wav_path, differential].save(out)
             else:
-                convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv,
+                convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms,
                         **({} if differential else pitch)).save(out)
 
 

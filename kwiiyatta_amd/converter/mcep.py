@@ -53,17 +53,21 @@ def _f0_tracks(dataset, keys):
     return sides
 
 
-def _target_mel_cepstra(dataset, keys, order, fs):
-    """the target side's mel-cepstra (frames, order + 1) of `keys` in sorted order, at the given order and sampling
+def _side_mel_cepstra(dataset, keys, order, fs, side):
+    """one side's (0: source, 1: target) MelCepstrum records of `keys` in sorted order, at the given order and sampling
     rate: the frames `_f0_tracks` takes, c0 included"""
     stage = _trimmed_stage(dataset)
-    mats = []
+    records = []
     for key in sorted(keys):
-        snap = _pkg().feature(stage[key][1])
+        snap = _pkg().feature(stage[key][side])
         snap.mel_cepstrum_order = order
-        record = snap.mel_cepstrum if snap.fs == fs else snap.resample_mel_cepstrum(fs)
-        mats.append(np.ascontiguousarray(record.data, dtype=np.float64))
-    return mats
+        records.append(snap.mel_cepstrum if snap.fs == fs else snap.resample_mel_cepstrum(fs))
+    return records
+
+
+def _target_mel_cepstra(dataset, keys, order, fs):
+    """the target side's mel-cepstra (frames, order + 1) of `keys` in sorted order"""
+    return [np.ascontiguousarray(r.data, dtype=np.float64) for r in _side_mel_cepstra(dataset, keys, order, fs, 1)]
 
 
 class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
@@ -72,6 +76,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         self.mcep_fs = mcep_fs
         self.f0_stats = None
         self.gv_stats = None
+        self.ms_stats, self.ms_length = None, None
         # the pitch ratio the source waveforms were (and are to be) shifted by before analysis (backend.pitch): set by
         # whoever prepares the training set (Config.train_converter), kept in the model file; 1: no shift
         self.source_f0_rate = 1.0
@@ -79,14 +84,22 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         self.align_iterations = 0
         self.align_history = []
 
-    def train(self, dataset, keys, f0_stats=False, gv_stats=False, align_iterations=0, **kwargs):
+    def train(self, dataset, keys, f0_stats=False, gv_stats=False, align_iterations=0, ms_stats=False, ms_length=4096,
+              **kwargs):
         """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`).
         gv_stats=True: also the target side's global variance (`gv_stats`, order + 1 values: per coefficient the mean
         over the training utterances of its variance within the utterance; used by `convert(gv=...)`).
-        align_iterations=N > 0: iterative re-alignment of the training set, see `_train_realigned`"""
+        align_iterations=N > 0: iterative re-alignment of the training set, see `_train_realigned`
+        ms_stats=True: also the modulation-spectrum statistics (`ms_stats` = (G, N), each (order + 1, ms_length / 2 + 1,
+        3): per coefficient and modulation-frequency bin the count, mean and M2 over the training utterances of the log
+        modulation spectrum -- N of the target side's mel-cepstra, G of the source side's converted by the mixture just
+        fitted (`convert(..., diff=False)`); used by `convert(ms=...)`).  ms_length: the transform length, which no
+        utterance may exceed (`ms_length`)"""
         if isinstance(align_iterations, bool) or int(align_iterations) != align_iterations or align_iterations < 0:
             raise ValueError(f'align_iterations must be a non-negative integer, not {align_iterations!r}')
         self.align_iterations, self.align_history = int(align_iterations), []
+        if ms_stats:
+            self._check_ms_lengths(dataset, keys, ms_length)          # (before the fit is paid for)
         if self.align_iterations > 0:
             self._train_realigned(dataset, list(keys), self.align_iterations, kwargs)
         else:
@@ -108,6 +121,40 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             if not mats:
                 raise ValueError('global variance statistics: no training files')
             self.gv_stats = gvfilter.gv_from_moments(gvfilter.column_moments(mats))
+        self.ms_stats, self.ms_length = None, None
+        if ms_stats:
+            self._train_ms(dataset, keys, ms_length)
+
+    @staticmethod
+    def _check_ms_lengths(dataset, keys, length):
+        """what the modulation-spectrum statistics need of the training set, as far as frame counts tell: no utterance
+        of either side longer than the transform (the converted source has the source's frames), two of two frames"""
+        from ..backend import ms as msfilter
+        stage = _trimmed_stage(dataset)
+        usable = 0
+        for key in sorted(keys):
+            frames = [len(feature.f0) for feature in stage[key]]
+            msfilter._fits(frames, msfilter._length(length))
+            usable += min(frames) >= 2
+        if usable < 2:
+            raise ValueError('modulation spectrum statistics: fewer than two usable training utterances (of at least '
+                             'two frames)')
+
+    def _train_ms(self, dataset, keys, length):
+        from ..backend import ms as msfilter
+        as_f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        natural = _target_mel_cepstra(dataset, keys, self.order, self.fs)
+        if not natural:
+            raise ValueError('modulation spectrum statistics: no training files')
+        stats_n = msfilter.statistics(natural, length)
+        converted = [as_f64(self.convert(source, diff=False).data)
+                     for source in _side_mel_cepstra(dataset, keys, self.order, self.fs, 0)]
+        stats_g = msfilter.statistics(converted, length)
+        for name, stats in (('target', stats_n), ('converted source', stats_g)):
+            if stats[1:, 1:, 0].min() < 2:
+                raise ValueError(f'modulation spectrum statistics: fewer than two usable {name} utterances (of at least '
+                                 f'two frames and with every coefficient varying)')
+        self.ms_stats, self.ms_length = (stats_g, stats_n), int(length)
 
     def _train_realigned(self, dataset, keys, iterations, fit_options):
         """Iterative re-alignment of the training set (Toda et al.'s joint-feature iterations): fit 0 is the training
@@ -202,14 +249,17 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
 
     def save(self, path):
         """the trained stack as one .npz: the mixture's parameters and what the outer stages learnt from the
-        training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics and the global variance when
-        there are any; the pitch ratio of the source waveforms; the re-alignment passes of the training as
+        training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics, the global variance and the
+        modulation-spectrum statistics when there are any; the pitch ratio of the source waveforms; the re-alignment passes of the training as
         `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`)"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
             if self.gv_stats is not None:
                 extra['gv_stats'] = np.array(self.gv_stats, dtype=np.float64)
+            if self.ms_stats is not None:
+                extra.update(ms_stats_g=np.array(self.ms_stats[0], dtype=np.float64),
+                             ms_stats_n=np.array(self.ms_stats[1], dtype=np.float64), ms_length=int(self.ms_length))
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      source_f0_rate=float(self.source_f0_rate),
@@ -220,7 +270,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
 
     def load(self, path):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
-        the file.  `f0_stats` / `gv_stats` are None for a file without them (written without these statistics, or before
+        the file.  `f0_stats` / `gv_stats` / `ms_stats` are None for a file without them (written without these statistics, or before
         they existed); `source_f0_rate` is 1.0 for a file without it, `align_iterations` 0 and `align_history` empty"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
@@ -241,6 +291,10 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             gmm.converged_ = True
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
             self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None
+            has_ms = 'ms_stats_g' in z.files
+            self.ms_stats = tuple(np.array(z[n], dtype=np.float64)
+                                  for n in ('ms_stats_g', 'ms_stats_n')) if has_ms else None
+            self.ms_length = int(z['ms_length']) if has_ms else None
             self.source_f0_rate = float(z['source_f0_rate']) if 'source_f0_rate' in z.files else 1.0
             self.align_iterations = int(z['align_iterations']) if 'align_iterations' in z.files else 0
             mcd = z['align_mcd'] if 'align_mcd' in z.files else ()
@@ -249,29 +303,44 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                                   for n, v in zip(rows, mcd)]
         return self
 
-    def convert(self, mel_cepstrum, gv=0.0, **kwargs):
+    def convert(self, mel_cepstrum, gv=0.0, ms=0.0, **kwargs):
         """a MelCepstrum at the converter's sampling rate: c0 of the input, c1..cN converted.
         gv > 0 (a strength within [0, 1]; needs `gv_stats`): the converted c1..cN through the global-variance
         postfilter, each trajectory stretched about its own mean towards the target's variance.  With diff=True the
         filter's change of the NON-differential conversion is added to the differential one, which costs one more
-        conversion (MLPG) of the same input."""
+        conversion (MLPG) of the same input.
+        ms > 0 (a strength within [0, 1]; needs `ms_stats`): the converted c1..cN through the modulation-spectrum
+        postfilter, every modulation-frequency bin of each trajectory moved from the statistics of converted speech
+        towards the target's; it composes with diff=True as gv does.  With both, the modulation-spectrum filter comes
+        first and the global-variance filter takes its moments from that filter's output."""
         if mel_cepstrum.order != self.order:
             raise ValueError(f'order is expected to {self.order!s} but {mel_cepstrum.order!s}')
         if not 0.0 <= gv <= 1.0:
             raise ValueError(f'global variance: strength {gv!r} is outside [0, 1]')
         if gv > 0 and self.gv_stats is None:
             raise ValueError('global variance: the converter has no statistics (train it with gv_stats=True)')
+        if not 0.0 <= ms <= 1.0:
+            raise ValueError(f'modulation spectrum: strength {ms!r} is outside [0, 1]')
+        if ms > 0 and self.ms_stats is None:
+            raise ValueError('modulation spectrum: the converter has no statistics (train it with ms_stats=True)')
         out = copy.copy(mel_cepstrum) if mel_cepstrum.fs == self.fs else _pkg().resample(mel_cepstrum, self.fs)
         power, shape = out.data[:, :1], out.data[:, 1:]
         converted = super().convert(shape, raw=mel_cepstrum, **kwargs)
-        if gv > 0:
-            from ..backend import gv as gvfilter
+        if gv > 0 or ms > 0:
             as_f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-            target = as_f64(self.gv_stats[1:])
-            if kwargs.get('diff'):
-                plain = super().convert(shape, raw=mel_cepstrum, **dict(kwargs, diff=False))
-                converted = gvfilter.postfilter(as_f64(plain), target, gv, base=as_f64(converted), first_col=0)
-            else:
-                converted = gvfilter.postfilter(as_f64(converted), target, gv, first_col=0)
+            converted = as_f64(converted)
+            diff = bool(kwargs.get('diff'))
+            plain = as_f64(super().convert(shape, raw=mel_cepstrum, **dict(kwargs, diff=False))) if diff else converted
+            if ms > 0:
+                from ..backend import ms as msfilter
+                stats_g, stats_n = (as_f64(s[1:]) for s in self.ms_stats)
+                if diff:
+                    plain, converted = msfilter.postfilter([plain, plain], stats_g, stats_n, ms, base=[plain, converted],
+                                                           first_col=0)
+                else:
+                    plain = converted = msfilter.postfilter(plain, stats_g, stats_n, ms, first_col=0)
+            if gv > 0:
+                from ..backend import gv as gvfilter
+                converted = gvfilter.postfilter(plain, as_f64(self.gv_stats[1:]), gv, base=converted, first_col=0)
         out.data = np.hstack((power, converted))
         return out

@@ -708,6 +708,26 @@ def _gv_on_device(gv_stats, gv_strength, order, dev, on=True):
     return gv
 
 
+def _ms_on_device(ms_stats, ms_length, ms_strength, order, dev, on=True):
+    """the options of the modulation-spectrum postfilter, checked before anything is put on the device: -> the (G, N)
+    statistics, (order + 1, ms_length / 2 + 1, 3) each, as device tensors, or None when nothing is filtered (strength 0,
+    or on=False: no conversion)"""
+    if not 0.0 <= float(ms_strength) <= 1.0:
+        raise ValueError(f'modulation spectrum: strength {ms_strength!r} is outside [0, 1]')
+    if not (on and ms_strength > 0):
+        return None
+    if ms_stats is None or len(ms_stats) != 2:
+        raise ValueError('modulation spectrum: ms_strength > 0 needs ms_stats, the (G, N) pair of a trained converter')
+    pair = tuple(to_device(v, dev, dtype=np.float64).to(dev).contiguous() for v in ms_stats)
+    length = 2 * (pair[0].shape[1] - 1) if pair[0].dim() == 3 else None
+    if ms_length is not None and int(ms_length) != length:
+        raise ValueError(f'modulation spectrum: ms_stats are of length {length}, not ms_length = {ms_length}')
+    for v in pair:
+        if v.shape != (order + 1, (length or 0) // 2 + 1, 3) or v.dtype != torch.float64:
+            raise ValueError(f'modulation spectrum: ms_stats must be two ({order + 1}, L/2 + 1, 3) float64 arrays')
+    return pair
+
+
 def _f0_stats_on_device(f0_stats, dev):
     """(mu_src, sigma_src, mu_tgt, sigma_tgt) as 4 doubles on the device (a 4-tuple, or such a tensor already), or None"""
     return None if f0_stats is None else torch.as_tensor(f0_stats if torch.is_tensor(f0_stats) else list(f0_stats),
@@ -736,10 +756,16 @@ class ConvertWave:
     or on the device): the converted mel-cepstra through the global-variance postfilter right after the conversion
     (kwy_column_moments_batch_dev, kwy_gv_postfilter_batch_dev on c1..cN, in place); with diff=True the differential
     conversion then runs early and takes the filter's change of the plain conversion BEFORE that one is filtered in
-    place.  `gv_status` holds a word per utterance (non-zero: coefficients left unfiltered, backend.gv.postfilter)."""
+    place.  `gv_status` holds a word per utterance (non-zero: coefficients left unfiltered, backend.gv.postfilter).
+    ms_strength > 0 (with a GMM and ms_stats, the (G, N) pair of MelCepstrumFeatureConverter.ms_stats, of transform
+    length ms_length): the converted mel-cepstra through the modulation-spectrum postfilter between the conversion and
+    the global-variance filter (kwy_ms_postfilter_batch_dev on c1..cN, in place; the differential conversion takes the
+    filter's change of the plain one first, as with gv).  `ms_status` holds a word per utterance (non-zero: bins left
+    unfiltered, backend.ms.postfilter); an utterance of more than ms_length frames is a ValueError."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
-                 f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0):
+                 f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
+                 ms_strength=0.0):
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
         self.diff = bool(diff) and gmm is not None
         self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
@@ -835,6 +861,17 @@ class ConvertWave:
                 if self.diff:
                     self.j_gv_diff = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], self.mc_diff_rows[i],
                                                                   self.mc_diff_rows[i]) for i in range(n)])
+            self.ms_status, self.ms_strength = None, float(ms_strength)
+            self.ms = _ms_on_device(ms_stats, ms_length, ms_strength, order, dev, on=gmm is not None)
+            if self.ms is not None:
+                from .backend import ms as msfilter
+                self.ms_length = 2 * (self.ms[0].shape[1] - 1)
+                msfilter._fits(self.T, self.ms_length)
+                self.ms_status = torch.zeros(n, dtype=torch.int32, device=dev)
+                self.j_ms = _lib.job_array(_lib.MsJob, [(conv[i], self.T[i], conv[i], conv[i]) for i in range(n)])
+                if self.diff:
+                    self.j_ms_diff = _lib.job_array(_lib.MsJob, [(conv[i], self.T[i], self.mc_diff_rows[i],
+                                                                  self.mc_diff_rows[i]) for i in range(n)])
             self.j_render = _lib.synth_job_array([(self.plan[i], spec[i], ap[i], self.wave[i]) for i in range(n)])
         self.frames = int(sum(self.T))
 
@@ -863,13 +900,22 @@ class ConvertWave:
             else:
                 chk(lib.kwy_cheaptrick_mcep_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs), order, self.alpha))
                 chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv, n, order, self.gmm.M, _p(self.model)))
+                cols = order + 1
+                # the differential coefficients take a filter's change of the plain conversion, which the filter of the
+                # plain conversion (in place) then overwrites: the differential conversion in front of the first filter
+                # that runs, on one stream
+                if self.ms_status is not None:
+                    stats = (self.ms_length, _p(self.ms[0]), _p(self.ms[1]), self.ms_strength)
+                    if self.diff:
+                        chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
+                        chk(lib.kwy_ms_postfilter_batch_dev(h, self.j_ms_diff, n, cols, 1, *stats, None))
+                    chk(lib.kwy_ms_postfilter_batch_dev(h, self.j_ms, n, cols, 1, *stats, _p(self.ms_status)))
                 if self.gv_status is not None:
-                    cols = order + 1
                     chk(lib.kwy_column_moments_batch_dev(h, self.j_gv_mom, n, cols, _p(self.gv_moments)))
                     if self.diff:
-                        # the differential coefficients take the filter's change of the plain conversion, which the
-                        # filter of the plain conversion (in place) then overwrites: this order, on one stream
-                        chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
+                        if self.ms_status is None:
+                            chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M,
+                                                               _p(self.model_diff)))
                         chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv_diff, n, cols, 1, _p(self.gv), self.gv_strength,
                                                             None))
                     chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv, n, cols, 1, _p(self.gv), self.gv_strength,
@@ -882,7 +928,7 @@ class ConvertWave:
             if self.diff:
                 # the differential conversion of the same mel-cepstra, its filter over the INPUT waveforms: all
                 # utterances' recursions side by side (one wavefront each)
-                if self.gv_status is None:           # (with the postfilter it ran above)
+                if self.gv_status is None and self.ms_status is None:           # (with a postfilter it ran above)
                     chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
                 if not self.defer_mlsa:
                     self.run_mlsa(ls.ctx)
@@ -904,17 +950,21 @@ class ConvertWave:
 
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
-                    f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0):
+                    f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
+                    ms_strength=0.0):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
-    global-variance postfilter) are read back ONCE at the end."""
+    global-variance and modulation-spectrum postfilters) are read back ONCE at the end."""
     ls = ls if ls is not None else _Lockstep(device_index)
-    held, status, map_status, gv_status, waves_diff = [], [], [], [], []
+    if ms_strength:          # (checked and uploaded once: every wave takes the device tensors as they are)
+        ms_stats = _ms_on_device(ms_stats, ms_length, ms_strength, order, ls.dev, on=gmm is not None)
+    held, status, map_status, gv_status, ms_status, waves_diff = [], [], [], [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
                          diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key,
-                         **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}))
+                         **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}),
+                         **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}))
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -926,6 +976,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             map_status.append(wv.f0_map_status)
         if wv.gv_status is not None:
             gv_status.append(wv.gv_status)
+        if wv.ms_status is not None:
+            ms_status.append(wv.ms_status)
         if diff:
             waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
         held.append(wv)
@@ -948,9 +1000,11 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             for wv in waves_diff:
                 wv.finish_diff(ls.ctx)
     ls.sync()
-    words = torch.cat(status + map_status + gv_status).cpu() if status or map_status or gv_status else None
+    every = status + map_status + gv_status + ms_status
+    words = torch.cat(every).cpu() if every else None
     n_dio = sum(v.numel() for v in status)
     n_map = sum(v.numel() for v in map_status)
+    n_gv = sum(v.numel() for v in gv_status)
     if status and bool(words[:n_dio].any()):
         bad = torch.nonzero(words[:n_dio]).flatten().tolist()
         raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
@@ -959,7 +1013,10 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
         check_status(words[n_dio:n_dio + n_map], fs)
     if gv_status:
         from .backend import gv as gvfilter
-        gvfilter.check_status(words[n_dio + n_map:])
+        gvfilter.check_status(words[n_dio + n_map:n_dio + n_map + n_gv])
+    if ms_status:
+        from .backend import ms as msfilter
+        msfilter.check_status(words[n_dio + n_map + n_gv:])
     return ls
 
 
@@ -1336,7 +1393,7 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
 
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
                   shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
-                  gv_stats=None, gv_strength=0.0):
+                  gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1347,7 +1404,10 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     f0_stats / transpose_key (lockstep driver): the waveforms are synthesised on the mapped f0 (ConvertWave); a frame
     out of the map's range raises ValueError after the batch.
     gv_stats / gv_strength (lockstep driver): gv_strength > 0 runs the global-variance postfilter on the converted
-    mel-cepstra of both outputs (ConvertWave); a coefficient it cannot filter raises ValueError after the batch."""
+    mel-cepstra of both outputs (ConvertWave); a coefficient it cannot filter raises ValueError after the batch.
+    ms_stats / ms_length / ms_strength (lockstep driver): ms_strength > 0 runs the modulation-spectrum postfilter on
+    them first (ConvertWave); a bin it cannot filter raises ValueError after the batch, an utterance of more than
+    ms_length frames before it."""
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
@@ -1358,7 +1418,8 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         def keep_view(i, w, p, wd, pd):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
-                        f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength)
+                        f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
+                        ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
@@ -1368,6 +1429,8 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         raise ValueError('convert_batch: f0_stats and transpose_key need the lockstep driver')
     if gv_stats is not None or gv_strength != 0:
         raise ValueError('convert_batch: gv_stats and gv_strength need the lockstep driver')
+    if ms_stats is not None or ms_strength != 0:
+        raise ValueError('convert_batch: ms_stats and ms_strength need the lockstep driver')
     if pool is None:
         pool = StreamPool(device_index, streams)
 
