@@ -394,6 +394,36 @@ typedef struct kwy_pitch_job {
 /* device pointers; enqueued on the context's stream, not synchronised (uses the context's scratch arena) */
 int kwy_pitch_shift_batch_dev(kwy_ctx *ctx, const kwy_pitch_job *jobs, int count, int fs, double rate);
 
+/* ---- formant shift --------------------------------------------------------------------- */
+/* The reference has no counterpart: its dialog transposes the key and keeps the source's formants.  These entries add
+ * the second knob of an analysis / synthesis voice changer, a frequency-axis warp of the spectral envelope, which sets
+ * the apparent vocal-tract length.  For a row-major (rows, K) matrix sp of positive envelope values and a ratio rho
+ * (rho > 1 moves formants up, rho < 1 down), with l = log(sp[t]):
+ *   u_k = k / rho  (one IEEE division, k = 0 .. K-1),   j = floor(u_k),   a = u_k - j
+ *   out[t, k] = sp[t, K-1]                          if j >= K-1  (the band nothing maps to holds the edge value)
+ *             = sp[t, j]                            if a == 0    (bit for bit: k = 0, every bin at rho = 0.5, ...)
+ *             = exp(l[j] + a * (l[j+1] - l[j]))     otherwise    (linear in the log domain, evaluated as written)
+ * j, a and the choice between the three depend on (k, rho) only.  rho must be finite and within [0.5, 2]: KWY_EINVAL
+ * otherwise, and nothing is written.  At rho == 1 out is sp bit for bit, nothing is examined and every status is 0.
+ * A row that holds a value that is not finite or is <= 0 is copied unchanged and counted in its job's status word.
+ * 2 <= K <= KWY_FORMANT_MAX_K, the envelope width of the longest transform CheapTrick accepts.  out may equal sp: a
+ * row is stored only after all of it has been read.  The aperiodicity is deliberately not warped: it describes the
+ * excitation per absolute frequency band.  Every job's result equals the single call's bit for bit: it depends on the
+ * job alone.  The _dev forms allocate nothing and do not synchronise (legal inside a stream capture); the host form
+ * stages through HBM and synchronises. */
+#define KWY_FORMANT_MAX_K 2049
+typedef struct kwy_formant_job {
+  const double *sp;     /* rows x K envelope values */
+  int64_t rows;
+  double *out;          /* rows x K, written (may equal sp) */
+} kwy_formant_job;
+/* status: one int32 per job (or NULL), set to the number of the job's rows that were copied unchanged */
+int kwy_formant_shift(kwy_ctx *ctx, const kwy_formant_job *jobs, int count, int K, double rho, int32_t *status);
+int kwy_formant_shift_dev(kwy_ctx *ctx, const double *sp, int64_t rows, int K, double rho, double *out,
+                          int32_t *status);
+int kwy_formant_shift_batch_dev(kwy_ctx *ctx, const kwy_formant_job *jobs, int count, int K, double rho,
+                                int32_t *status);
+
 /* ---- objective evaluation ------------------------------------------------------------- */
 /* The reference has no counterpart: it compares features only in its tests (tests/feature.py: calc_feature_diffs).
  * These entries add the measures voice-conversion work reports on held-out parallel utterances, taken along an

@@ -28,6 +28,15 @@ def shift_pitch(wavdata, rate):
     return Wavdata(wavdata.fs, pitch.shift_pitch(np.ascontiguousarray(wavdata.data, dtype=np.float64), wavdata.fs, rate))
 
 
+def shift_formants(feature_set, ratio):
+    """a materialised copy of the feature set whose formants are `ratio` (within [0.5, 2.0]) times the input's: the
+    spectral envelope warped along frequency (MutableFeature.shift_formants, backend.formant, kwy_formant.hip); f0 and
+    aperiodicity are the input's"""
+    warped = feature(feature_set)
+    warped.shift_formants(ratio)
+    return warped
+
+
 name = "kwiiyatta_amd"
 
 __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFileDataset',
@@ -37,4 +46,6 @@ __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFil
            # additions to the reference's names: objective evaluation of a trained converter (evaluate_voice.py)
            'evaluate_pair', 'evaluate',
            # ... and the waveform pitch shifter in front of a differential conversion across genders (backend/pitch.py)
-           'shift_pitch']
+           'shift_pitch',
+           # ... and the formant shift beside it: the envelope of a feature set warped along frequency (backend/formant.py)
+           'shift_formants']

@@ -116,6 +116,9 @@ SIGNATURES = {
     'kwy_pitch_frames': (c_i64, [c_i64, c_int, c_dbl]),
     'kwy_pitch_shift': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
     'kwy_pitch_shift_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl]),
+    'kwy_formant_shift': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_vp]),
+    'kwy_formant_shift_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_vp, c_vp]),
+    'kwy_formant_shift_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_vp]),
     'kwy_mcd': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     'kwy_mcd_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
     'kwy_f0_error': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
@@ -285,6 +288,8 @@ MsJob = _job_struct('MsJob', 'kwy_ms_job: one matrix through the modulation-spec
                     [('x', c_vp), ('rows', c_i64), ('base', c_vp), ('out', c_vp)])
 PitchJob = _job_struct('PitchJob', 'kwy_pitch_job: one waveform through the pitch shifter',
                        [('x', c_vp), ('n', c_i64), ('y', c_vp), ('pos', c_vp)])
+FormantJob = _job_struct('FormantJob', 'kwy_formant_job: one envelope matrix through the formant shift',
+                         [('sp', c_vp), ('rows', c_i64), ('out', c_vp)])
 McdJob = _job_struct('McdJob', 'kwy_mcd_job: one utterance of a mel-cepstral distortion call',
                      [('a', c_vp), ('a_rows', c_i64), ('a_stride', c_i64), ('b', c_vp), ('b_rows', c_i64), ('b_stride', c_i64),
                       ('idx_a', c_vp), ('idx_b', c_vp), ('off_a', c_i64), ('off_b', c_i64), ('rows', c_i64), ('n_dev', c_vp),

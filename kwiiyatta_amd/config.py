@@ -108,6 +108,28 @@ TRANSPOSE_KEY_OPTION = ('--transpose-key', dict(type=transpose_key, default=0.0,
                                                      '(f0 * 2 ** (SEMITONES / 12); [-99.99, 99.99])'))
 
 
+FORMANT_SHIFT_RANGE = (-12.0, 12.0)
+
+
+def formant_shift(text):
+    """--formant-shift: semitones within [-12, 12], the range of the envelope warp (a ratio within [0.5, 2])"""
+    try:
+        semitones = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid semitone value: {text!r}') from None
+    lo, hi = FORMANT_SHIFT_RANGE
+    if not lo <= semitones <= hi:           # (false for nan)
+        raise argparse.ArgumentTypeError(f'{text} semitones is outside [{lo:g}, {hi:g}]')
+    return semitones
+
+
+FORMANT_SHIFT_OPTION = ('--formant-shift', dict(type=formant_shift, default=0.0, metavar='SEMITONES',
+                                                help='Move the formants of the synthesised voice by this many semitones '
+                                                     '(the spectral envelope warped along frequency by 2 ** (SEMITONES '
+                                                     '/ 12): above 0 a shorter vocal tract; [-12, 12]); the pitch '
+                                                     'stays'))
+
+
 def gv_strength(text):
     """--gv: the strength of the global-variance postfilter, within [0, 1]"""
     try:
@@ -151,6 +173,14 @@ class Config:
 
     def add_transpose_key_argument(self):
         self._declare((TRANSPOSE_KEY_OPTION,))
+
+    def add_formant_shift_argument(self):
+        self._declare((FORMANT_SHIFT_OPTION,))
+
+    @property
+    def formant_ratio(self):
+        """the warp ratio --formant-shift asks for (1 when the option is not declared)"""
+        return 2.0 ** (getattr(self, 'formant_shift', 0.0) / 12)
 
     def add_gv_argument(self):
         self._declare((GV_OPTION,))

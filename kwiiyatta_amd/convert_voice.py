@@ -27,7 +27,11 @@ or STRENGTH of the way there, keeping the phase.  No utterance may be longer tha
 `--align-iterations N` trains with iterative re-alignment: after the first fit every training pair is aligned again, N
 times over, with the source mel-cepstrum converted by the converter fitted so far in its DTW features (the reference
 aligns once, on the two speakers' own coefficients), the joint matrix is rebuilt along the new paths and the mixture
-refitted.  The count is kept in the converter model; 0 (the default) is the reference's training."""
+refitted.  The count is kept in the converter model; 0 (the default) is the reference's training.
+`--formant-shift SEMITONES` warps the CONVERTED spectral envelope along frequency by 2 ** (SEMITONES / 12) before the
+synthesis (Feature.shift_formants, `convert(..., formant_shift=)`; with `--batch` on the device, one launch over a wave's
+frames).  Like `--transpose-key` it reaches the .synth.wav output only: the .diff.wav output is the input waveform
+filtered by the converter's difference, which this option leaves alone."""
 import pathlib
 
 import numpy as np
@@ -35,13 +39,16 @@ import numpy as np
 OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
-def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0):
+def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
+            formant_shift=0.0):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
     global-variance postfilter of that strength (converter.convert(gv=...), either output); ms > 0: through the
     modulation-spectrum postfilter first (converter.convert(ms=...)).  A converter trained on
-    pitch-shifted sources (converter.source_f0_rate != 1) gets the file's waveform shifted the same way."""
+    pitch-shifted sources (converter.source_f0_rate != 1) gets the file's waveform shifted the same way.
+    formant_shift != 0 (semitones): the converted envelope of the synthesised output warped along frequency by
+    2 ** (formant_shift / 12) (Feature.shift_formants); the differential output ignores it."""
     import kwiiyatta_amd as k
     source = analyze_source(conf, converter, src_path)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
@@ -55,6 +62,8 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
         stats = converter.f0_stats if convert_f0 else None          # (converter.convert_f0 without the statistics)
         rendered.f0 = f0map.map_f0(np.ascontiguousarray(source.f0, dtype=np.float64), rendered.fs, stats=stats,
                                    key=transpose_key)
+    if formant_shift != 0:
+        rendered.shift_formants(2.0 ** (formant_shift / 12))
     return rendered.synthesize()
 
 
@@ -96,7 +105,8 @@ class _Pcm16:
         wavfile.write(wav, self.fs, self.pcm)
 
 
-def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0):
+def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
+                        formant_shift=0.0):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -107,7 +117,9 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     (corpus.convert_batch(pcm=True, diff=...)); the host reads the wav files and writes 2 bytes per sample.
     convert_f0 / transpose_key: the .synth.wav outputs on the mapped f0 (as `convert` does), mapped on the device.
     gv > 0 / ms > 0: both outputs from the postfiltered mel-cepstra (as `convert` does), filtered on the device; a file
-    longer than the converter's ms_length goes through `convert`, which names it."""
+    longer than the converter's ms_length goes through `convert`, which names it.
+    formant_shift != 0: the .synth.wav outputs from the warped converted envelopes (as `convert` does), warped on the
+    device (corpus.convert_batch(formant_ratio=...))."""
     import kwiiyatta_amd as k
     from . import corpus
     from ._lib import lib
@@ -123,7 +135,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
         if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or too_long or \
                 (period is not None and a.frame_period != period):
             out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
-                                       transpose_key=transpose_key, gv=gv, ms=ms)
+                                       transpose_key=transpose_key, gv=gv, ms=ms, formant_shift=formant_shift)
         else:
             batch.append((path, a))
     if batch:
@@ -137,7 +149,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                                    f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key,
                                    **(dict(gv_stats=converter.gv_stats, gv_strength=gv) if gv > 0 else {}),
                                    **(dict(ms_stats=converter.ms_stats, ms_length=converter.ms_length, ms_strength=ms)
-                                      if ms > 0 else {}))
+                                      if ms > 0 else {}),
+                                   **(dict(formant_ratio=2.0 ** (formant_shift / 12)) if formant_shift != 0 else {}))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -164,13 +177,14 @@ def main():
                       help='Map the f0 of the .synth.wav outputs to the target speaker (log-f0 mean and deviation of '
                            'the training data, kept in the converter model)')
     conf.add_transpose_key_argument()
+    conf.add_formant_shift_argument()
     conf.add_gv_argument()
     conf.add_ms_argument()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
                                      ms_stats=conf.ms > 0)
-    pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key)
+    pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, formant_shift=conf.formant_shift)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
                                   diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, **pitch) if conf.batch else {}
     for name in conf.files:

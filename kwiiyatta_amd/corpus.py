@@ -761,14 +761,20 @@ class ConvertWave:
     length ms_length): the converted mel-cepstra through the modulation-spectrum postfilter between the conversion and
     the global-variance filter (kwy_ms_postfilter_batch_dev on c1..cN, in place; the differential conversion takes the
     filter's change of the plain one first, as with gv).  `ms_status` holds a word per utterance (non-zero: bins left
-    unfiltered, backend.ms.postfilter); an utterance of more than ms_length frames is a ValueError."""
+    unfiltered, backend.ms.postfilter); an utterance of more than ms_length frames is a ValueError.
+    formant_ratio != 1 (within [0.5, 2]): the envelopes the rendering reads -- the converted ones, without a GMM the
+    analysed ones -- warped along frequency right before it, all rows of the wave in ONE in-place call
+    (kwy_formant_shift_dev, backend.formant); `formant_status` holds one word for the wave (non-zero: rows left as they
+    are).  The differential output is not touched.  At 1 no kernel is launched and no buffer added."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
                  f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                 ms_strength=0.0):
+                 ms_strength=0.0, formant_ratio=1.0):
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
         self.diff = bool(diff) and gmm is not None
         self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
+        from .backend import formant
+        self.formant_ratio, self.formant_status = formant.check_ratio(formant_ratio), None
         self.wav_in = len(utterances) > 0 and not isinstance(utterances[0], (tuple, list))
         dev = ls.dev
         self.fft = lib.kwy_cheaptrick_fft_size(self.fs, 71.0)
@@ -873,6 +879,8 @@ class ConvertWave:
                     self.j_ms_diff = _lib.job_array(_lib.MsJob, [(conv[i], self.T[i], self.mc_diff_rows[i],
                                                                   self.mc_diff_rows[i]) for i in range(n)])
             self.j_render = _lib.synth_job_array([(self.plan[i], spec[i], ap[i], self.wave[i]) for i in range(n)])
+            if self.formant_ratio != 1:
+                self.formant_status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.frames = int(sum(self.T))
 
     def run(self):
@@ -921,6 +929,10 @@ class ConvertWave:
                     chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv, n, cols, 1, _p(self.gv), self.gv_strength,
                                                         _p(self.gv_status)))
                 chk(lib.kwy_mc2sp_dev(h, _p(self.mc_conv), self.rows, order, self.alpha, fft, _p(self.sp_conv)))
+            if self.formant_status is not None:     # the rows the rendering reads, warped in place
+                rendered = self.sp_all if self.gmm is None else self.sp_conv
+                chk(lib.kwy_formant_shift_dev(h, _p(rendered), self.rows, K, self.formant_ratio, _p(rendered),
+                                              _p(self.formant_status)))
             ls.main.wait_stream(ls.side)
             chk(lib.kwy_synth_render_batch_dev(h, self.j_render, n, fft, self.frame_period, fs, float(fs)))
             if self.pcm is not None:
@@ -951,20 +963,22 @@ class ConvertWave:
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
                     f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                    ms_strength=0.0):
+                    ms_strength=0.0, formant_ratio=1.0):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
-    global-variance and modulation-spectrum postfilters) are read back ONCE at the end."""
+    global-variance and modulation-spectrum postfilters and of the formant shift, one per wave) are read back ONCE at the
+    end."""
     ls = ls if ls is not None else _Lockstep(device_index)
     if ms_strength:          # (checked and uploaded once: every wave takes the device tensors as they are)
         ms_stats = _ms_on_device(ms_stats, ms_length, ms_strength, order, ls.dev, on=gmm is not None)
-    held, status, map_status, gv_status, ms_status, waves_diff = [], [], [], [], [], []
+    held, status, map_status, gv_status, ms_status, formant_status, waves_diff = [], [], [], [], [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
                          diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key,
                          **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}),
-                         **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}))
+                         **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}),
+                         **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}))
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -978,6 +992,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             gv_status.append(wv.gv_status)
         if wv.ms_status is not None:
             ms_status.append(wv.ms_status)
+        if wv.formant_status is not None:
+            formant_status.append(wv.formant_status)
         if diff:
             waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
         held.append(wv)
@@ -1000,11 +1016,12 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             for wv in waves_diff:
                 wv.finish_diff(ls.ctx)
     ls.sync()
-    every = status + map_status + gv_status + ms_status
+    every = status + map_status + gv_status + ms_status + formant_status
     words = torch.cat(every).cpu() if every else None
     n_dio = sum(v.numel() for v in status)
     n_map = sum(v.numel() for v in map_status)
     n_gv = sum(v.numel() for v in gv_status)
+    n_ms = sum(v.numel() for v in ms_status)
     if status and bool(words[:n_dio].any()):
         bad = torch.nonzero(words[:n_dio]).flatten().tolist()
         raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
@@ -1016,7 +1033,10 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
         gvfilter.check_status(words[n_dio + n_map:n_dio + n_map + n_gv])
     if ms_status:
         from .backend import ms as msfilter
-        msfilter.check_status(words[n_dio + n_map + n_gv:])
+        msfilter.check_status(words[n_dio + n_map + n_gv:n_dio + n_map + n_gv + n_ms])
+    if formant_status:
+        from .backend import formant
+        formant.check_status(words[n_dio + n_map + n_gv + n_ms:], what='wave(s)')
     return ls
 
 
@@ -1391,9 +1411,19 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
         s_.synchronize()
 
 
+def _formant_ratio(formant_ratio, driver, pool, who):
+    """the checked ratio of a batch driver's formant shift, before anything is put on the device: ValueError outside
+    [0.5, 2], and for any ratio but 1 on the stream driver"""
+    from .backend import formant
+    ratio = formant.check_ratio(formant_ratio)
+    if ratio != 1 and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
+        raise ValueError(f'{who}: formant_ratio needs the lockstep driver')
+    return ratio
+
+
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
                   shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
-                  gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0):
+                  gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1407,7 +1437,11 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     mel-cepstra of both outputs (ConvertWave); a coefficient it cannot filter raises ValueError after the batch.
     ms_stats / ms_length / ms_strength (lockstep driver): ms_strength > 0 runs the modulation-spectrum postfilter on
     them first (ConvertWave); a bin it cannot filter raises ValueError after the batch, an utterance of more than
-    ms_length frames before it."""
+    ms_length frames before it.
+    formant_ratio (lockstep driver): a ratio other than 1 warps the converted envelopes along frequency before the
+    synthesis (ConvertWave); the differential outputs are not touched; a row it cannot warp raises ValueError after the
+    batch, a ratio outside [0.5, 2] before anything is put on the device."""
+    formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'convert_batch')
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
@@ -1419,7 +1453,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
                         f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
-                        ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength)
+                        ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
@@ -1442,11 +1476,14 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
 
 
 def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams=16, pool=None, shapes_per_stream=4,
-                       out=None, driver=None, lockstep=None):
+                       out=None, driver=None, lockstep=None, formant_ratio=1.0):
     """BASELINE config 4 on one rank: analyse + resynthesise every utterance ((x, f0, t) triples: numpy arrays or
     device tensors), more utterances than the driver has in flight.  Returns the list of waveforms (device tensors;
     written into `out[i]` instead when a list of preallocated tensors is given) and the number of frames analysed.
-    driver='lockstep' (default): waves of 16 through the batched entries; 'streams': a fixed pool of streams."""
+    driver='lockstep' (default): waves of 16 through the batched entries; 'streams': a fixed pool of streams.
+    formant_ratio (lockstep driver): a ratio other than 1 warps the analysed envelopes along frequency before the
+    synthesis (ConvertWave); ValueError for a row it cannot warp after the batch, for a ratio outside [0.5, 2] before."""
+    formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'resynthesize_batch')
     res = [None] * len(utterances)
     frames = 0
     for u in utterances:
@@ -1459,7 +1496,8 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
                 res[i] = out[i]
             else:
                 res[i] = w
-        _lockstep_batch(utterances, fs, device_index, None, 24, frame_period, lockstep, keep_view)
+        _lockstep_batch(utterances, fs, device_index, None, 24, frame_period, lockstep, keep_view,
+                        formant_ratio=formant_ratio)
         return res, frames
     from .pipeline import UtterancePipeline
     if pool is None:

@@ -4,7 +4,14 @@ own waveform is filtered towards the source's spectrum instead of being re-synth
 reference's kwiiyatta/resynthesize_voice.py; its Qt dialog (started when no source file is given) is not part of
 this build, but its key transposition is: --transpose-key SEMITONES multiplies the f0 by 2 ** (SEMITONES / 12)
 after the carrier and --mcep steps (kwiiyatta/view/qt/kwiieiya.py:152-155).  --diffvc returns before that step in
-the dialog, so the two together are refused."""
+the dialog, so the two together are refused.
+An addition to the reference's options: --formant-shift SEMITONES warps the spectral envelope along frequency by
+2 ** (SEMITONES / 12) (Feature.shift_formants: above 0 the formants move up, a shorter vocal tract; the pitch and the
+aperiodicity stay), after the carrier and --mcep steps, beside the transposition and before --result-fs.  With
+--diffvc the shift composes in two ways.  --carrier --diffvc: the source's envelope on the carrier's frames is warped
+BEFORE the difference to the carrier's mel-cepstrum is taken, so the carrier's waveform is filtered towards the shifted
+spectrum.  --diffvc without a carrier (ignored at shift 0, as it always was): the source's OWN waveform goes through the
+MLSA filter of mel-cepstrum(warped envelope) - mel-cepstrum(envelope) -- a formant shift with no resynthesis at all."""
 import copy
 import pathlib
 
@@ -12,12 +19,22 @@ import pathlib
 def render(conf, source):
     """the result waveform for the parsed options"""
     import kwiiyatta_amd as k
+    shift = getattr(conf, 'formant_shift', 0.0)
+    ratio = 2.0 ** (shift / 12)
     if conf.carrier is None:
         picture = k.feature(source)
+        if conf.diffvc and shift != 0:                   # the source's own waveform filtered by the warp's difference
+            plain = picture.mel_cepstrum.data
+            picture.shift_formants(ratio)
+            difference = copy.copy(picture.mel_cepstrum)
+            difference.data = difference.data - plain
+            return k.apply_mlsa_filter(source.wavdata, difference)
     else:
         carrier = conf.create_analyzer(conf.carrier, Analyzer=k.analyze_wav)
         picture = k.align(source, carrier)               # the source's features on the carrier's frames
         if conf.diffvc:
+            if shift != 0:
+                picture.shift_formants(ratio)
             difference = copy.copy(picture.mel_cepstrum)
             difference.data -= carrier.mel_cepstrum.data
             return k.apply_mlsa_filter(carrier.wavdata, difference)
@@ -25,6 +42,8 @@ def render(conf, source):
     if conf.mcep:
         picture.extract_mel_cepstrum()
         picture.spectrum_envelope = None                 # from here on the mel-cepstrum is the envelope
+    if shift != 0:
+        picture.shift_formants(ratio)
     if conf.transpose_key != 0:
         import numpy as np
         from .backend import f0 as f0map
@@ -47,6 +66,7 @@ def main():
     conf.add_argument('--diffvc', action='store_true', help='Use difference MelCepstrum synthesis')
     conf.add_argument('--result-fs', type=int, help='Result waveform sampling rate')
     conf.add_transpose_key_argument()
+    conf.add_formant_shift_argument()
     conf.parse_args()
     if conf.source is None:
         conf.parser.error('a source wav file is required (the Qt dialog of the reference is not part of this build)')

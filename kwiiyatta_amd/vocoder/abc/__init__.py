@@ -268,6 +268,23 @@ class MutableFeature(Feature):
             self._mel_cepstrum.resample(new_fs, Synthesizer=self.Synthesizer)
         self._mel_cepstrum._fs = new_fs
 
+    def shift_formants(self, ratio):
+        """Warp the frequency axis of the spectral envelope by `ratio` (within [0.5, 2]; > 1 moves the formants up:
+        a shorter vocal tract), in place: backend.formant.shift_formants, linear in the log domain, the band nothing
+        maps to holding the edge value.  A feature that holds only a mel-cepstrum gets its envelope from it first; the
+        mel-cepstrum slot is cleared, so it is derived again from the warped envelope.  f0 and aperiodicity stay: the
+        aperiodicity describes the excitation per absolute frequency band.  At ratio 1 nothing changes."""
+        from ...backend import formant
+        rho = formant.check_ratio(ratio)
+        if rho == 1.0:
+            return
+        envelope = self.spectrum_envelope
+        if envelope is None:
+            raise ValueError('shift_formants: the feature has neither a spectral envelope nor a mel-cepstrum')
+        warped = formant.shift_formants(np.ascontiguousarray(envelope, dtype=np.float64), rho)
+        self._mel_cepstrum.data = None
+        self._put('spectrum_envelope', warped)
+
     def ascontiguousarray(self):
         for slot in ARRAY_SLOTS:
             self._put(slot, np.ascontiguousarray(getattr(self, slot)))
