@@ -616,6 +616,43 @@ typedef struct kwy_convert_job {
 } kwy_convert_job;
 int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *jobs, int count, int d, int M,
                                const double *model);
+/* EM trajectory conversion over soft mixture posteriors (an addition: nnmnkwii, like the entries above, picks one arg-max
+ * mixture per frame, the "sub-optimal mixture sequence" of Toda, Black and Tokuda 2007; this is that paper's method).
+ * With the prepared model's mux_m, muy_m, A_m, v_m (the diagonal conditional variance, `diff` folded in), the source's
+ * delta features X (T x D, D = 3 d) and logp[t,m] = log w_m + log N(X_t; mux_m, Sxx_m):
+ *     E[m,t]   = muy_m + A_m (X_t - mux_m)
+ *     g[t,m]   = softmax over m of logp[t,:]
+ *     for k = 0 .. em_iterations:
+ *         pbar[t,c] = sum_m g[t,m] / v_m[c]
+ *         r[t,c]    = sum_m g[t,m] E[m,t][c] / v_m[c]                               (m ascending)
+ *         y_k       = per static dimension the solution of W' diag(pbar) W y = W' r   (the MLPG solver above)
+ *         Y_k       = [y_k | 0.5 (y_k[t+1] - y_k[t-1]) | y_k[t+1] - 2 y_k[t] + y_k[t-1]], zeros outside the utterance
+ *         l[t,m]    = logp[t,m] - 0.5 sum_c (log(2 pi v_m[c]) + (Y_k[t,c] - E[m,t][c])^2 / v_m[c])
+ *         L_k       = sum_t logsumexp_m l[t,:]
+ *         g[t,m]    = softmax over m of l[t,:]
+ * The result is y_em_iterations; loglik (em_iterations + 1 doubles, or NULL) receives L_0 .. L_em_iterations.  The
+ * posteriors are taken under the diagonal conditional model that the solve maximises, so this is exact EM:
+ * L_k never decreases.  em_iterations is a fixed count in [0, KWY_MLPG_EM_MAX]: no convergence test, and the _dev forms
+ * do not synchronise (legal inside a stream capture).  0 is the single solve under the source-only posteriors; the
+ * arg-max entries above are this scheme with g replaced by a one-hot and em_iterations = 0.  Without loglik the closing
+ * E-step that only yields the last L is skipped; y does not depend on whether loglik is given.  An em_iterations out of
+ * range, or an argument the entries above refuse, returns KWY_EINVAL with nothing written; count == 0 is KWY_OK.
+ * Every job of a batch equals the single call's bits.  kwy_gmm_mlpg_em: host pointers, as kwy_gmm_mlpg;
+ * kwy_convert_mcep_em_dev: device pointers (loglik too), column 0 kept, as kwy_convert_mcep_dev. */
+#define KWY_MLPG_EM_MAX 16
+int kwy_gmm_mlpg_em(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
+                    const double *means, const double *covs, int diff, int em_iterations, double *y,
+                    double *loglik);
+int kwy_convert_mcep_em_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
+                            int em_iterations, double *mc_out, double *loglik);
+typedef struct kwy_convert_em_job {
+  const double *mc;      /* T x (d + 1) */
+  int64_t T;
+  double *mc_out;        /* T x (d + 1) */
+  double *loglik;        /* em_iterations + 1 doubles on the device, or NULL */
+} kwy_convert_em_job;
+int kwy_convert_mcep_em_batch_dev(kwy_ctx *ctx, const kwy_convert_em_job *jobs, int count, int d, int M,
+                                  const double *model, int em_iterations);
 /* Re-alignment of the training set (an addition: the reference aligns once): the same batched conversion, with the
  * converted c1..cd of every job stored straight into columns 2.. of its DTW feature rows (kwy_align_features_dev's
  * layout, rows d + 2 doubles apart) -- columns 0 and 1, the source's own power and voicing terms, are not touched, and no

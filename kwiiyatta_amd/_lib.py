@@ -204,6 +204,9 @@ SIGNATURES = {
     'kwy_convert_mcep_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     'kwy_convert_mcep_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     'kwy_realign_features_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp]),
+    'kwy_gmm_mlpg_em': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'kwy_convert_mcep_em_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
+    'kwy_convert_mcep_em_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int]),
     'kwy_moments_accumulate_dev': (c_int, [c_vp, c_vp, c_int, c_vp]),
 }
 
@@ -265,6 +268,8 @@ GatherJob = _job_struct('GatherJob', 'kwy_gather_job: one row gather',
                         [('src', c_vp), ('src_rows', c_i64), ('idx', c_vp), ('n', c_i64), ('dst', c_vp)])
 ConvertJob = _job_struct('ConvertJob', 'kwy_convert_job: one utterance of a batched conversion',
                          [('mc', c_vp), ('T', c_i64), ('mc_out', c_vp)])
+ConvertEmJob = _job_struct('ConvertEmJob', 'kwy_convert_em_job: one utterance of a batched EM conversion',
+                           [('mc', c_vp), ('T', c_i64), ('mc_out', c_vp), ('loglik', c_vp)])
 RealignJob = _job_struct('RealignJob', 'kwy_realign_job: one source side of a re-alignment pass',
                          [('mc', c_vp), ('T', c_i64), ('feat', c_vp)])
 TrimJob = _job_struct('TrimJob', 'kwy_trim_job', [('sp', c_vp), ('T', c_i64), ('n_out', c_vp)])

@@ -7,6 +7,8 @@ import numpy as np
 from .. import _lib
 from .._lib import lib, ptr
 
+EM_MAX = 16      # KWY_MLPG_EM_MAX (include/kwy.h)
+
 DELTA_WINDOWS = [
     (0, 0, np.array([1.0])),
     (1, 1, np.array([-0.5, 0.0, 0.5])),
@@ -42,9 +44,14 @@ def delta_features(x, windows):
 class MLPG:
     """Maximum-likelihood parameter generation from a joint GMM
     (sklearn.mixture.GaussianMixture-like object with weights_, means_,
-    covariances_ and covariance_type == 'full')."""
+    covariances_ and covariance_type == 'full').
 
-    def __init__(self, gmm, windows=None, swap=False, diff=False, ctx=None):
+    em=None: one arg-max mixture per frame and a single trajectory solve, what nnmnkwii does.  em=N, an integer within
+    [0, EM_MAX] (an addition): every mixture weighs in with its posterior, and the posteriors are re-estimated N times
+    from the source frame and the trajectory solved last (kwy_gmm_mlpg_em, include/kwy.h); `loglik_` then holds
+    L_0 .. L_N of the last `transform`, which never decrease."""
+
+    def __init__(self, gmm, windows=None, swap=False, diff=False, ctx=None, em=None):
         if windows is None:
             windows = DELTA_WINDOWS
         self.framewise = _is_static_window(windows)     # DELTA_WINDOWS[0:1]: conversion without trajectory smoothing
@@ -53,6 +60,17 @@ class MLPG:
                                       'on the GPU')
         if swap:
             raise NotImplementedError('swap=True is not used by the reference and not implemented')
+        if em is not None:
+            if isinstance(em, bool) or not isinstance(em, (int, np.integer)):
+                raise ValueError(f'em must be None or an integer within [0, {EM_MAX}], not {em!r}')
+            if not 0 <= em <= EM_MAX:
+                raise ValueError(f'em = {em} is outside [0, {EM_MAX}]')
+            if self.framewise:
+                raise ValueError('em needs the trajectory solve: it does not go with the static window alone '
+                                 '(mlpg=False)')
+            em = int(em)
+        self.em = em
+        self.loglik_ = None
         assert gmm.covariance_type == 'full'
         self.weights = np.ascontiguousarray(gmm.weights_, dtype=np.float64)
         self.means = np.ascontiguousarray(gmm.means_, dtype=np.float64)
@@ -87,6 +105,13 @@ class MLPG:
         x = np.ascontiguousarray(src[:, :d])
         ctx = self.ctx or _lib.default_context()
         y = np.empty((x.shape[0], d))
+        if self.em is not None:
+            loglik = np.empty(self.em + 1)
+            _lib.check(ctx, lib.kwy_gmm_mlpg_em(ctx.handle, ptr(x), x.shape[0], d, self.num_mixtures, ptr(self.weights),
+                                                ptr(self.means), ptr(self.covs), int(self.diff), self.em, ptr(y),
+                                                ptr(loglik)))
+            self.loglik_ = loglik.tolist()
+            return y
         _lib.check(ctx, lib.kwy_gmm_mlpg(ctx.handle, ptr(x), x.shape[0], d, self.num_mixtures,
                                          ptr(self.weights), ptr(self.means), ptr(self.covs),
                                          int(self.diff), ptr(y)))

@@ -154,6 +154,30 @@ MS_OPTION = ('--ms', dict(type=gv_strength, nargs='?', const=1.0, default=0.0, m
                                '[0, 1], 1 when omitted'))
 
 
+MLPG_EM_RANGE = (0, 16)      # KWY_MLPG_EM_MAX (include/kwy.h)
+
+
+def mlpg_em(text):
+    """--mlpg-em: the re-estimations of the mixture posteriors, an integer within [0, 16]"""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid iteration count: {text!r}') from None
+    lo, hi = MLPG_EM_RANGE
+    if not lo <= n <= hi:
+        raise argparse.ArgumentTypeError(f'{text} is outside [{lo}, {hi}]')
+    return n
+
+
+MLPG_EM_OPTION = ('--mlpg-em', dict(type=mlpg_em, default=None, metavar='N',
+                                    help='EM trajectory conversion over soft mixture posteriors: weigh every mixture '
+                                         'of a frame by its posterior instead of picking the likeliest one, and '
+                                         're-estimate the posteriors N times from the source frame and the trajectory '
+                                         'solved last (Toda et al. 2007); N within [0, 16], 0: one solve under the '
+                                         'source-only posteriors (default: one arg-max mixture per frame, as the '
+                                         'reference does)'))
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -187,6 +211,9 @@ class Config:
 
     def add_ms_argument(self):
         self._declare((MS_OPTION,))
+
+    def add_mlpg_em_argument(self):
+        self._declare((MLPG_EM_OPTION,))
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)

@@ -31,7 +31,12 @@ refitted.  The count is kept in the converter model; 0 (the default) is the refe
 `--formant-shift SEMITONES` warps the CONVERTED spectral envelope along frequency by 2 ** (SEMITONES / 12) before the
 synthesis (Feature.shift_formants, `convert(..., formant_shift=)`; with `--batch` on the device, one launch over a wave's
 frames).  Like `--transpose-key` it reaches the .synth.wav output only: the .diff.wav output is the input waveform
-filtered by the converter's difference, which this option leaves alone."""
+filtered by the converter's difference, which this option leaves alone.
+`--mlpg-em N` converts the spectrum, for both outputs, by EM over soft mixture posteriors (Toda et al. 2007) instead
+of with one arg-max mixture per frame: every mixture of a frame weighs in with its posterior, and the posteriors are
+re-estimated N times from the source frame and the trajectory solved last (`convert(..., em=N)`; with `--batch`
+kwy_convert_mcep_em_batch_dev).  The statistics of `--ms` and the re-alignment of `--align-iterations` keep the arg-max
+conversion."""
 import pathlib
 
 import numpy as np
@@ -40,7 +45,7 @@ OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
 def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-            formant_shift=0.0):
+            formant_shift=0.0, mlpg_em=None):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
@@ -48,11 +53,12 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
     modulation-spectrum postfilter first (converter.convert(ms=...)).  A converter trained on
     pitch-shifted sources (converter.source_f0_rate != 1) gets the file's waveform shifted the same way.
     formant_shift != 0 (semitones): the converted envelope of the synthesised output warped along frequency by
-    2 ** (formant_shift / 12) (Feature.shift_formants); the differential output ignores it."""
+    2 ** (formant_shift / 12) (Feature.shift_formants); the differential output ignores it.
+    mlpg_em=N: the EM trajectory conversion with N re-estimations (converter.convert(em=N), either output)."""
     import kwiiyatta_amd as k
     source = analyze_source(conf, converter, src_path)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
-                                  **(dict(ms=ms) if ms > 0 else {}))
+                                  **(dict(ms=ms) if ms > 0 else {}), **({} if mlpg_em is None else dict(em=mlpg_em)))
     if diffvc:
         return k.apply_mlsa_filter(source, converted)
     rendered = k.feature(source)
@@ -106,7 +112,7 @@ class _Pcm16:
 
 
 def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-                        formant_shift=0.0):
+                        formant_shift=0.0, mlpg_em=None):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -119,7 +125,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     gv > 0 / ms > 0: both outputs from the postfiltered mel-cepstra (as `convert` does), filtered on the device; a file
     longer than the converter's ms_length goes through `convert`, which names it.
     formant_shift != 0: the .synth.wav outputs from the warped converted envelopes (as `convert` does), warped on the
-    device (corpus.convert_batch(formant_ratio=...))."""
+    device (corpus.convert_batch(formant_ratio=...)).
+    mlpg_em=N: both outputs from EM trajectory conversions (as `convert` does; corpus.convert_batch(mlpg_em=N))."""
     import kwiiyatta_amd as k
     from . import corpus
     from ._lib import lib
@@ -135,7 +142,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
         if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or too_long or \
                 (period is not None and a.frame_period != period):
             out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
-                                       transpose_key=transpose_key, gv=gv, ms=ms, formant_shift=formant_shift)
+                                       transpose_key=transpose_key, gv=gv, ms=ms, formant_shift=formant_shift,
+                                       mlpg_em=mlpg_em)
         else:
             batch.append((path, a))
     if batch:
@@ -150,7 +158,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                                    **(dict(gv_stats=converter.gv_stats, gv_strength=gv) if gv > 0 else {}),
                                    **(dict(ms_stats=converter.ms_stats, ms_length=converter.ms_length, ms_strength=ms)
                                       if ms > 0 else {}),
-                                   **(dict(formant_ratio=2.0 ** (formant_shift / 12)) if formant_shift != 0 else {}))
+                                   **(dict(formant_ratio=2.0 ** (formant_shift / 12)) if formant_shift != 0 else {}),
+                                   **({} if mlpg_em is None else dict(mlpg_em=mlpg_em)))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -180,13 +189,15 @@ def main():
     conf.add_formant_shift_argument()
     conf.add_gv_argument()
     conf.add_ms_argument()
+    conf.add_mlpg_em_argument()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
                                      ms_stats=conf.ms > 0)
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, formant_shift=conf.formant_shift)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
-                                  diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, **pitch) if conf.batch else {}
+                                  diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
+                                  **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -199,7 +210,7 @@ def main():
             if (wav_path, differential) in batched:
                 batched[wav_path, differential].save(out)
             else:
-                convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms,
+                convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
                         **({} if differential else pitch)).save(out)
 
 

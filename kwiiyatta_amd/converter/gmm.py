@@ -20,7 +20,10 @@ class GMMFeatureConverter(abc.FeatureConverter):
     def _train(self, dataarray, **kwargs):
         self.gmm.fit(dataarray, **kwargs)
 
-    def convert(self, feature, mlpg=True, diff=False):
+    def convert(self, feature, mlpg=True, diff=False, em=None):
         # mlpg=False: the static window alone -- every frame converted on its own (posterior-weighted conditional mean)
+        # em=N: EM trajectory conversion over soft mixture posteriors, N re-estimations (backend.mlpg.MLPG); the keyword
+        # is handed on only when set
         windows = delta.DELTA_WINDOWS if mlpg else delta.DELTA_WINDOWS[0:1]
-        return MLPG(self.gmm, windows=windows, diff=diff).transform(feature)
+        options = {} if em is None else dict(em=em)
+        return MLPG(self.gmm, windows=windows, diff=diff, **options).transform(feature)

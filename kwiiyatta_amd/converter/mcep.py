@@ -312,7 +312,12 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         ms > 0 (a strength within [0, 1]; needs `ms_stats`): the converted c1..cN through the modulation-spectrum
         postfilter, every modulation-frequency bin of each trajectory moved from the statistics of converted speech
         towards the target's; it composes with diff=True as gv does.  With both, the modulation-spectrum filter comes
-        first and the global-variance filter takes its moments from that filter's output."""
+        first and the global-variance filter takes its moments from that filter's output.
+        em=N (an integer within [0, 16], through **kwargs down to the mixture stage): EM trajectory conversion over
+        soft mixture posteriors instead of one arg-max mixture per frame, N re-estimations of the posteriors
+        (backend.mlpg.MLPG).  It composes with diff, gv and ms as the arg-max conversion does -- with diff=True the
+        non-differential conversion the filters look at is an EM conversion too.  `ms_stats` are learnt from ARG-MAX
+        conversions of the training set (as re-alignment uses them), whatever `em` is given here."""
         if mel_cepstrum.order != self.order:
             raise ValueError(f'order is expected to {self.order!s} but {mel_cepstrum.order!s}')
         if not 0.0 <= gv <= 1.0:

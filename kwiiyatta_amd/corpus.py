@@ -478,8 +478,9 @@ class EvalWave(TrainWave):
     caller's tensors.  `frame_period` is accepted and ignored, as in TrainWave."""
 
     def measure(self, pads, gmm, model, tot, first, frames='speech', gv=None, gv_strength=0.0, f0_stats=None,
-                transpose_key=0.0, per_frame=False):
-        """tot: the _EvalTotals of the corpus; gv / f0_stats: device tensors (order + 1 values / 4 values) or None"""
+                transpose_key=0.0, per_frame=False, mlpg_em=None):
+        """tot: the _EvalTotals of the corpus; gv / f0_stats: device tensors (order + 1 values / 4 values) or None;
+        mlpg_em: None, or the re-estimations of the EM trajectory conversion (kwy_convert_mcep_em_batch_dev)"""
         from .backend import distortion as dist
         a = self.align(pads)
         Tp = a.inputs.Tp
@@ -500,8 +501,8 @@ class EvalWave(TrainWave):
             own = Ragged(keep[0::2])                    # the sources' own time axes, end to end
             self.mc_conv = torch.empty((own.total, cols), **f64)
             conv = own.views(self.mc_conv)
-            chk(lib.kwy_convert_mcep_batch_dev(h, J(_lib.ConvertJob, [(src_mc[k], keep[2 * k], conv[k]) for k in range(n)]),
-                                               n, order, gmm.M, _p(model)))
+            chk(_convert_mcep_batch(h, _convert_jobs([(src_mc[k], keep[2 * k], conv[k]) for k in range(n)], mlpg_em),
+                                    n, order, gmm.M, model, mlpg_em))
             if gv is not None:
                 self.gv_moments = torch.empty((n, cols, 3), **f64)
                 chk(lib.kwy_column_moments_batch_dev(h, J(_lib.GvMatrix, [(conv[k], keep[2 * k]) for k in range(n)]), n,
@@ -693,6 +694,32 @@ class ConvertPipeline(_Graphed):
         return cs
 
 
+def _mlpg_em(mlpg_em):
+    """the option of the EM trajectory conversion, checked before anything is put on the device: None (one arg-max
+    mixture per frame) or the count of re-estimations as an int within [0, 16] (KWY_MLPG_EM_MAX)"""
+    if mlpg_em is None:
+        return None
+    if isinstance(mlpg_em, bool) or int(mlpg_em) != mlpg_em or not 0 <= int(mlpg_em) <= 16:
+        raise ValueError(f'mlpg_em must be None or an integer within [0, 16], not {mlpg_em!r}')
+    return int(mlpg_em)
+
+
+def _convert_jobs(rows, mlpg_em=None):
+    """the jobs of a batched conversion from (mc, T, mc_out) rows: kwy_convert_job, or with mlpg_em set
+    kwy_convert_em_job (no log-likelihoods asked for)"""
+    if mlpg_em is None:
+        return _lib.job_array(_lib.ConvertJob, rows)
+    return _lib.job_array(_lib.ConvertEmJob, [tuple(row) + (None,) for row in rows])
+
+
+def _convert_mcep_batch(handle, jobs, n, order, M, model, mlpg_em=None):
+    """kwy_convert_mcep_batch_dev over `_convert_jobs(rows, mlpg_em)`, or kwy_convert_mcep_em_batch_dev when mlpg_em is
+    set: -> the return code"""
+    if mlpg_em is None:
+        return lib.kwy_convert_mcep_batch_dev(handle, jobs, n, order, M, _p(model))
+    return lib.kwy_convert_mcep_em_batch_dev(handle, jobs, n, order, M, _p(model), mlpg_em)
+
+
 def _gv_on_device(gv_stats, gv_strength, order, dev, on=True):
     """the options of the global-variance postfilter, checked before anything is put on the device: -> the order + 1
     statistics as a device tensor, or None when nothing is filtered (strength 0, or on=False: no conversion)"""
@@ -765,11 +792,15 @@ class ConvertWave:
     formant_ratio != 1 (within [0.5, 2]): the envelopes the rendering reads -- the converted ones, without a GMM the
     analysed ones -- warped along frequency right before it, all rows of the wave in ONE in-place call
     (kwy_formant_shift_dev, backend.formant); `formant_status` holds one word for the wave (non-zero: rows left as they
-    are).  The differential output is not touched.  At 1 no kernel is launched and no buffer added."""
+    are).  The differential output is not touched.  At 1 no kernel is launched and no buffer added.
+    mlpg_em=N (with a GMM; an integer within [0, 16]): both conversions, plain and differential, are EM trajectory
+    conversions over soft mixture posteriors with N re-estimations (kwy_convert_mcep_em_batch_dev) instead of one
+    arg-max mixture per frame; everything after them runs as it does otherwise."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
                  f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                 ms_strength=0.0, formant_ratio=1.0):
+                 ms_strength=0.0, formant_ratio=1.0, mlpg_em=None):
+        self.mlpg_em = _mlpg_em(mlpg_em) if gmm is not None else None
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
         self.diff = bool(diff) and gmm is not None
         self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
@@ -838,12 +869,12 @@ class ConvertWave:
                 self.mc_conv = torch.empty((self.rows, order + 1), **f64)
                 self.sp_conv = torch.empty((self.rows, K), **f64)
                 conv, spec = rows.views(self.mc_conv), rows.views(self.sp_conv)
-                self.j_conv = _lib.job_array(_lib.ConvertJob, [(env[i], self.T[i], conv[i]) for i in range(n)])
+                self.j_conv = _convert_jobs([(env[i], self.T[i], conv[i]) for i in range(n)], self.mlpg_em)
             if self.diff:
                 self.model_diff = gmm.model(diff=True)
                 self.mc_diff = torch.empty((self.rows, order + 1), **f64)
                 self.mc_diff_rows = rows.views(self.mc_diff)
-                self.j_conv_diff = _lib.job_array(_lib.ConvertJob, [(env[i], self.T[i], self.mc_diff_rows[i]) for i in range(n)])
+                self.j_conv_diff = _convert_jobs([(env[i], self.T[i], self.mc_diff_rows[i]) for i in range(n)], self.mlpg_em)
                 samples = Ragged([v.numel() for v in self.x])         # the filtered inputs: as long as the inputs
                 self.wave_diff_all = torch.empty(samples.total, **f64)
                 self.wave_diff = samples.views(self.wave_diff_all)
@@ -907,7 +938,7 @@ class ConvertWave:
                 chk(lib.kwy_cheaptrick_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs)))
             else:
                 chk(lib.kwy_cheaptrick_mcep_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs), order, self.alpha))
-                chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv, n, order, self.gmm.M, _p(self.model)))
+                chk(_convert_mcep_batch(h, self.j_conv, n, order, self.gmm.M, self.model, self.mlpg_em))
                 cols = order + 1
                 # the differential coefficients take a filter's change of the plain conversion, which the filter of the
                 # plain conversion (in place) then overwrites: the differential conversion in front of the first filter
@@ -915,15 +946,15 @@ class ConvertWave:
                 if self.ms_status is not None:
                     stats = (self.ms_length, _p(self.ms[0]), _p(self.ms[1]), self.ms_strength)
                     if self.diff:
-                        chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
+                        chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em))
                         chk(lib.kwy_ms_postfilter_batch_dev(h, self.j_ms_diff, n, cols, 1, *stats, None))
                     chk(lib.kwy_ms_postfilter_batch_dev(h, self.j_ms, n, cols, 1, *stats, _p(self.ms_status)))
                 if self.gv_status is not None:
                     chk(lib.kwy_column_moments_batch_dev(h, self.j_gv_mom, n, cols, _p(self.gv_moments)))
                     if self.diff:
                         if self.ms_status is None:
-                            chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M,
-                                                               _p(self.model_diff)))
+                            chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff,
+                                                    self.mlpg_em))
                         chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv_diff, n, cols, 1, _p(self.gv), self.gv_strength,
                                                             None))
                     chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv, n, cols, 1, _p(self.gv), self.gv_strength,
@@ -941,7 +972,7 @@ class ConvertWave:
                 # the differential conversion of the same mel-cepstra, its filter over the INPUT waveforms: all
                 # utterances' recursions side by side (one wavefront each)
                 if self.gv_status is None and self.ms_status is None:           # (with a postfilter it ran above)
-                    chk(lib.kwy_convert_mcep_batch_dev(h, self.j_conv_diff, n, order, self.gmm.M, _p(self.model_diff)))
+                    chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em))
                 if not self.defer_mlsa:
                     self.run_mlsa(ls.ctx)
 
@@ -963,7 +994,7 @@ class ConvertWave:
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
                     f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                    ms_strength=0.0, formant_ratio=1.0):
+                    ms_strength=0.0, formant_ratio=1.0, mlpg_em=None):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
@@ -978,7 +1009,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
                          diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key,
                          **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}),
                          **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}),
-                         **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}))
+                         **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}),
+                         **(dict(mlpg_em=mlpg_em) if mlpg_em is not None else {}))
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -1423,7 +1455,8 @@ def _formant_ratio(formant_ratio, driver, pool, who):
 
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
                   shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
-                  gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0):
+                  gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0,
+                  mlpg_em=None):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1440,8 +1473,11 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     ms_length frames before it.
     formant_ratio (lockstep driver): a ratio other than 1 warps the converted envelopes along frequency before the
     synthesis (ConvertWave); the differential outputs are not touched; a row it cannot warp raises ValueError after the
-    batch, a ratio outside [0.5, 2] before anything is put on the device."""
+    batch, a ratio outside [0.5, 2] before anything is put on the device.
+    mlpg_em (lockstep driver): None, or N within [0, 16]: both outputs from EM trajectory conversions over soft mixture
+    posteriors with N re-estimations (ConvertWave; kwy_convert_mcep_em_batch_dev) instead of the arg-max conversion."""
     formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'convert_batch')
+    mlpg_em = _mlpg_em(mlpg_em)
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
@@ -1453,7 +1489,8 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
                         f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
-                        ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio)
+                        ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio,
+                        mlpg_em=mlpg_em)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
@@ -1465,6 +1502,8 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         raise ValueError('convert_batch: gv_stats and gv_strength need the lockstep driver')
     if ms_stats is not None or ms_strength != 0:
         raise ValueError('convert_batch: ms_stats and ms_strength need the lockstep driver')
+    if mlpg_em is not None:
+        raise ValueError('convert_batch: mlpg_em needs the lockstep driver')
     if pool is None:
         pool = StreamPool(device_index, streams)
 
@@ -1516,7 +1555,7 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
 
 def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_period=5.0, frames='speech', gv_stats=None,
                    gv_strength=0.0, f0_stats=None, transpose_key=0.0, per_frame=False, converter_fs=None, lockstep=None,
-                   wave_pairs=16):
+                   wave_pairs=16, mlpg_em=None):
     """Objective evaluation of the fitted mixture on parallel pairs, HBM-resident (what
     kwiiyatta_amd.evaluate_voice.evaluate does pair by pair through the Python API): waves of `wave_pairs` pairs
     through `EvalWave`.  pairs: ((x, f0, t), (x, f0, t)) triples as `build_training_matrix` takes them, all at the
@@ -1524,7 +1563,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     go through evaluate_voice.evaluate_pair, which resamples.  The silence pads are drawn from numpy's global
     generator in training's order, so under np.random.seed a pair's alignment is the one training would use.
     frames='speech': the distortion over the aligned frames whose target-side binarised power term is set; 'all': over
-    every aligned frame inside both utterances.  gv_stats / gv_strength, f0_stats / transpose_key: as in
+    every aligned frame inside both utterances.  gv_stats / gv_strength, f0_stats / transpose_key, mlpg_em: as in
     `convert_batch`.  Returns (records, total): a dict per pair and one of the pooled figures -- the triples
     mcd_moments, source_moments, f0_moments ((n, mean, M2); merged by kwy_moments_merge_dev for the total), counts
     (VV, VU, UV, UU), aligned (frames of the alignment) and outside (those beyond either utterance) -- read back once,
@@ -1538,6 +1577,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     dev = torch.device('cuda', device_index)
     gv = _gv_on_device(gv_stats, gv_strength, order, dev)       # (raises before anything else is put on the device)
     stats = _f0_stats_on_device(f0_stats, dev)
+    mlpg_em = _mlpg_em(mlpg_em)
     zero = dict(mcd_moments=(0.0, 0.0, 0.0), source_moments=(0.0, 0.0, 0.0), f0_moments=(0.0, 0.0, 0.0),
                 counts=(0, 0, 0, 0), aligned=0, outside=0)
     if not pairs:
@@ -1559,7 +1599,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
         wave = EvalWave(ls, fs, pairs[w0:w0 + wave_pairs], order=order, radius=radius, frame_period=frame_period)
         wave.analyse()
         wave.measure(pads, dg, model, tot, w0, frames=frames, gv=gv, gv_strength=gv_strength, f0_stats=stats,
-                     transpose_key=float(transpose_key), per_frame=per_frame)
+                     transpose_key=float(transpose_key), per_frame=per_frame, mlpg_em=mlpg_em)
         waves.append(wave)
         if not per_frame:
             while len(waves) > 2:

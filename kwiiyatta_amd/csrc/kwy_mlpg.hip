@@ -14,6 +14,8 @@
 //   k_gmm_cond   four frames per wavefront: arg-max mixture, conditional mean E (from A transposed) and variance D
 //   k_mlpg_build per (frame, dim): the pentadiagonal normal equations W'PW, W'P mu
 //   k_mlpg_chunks / k_mlpg_finish  per static dim: banded Cholesky, partitioned into chunks (nested dissection)
+//   k_em_prep / k_em_estep / k_em_loglik  EM trajectory conversion over soft mixture posteriors (at the end of the file):
+//                all M conditional means of a frame tile on the f64 MFMA, online softmax, precision-weighted sums
 //
 // Algorithmic HBM bytes per frame: d*8 in, d*8 out (+ the GMM once per call).
 #include <math.h>
@@ -1306,5 +1308,456 @@ extern "C" int kwy_gmm_mlpg(kwy_ctx *ctx, const double *x, int64_t T, int d, int
                             : "gmm_mlpg: MLPG system is not positive definite";
     return KWY_ENUMERIC;
   }
+  return KWY_OK;
+}
+
+// ---- EM trajectory conversion over soft mixture posteriors (Toda et al. 2007, section IV) -----------------------
+// The arithmetic is the contract of kwy_gmm_mlpg_em in include/kwy.h.  Instead of one arg-max mixture per frame every
+// mixture weighs in with its posterior, and the posteriors are re-estimated from the source frame AND the trajectory
+// of the previous solve (with its deltas) a fixed number of times.  Per iteration that takes all M conditional means of
+// every frame: k_em_estep, the E-step, on the f64 MFMA.
+//   k_em_prep    per mixture: 1 / v_m[c] and sum_c log(2 pi v_m[c]) (c ascending), once per call
+//   k_em_estep   a workgroup owns 64 frames, a wavefront 16 of them, and walks the mixtures in ascending order.  AT_m goes
+//                through registers into LDS in MFMA-fragment order (fragment (nb, ks) = the 64 lane values of the B
+//                operand of column block nb and k-step ks; the loads of mixture m + 1 are in flight while m is
+//                multiplied); E[m] = muy_m + A_m (x - mux_m) is accumulated from muy_m in ascending k, as k_gmm_cond
+//                does, the column blocks' accumulators as independent chains under every k-step.  In the accumulator layout (col = lane & 15, row = (lane >> 4) + 4 reg) a lane holds, for four
+//                frames and every column block, the trajectory's delta features, pbar and r; the quadratic term of a
+//                frame is a butterfly sum over the 16 lanes of its row group (every lane ends with the same bits), and
+//                the mixture is folded into pbar and r by an online softmax (running maximum, rescaling).  It stores
+//                Ebar = r / pbar and Dbar = 1 / pbar, which k_mlpg_build takes as they are, and logsumexp_m per frame.
+//   k_em_loglik  one workgroup per utterance: the sum of the frames' logsumexp in a fixed order
+// A frame's results depend on its own row of X, its neighbours' trajectory rows inside its utterance and the model
+// only: not on the tile it falls into, nor on what else is in the batch.
+#define ML_EM_NW 4
+#define ML_EM_TILE (16 * ML_EM_NW)
+#define ML_EM_MAXBLK ML_FRAG_MAXBLK      // D <= 96: beyond what k_gmm_prep admits (D <= 82)
+
+struct ml_em_out { double *loglik[KWY_BATCH_MAX]; };     // per utterance: em_iterations + 1 doubles, or null
+
+__global__ void k_em_prep(const double *__restrict__ model, int D, int M, double *__restrict__ iv,
+                          double *__restrict__ lc) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= M) return;
+  const double *dv = model + (size_t)m * ml_model_stride(D) + 2 * D * D + 2 * D;
+  double s = 0.0;
+  for (int c = 0; c < D; ++c) {
+    iv[(size_t)m * D + c] = 1.0 / dv[c];
+    s += log(2.0 * KWY_PI * dv[c]);
+  }
+  lc[m] = s;
+}
+
+template <int NBLK>
+__global__ __launch_bounds__(64 * ML_EM_NW) void k_em_estep(const double *__restrict__ X, ml_dims dm, ml_batch bt,
+                                                            const double *__restrict__ model,
+                                                            const double *__restrict__ logp,
+                                                            const double *__restrict__ iv, const double *__restrict__ lc,
+                                                            int first, double *__restrict__ E, double *__restrict__ Dv,
+                                                            double *__restrict__ lse) {
+  constexpr int KS = 4 * NBLK, NP = 16 * NBLK, NFRAG = NBLK * KS, NT = 64 * ML_EM_NW;
+  constexpr int PER = NFRAG * 64 / NT, PERV = (3 * NP + NT - 1) / NT;
+  extern __shared__ double smem[];
+  double *af = smem;                // NFRAG x 64: AT_m in fragment order (beyond D: copies of row / column D - 1)
+  double *vec = af + NFRAG * 64;    // mux_m | muy_m | 1 / v_m, NP each, zero beyond D
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int ar = lane & 15, ak = lane >> 4;
+  const int D = dm.D, M = dm.M, kp4 = ml_kp(D) / 4;      // 4 (NBLK - 1) < kp4 <= 4 NBLK
+  const int64_t t0 = (int64_t)blockIdx.x * ML_EM_TILE + 16 * wv;
+  // rows behind the last frame repeat it and store nothing (a wavefront without frames still keeps the barriers)
+  const double *xrow = X + min(t0 + ar, dm.T - 1) * D;
+  double xa[KS];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) {
+    const int c = 4 * ks + ak;
+    const double v = xrow[min(c, D - 1)];
+    xa[ks] = c < D ? v : 0.0;
+  }
+  int64_t tc[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) tc[r] = min(t0 + ak + 4 * r, dm.T - 1);
+  // delta features of the current trajectory at [frame (lane >> 4) + 4 r][column 16 nb + (lane & 15)]
+  double Yd[NBLK][4];
+#pragma unroll
+  for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Yd[nb][r] = 0.0;
+  if (!first) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int u = bt.find(tc[r]);
+      const int64_t t = tc[r] - bt.start[u], Tu = bt.start[u + 1] - bt.start[u];
+      const double *y = bt.u[u].y + t * bt.ldy;
+#pragma unroll
+      for (int nb = 0; nb < NBLK; ++nb) {
+        const int col = 16 * nb + ar;
+        if (col < D) {
+          const int w = col / dm.d, c = col - w * dm.d;
+          const double y0 = y[c];
+          const double ym = t > 0 ? y[c - bt.ldy] : 0.0;
+          const double yp = t + 1 < Tu ? y[c + bt.ldy] : 0.0;
+          Yd[nb][r] = w == 0 ? y0 : (w == 1 ? 0.5 * (yp - ym) : (yp - 2.0 * y0) + ym);
+        }
+      }
+    }
+  }
+  double pb[NBLK][4], ra[NBLK][4], mx[4], sm[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    mx[r] = -INFINITY;
+    sm[r] = 0.0;
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb) { pb[nb][r] = 0.0; ra[nb][r] = 0.0; }
+  }
+  double pre[PER], prv[PERV];
+  auto fetch = [&](int m) {
+    const double *mod = model + (size_t)m * ml_model_stride(D);
+    const double *AT = mod + ml_model_at(D), *mux = mod + 2 * D * D, *muy = mux + D, *ivm = iv + (size_t)m * D;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int idx = tid + i * NT, f = idx >> 6, l = idx & 63;
+      const int nb = f / KS, ks = f - nb * KS;
+      const int col = 16 * nb + (l & 15), k = 4 * ks + (l >> 4);
+      // no zero padding needed (and no select next to the load: the compiler turns one into a branch around the load
+      // with a wait inside, 25 load latencies in a row per mixture): a row k >= D meets the A operand 0 - 0, and a
+      // column >= D is weighed by the zero behind 1 / v_m and never stored; the clamped loads keep both finite
+      pre[i] = AT[(size_t)min(k, D - 1) * D + min(col, D - 1)];
+    }
+#pragma unroll
+    for (int i = 0; i < PERV; ++i) {
+      const int j = tid + i * NT, which = j / NP, c = j - which * NP;
+      const double *src = which == 0 ? mux : (which == 1 ? muy : ivm);
+      prv[i] = src[min(c, D - 1)];       // (zeroed beyond D where it is stored: a mask there, not a select here)
+    }
+  };
+  fetch(0);
+  for (int m = 0; m < M; ++m) {
+    __syncthreads();      // mixture m - 1 has been consumed
+#pragma unroll
+    for (int i = 0; i < PER; ++i) af[tid + i * NT] = pre[i];
+#pragma unroll
+    for (int i = 0; i < PERV; ++i) {
+      const int j = tid + i * NT;
+      const long long keep = -(long long)(j % NP < D);
+      if (j < 3 * NP) vec[j] = __longlong_as_double(__double_as_longlong(prv[i]) & keep);
+    }
+    __syncthreads();
+    if (m + 1 < M) fetch(m + 1);
+    double lpm[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lpm[r] = logp[tc[r] * M + m];
+    const double lcm = lc[m];
+    // NBLK independent accumulator chains (one per column block) under every k-step: a chain alone leaves the matrix
+    // core waiting for its own result
+    ml_v4f64 acc[NBLK];
+    double ivc[NBLK], q[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb) {
+      const double my = vec[NP + 16 * nb + ar];
+      ivc[nb] = vec[2 * NP + 16 * nb + ar];
+      acc[nb] = ml_v4f64{my, my, my, my};
+    }
+    // the operands of k-step ks + 1 are read from LDS before the products of k-step ks are issued (one wavefront per
+    // SIMD: nothing else hides the LDS latency in front of every product)
+    double bc[NBLK], bn[NBLK], mc = vec[ak], mn = 0.0;
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb) { bc[nb] = af[nb * KS * 64 + lane]; bn[nb] = 0.0; }
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if (ks + 1 < KS) {
+        mn = vec[4 * (ks + 1) + ak];
+#pragma unroll
+        for (int nb = 0; nb < NBLK; ++nb) bn[nb] = af[(nb * KS + ks + 1) * 64 + lane];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (ks <= KS - 4 || ks < kp4) {
+        const double a = xa[ks] - mc;
+#pragma unroll
+        for (int nb = 0; nb < NBLK; ++nb)
+          acc[nb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bc[nb], acc[nb], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      mc = mn;
+#pragma unroll
+      for (int nb = 0; nb < NBLK; ++nb) bc[nb] = bn[nb];
+    }
+#pragma unroll
+    for (int nb = 0; nb < NBLK; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double dl = Yd[nb][r] - acc[nb][r];
+        q[r] += (dl * dl) * ivc[nb];
+      }
+    if (!first) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {     // butterfly over the row group: commutative sums, the same bits in every lane
+        double v = q[r];
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        v += __shfl_xor(v, 4);
+        v += __shfl_xor(v, 8);
+        q[r] = v;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const double l = first ? lpm[r] : lpm[r] - 0.5 * (lcm + q[r]);
+      const double mn = fmax(mx[r], l);
+      double sc = 1.0, w = 0.0;
+      if (mn != -INFINITY) { sc = exp(mx[r] - mn); w = exp(l - mn); }
+      sm[r] = sm[r] * sc + w;
+      mx[r] = mn;
+#pragma unroll
+      for (int nb = 0; nb < NBLK; ++nb) {
+        const double wi = w * ivc[nb];
+        pb[nb][r] = pb[nb][r] * sc + wi;
+        ra[nb][r] = ra[nb][r] * sc + wi * acc[nb][r];
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t t = t0 + ak + 4 * r;
+    if (t < dm.T) {
+#pragma unroll
+      for (int nb = 0; nb < NBLK; ++nb) {
+        const int col = 16 * nb + ar;
+        if (col < D) {
+          E[t * D + col] = ra[nb][r] / pb[nb][r];
+          Dv[t * D + col] = sm[r] / pb[nb][r];
+        }
+      }
+      if (ar == 0) lse[t] = mx[r] + log(sm[r]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_em_loglik(const double *__restrict__ lse, ml_batch bt, ml_em_out out, int k) {
+  __shared__ double red[256];
+  const int u = blockIdx.x, tid = threadIdx.x;
+  double *dst = out.loglik[u];
+  if (!dst) return;
+  const int64_t t0 = bt.start[u], t1 = bt.start[u + 1];
+  double s = 0.0;
+  for (int64_t t = t0 + tid; t < t1; t += 256) s += lse[t];
+  red[tid] = s;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) dst[k] = red[0];
+}
+
+static size_t ml_em_scratch_bytes(int64_t T, int d, int M, int n = 1) {
+  return ml_scratch_bytes(T, d, M, n) + kwy_pad(sizeof(double) * (size_t)M * 3 * d) + kwy_pad(sizeof(double) * M) +
+         kwy_pad(sizeof(double) * T);
+}
+
+static size_t ml_em_lds(int nblk) { return sizeof(double) * ((size_t)4 * nblk * nblk * 64 + 48 * nblk); }
+
+template <int NBLK>
+static void ml_launch_estep(kwy_ctx *ctx, const double *X, const ml_dims &dm, const ml_batch &bt, const double *model,
+                            const double *logp, const double *iv, const double *lc, int first, double *E, double *Dv,
+                            double *lse) {
+  const unsigned grid = (unsigned)((dm.T + ML_EM_TILE - 1) / ML_EM_TILE);
+  KWY_PROF(ctx, "k_em_estep", hipLaunchKernelGGL(k_em_estep<NBLK>, dim3(grid), dim3(64 * ML_EM_NW), ml_em_lds(NBLK),
+                                                 ctx->stream, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse));
+}
+
+template <int NBLK>
+static int ml_estep_attr(kwy_ctx *ctx) {
+  KWY_HIP(hipFuncSetAttribute((const void *)k_em_estep<NBLK>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)ml_em_lds(NBLK)));
+  return KWY_OK;
+}
+
+// the counterpart of mlpg_batch_core: em_iterations + 1 trajectory solves, an E-step before each, and one more after
+// the last where a log-likelihood is asked for.  lik[k]: utterance k's em_iterations + 1 doubles on the device, or null.
+static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d, int M, const double *weights,
+                              const double *means, const double *covs, int diff, int **status_out,
+                              const double *prepared, int em_iterations, double *const *lik) {
+  const int D = 3 * d, n = bt.n, nblk = ml_frag_blocks(D);
+  int64_t T = 0, Tmax = 0;
+  int Pmax = 1;
+  bool want_lik = false;
+  ml_em_out out;
+  for (int k = 0; k < n; ++k) {
+    bt.start[k] = T;
+    T += Ts[k];
+    Tmax = std::max(Tmax, Ts[k]);
+    bt.u[k].pt = ml_partition(Ts[k], d);
+    Pmax = std::max(Pmax, bt.u[k].pt.P);
+    out.loglik[k] = lik ? lik[k] : nullptr;
+    want_lik = want_lik || out.loglik[k];
+  }
+  for (int k = n; k <= KWY_BATCH_MAX; ++k) bt.start[k] = T;
+  for (int k = n; k < KWY_BATCH_MAX; ++k) { bt.u[k] = bt.u[0]; out.loglik[k] = nullptr; }
+  ml_dims dm = {d, D, M, T};
+  double *model = prepared ? const_cast<double *>(prepared) : kwy_arena<double>(ctx, ml_model_stride(D) * M);
+  double *X = kwy_arena<double>(ctx, (size_t)T * D);
+  double *E = kwy_arena<double>(ctx, (size_t)T * D);
+  double *Dv = kwy_arena<double>(ctx, (size_t)T * D);
+  double *logp = kwy_arena<double>(ctx, (size_t)T * M);
+  double *band = kwy_arena<double>(ctx, (size_t)T * d * 4);
+  double *rhs = kwy_arena<double>(ctx, (size_t)T * d * 2);
+  double *Ysp = kwy_arena<double>(ctx, (size_t)T * d * 4);
+  double *bnd = kwy_arena<double>(ctx, (size_t)n * ML_CHUNK_WGS * 64 * ML_BD);
+  double *iv = kwy_arena<double>(ctx, (size_t)M * D);
+  double *lc = kwy_arena<double>(ctx, M);
+  double *lse = kwy_arena<double>(ctx, T);
+  int *status = kwy_arena<int>(ctx, 16);
+  if (!model || !X || !E || !Dv || !logp || !band || !rhs || !Ysp || !bnd || !iv || !lc || !lse || !status) {
+    ctx->err = "gmm_mlpg_em: scratch arena too small";
+    return KWY_ENOMEM;
+  }
+  *status_out = status;
+  KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
+  const size_t lds_prep = sizeof(double) * 3 * D * D;
+  const int cpw = 64 / d;
+  const size_t lds_solve = sizeof(double) * ((size_t)d * 2 * (Pmax - 1) * 5 + 8);
+  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
+  KWY_HIP(hipFuncSetAttribute((const void *)k_mlpg_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds_solve));
+  switch (nblk) {
+    case 1: KWY_TRY(ml_estep_attr<1>(ctx)); break;
+    case 2: KWY_TRY(ml_estep_attr<2>(ctx)); break;
+    case 3: KWY_TRY(ml_estep_attr<3>(ctx)); break;
+    case 4: KWY_TRY(ml_estep_attr<4>(ctx)); break;
+    case 5: KWY_TRY(ml_estep_attr<5>(ctx)); break;
+    default: KWY_TRY(ml_estep_attr<6>(ctx)); break;
+  }
+  auto estep = [&](int first) {
+    switch (nblk) {
+      case 1: ml_launch_estep<1>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
+      case 2: ml_launch_estep<2>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
+      case 3: ml_launch_estep<3>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
+      case 4: ml_launch_estep<4>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
+      case 5: ml_launch_estep<5>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
+      default: ml_launch_estep<6>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
+    }
+  };
+  if (!prepared)
+    hipLaunchKernelGGL(k_gmm_prep, dim3(M), dim3(KWY_THREADS), lds_prep, ctx->stream, weights, means, covs, D,
+                       diff, model, status);
+  const unsigned ge = (unsigned)((T * d + 255) / 256);
+  hipLaunchKernelGGL(k_delta, dim3(ge), dim3(256), 0, ctx->stream, bt, dm, X);
+  KWY_TRY(ml_launch_logp(ctx, X, dm, model, logp));
+  hipLaunchKernelGGL(k_em_prep, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, ctx->stream, model, D, M, iv, lc);
+  estep(1);
+  int fin = (int)((Tmax * d + 4 * ML_FIN_NT - 1) / (4 * ML_FIN_NT));
+  if (fin > ML_FIN_WGS) fin = ML_FIN_WGS;
+  for (int k = 0; k <= em_iterations; ++k) {
+    hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, E, Dv, bt, dm, band);
+    KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0, ctx->stream,
+                                                       band, rhs, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
+    KWY_PROF(ctx, "k_mlpg_finish", hipLaunchKernelGGL(k_mlpg_finish, dim3((unsigned)fin, n), dim3(ML_FIN_NT), lds_solve, ctx->stream,
+                                                       band, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
+    if (k < em_iterations || want_lik) {
+      estep(0);
+      if (want_lik) hipLaunchKernelGGL(k_em_loglik, dim3(n), dim3(256), 0, ctx->stream, lse, bt, out, k);
+    }
+  }
+  KWY_HIP(hipGetLastError());
+  return KWY_OK;
+}
+
+static int ml_em_check(kwy_ctx *ctx, const void *x, int64_t T, int d, int M, const void *w, const void *mu,
+                       const void *cv, const void *y, int em_iterations) {
+  KWY_TRY(ml_check(ctx, x, T, d, M, w, mu, cv, y));
+  if (em_iterations < 0 || em_iterations > KWY_MLPG_EM_MAX) {
+    ctx->err = "gmm_mlpg_em: em_iterations outside [0, KWY_MLPG_EM_MAX]";
+    return KWY_EINVAL;
+  }
+  // what kwy_gmm_prepare_dev refuses (three D x D matrices in LDS) cannot arrive here as a prepared model either
+  if (sizeof(double) * 3 * (3 * d) * (3 * d) > 160 * 1024 || ml_frag_blocks(3 * d) > ML_EM_MAXBLK) {
+    ctx->err = "gmm_mlpg_em: feature dimension too large";
+    return KWY_EINVAL;
+  }
+  return KWY_OK;
+}
+
+extern "C" int kwy_convert_mcep_em_batch_dev(kwy_ctx *ctx, const kwy_convert_em_job *jobs, int count, int d, int M,
+                                             const double *model, int em_iterations) {
+  if (!ctx) return KWY_EINVAL;
+  if (!jobs || count < 0) { ctx->err = "convert_mcep_em_batch: bad argument"; return KWY_EINVAL; }
+  if (count == 0) return KWY_OK;
+  size_t bytes = 0;
+  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
+    int64_t Tsum = 0;
+    const int n = std::min(KWY_BATCH_MAX, count - j0);
+    for (int j = j0; j < j0 + n; ++j) {
+      KWY_TRY(ml_em_check(ctx, jobs[j].mc, jobs[j].T, d, M, model, model, model, jobs[j].mc_out, em_iterations));
+      Tsum += jobs[j].T;
+    }
+    bytes += ml_em_scratch_bytes(Tsum, d, M, n);
+  }
+  KWY_HIP(hipSetDevice(ctx->device));
+  KWY_TRY(kwy_arena_begin(ctx, bytes));
+  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
+    ml_batch bt;
+    int64_t Ts[KWY_BATCH_MAX];
+    double *lik[KWY_BATCH_MAX];
+    bt.n = std::min(KWY_BATCH_MAX, count - j0);
+    bt.ldx = d + 1;
+    bt.ldy = d + 1;
+    for (int k = 0; k < bt.n; ++k) {
+      const kwy_convert_em_job &q = jobs[j0 + k];
+      bt.u[k].x = q.mc + 1; bt.u[k].y = q.mc_out + 1;
+      bt.u[k].keep_in = q.mc; bt.u[k].keep_out = q.mc_out;
+      Ts[k] = q.T;
+      lik[k] = q.loglik;
+    }
+    int *status;
+    KWY_TRY(mlpg_em_batch_core(ctx, bt, Ts, d, M, nullptr, nullptr, nullptr, 0, &status, model, em_iterations, lik));
+  }
+  return KWY_OK;
+}
+
+extern "C" int kwy_convert_mcep_em_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
+                                       int em_iterations, double *mc_out, double *loglik) {
+  if (!ctx) return KWY_EINVAL;
+  kwy_convert_em_job job = {mc, T, mc_out, loglik};
+  return kwy_convert_mcep_em_batch_dev(ctx, &job, 1, d, M, model, em_iterations);
+}
+
+extern "C" int kwy_gmm_mlpg_em(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
+                               const double *means, const double *covs, int diff, int em_iterations, double *y,
+                               double *loglik) {
+  KWY_TRY(ml_em_check(ctx, x, T, d, M, weights, means, covs, y, em_iterations));
+  KWY_HIP(hipSetDevice(ctx->device));
+  const int D2 = 6 * d;
+  size_t bx = kwy_pad(sizeof(double) * T * d), bw = kwy_pad(sizeof(double) * M);
+  size_t bm = kwy_pad(sizeof(double) * M * D2), bc = kwy_pad(sizeof(double) * (size_t)M * D2 * D2);
+  KWY_TRY(kwy_arena_begin(ctx, ml_em_scratch_bytes(T, d, M) + 2 * bx + bw + bm + bc +
+                                   kwy_pad(sizeof(double) * (KWY_MLPG_EM_MAX + 1))));
+  double *dx = kwy_arena<double>(ctx, (size_t)T * d), *dy = kwy_arena<double>(ctx, (size_t)T * d);
+  double *dw = kwy_arena<double>(ctx, M), *dmu = kwy_arena<double>(ctx, (size_t)M * D2);
+  double *dcv = kwy_arena<double>(ctx, (size_t)M * D2 * D2);
+  double *dlik = kwy_arena<double>(ctx, KWY_MLPG_EM_MAX + 1);
+  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * T * d, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dw, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dmu, means, sizeof(double) * M * D2, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dcv, covs, sizeof(double) * (size_t)M * D2 * D2, hipMemcpyHostToDevice, ctx->stream));
+  ml_batch bt;
+  bt.n = 1;
+  bt.ldx = d;
+  bt.ldy = d;
+  bt.u[0].x = dx; bt.u[0].y = dy; bt.u[0].keep_in = nullptr; bt.u[0].keep_out = nullptr;
+  double *lik[1] = {loglik ? dlik : nullptr};
+  int *status;
+  KWY_TRY(mlpg_em_batch_core(ctx, bt, &T, d, M, dw, dmu, dcv, diff, &status, nullptr, em_iterations, lik));
+  int hstatus = 0;
+  std::vector<double> hl(em_iterations + 1);
+  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * T * d, hipMemcpyDeviceToHost, ctx->stream));
+  if (loglik) KWY_HIP(hipMemcpyAsync(hl.data(), dlik, sizeof(double) * (em_iterations + 1), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  if (hstatus != 0) {
+    ctx->err = hstatus == 1 ? "gmm_mlpg_em: source covariance is not positive definite"
+                            : "gmm_mlpg_em: MLPG system is not positive definite";
+    return KWY_ENUMERIC;
+  }
+  if (loglik) std::copy(hl.begin(), hl.end(), loglik);
   return KWY_OK;
 }

@@ -104,14 +104,16 @@ def _check_options(gv, transpose_key, frames):
 
 
 def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose_key=0.0, frames='speech',
-                  per_frame=False):
+                  per_frame=False, em=None):
     """The figures of one parallel pair: two unaligned feature sets (trimmed as training trims them, if the alignment
     is to be the one training would use).  Both are padded and aligned as `align_even` does -- the same pad draws in
     the same order, so a seeded run reproduces training's alignment -- `source.mel_cepstrum` is converted on its own
     time axis through `converter.convert(..., gv=gv)` (which resamples a source of another sampling rate to the
     converter's; the comparison then runs at the converter's rate), and the kernels measure along the index lists.
     convert_f0 / transpose_key: the source f0 through the converter's f0 map first (convert_voice's options).
-    per_frame=True keeps the index lists and the per-frame distortion in the result."""
+    per_frame=True keeps the index lists and the per-frame distortion in the result.
+    em=N: the conversion is the EM trajectory conversion over soft mixture posteriors with N re-estimations
+    (`converter.convert(..., em=N)`, convert_voice's --mlpg-em); None: one arg-max mixture per frame."""
     import kwiiyatta_amd as k
     from .backend import distortion as dist
     from .backend import f0 as f0map
@@ -122,7 +124,8 @@ def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose
     a, b = k.pad_silence(source, PAD_LEN), k.pad_silence(target, PAD_LEN)
     xs, ys = even_indices(a, b, PAD_LEN, strict=True)
     idx_x, idx_y = (np.ascontiguousarray(v, dtype=np.int32) for v in (xs, ys))
-    converted = converter.convert(source.mel_cepstrum, **(dict(gv=gv) if gv > 0 else {}))
+    converted = converter.convert(source.mel_cepstrum, **(dict(gv=gv) if gv > 0 else {}),
+                                  **({} if em is None else dict(em=em)))
     fs = converted.fs
 
     def coefficients(f):
@@ -194,6 +197,7 @@ def make_config():
     conf.add_argument('--json', type=str, metavar='PATH', help='Write per-file and pooled figures to this file')
     conf.add_transpose_key_argument()
     conf.add_gv_argument()
+    conf.add_mlpg_em_argument()
     conf.add_converter_arguments()
     return conf
 
@@ -261,7 +265,8 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
             [p for _, p, _ in batch], converter.fs, converter.gmm, order=converter.order, frame_period=batch[0][2],
             f0_stats=converter.f0_stats if options['convert_f0'] else None, transpose_key=options['transpose_key'],
             frames=options['frames'], **(dict(gv_stats=converter.gv_stats, gv_strength=options['gv'])
-                                         if options['gv'] > 0 else {}))
+                                         if options['gv'] > 0 else {}),
+            **({} if options.get('em') is None else dict(mlpg_em=options['em'])))
         for (key, _, _), rec in zip(batch, records):
             results[key] = Result(rec['mcd_moments'], rec['source_moments'], rec['f0_moments'], rec['counts'],
                                   rec['aligned'], rec['outside'])
@@ -318,6 +323,8 @@ def main():
             print(warning, file=sys.stderr)
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0)
     options = dict(gv=conf.gv, convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, frames=conf.frames)
+    if conf.mlpg_em is not None:           # (--mlpg-em: EM trajectory conversion, as convert_voice runs it)
+        options['em'] = conf.mlpg_em
     if conf.batch:
         results = _evaluate_batched(conf, converter, dataset, keys, options)
         total = pool(results)
