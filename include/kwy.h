@@ -653,6 +653,85 @@ typedef struct kwy_convert_em_job {
 } kwy_convert_em_job;
 int kwy_convert_mcep_em_batch_dev(kwy_ctx *ctx, const kwy_convert_em_job *jobs, int count, int d, int M,
                                   const double *model, int em_iterations);
+/* Parameter generation considering the global variance (an addition: section IV of the same paper).  The postfilter
+ * kwy_gv_postfilter scales a converted track linearly about its mean; this maximises the trajectory likelihood and
+ * the likelihood of the trajectory's global variance jointly, starting from that scaled track.  Per utterance of T
+ * frames and per static dimension c (the dimensions are independent), with
+ *     P, b     the pentadiagonal W' diag(pbar) W and W' r, as records {P[t][t], P[t][t-1], P[t][t-2], b[t]} per (t, c)
+ *              (P[0][-1], P[0][-2], P[1][-1] are not read)
+ *     y_ML     the solution of P y = b
+ *     s        an offset track (zero when NULL): z = y + s is the track whose variance counts
+ *     mu, s2   gv_mean[c], gv_var[c]: mean and variance over the training utterances of the target's per-utterance
+ *              variance of this coefficient;    weight > 0;    w = 1 / (3 T)
+ *     zbar = mean of z,   v(y) = (1/T) sum_t (z_t - zbar)^2
+ *     Q(y) = w (-1/2 y'P y + b'y) - 1/2 weight (v(y) - mu)^2 / s2
+ *     g(y) = w (b - P y) - weight (v(y) - mu) / s2 * (2/T) (z - zbar)
+ * Start: y_0 = sqrt(mu / v(y_ML)) (z - zbar) + zbar - s (z, zbar of y_ML), taken if Q(y_0) >= Q(y_ML), else y_0 = y_ML.
+ * Iterations k = 1 .. N, nonlinear conjugate gradients (Polak-Ribiere+) with an exact line search:
+ *     p = g_1 for k = 1;  else beta = max(0, g_k.(g_k - g_k-1) / (g_k-1.g_k-1)), p = g_k + beta p, p = g_k if g_k.p <= 0
+ *     v(y + a p) = v(y) + 2 a cov(z, p) + a^2 var(p) (ddof 0), so with A = p'P p, B = p.(b - P y), e = v(y) - mu,
+ *     k = weight / s2 the derivative of a -> Q(y + a p) is the cubic
+ *         (w B - 2 k e cov) - (w A + k (4 cov^2 + 2 e var)) a - 6 k cov var a^2 - 2 k var^2 a^3
+ *     a = its smallest positive real root; y <- y + a p if Q, evaluated at the new point, is not smaller.
+ *     Without such a root, with g.p not positive and finite, or with the step refused, the column is frozen: it keeps y
+ *     for the remaining iterations.
+ * N is a fixed count in [0, KWY_MLPG_GV_MAX]: no convergence test.  objective (N + 1 doubles, or NULL) receives
+ * Q_0 .. Q_N of the utterance: the sum over its processed columns in ascending c; the sequence never decreases.
+ * A column with v(y_ML) == 0 (a constant track, T == 1) is returned unchanged and adds nothing to the objective.  So
+ * does a column whose mu or s2 is not finite or not positive, or whose v(y_ML) is not finite; those are counted in
+ * the utterance's status word (one int32 per job, or NULL).  Every reduction has a fixed order and no job depends on
+ * another: every job of a batch equals the single call's bits.  The _dev forms take scratch from the context's arena
+ * and do not synchronise (legal inside a stream capture once the arena has its size).  d <= 64.  Counts out of range, a
+ * weight that is not positive and finite, or a null matrix return KWY_EINVAL with nothing written; count == 0 is
+ * KWY_OK.
+ * kwy_gv_ascent (host pointers) / kwy_gv_ascent_batch_dev (device pointers: jobs' arrays, gv_mean, gv_var, status):
+ * the ascent on the caller's records. */
+#define KWY_MLPG_GV_MAX 256
+typedef struct kwy_gv_ascent_job {
+  const double *band;    /* T x d records of four doubles */
+  const double *offset;  /* T x d, or NULL */
+  double *y;             /* T x d: in y_ML, out y_N */
+  int64_t T;
+  double *objective;     /* iterations + 1 doubles, or NULL */
+} kwy_gv_ascent_job;
+int kwy_gv_ascent(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int count, int d, const double *gv_mean,
+                  const double *gv_var, double weight, int iterations, int32_t *status);
+int kwy_gv_ascent_batch_dev(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int count, int d, const double *gv_mean,
+                            const double *gv_var, double weight, int iterations, int32_t *status);
+/* gv_mean[c], gv_var[c] from (count, cols, 3) column moments: mean and variance (ddof 0, two passes, left folds in
+ * index order) of M2 / n over the matrices with n > 0.  gv_mean equals kwy_gv_from_moments' value bit for bit; with
+ * fewer than two such matrices gv_var is 0. */
+int kwy_gv_stats_from_moments(kwy_ctx *ctx, const double *moments, int count, int cols, double *gv_mean,
+                              double *gv_var);
+int kwy_gv_stats_from_moments_dev(kwy_ctx *ctx, const double *moments, int count, int cols, double *gv_mean,
+                                  double *gv_var);
+/* The conversion with the ascent behind it.  The posteriors are fixed first: em_iterations == -1 picks one arg-max
+ * mixture per frame (kwy_gmm_mlpg / kwy_convert_mcep_dev), em_iterations in [0, KWY_MLPG_EM_MAX] runs the EM scheme
+ * above; the ascent then runs on the P, b of the last solve and on its y.  gv_offset == 1: s = the source's static
+ * coefficients (for a model prepared with diff = 1: the trajectory is the differential y - x and the variance that
+ * matters is that of the converted spectrum); 0: s = 0.  gv_mean, gv_var: d values for c1..cd.  loglik
+ * (em_iterations + 1 doubles, or NULL; ignored with em_iterations == -1), objective (gv_iterations + 1 doubles, or
+ * NULL), status (one int32 per job, or NULL).  kwy_gmm_mlpg_gv: host pointers, as kwy_gmm_mlpg_em;
+ * kwy_convert_mcep_gv_dev / _batch_dev: device pointers (gv_mean, gv_var, loglik, objective and status too), column 0
+ * kept.  Refusals as above and as the EM entries'. */
+int kwy_gmm_mlpg_gv(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
+                    const double *means, const double *covs, int diff, int em_iterations, int gv_offset,
+                    const double *gv_mean, const double *gv_var, double weight, int gv_iterations, double *y,
+                    double *loglik, double *objective, int32_t *status);
+int kwy_convert_mcep_gv_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
+                            int em_iterations, int gv_offset, const double *gv_mean, const double *gv_var,
+                            double weight, int gv_iterations, double *mc_out, double *loglik, double *objective,
+                            int32_t *status);
+typedef struct kwy_convert_gv_job {
+  const double *mc;      /* T x (d + 1) */
+  int64_t T;
+  double *mc_out;        /* T x (d + 1) */
+  double *loglik;        /* em_iterations + 1 doubles on the device, or NULL */
+  double *objective;     /* gv_iterations + 1 doubles on the device, or NULL */
+} kwy_convert_gv_job;
+int kwy_convert_mcep_gv_batch_dev(kwy_ctx *ctx, const kwy_convert_gv_job *jobs, int count, int d, int M,
+                                  const double *model, int em_iterations, int gv_offset, const double *gv_mean,
+                                  const double *gv_var, double weight, int gv_iterations, int32_t *status);
 /* Re-alignment of the training set (an addition: the reference aligns once): the same batched conversion, with the
  * converted c1..cd of every job stored straight into columns 2.. of its DTW feature rows (kwy_align_features_dev's
  * layout, rows d + 2 doubles apart) -- columns 0 and 1, the source's own power and voicing terms, are not touched, and no

@@ -208,6 +208,16 @@ SIGNATURES = {
     'kwy_convert_mcep_em_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_vp]),
     'kwy_convert_mcep_em_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int]),
     'kwy_moments_accumulate_dev': (c_int, [c_vp, c_vp, c_int, c_vp]),
+    'kwy_gv_ascent': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_int, c_vp]),
+    'kwy_gv_ascent_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_int, c_vp]),
+    'kwy_gv_stats_from_moments': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'kwy_gv_stats_from_moments_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
+    'kwy_gmm_mlpg_gv': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_dbl,
+                                c_int, c_vp, c_vp, c_vp, c_vp]),
+    'kwy_convert_mcep_gv_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_int,
+                                        c_vp, c_vp, c_vp, c_vp]),
+    'kwy_convert_mcep_gv_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_dbl,
+                                              c_int, c_vp]),
 }
 
 MISSING = []
@@ -270,6 +280,10 @@ ConvertJob = _job_struct('ConvertJob', 'kwy_convert_job: one utterance of a batc
                          [('mc', c_vp), ('T', c_i64), ('mc_out', c_vp)])
 ConvertEmJob = _job_struct('ConvertEmJob', 'kwy_convert_em_job: one utterance of a batched EM conversion',
                            [('mc', c_vp), ('T', c_i64), ('mc_out', c_vp), ('loglik', c_vp)])
+ConvertGvJob = _job_struct('ConvertGvJob', 'kwy_convert_gv_job: one utterance of a batched conversion with the GV ascent',
+                           [('mc', c_vp), ('T', c_i64), ('mc_out', c_vp), ('loglik', c_vp), ('objective', c_vp)])
+GvAscentJob = _job_struct('GvAscentJob', 'kwy_gv_ascent_job: one utterance of the GV ascent on caller records',
+                          [('band', c_vp), ('offset', c_vp), ('y', c_vp), ('T', c_i64), ('objective', c_vp)])
 RealignJob = _job_struct('RealignJob', 'kwy_realign_job: one source side of a re-alignment pass',
                          [('mc', c_vp), ('T', c_i64), ('feat', c_vp)])
 TrimJob = _job_struct('TrimJob', 'kwy_trim_job', [('sp', c_vp), ('T', c_i64), ('n_out', c_vp)])

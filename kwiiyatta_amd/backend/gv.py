@@ -7,6 +7,9 @@ d) and the filter of Toda et al. (2007) that stretches each converted trajectory
 
 with base = x (the plain filter: at strength 1 the variance of y[:, d] is gv_d) or base = the differential conversion
 of the same input.  The reference has no counterpart: it synthesises the converter's output as it is.
+`gv_statistics` and `ascent` serve the parameter generation that considers the global variance instead of filtering
+afterwards (kwy_gv_ascent, include/kwy.h: conjugate-gradient steps on the joint likelihood of a trajectory and of its
+global variance; the conversion with it behind is backend.mlpg.MLPG(gv=...)).
 Inputs follow the other shims' contract: float64, C-contiguous (the same ValueError otherwise)."""
 import numpy as np
 
@@ -57,6 +60,69 @@ def gv_from_moments(moments, ctx=None):
     out = np.empty(moments.shape[1])
     _lib.check(ctx, lib.kwy_gv_from_moments(ctx.handle, ptr(moments), len(moments), moments.shape[1], ptr(out)))
     return out
+
+
+def gv_statistics(moments, ctx=None):
+    """(mean, var): per column the mean and the variance (ddof 0), over the matrices that have frames, of M2 / n -- the
+    statistics of the GV ascent (kwy_gv_ascent, include/kwy.h).  The mean is gv_from_moments' value bit for bit; with
+    fewer than two such matrices the variance is 0.  ValueError when no matrix has frames"""
+    moments = _lib.as_f64(moments)
+    if moments.ndim != 3 or moments.shape[2] != 3 or not 1 <= moments.shape[1] <= MAX_COLS:
+        raise ValueError('moments must be a (count, cols, 3) array')
+    if len(moments) == 0 or not (moments[:, 0, 0] > 0).any():
+        raise ValueError('global variance statistics: no utterance has frames')
+    ctx = ctx or _lib.default_context()
+    mean, var = np.empty(moments.shape[1]), np.empty(moments.shape[1])
+    _lib.check(ctx, lib.kwy_gv_stats_from_moments(ctx.handle, ptr(moments), len(moments), moments.shape[1], ptr(mean),
+                                                  ptr(var)))
+    return mean, var
+
+
+ASCENT_MAX = 256     # KWY_MLPG_GV_MAX (include/kwy.h)
+
+
+def ascent_arguments(mean, var, iterations, weight, cols=None):
+    """(mean, var, iterations, weight) checked: ValueError for a count outside [0, ASCENT_MAX], a weight that is not
+    positive and finite, or statistics of the wrong shape"""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or \
+            not 0 <= iterations <= ASCENT_MAX:
+        raise ValueError(f'GV ascent: iterations must be an integer within [0, {ASCENT_MAX}], not {iterations!r}')
+    weight = float(weight)
+    if not (weight > 0.0 and np.isfinite(weight)):
+        raise ValueError(f'GV ascent: weight {weight!r} must be positive and finite')
+    mean, var = _lib.as_f64(mean), _lib.as_f64(var)
+    if mean.ndim != 1 or mean.shape != var.shape or (cols is not None and mean.shape != (cols,)):
+        raise ValueError(f'GV ascent: mean and var must hold one value per column'
+                         f'{"" if cols is None else f" ({cols})"}, not shapes {mean.shape} and {var.shape}')
+    return mean, var, int(iterations), weight
+
+
+def ascent(bands, y, mean, var, iterations, offset=None, weight=1.0, ctx=None):
+    """the GV ascent on caller data (kwy_gv_ascent): bands (T, d, 4) records {P[t][t], P[t][t-1], P[t][t-2], b[t]},
+    y (T, d) the solution of P y = b, offset (T, d) or None.  Returns (y_N, [Q_0 .. Q_N], status); bands, y and offset
+    may be lists of utterances: one call, lists back"""
+    single = not isinstance(y, (list, tuple))
+    ys = [_matrix(a) for a in ([y] if single else y)]
+    bs = [_lib.as_f64(b) for b in ([bands] if single else bands)]
+    offs = [None] * len(ys) if offset is None else [_matrix(o) for o in ([offset] if single else offset)]
+    if not ys:
+        return []
+    d = ys[0].shape[1]
+    mean, var, iterations, weight = ascent_arguments(mean, var, iterations, weight, d)
+    if len(bs) != len(ys) or len(offs) != len(ys) or any(
+            a.shape[1] != d or len(a) < 1 or b.shape != a.shape + (4,) or (o is not None and o.shape != a.shape)
+            for a, b, o in zip(ys, bs, offs)):
+        raise ValueError('GV ascent: y (T, d), bands (T, d, 4) and offset (T, d) must agree, T >= 1')
+    ctx = ctx or _lib.default_context()
+    outs = [a.copy() for a in ys]
+    objs = [np.empty(iterations + 1) for _ in ys]
+    status = np.zeros(len(ys), dtype=np.int32)
+    jobs = _lib.job_array(_lib.GvAscentJob, [(b.ctypes.data, None if o is None else o.ctypes.data, a.ctypes.data, len(a),
+                                              q.ctypes.data) for b, o, a, q in zip(bs, offs, outs, objs)])
+    _lib.check(ctx, lib.kwy_gv_ascent(ctx.handle, jobs, len(ys), d, ptr(mean), ptr(var), weight, iterations,
+                                      ptr(status)))
+    res = [(a, q.tolist(), int(s)) for a, q, s in zip(outs, objs, status)]
+    return res[0] if single else res
 
 
 def _raise_status(status):
@@ -119,6 +185,26 @@ def postfilter_batch_dev(ctx, xs, moments, gv, strength, outs, bases=None, first
     _lib.check(ctx, lib.kwy_gv_postfilter_batch_dev(ctx.handle, jobs, len(xs), moments.shape[1], int(first_col),
                                                     gv.data_ptr(), _strength(strength),
                                                     None if status is None else status.data_ptr()))
+
+
+def gv_statistics_dev(ctx, moments, mean, var):
+    """moments: (count, cols, 3) device tensor; mean, var: cols doubles each on the device, written"""
+    _lib.check(ctx, lib.kwy_gv_stats_from_moments_dev(ctx.handle, moments.data_ptr(), moments.shape[0], moments.shape[1],
+                                                      mean.data_ptr(), var.data_ptr()))
+
+
+def ascent_batch_dev(ctx, bands, ys, mean, var, iterations, offsets=None, weight=1.0, objectives=None, status=None):
+    """bands (T, d, 4) / ys (T, d, in place) / offsets (T, d or None) / objectives (iterations + 1 doubles or None):
+    device tensors per utterance; mean, var: d doubles on the device; status: an int32 device tensor with a word per
+    utterance, or None"""
+    n = len(ys)
+    offsets = offsets or [None] * n
+    objectives = objectives or [None] * n
+    jobs = _lib.job_array(_lib.GvAscentJob, [(b, o, y, y.shape[0], q)
+                                             for b, o, y, q in zip(bands, offsets, ys, objectives)])
+    _lib.check(ctx, lib.kwy_gv_ascent_batch_dev(ctx.handle, jobs, n, ys[0].shape[1] if n else 1, mean.data_ptr(),
+                                                var.data_ptr(), float(weight), int(iterations),
+                                                None if status is None else status.data_ptr()))
 
 
 def check_status(status):

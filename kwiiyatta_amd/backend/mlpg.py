@@ -8,6 +8,7 @@ from .. import _lib
 from .._lib import lib, ptr
 
 EM_MAX = 16      # KWY_MLPG_EM_MAX (include/kwy.h)
+GV_MAX = 256     # KWY_MLPG_GV_MAX
 
 DELTA_WINDOWS = [
     (0, 0, np.array([1.0])),
@@ -49,9 +50,17 @@ class MLPG:
     em=None: one arg-max mixture per frame and a single trajectory solve, what nnmnkwii does.  em=N, an integer within
     [0, EM_MAX] (an addition): every mixture weighs in with its posterior, and the posteriors are re-estimated N times
     from the source frame and the trajectory solved last (kwy_gmm_mlpg_em, include/kwy.h); `loglik_` then holds
-    L_0 .. L_N of the last `transform`, which never decrease."""
+    L_0 .. L_N of the last `transform`, which never decrease.
 
-    def __init__(self, gmm, windows=None, swap=False, diff=False, ctx=None, em=None):
+    gv=(mean, var) (an addition; static_dim values each: mean and variance over the training utterances of the target's
+    per-utterance variance of every coefficient) with gv_iterations=N, an integer within [0, GV_MAX]: parameter
+    generation considering the global variance (kwy_gmm_mlpg_gv) -- after the posteriors are fixed (arg-max, or em=),
+    N conjugate-gradient steps on the joint objective from the linearly scaled track; gv_weight > 0 weighs the GV term.
+    With diff=True the variance is taken of trajectory + source statics.  `objective_` then holds Q_0 .. Q_N of the
+    last `transform`, which never decrease."""
+
+    def __init__(self, gmm, windows=None, swap=False, diff=False, ctx=None, em=None, gv=None, gv_iterations=None,
+                 gv_weight=1.0):
         if windows is None:
             windows = DELTA_WINDOWS
         self.framewise = _is_static_window(windows)     # DELTA_WINDOWS[0:1]: conversion without trajectory smoothing
@@ -71,6 +80,18 @@ class MLPG:
             em = int(em)
         self.em = em
         self.loglik_ = None
+        self.objective_ = None
+        if (gv is None) != (gv_iterations is None):
+            raise ValueError('gv=(mean, var) and gv_iterations go together')
+        if gv is not None:
+            from . import gv as gvgen
+            if self.framewise:
+                raise ValueError('gv needs the trajectory solve: it does not go with the static window alone '
+                                 '(mlpg=False)')
+            if len(gv) != 2:
+                raise ValueError('gv must be the pair (mean, var)')
+            gv = gvgen.ascent_arguments(gv[0], gv[1], gv_iterations, gv_weight)
+        self.gv = gv
         assert gmm.covariance_type == 'full'
         self.weights = np.ascontiguousarray(gmm.weights_, dtype=np.float64)
         self.means = np.ascontiguousarray(gmm.means_, dtype=np.float64)
@@ -103,8 +124,25 @@ class MLPG:
         if src.shape[1] not in (d, 3 * d):
             raise ValueError(f'feature dimension {src.shape[1]} does not match the GMM ({d})')
         x = np.ascontiguousarray(src[:, :d])
+        if self.gv is not None and self.gv[0].shape != (d,):
+            raise ValueError(f'gv statistics hold {self.gv[0].shape[0]} values, the GMM has {d} static dimensions')
         ctx = self.ctx or _lib.default_context()
         y = np.empty((x.shape[0], d))
+        if self.gv is not None:
+            mean, var, iterations, weight = self.gv
+            em = -1 if self.em is None else self.em
+            loglik, objective = np.empty(max(em, 0) + 1), np.empty(iterations + 1)
+            status = np.zeros(1, dtype=np.int32)
+            _lib.check(ctx, lib.kwy_gmm_mlpg_gv(ctx.handle, ptr(x), x.shape[0], d, self.num_mixtures, ptr(self.weights),
+                                                ptr(self.means), ptr(self.covs), int(self.diff), em, int(self.diff),
+                                                ptr(mean), ptr(var), weight, iterations, ptr(y),
+                                                ptr(loglik) if em >= 0 else None, ptr(objective), ptr(status)))
+            if status[0]:
+                raise ValueError(f'GV ascent: {int(status[0])} coefficient(s) were left at the maximum-likelihood track: '
+                                 f'their variance is not finite, or a statistic is not finite or not positive there')
+            self.loglik_ = loglik.tolist() if em >= 0 else None
+            self.objective_ = objective.tolist()
+            return y
         if self.em is not None:
             loglik = np.empty(self.em + 1)
             _lib.check(ctx, lib.kwy_gmm_mlpg_em(ctx.handle, ptr(x), x.shape[0], d, self.num_mixtures, ptr(self.weights),

@@ -178,6 +178,30 @@ MLPG_EM_OPTION = ('--mlpg-em', dict(type=mlpg_em, default=None, metavar='N',
                                          'reference does)'))
 
 
+MLPG_GV_RANGE = (0, 256)     # KWY_MLPG_GV_MAX (include/kwy.h)
+
+
+def mlpg_gv(text):
+    """--mlpg-gv: the conjugate-gradient steps of the GV-considering parameter generation, an integer within [0, 256]"""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid iteration count: {text!r}') from None
+    lo, hi = MLPG_GV_RANGE
+    if not lo <= n <= hi:
+        raise argparse.ArgumentTypeError(f'{text} is outside [{lo}, {hi}]')
+    return n
+
+
+MLPG_GV_OPTION = ('--mlpg-gv', dict(type=mlpg_gv, default=None, metavar='N',
+                                    help='Parameter generation considering the global variance: maximise the '
+                                         'likelihood of the trajectory and of its global variance jointly (Toda et '
+                                         'al. 2007) by N conjugate-gradient steps from the linearly scaled '
+                                         'trajectory; N within [0, 256], 0: that scaled trajectory (what --gv 1 '
+                                         'gives).  Uses the global-variance statistics of the converter model; goes '
+                                         'with --mlpg-em, not with --gv or --ms'))
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -215,12 +239,21 @@ class Config:
     def add_mlpg_em_argument(self):
         self._declare((MLPG_EM_OPTION,))
 
+    def add_mlpg_gv_argument(self):
+        self._declare((MLPG_GV_OPTION,))
+
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)
 
     def parse_args(self, args=None):
         """`args` come BEFORE the process arguments, which therefore win (the reference's order)"""
         self.parser.parse_args(args=list(args or []) + sys.argv[1:], namespace=self)
+        if getattr(self, 'mlpg_gv', None) is not None:
+            if getattr(self, 'gv', 0.0) > 0:
+                self.parser.error('--mlpg-gv does not go with --gv: the postfilter would repair the same variance twice')
+            if getattr(self, 'ms', 0.0) > 0:
+                self.parser.error('--mlpg-gv does not go with --ms: composing it with the modulation-spectrum filter is '
+                                  'left for later')
 
     # ---- factories --------------------------------------------------------------------------------------
     def create_analyzer(self, *args, Analyzer=None, **kwargs):
@@ -302,10 +335,12 @@ class Config:
         sides = [k.WavFileDataset(self.source_path, Analyzer=source), k.WavFileDataset(self.target_path, Analyzer=analyze)]
         return k.align(*sides)
 
-    def train_converter(self, f0_stats=False, gv_stats=False, ms_stats=False, **kwargs):
+    def train_converter(self, f0_stats=False, gv_stats=False, ms_stats=False, gv_var=False, **kwargs):
         """f0_stats=True / gv_stats=True / ms_stats=True: training also computes the f0 statistics / the target's global
         variance / the modulation-spectrum statistics at --ms-length (and the model file keeps them); a loaded model
-        without them is a parser error"""
+        without them is a parser error.  gv_var=True (--mlpg-gv): gv_stats, and a loaded model must also hold the
+        variance of the global variance"""
+        gv_stats = gv_stats or gv_var
         converter = self.create_converter(**kwargs)
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
@@ -327,6 +362,9 @@ class Config:
             if gv_stats and converter.gv_stats is None:
                 self.parser.error(f'{model}: the converter model has no global variance statistics; retrain it with '
                                   f'--gv (a new --converter-model file)')
+            if gv_var and converter.gv_var is None:
+                self.parser.error(f'{model}: the converter model has no variance of the global variance; retrain it '
+                                  f'with --mlpg-gv (a new --converter-model file)')
             if ms_stats and converter.ms_stats is None:
                 self.parser.error(f'{model}: the converter model has no modulation spectrum statistics; retrain it '
                                   f'with --ms (a new --converter-model file)')

@@ -45,7 +45,7 @@ OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
 def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-            formant_shift=0.0, mlpg_em=None):
+            formant_shift=0.0, mlpg_em=None, mlpg_gv=None):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
@@ -54,11 +54,14 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
     pitch-shifted sources (converter.source_f0_rate != 1) gets the file's waveform shifted the same way.
     formant_shift != 0 (semitones): the converted envelope of the synthesised output warped along frequency by
     2 ** (formant_shift / 12) (Feature.shift_formants); the differential output ignores it.
-    mlpg_em=N: the EM trajectory conversion with N re-estimations (converter.convert(em=N), either output)."""
+    mlpg_em=N: the EM trajectory conversion with N re-estimations (converter.convert(em=N), either output).
+    mlpg_gv=N: parameter generation considering the global variance, N steps (converter.convert(mlpg_gv=N), either
+    output)."""
     import kwiiyatta_amd as k
     source = analyze_source(conf, converter, src_path)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
-                                  **(dict(ms=ms) if ms > 0 else {}), **({} if mlpg_em is None else dict(em=mlpg_em)))
+                                  **(dict(ms=ms) if ms > 0 else {}), **({} if mlpg_em is None else dict(em=mlpg_em)),
+                                  **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)))
     if diffvc:
         return k.apply_mlsa_filter(source, converted)
     rendered = k.feature(source)
@@ -112,7 +115,7 @@ class _Pcm16:
 
 
 def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-                        formant_shift=0.0, mlpg_em=None):
+                        formant_shift=0.0, mlpg_em=None, mlpg_gv=None):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -126,9 +129,13 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     longer than the converter's ms_length goes through `convert`, which names it.
     formant_shift != 0: the .synth.wav outputs from the warped converted envelopes (as `convert` does), warped on the
     device (corpus.convert_batch(formant_ratio=...)).
-    mlpg_em=N: both outputs from EM trajectory conversions (as `convert` does; corpus.convert_batch(mlpg_em=N))."""
+    mlpg_em=N: both outputs from EM trajectory conversions (as `convert` does; corpus.convert_batch(mlpg_em=N)).
+    mlpg_gv=N: both outputs from GV-considering parameter generation (as `convert` does;
+    corpus.convert_batch(mlpg_gv=N))."""
     import kwiiyatta_amd as k
     from . import corpus
+    if mlpg_gv is not None:
+        converter.gv_ascent_statistics()          # (raises before any file is read)
     from ._lib import lib
     from .converter.delta import DeltaFeatureConverter
     out, batch = {}, []
@@ -143,7 +150,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                 (period is not None and a.frame_period != period):
             out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
                                        transpose_key=transpose_key, gv=gv, ms=ms, formant_shift=formant_shift,
-                                       mlpg_em=mlpg_em)
+                                       mlpg_em=mlpg_em, mlpg_gv=mlpg_gv)
         else:
             batch.append((path, a))
     if batch:
@@ -159,7 +166,9 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                                    **(dict(ms_stats=converter.ms_stats, ms_length=converter.ms_length, ms_strength=ms)
                                       if ms > 0 else {}),
                                    **(dict(formant_ratio=2.0 ** (formant_shift / 12)) if formant_shift != 0 else {}),
-                                   **({} if mlpg_em is None else dict(mlpg_em=mlpg_em)))
+                                   **({} if mlpg_em is None else dict(mlpg_em=mlpg_em)),
+                                   **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv, gv_stats=converter.gv_stats,
+                                                                      gv_var=converter.gv_var)))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -190,14 +199,15 @@ def main():
     conf.add_gv_argument()
     conf.add_ms_argument()
     conf.add_mlpg_em_argument()
+    conf.add_mlpg_gv_argument()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
-                                     ms_stats=conf.ms > 0)
+                                     ms_stats=conf.ms > 0, **(dict(gv_var=True) if conf.mlpg_gv is not None else {}))
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, formant_shift=conf.formant_shift)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
                                   diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                                  **pitch) if conf.batch else {}
+                                  mlpg_gv=conf.mlpg_gv, **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -211,7 +221,7 @@ def main():
                 batched[wav_path, differential].save(out)
             else:
                 convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                        **({} if differential else pitch)).save(out)
+                        mlpg_gv=conf.mlpg_gv, **({} if differential else pitch)).save(out)
 
 
 if __name__ == '__main__':

@@ -20,10 +20,15 @@ class GMMFeatureConverter(abc.FeatureConverter):
     def _train(self, dataarray, **kwargs):
         self.gmm.fit(dataarray, **kwargs)
 
-    def convert(self, feature, mlpg=True, diff=False, em=None):
+    def convert(self, feature, mlpg=True, diff=False, em=None, gv_stats=None, gv_iterations=None, gv_weight=1.0):
         # mlpg=False: the static window alone -- every frame converted on its own (posterior-weighted conditional mean)
         # em=N: EM trajectory conversion over soft mixture posteriors, N re-estimations (backend.mlpg.MLPG); the keyword
         # is handed on only when set
+        # gv_stats=(mean, var) with gv_iterations=N: the GV ascent behind the conversion (MLPG(gv=...)); `mlpg_`
+        # keeps the MLPG object of the last conversion (its loglik_ and objective_)
         windows = delta.DELTA_WINDOWS if mlpg else delta.DELTA_WINDOWS[0:1]
         options = {} if em is None else dict(em=em)
-        return MLPG(self.gmm, windows=windows, diff=diff, **options).transform(feature)
+        if gv_stats is not None or gv_iterations is not None:
+            options.update(gv=gv_stats, gv_iterations=gv_iterations, gv_weight=gv_weight)
+        self.mlpg_ = MLPG(self.gmm, windows=windows, diff=diff, **options)
+        return self.mlpg_.transform(feature)

@@ -76,6 +76,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         self.mcep_fs = mcep_fs
         self.f0_stats = None
         self.gv_stats = None
+        self.gv_var = None
         self.ms_stats, self.ms_length = None, None
         # the pitch ratio the source waveforms were (and are to be) shifted by before analysis (backend.pitch): set by
         # whoever prepares the training set (Config.train_converter), kept in the model file; 1: no shift
@@ -88,7 +89,9 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
               **kwargs):
         """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`).
         gv_stats=True: also the target side's global variance (`gv_stats`, order + 1 values: per coefficient the mean
-        over the training utterances of its variance within the utterance; used by `convert(gv=...)`).
+        over the training utterances of its variance within the utterance; used by `convert(gv=...)`) and `gv_var`, the
+        variance over the training utterances of the same quantity (0 everywhere when trained on one utterance; used,
+        with `gv_stats`, by `convert(mlpg_gv=...)`).
         align_iterations=N > 0: iterative re-alignment of the training set, see `_train_realigned`
         ms_stats=True: also the modulation-spectrum statistics (`ms_stats` = (G, N), each (order + 1, ms_length / 2 + 1,
         3): per coefficient and modulation-frequency bin the count, mean and M2 over the training utterances of the log
@@ -114,13 +117,15 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 raise ValueError('f0 statistics: no training files')
             self.f0_stats = f0map.stats_from_moments(f0map.merge_moments(f0map.logf0_moments(source)),
                                                      f0map.merge_moments(f0map.logf0_moments(target)))
-        self.gv_stats = None
+        self.gv_stats, self.gv_var = None, None
         if gv_stats:
             from ..backend import gv as gvfilter
             mats = _target_mel_cepstra(dataset, keys, self.order, self.fs)
             if not mats:
                 raise ValueError('global variance statistics: no training files')
-            self.gv_stats = gvfilter.gv_from_moments(gvfilter.column_moments(mats))
+            moments = gvfilter.column_moments(mats)
+            self.gv_stats = gvfilter.gv_from_moments(moments)
+            self.gv_var = gvfilter.gv_statistics(moments)[1]
         self.ms_stats, self.ms_length = None, None
         if ms_stats:
             self._train_ms(dataset, keys, ms_length)
@@ -257,6 +262,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
             if self.gv_stats is not None:
                 extra['gv_stats'] = np.array(self.gv_stats, dtype=np.float64)
+            if self.gv_var is not None:
+                extra['gv_var'] = np.array(self.gv_var, dtype=np.float64)
             if self.ms_stats is not None:
                 extra.update(ms_stats_g=np.array(self.ms_stats[0], dtype=np.float64),
                              ms_stats_n=np.array(self.ms_stats[1], dtype=np.float64), ms_length=int(self.ms_length))
@@ -291,6 +298,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             gmm.converged_ = True
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
             self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None
+            self.gv_var = np.array(z['gv_var'], dtype=np.float64) if 'gv_var' in z.files else None
             has_ms = 'ms_stats_g' in z.files
             self.ms_stats = tuple(np.array(z[n], dtype=np.float64)
                                   for n in ('ms_stats_g', 'ms_stats_n')) if has_ms else None
@@ -303,7 +311,19 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                                   for n, v in zip(rows, mcd)]
         return self
 
-    def convert(self, mel_cepstrum, gv=0.0, ms=0.0, **kwargs):
+    def gv_ascent_statistics(self):
+        """(mean, var) of c1..cN for `convert(mlpg_gv=...)`; ValueError when the converter has none, or when a variance
+        is not positive (a converter trained on one utterance)"""
+        if self.gv_stats is None or self.gv_var is None:
+            raise ValueError('mlpg_gv: the converter has no global-variance statistics with their variance (retrain it '
+                             'with gv_stats=True on two or more utterances)')
+        mean, var = (np.ascontiguousarray(a[1:], dtype=np.float64) for a in (self.gv_stats, self.gv_var))
+        if not (var > 0).all():
+            raise ValueError('mlpg_gv: the variance of the global variance is not positive everywhere (retrain the '
+                             'converter with gv_stats=True on two or more utterances)')
+        return mean, var
+
+    def convert(self, mel_cepstrum, gv=0.0, ms=0.0, mlpg_gv=None, gv_weight=1.0, **kwargs):
         """a MelCepstrum at the converter's sampling rate: c0 of the input, c1..cN converted.
         gv > 0 (a strength within [0, 1]; needs `gv_stats`): the converted c1..cN through the global-variance
         postfilter, each trajectory stretched about its own mean towards the target's variance.  With diff=True the
@@ -317,9 +337,23 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         soft mixture posteriors instead of one arg-max mixture per frame, N re-estimations of the posteriors
         (backend.mlpg.MLPG).  It composes with diff, gv and ms as the arg-max conversion does -- with diff=True the
         non-differential conversion the filters look at is an EM conversion too.  `ms_stats` are learnt from ARG-MAX
-        conversions of the training set (as re-alignment uses them), whatever `em` is given here."""
+        conversions of the training set (as re-alignment uses them), whatever `em` is given here.
+        mlpg_gv=N (an integer within [0, 256]; needs `gv_stats` and `gv_var`): parameter generation considering the
+        global variance instead of the postfilter -- N conjugate-gradient steps on the joint objective of trajectory
+        and GV likelihood, from the linearly scaled track (backend.mlpg.MLPG(gv=...)); gv_weight > 0 weighs the GV
+        term.  c0 is kept; with diff=True the variance is that of the converted spectrum (differential + source).  It
+        goes with em=N, and with neither gv > 0 (the same repair twice) nor ms > 0 (not composed yet)."""
         if mel_cepstrum.order != self.order:
             raise ValueError(f'order is expected to {self.order!s} but {mel_cepstrum.order!s}')
+        if mlpg_gv is not None:
+            if gv > 0:
+                raise ValueError('mlpg_gv does not go with gv > 0: the postfilter would repair the same variance twice')
+            if ms > 0:
+                raise ValueError('mlpg_gv does not go with ms > 0: composing it with the modulation-spectrum filter is '
+                                 'left for later')
+            from ..backend import gv as gvgen
+            mean, var, mlpg_gv, gv_weight = gvgen.ascent_arguments(*self.gv_ascent_statistics(), mlpg_gv, gv_weight)
+            kwargs = dict(kwargs, gv_stats=(mean, var), gv_iterations=mlpg_gv, gv_weight=gv_weight)
         if not 0.0 <= gv <= 1.0:
             raise ValueError(f'global variance: strength {gv!r} is outside [0, 1]')
         if gv > 0 and self.gv_stats is None:

@@ -478,9 +478,11 @@ class EvalWave(TrainWave):
     caller's tensors.  `frame_period` is accepted and ignored, as in TrainWave."""
 
     def measure(self, pads, gmm, model, tot, first, frames='speech', gv=None, gv_strength=0.0, f0_stats=None,
-                transpose_key=0.0, per_frame=False, mlpg_em=None):
+                transpose_key=0.0, per_frame=False, mlpg_em=None, gvgen=None):
         """tot: the _EvalTotals of the corpus; gv / f0_stats: device tensors (order + 1 values / 4 values) or None;
-        mlpg_em: None, or the re-estimations of the EM trajectory conversion (kwy_convert_mcep_em_batch_dev)"""
+        mlpg_em: None, or the re-estimations of the EM trajectory conversion (kwy_convert_mcep_em_batch_dev);
+        gvgen: None, or `_gvgen_on_device`'s options of the GV ascent behind the conversion
+        (kwy_convert_mcep_gv_batch_dev; its status words go where the postfilter's would, the two exclude each other)"""
         from .backend import distortion as dist
         a = self.align(pads)
         Tp = a.inputs.Tp
@@ -501,8 +503,9 @@ class EvalWave(TrainWave):
             own = Ragged(keep[0::2])                    # the sources' own time axes, end to end
             self.mc_conv = torch.empty((own.total, cols), **f64)
             conv = own.views(self.mc_conv)
-            chk(_convert_mcep_batch(h, _convert_jobs([(src_mc[k], keep[2 * k], conv[k]) for k in range(n)], mlpg_em),
-                                    n, order, gmm.M, model, mlpg_em))
+            chk(_convert_mcep_batch(h, _convert_jobs([(src_mc[k], keep[2 * k], conv[k]) for k in range(n)], mlpg_em, gvgen),
+                                    n, order, gmm.M, model, mlpg_em, gvgen, 0,
+                                    tot.gv_status[first:first + n] if gvgen is not None else None))
             if gv is not None:
                 self.gv_moments = torch.empty((n, cols, 3), **f64)
                 chk(lib.kwy_column_moments_batch_dev(h, J(_lib.GvMatrix, [(conv[k], keep[2 * k]) for k in range(n)]), n,
@@ -704,20 +707,62 @@ def _mlpg_em(mlpg_em):
     return int(mlpg_em)
 
 
-def _convert_jobs(rows, mlpg_em=None):
+def _convert_jobs(rows, mlpg_em=None, gvgen=None):
     """the jobs of a batched conversion from (mc, T, mc_out) rows: kwy_convert_job, or with mlpg_em set
-    kwy_convert_em_job (no log-likelihoods asked for)"""
+    kwy_convert_em_job (no log-likelihoods asked for), or with gvgen set kwy_convert_gv_job (no objective either)"""
+    if gvgen is not None:
+        return _lib.job_array(_lib.ConvertGvJob, [tuple(row) + (None, None) for row in rows])
     if mlpg_em is None:
         return _lib.job_array(_lib.ConvertJob, rows)
     return _lib.job_array(_lib.ConvertEmJob, [tuple(row) + (None,) for row in rows])
 
 
-def _convert_mcep_batch(handle, jobs, n, order, M, model, mlpg_em=None):
-    """kwy_convert_mcep_batch_dev over `_convert_jobs(rows, mlpg_em)`, or kwy_convert_mcep_em_batch_dev when mlpg_em is
-    set: -> the return code"""
+def _convert_mcep_batch(handle, jobs, n, order, M, model, mlpg_em=None, gvgen=None, offset=0, status=None):
+    """kwy_convert_mcep_batch_dev over `_convert_jobs(rows, mlpg_em, gvgen)`, kwy_convert_mcep_em_batch_dev when mlpg_em
+    is set, kwy_convert_mcep_gv_batch_dev when gvgen (`_gvgen_on_device`) is: -> the return code.  offset: 1 for a
+    model prepared with diff = 1 (the variance is that of trajectory + source); status: n int32 words on the device"""
+    if gvgen is not None:
+        return lib.kwy_convert_mcep_gv_batch_dev(handle, jobs, n, order, M, _p(model), -1 if mlpg_em is None else mlpg_em,
+                                                 int(offset), _p(gvgen['mean']), _p(gvgen['var']), gvgen['weight'],
+                                                 gvgen['iterations'], None if status is None else _p(status))
     if mlpg_em is None:
         return lib.kwy_convert_mcep_batch_dev(handle, jobs, n, order, M, _p(model))
     return lib.kwy_convert_mcep_em_batch_dev(handle, jobs, n, order, M, _p(model), mlpg_em)
+
+
+def _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order, dev, on=True):
+    """the options of the GV-considering parameter generation, checked before anything is put on the device: -> None
+    (mlpg_gv is None, or on=False: no conversion), or dict(iterations, weight, mean, var) with the statistics of
+    c1..cN (`order` values each) as device tensors.  gv_stats / gv_var: the order + 1 values of
+    MelCepstrumFeatureConverter.gv_stats / .gv_var"""
+    if mlpg_gv is None or not on:
+        return None
+    from .backend import gv as gvgen
+    if gv_strength:
+        raise ValueError('mlpg_gv does not go with gv_strength > 0: the postfilter would repair the same variance twice')
+    if ms_strength:
+        raise ValueError('mlpg_gv does not go with ms_strength > 0: composing it with the modulation-spectrum filter is '
+                         'left for later')
+    if gv_stats is None or gv_var is None:
+        raise ValueError('mlpg_gv needs gv_stats and gv_var (retrain the converter with gv_stats=True on two or more '
+                         'utterances)')
+    host = [v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64) for v in (gv_stats, gv_var)]
+    if any(v.shape != (order + 1,) for v in host):
+        raise ValueError(f'mlpg_gv: gv_stats and gv_var must be {order + 1} float64 values each')
+    if not (host[1][1:] > 0).all():
+        raise ValueError('mlpg_gv: the variance of the global variance is not positive everywhere (retrain the converter '
+                         'with gv_stats=True on two or more utterances)')
+    mean, var, iterations, weight = gvgen.ascent_arguments(np.ascontiguousarray(host[0][1:]),
+                                                           np.ascontiguousarray(host[1][1:]), mlpg_gv, gv_weight, order)
+    return dict(iterations=iterations, weight=weight, mean=to_device(mean, dev, dtype=np.float64).to(dev),
+                var=to_device(var, dev, dtype=np.float64).to(dev))
+
+
+def _check_gvgen_status(status):
+    bad = [i for i, v in enumerate(status.tolist() if hasattr(status, 'tolist') else status) if v]
+    if bad:
+        raise ValueError(f'GV ascent: coefficients of utterance(s) {bad} were left at the maximum-likelihood track: their '
+                         f'variance is not finite, or a statistic is not finite or not positive there')
 
 
 def _gv_on_device(gv_stats, gv_strength, order, dev, on=True):
@@ -795,12 +840,19 @@ class ConvertWave:
     are).  The differential output is not touched.  At 1 no kernel is launched and no buffer added.
     mlpg_em=N (with a GMM; an integer within [0, 16]): both conversions, plain and differential, are EM trajectory
     conversions over soft mixture posteriors with N re-estimations (kwy_convert_mcep_em_batch_dev) instead of one
-    arg-max mixture per frame; everything after them runs as it does otherwise."""
+    arg-max mixture per frame; everything after them runs as it does otherwise.
+    mlpg_gv=N (with a GMM, gv_stats and gv_var; an integer within [0, 256]): both conversions with the GV ascent behind
+    them (kwy_convert_mcep_gv_batch_dev; N conjugate-gradient steps, gv_weight weighs the GV term), the differential
+    one on the variance of differential + source.  `gvgen_status` holds two words per utterance (plain, then
+    differential; non-zero: coefficients left at the maximum-likelihood track).  Not with gv_strength or ms_strength."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
                  f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                 ms_strength=0.0, formant_ratio=1.0, mlpg_em=None):
+                 ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
         self.mlpg_em = _mlpg_em(mlpg_em) if gmm is not None else None
+        self.gvgen = _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order, ls.dev,
+                                      on=gmm is not None)
+        self.gvgen_status = None
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
         self.diff = bool(diff) and gmm is not None
         self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
@@ -869,12 +921,15 @@ class ConvertWave:
                 self.mc_conv = torch.empty((self.rows, order + 1), **f64)
                 self.sp_conv = torch.empty((self.rows, K), **f64)
                 conv, spec = rows.views(self.mc_conv), rows.views(self.sp_conv)
-                self.j_conv = _convert_jobs([(env[i], self.T[i], conv[i]) for i in range(n)], self.mlpg_em)
+                self.j_conv = _convert_jobs([(env[i], self.T[i], conv[i]) for i in range(n)], self.mlpg_em, self.gvgen)
+                if self.gvgen is not None:
+                    self.gvgen_status = torch.zeros(2 * n, dtype=torch.int32, device=dev)
             if self.diff:
                 self.model_diff = gmm.model(diff=True)
                 self.mc_diff = torch.empty((self.rows, order + 1), **f64)
                 self.mc_diff_rows = rows.views(self.mc_diff)
-                self.j_conv_diff = _convert_jobs([(env[i], self.T[i], self.mc_diff_rows[i]) for i in range(n)], self.mlpg_em)
+                self.j_conv_diff = _convert_jobs([(env[i], self.T[i], self.mc_diff_rows[i]) for i in range(n)], self.mlpg_em,
+                                                 self.gvgen)
                 samples = Ragged([v.numel() for v in self.x])         # the filtered inputs: as long as the inputs
                 self.wave_diff_all = torch.empty(samples.total, **f64)
                 self.wave_diff = samples.views(self.wave_diff_all)
@@ -938,7 +993,8 @@ class ConvertWave:
                 chk(lib.kwy_cheaptrick_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs)))
             else:
                 chk(lib.kwy_cheaptrick_mcep_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs), order, self.alpha))
-                chk(_convert_mcep_batch(h, self.j_conv, n, order, self.gmm.M, self.model, self.mlpg_em))
+                chk(_convert_mcep_batch(h, self.j_conv, n, order, self.gmm.M, self.model, self.mlpg_em, self.gvgen, 0,
+                                        None if self.gvgen is None else self.gvgen_status[:n]))
                 cols = order + 1
                 # the differential coefficients take a filter's change of the plain conversion, which the filter of the
                 # plain conversion (in place) then overwrites: the differential conversion in front of the first filter
@@ -972,7 +1028,8 @@ class ConvertWave:
                 # the differential conversion of the same mel-cepstra, its filter over the INPUT waveforms: all
                 # utterances' recursions side by side (one wavefront each)
                 if self.gv_status is None and self.ms_status is None:           # (with a postfilter it ran above)
-                    chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em))
+                    chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em,
+                                            self.gvgen, 1, None if self.gvgen is None else self.gvgen_status[n:]))
                 if not self.defer_mlsa:
                     self.run_mlsa(ls.ctx)
 
@@ -994,7 +1051,7 @@ class ConvertWave:
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
                     f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                    ms_strength=0.0, formant_ratio=1.0, mlpg_em=None):
+                    ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
@@ -1004,13 +1061,16 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     if ms_strength:          # (checked and uploaded once: every wave takes the device tensors as they are)
         ms_stats = _ms_on_device(ms_stats, ms_length, ms_strength, order, ls.dev, on=gmm is not None)
     held, status, map_status, gv_status, ms_status, formant_status, waves_diff = [], [], [], [], [], [], []
+    gvgen_status = []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
                          diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key,
                          **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}),
                          **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}),
                          **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}),
-                         **(dict(mlpg_em=mlpg_em) if mlpg_em is not None else {}))
+                         **(dict(mlpg_em=mlpg_em) if mlpg_em is not None else {}),
+                         **(dict(mlpg_gv=mlpg_gv, gv_stats=gv_stats, gv_var=gv_var, gv_weight=gv_weight)
+                            if mlpg_gv is not None else {}))
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -1024,6 +1084,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             gv_status.append(wv.gv_status)
         if wv.ms_status is not None:
             ms_status.append(wv.ms_status)
+        if wv.gvgen_status is not None:
+            gvgen_status.append(wv.gvgen_status)
         if wv.formant_status is not None:
             formant_status.append(wv.formant_status)
         if diff:
@@ -1069,6 +1131,9 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     if formant_status:
         from .backend import formant
         formant.check_status(words[n_dio + n_map + n_gv + n_ms:], what='wave(s)')
+    if gvgen_status:
+        # (two words per utterance of a wave: the plain conversion's, then the differential one's)
+        _check_gvgen_status(torch.cat([v.cpu()[:len(v) // 2] + v.cpu()[len(v) // 2:] for v in gvgen_status]))
     return ls
 
 
@@ -1166,7 +1231,7 @@ def _pair_uploads(pairs, dev):
 
 def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
                           silence_for=None, pool=None, rng=None, pairs_before=0, driver=None, lockstep=None,
-                          wave_pairs=16, f0_moments=False, gv_moments=False, keep=False):
+                          wave_pairs=16, f0_moments=False, gv_moments=False, keep=False, gv_variance=False):
     """driver='lockstep' (default): waves of `wave_pairs` pairs through the batched entries on two streams
     (`TrainWave`; `lockstep`: a _Lockstep to reuse), rows appended behind a device-side cursor, one read-back per wave;
     driver='streams': the pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
@@ -1176,11 +1241,15 @@ def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_
     gv_moments=True: a further result (after the f0 moments when both are asked for), the numpy vector of order + 1
     values of the target side's global variance -- the column moments of every pair's trimmed target mel-cepstra as
     the matrix path computes them, folded in pair order on the device (train(gv_stats=True)'s statistic).
+    gv_variance=True (with gv_moments=True): one more result behind it, the order + 1 values of the variance over the
+    pairs of the same per-utterance variance (train(gv_stats=True)'s `gv_var`, for mlpg_gv).
     keep=True (lockstep driver): a third result right behind (X, frames), the `TrainCache` with the alignment inputs of
     every pair for `realign_training_matrix`; the default keeps nothing, the waves' buffers go as they went before."""
     driver = driver or ('streams' if pool is not None else 'lockstep')
     if keep and driver != 'lockstep':
         raise ValueError(f"build_training_matrix(keep=True) needs the lockstep driver, not driver={driver!r}")
+    if gv_variance and not gv_moments:
+        raise ValueError('build_training_matrix(gv_variance=True) goes with gv_moments=True')
     moments = _PairMoments(len(pairs), device_index) if f0_moments else None
     gv = _PairGV(len(pairs), order, device_index) if gv_moments else None
     if driver == 'lockstep':
@@ -1191,7 +1260,9 @@ def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_
                                              pool, rng, pairs_before, moments, gv)
     if moments is not None:
         out = out + (moments.merged(),)
-    return out if gv is None else out + (gv.statistic(),)
+    if gv is None:
+        return out
+    return out + (gv.statistic(),) + ((gv.statistic(variance=True),) if gv_variance else ())
 
 
 class _PairMoments:
@@ -1236,15 +1307,21 @@ class _PairGV:
         from .backend import gv as gvfilter
         gvfilter.column_moments_batch_dev(ctx, mats, self.rows[first_pair:first_pair + len(mats)])
 
-    def statistic(self):
-        """(after the streams that ran `add` are synchronised) the global variance, order + 1 values"""
+    def statistic(self, variance=False):
+        """(after the streams that ran `add` are synchronised) the global variance, order + 1 values; variance=True: the
+        variance over the pairs of the per-utterance variance instead (kwy_gv_stats_from_moments_dev)"""
         if len(self.rows) == 0:
             return np.zeros(self.rows.shape[1])
         from .backend import gv as gvfilter
         ctx = _lib.Context(self.dev.index, stream=torch.cuda.current_stream(self.dev).cuda_stream)
         with torch.cuda.device(self.dev):
             out = torch.empty(self.rows.shape[1], dtype=torch.float64, device=self.dev)
-            gvfilter.gv_from_moments_dev(ctx, self.rows, out)
+            if variance:
+                mean = torch.empty_like(out)
+                torch.cuda.current_stream(self.dev).synchronize()
+                gvfilter.gv_statistics_dev(ctx, self.rows, mean, out)
+            else:
+                gvfilter.gv_from_moments_dev(ctx, self.rows, out)
             ctx.sync()            # (for the null stream the context runs a stream of its own, which .cpu() does not wait for)
             return out.cpu().numpy()
 
@@ -1456,7 +1533,7 @@ def _formant_ratio(formant_ratio, driver, pool, who):
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
                   shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
                   gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0,
-                  mlpg_em=None):
+                  mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1475,9 +1552,17 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     synthesis (ConvertWave); the differential outputs are not touched; a row it cannot warp raises ValueError after the
     batch, a ratio outside [0.5, 2] before anything is put on the device.
     mlpg_em (lockstep driver): None, or N within [0, 16]: both outputs from EM trajectory conversions over soft mixture
-    posteriors with N re-estimations (ConvertWave; kwy_convert_mcep_em_batch_dev) instead of the arg-max conversion."""
+    posteriors with N re-estimations (ConvertWave; kwy_convert_mcep_em_batch_dev) instead of the arg-max conversion.
+    mlpg_gv (lockstep driver): None, or N within [0, 256], with gv_stats and gv_var (the converter's): both outputs from
+    conversions with the GV ascent behind them (ConvertWave; kwy_convert_mcep_gv_batch_dev), gv_weight weighing the GV
+    term; it goes with mlpg_em, not with gv_strength or ms_strength; a coefficient it cannot process raises ValueError
+    after the batch."""
     formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'convert_batch')
     mlpg_em = _mlpg_em(mlpg_em)
+    if mlpg_gv is not None and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
+        raise ValueError('convert_batch: mlpg_gv needs the lockstep driver')
+    _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order,
+                     torch.device('cuda', device_index))          # (raises before anything else is put on the device)
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
@@ -1490,7 +1575,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
                         f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
                         ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio,
-                        mlpg_em=mlpg_em)
+                        mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, gv_var=gv_var, gv_weight=gv_weight)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
@@ -1555,7 +1640,7 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
 
 def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_period=5.0, frames='speech', gv_stats=None,
                    gv_strength=0.0, f0_stats=None, transpose_key=0.0, per_frame=False, converter_fs=None, lockstep=None,
-                   wave_pairs=16, mlpg_em=None):
+                   wave_pairs=16, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
     """Objective evaluation of the fitted mixture on parallel pairs, HBM-resident (what
     kwiiyatta_amd.evaluate_voice.evaluate does pair by pair through the Python API): waves of `wave_pairs` pairs
     through `EvalWave`.  pairs: ((x, f0, t), (x, f0, t)) triples as `build_training_matrix` takes them, all at the
@@ -1563,8 +1648,8 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     go through evaluate_voice.evaluate_pair, which resamples.  The silence pads are drawn from numpy's global
     generator in training's order, so under np.random.seed a pair's alignment is the one training would use.
     frames='speech': the distortion over the aligned frames whose target-side binarised power term is set; 'all': over
-    every aligned frame inside both utterances.  gv_stats / gv_strength, f0_stats / transpose_key, mlpg_em: as in
-    `convert_batch`.  Returns (records, total): a dict per pair and one of the pooled figures -- the triples
+    every aligned frame inside both utterances.  gv_stats / gv_strength, f0_stats / transpose_key, mlpg_em, mlpg_gv /
+    gv_var / gv_weight: as in `convert_batch`.  Returns (records, total): a dict per pair and one of the pooled figures -- the triples
     mcd_moments, source_moments, f0_moments ((n, mean, M2); merged by kwy_moments_merge_dev for the total), counts
     (VV, VU, UV, UU), aligned (frames of the alignment) and outside (those beyond either utterance) -- read back once,
     after the last wave.  per_frame=True: a record also holds idx_x, idx_y (frame indices into the trimmed utterances)
@@ -1578,6 +1663,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     gv = _gv_on_device(gv_stats, gv_strength, order, dev)       # (raises before anything else is put on the device)
     stats = _f0_stats_on_device(f0_stats, dev)
     mlpg_em = _mlpg_em(mlpg_em)
+    gvgen = _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, 0.0, order, dev)
     zero = dict(mcd_moments=(0.0, 0.0, 0.0), source_moments=(0.0, 0.0, 0.0), f0_moments=(0.0, 0.0, 0.0),
                 counts=(0, 0, 0, 0), aligned=0, outside=0)
     if not pairs:
@@ -1599,7 +1685,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
         wave = EvalWave(ls, fs, pairs[w0:w0 + wave_pairs], order=order, radius=radius, frame_period=frame_period)
         wave.analyse()
         wave.measure(pads, dg, model, tot, w0, frames=frames, gv=gv, gv_strength=gv_strength, f0_stats=stats,
-                     transpose_key=float(transpose_key), per_frame=per_frame, mlpg_em=mlpg_em)
+                     transpose_key=float(transpose_key), per_frame=per_frame, mlpg_em=mlpg_em, gvgen=gvgen)
         waves.append(wave)
         if not per_frame:
             while len(waves) > 2:
@@ -1613,6 +1699,8 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     if gv is not None:
         from .backend import gv as gvfilter
         gvfilter.check_status(status[:, 3])
+    if gvgen is not None:
+        _check_gvgen_status(status[:, 3])
     if stats is not None or transpose_key != 0:
         from .backend.f0 import check_status
         check_status(status[:, 4], fs)

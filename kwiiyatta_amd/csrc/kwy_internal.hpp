@@ -128,6 +128,23 @@ struct kwy_batch {
   }
 };
 
+// --- GV-considering trajectory generation (kwy_gvgen.hip) ---------------------------------
+// One utterance of the ascent for the conversion entries of kwy_mlpg.hip: the band records of its last solve (a copy:
+// k_mlpg_chunks consumes its own in place), the trajectory (rows ldy doubles apart) and the offset track (rows ldo
+// apart, or null).  kwy_gva_launch takes its scratch (kwy_gva_scratch_bytes) from the arena of the call in progress.
+struct kwy_gva_view {
+  const double *band;
+  const double *offset;
+  double *y;
+  int64_t T;
+  int ldy, ldo;
+  double *objective;       // iterations + 1 doubles on the device, or null
+  int32_t *status;         // one word on the device, or null
+};
+size_t kwy_gva_scratch_bytes(const int64_t *T, int n, int d, int iterations);
+int kwy_gva_launch(kwy_ctx *ctx, const kwy_gva_view *v, int n, int d, const double *gv_mean, const double *gv_var,
+                   double weight, int iterations);
+
 static inline int kwy_ilog2(int n) {
   int l = 0;
   while ((1 << l) < n) ++l;

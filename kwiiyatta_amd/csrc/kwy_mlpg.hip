@@ -983,12 +983,36 @@ static ml_part ml_partition(int64_t T, int d) {
   return pt;
 }
 
+// The ascent of kwy_gvgen.hip behind a conversion (kwy_gmm_mlpg_gv, include/kwy.h): null means none, and then the cores
+// below enqueue exactly what they did before.  The band records are copied after the build of the last solve, because
+// k_mlpg_chunks consumes its own in place (and, in the EM path, the closing E-step overwrites E / Dv).
+struct ml_gv_opts {
+  const double *mean, *var;       // d values each, on the device
+  double weight;
+  int iterations, offset;
+  double *const *objective;       // per utterance of the batch: iterations + 1 doubles on the device or null; or null
+  int32_t *status;                // per utterance of the batch, or null
+};
+static size_t ml_gv_scratch_bytes(const int64_t *Ts, int n, int d, int iterations) {
+  int64_t T = 0;
+  for (int k = 0; k < n; ++k) T += Ts[k];
+  return kwy_pad(sizeof(double) * T * d * 4) + kwy_gva_scratch_bytes(Ts, n, d, iterations);
+}
+static int ml_gv_ascent(kwy_ctx *ctx, const ml_batch &bt, const int64_t *Ts, int d, const double *band2,
+                        const ml_gv_opts &gv) {
+  kwy_gva_view v[KWY_BATCH_MAX];
+  for (int k = 0; k < bt.n; ++k)
+    v[k] = kwy_gva_view{band2 + bt.start[k] * d * 4, gv.offset ? bt.u[k].x : nullptr, bt.u[k].y, Ts[k], bt.ldy, bt.ldx,
+                        gv.objective ? gv.objective[k] : nullptr, gv.status ? gv.status + k : nullptr};
+  return kwy_gva_launch(ctx, v, bt.n, d, gv.mean, gv.var, gv.weight, gv.iterations);
+}
+
 // One conversion call over a batch of utterances: bt.n, bt.ldx / ldy and every u[k].x / y / keep_* filled in by the
 // caller, Ts[k] the utterances' frames.  `prepared`: a model made by kwy_gmm_prepare_dev (then weights / means / covs
 // are unused), or null.
 static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d, int M, const double *weights,
                            const double *means, const double *covs, int diff, int **status_out,
-                           const double *prepared) {
+                           const double *prepared, const ml_gv_opts *gv = nullptr) {
   const int D = 3 * d, n = bt.n;
   int64_t T = 0;
   int Pmax = 1;
@@ -1012,7 +1036,8 @@ static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d,
   double *Ysp = kwy_arena<double>(ctx, (size_t)T * d * 4);
   double *bnd = kwy_arena<double>(ctx, (size_t)n * ML_CHUNK_WGS * 64 * ML_BD);
   int *status = kwy_arena<int>(ctx, 16);
-  if (!model || !X || !E || !Dv || !logp || !mix || !band || !rhs || !Ysp || !bnd || !status) {
+  double *band2 = gv ? kwy_arena<double>(ctx, (size_t)T * d * 4) : band;
+  if (!model || !X || !E || !Dv || !logp || !mix || !band || !rhs || !Ysp || !bnd || !status || !band2) {
     ctx->err = "gmm_mlpg: scratch arena too small";
     return KWY_ENOMEM;
   }
@@ -1035,6 +1060,7 @@ static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d,
   KWY_TRY(ml_launch_logp(ctx, X, dm, model, logp));
   hipLaunchKernelGGL(k_gmm_cond, dim3((unsigned)((T + ML_COND_F * ML_COND_W - 1) / (ML_COND_F * ML_COND_W))), dim3(64 * ML_COND_W), 0, ctx->stream, X, dm, model, logp, E, Dv, mix);
   hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, E, Dv, bt, dm, band);
+  if (gv) KWY_HIP(hipMemcpyAsync(band2, band, sizeof(double) * T * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
   KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0, ctx->stream,
                                                      band, rhs, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
   {
@@ -1046,6 +1072,7 @@ static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d,
                                                        band, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
   }
   KWY_HIP(hipGetLastError());
+  if (gv) KWY_TRY(ml_gv_ascent(ctx, bt, Ts, d, band2, *gv));
   return KWY_OK;
 }
 
@@ -1576,7 +1603,8 @@ static int ml_estep_attr(kwy_ctx *ctx) {
 // the last where a log-likelihood is asked for.  lik[k]: utterance k's em_iterations + 1 doubles on the device, or null.
 static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d, int M, const double *weights,
                               const double *means, const double *covs, int diff, int **status_out,
-                              const double *prepared, int em_iterations, double *const *lik) {
+                              const double *prepared, int em_iterations, double *const *lik,
+                              const ml_gv_opts *gv = nullptr) {
   const int D = 3 * d, n = bt.n, nblk = ml_frag_blocks(D);
   int64_t T = 0, Tmax = 0;
   int Pmax = 1;
@@ -1607,7 +1635,8 @@ static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int
   double *lc = kwy_arena<double>(ctx, M);
   double *lse = kwy_arena<double>(ctx, T);
   int *status = kwy_arena<int>(ctx, 16);
-  if (!model || !X || !E || !Dv || !logp || !band || !rhs || !Ysp || !bnd || !iv || !lc || !lse || !status) {
+  double *band2 = gv ? kwy_arena<double>(ctx, (size_t)T * d * 4) : band;
+  if (!model || !X || !E || !Dv || !logp || !band || !rhs || !Ysp || !bnd || !iv || !lc || !lse || !status || !band2) {
     ctx->err = "gmm_mlpg_em: scratch arena too small";
     return KWY_ENOMEM;
   }
@@ -1649,6 +1678,8 @@ static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int
   if (fin > ML_FIN_WGS) fin = ML_FIN_WGS;
   for (int k = 0; k <= em_iterations; ++k) {
     hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, E, Dv, bt, dm, band);
+    if (gv && k == em_iterations)
+      KWY_HIP(hipMemcpyAsync(band2, band, sizeof(double) * T * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
     KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0, ctx->stream,
                                                        band, rhs, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
     KWY_PROF(ctx, "k_mlpg_finish", hipLaunchKernelGGL(k_mlpg_finish, dim3((unsigned)fin, n), dim3(ML_FIN_NT), lds_solve, ctx->stream,
@@ -1659,6 +1690,7 @@ static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int
     }
   }
   KWY_HIP(hipGetLastError());
+  if (gv) KWY_TRY(ml_gv_ascent(ctx, bt, Ts, d, band2, *gv));
   return KWY_OK;
 }
 
@@ -1759,5 +1791,140 @@ extern "C" int kwy_gmm_mlpg_em(kwy_ctx *ctx, const double *x, int64_t T, int d, 
     return KWY_ENUMERIC;
   }
   if (loglik) std::copy(hl.begin(), hl.end(), loglik);
+  return KWY_OK;
+}
+
+// ---- the conversion with the GV ascent behind it (kwy_gvgen.hip; the contract is kwy_gv_ascent's in include/kwy.h) ----
+static int ml_gv_check(kwy_ctx *ctx, const void *x, int64_t T, int d, int M, const void *w, const void *mu,
+                       const void *cv, const void *y, int em_iterations, const void *gv_mean, const void *gv_var,
+                       double weight, int gv_iterations) {
+  if (em_iterations == -1) KWY_TRY(ml_check(ctx, x, T, d, M, w, mu, cv, y));
+  else KWY_TRY(ml_em_check(ctx, x, T, d, M, w, mu, cv, y, em_iterations));
+  if (!gv_mean || !gv_var) { ctx->err = "gmm_mlpg_gv: bad argument"; return KWY_EINVAL; }
+  if (!(weight > 0.0 && weight <= 1.79769313486231570815e+308)) {
+    ctx->err = "gmm_mlpg_gv: weight must be positive and finite";
+    return KWY_EINVAL;
+  }
+  if (gv_iterations < 0 || gv_iterations > KWY_MLPG_GV_MAX) {
+    ctx->err = "gmm_mlpg_gv: gv_iterations outside [0, KWY_MLPG_GV_MAX]";
+    return KWY_EINVAL;
+  }
+  return KWY_OK;
+}
+
+static size_t ml_gv_total_bytes(const int64_t *Ts, int n, int d, int M, int em_iterations, int gv_iterations) {
+  int64_t T = 0;
+  for (int k = 0; k < n; ++k) T += Ts[k];
+  return (em_iterations < 0 ? ml_scratch_bytes(T, d, M, n) : ml_em_scratch_bytes(T, d, M, n)) +
+         ml_gv_scratch_bytes(Ts, n, d, gv_iterations);
+}
+
+extern "C" int kwy_convert_mcep_gv_batch_dev(kwy_ctx *ctx, const kwy_convert_gv_job *jobs, int count, int d, int M,
+                                             const double *model, int em_iterations, int gv_offset,
+                                             const double *gv_mean, const double *gv_var, double weight,
+                                             int gv_iterations, int32_t *status) {
+  if (!ctx) return KWY_EINVAL;
+  if (!jobs || count < 0) { ctx->err = "convert_mcep_gv_batch: bad argument"; return KWY_EINVAL; }
+  if (count == 0) return KWY_OK;
+  size_t bytes = 0;
+  std::vector<int64_t> T(count);
+  for (int j = 0; j < count; ++j) {
+    KWY_TRY(ml_gv_check(ctx, jobs[j].mc, jobs[j].T, d, M, model, model, model, jobs[j].mc_out, em_iterations, gv_mean,
+                        gv_var, weight, gv_iterations));
+    T[j] = jobs[j].T;
+  }
+  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX)
+    bytes += ml_gv_total_bytes(T.data() + j0, std::min(KWY_BATCH_MAX, count - j0), d, M, em_iterations, gv_iterations);
+  KWY_HIP(hipSetDevice(ctx->device));
+  KWY_TRY(kwy_arena_begin(ctx, bytes));
+  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
+    ml_batch bt;
+    double *lik[KWY_BATCH_MAX], *obj[KWY_BATCH_MAX];
+    bt.n = std::min(KWY_BATCH_MAX, count - j0);
+    bt.ldx = d + 1;
+    bt.ldy = d + 1;
+    for (int k = 0; k < bt.n; ++k) {
+      const kwy_convert_gv_job &q = jobs[j0 + k];
+      bt.u[k].x = q.mc + 1; bt.u[k].y = q.mc_out + 1;
+      bt.u[k].keep_in = q.mc; bt.u[k].keep_out = q.mc_out;
+      lik[k] = q.loglik;
+      obj[k] = q.objective;
+    }
+    const ml_gv_opts gv = {gv_mean, gv_var, weight, gv_iterations, gv_offset, obj, status ? status + j0 : nullptr};
+    int *st;
+    if (em_iterations < 0)
+      KWY_TRY(mlpg_batch_core(ctx, bt, T.data() + j0, d, M, nullptr, nullptr, nullptr, 0, &st, model, &gv));
+    else
+      KWY_TRY(mlpg_em_batch_core(ctx, bt, T.data() + j0, d, M, nullptr, nullptr, nullptr, 0, &st, model, em_iterations,
+                                 lik, &gv));
+  }
+  return KWY_OK;
+}
+
+extern "C" int kwy_convert_mcep_gv_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
+                                       int em_iterations, int gv_offset, const double *gv_mean, const double *gv_var,
+                                       double weight, int gv_iterations, double *mc_out, double *loglik,
+                                       double *objective, int32_t *status) {
+  if (!ctx) return KWY_EINVAL;
+  kwy_convert_gv_job job = {mc, T, mc_out, loglik, objective};
+  return kwy_convert_mcep_gv_batch_dev(ctx, &job, 1, d, M, model, em_iterations, gv_offset, gv_mean, gv_var, weight,
+                                       gv_iterations, status);
+}
+
+extern "C" int kwy_gmm_mlpg_gv(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
+                               const double *means, const double *covs, int diff, int em_iterations, int gv_offset,
+                               const double *gv_mean, const double *gv_var, double weight, int gv_iterations, double *y,
+                               double *loglik, double *objective, int32_t *status) {
+  if (!ctx) return KWY_EINVAL;
+  KWY_TRY(ml_gv_check(ctx, x, T, d, M, weights, means, covs, y, em_iterations, gv_mean, gv_var, weight, gv_iterations));
+  KWY_HIP(hipSetDevice(ctx->device));
+  const int D2 = 6 * d, nl = em_iterations < 0 ? 0 : em_iterations + 1;
+  size_t bx = kwy_pad(sizeof(double) * T * d), bw = kwy_pad(sizeof(double) * M);
+  size_t bm = kwy_pad(sizeof(double) * M * D2), bc = kwy_pad(sizeof(double) * (size_t)M * D2 * D2);
+  KWY_TRY(kwy_arena_begin(ctx, ml_gv_total_bytes(&T, 1, d, M, em_iterations, gv_iterations) + 2 * bx + bw + bm + bc +
+                                   kwy_pad(sizeof(double) * (KWY_MLPG_EM_MAX + 1)) +
+                                   kwy_pad(sizeof(double) * (KWY_MLPG_GV_MAX + 1)) + 2 * kwy_pad(sizeof(double) * d) +
+                                   kwy_pad(64)));
+  double *dx = kwy_arena<double>(ctx, (size_t)T * d), *dy = kwy_arena<double>(ctx, (size_t)T * d);
+  double *dw = kwy_arena<double>(ctx, M), *dmu = kwy_arena<double>(ctx, (size_t)M * D2);
+  double *dcv = kwy_arena<double>(ctx, (size_t)M * D2 * D2);
+  double *dlik = kwy_arena<double>(ctx, KWY_MLPG_EM_MAX + 1), *dobj = kwy_arena<double>(ctx, KWY_MLPG_GV_MAX + 1);
+  double *dgm = kwy_arena<double>(ctx, d), *dgv = kwy_arena<double>(ctx, d);
+  int32_t *dst = kwy_arena<int32_t>(ctx, 16);
+  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * T * d, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dw, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dmu, means, sizeof(double) * M * D2, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dcv, covs, sizeof(double) * (size_t)M * D2 * D2, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dgm, gv_mean, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(dgv, gv_var, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+  ml_batch bt;
+  bt.n = 1;
+  bt.ldx = d;
+  bt.ldy = d;
+  bt.u[0].x = dx; bt.u[0].y = dy; bt.u[0].keep_in = nullptr; bt.u[0].keep_out = nullptr;
+  double *lik[1] = {loglik && nl ? dlik : nullptr}, *obj[1] = {dobj};
+  const ml_gv_opts gv = {dgm, dgv, weight, gv_iterations, gv_offset, obj, dst};
+  int *st;
+  if (em_iterations < 0)
+    KWY_TRY(mlpg_batch_core(ctx, bt, &T, d, M, dw, dmu, dcv, diff, &st, nullptr, &gv));
+  else
+    KWY_TRY(mlpg_em_batch_core(ctx, bt, &T, d, M, dw, dmu, dcv, diff, &st, nullptr, em_iterations, lik, &gv));
+  int hstatus = 0;
+  int32_t hgv = 0;
+  std::vector<double> hl(nl + 1), ho(gv_iterations + 1);
+  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * T * d, hipMemcpyDeviceToHost, ctx->stream));
+  if (lik[0]) KWY_HIP(hipMemcpyAsync(hl.data(), dlik, sizeof(double) * nl, hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(ho.data(), dobj, sizeof(double) * (gv_iterations + 1), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(&hstatus, st, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(&hgv, dst, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  if (hstatus != 0) {
+    ctx->err = hstatus == 1 ? "gmm_mlpg_gv: source covariance is not positive definite"
+                            : "gmm_mlpg_gv: MLPG system is not positive definite";
+    return KWY_ENUMERIC;
+  }
+  if (lik[0]) std::copy(hl.begin(), hl.begin() + nl, loglik);
+  if (objective) std::copy(ho.begin(), ho.end(), objective);
+  if (status) *status = hgv;
   return KWY_OK;
 }

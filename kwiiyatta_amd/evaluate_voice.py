@@ -104,7 +104,7 @@ def _check_options(gv, transpose_key, frames):
 
 
 def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose_key=0.0, frames='speech',
-                  per_frame=False, em=None):
+                  per_frame=False, em=None, mlpg_gv=None):
     """The figures of one parallel pair: two unaligned feature sets (trimmed as training trims them, if the alignment
     is to be the one training would use).  Both are padded and aligned as `align_even` does -- the same pad draws in
     the same order, so a seeded run reproduces training's alignment -- `source.mel_cepstrum` is converted on its own
@@ -113,7 +113,9 @@ def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose
     convert_f0 / transpose_key: the source f0 through the converter's f0 map first (convert_voice's options).
     per_frame=True keeps the index lists and the per-frame distortion in the result.
     em=N: the conversion is the EM trajectory conversion over soft mixture posteriors with N re-estimations
-    (`converter.convert(..., em=N)`, convert_voice's --mlpg-em); None: one arg-max mixture per frame."""
+    (`converter.convert(..., em=N)`, convert_voice's --mlpg-em); None: one arg-max mixture per frame.
+    mlpg_gv=N: parameter generation considering the global variance behind it, N steps
+    (`converter.convert(..., mlpg_gv=N)`, --mlpg-gv); it does not go with gv > 0."""
     import kwiiyatta_amd as k
     from .backend import distortion as dist
     from .backend import f0 as f0map
@@ -125,7 +127,8 @@ def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose
     xs, ys = even_indices(a, b, PAD_LEN, strict=True)
     idx_x, idx_y = (np.ascontiguousarray(v, dtype=np.int32) for v in (xs, ys))
     converted = converter.convert(source.mel_cepstrum, **(dict(gv=gv) if gv > 0 else {}),
-                                  **({} if em is None else dict(em=em)))
+                                  **({} if em is None else dict(em=em)),
+                                  **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)))
     fs = converted.fs
 
     def coefficients(f):
@@ -198,6 +201,7 @@ def make_config():
     conf.add_transpose_key_argument()
     conf.add_gv_argument()
     conf.add_mlpg_em_argument()
+    conf.add_mlpg_gv_argument()
     conf.add_converter_arguments()
     return conf
 
@@ -266,7 +270,9 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
             f0_stats=converter.f0_stats if options['convert_f0'] else None, transpose_key=options['transpose_key'],
             frames=options['frames'], **(dict(gv_stats=converter.gv_stats, gv_strength=options['gv'])
                                          if options['gv'] > 0 else {}),
-            **({} if options.get('em') is None else dict(mlpg_em=options['em'])))
+            **({} if options.get('em') is None else dict(mlpg_em=options['em'])),
+            **({} if options.get('mlpg_gv') is None else dict(mlpg_gv=options['mlpg_gv'], gv_stats=converter.gv_stats,
+                                                              gv_var=converter.gv_var)))
         for (key, _, _), rec in zip(batch, records):
             results[key] = Result(rec['mcd_moments'], rec['source_moments'], rec['f0_moments'], rec['counts'],
                                   rec['aligned'], rec['outside'])
@@ -321,10 +327,13 @@ def main():
         warning = overlap_warning(file_slice(dataset.keys(), conf.skip_files, conf.max_files), keys)
         if warning:
             print(warning, file=sys.stderr)
-    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0)
+    converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
+                                     **(dict(gv_var=True) if conf.mlpg_gv is not None else {}))
     options = dict(gv=conf.gv, convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, frames=conf.frames)
     if conf.mlpg_em is not None:           # (--mlpg-em: EM trajectory conversion, as convert_voice runs it)
         options['em'] = conf.mlpg_em
+    if conf.mlpg_gv is not None:           # (--mlpg-gv: GV-considering parameter generation, likewise)
+        options['mlpg_gv'] = conf.mlpg_gv
     if conf.batch:
         results = _evaluate_batched(conf, converter, dataset, keys, options)
         total = pool(results)
