@@ -764,9 +764,11 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
 template <int LOG2N>
 static constexpr size_t d4c_bands_lds() {
   constexpr int N = 1 << LOG2N, H = N / 2, NT = d4c_nt<LOG2N>::value;
+  // the select's words lie in B: control words, list and sums first, the histogram's copies behind them -- except
+  // in the drained form, where the copies take the upper half of B (see the kernel) and nothing is added
+  constexpr size_t sel = sizeof(uint32_t) * (KWY_SELECT_WORDS(NT) + (d4c_drain<LOG2N>::value ? 0 : KWY_SELECT_WIDE_WORDS));
   return sizeof(double) * (16 + D4C_MAX_BANDS + 2 + 2 * NT) + sizeof(double) * ((2 * H + 2) + 2) +
-         ((sizeof(uint32_t) * KWY_SELECT_WORDS(NT) > sizeof(double) * (2 * H + 4))
-              ? sizeof(uint32_t) * KWY_SELECT_WORDS(NT) - sizeof(double) * (2 * H + 4) : 0);
+         (sel > sizeof(double) * (2 * H + 4) ? sel - sizeof(double) * (2 * H + 4) : 0);
 }
 
 // SPARSE: the window fits the first H/8 (+1) packed points (compile-time, so that the two input paths do not share
@@ -788,7 +790,10 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
   double *wns = coarse + D4C_MAX_BANDS + 2;  // 2 NT: the thread's two window values (sparse path), parked between bands
   kwy_c *B = (kwy_c *)(wns + 2 * NT);        // H+1 complex (+2 doubles)
   double *Bd = (double *)B;
+  // the select's scratch: control words, list and the bins' sums in the first points of B; the histogram's copies
+  // behind them, or -- drained form, whose exchange of powers uses the points NT .. 4 NT -- from point 4 NT on
   uint32_t *hist = (uint32_t *)B;
+  uint32_t *wide = DRAIN ? (uint32_t *)(B + 4 * NT) : hist + KWY_SELECT_WORDS(NT);
 
   const int tid = threadIdx.x;
   const int utt = batch.find(blockIdx.x);
@@ -869,8 +874,11 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
       // -- this thread's own slots q = 0 and q = 2 -- and k = 2 NT - tid, 4 NT - tid, which are slots q = 1 and q = 3
       // of thread NT - tid.  The selection sums a thread's keys in slot order, so the keys stay where they were: those
       // two pairs of powers change hands through Z[2 NT - tid] and Z[4 NT - tid], two of the points this thread has
-      // just read itself (no barrier in front of the stores) and clear of the select's histogram words.
-      static_assert(Q == 4 && sizeof(uint32_t) * KWY_SELECT_WORDS(NT) <= sizeof(kwy_c) * NT, "exchange clear of the histogram");
+      // just read itself (no barrier in front of the stores) and clear of the select's words: those lie in the points
+      // [0, NT) (control words, list, sums) and [4 NT, H] (the histogram's copies), the exchange in (NT, 4 NT).
+      static_assert(Q == 4 && sizeof(uint32_t) * KWY_SELECT_WORDS(NT) <= sizeof(kwy_c) * NT &&
+                    sizeof(kwy_c) * 4 * NT + sizeof(uint32_t) * KWY_SELECT_WIDE_WORDS <= sizeof(kwy_c) * (H + 1),
+                    "exchange clear of the select's words");
       kwy_c lo[4], hi[4], md;
       kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, lo, hi, md);
       const kwy_c twc = D4C_DRAIN_TWC(twN, NT, tid);
@@ -916,16 +924,24 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
     }
     if (b == 1) D4C_STAMP(19);
     double nsmall, nall;
-    kwy_block_smallest_sum<RK, NT>(key, H + 1, H - boundary, hist, red, &nsmall, &nall);
+    // (the two sums arrive in thread 0 only)
+    kwy_block_smallest_sum<RK, NT, false>(key, H + 1, H - boundary, hist, wide, red, &nsmall, &nall);
     if (b == 1) D4C_STAMP(20);
-    if (dbg && tid == 0 && blockIdx.x == (unsigned)dbg[63])
-      for (int q = 0; q < 12; ++q) dbg[24 + 12 * (b & 1) + q] = hist[2 * KWY_SELECT_BINS + q];
+    if (dbg) {                     // (stamped runs only: the control words, before the next band's transform takes B)
+      if (tid == 0 && blockIdx.x == (unsigned)dbg[63])
+        for (int q = 0; q < 12; ++q) dbg[24 + 12 * (b & 1) + q] = hist[2 * KWY_SELECT_BINS + q];
+      __syncthreads();
+    }
     if (tid == 0) {
       double cv = 10 * log10(nsmall / nall);
       cv = cv + (cf0 - 100) / 50.0;
       coarse[b + 1] = cv < 0.0 ? cv : 0.0;
     }
-    __syncthreads();
+    // No barrier here.  The select's last barrier (R) is behind every read of its words in B, so the next band's
+    // transform may write B at once; thread 0 alone still reads red[] (the wavefronts' partial sums), and red[] is not
+    // written again before the next select, i.e. behind the barriers of the next band's transform, at which thread 0
+    // has arrived only after these reads; coarse[] is written by thread 0 alone and read behind the barrier that
+    // follows the loop.
   }
   D4C_STAMP(21);
   if (tid == 0) {

@@ -532,23 +532,54 @@ __device__ __forceinline__ void kwy_block_sum2(double a, double b, double *red, 
 // Sum of the m smallest of n non-negative doubles, and the sum of all of them, without sorting.  Thread t holds the
 // IEEE bit patterns of elements t, t+NT, ... in key[] (~0 for slots beyond n); the patterns order like the values
 // for x >= 0.  The m-th smallest value v* is found, then sum_small = sum(v < v*) + (m - #{v < v*}) * v*.
-//   hist: KWY_SELECT_WORDS uint32 of LDS (16-byte aligned) that no thread touches any more when the call starts;
-//   red: >= 2*NT/64 doubles.
+//   hist: KWY_SELECT_WORDS uint32 of LDS (16-byte aligned), wide: KWY_SELECT_WIDE_WORDS uint32 of LDS (16-byte
+//   aligned), red: >= 2*NT/64 doubles -- none of them touched by any thread any more when the call starts (a barrier
+//   between two calls, or between the last read of the results' partial sums and the next call).
+//   ALL = false: only thread 0 receives the two sums (D4C reads them there and nowhere else).
 // Two ways to v*:
 //  (1) FROM THE TOP, one histogram: bin = distance of the key's high word from the block's largest high word in
 //      quarter binades (256 bins = 64 binades below the maximum, everything lower in the last bin).  The bin that
 //      holds the wanted rank -- counted from the largest value -- is left with a few dozen keys of a 2 049-bin
 //      spectrum; they are listed in LDS and ranked against each other with full keys.  Only the maximum is reduced,
-//      the keys stay as they are, three barriers + the ranking.  D4C asks for the 66th largest of 2 049: always here.
+//      the keys stay as they are.  D4C asks for the 66th largest of 2 049: always here.
+//      The spectra are smooth and oversampled: the lanes of a wavefront hold neighbouring bins of the spectrum and
+//      count into the same bin of the histogram, one same-address atomic after the other.  So the histogram is kept
+//      in KWY_SELECT_COPIES private copies, the copy taken from the lane number, laid out bin-major (the copies of a
+//      bin are consecutive words: lanes that share a bin hit different banks; copy-major they would share the bank).
+//      One thread per bin adds the copies up with 16-byte reads and leaves the sum in hist[bin], which wavefront 0
+//      scans as before.
+//      Barriers: [maxima, wavefront sums of all keys, cleared copies] A [counting] B [adding the copies up] C [scan
+//      by wavefront 0] S [list] L [ranking by the first threads] K [sum below v*] R [thread 0 / everyone adds the
+//      wavefronts' partial sums]: seven, where the single histogram with kwy_block_sum2 behind it and its caller's
+//      closing barrier made eight.  The sum of all keys needs nothing the selection finds and leaves with the
+//      maxima; behind R nobody reads hist / wide any more, and red[] only in the threads that take the results.
 //  (2) GENERAL, MSB-first radix select (KWY_SELECT_BITS bits a round) on key - min(key), starting at the highest bit
 //      in which the block's keys differ; two barriers per round, histogram and control words double-buffered; a
 //      round that leaves <= 124 keys hands over to the same ranking.  Taken when (1) ends in its last bin or with a
 //      crowded one (flat data, ties by the hundred, a rank far from the top).
+// The two results are summed as they always were -- per thread in slot order, over the wavefront (kwy_wave_sum), then
+// the wavefronts' sums left to right -- and v* is one of the keys, fixed by the data: the bits do not depend on how
+// v* was found.
 // Digit width 8 (256 bins) is what the kernels use.  11 bits -- the whole exponent of a non-negative IEEE double in
 // the first round -- was measured and is SLOWER (what the rounds save in barriers is lost clearing and scanning
 // 2048 bins per round).  Wave-aggregated atomics (the lanes that share the first live lane's digit counted with one
 // atomic) were measured too: on real group-delay spectra the ballots cost more issue slots than the same-address
 // atomics they save (3 280 against 1 936 clocks for the nine slots of a round): KWY_SELECT_AGG=1 keeps that form.
+// KWY_SELECT_COPIES (k_d4c_bands<12, true> per launch, one wave of 16 pairs on one stream, two runs each in one
+// session, profiles/sel_variants_serial.txt; the single histogram with kwy_block_sum2 and the caller's barrier: 1.284 ms):
+//   1 copy (the single histogram, with the barriers as above)   1.267 ms
+//   16 copies   1.278 ms (16 B of scratch in the band kernel)      8 copies   1.255 ms (12 B)
+//   4 copies    1.206 ms (no scratch)  <- chosen; LDS bank conflicts / LDS active and SQ_WAIT_ANY / wave cycles of the
+//   kernel against the single histogram's: profiles/sel_*_pmc_sq_summary.json.  Every copy is a 16-byte clear and a
+//   16-byte read per thread and call; no padding between the bins (neighbouring bins lie in different banks as it is).
+// Measured in the same session and LEFT OUT, each slower than the form kept (the wavefronts of four workgroups share
+// a SIMD: one that waits at a barrier leaves the issue slots to the others, while ballots and work repeated in every
+// wavefront take them):
+//   - the list appended per wavefront (a ballot per slot, one returning atomic per wavefront, the lane's place from
+//     the prefix count of its ballot) instead of one returning atomic per key: 1.267 -> 1.295 ms;
+//   - every wavefront scanning the histogram and ranking the list for itself, bin, rank and key in scalar registers,
+//     barriers S and K gone: 1.267 -> 1.301 ms; both with 16 copies: 1.321 ms;
+//   - wavefront 0 adding the copies up inside its scan (barrier C gone): 1.263 ms with 4 copies, 16 B of scratch.
 #ifndef KWY_SELECT_BITS
 #define KWY_SELECT_BITS 8
 #endif
@@ -556,7 +587,11 @@ __device__ __forceinline__ void kwy_block_sum2(double a, double b, double *red, 
 #ifndef KWY_SELECT_AGG
 #define KWY_SELECT_AGG 0
 #endif
-#define KWY_SELECT_WORDS(NT) (2 * KWY_SELECT_BINS + 32)
+#ifndef KWY_SELECT_COPIES
+#define KWY_SELECT_COPIES 4
+#endif
+#define KWY_SELECT_WORDS(NT) (2 * KWY_SELECT_BINS + 64)
+#define KWY_SELECT_WIDE_WORDS (KWY_SELECT_BINS * KWY_SELECT_COPIES)
 #define KWY_SELECT_LIST (KWY_SELECT_BINS / 2 - 4)         // keys the ranking takes (the other histogram's words)
 
 __device__ __forceinline__ uint32_t kwy_wave_max_u32(uint32_t v) {
@@ -568,9 +603,12 @@ __device__ __forceinline__ uint32_t kwy_wave_max_u32(uint32_t v) {
              max((uint32_t)__builtin_amdgcn_readlane((int)v, 32), (uint32_t)__builtin_amdgcn_readlane((int)v, 48)));
 }
 
-// wavefront 0: the bin of h[0 .. BINS) that holds rank kk (1-based, bins taken in index order) -> ctl[0] = bin,
-// ctl[1] = rank inside it, ctl[2] = its population, ctl[3] = keys in the bins before it
-__device__ __forceinline__ void kwy_select_scan(const uint32_t *h, int kk, uint32_t *ctl, int lane) {
+// one wavefront: the bin of h[0 .. BINS) that holds rank kk (1-based, bins taken in index order).  True in the one
+// lane whose bins hold it, with c[0] = bin, c[1] = rank inside it, c[2] = its population, c[3] = keys in the bins
+// before it.
+// (Scan and ranking are each split into a part that finds and a part that publishes: with the bodies in one piece
+// the register allocation of k_d4c_bands<12, true>, which sits at its cap of 128, spills 28 bytes per lane; so, none.)
+__device__ __forceinline__ bool kwy_select_scan_lane(const uint32_t *h, int kk, int lane, uint32_t (&c)[4]) {
   constexpr int PERLANE = KWY_SELECT_BINS / 64;           // bins scanned per lane
   static_assert(PERLANE % 4 == 0 && PERLANE >= 4, "bins per lane must be a multiple of 4");
   // lane l owns bins [PERLANE l, PERLANE (l + 1)): their total first, then only the lane whose range holds the
@@ -583,20 +621,30 @@ __device__ __forceinline__ void kwy_select_scan(const uint32_t *h, int kk, uint3
     tot += (c4.x + c4.y) + (c4.z + c4.w);
   }
   uint32_t before = kwy_wave_scan_u32(tot) - tot;
-  if ((uint32_t)kk > before && (uint32_t)kk <= before + tot) {
+  const bool mine = (uint32_t)kk > before && (uint32_t)kk <= before + tot;
+  c[0] = c[1] = c[2] = c[3] = 0u;
+  if (mine) {
     const uint32_t *hb = h + PERLANE * lane;
     for (int q = 0; q < PERLANE; ++q) {
-      const uint32_t c = hb[q];
-      if ((uint32_t)kk <= before + c) {
-        ctl[0] = PERLANE * lane + q;
-        ctl[1] = (uint32_t)kk - before;
-        ctl[2] = c;
-        ctl[3] = before;
+      const uint32_t n = hb[q];
+      if ((uint32_t)kk <= before + n) {
+        c[0] = PERLANE * lane + q;
+        c[1] = (uint32_t)kk - before;
+        c[2] = n;
+        c[3] = before;
         break;
       }
-      before += c;
+      before += n;
     }
   }
+  return mine;
+}
+
+// wavefront 0: the same into LDS -> ctl[0] = bin, ctl[1] = rank inside it, ctl[2] = its population, ctl[3] = keys in
+// the bins before it
+__device__ __forceinline__ void kwy_select_scan(const uint32_t *h, int kk, uint32_t *ctl, int lane) {
+  uint32_t c[4];
+  if (kwy_select_scan_lane(h, kk, lane, c)) { ctl[0] = c[0]; ctl[1] = c[1]; ctl[2] = c[2]; ctl[3] = c[3]; }
 }
 
 // the listed keys list[0 .. pop) ranked against each other (pop <= KWY_SELECT_LIST; four entries behind the list
@@ -605,51 +653,74 @@ __device__ __forceinline__ void kwy_select_scan(const uint32_t *h, int kk, uint3
 // of listed keys in front of it (strictly) and out_count[1] = the listed keys equal to it.  Ascending order: the same
 // with the comparison turned round.
 template <bool DESCENDING>
+__device__ __forceinline__ bool kwy_select_rank_entry(const unsigned long long *list, int pop, int rank, int e,
+                                                      unsigned long long mine, int *front_out, int *ties_out) {
+  int front = 0, tie_front = 0, ties = 0;
+  for (int j = 0; j < pop; j += 4) {                       // four keys a trip: two 16-byte reads in flight
+    const ulonglong2 o01 = *(const ulonglong2 *)(list + j), o23 = *(const ulonglong2 *)(list + j + 2);
+    const unsigned long long o[4] = {o01.x, o01.y, o23.x, o23.y};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool in = j + q < pop;
+      front += in & (DESCENDING ? o[q] > mine : o[q] < mine);
+      const bool eq = in & (o[q] == mine);
+      ties += eq;
+      tie_front += eq & (j + q < e);
+    }
+  }
+  *front_out = front; *ties_out = ties;
+  return front + tie_front == rank - 1;
+}
+template <bool DESCENDING>
 __device__ __forceinline__ void kwy_select_rank(const unsigned long long *list, int pop, int rank, int tid,
                                                 unsigned long long *out_key, uint32_t *out_count) {
   if (tid < pop) {
     const unsigned long long mine = list[tid];
-    int front = 0, tie_front = 0, ties = 0;
-    for (int j = 0; j < pop; j += 4) {                       // four keys a trip: two 16-byte reads in flight
-      const ulonglong2 o01 = *(const ulonglong2 *)(list + j), o23 = *(const ulonglong2 *)(list + j + 2);
-      const unsigned long long o[4] = {o01.x, o01.y, o23.x, o23.y};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const bool in = j + q < pop;
-        front += in & (DESCENDING ? o[q] > mine : o[q] < mine);
-        const bool eq = in & (o[q] == mine);
-        ties += eq;
-        tie_front += eq & (j + q < tid);
-      }
+    int front, ties;
+    if (kwy_select_rank_entry<DESCENDING>(list, pop, rank, tid, mine, &front, &ties)) {
+      *out_key = mine; out_count[0] = (uint32_t)front; out_count[1] = (uint32_t)ties;
     }
-    if (front + tie_front == rank - 1) { *out_key = mine; out_count[0] = (uint32_t)front; out_count[1] = (uint32_t)ties; }
   }
 }
-
-template <int RMAX, int NT = KWY_THREADS>
+template <int RMAX, int NT = KWY_THREADS, bool ALL = true>
 __device__ inline void kwy_block_smallest_sum(unsigned long long (&key)[RMAX], int n, int m,
-                                              uint32_t *hist, double *red, double *sum_small,
+                                              uint32_t *hist, uint32_t *wide, double *red, double *sum_small,
                                               double *sum_all) {
-  constexpr int BITS = KWY_SELECT_BITS, BINS = 1 << BITS;
+  constexpr int BITS = KWY_SELECT_BITS, BINS = 1 << BITS, C = KWY_SELECT_COPIES;
   constexpr int TOP_SHIFT = 18;                           // high word: 20 mantissa bits -> quarter binades
+  static_assert(C == 1 || (C >= 4 && C <= 64 && (C & (C - 1)) == 0), "copies: one, or a power of two in whole 16-byte reads");
+  static_assert(NT <= 512, "the general path's extrema take 4 NT / 64 control words");
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   uint32_t *ctlb = hist + 2 * BINS;  // 2 x {digit, rank, population, before}; [8..9] one 64-bit key; [10] list
-                                     // length; [11..12] two counts; [16 ..] one word per wavefront
+                                     // length; [11..12] two counts; [16 ..] one word per wavefront; [32 ..] the
+                                     // general path's extrema, two doubles per wavefront
   unsigned long long *k64 = (unsigned long long *)(ctlb + 8);
   unsigned long long *list = (unsigned long long *)(hist + BINS);
   unsigned long long vkey;           // bit pattern of v*
   int copies;                        // how many keys equal to v* belong to the m smallest
 
-  // ---- (1) from the top
+  // ---- (1) from the top.  The sum of all keys needs nothing the selection finds: its wavefront sums leave with the
+  // exchange of the maxima (barrier A) and are read behind barrier R.
   uint32_t hmax = 0;
+  double s_all = 0.0;
 #pragma unroll
-  for (int r = 0; r < RMAX; ++r)
-    if (tid + NT * r < n) hmax = max(hmax, (uint32_t)(key[r] >> 32));
+  for (int r = 0; r < RMAX; ++r) {
+    if (tid + NT * r < n) {
+      hmax = max(hmax, (uint32_t)(key[r] >> 32));
+      s_all += __longlong_as_double((long long)key[r]);
+    }
+  }
   hmax = kwy_wave_max_u32(hmax);
-  if (lane == 0) ctlb[16 + wv] = hmax;
-  for (int i = tid; i < BINS; i += NT) hist[i] = 0;
+  s_all = kwy_wave_sum(s_all);
+  if (lane == 0) { ctlb[16 + wv] = hmax; red[NT / 64 + wv] = s_all; }
+  if constexpr (C > 1) {
+    static_assert(C == 1 || BINS * C % 4 == 0, "cleared in 16-byte stores");
+    for (int i = tid; i < BINS * C / 4; i += NT) ((uint4 *)wide)[i] = make_uint4(0u, 0u, 0u, 0u);
+  } else {
+    for (int i = tid; i < BINS; i += NT) hist[i] = 0;
+  }
   if (tid == 0) ctlb[10] = 0;
-  __syncthreads();
+  __syncthreads();                                        // A
   hmax = ctlb[16];
 #pragma unroll
   for (int i = 1; i < NT / 64; ++i) hmax = max(hmax, ctlb[16 + i]);
@@ -660,25 +731,43 @@ __device__ inline void kwy_block_smallest_sum(unsigned long long (&key)[RMAX], i
     if (NT * r + (tid & ~63) >= n) continue;              // nothing in this slot for the whole wavefront
     if (tid + NT * r < n) {
       dg[r] = min((hmax - (uint32_t)(key[r] >> 32)) >> TOP_SHIFT, (uint32_t)(BINS - 1));
-      atomicAdd(&hist[dg[r]], 1u);
+      if constexpr (C > 1) atomicAdd(&wide[dg[r] * C + (lane & (C - 1))], 1u);
+      else atomicAdd(&hist[dg[r]], 1u);
     }
   }
-  __syncthreads();
+  __syncthreads();                                        // B
+  if constexpr (C > 1) {
+    // one thread per bin adds its copies up: 16-byte reads, the lanes of a read group that start in the same bank
+    // (64 / C apart) at different quarters of their bins
+    for (int b = tid; b < BINS; b += NT) {
+      const uint4 *bp = (const uint4 *)(wide + b * C);
+      uint32_t c = 0;
+#pragma unroll
+      for (int q = 0; q < C / 4; ++q) {
+        const uint4 c4 = bp[(q + b / (64 / C)) & (C / 4 - 1)];
+        c += (c4.x + c4.y) + (c4.z + c4.w);
+      }
+      hist[b] = c;
+    }
+    __syncthreads();                                      // C
+  }
   if (wv == 0) kwy_select_scan(hist, n - m + 1, ctlb, lane);
-  __syncthreads();
+  __syncthreads();                                        // S
   const uint32_t chosen = ctlb[0], pop = ctlb[2];
+  const int rank = (int)ctlb[1], above = (int)ctlb[3];
   if (chosen < (uint32_t)(BINS - 1) && pop <= (uint32_t)KWY_SELECT_LIST) {
-    const int rank = (int)ctlb[1], above = (int)ctlb[3];
 #pragma unroll
     for (int r = 0; r < RMAX; ++r)
       if (dg[r] == chosen) list[atomicAdd(&ctlb[10], 1u)] = key[r];
-    __syncthreads();
+    __syncthreads();                                      // L
     kwy_select_rank<true>(list, (int)pop, rank, tid, k64, &ctlb[11]);
-    __syncthreads();
+    __syncthreads();                                      // K
     vkey = *k64;
-    copies = m - (n - above - (int)ctlb[11] - (int)ctlb[12]);   // keys >= v*: above + listed in front + ties
+    const int front = (int)ctlb[11], ties = (int)ctlb[12];
+    copies = m - (n - above - front - ties);              // keys >= v*: above + listed in front + ties
   } else {
     // ---- (2) general: the block's smallest and largest key, relative keys, radix rounds
+    double *ext = (double *)(ctlb + 32);
     double lo = INFINITY, hi = 0.0;
 #pragma unroll
     for (int r = 0; r < RMAX; ++r) {
@@ -689,13 +778,13 @@ __device__ inline void kwy_block_smallest_sum(unsigned long long (&key)[RMAX], i
     }
     lo = kwy_wave_min_f64(lo);
     hi = kwy_wave_max_f64(hi);
-    if (lane == 0) { red[wv] = lo; red[NT / 64 + wv] = hi; }
+    if (lane == 0) { ext[wv] = lo; ext[NT / 64 + wv] = hi; }
     for (int i = tid; i < BINS; i += NT) hist[i] = 0;
     if (tid == 0) ctlb[10] = 0;
     __syncthreads();
-    lo = red[0]; hi = red[NT / 64];
+    lo = ext[0]; hi = ext[NT / 64];
 #pragma unroll
-    for (int i = 1; i < NT / 64; ++i) { lo = fmin(lo, red[i]); hi = fmax(hi, red[NT / 64 + i]); }
+    for (int i = 1; i < NT / 64; ++i) { lo = fmin(lo, ext[i]); hi = fmax(hi, ext[NT / 64 + i]); }
     const unsigned long long kmin = (unsigned long long)__double_as_longlong(lo);
     const unsigned long long range = (unsigned long long)__double_as_longlong(hi) - kmin;
     const int top0 = range ? 64 - __clzll((long long)range) : 0;     // one past the highest differing bit
@@ -773,19 +862,20 @@ __device__ inline void kwy_block_smallest_sum(unsigned long long (&key)[RMAX], i
     for (int r = 0; r < RMAX; ++r) key[r] += kmin;
   }
   const double vstar = __longlong_as_double((long long)vkey);
-  double s_less = 0.0, s_all = 0.0;
+  double s_less = 0.0;
 #pragma unroll
-  for (int r = 0; r < RMAX; ++r) {
-    if (tid + NT * r < n) {
-      const double x = __longlong_as_double((long long)key[r]);
-      s_all += x;
-      if (key[r] < vkey) s_less += x;
-    }
+  for (int r = 0; r < RMAX; ++r)
+    if (tid + NT * r < n && key[r] < vkey) s_less += __longlong_as_double((long long)key[r]);
+  s_less = kwy_wave_sum(s_less);
+  if (lane == 0) red[wv] = s_less;
+  __syncthreads();                                        // R
+  if (ALL || tid == 0) {
+    double t_less = red[0], t_all = red[NT / 64];
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) { t_less += red[i]; t_all += red[NT / 64 + i]; }
+    *sum_small = t_less + (double)copies * vstar;
+    *sum_all = t_all;
   }
-  double t_less, t_all;
-  kwy_block_sum2<NT>(s_less, s_all, red, &t_less, &t_all);
-  *sum_small = t_less + (double)copies * vstar;
-  *sum_all = t_all;
 }
 
 // ------------------------------------------------------------------- LDS FFTs

@@ -9,6 +9,15 @@ extern "C" {
  * values: problems x n non-negative doubles (device); out: problems x {sum of the m smallest, sum of all} (device).
  * n <= 2304.  stream: a hipStream_t (NULL = the default stream).  Returns 0, -1 (arguments) or -2 (launch failed). */
 int kwy_debug_smallest_sum_dev(void *stream, const double *values, int problems, int n, int m, double *out);
+/* The same routine beside the reference copy of its earlier form (one histogram counted with same-address atomics,
+ * kwy_block_sum2 behind the selection) that the self-test library keeps, both on the same keys; the current one in
+ * the form the band kernel calls (sums in thread 0 only).  out_ref / out_new: problems x {sum of the m smallest, sum of all} (device); the two
+ * are meant to agree bit for bit.  256 threads per problem, n <= 2304; the 512-thread form of the 96 kHz band kernel,
+ * n <= 4608. */
+int kwy_debug_select_paths_dev(void *stream, const double *values, int problems, int n, int m, double *out_ref,
+                               double *out_new);
+int kwy_debug_select_paths512_dev(void *stream, const double *values, int problems, int n, int m, double *out_ref,
+                                  double *out_new);
 /* kwy_log(x) and kwy_sincos_medium(x) of kwy_device.hpp for every element of x (n doubles, device). */
 int kwy_debug_devmath_dev(void *stream, const double *x, int n, double *log_out, double *sin_out, double *cos_out);
 /* The real FFT of rows of 2^log2n samples through both closing passes of the LDS transform: the stored one and the

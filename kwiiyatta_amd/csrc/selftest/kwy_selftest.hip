@@ -1,6 +1,6 @@
 // libkwy_selftest.so -- NOT part of the product: entry points that let tests drive device-side building blocks of
 // kwy_device.hpp on caller data.  Built beside libkwy.so by build.sh, loaded only by tests (test_select_gpu.py,
-// test_devmath_gpu.py, test_fft_regs_gpu.py).
+// test_select_paths_gpu.py, test_devmath_gpu.py, test_fft_regs_gpu.py).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -18,7 +18,7 @@
 __global__ __launch_bounds__(D4C_NT) void k_select_selftest(const double *__restrict__ v, int n, int m,
                                                            double *__restrict__ out) {
   constexpr int RK = 9;
-  __shared__ __attribute__((aligned(16))) uint32_t hist[KWY_SELECT_WORDS(D4C_NT)];
+  __shared__ __attribute__((aligned(16))) uint32_t hist[KWY_SELECT_WORDS(D4C_NT) + KWY_SELECT_WIDE_WORDS];
   __shared__ double red[2 * D4C_NT / 64];
   const int tid = threadIdx.x;
   const double *x = v + (size_t)blockIdx.x * n;
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(D4C_NT) void k_select_selftest(const double *__rest
     key[r] = k < n ? (unsigned long long)__double_as_longlong(x[k]) : ~0ull;
   }
   double s_small, s_all;
-  kwy_block_smallest_sum<RK, D4C_NT>(key, n, m, hist, red, &s_small, &s_all);
+  kwy_block_smallest_sum<RK, D4C_NT>(key, n, m, hist, hist + KWY_SELECT_WORDS(D4C_NT), red, &s_small, &s_all);
   if (tid == 0) { out[2 * blockIdx.x] = s_small; out[2 * blockIdx.x + 1] = s_all; }
 }
 
@@ -37,6 +37,214 @@ extern "C" int kwy_debug_smallest_sum_dev(void *stream, const double *values, in
                                           double *out) {
   if (!values || !out || problems <= 0 || n <= 0 || n > 9 * D4C_NT || m <= 0 || m > n) return -1;
   hipLaunchKernelGGL(k_select_selftest, dim3(problems), dim3(D4C_NT), 0, (hipStream_t)stream, values, n, m, out);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- diagnostic: the select as it was before its from-the-top path got private histogram copies and fewer
+// barriers -- ONE histogram counted with same-address atomics, both sums formed behind the selection and exchanged by
+// kwy_block_sum2 -- kept here as the reference the current one is held to, bit for bit
+// (its scratch: 2 * KWY_SELECT_BINS + 32 words)
+#define REF_SELECT_WORDS (2 * KWY_SELECT_BINS + 32)
+template <int RMAX, int NT = KWY_THREADS>
+__device__ inline void ref_block_smallest_sum(unsigned long long (&key)[RMAX], int n, int m,
+                                              uint32_t *hist, double *red, double *sum_small,
+                                              double *sum_all) {
+  constexpr int BITS = KWY_SELECT_BITS, BINS = 1 << BITS;
+  constexpr int TOP_SHIFT = 18;                           // high word: 20 mantissa bits -> quarter binades
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  uint32_t *ctlb = hist + 2 * BINS;  // 2 x {digit, rank, population, before}; [8..9] one 64-bit key; [10] list
+                                     // length; [11..12] two counts; [16 ..] one word per wavefront
+  unsigned long long *k64 = (unsigned long long *)(ctlb + 8);
+  unsigned long long *list = (unsigned long long *)(hist + BINS);
+  unsigned long long vkey;           // bit pattern of v*
+  int copies;                        // how many keys equal to v* belong to the m smallest
+
+  // ---- (1) from the top
+  uint32_t hmax = 0;
+#pragma unroll
+  for (int r = 0; r < RMAX; ++r)
+    if (tid + NT * r < n) hmax = max(hmax, (uint32_t)(key[r] >> 32));
+  hmax = kwy_wave_max_u32(hmax);
+  if (lane == 0) ctlb[16 + wv] = hmax;
+  for (int i = tid; i < BINS; i += NT) hist[i] = 0;
+  if (tid == 0) ctlb[10] = 0;
+  __syncthreads();
+  hmax = ctlb[16];
+#pragma unroll
+  for (int i = 1; i < NT / 64; ++i) hmax = max(hmax, ctlb[16 + i]);
+  uint32_t dg[RMAX];
+#pragma unroll
+  for (int r = 0; r < RMAX; ++r) {
+    dg[r] = BINS;                                         // (no bin: slot beyond n)
+    if (NT * r + (tid & ~63) >= n) continue;              // nothing in this slot for the whole wavefront
+    if (tid + NT * r < n) {
+      dg[r] = min((hmax - (uint32_t)(key[r] >> 32)) >> TOP_SHIFT, (uint32_t)(BINS - 1));
+      atomicAdd(&hist[dg[r]], 1u);
+    }
+  }
+  __syncthreads();
+  if (wv == 0) kwy_select_scan(hist, n - m + 1, ctlb, lane);
+  __syncthreads();
+  const uint32_t chosen = ctlb[0], pop = ctlb[2];
+  if (chosen < (uint32_t)(BINS - 1) && pop <= (uint32_t)KWY_SELECT_LIST) {
+    const int rank = (int)ctlb[1], above = (int)ctlb[3];
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r)
+      if (dg[r] == chosen) list[atomicAdd(&ctlb[10], 1u)] = key[r];
+    __syncthreads();
+    kwy_select_rank<true>(list, (int)pop, rank, tid, k64, &ctlb[11]);
+    __syncthreads();
+    vkey = *k64;
+    copies = m - (n - above - (int)ctlb[11] - (int)ctlb[12]);   // keys >= v*: above + listed in front + ties
+  } else {
+    // ---- (2) general: the block's smallest and largest key, relative keys, radix rounds
+    double lo = INFINITY, hi = 0.0;
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) {
+      if (tid + NT * r < n) {
+        const double x = __longlong_as_double((long long)key[r]);
+        lo = fmin(lo, x); hi = fmax(hi, x);
+      }
+    }
+    lo = kwy_wave_min_f64(lo);
+    hi = kwy_wave_max_f64(hi);
+    if (lane == 0) { red[wv] = lo; red[NT / 64 + wv] = hi; }
+    for (int i = tid; i < BINS; i += NT) hist[i] = 0;
+    if (tid == 0) ctlb[10] = 0;
+    __syncthreads();
+    lo = red[0]; hi = red[NT / 64];
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) { lo = fmin(lo, red[i]); hi = fmax(hi, red[NT / 64 + i]); }
+    const unsigned long long kmin = (unsigned long long)__double_as_longlong(lo);
+    const unsigned long long range = (unsigned long long)__double_as_longlong(hi) - kmin;
+    const int top0 = range ? 64 - __clzll((long long)range) : 0;     // one past the highest differing bit
+    const int rounds = (top0 + BITS - 1) / BITS;                    // 0: all keys equal
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) key[r] -= kmin;                  // (slots beyond n are never looked at)
+    unsigned long long prefix = 0ull;
+    int kk = m;  // 1-based rank of the wanted element among the still-matching keys
+    bool alive[RMAX];  // key still carries the prefix found so far
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) alive[r] = tid + NT * r < n;
+    for (int round = 0; round < rounds; ++round) {
+      // digits are taken from bit top0 - 1 downwards; the last one may be narrower
+      const int top = top0 - BITS * round;                  // one past the digit's highest bit
+      const int shift = top - BITS > 0 ? top - BITS : 0;
+      const unsigned long long mask = (1ull << (top - shift)) - 1ull;
+      uint32_t *h = hist + (round & 1) * BINS, *hn = hist + ((round + 1) & 1) * BINS;
+      uint32_t *ctl = ctlb + (round & 1) * 4;
+      for (int i = tid; i < BINS; i += NT) hn[i] = 0;
+#pragma unroll
+      for (int r = 0; r < RMAX; ++r) {
+        if (NT * r + (tid & ~63) >= n) continue;  // nothing in this slot for the whole wavefront
+        const int d = (int)((key[r] >> shift) & mask);
+#if KWY_SELECT_AGG
+        const unsigned long long mm = __ballot(alive[r]);
+        if (mm != 0ull) {
+          const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)mm) - 1);
+          const int d0 = __builtin_amdgcn_readlane(d, leader);
+          const bool same = alive[r] && d == d0;
+          const unsigned long long ms = __ballot(same);
+          if (lane == leader) atomicAdd(&h[d0], (uint32_t)__popcll(ms));
+          if (alive[r] && !same) atomicAdd(&h[d], 1u);
+        }
+#else
+        if (alive[r]) atomicAdd(&h[d], 1u);
+#endif
+      }
+      __syncthreads();
+      if (wv == 0) kwy_select_scan(h, kk, ctl, lane);
+      __syncthreads();
+      const int chosen_d = (int)ctl[0];
+      prefix |= (unsigned long long)chosen_d << shift;
+      kk = (int)ctl[1];
+#pragma unroll
+      for (int r = 0; r < RMAX; ++r) alive[r] = alive[r] && (int)((key[r] >> shift) & mask) == chosen_d;
+      const uint32_t left = ctl[2];
+      if (left == 1u && round < rounds - 1) {
+        // exactly one key carries this prefix: it IS the wanted element, skip the remaining rounds
+#pragma unroll
+        for (int r = 0; r < RMAX; ++r)
+          if (alive[r]) *k64 = key[r];
+        __syncthreads();
+        prefix = *k64;
+        kk = 1;
+        break;
+      }
+      if (left <= (uint32_t)KWY_SELECT_LIST && round < rounds - 1) {
+        // a handful of keys carry this prefix: listed in the other histogram's words and ranked against each other
+        unsigned long long *lst = (unsigned long long *)hn;
+#pragma unroll
+        for (int r = 0; r < RMAX; ++r)
+          if (alive[r]) lst[atomicAdd(&ctlb[10], 1u)] = key[r];
+        __syncthreads();
+        kwy_select_rank<false>(lst, (int)left, kk, tid, k64, &ctlb[11]);
+        __syncthreads();
+        prefix = *k64;
+        kk -= (int)ctlb[11];                                // copies of v* among the m smallest
+        break;
+      }
+    }
+    // (all keys equal: no round ran, prefix = 0 = every relative key, kk = m of them)
+    vkey = prefix + kmin;
+    copies = kk;
+#pragma unroll
+    for (int r = 0; r < RMAX; ++r) key[r] += kmin;
+  }
+  const double vstar = __longlong_as_double((long long)vkey);
+  double s_less = 0.0, s_all = 0.0;
+#pragma unroll
+  for (int r = 0; r < RMAX; ++r) {
+    if (tid + NT * r < n) {
+      const double x = __longlong_as_double((long long)key[r]);
+      s_all += x;
+      if (key[r] < vkey) s_less += x;
+    }
+  }
+  double t_less, t_all;
+  kwy_block_sum2<NT>(s_less, s_all, red, &t_less, &t_all);
+  *sum_small = t_less + (double)copies * vstar;
+  *sum_all = t_all;
+}
+
+// both on the same keys, NT threads per problem: out_ref[p], out_new[p] = {sum of the m smallest, sum of all}; the
+// current one in the form the band kernel calls (results in thread 0 only)
+template <int NT>
+__global__ __launch_bounds__(NT) void k_select_paths_selftest(const double *__restrict__ v, int n, int m,
+                                                              double *__restrict__ out_ref, double *__restrict__ out_new) {
+  constexpr int RK = 9;
+  __shared__ __attribute__((aligned(16))) uint32_t hist[KWY_SELECT_WORDS(NT) + KWY_SELECT_WIDE_WORDS];
+  __shared__ double red[2 * NT / 64];
+  static_assert(REF_SELECT_WORDS <= KWY_SELECT_WORDS(NT), "the reference's scratch fits the current one's");
+  const int tid = threadIdx.x;
+  const double *x = v + (size_t)blockIdx.x * n;
+  unsigned long long key[RK];
+#pragma unroll
+  for (int r = 0; r < RK; ++r) {
+    const int k = tid + NT * r;
+    key[r] = k < n ? (unsigned long long)__double_as_longlong(x[k]) : ~0ull;
+  }
+  double s_small, s_all;
+  ref_block_smallest_sum<RK, NT>(key, n, m, hist, red, &s_small, &s_all);
+  if (tid == 0) { out_ref[2 * blockIdx.x] = s_small; out_ref[2 * blockIdx.x + 1] = s_all; }
+  __syncthreads();
+  kwy_block_smallest_sum<RK, NT, false>(key, n, m, hist, hist + KWY_SELECT_WORDS(NT), red, &s_small, &s_all);
+  if (tid == 0) { out_new[2 * blockIdx.x] = s_small; out_new[2 * blockIdx.x + 1] = s_all; }
+}
+
+extern "C" int kwy_debug_select_paths_dev(void *stream, const double *values, int problems, int n, int m,
+                                          double *out_ref, double *out_new) {
+  if (!values || !out_ref || !out_new || problems <= 0 || n <= 0 || n > 9 * 256 || m <= 0 || m > n) return -1;
+  hipLaunchKernelGGL(k_select_paths_selftest<256>, dim3(problems), dim3(256), 0, (hipStream_t)stream, values, n, m,
+                     out_ref, out_new);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+extern "C" int kwy_debug_select_paths512_dev(void *stream, const double *values, int problems, int n, int m,
+                                             double *out_ref, double *out_new) {
+  if (!values || !out_ref || !out_new || problems <= 0 || n <= 0 || n > 9 * 512 || m <= 0 || m > n) return -1;
+  hipLaunchKernelGGL(k_select_paths_selftest<512>, dim3(problems), dim3(512), 0, (hipStream_t)stream, values, n, m,
+                     out_ref, out_new);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
