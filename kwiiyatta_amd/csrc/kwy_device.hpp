@@ -1088,6 +1088,56 @@ __device__ __forceinline__ void kwy_fft_pass8_first_sparse(kwy_c *z, const kwy_c
   kwy_fft_pass8_first_sparse_core<LOG2H, NT, INV>(z, kwy_tw_table{tw}, a0, a1);
 }
 
+// kwy_dft8 of an input whose a[5], a[6], a[7] are zero: the sums and differences with those zeros are left out, every
+// other operation keeps its operands and order, so the values are kwy_dft8's (a zero may come out with the other sign).
+template <bool INV>
+__device__ __forceinline__ void kwy_dft8_low5(kwy_c (&a)[8]) {
+  const double h = 0.70710678118654752440;
+  kwy_c t0 = cadd(a[0], a[4]), t1 = csub(a[0], a[4]);
+  kwy_c t2 = a[2], t3 = kwy_rot90<INV>(a[2]);
+  kwy_c t4 = a[1], t5 = a[1];
+  kwy_c t6 = a[3], t7 = a[3];
+  kwy_c u0 = cadd(t0, t2), u1 = csub(t0, t2), u2 = cadd(t4, t6), u3 = kwy_rot90<INV>(csub(t4, t6));
+  kwy_c c1 = INV ? kwy_c{h * (t5.x - t5.y), h * (t5.x + t5.y)} : kwy_c{h * (t5.x + t5.y), h * (t5.y - t5.x)};
+  kwy_c c3 = INV ? kwy_c{h * (-t7.x - t7.y), h * (t7.x - t7.y)} : kwy_c{h * (t7.y - t7.x), h * (-t7.x - t7.y)};
+  kwy_c v0 = cadd(t1, t3), v1 = csub(t1, t3), v2 = cadd(c1, c3), v3 = kwy_rot90<INV>(csub(c1, c3));
+  a[0] = cadd(u0, u2); a[4] = csub(u0, u2); a[2] = cadd(u1, u3); a[6] = csub(u1, u3);
+  a[1] = cadd(v0, v2); a[5] = csub(v0, v2); a[3] = cadd(v1, v3); a[7] = csub(v1, v3);
+}
+
+// First radix-8 pass (S = 1) of a transform whose input is zero from x[H/2 + 1] on (a real sequence of 2H samples
+// that ends at sample H, packed): inputs 4 .. 7 of every butterfly are known zeros, except x[H/2], input 4 of thread 0.
+// Four (thread 0: five) loads instead of eight, and the caller does not have to write the zeros.  The caller has a
+// barrier between filling z[0 .. H/2] and this call; ends with a barrier.
+template <int LOG2H, int NT, bool INV, class TW>
+__device__ __forceinline__ void kwy_fft_pass8_first_half_core(kwy_c *z, TW tw) {
+  constexpr int H = 1 << LOG2H, Q = H / 8;
+  static_assert(Q <= NT && Q >= 8, "one butterfly per thread");
+  const int j = kwy_tid_opaque();
+  kwy_c a[8];
+  if (j < Q) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) a[m] = z[j + m * Q];
+    a[4] = {0.0, 0.0};
+    if (j == 0) a[4] = z[H / 2];
+    kwy_dft8_low5<INV>(a);
+    kwy_c w1 = tw(j);
+    if (INV) w1.y = -w1.y;
+    const kwy_c w2 = cmulf(w1, w1), w4 = cmulf(w2, w2);
+    const kwy_c w3 = cmulf(w1, w2), w5 = cmulf(w4, w1), w6 = cmulf(w4, w2);
+    const kwy_c w7 = cmulf(w4, w3);
+    a[1] = cmulf(w1, a[1]); a[2] = cmulf(w2, a[2]); a[3] = cmulf(w3, a[3]);
+    a[4] = cmulf(w4, a[4]); a[5] = cmulf(w5, a[5]); a[6] = cmulf(w6, a[6]);
+    a[7] = cmulf(w7, a[7]);
+  }
+  __syncthreads();
+  if (j < Q) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) z[8 * j + (m ^ (j & 7))] = a[m];
+  }
+  __syncthreads();
+}
+
 template <int LOG2H, int TAIL, int NT, bool INV>
 __device__ __forceinline__ void kwy_fft_tail(kwy_c *z);
 
@@ -1260,6 +1310,126 @@ __device__ inline void kwy_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw,
   }
   __syncthreads();
   kwy_fft_inplace<LOG2H, NT, true>(z, tw, pw);
+}
+
+// ---- the real split of the synthesis pulse kernel (k_syn_pulse) and the cepstrum fold behind it
+// The kernel runs NT threads that each stand for the V "virtual" threads t + NT g of a 256-thread workgroup.  Pair
+// twiddles: exp(-2 pi i k / N) for k = t + NT r as base[r % V] times an 8th root of unity,
+// base[g] = exp(-2 pi i (t + NT g) / N).
+template <int LOG2H, int NT, int V>
+__device__ __forceinline__ kwy_c syn_pair_twiddle(const kwy_c (&base)[V], int r) {
+  constexpr int N = 2 << LOG2H;
+  constexpr int OCT = 8 * (NT * V) / N;                     // >= 1: N <= 2048 here, or V = 1 and NT >= N/8
+  return kwy_tw_octant(base[r % V], OCT * (r / V));
+}
+
+// the packed half-length transform in z -> the bins X[0 .. H] in z[0 .. H] (as kwy_rfft_inplace).  Ends with a barrier.
+template <int LOG2H, int NT, int V>
+__device__ __forceinline__ void kwy_syn_rsplit(kwy_c *z, const kwy_c (&base)[V], const kwy_c *__restrict__ twN) {
+  constexpr int H = 1 << LOG2H, N = 2 * H;
+  constexpr bool TABLE = 8 * (NT * V) / N < 1;              // the long transforms read the pair twiddles
+  const int tid = kwy_tid_opaque();
+#pragma unroll
+  for (int r = 0; r * NT <= H / 2; ++r) {
+    const int k = tid + NT * r;
+    if (k > H / 2) continue;
+    if (k == 0) {
+      const kwy_c z0 = z[0];
+      z[0] = {z0.x + z0.y, 0.0};
+      z[H] = {z0.x - z0.y, 0.0};
+    } else {
+      kwy_c w;
+      if constexpr (TABLE) w = twN[k]; else w = syn_pair_twiddle<LOG2H, NT, V>(base, r);
+      const kwy_c A = z[k], Bc = z[H - k];
+      const double er = 0.5 * (A.x + Bc.x), ei = 0.5 * (A.y - Bc.y);
+      const double dr = 0.5 * (A.x - Bc.x), di = 0.5 * (A.y + Bc.y);
+      const double orr = di, oi = -dr;
+      const double pr = __builtin_fma(orr, w.x, -(oi * w.y)), pi = __builtin_fma(orr, w.y, oi * w.x);
+      z[k] = {er + pr, ei + pi};
+      if (k != H - k) z[H - k] = {er - pr, -(ei - pi)};
+    }
+  }
+  __syncthreads();
+}
+
+// The causal fold of the cepstrum whose bins kwy_syn_rsplit left in z (a real, even log-spectrum went in, so only the
+// real parts count): c[0], 2 c[1 .. H-1], c[H] as packed reals over the complex bins they came from; ZEROS: and
+// zeros up to sample N - 1, for a dense first pass behind it.  The caller has a barrier in front; ends with a barrier.
+template <int LOG2H, int NT, bool ZEROS>
+__device__ __forceinline__ void kwy_syn_fold(kwy_c *z) {
+  constexpr int H = 1 << LOG2H, N = 2 * H, RK = (H + 1 + NT - 1) / NT;
+  double *L = (double *)z;
+  const int tid = kwy_tid_opaque();
+  double cv[RK];
+#pragma unroll
+  for (int r = 0; r < RK; ++r) {
+    const int n = tid + NT * r;
+    double v = 0.0;
+    if (n <= H) {
+      v = z[n].x;
+      if (n >= 1 && n < H) v *= 2.0;
+    }
+    cv[r] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < RK; ++r) {
+    const int n = tid + NT * r;
+    if (n <= H) L[n] = cv[r];
+  }
+  if constexpr (ZEROS) {
+    for (int n = H + 1 + tid; n < N; n += NT) L[n] = 0.0;
+  }
+  __syncthreads();
+}
+
+// kwy_syn_rsplit and kwy_syn_fold<.., false> in one: the split forms only the real parts of its pairs (k, H - k), by
+// the same expressions, keeps them in registers with the fold's factor 2, and writes the folded cepstrum behind ONE
+// barrier -- no imaginary parts, no store of the bins and no second read.  ZEROS as for kwy_syn_fold.  Ends with a
+// barrier.
+template <int LOG2H, int NT, int V, bool ZEROS>
+__device__ __forceinline__ void kwy_syn_rsplit_fold(kwy_c *z, const kwy_c (&base)[V], const kwy_c *__restrict__ twN) {
+  constexpr int H = 1 << LOG2H, N = 2 * H, R = H / 2 / NT + 1;
+  constexpr bool TABLE = 8 * (NT * V) / N < 1;
+  double *L = (double *)z;
+  const int tid = kwy_tid_opaque();
+  double lo[R], hi[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid + NT * r;
+    lo[r] = hi[r] = 0.0;
+    if (k > H / 2) continue;
+    if (k == 0) {
+      const kwy_c z0 = z[0];
+      lo[r] = z0.x + z0.y;
+      hi[r] = z0.x - z0.y;
+    } else {
+      kwy_c w;
+      if constexpr (TABLE) w = twN[k]; else w = syn_pair_twiddle<LOG2H, NT, V>(base, r);
+      const kwy_c A = z[k], Bc = z[H - k];
+      const double er = 0.5 * (A.x + Bc.x);
+      const double dr = 0.5 * (A.x - Bc.x), di = 0.5 * (A.y + Bc.y);
+      const double orr = di, oi = -dr;
+      const double pr = __builtin_fma(orr, w.x, -(oi * w.y));
+      double a = er + pr, b = er - pr;
+      a *= 2.0;
+      b *= 2.0;
+      lo[r] = a;
+      hi[r] = b;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = tid + NT * r;
+    if (k > H / 2) continue;
+    L[k] = lo[r];
+    if (k != H - k) L[H - k] = hi[r];
+  }
+  if constexpr (ZEROS) {
+    for (int n = H + 1 + tid; n < N; n += NT) L[n] = 0.0;
+  }
+  __syncthreads();
 }
 
 // Bin k (0 <= k <= H) of the real FFT of the N = 2H reals whose packed

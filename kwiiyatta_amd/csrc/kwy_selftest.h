@@ -33,6 +33,15 @@ int kwy_debug_rfft_paths_dev(void *stream, const double *x, int problems, int lo
  * Synchronises the stream.  Returns 0, -1 (arguments) or -2 (HIP failure). */
 int kwy_debug_fft_powers_dev(void *stream, const double *x, int problems, int log2h, int nt, int inverse,
                              double *out_lane, double *out_table, double *tab, double *tab_ref, double *tab_ref_conj);
+/* The first passes and the real split of the 2048-point synthesis kernel (1024 complex points, 128 threads), every form
+ * on the same rows.  x: problems x 1024 x {re, im} (device).  out_dense, out_sparse, out_half: problems x 1024 x {re, im}
+ * (device): the complex transform through kwy_fft_pass8 (dense), kwy_fft_pass8_first_sparse_core (which takes x[0 .. 128]
+ * from registers and assumes zeros behind) and kwy_fft_pass8_first_half_core (which reads x[0 .. 512] and assumes zeros
+ * behind), the same remaining passes behind each.  fold_ref, fold_new: problems x 1025 doubles (device): the folded
+ * cepstrum behind the dense transform by kwy_syn_rsplit + kwy_syn_fold and by kwy_syn_rsplit_fold.  Synchronises the
+ * stream.  Returns 0, -1 (arguments) or -2 (HIP failure). */
+int kwy_debug_syn_first_passes_dev(void *stream, const double *x, int problems, double *out_dense, double *out_sparse,
+                                   double *out_half, double *fold_ref, double *fold_new);
 #ifdef __cplusplus
 }
 #endif

@@ -811,46 +811,32 @@ __global__ __launch_bounds__(KWY_THREADS) void k_syn_pulse_emit(syn_plan_batch b
 // -- every wavefront works in every pass, and the registers of the idle half buy two more workgroups per CU -- but
 // keeps the arithmetic of the 256-thread form it replaced, bit for bit: thread t stands for the V = 256/NT "virtual"
 // threads t + NT g.  Pair twiddles: exp(-2 pi i k / N) for k = t + NT r as base[r % V] times an 8th root of unity,
-// base[g] = exp(-2 pi i (t + NT g) / N); block sums: the partial sums of the virtual threads, wavefront by
-// wavefront (syn_block_sum_v).
+// base[g] = exp(-2 pi i (t + NT g) / N) (syn_pair_twiddle, kwy_device.hpp); block sums: the partial sums of the virtual
+// threads, wavefront by wavefront (syn_block_sum_v).
 template <int LOG2N>
 struct syn_pulse_nt { static constexpr int value = LOG2N <= 10 ? 64 : (LOG2N == 11 ? 128 : 256); };
 
-template <int LOG2H, int NT, int V>
-__device__ __forceinline__ kwy_c syn_pair_twiddle(const kwy_c (&base)[V], int r) {
-  constexpr int N = 2 << LOG2H;
-  constexpr int OCT = 8 * (NT * V) / N;                     // >= 1: N <= 2048 here, or V = 1 and NT >= N/8
-  return kwy_tw_octant(base[r % V], OCT * (r / V));
-}
+// What the 2048-point kernel (32 - 48 kHz, and 2048-point features at any rate) does differently from the other lengths
+// (profiles/syn6_variants_serial.txt):
+//   * the generator's word sequence lives inside the FFT buffer, which is idle where it is made and read, so that the
+//     LDS request (26 720 B) lets the CU hold six workgroups -- as many as the registers allow -- instead of five;
+//   * the causal cepstrum goes through kwy_fft_pass8_first_half_core, which knows the zero half: no zero fill;
+//   * the split in front of it forms only the real parts the fold reads and writes the folded cepstrum itself
+//     (kwy_syn_rsplit_fold).
+template <int LOG2N>
+struct syn_pulse_form {
+  static constexpr bool SHORT = LOG2N == 11;
+  static constexpr bool E_IN_BUF = SHORT, HALF_FIRST = SHORT, FUSED_FOLD = SHORT;
+  static constexpr int H = 1 << (LOG2N - 1), TWL = (H / 8 > 1) ? H / 8 : 1;
+  static constexpr size_t lds = sizeof(kwy_c) * ((H + 1) + TWL) + sizeof(double) * ((H + 2) + 8) +
+                                (E_IN_BUF ? 0 : sizeof(uint32_t) * KWY_EBASE_WORDS);
+};
 
 template <int LOG2H, int NT, int V>
 __device__ inline void syn_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw, const kwy_c (&base)[V],
                                         const kwy_c *__restrict__ twN) {
-  constexpr int H = 1 << LOG2H, N = 2 * H;
-  constexpr bool TABLE = 8 * (NT * V) / N < 1;              // the long transforms read the pair twiddles
   kwy_fft_inplace<LOG2H, NT, false>(z, tw, pw);
-  const int tid = kwy_tid_opaque();
-#pragma unroll
-  for (int r = 0; r * NT <= H / 2; ++r) {
-    const int k = tid + NT * r;
-    if (k > H / 2) continue;
-    if (k == 0) {
-      const kwy_c z0 = z[0];
-      z[0] = {z0.x + z0.y, 0.0};
-      z[H] = {z0.x - z0.y, 0.0};
-    } else {
-      kwy_c w;
-      if constexpr (TABLE) w = twN[k]; else w = syn_pair_twiddle<LOG2H, NT, V>(base, r);
-      const kwy_c A = z[k], Bc = z[H - k];
-      const double er = 0.5 * (A.x + Bc.x), ei = 0.5 * (A.y - Bc.y);
-      const double dr = 0.5 * (A.x - Bc.x), di = 0.5 * (A.y + Bc.y);
-      const double orr = di, oi = -dr;
-      const double pr = __builtin_fma(orr, w.x, -(oi * w.y)), pi = __builtin_fma(orr, w.y, oi * w.x);
-      z[k] = {er + pr, ei + pi};
-      if (k != H - k) z[H - k] = {er - pr, -(ei - pi)};
-    }
-  }
-  __syncthreads();
+  kwy_syn_rsplit<LOG2H, NT, V>(z, base, twN);
 }
 
 template <int LOG2H, int NT, int V>
@@ -908,8 +894,8 @@ __device__ __forceinline__ double syn_safe_ap(double x) {
 
 // One pulse per workgroup iteration; its response goes to slot (pulse - first_pulse) of `resp`.  LDS: one FFT buffer
 // (in-place transforms), the half log-spectrum of the aperiodic part (formed with the periodic one's in the single pass
-// over the interpolated envelope / aperiodicity rows, which are not kept), a small twiddle table -- 27 KB at 48 kHz:
-// five workgroups of two wavefronts per CU, all ten at work in every pass (the 256-thread form of rounds 1-4 held
+// over the interpolated envelope / aperiodicity rows, which are not kept), a small twiddle table -- 26 720 B at 48 kHz:
+// six workgroups of two wavefronts per CU, all twelve at work in every pass (the 256-thread form of rounds 1-4 held
 // 51 KB and kept half of its twelve wavefronts per CU idle through the seven transforms of a pulse).  What is kept
 // of the periodic response (H samples and a scalar) takes the place of the aperiodic log-spectrum when that moves
 // into the FFT buffer; the minimum-phase spectrum waits in registers while the noise is transformed.
@@ -953,12 +939,17 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
   constexpr int C = N / NT;                // draws / output samples per thread: sample tid + NT m
   constexpr int RK = (H + 1 + NT - 1) / NT;
   constexpr int TWL = (H / 8 > 1) ? H / 8 : 1;
+  typedef syn_pulse_form<LOG2N> F;
   extern __shared__ double smem[];
   double *red = smem;                      // 8
-  uint32_t *e = (uint32_t *)(red + 8);     // KWY_EBASE_WORDS
-  kwy_c *twl = (kwy_c *)(e + KWY_EBASE_WORDS);  // exp(-2 pi i k / H), k < H/8
+  uint32_t *e_own = (uint32_t *)(red + 8); // KWY_EBASE_WORDS, unless the words live in the FFT buffer
+  kwy_c *twl = (kwy_c *)(e_own + (F::E_IN_BUF ? 0 : KWY_EBASE_WORDS));  // exp(-2 pi i k / H), k < H/8
   kwy_c *buf = twl + TWL;                  // H+1 complex
   double *lap = (double *)(buf + (H + 1)); // K: half log-spectrum of the aperiodic part
+  // the generator's word sequence is made and read on the path beyond the noise table only, while the FFT buffer is
+  // idle: behind the 8 KB jump table that is built from it there
+  uint32_t *e = F::E_IN_BUF ? (uint32_t *)(buf + 512) : e_own;
+  static_assert(!F::E_IN_BUF || sizeof(kwy_c) * (H + 1) >= 8192 + sizeof(uint32_t) * KWY_EBASE_WORDS, "no room");
 
   const int tid = threadIdx.x;
   for (int i = tid; i < TWL; i += NT) twl[i] = twH[i];
@@ -1059,31 +1050,19 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
 #pragma nounroll
       for (int it = 0; it < 2 + part; ++it) {
         const int tid = kwy_tid_opaque();
+        bool dense_first = true;             // (2048 points) the first radix-8 pass is still to run
         if (it == 0) {
           __syncthreads();
           for (int i = H + 1 + tid; i < N; i += NT) L[i] = L[N - i];
           __syncthreads();
         } else if (it == 1) {
           // causal cepstrum: c[0], 2 c[1..H-1], c[H], zeros -- packed reals over the complex bins they came from
-          double cv[RK];
-#pragma unroll
-          for (int r = 0; r < RK; ++r) {
-            const int n = tid + NT * r;
-            double v = 0.0;
-            if (n <= H) {
-              v = buf[n].x;
-              if (n >= 1 && n < H) v *= 2.0;
-            }
-            cv[r] = v;
+          // (2048 points: folded by the split of the transform before, and the first pass knows the zeros)
+          if constexpr (!F::FUSED_FOLD) kwy_syn_fold<LOG2N - 1, NT, !F::HALF_FIRST>(buf);
+          if constexpr (F::HALF_FIRST) {
+            kwy_fft_pass8_first_half_core<LOG2N - 1, NT, false>(buf, kwy_tw_table{twl});
+            dense_first = false;
           }
-          __syncthreads();
-#pragma unroll
-          for (int r = 0; r < RK; ++r) {
-            const int n = tid + NT * r;
-            if (n <= H) L[n] = cv[r];
-          }
-          for (int n = H + 1 + tid; n < N; n += NT) L[n] = 0.0;
-          __syncthreads();
         } else {
 #pragma unroll
           for (int r = 0; r < RK; ++r) {
@@ -1137,7 +1116,15 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
           }
           __syncthreads();
         }
-        syn_rfft_inplace<LOG2N - 1, NT, V>(buf, twl, twP, twb, twN);
+        if constexpr (!F::SHORT) {
+          syn_rfft_inplace<LOG2N - 1, NT, V>(buf, twl, twP, twb, twN);
+        } else {
+          // (one copy of each pass in the binary, whichever first pass ran above)
+          if (dense_first) kwy_fft_pass8<LOG2N - 1, 0, NT, false>(buf, twl);
+          kwy_fft_inplace_rest<LOG2N - 1, NT, false>(buf, twl, twP);
+          if (F::FUSED_FOLD && it == 0) kwy_syn_rsplit_fold<LOG2N - 1, NT, V, !F::HALF_FIRST>(buf, twb, twN);
+          else kwy_syn_rsplit<LOG2N - 1, NT, V>(buf, twb, twN);
+        }
         if (it == 1) {
           // (three bins a trip: their exp / sincos chains are independent and fill each other's issue gaps)
           constexpr int G = 3;
@@ -1304,8 +1291,8 @@ static int launch_pulse(kwy_ctx *ctx, syn_batch &batch) {
   KWY_TRY(kwy_get_poly(ctx, 12ull * (N / syn_pulse_nt<LOG2N>::value), &poly));
   KWY_TRY(get_dc_remover(ctx, N, &dcrem));
   constexpr int NT = syn_pulse_nt<LOG2N>::value;
-  size_t lds = sizeof(kwy_c) * ((H + 1) + (H / 8 > 1 ? H / 8 : 1)) +
-               sizeof(double) * ((K + 1) + 8) + sizeof(uint32_t) * KWY_EBASE_WORDS;
+  static_assert(K + 1 == syn_pulse_form<LOG2N>::H + 2, "the log-spectrum rows");
+  size_t lds = syn_pulse_form<LOG2N>::lds;
   KWY_HIP(hipFuncSetAttribute((const void *)k_syn_pulse<LOG2N, false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_HIP(hipFuncSetAttribute((const void *)k_syn_pulse<LOG2N, true>,

@@ -431,3 +431,81 @@ extern "C" int kwy_debug_fft_powers_dev(void *stream, const double *x, int probl
   hipFree(tw);
   return rc;
 }
+
+// ---- diagnostic: the first passes and the real split of the 2048-point synthesis kernel, every form on the same rows ----
+// (one 128-thread workgroup per row of 1024 complex; the passes behind the first one and the transform in front of the
+// split are the same calls in every path.  The half pass gets NaNs where it must not read.)
+template <int = 0>
+__global__ __launch_bounds__(128) void k_syn_first_passes_selftest(const kwy_c *__restrict__ x, const kwy_c *__restrict__ twH,
+                                                                   const kwy_c *__restrict__ twP, const kwy_c *__restrict__ twN,
+                                                                   kwy_c *__restrict__ out_dense, kwy_c *__restrict__ out_sparse,
+                                                                   kwy_c *__restrict__ out_half, double *__restrict__ fold_ref,
+                                                                   double *__restrict__ fold_new) {
+  constexpr int LOG2H = 10, NT = 128, V = 2, H = 1 << LOG2H, Q = H / 8;
+  extern __shared__ double smem[];
+  kwy_c *B = (kwy_c *)smem;          // H + 1 complex
+  const double *L = smem;
+  const int tid = threadIdx.x;
+  const kwy_c *row = x + (size_t)blockIdx.x * H;
+  kwy_c twb[V];
+#pragma unroll
+  for (int g = 0; g < V; ++g) twb[g] = twN[tid + NT * g];
+#pragma nounroll
+  for (int path = 0; path < 5; ++path) {
+    if (path == 1) {
+      const kwy_c a0 = row[tid], a1 = tid == 0 ? row[Q] : kwy_c{0.0, 0.0};
+      kwy_fft_pass8_first_sparse_core<LOG2H, NT, false>(B, kwy_tw_table{twH}, a0, a1);
+    } else if (path == 2) {
+      const double nan = __longlong_as_double(0x7ff8000000000000ll);
+      for (int i = tid; i <= H; i += NT) B[i] = i <= H / 2 ? row[i] : kwy_c{nan, nan};
+      __syncthreads();
+      kwy_fft_pass8_first_half_core<LOG2H, NT, false>(B, kwy_tw_table{twH});
+    } else {
+      for (int i = tid; i < H; i += NT) B[i] = row[i];
+      __syncthreads();
+      kwy_fft_pass8<LOG2H, 0, NT, false>(B, twH);
+    }
+    kwy_fft_inplace_rest<LOG2H, NT, false>(B, twH, twP);
+    if (path < 3) {
+      kwy_c *o = (path == 0 ? out_dense : (path == 1 ? out_sparse : out_half)) + (size_t)blockIdx.x * H;
+      for (int i = tid; i < H; i += NT) o[i] = B[i];
+    } else {
+      if (path == 3) {
+        kwy_syn_rsplit<LOG2H, NT, V>(B, twb, twN);
+        kwy_syn_fold<LOG2H, NT, true>(B);
+      } else {
+        kwy_syn_rsplit_fold<LOG2H, NT, V, true>(B, twb, twN);
+      }
+      double *o = (path == 3 ? fold_ref : fold_new) + (size_t)blockIdx.x * (H + 1);
+      for (int i = tid; i <= H; i += NT) o[i] = L[i];
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" int kwy_debug_syn_first_passes_dev(void *stream, const double *x, int problems, double *out_dense,
+                                              double *out_sparse, double *out_half, double *fold_ref, double *fold_new) {
+  if (!x || !out_dense || !out_sparse || !out_half || !fold_ref || !fold_new || problems <= 0) return -1;
+  constexpr int LOG2H = 10, H = 1 << LOG2H, N = 2 * H;
+  constexpr int TWP = KWY_TWP_ENTRY * KWY_TWP_ENTRIES(LOG2H);        // the powers table behind the two twiddle tables
+  std::vector<kwy_c> h(H / 8 + N + TWP);
+  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * KWY_PI * k / H; h[k] = {cos(a), sin(a)}; }
+  for (int k = 0; k < N; ++k) { const double a = -2.0 * KWY_PI * k / N; h[H / 8 + k] = {cos(a), sin(a)}; }
+  kwy_c *tw = nullptr;
+  if (hipMalloc((void **)&tw, sizeof(kwy_c) * h.size()) != hipSuccess) return -2;
+  int rc = 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * h.size(), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  if (rc == 0) {
+    const size_t lds = sizeof(kwy_c) * (H + 1);
+    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, tw + H / 8 + N,
+                       KWY_TWP_ENTRIES(LOG2H));
+    hipLaunchKernelGGL(k_syn_first_passes_selftest<0>, dim3(problems), dim3(128), lds, s, (const kwy_c *)x, (const kwy_c *)tw,
+                       (const kwy_c *)(tw + H / 8 + N), (const kwy_c *)(tw + H / 8), (kwy_c *)out_dense, (kwy_c *)out_sparse,
+                       (kwy_c *)out_half, fold_ref, fold_new);
+    if (hipGetLastError() != hipSuccess) rc = -2;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
+  (void)hipFree(tw);
+  return rc;
+}
