@@ -14,13 +14,17 @@
 //   k_gmm_cond   four frames per wavefront: arg-max mixture, conditional mean E (from A transposed) and variance D
 //   k_mlpg_build per (frame, dim): the pentadiagonal normal equations W'PW, W'P mu
 //   k_mlpg_chunks / k_mlpg_finish  per static dim: banded Cholesky, partitioned into chunks (nested dissection)
-//   k_em_prep / k_em_estep / k_em_loglik  EM trajectory conversion over soft mixture posteriors (at the end of the file):
+//   k_em_prep / k_em_estep / k_em_loglik  EM trajectory conversion over soft mixture posteriors (below the others):
 //                all M conditional means of a frame tile on the f64 MFMA, online softmax, precision-weighted sums
+// Host side, behind the kernels: one core (ml_convert_core) for arg-max, EM and the GV ascent, one driver for the device
+// entries (ml_convert_jobs), one staging path for the host-pointer entries (ml_convert_host).
 //
 // Algorithmic HBM bytes per frame: d*8 in, d*8 out (+ the GMM once per call).
 #include <math.h>
 
 #include <algorithm>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kwy_internal.hpp"
@@ -894,14 +898,21 @@ __global__ __launch_bounds__(ML_FIN_NT) void k_mlpg_finish(const double *__restr
 #undef ML_STAMP
 }
 
-// ---- host side ------------------------------------------------------------------------------------------
-// T: the frames of all utterances of the call, n: their number
-static size_t ml_scratch_bytes(int64_t T, int d, int M, int n = 1) {
-  const int D = 3 * d;
-  return kwy_pad(sizeof(double) * ml_model_stride(D) * M) + 3 * kwy_pad(sizeof(double) * T * D) +
-         kwy_pad(sizeof(double) * T * M) + kwy_pad(sizeof(int) * T) + kwy_pad(sizeof(double) * T * d * 4) +
-         kwy_pad(sizeof(double) * T * d * 2) + kwy_pad(sizeof(double) * T * d * 4) +
-         kwy_pad(sizeof(double) * (size_t)n * ML_CHUNK_WGS * 64 * ML_BD) + kwy_pad(64);
+// ---- host side: launch geometry ---------------------------------------------------------------------------------------
+#define ML_LDS_MAX (160 * 1024)   // bytes of LDS a workgroup can have
+
+// f(std::integral_constant<int, N>) for the block count nblk = N of 1 .. 6: the kernels with one code path per number
+// of 16-column blocks are templates over it
+template <class F>
+static int ml_with_blocks(int nblk, F f) {
+  switch (nblk) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    default: return f(std::integral_constant<int, 6>());
+  }
 }
 
 // frame-tile walkers per mixture: enough workgroups for every CU (one fits per CU), not more than tiles
@@ -948,14 +959,9 @@ static int ml_launch_frag(kwy_ctx *ctx, const double *X, const ml_dims &dm, cons
 
 static int ml_launch_logp(kwy_ctx *ctx, const double *X, const ml_dims &dm, const double *model, double *logp) {
   if (ml_logp_frag(dm.D)) {
-    switch (ml_frag_blocks(dm.D)) {
-      case 1: return ml_launch_frag<1>(ctx, X, dm, model, logp);
-      case 2: return ml_launch_frag<2>(ctx, X, dm, model, logp);
-      case 3: return ml_launch_frag<3>(ctx, X, dm, model, logp);
-      case 4: return ml_launch_frag<4>(ctx, X, dm, model, logp);
-      case 5: return ml_launch_frag<5>(ctx, X, dm, model, logp);
-      default: return ml_launch_frag<6>(ctx, X, dm, model, logp);
-    }
+    return ml_with_blocks(ml_frag_blocks(dm.D), [&](auto nb) {
+      return ml_launch_frag<decltype(nb)::value>(ctx, X, dm, model, logp);
+    });
   }
   // wider features: rows of Z_m and the frame tile in LDS
   const size_t lds = ml_logp_lds(dm.D);
@@ -981,361 +987,6 @@ static ml_part ml_partition(int64_t T, int d) {
   pt.base = (int)((T - 2 * (pt.P - 1)) / pt.P);
   pt.extra = (int)((T - 2 * (pt.P - 1)) % pt.P);
   return pt;
-}
-
-// The ascent of kwy_gvgen.hip behind a conversion (kwy_gmm_mlpg_gv, include/kwy.h): null means none, and then the cores
-// below enqueue exactly what they did before.  The band records are copied after the build of the last solve, because
-// k_mlpg_chunks consumes its own in place (and, in the EM path, the closing E-step overwrites E / Dv).
-struct ml_gv_opts {
-  const double *mean, *var;       // d values each, on the device
-  double weight;
-  int iterations, offset;
-  double *const *objective;       // per utterance of the batch: iterations + 1 doubles on the device or null; or null
-  int32_t *status;                // per utterance of the batch, or null
-};
-static size_t ml_gv_scratch_bytes(const int64_t *Ts, int n, int d, int iterations) {
-  int64_t T = 0;
-  for (int k = 0; k < n; ++k) T += Ts[k];
-  return kwy_pad(sizeof(double) * T * d * 4) + kwy_gva_scratch_bytes(Ts, n, d, iterations);
-}
-static int ml_gv_ascent(kwy_ctx *ctx, const ml_batch &bt, const int64_t *Ts, int d, const double *band2,
-                        const ml_gv_opts &gv) {
-  kwy_gva_view v[KWY_BATCH_MAX];
-  for (int k = 0; k < bt.n; ++k)
-    v[k] = kwy_gva_view{band2 + bt.start[k] * d * 4, gv.offset ? bt.u[k].x : nullptr, bt.u[k].y, Ts[k], bt.ldy, bt.ldx,
-                        gv.objective ? gv.objective[k] : nullptr, gv.status ? gv.status + k : nullptr};
-  return kwy_gva_launch(ctx, v, bt.n, d, gv.mean, gv.var, gv.weight, gv.iterations);
-}
-
-// One conversion call over a batch of utterances: bt.n, bt.ldx / ldy and every u[k].x / y / keep_* filled in by the
-// caller, Ts[k] the utterances' frames.  `prepared`: a model made by kwy_gmm_prepare_dev (then weights / means / covs
-// are unused), or null.
-static int mlpg_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d, int M, const double *weights,
-                           const double *means, const double *covs, int diff, int **status_out,
-                           const double *prepared, const ml_gv_opts *gv = nullptr) {
-  const int D = 3 * d, n = bt.n;
-  int64_t T = 0;
-  int Pmax = 1;
-  for (int k = 0; k < n; ++k) {
-    bt.start[k] = T;
-    T += Ts[k];
-    bt.u[k].pt = ml_partition(Ts[k], d);
-    Pmax = std::max(Pmax, bt.u[k].pt.P);
-  }
-  for (int k = n; k <= KWY_BATCH_MAX; ++k) bt.start[k] = T;
-  for (int k = n; k < KWY_BATCH_MAX; ++k) bt.u[k] = bt.u[0];
-  ml_dims dm = {d, D, M, T};
-  double *model = prepared ? const_cast<double *>(prepared) : kwy_arena<double>(ctx, ml_model_stride(D) * M);
-  double *X = kwy_arena<double>(ctx, (size_t)T * D);
-  double *E = kwy_arena<double>(ctx, (size_t)T * D);
-  double *Dv = kwy_arena<double>(ctx, (size_t)T * D);
-  double *logp = kwy_arena<double>(ctx, (size_t)T * M);
-  int *mix = kwy_arena<int>(ctx, T);
-  double *band = kwy_arena<double>(ctx, (size_t)T * d * 4);   // records {P0, P1, P2, rhs}
-  double *rhs = kwy_arena<double>(ctx, (size_t)T * d * 2);    // forward solutions of the two top columns
-  double *Ysp = kwy_arena<double>(ctx, (size_t)T * d * 4);
-  double *bnd = kwy_arena<double>(ctx, (size_t)n * ML_CHUNK_WGS * 64 * ML_BD);
-  int *status = kwy_arena<int>(ctx, 16);
-  double *band2 = gv ? kwy_arena<double>(ctx, (size_t)T * d * 4) : band;
-  if (!model || !X || !E || !Dv || !logp || !mix || !band || !rhs || !Ysp || !bnd || !status || !band2) {
-    ctx->err = "gmm_mlpg: scratch arena too small";
-    return KWY_ENOMEM;
-  }
-  *status_out = status;
-  KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
-  size_t lds_prep = sizeof(double) * 3 * D * D;
-  size_t lds_logp = ml_logp_frag(D) ? ml_frag_lds(D) : ml_logp_lds(D);
-  if (lds_prep > 160 * 1024 || lds_logp > 160 * 1024) { ctx->err = "gmm_mlpg: feature dimension too large"; return KWY_EINVAL; }
-  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-  const int cpw = 64 / d;
-  const size_t lds_solve = sizeof(double) * ((size_t)d * 2 * (Pmax - 1) * 5 + 8);
-  if (lds_solve > 160 * 1024) { ctx->err = "gmm_mlpg: static dimension too large"; return KWY_EINVAL; }
-  KWY_HIP(hipFuncSetAttribute((const void *)k_mlpg_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_solve));
-  if (!prepared)
-    hipLaunchKernelGGL(k_gmm_prep, dim3(M), dim3(KWY_THREADS), lds_prep, ctx->stream, weights, means, covs, D,
-                       diff, model, status);
-  const unsigned ge = (unsigned)((T * d + 255) / 256);
-  hipLaunchKernelGGL(k_delta, dim3(ge), dim3(256), 0, ctx->stream, bt, dm, X);
-  KWY_TRY(ml_launch_logp(ctx, X, dm, model, logp));
-  hipLaunchKernelGGL(k_gmm_cond, dim3((unsigned)((T + ML_COND_F * ML_COND_W - 1) / (ML_COND_F * ML_COND_W))), dim3(64 * ML_COND_W), 0, ctx->stream, X, dm, model, logp, E, Dv, mix);
-  hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, E, Dv, bt, dm, band);
-  if (gv) KWY_HIP(hipMemcpyAsync(band2, band, sizeof(double) * T * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0, ctx->stream,
-                                                     band, rhs, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
-  {
-    int64_t Tmax = 0;
-    for (int k = 0; k < n; ++k) Tmax = std::max(Tmax, Ts[k]);
-    int fin = (int)((Tmax * d + 4 * ML_FIN_NT - 1) / (4 * ML_FIN_NT));
-    if (fin > ML_FIN_WGS) fin = ML_FIN_WGS;
-    KWY_PROF(ctx, "k_mlpg_finish", hipLaunchKernelGGL(k_mlpg_finish, dim3((unsigned)fin, n), dim3(ML_FIN_NT), lds_solve, ctx->stream,
-                                                       band, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
-  }
-  KWY_HIP(hipGetLastError());
-  if (gv) KWY_TRY(ml_gv_ascent(ctx, bt, Ts, d, band2, *gv));
-  return KWY_OK;
-}
-
-// one utterance.  x / y: T x d with rows ldx / ldy doubles apart (0: packed); keep_in / keep_out: see k_delta
-static int mlpg_core(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
-                     const double *means, const double *covs, int diff, double *y, int **status_out,
-                     const double *prepared = nullptr, int ldx = 0, int ldy = 0, const double *keep_in = nullptr,
-                     double *keep_out = nullptr) {
-  ml_batch bt;
-  bt.n = 1;
-  bt.ldx = ldx > 0 ? ldx : d;
-  bt.ldy = ldy > 0 ? ldy : d;
-  bt.u[0].x = x; bt.u[0].y = y; bt.u[0].keep_in = keep_in; bt.u[0].keep_out = keep_out;
-  return mlpg_batch_core(ctx, bt, &T, d, M, weights, means, covs, diff, status_out, prepared);
-}
-
-// x, y: T x D device rows; weights / means / covs: the joint mixture over 2 D dimensions, on the device
-static int soft_core(kwy_ctx *ctx, const double *x, int64_t T, int D, int M, const double *weights,
-                     const double *means, const double *covs, int diff, double *y, int **status_out) {
-  ml_dims dm = {D, D, M, T};
-  double *model = kwy_arena<double>(ctx, ml_model_stride(D) * M);
-  double *logp = kwy_arena<double>(ctx, (size_t)T * M);
-  int *status = kwy_arena<int>(ctx, 16);
-  if (!model || !logp || !status) { ctx->err = "gmm_convert_frames: scratch arena too small"; return KWY_ENOMEM; }
-  *status_out = status;
-  KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
-  const size_t lds_prep = sizeof(double) * 3 * D * D;
-  const size_t lds_logp = ml_logp_frag(D) ? ml_frag_lds(D) : ml_logp_lds(D);
-  if (lds_prep > 160 * 1024 || lds_logp > 160 * 1024 || D > 192 || M > 256) {
-    // (3 D^2 doubles of LDS for the preparation: 160 KB hold D <= 82)
-    ctx->err = "gmm_convert_frames: feature dimension (<= 82 per side) or mixture count (<= 256) too large";
-    return KWY_EINVAL;
-  }
-  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-  hipLaunchKernelGGL(k_gmm_prep, dim3(M), dim3(KWY_THREADS), lds_prep, ctx->stream, weights, means, covs, D, diff, model,
-                     status);
-  KWY_TRY(ml_launch_logp(ctx, x, dm, model, logp));
-  hipLaunchKernelGGL(k_gmm_soft, dim3((unsigned)T), dim3(128), 0, ctx->stream, x, dm, model, logp, y);
-  KWY_HIP(hipGetLastError());
-  return KWY_OK;
-}
-
-static size_t soft_scratch_bytes(int64_t T, int D, int M) {
-  return kwy_pad(sizeof(double) * ml_model_stride(D) * M) + kwy_pad(sizeof(double) * T * M) + kwy_pad(64);
-}
-
-static int soft_check(kwy_ctx *ctx, const void *x, int64_t T, int D, int M, const void *w, const void *mu,
-                      const void *cv, const void *y) {
-  if (!ctx) return KWY_EINVAL;
-  if (!x || !w || !mu || !cv || !y || T <= 0 || D <= 0 || M <= 0) {
-    ctx->err = "gmm_convert_frames: bad argument";
-    return KWY_EINVAL;
-  }
-  return KWY_OK;
-}
-
-extern "C" int kwy_gmm_convert_frames_dev(kwy_ctx *ctx, const double *x, int64_t T, int D, int M,
-                                          const double *weights, const double *means, const double *covs, int diff,
-                                          double *y) {
-  KWY_TRY(soft_check(ctx, x, T, D, M, weights, means, covs, y));
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, soft_scratch_bytes(T, D, M)));
-  int *status;
-  return soft_core(ctx, x, T, D, M, weights, means, covs, diff, y, &status);
-}
-
-extern "C" int kwy_gmm_convert_frames(kwy_ctx *ctx, const double *x, int64_t T, int D, int M, const double *weights,
-                                      const double *means, const double *covs, int diff, double *y) {
-  KWY_TRY(soft_check(ctx, x, T, D, M, weights, means, covs, y));
-  KWY_HIP(hipSetDevice(ctx->device));
-  const int D2 = 2 * D;
-  const size_t bx = kwy_pad(sizeof(double) * T * D), bw = kwy_pad(sizeof(double) * M);
-  const size_t bm = kwy_pad(sizeof(double) * M * D2), bc = kwy_pad(sizeof(double) * (size_t)M * D2 * D2);
-  KWY_TRY(kwy_arena_begin(ctx, soft_scratch_bytes(T, D, M) + 2 * bx + bw + bm + bc));
-  double *dx = kwy_arena<double>(ctx, (size_t)T * D), *dy = kwy_arena<double>(ctx, (size_t)T * D);
-  double *dw = kwy_arena<double>(ctx, M), *dmu = kwy_arena<double>(ctx, (size_t)M * D2);
-  double *dcv = kwy_arena<double>(ctx, (size_t)M * D2 * D2);
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * T * D, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dw, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dmu, means, sizeof(double) * M * D2, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dcv, covs, sizeof(double) * (size_t)M * D2 * D2, hipMemcpyHostToDevice, ctx->stream));
-  int *status;
-  KWY_TRY(soft_core(ctx, dx, T, D, M, dw, dmu, dcv, diff, dy, &status));
-  int hstatus = 0;
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * T * D, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  if (hstatus != 0) { ctx->err = "gmm_convert_frames: source covariance is not positive definite"; return KWY_ENUMERIC; }
-  return KWY_OK;
-}
-
-static int ml_check(kwy_ctx *ctx, const void *x, int64_t T, int d, int M, const void *w, const void *mu,
-                    const void *cv, const void *y) {
-  if (!ctx) return KWY_EINVAL;
-  if (!x || !w || !mu || !cv || !y || T <= 0 || d <= 0 || d > 64 || M <= 0) {
-    ctx->err = "gmm_mlpg: bad argument";
-    return KWY_EINVAL;
-  }
-  return KWY_OK;
-}
-
-extern "C" int kwy_gmm_mlpg_dev(kwy_ctx *ctx, const double *x, int64_t T, int d, int M,
-                                const double *weights, const double *means, const double *covs, int diff,
-                                double *y) {
-  KWY_TRY(ml_check(ctx, x, T, d, M, weights, means, covs, y));
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, ml_scratch_bytes(T, d, M)));
-  int *status;
-  return mlpg_core(ctx, x, T, d, M, weights, means, covs, diff, y, &status);
-}
-
-extern "C" int64_t kwy_gmm_model_doubles(int d, int M) {
-  if (d <= 0 || d > 64 || M <= 0) return 0;
-  return (int64_t)ml_model_stride(3 * d) * M;
-}
-
-extern "C" int kwy_gmm_prepare_dev(kwy_ctx *ctx, const double *weights, const double *means, const double *covs,
-                                   int d, int M, int diff, double *model) {
-  if (!ctx) return KWY_EINVAL;
-  if (!weights || !means || !covs || !model || d <= 0 || d > 64 || M <= 0) {
-    ctx->err = "gmm_prepare: bad argument";
-    return KWY_EINVAL;
-  }
-  KWY_HIP(hipSetDevice(ctx->device));
-  const int D = 3 * d;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(64)));
-  int *status = kwy_arena<int>(ctx, 16);
-  if (!status) { ctx->err = "gmm_prepare: scratch arena too small"; return KWY_ENOMEM; }
-  KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
-  size_t lds_prep = sizeof(double) * 3 * D * D;
-  if (lds_prep > 160 * 1024) { ctx->err = "gmm_prepare: feature dimension too large"; return KWY_EINVAL; }
-  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-  KWY_PROF(ctx, "k_gmm_prep", hipLaunchKernelGGL(k_gmm_prep, dim3(M), dim3(KWY_THREADS), lds_prep, ctx->stream, weights, means, covs, D,
-                     diff, model, status));
-  KWY_HIP(hipGetLastError());
-  int hstatus = 0;
-  KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  if (hstatus != 0) { ctx->err = "gmm_prepare: source covariance is not positive definite"; return KWY_ENUMERIC; }
-  return KWY_OK;
-}
-
-extern "C" int kwy_gmm_mlpg_model_dev(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *model,
-                                      double *y) {
-  KWY_TRY(ml_check(ctx, x, T, d, M, model, model, model, y));
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, ml_scratch_bytes(T, d, M)));
-  int *status;
-  return mlpg_core(ctx, x, T, d, M, nullptr, nullptr, nullptr, 0, y, &status, model);
-}
-
-// MelCepstrumFeatureConverter.convert at the converter's own sampling rate (kwiiyatta/converter/mcep.py:47-61):
-// mc, mc_out: T x (d + 1) mel-cepstra; column 0 (power) is copied, columns 1..d go through delta + GMM + MLPG.
-extern "C" int kwy_convert_mcep_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
-                                    double *mc_out) {
-  KWY_TRY(ml_check(ctx, mc, T, d, M, model, model, model, mc_out));
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, ml_scratch_bytes(T, d, M)));
-  int *status;
-  return mlpg_core(ctx, mc + 1, T, d, M, nullptr, nullptr, nullptr, 0, mc_out + 1, &status, model, d + 1, d + 1, mc,
-                   mc_out);
-}
-
-// a batch of conversions with a prepared model, KWY_BATCH_MAX utterances per pass of launches.  Utterance j reads the
-// d static coefficients of row t at x[j] + t * ldx and gets its trajectory at y[j] + t * ldy: the final store of
-// k_mlpg_finish runs along the coefficient index whatever the row stride, so consecutive lanes write consecutive
-// doubles of a row.  keep_in / keep_out (arrays, or null): one more column copied through (k_delta).
-static int convert_batch_strided(kwy_ctx *ctx, int count, const double *const *x, const int64_t *T, double *const *y,
-                                 const double *const *keep_in, double *const *keep_out, int ldx, int ldy, int d, int M,
-                                 const double *model) {
-  size_t bytes = 0;
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    int64_t Tsum = 0;
-    const int n = std::min(KWY_BATCH_MAX, count - j0);
-    for (int j = j0; j < j0 + n; ++j) {
-      KWY_TRY(ml_check(ctx, x[j], T[j], d, M, model, model, model, y[j]));
-      Tsum += T[j];
-    }
-    bytes += ml_scratch_bytes(Tsum, d, M, n);
-  }
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    ml_batch bt;
-    int64_t Ts[KWY_BATCH_MAX];
-    bt.n = std::min(KWY_BATCH_MAX, count - j0);
-    bt.ldx = ldx;
-    bt.ldy = ldy;
-    for (int k = 0; k < bt.n; ++k) {
-      bt.u[k].x = x[j0 + k]; bt.u[k].y = y[j0 + k];
-      bt.u[k].keep_in = keep_in ? keep_in[j0 + k] : nullptr;
-      bt.u[k].keep_out = keep_out ? keep_out[j0 + k] : nullptr;
-      Ts[k] = T[j0 + k];
-    }
-    int *status;
-    KWY_TRY(mlpg_batch_core(ctx, bt, Ts, d, M, nullptr, nullptr, nullptr, 0, &status, model));
-  }
-  return KWY_OK;
-}
-
-extern "C" int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *jobs, int count, int d, int M,
-                                          const double *model) {
-  if (!ctx) return KWY_EINVAL;
-  if (!jobs || count < 0) { ctx->err = "convert_mcep_batch: bad argument"; return KWY_EINVAL; }
-  if (count == 0) return KWY_OK;
-  std::vector<const double *> x(count), keep_in(count);
-  std::vector<double *> y(count), keep_out(count);
-  std::vector<int64_t> T(count);
-  for (int j = 0; j < count; ++j) {
-    const kwy_convert_job &q = jobs[j];
-    // (a null matrix stays null for ml_check: no pointer arithmetic on it)
-    x[j] = q.mc ? q.mc + 1 : nullptr; y[j] = q.mc_out ? q.mc_out + 1 : nullptr;
-    keep_in[j] = q.mc; keep_out[j] = q.mc_out; T[j] = q.T;
-  }
-  return convert_batch_strided(ctx, count, x.data(), T.data(), y.data(), keep_in.data(), keep_out.data(), d + 1, d + 1, d,
-                               M, model);
-}
-
-// Re-alignment of a training pair (include/kwy.h): the conversion of kwy_convert_mcep_batch_dev, its trajectories
-// stored straight into columns 2.. of the DTW feature rows (row stride d + 2); columns 0 and 1 (the source's own power
-// and voicing terms) are not touched, and there is no T x (d + 1) intermediate.
-extern "C" int kwy_realign_features_batch_dev(kwy_ctx *ctx, const kwy_realign_job *jobs, int count, int d, int M,
-                                              const double *model) {
-  if (!ctx) return KWY_EINVAL;
-  if (!jobs || count < 0) { ctx->err = "realign_features_batch: bad argument"; return KWY_EINVAL; }
-  if (count == 0) return KWY_OK;
-  std::vector<const double *> x(count);
-  std::vector<double *> y(count);
-  std::vector<int64_t> T(count);
-  for (int j = 0; j < count; ++j) {
-    const kwy_realign_job &q = jobs[j];
-    x[j] = q.mc ? q.mc + 1 : nullptr; y[j] = q.feat ? q.feat + 2 : nullptr; T[j] = q.T;
-  }
-  return convert_batch_strided(ctx, count, x.data(), T.data(), y.data(), nullptr, nullptr, d + 1, d + 2, d, M, model);
-}
-
-extern "C" int kwy_gmm_mlpg(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
-                            const double *means, const double *covs, int diff, double *y) {
-  KWY_TRY(ml_check(ctx, x, T, d, M, weights, means, covs, y));
-  KWY_HIP(hipSetDevice(ctx->device));
-  const int D2 = 6 * d;
-  size_t bx = kwy_pad(sizeof(double) * T * d), bw = kwy_pad(sizeof(double) * M);
-  size_t bm = kwy_pad(sizeof(double) * M * D2), bc = kwy_pad(sizeof(double) * (size_t)M * D2 * D2);
-  KWY_TRY(kwy_arena_begin(ctx, ml_scratch_bytes(T, d, M) + 2 * bx + bw + bm + bc));
-  double *dx = kwy_arena<double>(ctx, (size_t)T * d), *dy = kwy_arena<double>(ctx, (size_t)T * d);
-  double *dw = kwy_arena<double>(ctx, M), *dmu = kwy_arena<double>(ctx, (size_t)M * D2);
-  double *dcv = kwy_arena<double>(ctx, (size_t)M * D2 * D2);
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * T * d, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dw, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dmu, means, sizeof(double) * M * D2, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dcv, covs, sizeof(double) * (size_t)M * D2 * D2, hipMemcpyHostToDevice, ctx->stream));
-  int *status;
-  KWY_TRY(mlpg_core(ctx, dx, T, d, M, dw, dmu, dcv, diff, dy, &status));
-  int hstatus = 0;
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * T * d, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  if (hstatus != 0) {
-    ctx->err = hstatus == 1 ? "gmm_mlpg: source covariance is not positive definite"
-                            : "gmm_mlpg: MLPG system is not positive definite";
-    return KWY_ENUMERIC;
-  }
-  return KWY_OK;
 }
 
 // ---- EM trajectory conversion over soft mixture posteriors (Toda et al. 2007, section IV) -----------------------
@@ -1576,36 +1227,153 @@ __global__ __launch_bounds__(256) void k_em_loglik(const double *__restrict__ ls
   if (tid == 0) dst[k] = red[0];
 }
 
-static size_t ml_em_scratch_bytes(int64_t T, int d, int M, int n = 1) {
-  return ml_scratch_bytes(T, d, M, n) + kwy_pad(sizeof(double) * (size_t)M * 3 * d) + kwy_pad(sizeof(double) * M) +
-         kwy_pad(sizeof(double) * T);
-}
-
+// ---- host side: the conversion ----------------------------------------------------------------------------------------
 static size_t ml_em_lds(int nblk) { return sizeof(double) * ((size_t)4 * nblk * nblk * 64 + 48 * nblk); }
 
-template <int NBLK>
-static void ml_launch_estep(kwy_ctx *ctx, const double *X, const ml_dims &dm, const ml_batch &bt, const double *model,
-                            const double *logp, const double *iv, const double *lc, int first, double *E, double *Dv,
-                            double *lse) {
-  const unsigned grid = (unsigned)((dm.T + ML_EM_TILE - 1) / ML_EM_TILE);
-  KWY_PROF(ctx, "k_em_estep", hipLaunchKernelGGL(k_em_estep<NBLK>, dim3(grid), dim3(64 * ML_EM_NW), ml_em_lds(NBLK),
-                                                 ctx->stream, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse));
-}
+// The mixture of a call: the joint mixture's parameters on the device, or a model made by kwy_gmm_prepare_dev (then
+// weights / means / covs only stand in for it where the arguments are checked).
+struct ml_mixture {
+  const double *weights, *means, *covs;
+  int diff;
+  const double *prepared;
+};
+static ml_mixture ml_prepared(const double *model) { return ml_mixture{model, model, model, 0, model}; }
 
-template <int NBLK>
-static int ml_estep_attr(kwy_ctx *ctx) {
-  KWY_HIP(hipFuncSetAttribute((const void *)k_em_estep<NBLK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)ml_em_lds(NBLK)));
+// The ascent of kwy_gvgen.hip behind a conversion (kwy_gmm_mlpg_gv, include/kwy.h): null means none.  The band records
+// are copied after the build of the last solve, because k_mlpg_chunks consumes its own in place (and, with EM, the
+// closing E-step overwrites E / Dv).
+struct ml_gv_opts {
+  const double *mean, *var;       // d values each
+  double weight;
+  int iterations, offset;
+  int32_t *status;                // one word per utterance of the call on the device, or null
+};
+struct ml_opts {
+  int em;                         // EM re-estimations of the posteriors; -1: one arg-max mixture per frame
+  bool em_only;                   // set by the kwy_*_em entries: they have no arg-max form, so em = -1 is refused
+  const ml_gv_opts *gv;
+};
+// one utterance: T x d static features and their trajectory (row strides: the call's), one more column copied through
+// (k_delta; or null), em + 1 log-likelihoods and gv->iterations + 1 objective values on the device (or null)
+struct ml_job {
+  const double *x;
+  double *y;
+  const double *keep_in;
+  double *keep_out;
+  int64_t T;
+  double *loglik, *objective;
+};
+
+static int ml_check(kwy_ctx *ctx, const ml_job &q, int d, int M, const ml_mixture &gm, const ml_opts &o) {
+  if (!ctx) return KWY_EINVAL;
+  if (!q.x || !gm.weights || !gm.means || !gm.covs || !q.y || q.T <= 0 || d <= 0 || d > 64 || M <= 0) {
+    ctx->err = "gmm_mlpg: bad argument";
+    return KWY_EINVAL;
+  }
+  // (the GV entries take em = -1 as "arg-max"; to the EM entries it is an iteration count out of range)
+  if (o.em_only || o.em != -1) {
+    if (o.em < 0 || o.em > KWY_MLPG_EM_MAX) {
+      ctx->err = "gmm_mlpg_em: em_iterations outside [0, KWY_MLPG_EM_MAX]";
+      return KWY_EINVAL;
+    }
+    // what kwy_gmm_prepare_dev refuses (three D x D matrices in LDS) cannot arrive here as a prepared model either
+    if (sizeof(double) * 3 * (3 * d) * (3 * d) > ML_LDS_MAX || ml_frag_blocks(3 * d) > ML_EM_MAXBLK) {
+      ctx->err = "gmm_mlpg_em: feature dimension too large";
+      return KWY_EINVAL;
+    }
+  }
+  if (o.gv) {
+    if (!o.gv->mean || !o.gv->var) { ctx->err = "gmm_mlpg_gv: bad argument"; return KWY_EINVAL; }
+    if (!(o.gv->weight > 0.0 && o.gv->weight <= 1.79769313486231570815e+308)) {
+      ctx->err = "gmm_mlpg_gv: weight must be positive and finite";
+      return KWY_EINVAL;
+    }
+    if (o.gv->iterations < 0 || o.gv->iterations > KWY_MLPG_GV_MAX) {
+      ctx->err = "gmm_mlpg_gv: gv_iterations outside [0, KWY_MLPG_GV_MAX]";
+      return KWY_EINVAL;
+    }
+  }
   return KWY_OK;
 }
 
-// the counterpart of mlpg_batch_core: em_iterations + 1 trajectory solves, an E-step before each, and one more after
-// the last where a log-likelihood is asked for.  lik[k]: utterance k's em_iterations + 1 doubles on the device, or null.
-static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int d, int M, const double *weights,
-                              const double *means, const double *covs, int diff, int **status_out,
-                              const double *prepared, int em_iterations, double *const *lik,
-                              const ml_gv_opts *gv = nullptr) {
+// The arena buffers of a call are described once, by a function that names each pointer with its element count: walked
+// with ctx == null it sums the bytes kwy_arena_begin is asked for, walked with the context it takes them, in that order.
+struct ml_arena {
+  kwy_ctx *ctx;
+  size_t bytes = 0;
+  bool ok = true;
+  template <class T>
+  void take(T *&p, size_t n) {
+    bytes += kwy_pad(sizeof(T) * n);
+    if (ctx && !(p = kwy_arena<T>(ctx, n))) ok = false;
+  }
+};
+
+// the work buffers of one pass of the core over n utterances with T frames in all
+struct ml_work {
+  double *model, *X, *E, *Dv, *logp;
+  int *mix;
+  double *band, *rhs, *Ysp, *bnd;
+  double *iv, *lc, *lse;
+  int *status;
+  double *band2;
+};
+static void ml_work_buffers(ml_arena &a, ml_work &w, int64_t T, int n, int d, int M, const ml_mixture &gm, const ml_opts &o) {
+  const int D = 3 * d;
+  if (gm.prepared) w.model = const_cast<double *>(gm.prepared);
+  else a.take(w.model, ml_model_stride(D) * M);
+  a.take(w.X, (size_t)T * D);
+  a.take(w.E, (size_t)T * D);
+  a.take(w.Dv, (size_t)T * D);
+  a.take(w.logp, (size_t)T * M);
+  if (o.em < 0) a.take(w.mix, T);
+  a.take(w.band, (size_t)T * d * 4);   // records {P0, P1, P2, rhs}
+  a.take(w.rhs, (size_t)T * d * 2);    // forward solutions of the two top columns
+  a.take(w.Ysp, (size_t)T * d * 4);
+  a.take(w.bnd, (size_t)n * ML_CHUNK_WGS * 64 * ML_BD);
+  if (o.em >= 0) {
+    a.take(w.iv, (size_t)M * D);
+    a.take(w.lc, M);
+    a.take(w.lse, T);
+  }
+  a.take(w.status, 16);
+  if (o.gv) a.take(w.band2, (size_t)T * d * 4);
+  else w.band2 = w.band;
+}
+// what a pass asks of the arena: its work buffers and the ascent's scratch
+static size_t ml_pass_bytes(const int64_t *Ts, int n, int d, int M, const ml_mixture &gm, const ml_opts &o) {
+  int64_t T = 0;
+  for (int k = 0; k < n; ++k) T += Ts[k];
+  ml_arena a{nullptr};
+  ml_work w = {};
+  ml_work_buffers(a, w, T, n, d, M, gm, o);
+  return a.bytes + (o.gv ? kwy_gva_scratch_bytes(Ts, n, d, o.gv->iterations) : 0);
+}
+
+// k_gmm_prep keeps three D x D matrices in LDS, the log-density kernels Z_m or its fragments and a frame tile
+static size_t ml_prep_lds(int D) { return sizeof(double) * 3 * D * D; }
+static bool ml_lds_fits(int D) {
+  return ml_prep_lds(D) <= ML_LDS_MAX && (ml_logp_frag(D) ? ml_frag_lds(D) : ml_logp_lds(D)) <= ML_LDS_MAX;
+}
+// the preparation of the mixture over D dimensions per side: its LDS attribute, and the launch
+static int ml_prep_attr(kwy_ctx *ctx, int D) {
+  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml_prep_lds(D)));
+  return KWY_OK;
+}
+static void ml_launch_prep(kwy_ctx *ctx, const ml_mixture &gm, int D, int M, double *model, int *status) {
+  hipLaunchKernelGGL(k_gmm_prep, dim3(M), dim3(KWY_THREADS), ml_prep_lds(D), ctx->stream, gm.weights, gm.means, gm.covs, D,
+                     gm.diff, model, status);
+}
+
+// One conversion over a batch of utterances: bt.n, bt.ldx / ldy and every u[k].x / y / keep_* filled in by the caller,
+// Ts[k] the utterances' frames.  o.em + 1 trajectory solves; with EM an E-step before each, and one more after the last
+// where a log-likelihood is asked for (lik[k]: utterance k's o.em + 1 doubles on the device, or null).  objective[k]:
+// the ascent's o.gv->iterations + 1 doubles of utterance k, or null.  who: the prefix of its messages.
+static int ml_convert_core(kwy_ctx *ctx, const char *who, ml_batch &bt, const int64_t *Ts, int d, int M,
+                           const ml_mixture &gm, const ml_opts &o, double *const *lik, double *const *objective,
+                           int **status_out) {
   const int D = 3 * d, n = bt.n, nblk = ml_frag_blocks(D);
+  const bool em = o.em >= 0;
   int64_t T = 0, Tmax = 0;
   int Pmax = 1;
   bool want_lik = false;
@@ -1616,315 +1384,420 @@ static int mlpg_em_batch_core(kwy_ctx *ctx, ml_batch &bt, const int64_t *Ts, int
     Tmax = std::max(Tmax, Ts[k]);
     bt.u[k].pt = ml_partition(Ts[k], d);
     Pmax = std::max(Pmax, bt.u[k].pt.P);
-    out.loglik[k] = lik ? lik[k] : nullptr;
+    out.loglik[k] = em ? lik[k] : nullptr;
     want_lik = want_lik || out.loglik[k];
   }
   for (int k = n; k <= KWY_BATCH_MAX; ++k) bt.start[k] = T;
   for (int k = n; k < KWY_BATCH_MAX; ++k) { bt.u[k] = bt.u[0]; out.loglik[k] = nullptr; }
   ml_dims dm = {d, D, M, T};
-  double *model = prepared ? const_cast<double *>(prepared) : kwy_arena<double>(ctx, ml_model_stride(D) * M);
-  double *X = kwy_arena<double>(ctx, (size_t)T * D);
-  double *E = kwy_arena<double>(ctx, (size_t)T * D);
-  double *Dv = kwy_arena<double>(ctx, (size_t)T * D);
-  double *logp = kwy_arena<double>(ctx, (size_t)T * M);
-  double *band = kwy_arena<double>(ctx, (size_t)T * d * 4);
-  double *rhs = kwy_arena<double>(ctx, (size_t)T * d * 2);
-  double *Ysp = kwy_arena<double>(ctx, (size_t)T * d * 4);
-  double *bnd = kwy_arena<double>(ctx, (size_t)n * ML_CHUNK_WGS * 64 * ML_BD);
-  double *iv = kwy_arena<double>(ctx, (size_t)M * D);
-  double *lc = kwy_arena<double>(ctx, M);
-  double *lse = kwy_arena<double>(ctx, T);
-  int *status = kwy_arena<int>(ctx, 16);
-  double *band2 = gv ? kwy_arena<double>(ctx, (size_t)T * d * 4) : band;
-  if (!model || !X || !E || !Dv || !logp || !band || !rhs || !Ysp || !bnd || !iv || !lc || !lse || !status || !band2) {
-    ctx->err = "gmm_mlpg_em: scratch arena too small";
-    return KWY_ENOMEM;
-  }
-  *status_out = status;
-  KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
-  const size_t lds_prep = sizeof(double) * 3 * D * D;
+  ml_arena a{ctx};
+  ml_work w = {};
+  ml_work_buffers(a, w, T, n, d, M, gm, o);
+  if (!a.ok) { ctx->err = std::string(who) + ": scratch arena too small"; return KWY_ENOMEM; }
+  *status_out = w.status;
+  KWY_HIP(hipMemsetAsync(w.status, 0, sizeof(int) * 16, ctx->stream));
   const int cpw = 64 / d;
   const size_t lds_solve = sizeof(double) * ((size_t)d * 2 * (Pmax - 1) * 5 + 8);
-  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_prep));
-  KWY_HIP(hipFuncSetAttribute((const void *)k_mlpg_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds_solve));
-  switch (nblk) {
-    case 1: KWY_TRY(ml_estep_attr<1>(ctx)); break;
-    case 2: KWY_TRY(ml_estep_attr<2>(ctx)); break;
-    case 3: KWY_TRY(ml_estep_attr<3>(ctx)); break;
-    case 4: KWY_TRY(ml_estep_attr<4>(ctx)); break;
-    case 5: KWY_TRY(ml_estep_attr<5>(ctx)); break;
-    default: KWY_TRY(ml_estep_attr<6>(ctx)); break;
-  }
+  if (!ml_lds_fits(D)) { ctx->err = std::string(who) + ": feature dimension too large"; return KWY_EINVAL; }
+  if (lds_solve > ML_LDS_MAX) { ctx->err = std::string(who) + ": static dimension too large"; return KWY_EINVAL; }
+  KWY_HIP(hipFuncSetAttribute((const void *)k_mlpg_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
+  if (em)
+    KWY_TRY(ml_with_blocks(nblk, [&](auto nb) -> int {
+      KWY_HIP(hipFuncSetAttribute((const void *)k_em_estep<decltype(nb)::value>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml_em_lds(decltype(nb)::value)));
+      return KWY_OK;
+    }));
   auto estep = [&](int first) {
-    switch (nblk) {
-      case 1: ml_launch_estep<1>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
-      case 2: ml_launch_estep<2>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
-      case 3: ml_launch_estep<3>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
-      case 4: ml_launch_estep<4>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
-      case 5: ml_launch_estep<5>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
-      default: ml_launch_estep<6>(ctx, X, dm, bt, model, logp, iv, lc, first, E, Dv, lse); break;
-    }
+    ml_with_blocks(nblk, [&](auto nb) -> int {
+      constexpr int NBLK = decltype(nb)::value;
+      KWY_PROF(ctx, "k_em_estep", hipLaunchKernelGGL(k_em_estep<NBLK>, dim3((unsigned)((T + ML_EM_TILE - 1) / ML_EM_TILE)),
+                                                     dim3(64 * ML_EM_NW), ml_em_lds(NBLK), ctx->stream, w.X, dm, bt, w.model,
+                                                     w.logp, w.iv, w.lc, first, w.E, w.Dv, w.lse));
+      return 0;
+    });
   };
-  if (!prepared)
-    hipLaunchKernelGGL(k_gmm_prep, dim3(M), dim3(KWY_THREADS), lds_prep, ctx->stream, weights, means, covs, D,
-                       diff, model, status);
+  KWY_TRY(ml_prep_attr(ctx, D));
+  if (!gm.prepared) ml_launch_prep(ctx, gm, D, M, w.model, w.status);
   const unsigned ge = (unsigned)((T * d + 255) / 256);
-  hipLaunchKernelGGL(k_delta, dim3(ge), dim3(256), 0, ctx->stream, bt, dm, X);
-  KWY_TRY(ml_launch_logp(ctx, X, dm, model, logp));
-  hipLaunchKernelGGL(k_em_prep, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, ctx->stream, model, D, M, iv, lc);
-  estep(1);
+  hipLaunchKernelGGL(k_delta, dim3(ge), dim3(256), 0, ctx->stream, bt, dm, w.X);
+  KWY_TRY(ml_launch_logp(ctx, w.X, dm, w.model, w.logp));
+  if (em) {
+    hipLaunchKernelGGL(k_em_prep, dim3((unsigned)((M + 63) / 64)), dim3(64), 0, ctx->stream, w.model, D, M, w.iv, w.lc);
+    estep(1);
+  } else {
+    hipLaunchKernelGGL(k_gmm_cond, dim3((unsigned)((T + ML_COND_F * ML_COND_W - 1) / (ML_COND_F * ML_COND_W))),
+                       dim3(64 * ML_COND_W), 0, ctx->stream, w.X, dm, w.model, w.logp, w.E, w.Dv, w.mix);
+  }
   int fin = (int)((Tmax * d + 4 * ML_FIN_NT - 1) / (4 * ML_FIN_NT));
   if (fin > ML_FIN_WGS) fin = ML_FIN_WGS;
-  for (int k = 0; k <= em_iterations; ++k) {
-    hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, E, Dv, bt, dm, band);
-    if (gv && k == em_iterations)
-      KWY_HIP(hipMemcpyAsync(band2, band, sizeof(double) * T * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0, ctx->stream,
-                                                       band, rhs, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
-    KWY_PROF(ctx, "k_mlpg_finish", hipLaunchKernelGGL(k_mlpg_finish, dim3((unsigned)fin, n), dim3(ML_FIN_NT), lds_solve, ctx->stream,
-                                                       band, Ysp, bnd, dm, bt, status, (long long *)ctx->dbg));
-    if (k < em_iterations || want_lik) {
+  const int solves = std::max(o.em, 0) + 1;
+  for (int k = 0; k < solves; ++k) {
+    hipLaunchKernelGGL(k_mlpg_build, dim3(ge), dim3(256), 0, ctx->stream, w.E, w.Dv, bt, dm, w.band);
+    if (o.gv && k == solves - 1)
+      KWY_HIP(hipMemcpyAsync(w.band2, w.band, sizeof(double) * T * d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    KWY_PROF(ctx, "k_mlpg_chunks", hipLaunchKernelGGL(k_mlpg_chunks, dim3((unsigned)((Pmax + cpw - 1) / cpw), n), dim3(64), 0,
+                                                       ctx->stream, w.band, w.rhs, w.Ysp, w.bnd, dm, bt, w.status,
+                                                       (long long *)ctx->dbg));
+    KWY_PROF(ctx, "k_mlpg_finish", hipLaunchKernelGGL(k_mlpg_finish, dim3((unsigned)fin, n), dim3(ML_FIN_NT), lds_solve,
+                                                       ctx->stream, w.band, w.Ysp, w.bnd, dm, bt, w.status,
+                                                       (long long *)ctx->dbg));
+    if (em && (k < o.em || want_lik)) {
       estep(0);
-      if (want_lik) hipLaunchKernelGGL(k_em_loglik, dim3(n), dim3(256), 0, ctx->stream, lse, bt, out, k);
+      if (want_lik) hipLaunchKernelGGL(k_em_loglik, dim3(n), dim3(256), 0, ctx->stream, w.lse, bt, out, k);
     }
   }
   KWY_HIP(hipGetLastError());
-  if (gv) KWY_TRY(ml_gv_ascent(ctx, bt, Ts, d, band2, *gv));
+  if (!o.gv) return KWY_OK;
+  kwy_gva_view v[KWY_BATCH_MAX];
+  for (int k = 0; k < n; ++k)
+    v[k] = kwy_gva_view{w.band2 + bt.start[k] * d * 4, o.gv->offset ? bt.u[k].x : nullptr, bt.u[k].y, Ts[k], bt.ldy, bt.ldx,
+                        objective[k], o.gv->status ? o.gv->status + k : nullptr};
+  return kwy_gva_launch(ctx, v, n, d, o.gv->mean, o.gv->var, o.gv->weight, o.gv->iterations);
+}
+
+// one pass of launches: jobs q[0 .. n), n <= KWY_BATCH_MAX, the first of them job `first` of the call.  Utterance j
+// reads the d static coefficients of row t at x + t * ldx and gets its trajectory at y + t * ldy: the final store of
+// k_mlpg_finish runs along the coefficient index whatever the row stride, so consecutive lanes write consecutive
+// doubles of a row.
+static int ml_convert_pass(kwy_ctx *ctx, const ml_job *q, int n, int first, int ldx, int ldy, int d, int M,
+                           const ml_mixture &gm, ml_opts o, int **status_out) {
+  ml_batch bt;
+  int64_t Ts[KWY_BATCH_MAX];
+  double *lik[KWY_BATCH_MAX], *obj[KWY_BATCH_MAX];
+  bt.n = n;
+  bt.ldx = ldx;
+  bt.ldy = ldy;
+  for (int k = 0; k < n; ++k) {
+    bt.u[k].x = q[k].x; bt.u[k].y = q[k].y; bt.u[k].keep_in = q[k].keep_in; bt.u[k].keep_out = q[k].keep_out;
+    Ts[k] = q[k].T;
+    lik[k] = q[k].loglik;
+    obj[k] = q[k].objective;
+  }
+  ml_gv_opts gv;
+  if (o.gv) {
+    gv = *o.gv;
+    if (gv.status) gv.status += first;
+    o.gv = &gv;
+  }
+  return ml_convert_core(ctx, o.em < 0 ? "gmm_mlpg" : "gmm_mlpg_em", bt, Ts, d, M, gm, o, lik, obj, status_out);
+}
+
+// A call on device pointers: `count` jobs, job j as read(j) gives it, KWY_BATCH_MAX of them per pass.  Every job is
+// checked before anything is enqueued.  entry: the name of a batch entry for the check of its own arguments, or null.
+template <class READ>
+static int ml_convert_jobs(kwy_ctx *ctx, const char *entry, const void *jobs, int count, READ read, int ldx, int ldy, int d,
+                           int M, const ml_mixture &gm, const ml_opts &o) {
+  if (!ctx) return KWY_EINVAL;
+  if (entry && (!jobs || count < 0)) { ctx->err = std::string(entry) + ": bad argument"; return KWY_EINVAL; }
+  if (count == 0) return KWY_OK;
+  ml_job one;                      // a single-utterance entry allocates nothing
+  std::vector<ml_job> many(count > 1 ? count : 0);
+  ml_job *q = count > 1 ? many.data() : &one;
+  size_t bytes = 0;
+  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
+    int64_t Ts[KWY_BATCH_MAX];
+    const int n = std::min(KWY_BATCH_MAX, count - j0);
+    for (int k = 0; k < n; ++k) {
+      q[j0 + k] = read(j0 + k);
+      KWY_TRY(ml_check(ctx, q[j0 + k], d, M, gm, o));
+      Ts[k] = q[j0 + k].T;
+    }
+    bytes += ml_pass_bytes(Ts, n, d, M, gm, o);
+  }
+  KWY_HIP(hipSetDevice(ctx->device));
+  KWY_TRY(kwy_arena_begin(ctx, bytes));
+  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
+    int *status;
+    KWY_TRY(ml_convert_pass(ctx, &q[j0], std::min(KWY_BATCH_MAX, count - j0), j0, ldx, ldy, d, M, gm, o, &status));
+  }
   return KWY_OK;
 }
 
-static int ml_em_check(kwy_ctx *ctx, const void *x, int64_t T, int d, int M, const void *w, const void *mu,
-                       const void *cv, const void *y, int em_iterations) {
-  KWY_TRY(ml_check(ctx, x, T, d, M, w, mu, cv, y));
-  if (em_iterations < 0 || em_iterations > KWY_MLPG_EM_MAX) {
-    ctx->err = "gmm_mlpg_em: em_iterations outside [0, KWY_MLPG_EM_MAX]";
+// a T x (d + 1) mel-cepstrum matrix as a job: column 0 (power) is copied, columns 1 .. d are converted.  A null matrix
+// stays null for ml_check: no pointer arithmetic on it.
+static ml_job ml_mcep_job(const double *mc, int64_t T, double *mc_out, double *loglik = nullptr,
+                          double *objective = nullptr) {
+  return ml_job{mc ? mc + 1 : nullptr, mc_out ? mc_out + 1 : nullptr, mc, mc_out, T, loglik, objective};
+}
+
+static const ml_opts ML_ARGMAX = {-1, false, nullptr};
+
+extern "C" int kwy_gmm_mlpg_dev(kwy_ctx *ctx, const double *x, int64_t T, int d, int M,
+                                const double *weights, const double *means, const double *covs, int diff,
+                                double *y) {
+  const ml_job job = {x, y, nullptr, nullptr, T, nullptr, nullptr};
+  return ml_convert_jobs(ctx, nullptr, nullptr, 1, [&](int) { return job; }, d, d, d, M,
+                         ml_mixture{weights, means, covs, diff, nullptr}, ML_ARGMAX);
+}
+
+extern "C" int64_t kwy_gmm_model_doubles(int d, int M) {
+  if (d <= 0 || d > 64 || M <= 0) return 0;
+  return (int64_t)ml_model_stride(3 * d) * M;
+}
+
+extern "C" int kwy_gmm_prepare_dev(kwy_ctx *ctx, const double *weights, const double *means, const double *covs,
+                                   int d, int M, int diff, double *model) {
+  if (!ctx) return KWY_EINVAL;
+  if (!weights || !means || !covs || !model || d <= 0 || d > 64 || M <= 0) {
+    ctx->err = "gmm_prepare: bad argument";
     return KWY_EINVAL;
   }
-  // what kwy_gmm_prepare_dev refuses (three D x D matrices in LDS) cannot arrive here as a prepared model either
-  if (sizeof(double) * 3 * (3 * d) * (3 * d) > 160 * 1024 || ml_frag_blocks(3 * d) > ML_EM_MAXBLK) {
-    ctx->err = "gmm_mlpg_em: feature dimension too large";
-    return KWY_EINVAL;
-  }
+  KWY_HIP(hipSetDevice(ctx->device));
+  const int D = 3 * d;
+  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(64)));
+  int *status = kwy_arena<int>(ctx, 16);
+  if (!status) { ctx->err = "gmm_prepare: scratch arena too small"; return KWY_ENOMEM; }
+  KWY_HIP(hipMemsetAsync(status, 0, sizeof(int) * 16, ctx->stream));
+  if (ml_prep_lds(D) > ML_LDS_MAX) { ctx->err = "gmm_prepare: feature dimension too large"; return KWY_EINVAL; }
+  KWY_TRY(ml_prep_attr(ctx, D));
+  KWY_PROF(ctx, "k_gmm_prep", ml_launch_prep(ctx, ml_mixture{weights, means, covs, diff, nullptr}, D, M, model, status));
+  KWY_HIP(hipGetLastError());
+  int hstatus = 0;
+  KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  if (hstatus != 0) { ctx->err = "gmm_prepare: source covariance is not positive definite"; return KWY_ENUMERIC; }
   return KWY_OK;
+}
+
+extern "C" int kwy_gmm_mlpg_model_dev(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *model,
+                                      double *y) {
+  const ml_job job = {x, y, nullptr, nullptr, T, nullptr, nullptr};
+  return ml_convert_jobs(ctx, nullptr, nullptr, 1, [&](int) { return job; }, d, d, d, M, ml_prepared(model), ML_ARGMAX);
+}
+
+// MelCepstrumFeatureConverter.convert at the converter's own sampling rate (kwiiyatta/converter/mcep.py:47-61):
+// mc, mc_out: T x (d + 1) mel-cepstra; column 0 (power) is copied, columns 1..d go through delta + GMM + MLPG.
+extern "C" int kwy_convert_mcep_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
+                                    double *mc_out) {
+  return ml_convert_jobs(ctx, nullptr, nullptr, 1, [&](int) { return ml_mcep_job(mc, T, mc_out); }, d + 1, d + 1, d, M,
+                         ml_prepared(model), ML_ARGMAX);
+}
+
+extern "C" int kwy_convert_mcep_batch_dev(kwy_ctx *ctx, const kwy_convert_job *jobs, int count, int d, int M,
+                                          const double *model) {
+  return ml_convert_jobs(ctx, "convert_mcep_batch", jobs, count,
+                         [&](int j) { return ml_mcep_job(jobs[j].mc, jobs[j].T, jobs[j].mc_out); }, d + 1, d + 1, d, M,
+                         ml_prepared(model), ML_ARGMAX);
+}
+
+// Re-alignment of a training pair (include/kwy.h): the conversion of kwy_convert_mcep_batch_dev, its trajectories
+// stored straight into columns 2.. of the DTW feature rows (row stride d + 2); columns 0 and 1 (the source's own power
+// and voicing terms) are not touched, and there is no T x (d + 1) intermediate.
+extern "C" int kwy_realign_features_batch_dev(kwy_ctx *ctx, const kwy_realign_job *jobs, int count, int d, int M,
+                                              const double *model) {
+  return ml_convert_jobs(ctx, "realign_features_batch", jobs, count, [&](int j) {
+    const kwy_realign_job &q = jobs[j];
+    return ml_job{q.mc ? q.mc + 1 : nullptr, q.feat ? q.feat + 2 : nullptr, nullptr, nullptr, q.T, nullptr, nullptr};
+  }, d + 1, d + 2, d, M, ml_prepared(model), ML_ARGMAX);
 }
 
 extern "C" int kwy_convert_mcep_em_batch_dev(kwy_ctx *ctx, const kwy_convert_em_job *jobs, int count, int d, int M,
                                              const double *model, int em_iterations) {
-  if (!ctx) return KWY_EINVAL;
-  if (!jobs || count < 0) { ctx->err = "convert_mcep_em_batch: bad argument"; return KWY_EINVAL; }
-  if (count == 0) return KWY_OK;
-  size_t bytes = 0;
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    int64_t Tsum = 0;
-    const int n = std::min(KWY_BATCH_MAX, count - j0);
-    for (int j = j0; j < j0 + n; ++j) {
-      KWY_TRY(ml_em_check(ctx, jobs[j].mc, jobs[j].T, d, M, model, model, model, jobs[j].mc_out, em_iterations));
-      Tsum += jobs[j].T;
-    }
-    bytes += ml_em_scratch_bytes(Tsum, d, M, n);
-  }
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    ml_batch bt;
-    int64_t Ts[KWY_BATCH_MAX];
-    double *lik[KWY_BATCH_MAX];
-    bt.n = std::min(KWY_BATCH_MAX, count - j0);
-    bt.ldx = d + 1;
-    bt.ldy = d + 1;
-    for (int k = 0; k < bt.n; ++k) {
-      const kwy_convert_em_job &q = jobs[j0 + k];
-      bt.u[k].x = q.mc + 1; bt.u[k].y = q.mc_out + 1;
-      bt.u[k].keep_in = q.mc; bt.u[k].keep_out = q.mc_out;
-      Ts[k] = q.T;
-      lik[k] = q.loglik;
-    }
-    int *status;
-    KWY_TRY(mlpg_em_batch_core(ctx, bt, Ts, d, M, nullptr, nullptr, nullptr, 0, &status, model, em_iterations, lik));
-  }
-  return KWY_OK;
+  return ml_convert_jobs(ctx, "convert_mcep_em_batch", jobs, count,
+                         [&](int j) { return ml_mcep_job(jobs[j].mc, jobs[j].T, jobs[j].mc_out, jobs[j].loglik); }, d + 1,
+                         d + 1, d, M, ml_prepared(model), ml_opts{em_iterations, true, nullptr});
 }
 
 extern "C" int kwy_convert_mcep_em_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
                                        int em_iterations, double *mc_out, double *loglik) {
-  if (!ctx) return KWY_EINVAL;
-  kwy_convert_em_job job = {mc, T, mc_out, loglik};
+  const kwy_convert_em_job job = {mc, T, mc_out, loglik};
   return kwy_convert_mcep_em_batch_dev(ctx, &job, 1, d, M, model, em_iterations);
 }
 
-extern "C" int kwy_gmm_mlpg_em(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
-                               const double *means, const double *covs, int diff, int em_iterations, double *y,
-                               double *loglik) {
-  KWY_TRY(ml_em_check(ctx, x, T, d, M, weights, means, covs, y, em_iterations));
-  KWY_HIP(hipSetDevice(ctx->device));
-  const int D2 = 6 * d;
-  size_t bx = kwy_pad(sizeof(double) * T * d), bw = kwy_pad(sizeof(double) * M);
-  size_t bm = kwy_pad(sizeof(double) * M * D2), bc = kwy_pad(sizeof(double) * (size_t)M * D2 * D2);
-  KWY_TRY(kwy_arena_begin(ctx, ml_em_scratch_bytes(T, d, M) + 2 * bx + bw + bm + bc +
-                                   kwy_pad(sizeof(double) * (KWY_MLPG_EM_MAX + 1))));
-  double *dx = kwy_arena<double>(ctx, (size_t)T * d), *dy = kwy_arena<double>(ctx, (size_t)T * d);
-  double *dw = kwy_arena<double>(ctx, M), *dmu = kwy_arena<double>(ctx, (size_t)M * D2);
-  double *dcv = kwy_arena<double>(ctx, (size_t)M * D2 * D2);
-  double *dlik = kwy_arena<double>(ctx, KWY_MLPG_EM_MAX + 1);
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * T * d, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dw, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dmu, means, sizeof(double) * M * D2, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dcv, covs, sizeof(double) * (size_t)M * D2 * D2, hipMemcpyHostToDevice, ctx->stream));
-  ml_batch bt;
-  bt.n = 1;
-  bt.ldx = d;
-  bt.ldy = d;
-  bt.u[0].x = dx; bt.u[0].y = dy; bt.u[0].keep_in = nullptr; bt.u[0].keep_out = nullptr;
-  double *lik[1] = {loglik ? dlik : nullptr};
-  int *status;
-  KWY_TRY(mlpg_em_batch_core(ctx, bt, &T, d, M, dw, dmu, dcv, diff, &status, nullptr, em_iterations, lik));
-  int hstatus = 0;
-  std::vector<double> hl(em_iterations + 1);
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * T * d, hipMemcpyDeviceToHost, ctx->stream));
-  if (loglik) KWY_HIP(hipMemcpyAsync(hl.data(), dlik, sizeof(double) * (em_iterations + 1), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  if (hstatus != 0) {
-    ctx->err = hstatus == 1 ? "gmm_mlpg_em: source covariance is not positive definite"
-                            : "gmm_mlpg_em: MLPG system is not positive definite";
-    return KWY_ENUMERIC;
-  }
-  if (loglik) std::copy(hl.begin(), hl.end(), loglik);
-  return KWY_OK;
-}
-
-// ---- the conversion with the GV ascent behind it (kwy_gvgen.hip; the contract is kwy_gv_ascent's in include/kwy.h) ----
-static int ml_gv_check(kwy_ctx *ctx, const void *x, int64_t T, int d, int M, const void *w, const void *mu,
-                       const void *cv, const void *y, int em_iterations, const void *gv_mean, const void *gv_var,
-                       double weight, int gv_iterations) {
-  if (em_iterations == -1) KWY_TRY(ml_check(ctx, x, T, d, M, w, mu, cv, y));
-  else KWY_TRY(ml_em_check(ctx, x, T, d, M, w, mu, cv, y, em_iterations));
-  if (!gv_mean || !gv_var) { ctx->err = "gmm_mlpg_gv: bad argument"; return KWY_EINVAL; }
-  if (!(weight > 0.0 && weight <= 1.79769313486231570815e+308)) {
-    ctx->err = "gmm_mlpg_gv: weight must be positive and finite";
-    return KWY_EINVAL;
-  }
-  if (gv_iterations < 0 || gv_iterations > KWY_MLPG_GV_MAX) {
-    ctx->err = "gmm_mlpg_gv: gv_iterations outside [0, KWY_MLPG_GV_MAX]";
-    return KWY_EINVAL;
-  }
-  return KWY_OK;
-}
-
-static size_t ml_gv_total_bytes(const int64_t *Ts, int n, int d, int M, int em_iterations, int gv_iterations) {
-  int64_t T = 0;
-  for (int k = 0; k < n; ++k) T += Ts[k];
-  return (em_iterations < 0 ? ml_scratch_bytes(T, d, M, n) : ml_em_scratch_bytes(T, d, M, n)) +
-         ml_gv_scratch_bytes(Ts, n, d, gv_iterations);
-}
-
+// the conversion with the GV ascent behind it (kwy_gvgen.hip; the contract is kwy_gv_ascent's in include/kwy.h)
 extern "C" int kwy_convert_mcep_gv_batch_dev(kwy_ctx *ctx, const kwy_convert_gv_job *jobs, int count, int d, int M,
                                              const double *model, int em_iterations, int gv_offset,
                                              const double *gv_mean, const double *gv_var, double weight,
                                              int gv_iterations, int32_t *status) {
-  if (!ctx) return KWY_EINVAL;
-  if (!jobs || count < 0) { ctx->err = "convert_mcep_gv_batch: bad argument"; return KWY_EINVAL; }
-  if (count == 0) return KWY_OK;
-  size_t bytes = 0;
-  std::vector<int64_t> T(count);
-  for (int j = 0; j < count; ++j) {
-    KWY_TRY(ml_gv_check(ctx, jobs[j].mc, jobs[j].T, d, M, model, model, model, jobs[j].mc_out, em_iterations, gv_mean,
-                        gv_var, weight, gv_iterations));
-    T[j] = jobs[j].T;
-  }
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX)
-    bytes += ml_gv_total_bytes(T.data() + j0, std::min(KWY_BATCH_MAX, count - j0), d, M, em_iterations, gv_iterations);
-  KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    ml_batch bt;
-    double *lik[KWY_BATCH_MAX], *obj[KWY_BATCH_MAX];
-    bt.n = std::min(KWY_BATCH_MAX, count - j0);
-    bt.ldx = d + 1;
-    bt.ldy = d + 1;
-    for (int k = 0; k < bt.n; ++k) {
-      const kwy_convert_gv_job &q = jobs[j0 + k];
-      bt.u[k].x = q.mc + 1; bt.u[k].y = q.mc_out + 1;
-      bt.u[k].keep_in = q.mc; bt.u[k].keep_out = q.mc_out;
-      lik[k] = q.loglik;
-      obj[k] = q.objective;
-    }
-    const ml_gv_opts gv = {gv_mean, gv_var, weight, gv_iterations, gv_offset, obj, status ? status + j0 : nullptr};
-    int *st;
-    if (em_iterations < 0)
-      KWY_TRY(mlpg_batch_core(ctx, bt, T.data() + j0, d, M, nullptr, nullptr, nullptr, 0, &st, model, &gv));
-    else
-      KWY_TRY(mlpg_em_batch_core(ctx, bt, T.data() + j0, d, M, nullptr, nullptr, nullptr, 0, &st, model, em_iterations,
-                                 lik, &gv));
-  }
-  return KWY_OK;
+  const ml_gv_opts gv = {gv_mean, gv_var, weight, gv_iterations, gv_offset, status};
+  return ml_convert_jobs(ctx, "convert_mcep_gv_batch", jobs, count, [&](int j) {
+    return ml_mcep_job(jobs[j].mc, jobs[j].T, jobs[j].mc_out, jobs[j].loglik, jobs[j].objective);
+  }, d + 1, d + 1, d, M, ml_prepared(model), ml_opts{em_iterations, false, &gv});
 }
 
 extern "C" int kwy_convert_mcep_gv_dev(kwy_ctx *ctx, const double *mc, int64_t T, int d, int M, const double *model,
                                        int em_iterations, int gv_offset, const double *gv_mean, const double *gv_var,
                                        double weight, int gv_iterations, double *mc_out, double *loglik,
                                        double *objective, int32_t *status) {
-  if (!ctx) return KWY_EINVAL;
-  kwy_convert_gv_job job = {mc, T, mc_out, loglik, objective};
+  const kwy_convert_gv_job job = {mc, T, mc_out, loglik, objective};
   return kwy_convert_mcep_gv_batch_dev(ctx, &job, 1, d, M, model, em_iterations, gv_offset, gv_mean, gv_var, weight,
                                        gv_iterations, status);
+}
+
+// ---- the entries on host pointers ---------------------------------------------------------------------------------
+// device copies of what such a call brings and takes home: x and y (T rows of `width`), the joint mixture over `joint`
+// dimensions, and where asked for the log-likelihoods, the ascent's objective, its statistics and its status word
+struct ml_staged {
+  double *x, *y, *w, *mu, *cv, *lik, *obj, *gv_mean, *gv_var;
+  int32_t *gv_status;
+};
+static void ml_staged_buffers(ml_arena &a, ml_staged &s, int64_t T, int width, int M, int joint, bool lik, bool gv) {
+  a.take(s.x, (size_t)T * width);
+  a.take(s.y, (size_t)T * width);
+  a.take(s.w, M);
+  a.take(s.mu, (size_t)M * joint);
+  a.take(s.cv, (size_t)M * joint * joint);
+  if (lik) a.take(s.lik, KWY_MLPG_EM_MAX + 1);
+  if (gv) {
+    a.take(s.obj, KWY_MLPG_GV_MAX + 1);
+    a.take(s.gv_mean, width);
+    a.take(s.gv_var, width);
+    a.take(s.gv_status, 16);
+  }
+}
+static int ml_upload(kwy_ctx *ctx, const ml_staged &s, const double *x, int64_t T, int width, int M, int joint,
+                     const double *weights, const double *means, const double *covs) {
+  KWY_HIP(hipMemcpyAsync(s.x, x, sizeof(double) * T * width, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(s.w, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(s.mu, means, sizeof(double) * M * joint, hipMemcpyHostToDevice, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(s.cv, covs, sizeof(double) * (size_t)M * joint * joint, hipMemcpyHostToDevice, ctx->stream));
+  return KWY_OK;
+}
+// y, the optional series (nl log-likelihoods, no objective values) and the status words in one synchronisation; the
+// core's status word 1 or 2 becomes the entry's message, and then only y has been written
+static int ml_read_back(kwy_ctx *ctx, const char *entry, const ml_staged &s, const int *core_status, double *y,
+                        size_t ny, double *loglik, int nl, double *objective, int no, int32_t *gv_status) {
+  int hstatus = 0;
+  int32_t hgv = 0;
+  std::vector<double> hl(nl), ho(no);
+  KWY_HIP(hipMemcpyAsync(y, s.y, sizeof(double) * ny, hipMemcpyDeviceToHost, ctx->stream));
+  if (nl) KWY_HIP(hipMemcpyAsync(hl.data(), s.lik, sizeof(double) * nl, hipMemcpyDeviceToHost, ctx->stream));
+  if (no) KWY_HIP(hipMemcpyAsync(ho.data(), s.obj, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipMemcpyAsync(&hstatus, core_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  if (no) KWY_HIP(hipMemcpyAsync(&hgv, s.gv_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  if (hstatus != 0) {
+    ctx->err = std::string(entry) + (hstatus == 1 ? ": source covariance is not positive definite"
+                                                  : ": MLPG system is not positive definite");
+    return KWY_ENUMERIC;
+  }
+  if (loglik) std::copy(hl.begin(), hl.end(), loglik);
+  if (objective) std::copy(ho.begin(), ho.end(), objective);
+  if (gv_status) *gv_status = hgv;
+  return KWY_OK;
+}
+
+// the three kwy_gmm_mlpg* entries: o.gv (if any) with the statistics on the host
+static int ml_convert_host(kwy_ctx *ctx, const char *entry, const double *x, int64_t T, int d, int M,
+                           const double *weights, const double *means, const double *covs, int diff, ml_opts o,
+                           double *y, double *loglik, double *objective, int32_t *gv_status) {
+  const ml_mixture host = {weights, means, covs, diff, nullptr};
+  KWY_TRY(ml_check(ctx, ml_job{x, y, nullptr, nullptr, T, nullptr, nullptr}, d, M, host, o));
+  KWY_HIP(hipSetDevice(ctx->device));
+  const int nl = loglik && o.em >= 0 ? o.em + 1 : 0, no = o.gv ? o.gv->iterations + 1 : 0;
+  ml_staged s = {};
+  ml_arena measure{nullptr}, take{ctx};
+  ml_staged_buffers(measure, s, T, d, M, 6 * d, o.em_only || o.gv, o.gv);
+  KWY_TRY(kwy_arena_begin(ctx, measure.bytes + ml_pass_bytes(&T, 1, d, M, host, o)));
+  ml_staged_buffers(take, s, T, d, M, 6 * d, o.em_only || o.gv, o.gv);
+  KWY_TRY(ml_upload(ctx, s, x, T, d, M, 6 * d, weights, means, covs));
+  ml_gv_opts gv;
+  if (o.gv) {
+    gv = *o.gv;
+    KWY_HIP(hipMemcpyAsync(s.gv_mean, gv.mean, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+    KWY_HIP(hipMemcpyAsync(s.gv_var, gv.var, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+    gv.mean = s.gv_mean; gv.var = s.gv_var; gv.status = s.gv_status;
+    o.gv = &gv;
+  }
+  const ml_job job = {s.x, s.y, nullptr, nullptr, T, nl ? s.lik : nullptr, o.gv ? s.obj : nullptr};
+  int *status;
+  KWY_TRY(ml_convert_pass(ctx, &job, 1, 0, d, d, d, M, ml_mixture{s.w, s.mu, s.cv, diff, nullptr}, o, &status));
+  return ml_read_back(ctx, entry, s, status, y, (size_t)T * d, loglik, nl, objective, no, gv_status);
+}
+
+extern "C" int kwy_gmm_mlpg(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
+                            const double *means, const double *covs, int diff, double *y) {
+  return ml_convert_host(ctx, "gmm_mlpg", x, T, d, M, weights, means, covs, diff, ML_ARGMAX, y, nullptr, nullptr, nullptr);
+}
+
+extern "C" int kwy_gmm_mlpg_em(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
+                               const double *means, const double *covs, int diff, int em_iterations, double *y,
+                               double *loglik) {
+  return ml_convert_host(ctx, "gmm_mlpg_em", x, T, d, M, weights, means, covs, diff, ml_opts{em_iterations, true, nullptr},
+                         y, loglik, nullptr, nullptr);
 }
 
 extern "C" int kwy_gmm_mlpg_gv(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
                                const double *means, const double *covs, int diff, int em_iterations, int gv_offset,
                                const double *gv_mean, const double *gv_var, double weight, int gv_iterations, double *y,
                                double *loglik, double *objective, int32_t *status) {
-  if (!ctx) return KWY_EINVAL;
-  KWY_TRY(ml_gv_check(ctx, x, T, d, M, weights, means, covs, y, em_iterations, gv_mean, gv_var, weight, gv_iterations));
-  KWY_HIP(hipSetDevice(ctx->device));
-  const int D2 = 6 * d, nl = em_iterations < 0 ? 0 : em_iterations + 1;
-  size_t bx = kwy_pad(sizeof(double) * T * d), bw = kwy_pad(sizeof(double) * M);
-  size_t bm = kwy_pad(sizeof(double) * M * D2), bc = kwy_pad(sizeof(double) * (size_t)M * D2 * D2);
-  KWY_TRY(kwy_arena_begin(ctx, ml_gv_total_bytes(&T, 1, d, M, em_iterations, gv_iterations) + 2 * bx + bw + bm + bc +
-                                   kwy_pad(sizeof(double) * (KWY_MLPG_EM_MAX + 1)) +
-                                   kwy_pad(sizeof(double) * (KWY_MLPG_GV_MAX + 1)) + 2 * kwy_pad(sizeof(double) * d) +
-                                   kwy_pad(64)));
-  double *dx = kwy_arena<double>(ctx, (size_t)T * d), *dy = kwy_arena<double>(ctx, (size_t)T * d);
-  double *dw = kwy_arena<double>(ctx, M), *dmu = kwy_arena<double>(ctx, (size_t)M * D2);
-  double *dcv = kwy_arena<double>(ctx, (size_t)M * D2 * D2);
-  double *dlik = kwy_arena<double>(ctx, KWY_MLPG_EM_MAX + 1), *dobj = kwy_arena<double>(ctx, KWY_MLPG_GV_MAX + 1);
-  double *dgm = kwy_arena<double>(ctx, d), *dgv = kwy_arena<double>(ctx, d);
-  int32_t *dst = kwy_arena<int32_t>(ctx, 16);
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * T * d, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dw, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dmu, means, sizeof(double) * M * D2, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dcv, covs, sizeof(double) * (size_t)M * D2 * D2, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dgm, gv_mean, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dgv, gv_var, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-  ml_batch bt;
-  bt.n = 1;
-  bt.ldx = d;
-  bt.ldy = d;
-  bt.u[0].x = dx; bt.u[0].y = dy; bt.u[0].keep_in = nullptr; bt.u[0].keep_out = nullptr;
-  double *lik[1] = {loglik && nl ? dlik : nullptr}, *obj[1] = {dobj};
-  const ml_gv_opts gv = {dgm, dgv, weight, gv_iterations, gv_offset, obj, dst};
-  int *st;
-  if (em_iterations < 0)
-    KWY_TRY(mlpg_batch_core(ctx, bt, &T, d, M, dw, dmu, dcv, diff, &st, nullptr, &gv));
-  else
-    KWY_TRY(mlpg_em_batch_core(ctx, bt, &T, d, M, dw, dmu, dcv, diff, &st, nullptr, em_iterations, lik, &gv));
-  int hstatus = 0;
-  int32_t hgv = 0;
-  std::vector<double> hl(nl + 1), ho(gv_iterations + 1);
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * T * d, hipMemcpyDeviceToHost, ctx->stream));
-  if (lik[0]) KWY_HIP(hipMemcpyAsync(hl.data(), dlik, sizeof(double) * nl, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(ho.data(), dobj, sizeof(double) * (gv_iterations + 1), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hstatus, st, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hgv, dst, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  if (hstatus != 0) {
-    ctx->err = hstatus == 1 ? "gmm_mlpg_gv: source covariance is not positive definite"
-                            : "gmm_mlpg_gv: MLPG system is not positive definite";
-    return KWY_ENUMERIC;
+  const ml_gv_opts gv = {gv_mean, gv_var, weight, gv_iterations, gv_offset, nullptr};
+  return ml_convert_host(ctx, "gmm_mlpg_gv", x, T, d, M, weights, means, covs, diff, ml_opts{em_iterations, false, &gv}, y,
+                         loglik, objective, status);
+}
+
+// ---- frame-wise conversion (MLPG switched off) ---------------------------------------------------------------------
+struct soft_work {
+  double *model, *logp;
+  int *status;
+};
+static void soft_buffers(ml_arena &a, soft_work &w, int64_t T, int D, int M) {
+  a.take(w.model, ml_model_stride(D) * M);
+  a.take(w.logp, (size_t)T * M);
+  a.take(w.status, 16);
+}
+
+// x, y: T x D device rows; gm: the joint mixture over 2 D dimensions, on the device
+static int soft_core(kwy_ctx *ctx, const double *x, int64_t T, int D, int M, const ml_mixture &gm, double *y,
+                     int **status_out) {
+  ml_dims dm = {D, D, M, T};
+  ml_arena a{ctx};
+  soft_work w;
+  soft_buffers(a, w, T, D, M);
+  if (!a.ok) { ctx->err = "gmm_convert_frames: scratch arena too small"; return KWY_ENOMEM; }
+  *status_out = w.status;
+  KWY_HIP(hipMemsetAsync(w.status, 0, sizeof(int) * 16, ctx->stream));
+  if (!ml_lds_fits(D) || D > 192 || M > 256) {
+    // (3 D^2 doubles of LDS for the preparation: 160 KB hold D <= 82)
+    ctx->err = "gmm_convert_frames: feature dimension (<= 82 per side) or mixture count (<= 256) too large";
+    return KWY_EINVAL;
   }
-  if (lik[0]) std::copy(hl.begin(), hl.begin() + nl, loglik);
-  if (objective) std::copy(ho.begin(), ho.end(), objective);
-  if (status) *status = hgv;
+  KWY_TRY(ml_prep_attr(ctx, D));
+  if (!gm.prepared) ml_launch_prep(ctx, gm, D, M, w.model, w.status);
+  KWY_TRY(ml_launch_logp(ctx, x, dm, w.model, w.logp));
+  hipLaunchKernelGGL(k_gmm_soft, dim3((unsigned)T), dim3(128), 0, ctx->stream, x, dm, w.model, w.logp, y);
+  KWY_HIP(hipGetLastError());
   return KWY_OK;
+}
+
+static int soft_check(kwy_ctx *ctx, const void *x, int64_t T, int D, int M, const void *w, const void *mu,
+                      const void *cv, const void *y) {
+  if (!ctx) return KWY_EINVAL;
+  if (!x || !w || !mu || !cv || !y || T <= 0 || D <= 0 || M <= 0) {
+    ctx->err = "gmm_convert_frames: bad argument";
+    return KWY_EINVAL;
+  }
+  return KWY_OK;
+}
+
+static size_t soft_bytes(int64_t T, int D, int M) {
+  ml_arena a{nullptr};
+  soft_work w;
+  soft_buffers(a, w, T, D, M);
+  return a.bytes;
+}
+
+extern "C" int kwy_gmm_convert_frames_dev(kwy_ctx *ctx, const double *x, int64_t T, int D, int M,
+                                          const double *weights, const double *means, const double *covs, int diff,
+                                          double *y) {
+  KWY_TRY(soft_check(ctx, x, T, D, M, weights, means, covs, y));
+  KWY_HIP(hipSetDevice(ctx->device));
+  KWY_TRY(kwy_arena_begin(ctx, soft_bytes(T, D, M)));
+  int *status;
+  return soft_core(ctx, x, T, D, M, ml_mixture{weights, means, covs, diff, nullptr}, y, &status);
+}
+
+extern "C" int kwy_gmm_convert_frames(kwy_ctx *ctx, const double *x, int64_t T, int D, int M, const double *weights,
+                                      const double *means, const double *covs, int diff, double *y) {
+  KWY_TRY(soft_check(ctx, x, T, D, M, weights, means, covs, y));
+  KWY_HIP(hipSetDevice(ctx->device));
+  ml_staged s = {};
+  ml_arena measure{nullptr}, take{ctx};
+  ml_staged_buffers(measure, s, T, D, M, 2 * D, false, false);
+  KWY_TRY(kwy_arena_begin(ctx, measure.bytes + soft_bytes(T, D, M)));
+  ml_staged_buffers(take, s, T, D, M, 2 * D, false, false);
+  KWY_TRY(ml_upload(ctx, s, x, T, D, M, 2 * D, weights, means, covs));
+  int *status;
+  KWY_TRY(soft_core(ctx, s.x, T, D, M, ml_mixture{s.w, s.mu, s.cv, diff, nullptr}, s.y, &status));
+  return ml_read_back(ctx, "gmm_convert_frames", s, status, y, (size_t)T * D, nullptr, 0, nullptr, 0, nullptr);
 }
