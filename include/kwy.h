@@ -532,7 +532,9 @@ int kwy_fastdtw_batch_dev(kwy_ctx *ctx, const kwy_dtw_job *jobs, int count, int 
  * stages (used by the batched pipeline; the host API does these in numpy):
  * DTW feature rows [power, voicing, mc1..mcN] -- make_feature(power='binalize',
  * power_pivot='max', vuv='f0')                      kwiiyatta/vocoder/align.py:20-58
- * mc: T x ncoef, out: T x (ncoef+1). */
+ * mc: T x ncoef, out: T x (ncoef+1).  The power coefficients mc[:, 0] must be finite: with a NaN among them the
+ * pivot differs from numpy's max (the kernel's fmax skips a NaN, numpy's max returns it); such input is outside the
+ * contract. */
 int kwy_align_features_dev(kwy_ctx *ctx, const double *mc, int64_t T, int ncoef, const double *f0,
                            double power_weight, double power_threshold, double vuv_weight,
                            double *out);
@@ -546,7 +548,9 @@ int kwy_align_features_batch_dev(kwy_ctx *ctx, const kwy_align_job *jobs, int co
                                  double power_threshold, double vuv_weight);
 /* project_path_iter(path, trim, trim_len): one x index per y frame
  *                                                    kwiiyatta/vocoder/align.py:99-120
- * path / path_len as produced by kwy_fastdtw_dev (device); trim_len = 0: no trimming. */
+ * path / path_len as produced by kwy_fastdtw_dev (device); trim_len = 0: no trimming.  A jump in y of any length is
+ * filled as the generator fills it.  n_out[0] <- the number of indices the generator yields, whatever the capacity:
+ * when it exceeds idx_capacity, idx holds the first idx_capacity of them and nothing is written behind. */
 int kwy_align_project_dev(kwy_ctx *ctx, const int32_t *path, const int64_t *path_len, int trim_len,
                           int32_t *idx, int64_t idx_capacity, int64_t *n_out);
 typedef struct kwy_project_job {
@@ -557,7 +561,9 @@ typedef struct kwy_project_job {
   int64_t *n_out;
 } kwy_project_job;
 int kwy_align_project_batch_dev(kwy_ctx *ctx, const kwy_project_job *jobs, int count, int trim_len);
-/* Feature.__getitem__(list): dst[i] = src[idx[i]]    kwiiyatta/vocoder/abc/feature.py:170-194 */
+/* Feature.__getitem__(list): dst[i] = src[idx[i]]    kwiiyatta/vocoder/abc/feature.py:170-194
+ * An index outside [0, src_rows) does not fail and does not wrap: it is clamped, below 0 to the first row, at or above
+ * src_rows to the last one (callers gather a fixed capacity of rows from index lists whose tail is stale). */
 int kwy_gather_rows_dev(kwy_ctx *ctx, const double *src, int64_t src_rows, int width,
                         const int32_t *idx, int64_t n, double *dst);
 typedef struct kwy_gather_job {
@@ -936,7 +942,8 @@ int kwy_km_onehot_dev(kwy_ctx *ctx, const int32_t *labels, int64_t n, int M, dou
  * calls so that the joint feature rows are produced in HBM.  Counts that depend on the data
  * (path length, kept rows) are device scalars; buffers are sized by their capacities. */
 /* TrimmedDataset (dataset.py:49-52): n_out[0] = len(trim_zeros_frames(sp)), rows with L1 norm < eps
- * (nnmnkwii: 1e-7) counting as zero; the caller keeps the FIRST n_out frames, as the reference does */
+ * (nnmnkwii: 1e-7) counting as zero (a row with a NaN is not below eps: it counts as a frame, as np.trim_zeros has
+ * it); the caller keeps the FIRST n_out frames, as the reference does */
 int kwy_trim_length_dev(kwy_ctx *ctx, const double *sp, int64_t T, int K, double eps, int64_t *n_out);
 typedef struct kwy_trim_job {
   const double *sp;      /* T x K */
@@ -948,7 +955,8 @@ int kwy_trim_length_batch_dev(kwy_ctx *ctx, const kwy_trim_job *jobs, int count,
  * stored with pad_len frames of room on both ends -- f0_pad (n + 2 pad_len): the f0 track between zeros; ap_pad
  * ((n + 2 pad_len) x K): the rows behind the kept frames = 1 - 1e-12 (the rows in front are the caller's
  * initialisation) -- and, when `voiced` is not NULL, WorldSynthesizer.extract_is_voiced of the padded feature
- * (world.py:147-151).  The pad SPECTRA come from kwy_np_normal_blocks_dev. */
+ * (world.py:147-151).  The pad SPECTRA come from kwy_np_normal_blocks_dev.  A job with n = 0 is allowed; with
+ * pad_len = 0 as well it has nothing to write, which is no error. */
 typedef struct kwy_pad_job {
   const double *f0;      /* >= n */
   int64_t n;             /* frames kept (kwy_trim_length_dev) */
@@ -962,7 +970,11 @@ int kwy_is_voiced_dev(kwy_ctx *ctx, const double *f0, const double *ap, int64_t 
                       double *voiced);
 /* dtw_feature's strict filter (align.py:73-92) and align_even's cut to [pad_len, T - pad_len)
  * (align.py:134-146) on a FastDTW path over the DTW features feat_x (Tx x width) / feat_y:
- * idx_x / idx_y <- the x and y of the surviving cells, n_out[0] their number (<= capacity). */
+ * idx_x / idx_y <- the x and y of the surviving cells, n_out[0] their number (<= capacity): with more survivors than
+ * `capacity`, the first `capacity` of them are stored, nothing is written behind, and n_out[0] = capacity.
+ * pad_len = 0: no cut (the reference's pad_silence=False).  A one-cell path comes out twice under `strict` (the
+ * reference's chain(path[0], ..., path[-1])) and once without it (its np.array(path)).
+ * The path has at most Tx + Ty + 4 cells (any FastDTW path has fewer than Tx + Ty). */
 int kwy_align_even_dev(kwy_ctx *ctx, const int32_t *path, const int64_t *path_len, const double *feat_x,
                        const double *feat_y, int width, int strict, int use_power, int use_vuv, int64_t Tx,
                        int64_t Ty, int pad_len, int32_t *idx_x, int32_t *idx_y, int64_t capacity,
@@ -972,7 +984,9 @@ int kwy_align_even_dev(kwy_ctx *ctx, const int32_t *path, const int64_t *path_le
 int kwy_delta_features_dev(kwy_ctx *ctx, const double *x, const int64_t *n, int64_t capacity, int d,
                            double *out);
 /* make_dataset_to_array's np.hstack + remove_zeros_frames (dataset.py:61-77): joint <- [xd[t] | yd[t]]
- * for the rows t < n[0] with L1 norm >= eps, in order; n_out[0] = rows written */
+ * for the rows t < n[0] (n[0] above `capacity` counts as `capacity`) whose L1 norm is not below eps, in order;
+ * n_out[0] = rows written.  A row with a NaN is not below eps and is written; nnmnkwii's `s > 0` would leave it
+ * out, but the analysis produces no NaN features, so the training path never meets that difference. */
 int kwy_joint_rows_dev(kwy_ctx *ctx, const double *xd, const double *yd, const int64_t *n, int64_t capacity,
                        int width, double eps, double *joint, int64_t *n_out);
 /* Everything between FastDTW and the training matrix for a batch of aligned pairs, counts staying on the device:

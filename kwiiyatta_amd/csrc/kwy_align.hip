@@ -46,7 +46,10 @@ __device__ __forceinline__ void align_features_body(const double *__restrict__ m
 // yields, for every target frame y in [trim, last_y - trim], the x of the first path cell with that y
 // -- independent per cell, done by all threads.  Any other path (a jump in y, a y that goes back) takes
 // the reference's loop literally: the first wavefront stages path tiles in LDS, lane 0 walks them, and
-// the produced indices leave through LDS as well.
+// the produced indices leave through LDS as well.  A jump in y is a ramp of diff_y indices, however many: lane 0
+// fills the output tile as far as it goes, notes in st[4] how much of the ramp is out, and stops in front of that
+// cell; the tile is flushed, the path is staged again from that cell and the ramp goes on where it stopped -- as
+// often as its length asks for.  (Cells before it stay consumed, prev_x / prev_y move only once the ramp is done.)
 #define AL_TILE 1024
 #define AL_NT 256
 __device__ __forceinline__ void align_project_body(const int32_t *__restrict__ path,
@@ -55,7 +58,7 @@ __device__ __forceinline__ void align_project_body(const int32_t *__restrict__ p
                                                    int64_t *__restrict__ n_out) {
   __shared__ int32_t sp[2 * AL_TILE];
   __shared__ int32_t so[AL_TILE];
-  __shared__ long long st[4];  // prev_x, prev_y, n, stop
+  __shared__ long long st[5];  // prev_x, prev_y, n, stop, indices out of an unfinished ramp
   __shared__ int s_irregular;
   const int tid = threadIdx.x, lane = tid & 63;
   const int64_t L = *path_len;
@@ -86,7 +89,7 @@ __device__ __forceinline__ void align_project_body(const int32_t *__restrict__ p
     return;
   }
   if (tid >= 64) return;   // the general case: one wavefront, no workgroup barrier below
-  if (lane == 0) { st[0] = -1; st[1] = prev_y0; st[2] = 0; st[3] = 0; }
+  if (lane == 0) { st[0] = -1; st[1] = prev_y0; st[2] = 0; st[3] = 0; st[4] = 0; }
   int64_t k0 = 0;
   while (k0 < L) {
     const int nk = (int)min((int64_t)AL_TILE, L - k0);
@@ -105,15 +108,14 @@ __device__ __forceinline__ void align_project_body(const int32_t *__restrict__ p
         if (y - prev_y > 1) {
           if (y > len_y - 1) y = len_y - 1;
           const long long diff_x = x - prev_x, diff_y = y - prev_y;
-          if (made + diff_y > AL_TILE) {
-            if (made > 0) break;         // flush what we have, redo this cell next round
-            // a single gap longer than the tile: emit directly
-          }
-          for (long long i = 0; i < diff_y; ++i) {
+          long long i = st[4];           // what earlier rounds put out of this ramp (0: a new one)
+          for (; i < diff_y && made < AL_TILE; ++i) {
             const long long den = diff_y - 1, num = diff_x * i;
             const long long q = den != 0 ? (num >= 0 ? num / den : -((-num + den - 1) / den)) : 0;
-            if (made < AL_TILE) so[made++] = (int32_t)(prev_x + q);
+            so[made++] = (int32_t)(prev_x + q);
           }
+          if (i < diff_y) { st[4] = i; break; }   // the tile is full: flush it, go on with this cell next round
+          st[4] = 0;
         } else if (y >= len_y) {
           stop = true;
           break;
@@ -139,7 +141,8 @@ __device__ __forceinline__ void align_project_body(const int32_t *__restrict__ p
     __builtin_amdgcn_wave_barrier();
     __threadfence_block();
     if (st[3]) break;
-    k0 += used > 0 ? used : 1;
+    if (used == 0 && made == 0) break;   // (every round consumes a cell or produces an index)
+    k0 += used;
   }
   if (lane == 0) *n_out = st[2];
 }

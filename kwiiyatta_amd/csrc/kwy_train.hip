@@ -87,8 +87,9 @@ __device__ __forceinline__ void tr_align_even_body(const int32_t *__restrict__ p
   const int tid = threadIdx.x;
   const int64_t L = path_len[0];
   if (L <= 0) { if (tid == 0) n_out[0] = 0; return; }
-  // np.fromiter(chain(path[0], <kept inner cells>, path[-1])): a one-cell path yields that cell twice
-  const int64_t Lv = L == 1 ? 2 : L;            // virtual length: cell v = path[min(v, L - 1)]
+  // np.fromiter(chain(path[0], <kept inner cells>, path[-1])): a one-cell path yields that cell twice -- under
+  // `strict` only: without it the reference keeps np.array(path), the one cell
+  const int64_t Lv = (L == 1 && strict) ? 2 : L;            // virtual length: cell v = path[min(v, L - 1)]
   auto keep = [&](int64_t v) -> bool {
     if (!strict || v == 0 || v == Lv - 1) return true;
     const int x = path[2 * v], y = path[2 * v + 1];
@@ -367,6 +368,7 @@ extern "C" int kwy_train_pad_batch_dev(kwy_ctx *ctx, const kwy_pad_job *jobs, in
       Tp = std::max(Tp, q.n + 2 * (int64_t)pad_len);
     }
     const unsigned g = (unsigned)std::max<int64_t>(pad_len, (Tp + TR_NT - 1) / TR_NT);
+    if (g == 0) continue;              // nothing kept and no pad: nothing to write
     hipLaunchKernelGGL(k_tr_pad, dim3(g, b.n), dim3(TR_NT), 0, ctx->stream, b, K, pad_len, lowest);
   }
   KWY_HIP(hipGetLastError());
