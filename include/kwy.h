@@ -821,6 +821,39 @@ typedef struct kwy_mlsa_job {
 int kwy_mlsa_filter_batch_dev(kwy_ctx *ctx, const kwy_mlsa_job *jobs, int count, int order, double alpha, int pd,
                               int hopsize, int ignore_c0);
 
+/* ---- frame-parallel FFT form of the differential filter -------------------------------------
+ * The filter the MLSA filter approximates, H(z) = exp sum_m c_m z~^-m, applied frame by frame through its closed
+ * frequency response (overlap-save), all frames of all signals side by side.  An option beside the MLSA filter, not a
+ * replacement: the MLSA filter interpolates the coefficients across a frame, this one crossfades the outputs of the
+ * two fixed filters over the same samples with the same weights.
+ *   x: n samples, mc: T x (order+1) mel-cepstra, N = fft_size, hop = hopsize, m0 = ignore_c0 ? 1 : 0
+ *   w_k = 2 pi k / N,  w~_k = w_k + 2 atan2(alpha sin w_k, 1 - alpha cos w_k)
+ *   H_i[k] = exp( sum_{m = m0 .. order} mc[i][m] e^{-j m w~_k} ),  k = 0 .. N/2   (real at k = 0 and k = N/2)
+ *   nproc = min(T, (n - 1) / hop) (integer division: the MLSA filter's rule); y[nproc hop ..] = 0.0 exactly, so
+ *   n <= hop gives an all-zero output.  For frame i < nproc:
+ *     X = rfft of the N samples x[(i+1) hop - N .. (i+1) hop), samples before index 0 counting as zero
+ *     a = irfft(X H_{max(i-1, 0)}), b = irfft(X H_i), the last hop samples of each
+ *     y[i hop + j] = (1 - j/hop) a_j + (j/hop) b_j,  j = 0 .. hop-1
+ * Every output sample is written by exactly one workgroup, without atomics or accumulation in memory: the result is
+ * bit-reproducible from run to run and does not depend on the batch a signal is part of.
+ * KWY_EINVAL, nothing written: fft_size outside {1024, 2048, 4096, 8192} or <= hopsize, hopsize < 1, an order
+ * kwy_mlsa_synthesis does not accept (2 .. 62), a null pointer, an empty input, y overlapping x (a frame reads the
+ * input of the frames before it).
+ * kwy_mcep_filter_fft_size: max(1024, smallest power of two >= hopsize + ceil(0.025 fs)), 0 if that exceeds 8192 (the
+ * transforms the LDS FFTs provide): 1024 at 16 / 22.05 kHz, 2048 at 44.1 / 48 kHz, 4096 at 96 kHz with 5 ms frames.
+ * With fft_size - hopsize >= 25 ms the impulse response behind the kept samples is at rounding level for
+ * |log H| <= 3.6, so the N-point filter is the exact LTI filter to working precision.  Needs no device.
+ * _dev: device pointers, not synchronised, legal inside a stream capture once the tables of (fft_size, alpha) exist
+ * (the first call makes them).  _batch_dev: every job equals the single call bit for bit; more jobs than one launch
+ * holds are split; count == 0 is KWY_OK. */
+int kwy_mcep_filter_fft_size(int fs, int hopsize);
+int kwy_mcep_filter_fft(kwy_ctx *ctx, const double *x, int64_t n, const double *mc, int64_t T, int order, double alpha,
+                        int hopsize, int fft_size, int ignore_c0, double *y);
+int kwy_mcep_filter_fft_dev(kwy_ctx *ctx, const double *x, int64_t n, const double *mc, int64_t T, int order,
+                            double alpha, int hopsize, int fft_size, int ignore_c0, double *y);
+int kwy_mcep_filter_fft_batch_dev(kwy_ctx *ctx, const kwy_mlsa_job *jobs, int count, int order, double alpha,
+                                  int hopsize, int fft_size, int ignore_c0);
+
 
 /* ---- converter fit: EM building blocks --------------------------------------------------------
  * sklearn.mixture.GaussianMixture(covariance_type='full').fit as used at

@@ -14,7 +14,7 @@ from .wavfile import Wavdata, load_wav
 from .vocoder import (Analyzer, Feature, MelCepstrum, Synthesizer, align_even, analyze_wav,
                       feature, pad_silence, resample, reshape)
 from .converter import MelCepstrumConverter, ParallelDataset, WavFileDataset, align_dataset
-from .filter import apply_mlsa_filter
+from .filter import apply_diff_filter, apply_mlsa_filter
 from .align import align
 from .config import Config
 from .evaluate_voice import evaluate, evaluate_pair
@@ -40,7 +40,7 @@ def shift_formants(feature_set, ratio):
 name = "kwiiyatta_amd"
 
 __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFileDataset',
-           'align_dataset', 'apply_mlsa_filter', 'Analyzer', 'Feature', 'MelCepstrum',
+           'align_dataset', 'apply_mlsa_filter', 'apply_diff_filter', 'Analyzer', 'Feature', 'MelCepstrum',
            'Synthesizer', 'align_even', 'analyze_wav', 'feature', 'pad_silence', 'resample',
            'reshape', 'Wavdata', 'load_wav',
            # additions to the reference's names: objective evaluation of a trained converter (evaluate_voice.py)

@@ -202,6 +202,13 @@ MLPG_GV_OPTION = ('--mlpg-gv', dict(type=mlpg_gv, default=None, metavar='N',
                                          'with --mlpg-em, not with --gv or --ms'))
 
 
+DIFF_FILTER_OPTION = ('--diff-filter', dict(choices=('mlsa', 'fft'), default='mlsa',
+                                            help='The filter of the differential outputs: mlsa, the MLSA filter of the '
+                                                 'reference (serial in the sample), or fft, the same mel-cepstral '
+                                                 'filter applied frame by frame through its frequency response, all '
+                                                 'frames in parallel, neighbouring frames crossfaded'))
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -241,6 +248,9 @@ class Config:
 
     def add_mlpg_gv_argument(self):
         self._declare((MLPG_GV_OPTION,))
+
+    def add_diff_filter_argument(self):
+        self._declare((DIFF_FILTER_OPTION,))
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)

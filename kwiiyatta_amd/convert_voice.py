@@ -36,7 +36,14 @@ filtered by the converter's difference, which this option leaves alone.
 of with one arg-max mixture per frame: every mixture of a frame weighs in with its posterior, and the posteriors are
 re-estimated N times from the source frame and the trajectory solved last (`convert(..., em=N)`; with `--batch`
 kwy_convert_mcep_em_batch_dev).  The statistics of `--ms` and the re-alignment of `--align-iterations` keep the arg-max
-conversion."""
+conversion.
+`--diff-filter fft` writes the .diff.wav outputs through the frame-parallel FFT form of the differential filter instead
+of the MLSA filter (`convert(..., diff_filter='fft')`, kwiiyatta_amd.apply_diff_filter; with `--batch`
+kwy_mcep_filter_fft_batch_dev over all frames of a wave's files): the mel-cepstral filter the MLSA filter approximates,
+applied to every frame through its frequency response, the outputs of neighbouring frames' filters crossfaded where the
+MLSA filter interpolates their coefficients.  Its time shrinks with the GPU where the MLSA recursion's does not (about
+0.5 us per sample of the longest file, whatever runs beside it).  The default, `mlsa`, is the reference's filter,
+unchanged; the .synth.wav outputs do not depend on the option."""
 import pathlib
 
 import numpy as np
@@ -45,7 +52,7 @@ OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
 def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-            formant_shift=0.0, mlpg_em=None, mlpg_gv=None):
+            formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa'):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
@@ -56,14 +63,18 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
     2 ** (formant_shift / 12) (Feature.shift_formants); the differential output ignores it.
     mlpg_em=N: the EM trajectory conversion with N re-estimations (converter.convert(em=N), either output).
     mlpg_gv=N: parameter generation considering the global variance, N steps (converter.convert(mlpg_gv=N), either
-    output)."""
+    output).
+    diff_filter: the filter of the differential output, 'mlsa' (apply_mlsa_filter) or 'fft'
+    (apply_diff_filter(method='fft')); the synthesised output ignores it."""
     import kwiiyatta_amd as k
     source = analyze_source(conf, converter, src_path)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
                                   **(dict(ms=ms) if ms > 0 else {}), **({} if mlpg_em is None else dict(em=mlpg_em)),
                                   **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)))
     if diffvc:
-        return k.apply_mlsa_filter(source, converted)
+        if diff_filter == 'mlsa':
+            return k.apply_mlsa_filter(source, converted)
+        return k.apply_diff_filter(source, converted, method=diff_filter)
     rendered = k.feature(source)
     rendered.mel_cepstrum = converted                   # takes over from the analysed envelope
     if convert_f0 or transpose_key != 0:
@@ -115,7 +126,7 @@ class _Pcm16:
 
 
 def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-                        formant_shift=0.0, mlpg_em=None, mlpg_gv=None):
+                        formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa'):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -131,7 +142,9 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     device (corpus.convert_batch(formant_ratio=...)).
     mlpg_em=N: both outputs from EM trajectory conversions (as `convert` does; corpus.convert_batch(mlpg_em=N)).
     mlpg_gv=N: both outputs from GV-considering parameter generation (as `convert` does;
-    corpus.convert_batch(mlpg_gv=N))."""
+    corpus.convert_batch(mlpg_gv=N)).
+    diff_filter='fft': the .diff.wav outputs through the frame-parallel FFT filter instead of the MLSA filter
+    (corpus.convert_batch(diff_filter='fft'): all frames of a wave's files in one launch)."""
     import kwiiyatta_amd as k
     from . import corpus
     if mlpg_gv is not None:
@@ -168,7 +181,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                                    **(dict(formant_ratio=2.0 ** (formant_shift / 12)) if formant_shift != 0 else {}),
                                    **({} if mlpg_em is None else dict(mlpg_em=mlpg_em)),
                                    **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv, gv_stats=converter.gv_stats,
-                                                                      gv_var=converter.gv_var)))
+                                                                      gv_var=converter.gv_var)),
+                                   **({} if diff_filter == 'mlsa' else dict(diff_filter=diff_filter)))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -200,6 +214,7 @@ def main():
     conf.add_ms_argument()
     conf.add_mlpg_em_argument()
     conf.add_mlpg_gv_argument()
+    conf.add_diff_filter_argument()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
@@ -207,7 +222,7 @@ def main():
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, formant_shift=conf.formant_shift)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
                                   diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                                  mlpg_gv=conf.mlpg_gv, **pitch) if conf.batch else {}
+                                  mlpg_gv=conf.mlpg_gv, diff_filter=conf.diff_filter, **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -221,7 +236,8 @@ def main():
                 batched[wav_path, differential].save(out)
             else:
                 convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                        mlpg_gv=conf.mlpg_gv, **({} if differential else pitch)).save(out)
+                        mlpg_gv=conf.mlpg_gv,
+                        **(dict(diff_filter=conf.diff_filter) if differential else pitch)).save(out)
 
 
 if __name__ == '__main__':

@@ -844,11 +844,16 @@ class ConvertWave:
     mlpg_gv=N (with a GMM, gv_stats and gv_var; an integer within [0, 256]): both conversions with the GV ascent behind
     them (kwy_convert_mcep_gv_batch_dev; N conjugate-gradient steps, gv_weight weighs the GV term), the differential
     one on the variance of differential + source.  `gvgen_status` holds two words per utterance (plain, then
-    differential; non-zero: coefficients left at the maximum-likelihood track).  Not with gv_strength or ms_strength."""
+    differential; non-zero: coefficients left at the maximum-likelihood track).  Not with gv_strength or ms_strength.
+    diff_filter='fft' (with diff=True): `wave_diff[i]` through the frame-parallel FFT form of the differential filter
+    (kwy_mcep_filter_fft_batch_dev over the MLSA filter's jobs: one workgroup per frame, launched with the wave, so
+    defer_mlsa has nothing to defer) instead of the MLSA recursion; 'mlsa' (default) is that recursion, unchanged."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
                  f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                 ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
+                 ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0,
+                 diff_filter='mlsa'):
+        self.diff_filter = _diff_filter(diff_filter)
         self.mlpg_em = _mlpg_em(mlpg_em) if gmm is not None else None
         self.gvgen = _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order, ls.dev,
                                       on=gmm is not None)
@@ -936,6 +941,9 @@ class ConvertWave:
                 self.j_mlsa = _lib.job_array(_lib.MlsaJob, [(self.x[i], self.x[i].numel(), self.mc_diff_rows[i], self.T[i],
                                                             self.wave_diff[i]) for i in range(n)])
                 self.hop = int(self.fs * (self.frame_period * 0.001))
+                if self.diff_filter == 'fft':
+                    from .backend import fftfilt
+                    self.diff_fft = fftfilt.fft_filter_size(self.fs, self.hop)
                 self.pcm_diff = None
                 if pcm:
                     self.pcm_diff_all = torch.zeros(samples.total, dtype=torch.int16, device=dev)
@@ -1030,7 +1038,9 @@ class ConvertWave:
                 if self.gv_status is None and self.ms_status is None:           # (with a postfilter it ran above)
                     chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em,
                                             self.gvgen, 1, None if self.gvgen is None else self.gvgen_status[n:]))
-                if not self.defer_mlsa:
+                if self.diff_filter == 'fft':       # every frame of every file in one grid: nothing to defer
+                    self.run_fft_filter(ls.ctx)
+                elif not self.defer_mlsa:
                     self.run_mlsa(ls.ctx)
 
     def mlsa_rows(self):
@@ -1043,6 +1053,12 @@ class ConvertWave:
         chk(lib.kwy_mlsa_filter_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, 4, self.hop, 1))
         self.finish_diff(ctx)
 
+    def run_fft_filter(self, ctx):
+        """the wave's differential outputs through the frame-parallel FFT filter (the jobs of the MLSA filter as they are)"""
+        _lib.check(ctx, lib.kwy_mcep_filter_fft_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, self.hop,
+                                                          self.diff_fft, 1))
+        self.finish_diff(ctx)
+
     def finish_diff(self, ctx):
         if self.pcm_diff is not None:
             _lib.check(ctx, lib.kwy_finish_pcm16_batch_dev(ctx.handle, self.j_fin_diff, self.n, self.fs, 0, PIECE_CEILING, 1,
@@ -1051,7 +1067,8 @@ class ConvertWave:
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
                     f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                    ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
+                    ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0,
+                    diff_filter='mlsa'):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
@@ -1064,7 +1081,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     gvgen_status = []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
-                         diff=diff, defer_mlsa=diff, f0_stats=f0_stats, transpose_key=transpose_key,
+                         diff=diff, defer_mlsa=diff and diff_filter == 'mlsa', f0_stats=f0_stats,
+                         transpose_key=transpose_key, **(dict(diff_filter=diff_filter) if diff_filter != 'mlsa' else {}),
                          **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}),
                          **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}),
                          **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}),
@@ -1088,7 +1106,7 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             gvgen_status.append(wv.gvgen_status)
         if wv.formant_status is not None:
             formant_status.append(wv.formant_status)
-        if diff:
+        if diff and diff_filter == 'mlsa':
             waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
         held.append(wv)
         while len(held) > 2:
@@ -1520,6 +1538,14 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
         s_.synchronize()
 
 
+def _diff_filter(name):
+    """the differential filter a driver is asked for, checked"""
+    from .filter import DIFF_FILTERS
+    if name not in DIFF_FILTERS:
+        raise ValueError(f'differential filter: {name!r} is not one of {DIFF_FILTERS}')
+    return name
+
+
 def _formant_ratio(formant_ratio, driver, pool, who):
     """the checked ratio of a batch driver's formant shift, before anything is put on the device: ValueError outside
     [0.5, 2], and for any ratio but 1 on the stream driver"""
@@ -1533,7 +1559,7 @@ def _formant_ratio(formant_ratio, driver, pool, who):
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
                   shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
                   gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0,
-                  mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
+                  mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0, diff_filter='mlsa'):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1556,7 +1582,11 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     mlpg_gv (lockstep driver): None, or N within [0, 256], with gv_stats and gv_var (the converter's): both outputs from
     conversions with the GV ascent behind them (ConvertWave; kwy_convert_mcep_gv_batch_dev), gv_weight weighing the GV
     term; it goes with mlpg_em, not with gv_strength or ms_strength; a coefficient it cannot process raises ValueError
-    after the batch."""
+    after the batch.
+    diff_filter (with diff=True): 'mlsa' (default), or 'fft': the differential outputs through the frame-parallel FFT
+    form of the filter (kwy_mcep_filter_fft_batch_dev, one grid over all frames of a wave's files, launched with the
+    wave) instead of the MLSA recursions (which wait for the last wave and run side by side, one wavefront per file)."""
+    diff_filter = _diff_filter(diff_filter)
     formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'convert_batch')
     mlpg_em = _mlpg_em(mlpg_em)
     if mlpg_gv is not None and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
@@ -1575,7 +1605,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
                         f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
                         ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio,
-                        mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, gv_var=gv_var, gv_weight=gv_weight)
+                        mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, gv_var=gv_var, gv_weight=gv_weight, diff_filter=diff_filter)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out

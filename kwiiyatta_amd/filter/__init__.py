@@ -1,10 +1,14 @@
 """Differential-spectrum filtering: a waveform is passed through the MLSA filter described by a mel-cepstrum (for
 voice conversion: the difference between target and source mel-cepstra), which changes its spectral envelope
 without re-synthesising it.  API of kwiiyatta.filter (/root/reference/kwiiyatta/filter/mlsa.py:9-30).  mc2b and the
-filter itself are HIP kernels behind the pysptk-shaped classes of kwiiyatta_amd.backend.sptk."""
+filter itself are HIP kernels behind the pysptk-shaped classes of kwiiyatta_amd.backend.sptk.
+`apply_diff_filter(wav, mcep, method=)` chooses between that filter ('mlsa', serial in the sample) and the
+frame-parallel FFT form of the same mel-cepstral filter ('fft', backend.fftfilt)."""
 import numpy as np
 
 from ..backend import sptk
+
+DIFF_FILTERS = ('mlsa', 'fft')
 
 
 def _at_waveform_rate(mcep, fs):
@@ -24,16 +28,36 @@ def _at_waveform_rate(mcep, fs):
     return out
 
 
+def _shape_only(wav, mcep):
+    """what both filters run on: the mel-cepstrum at the waveform's rate, its coefficients with c0 = 0 (the filter
+    changes the envelope's shape, not its power), alpha and the hop in samples"""
+    mcep = _at_waveform_rate(mcep, wav.fs)
+    shape_only = np.array(mcep.data, dtype=np.float64)
+    shape_only[:, 0] = 0.0
+    return mcep, shape_only, mcep.alpha(), int(mcep.fs * (mcep.frame_period * 0.001))
+
+
 def apply_mlsa_filter(wav, mcep):
     """`wav` (Wavdata or anything with .fs / .data) filtered frame by frame with `mcep` (c0 ignored)"""
     import kwiiyatta_amd as k
-    mcep = _at_waveform_rate(mcep, wav.fs)
-    shape_only = np.array(mcep.data, dtype=np.float64)
-    shape_only[:, 0] = 0.0                               # the filter changes the envelope's shape, not its power
-    alpha = mcep.alpha()
-    hop = int(mcep.fs * (mcep.frame_period * 0.001))
+    mcep, shape_only, alpha, hop = _shape_only(wav, mcep)
     engine = sptk.Synthesizer(sptk.MLSADF(order=mcep.order, alpha=alpha), hopsize=hop)
     return k.Wavdata(wav.fs, engine.synthesis(wav.data, sptk.mc2b(shape_only, alpha=alpha)))
 
 
-__all__ = ['apply_mlsa_filter']
+def apply_diff_filter(wav, mcep, method='mlsa'):
+    """`wav` through the differential filter of `mcep` (c0 ignored): method 'mlsa' is apply_mlsa_filter; 'fft' filters
+    every frame through the frequency response of its mel-cepstrum and crossfades the outputs of neighbouring frames'
+    filters where the MLSA filter interpolates their coefficients -- all frames at once instead of sample by sample"""
+    if method not in DIFF_FILTERS:
+        raise ValueError(f'differential filter: {method!r} is not one of {DIFF_FILTERS}')
+    if method == 'mlsa':
+        return apply_mlsa_filter(wav, mcep)
+    import kwiiyatta_amd as k
+    from ..backend import fftfilt
+    mcep, shape_only, alpha, hop = _shape_only(wav, mcep)
+    size = fftfilt.fft_filter_size(wav.fs, hop)
+    return k.Wavdata(wav.fs, fftfilt.mcep_fft_filter(wav.data, shape_only, alpha, hop, size, ignore_c0=True))
+
+
+__all__ = ['apply_mlsa_filter', 'apply_diff_filter']

@@ -11,9 +11,22 @@ aperiodicity stay), after the carrier and --mcep steps, beside the transposition
 --diffvc the shift composes in two ways.  --carrier --diffvc: the source's envelope on the carrier's frames is warped
 BEFORE the difference to the carrier's mel-cepstrum is taken, so the carrier's waveform is filtered towards the shifted
 spectrum.  --diffvc without a carrier (ignored at shift 0, as it always was): the source's OWN waveform goes through the
-MLSA filter of mel-cepstrum(warped envelope) - mel-cepstrum(envelope) -- a formant shift with no resynthesis at all."""
+MLSA filter of mel-cepstrum(warped envelope) - mel-cepstrum(envelope) -- a formant shift with no resynthesis at all.
+--diff-filter fft runs every --diffvc path above -- with and without --carrier, the --formant-shift difference
+included -- through the frame-parallel FFT form of the filter (kwiiyatta_amd.apply_diff_filter(method='fft')) instead
+of the MLSA recursion: the same mel-cepstral filter, every frame filtered by a transform of its own and neighbouring
+frames' outputs crossfaded, in milliseconds for a file of minutes.  The default, mlsa, is the reference's filter."""
 import copy
 import pathlib
+
+
+def _diff_filter(conf, wav, difference):
+    """the --diffvc filter the options ask for: the MLSA filter unless --diff-filter names another"""
+    import kwiiyatta_amd as k
+    method = getattr(conf, 'diff_filter', 'mlsa')
+    if method == 'mlsa':
+        return k.apply_mlsa_filter(wav, difference)
+    return k.apply_diff_filter(wav, difference, method=method)
 
 
 def render(conf, source):
@@ -28,7 +41,7 @@ def render(conf, source):
             picture.shift_formants(ratio)
             difference = copy.copy(picture.mel_cepstrum)
             difference.data = difference.data - plain
-            return k.apply_mlsa_filter(source.wavdata, difference)
+            return _diff_filter(conf, source.wavdata, difference)
     else:
         carrier = conf.create_analyzer(conf.carrier, Analyzer=k.analyze_wav)
         picture = k.align(source, carrier)               # the source's features on the carrier's frames
@@ -37,7 +50,7 @@ def render(conf, source):
                 picture.shift_formants(ratio)
             difference = copy.copy(picture.mel_cepstrum)
             difference.data -= carrier.mel_cepstrum.data
-            return k.apply_mlsa_filter(carrier.wavdata, difference)
+            return _diff_filter(conf, carrier.wavdata, difference)
         picture.f0 = carrier.f0
     if conf.mcep:
         picture.extract_mel_cepstrum()
@@ -67,6 +80,7 @@ def main():
     conf.add_argument('--result-fs', type=int, help='Result waveform sampling rate')
     conf.add_transpose_key_argument()
     conf.add_formant_shift_argument()
+    conf.add_diff_filter_argument()
     conf.parse_args()
     if conf.source is None:
         conf.parser.error('a source wav file is required (the Qt dialog of the reference is not part of this build)')
