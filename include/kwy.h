@@ -11,7 +11,9 @@
  *     retains or frees a caller pointer
  *   - `kwy_<op>`      takes HOST pointers (what a ctypes/numpy binding passes);
  *                     it stages through HBM, runs the HIP kernels and copies
- *                     the result back (synchronous on return)
+ *                     the result back (synchronous on return).  Every such entry
+ *                     can return KWY_ENOMEM with "<op>: scratch arena too small"
+ *                     (a staged buffer did not fit the arena the call had sized)
  *   - `kwy_<op>_dev`  takes DEVICE pointers; work is enqueued on the context's
  *                     HIP stream and NOT synchronised (call kwy_ctx_sync)
  *   - return value: 0 on success, a negative KWY_E* code otherwise;

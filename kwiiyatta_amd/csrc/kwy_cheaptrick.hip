@@ -548,16 +548,13 @@ extern "C" int kwy_cheaptrick(kwy_ctx *ctx, const double *x, int64_t x_length, i
   const int K = fft_size / 2 + 1;
   for (int64_t i = 0; i < T; ++i)
     if (!(f0[i] < fs * 0.375)) { ctx->err = "cheaptrick: f0 must be below 3*fs/8"; return KWY_EINVAL; }
-  size_t bx = kwy_pad(sizeof(double) * x_length), bt = kwy_pad(sizeof(double) * T);
-  size_t bo = kwy_pad(sizeof(double) * T * K);
-  KWY_TRY(kwy_arena_begin(ctx, ct_scratch_bytes(T) + bx + 2 * bt + bo));
-  double *dx = kwy_arena<double>(ctx, x_length), *dt = kwy_arena<double>(ctx, T);
-  double *df0 = kwy_arena<double>(ctx, T), *dout = kwy_arena<double>(ctx, (size_t)T * K);
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * x_length, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dt, t, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(df0, f0, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "cheaptrick");
+  double *dx, *dt, *df0, *dout;
+  st.in(dx, x, (size_t)x_length);
+  st.in(dt, t, (size_t)T);
+  st.in(df0, f0, (size_t)T);
+  st.out(dout, out, (size_t)T * K);
+  KWY_TRY(st.begin(ct_scratch_bytes(T)));
   KWY_TRY(cheaptrick_one(ctx, dx, x_length, fs, dt, df0, T, q1, fft_size, out_div, dout));
-  KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * T * K, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

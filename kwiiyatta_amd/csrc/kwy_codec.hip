@@ -116,26 +116,24 @@ extern "C" int kwy_code_aperiodicity(kwy_ctx *ctx, const double *ap, int64_t T, 
   KWY_TRY(codec_check(ctx, ap, coded, T, fs, fft_size, nb));
   KWY_HIP(hipSetDevice(ctx->device));
   if (nb == 0) return KWY_OK;
-  const int K = fft_size / 2 + 1;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * T * K) + kwy_pad(sizeof(double) * T * nb)));
-  double *dap = kwy_arena<double>(ctx, (size_t)T * K), *dc = kwy_arena<double>(ctx, (size_t)T * nb);
-  KWY_HIP(hipMemcpyAsync(dap, ap, sizeof(double) * T * K, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "code_aperiodicity");
+  double *dap, *dc;
+  st.in(dap, ap, (size_t)T * (fft_size / 2 + 1));
+  st.out(dc, coded, (size_t)T * nb);
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_code_aperiodicity_dev(ctx, dap, T, fs, fft_size, dc));
-  KWY_HIP(hipMemcpyAsync(coded, dc, sizeof(double) * T * nb, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 extern "C" int kwy_decode_aperiodicity(kwy_ctx *ctx, const double *coded, int64_t T, int fs, int fft_size, int nb,
                                        double *ap) {
   KWY_TRY(codec_check(ctx, coded, ap, T, fs, fft_size, nb));
   KWY_HIP(hipSetDevice(ctx->device));
-  const int K = fft_size / 2 + 1;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * T * K) + kwy_pad(sizeof(double) * T * (nb + 1))));
-  double *dap = kwy_arena<double>(ctx, (size_t)T * K), *dc = kwy_arena<double>(ctx, (size_t)T * (nb + 1));
-  if (nb > 0) KWY_HIP(hipMemcpyAsync(dc, coded, sizeof(double) * T * nb, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "decode_aperiodicity");
+  double *dap, *dc;
+  st.out(dap, ap, (size_t)T * (fft_size / 2 + 1));
+  st.in(dc, coded, (size_t)T * nb);
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_decode_aperiodicity_dev(ctx, dc, T, fs, fft_size, nb, dap));
-  KWY_HIP(hipMemcpyAsync(ap, dap, sizeof(double) * T * K, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -252,7 +252,40 @@ void *kwy_arena_alloc(kwy_ctx *ctx, size_t bytes) {
   return p;
 }
 
+// ================================================================ staging
+int kwy_staging::begin(size_t scratch) {
+  size_t bytes = scratch;
+  for (const buffer &b : buffers) bytes += kwy_pad(b.bytes);
+  KWY_TRY(kwy_arena_begin(ctx, bytes));
+  for (const buffer &b : buffers)
+    if (!(*b.dev = kwy_arena_alloc(ctx, b.bytes))) {
+      ctx->err = std::string(entry) + ": scratch arena too small";
+      return KWY_ENOMEM;
+    }
+  for (const buffer &b : buffers)
+    if (b.src && b.bytes) KWY_HIP(hipMemcpyAsync(*b.dev, b.src, b.bytes, hipMemcpyHostToDevice, ctx->stream));
+  return KWY_OK;
+}
+
+int kwy_staging::finish() {
+  for (const buffer &b : buffers)
+    if (b.dst && b.bytes) KWY_HIP(hipMemcpyAsync(b.dst, *b.dev, b.bytes, hipMemcpyDeviceToHost, ctx->stream));
+  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  return KWY_OK;
+}
+
 // ================================================================ tables
+int kwy_table_upload(kwy_ctx *ctx, const std::string &key, const void *host, size_t bytes, void **out) {
+  void *d = nullptr;
+  KWY_HIP(hipMalloc(&d, bytes));
+  const hipError_t e = hipMemcpy(d, host, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) (void)hipFree(d);
+  KWY_HIP(e);
+  ctx->d_mats.emplace(key, d);
+  *out = d;
+  return KWY_OK;
+}
+
 // The powers table of the stride-64 pass (kwy_device.hpp: kwy_tw_powers), filled on the device with the expressions the
 // per-lane pass uses, under the same -ffp-contract=off (k_twiddle_powers_fill): entry u holds the bits every lane of a
 // wavefront with j >> 6 == u would form from tw[64 u].

@@ -1023,21 +1023,15 @@ static int launch_body(kwy_ctx *ctx, const d4c_batch &b, const d4c_params &p, co
 
 static int get_nuttall(kwy_ctx *ctx, int window_length, const double **out) {
   std::string key = "nuttall:" + std::to_string(window_length);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  return kwy_cached_table<double>(ctx, key, [&] {
     std::vector<double> h(window_length);
     for (int i = 0; i < window_length; ++i) {
       double tmp = i / (window_length - 1.0);
       h[i] = 0.355768 - 0.487396 * cos(2.0 * KWY_PI * tmp) + 0.144232 * cos(4.0 * KWY_PI * tmp) -
              0.012604 * cos(6.0 * KWY_PI * tmp);
     }
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(double) * window_length));
-    KWY_HIP(hipMemcpy(d, h.data(), sizeof(double) * window_length, hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  *out = it->second;
-  return KWY_OK;
+    return h;
+  }, out);
 }
 
 static int d4c_fft_size(int fs) {
@@ -1190,17 +1184,13 @@ extern "C" int kwy_d4c(kwy_ctx *ctx, const double *x, int64_t x_length, int fs, 
   KWY_HIP(hipSetDevice(ctx->device));
   for (int64_t i = 0; i < T; ++i)
     if (!(f0[i] >= 0.0 && f0[i] < fs * 0.2)) { ctx->err = "d4c: f0 must lie in [0, fs/5)"; return KWY_EINVAL; }
-  const int K = fft_size / 2 + 1;
-  size_t bx = kwy_pad(sizeof(double) * x_length), bt = kwy_pad(sizeof(double) * T);
-  size_t bo = kwy_pad(sizeof(double) * T * K);
-  KWY_TRY(kwy_arena_begin(ctx, d4c_scratch_bytes(T, fs) + bx + 2 * bt + bo));
-  double *dx = kwy_arena<double>(ctx, x_length), *dt = kwy_arena<double>(ctx, T);
-  double *df0 = kwy_arena<double>(ctx, T), *dout = kwy_arena<double>(ctx, (size_t)T * K);
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * x_length, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dt, t, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(df0, f0, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "d4c");
+  double *dx, *dt, *df0, *dout;
+  st.in(dx, x, (size_t)x_length);
+  st.in(dt, t, (size_t)T);
+  st.in(df0, f0, (size_t)T);
+  st.out(dout, out, (size_t)T * (fft_size / 2 + 1));
+  KWY_TRY(st.begin(d4c_scratch_bytes(T, fs)));
   KWY_TRY(d4c_one(ctx, dx, x_length, fs, dt, df0, T, threshold, fft_size, dout));
-  KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * T * K, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

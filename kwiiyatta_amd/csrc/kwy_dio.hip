@@ -693,8 +693,7 @@ static int dio_get_filters(kwy_ctx *ctx, int fs, double f0_floor, double f0_ceil
   }
   char key[160];
   snprintf(key, sizeof(key), "dio:%d:%.17g:%.17g:%.17g", fs, f0_floor, f0_ceil, channels_in_octave);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  KWY_TRY(kwy_cached_table<kwy_c>(ctx, key, [&] {
     const int N = DIO_N, H = DIO_H;
     std::vector<std::complex<double>> lc(N, 0.0), nu(N);
     {
@@ -721,12 +720,8 @@ static int dio_get_filters(kwy_ctx *ctx, int fs, double f0_floor, double f0_ceil
         G[(size_t)b * (H + 1) + k] = {v.real(), v.imag()};
       }
     }
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(kwy_c) * G.size()));
-    KWY_HIP(hipMemcpy(d, G.data(), sizeof(kwy_c) * G.size(), hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  f.G = (const kwy_c *)it->second;
+    return G;
+  }, &f.G));
   *out = f;
   return KWY_OK;
 }
@@ -879,20 +874,19 @@ extern "C" int kwy_dio(kwy_ctx *ctx, const double *x, int64_t x_length, int fs, 
   KWY_TRY(dio_prepare(ctx, fs, f0_floor, f0_ceil, channels_in_octave, frame_period_ms, speed, allowed_range, x_length,
                       &p, &block));
   const int64_t T = p.T_max;
-  KWY_TRY(kwy_arena_begin(ctx, block + kwy_pad(sizeof(double) * x_length) + 2 * kwy_pad(sizeof(double) * T) +
-                                   kwy_pad(sizeof(int) * KWY_BATCH_MAX)));
-  char *scratch = (char *)kwy_arena_alloc(ctx, block);
-  double *dx = kwy_arena<double>(ctx, x_length), *dt = kwy_arena<double>(ctx, T), *df0 = kwy_arena<double>(ctx, T);
-  int *dstatus = kwy_arena<int>(ctx, KWY_BATCH_MAX);
-  if (!scratch || !dx || !dt || !df0 || !dstatus) { ctx->err = "dio: scratch arena too small"; return KWY_ENOMEM; }
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * x_length, hipMemcpyHostToDevice, ctx->stream));
-  const kwy_f0_job job = {dx, x_length, dt, df0, nullptr};
+  kwy_staging st(ctx, "dio");
+  char *scratch;
+  int *dstatus, hstatus = 0;
+  kwy_f0_job job = {x, x_length, temporal_positions, f0, nullptr};
+  st.tmp(scratch, block);
+  st.in(job.x, x, (size_t)x_length);
+  st.out(job.temporal_positions, temporal_positions, (size_t)T);
+  st.out(job.f0, f0, (size_t)T);
+  st.tmp(dstatus, KWY_BATCH_MAX);
+  KWY_TRY(st.begin());
   KWY_TRY(dio_pass(ctx, &job, 1, p, scratch, dstatus));
-  int hstatus = 0;
-  KWY_HIP(hipMemcpyAsync(temporal_positions, dt, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(f0, df0, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hstatus, dstatus, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  st.fetch(dstatus, &hstatus, 1);
+  KWY_TRY(st.finish());
   if (hstatus != 0) { ctx->err = "dio: zero-crossing buffer overflow (signal too noisy for the band filters)"; return KWY_EHIP; }
   return KWY_OK;
 }
@@ -963,17 +957,13 @@ extern "C" int kwy_stonemask(kwy_ctx *ctx, const double *x, int64_t x_length, in
   KWY_HIP(hipSetDevice(ctx->device));
   sm_tables tabs;
   KWY_TRY(sm_tables_for(ctx, fs, &tabs));
-  size_t bx = kwy_pad(sizeof(double) * x_length), bt = kwy_pad(sizeof(double) * T);
-  KWY_TRY(kwy_arena_begin(ctx, bx + 3 * bt));
-  double *dx = kwy_arena<double>(ctx, x_length), *dt = kwy_arena<double>(ctx, T);
-  double *df0 = kwy_arena<double>(ctx, T), *dout = kwy_arena<double>(ctx, T);
-  if (!dx || !dt || !df0 || !dout) { ctx->err = "stonemask: scratch arena too small"; return KWY_ENOMEM; }
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * x_length, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dt, t, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(df0, f0, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
-  const kwy_utterance u = {dx, x_length, dt, df0, T, dout};
+  kwy_staging st(ctx, "stonemask");
+  kwy_utterance u = {x, x_length, t, f0, T, refined_f0};
+  st.in(u.x, x, (size_t)x_length);
+  st.in(u.temporal_positions, t, (size_t)T);
+  st.in(u.f0, f0, (size_t)T);
+  st.out(u.out, refined_f0, (size_t)T);
+  KWY_TRY(st.begin());
   KWY_TRY(sm_launch(ctx, &u, 1, fs, tabs));
-  KWY_HIP(hipMemcpyAsync(refined_f0, dout, sizeof(double) * T, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -1271,27 +1271,22 @@ extern "C" int kwy_fastdtw(kwy_ctx *ctx, const double *x, int64_t Tx, const doub
   KWY_HIP(hipSetDevice(ctx->device));
   for (int attempt = 0; attempt < 2; ++attempt) {
     const bool full = attempt == 1;     // (the capacities are bounds: the second attempt is a safeguard only)
-    size_t bx = kwy_pad(sizeof(double) * Tx * dim), by = kwy_pad(sizeof(double) * Ty * dim);
-    size_t bp = kwy_pad(sizeof(int32_t) * 2 * (Tx + Ty + 2));
-    KWY_TRY(kwy_arena_begin(ctx, dtw_layout(Tx, Ty, dim, radius, full, nullptr) + bx + by + bp + 2 * kwy_pad(64)));
-    double *dx = kwy_arena<double>(ctx, (size_t)Tx * dim), *dy = kwy_arena<double>(ctx, (size_t)Ty * dim);
-    int32_t *dpath = kwy_arena<int32_t>(ctx, 2 * (Tx + Ty + 2));
-    double *ddist = kwy_arena<double>(ctx, 8);
-    int64_t *dlen = kwy_arena<int64_t>(ctx, 8);
-    KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * Tx * dim, hipMemcpyHostToDevice, ctx->stream));
-    KWY_HIP(hipMemcpyAsync(dy, y, sizeof(double) * Ty * dim, hipMemcpyHostToDevice, ctx->stream));
-    int *status;
-    const dtw_pair pr = {dx, dy, (int)Tx, (int)Ty, ddist, dpath, dlen};
-    KWY_TRY(fastdtw_core(ctx, &pr, 1, dim, radius, full, &status));
-    int hstatus = 0;
+    kwy_staging st(ctx, "fastdtw");
+    dtw_pair pr = {x, y, (int)Tx, (int)Ty, dist, path, path_len};
+    int *status, hstatus = 0;
     int64_t hlen = 0;
-    KWY_HIP(hipMemcpyAsync(&hstatus, status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    KWY_HIP(hipMemcpyAsync(&hlen, dlen, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    KWY_HIP(hipMemcpyAsync(dist, ddist, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    KWY_HIP(hipStreamSynchronize(ctx->stream));
+    st.in(pr.x, x, (size_t)Tx * dim);
+    st.in(pr.y, y, (size_t)Ty * dim);
+    st.tmp(pr.path, 2 * (size_t)(Tx + Ty + 2));
+    st.out(pr.dist, dist, 1);
+    st.out(pr.path_len, &hlen, 1);
+    KWY_TRY(st.begin(dtw_layout(Tx, Ty, dim, radius, full, nullptr)));
+    KWY_TRY(fastdtw_core(ctx, &pr, 1, dim, radius, full, &status));
+    st.fetch(status, &hstatus, 1);
+    KWY_TRY(st.finish());
     if (hstatus != 0) continue;  // band storage exceeded
     if (hlen > Tx + Ty) { ctx->err = "fastdtw: path overflow"; return KWY_EHIP; }
-    KWY_HIP(hipMemcpy(path, dpath, sizeof(int32_t) * 2 * hlen, hipMemcpyDeviceToHost));
+    KWY_HIP(hipMemcpy(path, pr.path, sizeof(int32_t) * 2 * hlen, hipMemcpyDeviceToHost));
     *path_len = hlen;
     return KWY_OK;
   }

@@ -330,50 +330,30 @@ static inline size_t ev_span(int64_t rows, int64_t stride, int64_t last) {
   return rows > 0 ? (size_t)((rows - 1) * stride + last) : 0;
 }
 
-template <class T>
-static int ev_upload(kwy_ctx *ctx, const T *host, size_t n, const T **dev) {
-  T *d = kwy_arena<T>(ctx, n);
-  if (n > 0) KWY_HIP(hipMemcpyAsync(d, host, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
-  *dev = d;
-  return KWY_OK;
-}
-
 extern "C" int kwy_mcd(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int cols, int first_col, double *moments,
                        int32_t *status) {
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(ev_check_mcd(ctx, jobs, count, cols, first_col, moments, true));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bytes = kwy_pad(sizeof(double) * 3 * (size_t)count) + kwy_pad(sizeof(int32_t) * (size_t)count);
-  for (int i = 0; i < count; ++i) {
-    const kwy_mcd_job &j = jobs[i];
-    bytes += kwy_pad(sizeof(double) * ev_span(j.a_rows, j.a_stride, cols)) +
-             kwy_pad(sizeof(double) * ev_span(j.b_rows, j.b_stride, cols)) +
-             2 * kwy_pad(sizeof(int32_t) * (size_t)j.rows) + kwy_pad(sizeof(double) * (size_t)j.rows) +
-             kwy_pad(sizeof(double) * (j.mask ? ev_span(j.mask_rows, j.mask_stride, 1) : 0));
-  }
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dm = kwy_arena<double>(ctx, 3 * (size_t)count);
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
+  kwy_staging st(ctx, "mcd");
+  double *dm;
+  int32_t *dstatus;
+  st.out(dm, moments, 3 * (size_t)count);
+  st.out(dstatus, status, (size_t)count);
   std::vector<kwy_mcd_job> staged(jobs, jobs + count);
   for (int i = 0; i < count; ++i) {
     const kwy_mcd_job &j = jobs[i];
     kwy_mcd_job &s = staged[i];
-    KWY_TRY(ev_upload(ctx, j.a, ev_span(j.a_rows, j.a_stride, cols), &s.a));
-    KWY_TRY(ev_upload(ctx, j.b, ev_span(j.b_rows, j.b_stride, cols), &s.b));
-    if (j.idx_a) KWY_TRY(ev_upload(ctx, j.idx_a, (size_t)j.rows, &s.idx_a));
-    if (j.idx_b) KWY_TRY(ev_upload(ctx, j.idx_b, (size_t)j.rows, &s.idx_b));
-    if (j.mask) KWY_TRY(ev_upload(ctx, j.mask, ev_span(j.mask_rows, j.mask_stride, 1), &s.mask));
-    if (j.per_row) s.per_row = kwy_arena<double>(ctx, (size_t)j.rows);
+    st.in(s.a, j.a, ev_span(j.a_rows, j.a_stride, cols));
+    st.in(s.b, j.b, ev_span(j.b_rows, j.b_stride, cols));
+    if (j.idx_a) st.in(s.idx_a, j.idx_a, (size_t)j.rows);
+    if (j.idx_b) st.in(s.idx_b, j.idx_b, (size_t)j.rows);
+    if (j.mask) st.in(s.mask, j.mask, ev_span(j.mask_rows, j.mask_stride, 1));
+    if (j.per_row) st.out(s.per_row, j.per_row, (size_t)j.rows);
   }
+  KWY_TRY(st.begin());
   KWY_TRY(ev_launch_mcd(ctx, staged.data(), count, cols, first_col, dm, dstatus));
-  for (int i = 0; i < count; ++i)
-    if (jobs[i].per_row && jobs[i].rows > 0)
-      KWY_HIP(hipMemcpyAsync(jobs[i].per_row, staged[i].per_row, sizeof(double) * jobs[i].rows, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  KWY_HIP(hipMemcpyAsync(moments, dm, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, ctx->stream));
-  if (status) KWY_HIP(hipMemcpyAsync(status, dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 // ---- f0 and voicing error ----------------------------------------------------------------------------------------------
@@ -425,30 +405,25 @@ extern "C" int kwy_f0_error(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int coun
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(ev_check_f0(ctx, jobs, count, counts, moments, true));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bytes = kwy_pad(sizeof(double) * 3 * (size_t)count) + kwy_pad(sizeof(int64_t) * 4 * (size_t)count) +
-                 kwy_pad(sizeof(int32_t) * (size_t)count);
-  for (int i = 0; i < count; ++i)
-    bytes += kwy_pad(sizeof(double) * (size_t)jobs[i].a_length) + kwy_pad(sizeof(double) * (size_t)jobs[i].b_length) +
-             2 * kwy_pad(sizeof(int32_t) * (size_t)jobs[i].rows);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dm = kwy_arena<double>(ctx, 3 * (size_t)count);
-  int64_t *dc = kwy_arena<int64_t>(ctx, 4 * (size_t)count);
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
+  kwy_staging st(ctx, "f0_error");
+  double *dm;
+  int64_t *dc;
+  int32_t *dstatus;
+  st.out(dm, moments, 3 * (size_t)count);
+  st.out(dc, counts, 4 * (size_t)count);
+  st.out(dstatus, status, (size_t)count);
   std::vector<kwy_f0_error_job> staged(jobs, jobs + count);
   for (int i = 0; i < count; ++i) {
     const kwy_f0_error_job &j = jobs[i];
     kwy_f0_error_job &s = staged[i];
-    KWY_TRY(ev_upload(ctx, j.f0_a, (size_t)j.a_length, &s.f0_a));
-    KWY_TRY(ev_upload(ctx, j.f0_b, (size_t)j.b_length, &s.f0_b));
-    if (j.idx_a) KWY_TRY(ev_upload(ctx, j.idx_a, (size_t)j.rows, &s.idx_a));
-    if (j.idx_b) KWY_TRY(ev_upload(ctx, j.idx_b, (size_t)j.rows, &s.idx_b));
+    st.in(s.f0_a, j.f0_a, (size_t)j.a_length);
+    st.in(s.f0_b, j.f0_b, (size_t)j.b_length);
+    if (j.idx_a) st.in(s.idx_a, j.idx_a, (size_t)j.rows);
+    if (j.idx_b) st.in(s.idx_b, j.idx_b, (size_t)j.rows);
   }
+  KWY_TRY(st.begin());
   KWY_TRY(ev_launch_f0(ctx, staged.data(), count, dc, dm, dstatus));
-  KWY_HIP(hipMemcpyAsync(counts, dc, sizeof(int64_t) * 4 * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(moments, dm, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, ctx->stream));
-  if (status) KWY_HIP(hipMemcpyAsync(status, dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 // ---- merging -------------------------------------------------------------------------------------------------------------
@@ -474,14 +449,13 @@ extern "C" int kwy_moments_merge(kwy_ctx *ctx, const double *moments, int count,
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(ev_check_merge(ctx, moments, count, width, out));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t nm = 3 * (size_t)width * (size_t)count, no = 3 * (size_t)width;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * nm) + kwy_pad(sizeof(double) * no)));
-  double *dm = kwy_arena<double>(ctx, nm), *dout = kwy_arena<double>(ctx, no);
-  KWY_HIP(hipMemcpyAsync(dm, moments, sizeof(double) * nm, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "moments_merge");
+  double *dm, *dout;
+  st.in(dm, moments, 3 * (size_t)width * (size_t)count);
+  st.out(dout, out, 3 * (size_t)width);
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_moments_merge_dev(ctx, dm, count, width, dout));
-  KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 extern "C" int kwy_moments_accumulate_dev(kwy_ctx *ctx, const double *moments, int count, double *acc) {

@@ -137,21 +137,14 @@ extern "C" int kwy_logf0_moments(kwy_ctx *ctx, const kwy_f0_track *tracks, int c
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(f0m_check_tracks(ctx, tracks, count, moments));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bytes = kwy_pad(sizeof(double) * 3 * (size_t)count);
-  for (int i = 0; i < count; ++i) bytes += kwy_pad(sizeof(double) * (size_t)tracks[i].length);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dm = kwy_arena<double>(ctx, 3 * (size_t)count);
+  kwy_staging st(ctx, "logf0_moments");
+  double *dm;
+  st.out(dm, moments, 3 * (size_t)count);
   std::vector<kwy_f0_track> staged(tracks, tracks + count);
-  for (int i = 0; i < count; ++i) {
-    double *d = kwy_arena<double>(ctx, (size_t)tracks[i].length);
-    if (tracks[i].length > 0)
-      KWY_HIP(hipMemcpyAsync(d, tracks[i].f0, sizeof(double) * tracks[i].length, hipMemcpyHostToDevice, ctx->stream));
-    staged[i].f0 = d;
-  }
+  for (int i = 0; i < count; ++i) st.in(staged[i].f0, tracks[i].f0, (size_t)tracks[i].length);
+  KWY_TRY(st.begin());
   KWY_TRY(f0m_launch_moments(ctx, staged.data(), count, dm));
-  KWY_HIP(hipMemcpyAsync(moments, dm, sizeof(double) * 3 * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 extern "C" int kwy_logf0_moments_merge(kwy_ctx *ctx, const double *moments, int count, double *out) {
@@ -201,28 +194,17 @@ extern "C" int kwy_f0_map(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, i
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(f0m_check_maps(ctx, jobs, count, fs, ratio));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bytes = kwy_pad(sizeof(double) * 4) + kwy_pad(sizeof(int32_t) * (size_t)count);
-  for (int i = 0; i < count; ++i) bytes += 2 * kwy_pad(sizeof(double) * (size_t)jobs[i].length);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dstats = kwy_arena<double>(ctx, 4);
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
-  if (stats) KWY_HIP(hipMemcpyAsync(dstats, stats, sizeof(double) * 4, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "f0_map");
+  double *dstats;
+  int32_t *dstatus;
+  st.in(dstats, stats, 4);
+  st.out(dstatus, status, (size_t)count);
   std::vector<kwy_f0_map_job> staged(jobs, jobs + count);
   for (int i = 0; i < count; ++i) {
-    const int64_t n = jobs[i].length;
-    staged[i].f0_in = kwy_arena<double>(ctx, (size_t)n);
-    staged[i].f0_out = kwy_arena<double>(ctx, (size_t)n);
-    if (n > 0)
-      KWY_HIP(hipMemcpyAsync(const_cast<double *>(staged[i].f0_in), jobs[i].f0_in, sizeof(double) * n,
-                             hipMemcpyHostToDevice, ctx->stream));
+    st.in(staged[i].f0_in, jobs[i].f0_in, (size_t)jobs[i].length);
+    st.out(staged[i].f0_out, jobs[i].f0_out, (size_t)jobs[i].length);
   }
+  KWY_TRY(st.begin());
   KWY_TRY(f0m_launch_map(ctx, staged.data(), count, fs, stats ? dstats : nullptr, ratio, dstatus));
-  for (int i = 0; i < count; ++i)
-    if (jobs[i].length > 0)
-      KWY_HIP(hipMemcpyAsync(jobs[i].f0_out, staged[i].f0_out, sizeof(double) * jobs[i].length, hipMemcpyDeviceToHost,
-                             ctx->stream));
-  if (status)
-    KWY_HIP(hipMemcpyAsync(status, dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

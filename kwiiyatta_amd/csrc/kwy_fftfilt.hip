@@ -128,8 +128,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_fft_filter(ff_jobs J, int m, in
 static int ff_warp_table(kwy_ctx *ctx, int N, double alpha, const kwy_c **out) {
   char key[96];
   snprintf(key, sizeof(key), "fftfilt_warp:%d:%.17g", N, alpha);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  return kwy_cached_table<kwy_c>(ctx, key, [&] {
     const int H = N / 2;
     std::vector<kwy_c> h(H + 1);
     for (int k = 0; k <= H; ++k) {
@@ -140,13 +139,8 @@ static int ff_warp_table(kwy_ctx *ctx, int N, double alpha, const kwy_c **out) {
     }
     h[0] = {1.0, 0.0};
     h[H] = {-1.0, 0.0};
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(kwy_c) * (H + 1)));
-    KWY_HIP(hipMemcpy(d, h.data(), sizeof(kwy_c) * (H + 1), hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  *out = (const kwy_c *)it->second;
-  return KWY_OK;
+    return h;
+  }, out);
 }
 
 static bool ff_overlap(const double *a, const double *b, int64_t n) {
@@ -250,15 +244,12 @@ extern "C" int kwy_mcep_filter_fft(kwy_ctx *ctx, const double *x, int64_t n, con
   KWY_TRY(ff_check_common(ctx, order, alpha, hopsize, fft_size));
   KWY_TRY(ff_check_job(ctx, x, n, mc, T, hopsize, y));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t bx = kwy_pad(sizeof(double) * n), bm = kwy_pad(sizeof(double) * T * (order + 1));
-  KWY_TRY(kwy_arena_begin(ctx, 2 * bx + bm));
-  double *dx = kwy_arena<double>(ctx, n), *dy = kwy_arena<double>(ctx, n);
-  double *dm = kwy_arena<double>(ctx, (size_t)T * (order + 1));
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dm, mc, sizeof(double) * T * (order + 1), hipMemcpyHostToDevice, ctx->stream));
-  const kwy_mlsa_job q = {dx, n, dm, T, dy};
+  kwy_staging st(ctx, "mcep_filter_fft");
+  kwy_mlsa_job q = {x, n, mc, T, y};
+  st.in(q.x, x, (size_t)n);
+  st.out(q.y, y, (size_t)n);
+  st.in(q.mc, mc, (size_t)T * (order + 1));
+  KWY_TRY(st.begin());
   KWY_TRY(ff_run(ctx, &q, 1, order, alpha, hopsize, fft_size, ignore_c0));
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -204,23 +204,14 @@ extern "C" int kwy_formant_shift(kwy_ctx *ctx, const kwy_formant_job *jobs, int 
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(fs_check(ctx, jobs, count, K, rho));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bytes = kwy_pad(sizeof(int32_t) * (size_t)count);
-  for (int i = 0; i < count; ++i) bytes += kwy_pad(sizeof(double) * (size_t)jobs[i].rows * K);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
-  std::vector<kwy_formant_job> staged((size_t)count);
-  for (int i = 0; i < count; ++i) {
-    const size_t n = (size_t)jobs[i].rows * K;
-    double *d = kwy_arena<double>(ctx, n);                    // warped in place on the device
-    if (n > 0) KWY_HIP(hipMemcpyAsync(d, jobs[i].sp, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    staged[i] = kwy_formant_job{d, jobs[i].rows, d};
-  }
+  kwy_staging st(ctx, "formant_shift");
+  int32_t *dstatus;
+  st.out(dstatus, status, (size_t)count);
+  std::vector<kwy_formant_job> staged(jobs, jobs + count);
+  for (int i = 0; i < count; ++i)                             // warped in place on the device
+    st.inout(staged[i].out, jobs[i].sp, jobs[i].out, (size_t)jobs[i].rows * K);
+  KWY_TRY(st.begin());
+  for (int i = 0; i < count; ++i) staged[i].sp = staged[i].out;
   KWY_TRY(fs_launch(ctx, staged.data(), count, K, rho, dstatus));
-  for (int i = 0; i < count; ++i) {
-    const size_t n = (size_t)jobs[i].rows * K;
-    if (n > 0) KWY_HIP(hipMemcpyAsync(jobs[i].out, staged[i].out, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (status) KWY_HIP(hipMemcpyAsync(status, dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -216,21 +216,14 @@ extern "C" int kwy_column_moments(kwy_ctx *ctx, const kwy_gv_matrix *mats, int c
   KWY_TRY(gv_check_mats(ctx, mats, count, cols, moments));
   KWY_HIP(hipSetDevice(ctx->device));
   const size_t nm = 3 * (size_t)cols * (size_t)count;
-  size_t bytes = kwy_pad(sizeof(double) * nm);
-  for (int i = 0; i < count; ++i) bytes += kwy_pad(sizeof(double) * (size_t)mats[i].rows * cols);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dm = kwy_arena<double>(ctx, nm);
+  kwy_staging st(ctx, "column_moments");
+  double *dm;
+  st.out(dm, moments, nm);
   std::vector<kwy_gv_matrix> staged(mats, mats + count);
-  for (int i = 0; i < count; ++i) {
-    const size_t n = (size_t)mats[i].rows * cols;
-    double *d = kwy_arena<double>(ctx, n);
-    if (n > 0) KWY_HIP(hipMemcpyAsync(d, mats[i].x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    staged[i].x = d;
-  }
+  for (int i = 0; i < count; ++i) st.in(staged[i].x, mats[i].x, (size_t)mats[i].rows * cols);
+  KWY_TRY(st.begin());
   KWY_TRY(gv_launch_moments(ctx, staged.data(), count, cols, dm));
-  KWY_HIP(hipMemcpyAsync(moments, dm, sizeof(double) * nm, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 static int gv_check_statistic(kwy_ctx *ctx, const double *moments, int count, int cols, const double *gv) {
@@ -253,14 +246,13 @@ extern "C" int kwy_gv_from_moments(kwy_ctx *ctx, const double *moments, int coun
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(gv_check_statistic(ctx, moments, count, cols, gv));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t nm = 3 * (size_t)cols * (size_t)count;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * nm) + kwy_pad(sizeof(double) * cols)));
-  double *dm = kwy_arena<double>(ctx, nm), *dgv = kwy_arena<double>(ctx, (size_t)cols);
-  KWY_HIP(hipMemcpyAsync(dm, moments, sizeof(double) * nm, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "gv_from_moments");
+  double *dm, *dgv;
+  st.in(dm, moments, 3 * (size_t)cols * (size_t)count);
+  st.out(dgv, gv, (size_t)cols);
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_gv_from_moments_dev(ctx, dm, count, cols, dgv));
-  KWY_HIP(hipMemcpyAsync(gv, dgv, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 static int gv_check_jobs(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col, const double *gv,
@@ -325,37 +317,27 @@ extern "C" int kwy_gv_postfilter(kwy_ctx *ctx, const kwy_gv_job *jobs, int count
   KWY_TRY(gv_check_jobs(ctx, jobs, count, cols, first_col, gv, strength, false));
   KWY_HIP(hipSetDevice(ctx->device));
   const size_t nm = 3 * (size_t)cols;
-  size_t bytes = kwy_pad(sizeof(double) * cols) + kwy_pad(sizeof(int32_t) * (size_t)count) +
-                 kwy_pad(sizeof(double) * nm * (size_t)count);
-  for (int i = 0; i < count; ++i) {
-    const size_t n = kwy_pad(sizeof(double) * (size_t)jobs[i].rows * cols);
-    bytes += (jobs[i].base == jobs[i].x ? 2 : 3) * n;
-  }
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dgv = kwy_arena<double>(ctx, (size_t)cols);
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
-  double *dm = kwy_arena<double>(ctx, nm * (size_t)count);
-  KWY_HIP(hipMemcpyAsync(dgv, gv, sizeof(double) * cols, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "gv_postfilter");
+  double *dgv, *dm;
+  int32_t *dstatus;
+  st.in(dgv, gv, (size_t)cols);
+  st.out(dstatus, status, (size_t)count);
+  st.tmp(dm, nm * (size_t)count);
   std::vector<kwy_gv_job> staged(jobs, jobs + count);
   std::vector<kwy_gv_matrix> mats((size_t)count);
   for (int i = 0; i < count; ++i) {
     const size_t n = (size_t)jobs[i].rows * cols;
-    double *dx = kwy_arena<double>(ctx, n), *dbase = dx;
-    if (n > 0) KWY_HIP(hipMemcpyAsync(dx, jobs[i].x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (jobs[i].base != jobs[i].x) {
-      dbase = kwy_arena<double>(ctx, n);
-      if (n > 0) KWY_HIP(hipMemcpyAsync(dbase, jobs[i].base, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    staged[i] = kwy_gv_job{dx, jobs[i].rows, dm + nm * (size_t)i, dbase, kwy_arena<double>(ctx, n)};
-    mats[i] = kwy_gv_matrix{dx, jobs[i].rows};
+    st.in(staged[i].x, jobs[i].x, n);
+    if (jobs[i].base != jobs[i].x) st.in(staged[i].base, jobs[i].base, n);
+    st.out(staged[i].out, jobs[i].out, n);
+  }
+  KWY_TRY(st.begin());
+  for (int i = 0; i < count; ++i) {
+    if (jobs[i].base == jobs[i].x) staged[i].base = staged[i].x;
+    staged[i].moments = dm + nm * (size_t)i;
+    mats[i] = kwy_gv_matrix{staged[i].x, jobs[i].rows};
   }
   KWY_TRY(gv_launch_moments(ctx, mats.data(), count, cols, dm));
   KWY_TRY(gv_launch_apply(ctx, staged.data(), count, cols, first_col, dgv, strength, dstatus));
-  for (int i = 0; i < count; ++i) {
-    const size_t n = (size_t)jobs[i].rows * cols;
-    if (n > 0) KWY_HIP(hipMemcpyAsync(jobs[i].out, staged[i].out, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (status) KWY_HIP(hipMemcpyAsync(status, dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -480,47 +480,23 @@ extern "C" int kwy_gv_ascent(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int co
   if (count == 0) return KWY_OK;
   KWY_TRY(gva_check(ctx, jobs, count, d, gv_mean, gv_var, weight, iterations));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bytes = gva_jobs_scratch(jobs, count, d, iterations) + 2 * kwy_pad(sizeof(double) * d) +
-                 kwy_pad(sizeof(int32_t) * (size_t)count);
-  for (int j = 0; j < count; ++j)
-    bytes += kwy_pad(sizeof(double) * (size_t)jobs[j].T * d * 4) + 2 * kwy_pad(sizeof(double) * (size_t)jobs[j].T * d) +
-             kwy_pad(sizeof(double) * (iterations + 1));
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dmean = kwy_arena<double>(ctx, d), *dvar = kwy_arena<double>(ctx, d);
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
-  KWY_HIP(hipMemcpyAsync(dmean, gv_mean, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dvar, gv_var, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "gv_ascent");
+  double *dmean, *dvar;
+  int32_t *dstatus;
+  st.in(dmean, gv_mean, (size_t)d);
+  st.in(dvar, gv_var, (size_t)d);
+  st.out(dstatus, status, (size_t)count);
   std::vector<kwy_gv_ascent_job> staged(jobs, jobs + count);
   for (int j = 0; j < count; ++j) {
     const size_t n = (size_t)jobs[j].T * d;
-    double *db = kwy_arena<double>(ctx, n * 4), *dy = kwy_arena<double>(ctx, n);
-    double *doff = jobs[j].offset ? kwy_arena<double>(ctx, n) : nullptr;
-    double *dobj = jobs[j].objective ? kwy_arena<double>(ctx, iterations + 1) : nullptr;
-    KWY_HIP(hipMemcpyAsync(db, jobs[j].band, sizeof(double) * n * 4, hipMemcpyHostToDevice, ctx->stream));
-    KWY_HIP(hipMemcpyAsync(dy, jobs[j].y, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (doff) KWY_HIP(hipMemcpyAsync(doff, jobs[j].offset, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    staged[j] = kwy_gv_ascent_job{db, doff, dy, jobs[j].T, dobj};
+    st.in(staged[j].band, jobs[j].band, n * 4);
+    st.inout(staged[j].y, jobs[j].y, n);
+    if (jobs[j].offset) st.in(staged[j].offset, jobs[j].offset, n);
+    if (jobs[j].objective) st.out(staged[j].objective, jobs[j].objective, (size_t)iterations + 1);
   }
+  KWY_TRY(st.begin(gva_jobs_scratch(jobs, count, d, iterations)));
   KWY_TRY(gva_run(ctx, staged.data(), count, d, dmean, dvar, weight, iterations, dstatus));
-  std::vector<std::vector<double>> hy(count), ho(count);
-  std::vector<int32_t> hs(count);
-  for (int j = 0; j < count; ++j) {
-    hy[j].resize((size_t)jobs[j].T * d);
-    KWY_HIP(hipMemcpyAsync(hy[j].data(), staged[j].y, sizeof(double) * hy[j].size(), hipMemcpyDeviceToHost, ctx->stream));
-    if (jobs[j].objective) {
-      ho[j].resize(iterations + 1);
-      KWY_HIP(hipMemcpyAsync(ho[j].data(), staged[j].objective, sizeof(double) * (iterations + 1), hipMemcpyDeviceToHost,
-                             ctx->stream));
-    }
-  }
-  KWY_HIP(hipMemcpyAsync(hs.data(), dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  for (int j = 0; j < count; ++j) {
-    std::copy(hy[j].begin(), hy[j].end(), jobs[j].y);
-    if (jobs[j].objective) std::copy(ho[j].begin(), ho[j].end(), jobs[j].objective);
-    if (status) status[j] = hs[j];
-  }
-  return KWY_OK;
+  return st.finish();
 }
 
 static int gvs_check(kwy_ctx *ctx, const double *moments, int count, int cols, const double *mean, const double *var) {
@@ -545,13 +521,12 @@ extern "C" int kwy_gv_stats_from_moments(kwy_ctx *ctx, const double *moments, in
   if (!ctx) return KWY_EINVAL;
   KWY_TRY(gvs_check(ctx, moments, count, cols, gv_mean, gv_var));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t nm = 3 * (size_t)cols * (size_t)count;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * nm) + 2 * kwy_pad(sizeof(double) * cols)));
-  double *dm = kwy_arena<double>(ctx, nm), *dmean = kwy_arena<double>(ctx, cols), *dvar = kwy_arena<double>(ctx, cols);
-  KWY_HIP(hipMemcpyAsync(dm, moments, sizeof(double) * nm, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "gv_stats_from_moments");
+  double *dm, *dmean, *dvar;
+  st.in(dm, moments, 3 * (size_t)cols * (size_t)count);
+  st.out(dmean, gv_mean, (size_t)cols);
+  st.out(dvar, gv_var, (size_t)cols);
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_gv_stats_from_moments_dev(ctx, dm, count, cols, dmean, dvar));
-  KWY_HIP(hipMemcpyAsync(gv_mean, dmean, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(gv_var, dvar, sizeof(double) * cols, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -30,7 +30,7 @@ struct kwy_ctx {
   kwy_c *d_tw[20] = {nullptr};             // d_tw[l]: exp(-2 pi i k / 2^l), k < 2^l
   kwy_c *d_twp[20] = {nullptr};            // d_twp[l]: powers of the stride-64 pass factors of a 2^l-point transform
   std::map<uint64_t, uint4 *> d_poly;      // stride(steps) -> x^(stride*t) mod P, t < 256
-  std::map<std::string, double *> d_mats;  // cached host-built matrices (mcep etc.)
+  std::map<std::string, void *> d_mats;    // cached host-built tables (kwy_cached_table)
   std::map<std::string, int64_t> i_vals;   // small cached integers that go with them
 
   // optional per-kernel timing with HIP events on this context's stream
@@ -87,7 +87,48 @@ static inline T *kwy_arena(kwy_ctx *ctx, size_t n) {
 }
 static inline size_t kwy_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// --- staging of the entries on host pointers ------------------------------------------
+// A host entry names every buffer it stages once: in() is uploaded, out() is downloaded, inout() both (worked on in
+// place on the device), tmp() is device scratch that keeps its place among them.  begin() sizes the arena for all of
+// them (kwy_pad(sizeof(T) * n) each) plus `scratch` bytes the entry's core takes afterwards, takes the device pointers
+// in the order of the statements, stores them where the statements said, and enqueues the uploads; finish() enqueues
+// the downloads and synchronises.  A buffer of no elements is allocated (zero bytes) and never copied; neither is one
+// whose host pointer is null (an optional output).  The device pointers are valid from begin() on: an alias
+// (base == x) is filled in after it.
+struct kwy_staging {
+  kwy_ctx *ctx;
+  const char *entry;   // for "<entry>: scratch arena too small"
+  struct buffer { void **dev; const void *src; void *dst; size_t bytes; };
+  std::vector<buffer> buffers;
+  kwy_staging(kwy_ctx *c, const char *e) : ctx(c), entry(e) {}
+  template <class D, class T> void in(D *&d, const T *h, size_t n) { add(d, h, nullptr, sizeof(T) * n); }
+  template <class D, class T> void out(D *&d, T *h, size_t n) { add(d, nullptr, h, sizeof(T) * n); }
+  template <class D, class T> void inout(D *&d, T *h, size_t n) { inout(d, h, h, n); }
+  template <class D, class T> void inout(D *&d, const T *src, T *dst, size_t n) { add(d, src, dst, sizeof(T) * n); }
+  template <class D> void tmp(D *&d, size_t n) { add(d, nullptr, nullptr, sizeof(D) * n); }
+  // after begin(): n values of a buffer that was not staged as an output (a status word in the core's scratch or in a
+  // tmp() block), downloaded by finish() with the others
+  template <class D, class T> void fetch(D *&d, T *h, size_t n) { add(d, nullptr, h, sizeof(T) * n); }
+  int begin(size_t scratch = 0);
+  int finish();
+ private:
+  template <class D> void add(D *&d, const void *src, void *dst, size_t bytes) {
+    buffers.push_back({(void **)&d, src, dst, bytes});
+  }
+};
+
 // --- tables -----------------------------------------------------------------
+// The device copy of a host-built table, made on first use (never inside a captured region) and kept in ctx->d_mats
+// until the context goes: `build` returns the table as a std::vector (or a reference to one that outlives the call).
+int kwy_table_upload(kwy_ctx *ctx, const std::string &key, const void *host, size_t bytes, void **out);
+template <class T, class BUILD>
+static inline int kwy_cached_table(kwy_ctx *ctx, const std::string &key, BUILD build, const T **out) {
+  auto it = ctx->d_mats.find(key);
+  if (it != ctx->d_mats.end()) { *out = (const T *)it->second; return KWY_OK; }
+  const std::vector<T> &h = build();
+  return kwy_table_upload(ctx, key, h.data(), sizeof(T) * h.size(), (void **)out);
+}
+
 int kwy_get_twiddles(kwy_ctx *ctx, int log2n, const kwy_c **out);
 // w^1 .. w^7 of every factor w the stride-64 radix-8 pass of a 2^log2h-point LDS transform uses (kwy_device.hpp:
 // kwy_tw_powers), KWY_TWP_ENTRY complex per factor; made together with the twiddles of that length.  Transforms below

@@ -206,8 +206,7 @@ int kwy_get_sp2mc_matrix(kwy_ctx *ctx, int N, int order, double alpha, const dou
   char key[96];
   snprintf(key, sizeof(key), "sp2mc:%d:%d:%.17g", N, order, alpha);
   std::string cnt_key = std::string(key) + ":ncut";
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  KWY_TRY(kwy_cached_table<double>(ctx, key, [&] {
     std::vector<double> F;
     freqt_matrix(N, order, alpha, F);
     // columns beyond ncut contribute < 1e-40 of a unit cepstral value: drop them
@@ -221,13 +220,9 @@ int kwy_get_sp2mc_matrix(kwy_ctx *ctx, int N, int order, double alpha, const dou
     std::vector<double> Fp((size_t)nc * MC_STRIDE, 0.0);
     for (int n = 0; n < nc; ++n)
       for (int j = 0; j <= order; ++j) Fp[(size_t)n * MC_STRIDE + j] = F[(size_t)n * (order + 1) + j];
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(double) * Fp.size()));
-    KWY_HIP(hipMemcpy(d, Fp.data(), sizeof(double) * Fp.size(), hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
     ctx->i_vals[cnt_key] = nc;
-  }
-  *out = it->second;
+    return Fp;
+  }, out));
   *ncut = (int)ctx->i_vals[cnt_key];
   return KWY_OK;
 }
@@ -263,8 +258,7 @@ static std::map<std::string, std::vector<double>> g_dense_host;     // built onc
 static int get_sp2mc_dense(kwy_ctx *ctx, int K, int order, double alpha, const double **out) {
   char key[96];
   snprintf(key, sizeof(key), "sp2mc_dense:%d:%d:%.17g", K, order, alpha);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  return kwy_cached_table<double>(ctx, key, [&]() -> const std::vector<double> & {
     std::lock_guard<std::mutex> guard(g_dense_mutex);
     std::vector<double> &G = g_dense_host[key];
     if (G.empty()) {
@@ -294,21 +288,15 @@ static int get_sp2mc_dense(kwy_ctx *ctx, int K, int order, double alpha, const d
         for (int j = 0; j <= order; ++j) G[(size_t)k * MC_STRIDE + j] = (double)acc[j];
       }
     }
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(double) * G.size()));
-    KWY_HIP(hipMemcpy(d, G.data(), sizeof(double) * G.size(), hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  *out = it->second;
-  return KWY_OK;
+    return G;
+  }, out);
 }
 
 
 static int get_mc2sp_dense(kwy_ctx *ctx, int K, int order, double alpha, const double **out) {
   char key[96];
   snprintf(key, sizeof(key), "mc2sp_dense:%d:%d:%.17g", K, order, alpha);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  return kwy_cached_table<double>(ctx, key, [&]() -> const std::vector<double> & {
     std::lock_guard<std::mutex> guard(g_dense_mutex);
     std::vector<double> &G2 = g_dense_host[key];
     if (G2.empty()) {
@@ -329,13 +317,8 @@ static int get_mc2sp_dense(kwy_ctx *ctx, int K, int order, double alpha, const d
         for (int j = 0; j <= order; ++j) G2[(size_t)j * K + k] = (double)acc[j];
       }
     }
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(double) * G2.size()));
-    KWY_HIP(hipMemcpy(d, G2.data(), sizeof(double) * G2.size(), hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  *out = it->second;
-  return KWY_OK;
+    return G2;
+  }, out);
 }
 
 static int launch_sp2mc_dense(kwy_ctx *ctx, const double *sp, int64_t T, int K, int order, double alpha, double *mc) {
@@ -405,14 +388,13 @@ extern "C" int kwy_sp2mc(kwy_ctx *ctx, const double *sp, int64_t T, int K, int o
   int l;
   KWY_TRY(mcep_check(ctx, sp, mc, T, K, order, alpha, &l));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bs = kwy_pad(sizeof(double) * T * K), bm = kwy_pad(sizeof(double) * T * (order + 1));
-  KWY_TRY(kwy_arena_begin(ctx, bs + bm));
-  double *dsp = kwy_arena<double>(ctx, (size_t)T * K), *dmc = kwy_arena<double>(ctx, (size_t)T * (order + 1));
-  KWY_HIP(hipMemcpyAsync(dsp, sp, sizeof(double) * T * K, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "sp2mc");
+  double *dsp, *dmc;
+  st.in(dsp, sp, (size_t)T * K);
+  st.out(dmc, mc, (size_t)T * (order + 1));
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_sp2mc_dev(ctx, dsp, T, K, order, alpha, dmc));
-  KWY_HIP(hipMemcpyAsync(mc, dmc, sizeof(double) * T * (order + 1), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 extern "C" int kwy_mc2sp(kwy_ctx *ctx, const double *mc, int64_t T, int order, double alpha, int fftlen,
@@ -421,12 +403,11 @@ extern "C" int kwy_mc2sp(kwy_ctx *ctx, const double *mc, int64_t T, int order, d
   const int K = fftlen / 2 + 1;
   KWY_TRY(mcep_check(ctx, mc, sp, T, K, order, alpha, &l));
   KWY_HIP(hipSetDevice(ctx->device));
-  size_t bs = kwy_pad(sizeof(double) * T * K), bm = kwy_pad(sizeof(double) * T * (order + 1));
-  KWY_TRY(kwy_arena_begin(ctx, bs + bm));
-  double *dsp = kwy_arena<double>(ctx, (size_t)T * K), *dmc = kwy_arena<double>(ctx, (size_t)T * (order + 1));
-  KWY_HIP(hipMemcpyAsync(dmc, mc, sizeof(double) * T * (order + 1), hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "mc2sp");
+  double *dsp, *dmc;
+  st.out(dsp, sp, (size_t)T * K);
+  st.in(dmc, mc, (size_t)T * (order + 1));
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_mc2sp_dev(ctx, dmc, T, order, alpha, fftlen, dsp));
-  KWY_HIP(hipMemcpyAsync(sp, dsp, sizeof(double) * T * K, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -1625,59 +1625,35 @@ extern "C" int kwy_convert_mcep_gv_dev(kwy_ctx *ctx, const double *mc, int64_t T
 }
 
 // ---- the entries on host pointers ---------------------------------------------------------------------------------
-// device copies of what such a call brings and takes home: x and y (T rows of `width`), the joint mixture over `joint`
-// dimensions, and where asked for the log-likelihoods, the ascent's objective, its statistics and its status word
+// what every such call brings and takes home: x and y (T rows of `width`) and the joint mixture over `joint` dimensions
 struct ml_staged {
-  double *x, *y, *w, *mu, *cv, *lik, *obj, *gv_mean, *gv_var;
-  int32_t *gv_status;
+  double *x, *y, *w, *mu, *cv;
 };
-static void ml_staged_buffers(ml_arena &a, ml_staged &s, int64_t T, int width, int M, int joint, bool lik, bool gv) {
-  a.take(s.x, (size_t)T * width);
-  a.take(s.y, (size_t)T * width);
-  a.take(s.w, M);
-  a.take(s.mu, (size_t)M * joint);
-  a.take(s.cv, (size_t)M * joint * joint);
-  if (lik) a.take(s.lik, KWY_MLPG_EM_MAX + 1);
-  if (gv) {
-    a.take(s.obj, KWY_MLPG_GV_MAX + 1);
-    a.take(s.gv_mean, width);
-    a.take(s.gv_var, width);
-    a.take(s.gv_status, 16);
-  }
+static void ml_stage(kwy_staging &st, ml_staged &s, const double *x, int64_t T, int width, int M, int joint,
+                     const double *weights, const double *means, const double *covs, double *y) {
+  st.in(s.x, x, (size_t)T * width);
+  st.out(s.y, y, (size_t)T * width);
+  st.in(s.w, weights, (size_t)M);
+  st.in(s.mu, means, (size_t)M * joint);
+  st.in(s.cv, covs, (size_t)M * joint * joint);
 }
-static int ml_upload(kwy_ctx *ctx, const ml_staged &s, const double *x, int64_t T, int width, int M, int joint,
-                     const double *weights, const double *means, const double *covs) {
-  KWY_HIP(hipMemcpyAsync(s.x, x, sizeof(double) * T * width, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(s.w, weights, sizeof(double) * M, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(s.mu, means, sizeof(double) * M * joint, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(s.cv, covs, sizeof(double) * (size_t)M * joint * joint, hipMemcpyHostToDevice, ctx->stream));
-  return KWY_OK;
-}
-// y, the optional series (nl log-likelihoods, no objective values) and the status words in one synchronisation; the
-// core's status word 1 or 2 becomes the entry's message, and then only y has been written
-static int ml_read_back(kwy_ctx *ctx, const char *entry, const ml_staged &s, const int *core_status, double *y,
-                        size_t ny, double *loglik, int nl, double *objective, int no, int32_t *gv_status) {
+// the staged outputs and the core's status word in one synchronisation; word 1 or 2 becomes the entry's message
+static int ml_finish(kwy_staging &st, int *core_status) {
+  kwy_ctx *ctx = st.ctx;
   int hstatus = 0;
-  int32_t hgv = 0;
-  std::vector<double> hl(nl), ho(no);
-  KWY_HIP(hipMemcpyAsync(y, s.y, sizeof(double) * ny, hipMemcpyDeviceToHost, ctx->stream));
-  if (nl) KWY_HIP(hipMemcpyAsync(hl.data(), s.lik, sizeof(double) * nl, hipMemcpyDeviceToHost, ctx->stream));
-  if (no) KWY_HIP(hipMemcpyAsync(ho.data(), s.obj, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(&hstatus, core_status, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  if (no) KWY_HIP(hipMemcpyAsync(&hgv, s.gv_status, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
+  st.fetch(core_status, &hstatus, 1);
+  KWY_TRY(st.finish());
   if (hstatus != 0) {
-    ctx->err = std::string(entry) + (hstatus == 1 ? ": source covariance is not positive definite"
-                                                  : ": MLPG system is not positive definite");
+    ctx->err = std::string(st.entry) + (hstatus == 1 ? ": source covariance is not positive definite"
+                                                     : ": MLPG system is not positive definite");
     return KWY_ENUMERIC;
   }
-  if (loglik) std::copy(hl.begin(), hl.end(), loglik);
-  if (objective) std::copy(ho.begin(), ho.end(), objective);
-  if (gv_status) *gv_status = hgv;
   return KWY_OK;
 }
 
-// the three kwy_gmm_mlpg* entries: o.gv (if any) with the statistics on the host
+// the three kwy_gmm_mlpg* entries: o.gv (if any) with the statistics on the host.  The optional series (nl
+// log-likelihoods, no objective values) and the ascent's status word come home through host copies: on a status word of
+// the core only y has been written.
 static int ml_convert_host(kwy_ctx *ctx, const char *entry, const double *x, int64_t T, int d, int M,
                            const double *weights, const double *means, const double *covs, int diff, ml_opts o,
                            double *y, double *loglik, double *objective, int32_t *gv_status) {
@@ -1685,24 +1661,32 @@ static int ml_convert_host(kwy_ctx *ctx, const char *entry, const double *x, int
   KWY_TRY(ml_check(ctx, ml_job{x, y, nullptr, nullptr, T, nullptr, nullptr}, d, M, host, o));
   KWY_HIP(hipSetDevice(ctx->device));
   const int nl = loglik && o.em >= 0 ? o.em + 1 : 0, no = o.gv ? o.gv->iterations + 1 : 0;
-  ml_staged s = {};
-  ml_arena measure{nullptr}, take{ctx};
-  ml_staged_buffers(measure, s, T, d, M, 6 * d, o.em_only || o.gv, o.gv);
-  KWY_TRY(kwy_arena_begin(ctx, measure.bytes + ml_pass_bytes(&T, 1, d, M, host, o)));
-  ml_staged_buffers(take, s, T, d, M, 6 * d, o.em_only || o.gv, o.gv);
-  KWY_TRY(ml_upload(ctx, s, x, T, d, M, 6 * d, weights, means, covs));
+  const size_t scratch = ml_pass_bytes(&T, 1, d, M, host, o);
+  kwy_staging st(ctx, entry);
+  ml_staged s;
+  double *dlik = nullptr, *dobj = nullptr;
+  std::vector<double> hl(nl), ho(no);
+  int32_t hgv = 0;
   ml_gv_opts gv;
+  ml_stage(st, s, x, T, d, M, 6 * d, weights, means, covs, y);
+  if (nl) st.out(dlik, hl.data(), (size_t)nl);
   if (o.gv) {
     gv = *o.gv;
-    KWY_HIP(hipMemcpyAsync(s.gv_mean, gv.mean, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-    KWY_HIP(hipMemcpyAsync(s.gv_var, gv.var, sizeof(double) * d, hipMemcpyHostToDevice, ctx->stream));
-    gv.mean = s.gv_mean; gv.var = s.gv_var; gv.status = s.gv_status;
+    st.out(dobj, ho.data(), (size_t)no);
+    st.in(gv.mean, o.gv->mean, (size_t)d);
+    st.in(gv.var, o.gv->var, (size_t)d);
+    st.out(gv.status, &hgv, 1);
     o.gv = &gv;
   }
-  const ml_job job = {s.x, s.y, nullptr, nullptr, T, nl ? s.lik : nullptr, o.gv ? s.obj : nullptr};
+  KWY_TRY(st.begin(scratch));
+  const ml_job job = {s.x, s.y, nullptr, nullptr, T, dlik, dobj};
   int *status;
   KWY_TRY(ml_convert_pass(ctx, &job, 1, 0, d, d, d, M, ml_mixture{s.w, s.mu, s.cv, diff, nullptr}, o, &status));
-  return ml_read_back(ctx, entry, s, status, y, (size_t)T * d, loglik, nl, objective, no, gv_status);
+  KWY_TRY(ml_finish(st, status));
+  if (loglik) std::copy(hl.begin(), hl.end(), loglik);
+  if (objective) std::copy(ho.begin(), ho.end(), objective);
+  if (gv_status) *gv_status = hgv;
+  return KWY_OK;
 }
 
 extern "C" int kwy_gmm_mlpg(kwy_ctx *ctx, const double *x, int64_t T, int d, int M, const double *weights,
@@ -1791,13 +1775,11 @@ extern "C" int kwy_gmm_convert_frames(kwy_ctx *ctx, const double *x, int64_t T, 
                                       const double *means, const double *covs, int diff, double *y) {
   KWY_TRY(soft_check(ctx, x, T, D, M, weights, means, covs, y));
   KWY_HIP(hipSetDevice(ctx->device));
-  ml_staged s = {};
-  ml_arena measure{nullptr}, take{ctx};
-  ml_staged_buffers(measure, s, T, D, M, 2 * D, false, false);
-  KWY_TRY(kwy_arena_begin(ctx, measure.bytes + soft_bytes(T, D, M)));
-  ml_staged_buffers(take, s, T, D, M, 2 * D, false, false);
-  KWY_TRY(ml_upload(ctx, s, x, T, D, M, 2 * D, weights, means, covs));
+  kwy_staging st(ctx, "gmm_convert_frames");
+  ml_staged s;
+  ml_stage(st, s, x, T, D, M, 2 * D, weights, means, covs, y);
+  KWY_TRY(st.begin(soft_bytes(T, D, M)));
   int *status;
   KWY_TRY(soft_core(ctx, s.x, T, D, M, ml_mixture{s.w, s.mu, s.cv, diff, nullptr}, s.y, &status));
-  return ml_read_back(ctx, "gmm_convert_frames", s, status, y, (size_t)T * D, nullptr, 0, nullptr, 0, nullptr);
+  return ml_finish(st, status);
 }

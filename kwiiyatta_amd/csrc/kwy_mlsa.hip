@@ -255,14 +255,13 @@ extern "C" int kwy_mc2b(kwy_ctx *ctx, const double *mc, int64_t T, int order, do
   if (!ctx) return KWY_EINVAL;
   if (!mc || !b || T <= 0 || order < 1) { ctx->err = "mc2b: bad argument"; return KWY_EINVAL; }
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t bm = kwy_pad(sizeof(double) * T * (order + 1));
-  KWY_TRY(kwy_arena_begin(ctx, 2 * bm));
-  double *dmc = kwy_arena<double>(ctx, (size_t)T * (order + 1)), *db = kwy_arena<double>(ctx, (size_t)T * (order + 1));
-  KWY_HIP(hipMemcpyAsync(dmc, mc, sizeof(double) * T * (order + 1), hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "mc2b");
+  double *dmc, *db;
+  st.in(dmc, mc, (size_t)T * (order + 1));
+  st.out(db, b, (size_t)T * (order + 1));
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_mc2b_dev(ctx, dmc, T, order, alpha, db));
-  KWY_HIP(hipMemcpyAsync(b, db, sizeof(double) * T * (order + 1), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 extern "C" int kwy_mlsa_synthesis_dev(kwy_ctx *ctx, const double *x, int64_t n, const double *b, int64_t T,
@@ -308,14 +307,12 @@ extern "C" int kwy_mlsa_synthesis(kwy_ctx *ctx, const double *x, int64_t n, cons
                                   double alpha, int pd, int hopsize, double *y) {
   KWY_TRY(mlsa_check(ctx, x, n, b, T, order, alpha, pd, hopsize, y));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t bx = kwy_pad(sizeof(double) * n), bm = kwy_pad(sizeof(double) * T * (order + 1));
-  KWY_TRY(kwy_arena_begin(ctx, 2 * bx + bm));
-  double *dx = kwy_arena<double>(ctx, n), *dy = kwy_arena<double>(ctx, n);
-  double *db = kwy_arena<double>(ctx, (size_t)T * (order + 1));
-  KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(db, b, sizeof(double) * T * (order + 1), hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "mlsa_synthesis");
+  double *dx, *dy, *db;
+  st.in(dx, x, (size_t)n);
+  st.out(dy, y, (size_t)n);
+  st.in(db, b, (size_t)T * (order + 1));
+  KWY_TRY(st.begin());
   KWY_TRY(mlsa_core(ctx, mlsa_one(dx, n, nullptr, db, T, dy), order, alpha, pd, hopsize));
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

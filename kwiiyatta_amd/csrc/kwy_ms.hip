@@ -281,24 +281,16 @@ extern "C" int kwy_ms_logspectra(kwy_ctx *ctx, const kwy_gv_matrix *mats, int co
   int log2h;
   KWY_TRY(ms_check_mats(ctx, mats, count, cols, L, spectra, valid, &log2h));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t ns = (size_t)count * cols * (L / 2 + 1), nv = (size_t)count * cols;
-  size_t bytes = kwy_pad(sizeof(double) * ns) + kwy_pad(sizeof(int32_t) * nv);
-  for (int i = 0; i < count; ++i) bytes += kwy_pad(sizeof(double) * (size_t)mats[i].rows * cols);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *ds = kwy_arena<double>(ctx, ns);
-  int32_t *dv = kwy_arena<int32_t>(ctx, nv);
+  kwy_staging st(ctx, "ms_logspectra");
+  double *ds;
+  int32_t *dv;
+  st.out(ds, spectra, (size_t)count * cols * (L / 2 + 1));
+  st.out(dv, valid, (size_t)count * cols);
   std::vector<kwy_gv_matrix> staged(mats, mats + count);
-  for (int i = 0; i < count; ++i) {
-    const size_t n = (size_t)mats[i].rows * cols;
-    double *d = kwy_arena<double>(ctx, n);
-    if (n > 0) KWY_HIP(hipMemcpyAsync(d, mats[i].x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    staged[i].x = d;
-  }
+  for (int i = 0; i < count; ++i) st.in(staged[i].x, mats[i].x, (size_t)mats[i].rows * cols);
+  KWY_TRY(st.begin());
   KWY_TRY(ms_launch_logspectra(ctx, log2h, staged.data(), count, cols, ds, dv));
-  KWY_HIP(hipMemcpyAsync(spectra, ds, sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(valid, dv, sizeof(int32_t) * nv, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 // ------------------------------------------------------------------------------------------------- statistics
@@ -333,17 +325,15 @@ extern "C" int kwy_ms_stats_update(kwy_ctx *ctx, double *acc, const double *spec
   int log2h;
   KWY_TRY(ms_check_stats(ctx, acc, spectra, valid, count, cols, L, &log2h));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t na = 3 * (size_t)cols * (L / 2 + 1), ns = (size_t)count * cols * (L / 2 + 1), nv = (size_t)count * cols;
-  KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * na) + kwy_pad(sizeof(double) * ns) + kwy_pad(sizeof(int32_t) * nv)));
-  double *da = kwy_arena<double>(ctx, na), *ds = kwy_arena<double>(ctx, ns);
-  int32_t *dv = kwy_arena<int32_t>(ctx, nv);
-  KWY_HIP(hipMemcpyAsync(da, acc, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(ds, spectra, sizeof(double) * ns, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dv, valid, sizeof(int32_t) * nv, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "ms_stats_update");
+  double *da, *ds;
+  int32_t *dv;
+  st.inout(da, acc, 3 * (size_t)cols * (L / 2 + 1));
+  st.in(ds, spectra, (size_t)count * cols * (L / 2 + 1));
+  st.in(dv, valid, (size_t)count * cols);
+  KWY_TRY(st.begin());
   KWY_TRY(ms_launch_stats(ctx, da, ds, dv, count, cols, L));
-  KWY_HIP(hipMemcpyAsync(acc, da, sizeof(double) * na, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
 
 // ----------------------------------------------------------------------------------------------------- filter
@@ -408,33 +398,22 @@ extern "C" int kwy_ms_postfilter(kwy_ctx *ctx, const kwy_ms_job *jobs, int count
   KWY_TRY(ms_check_jobs(ctx, jobs, count, cols, first_col, L, statsG, statsN, strength, &log2h));
   KWY_HIP(hipSetDevice(ctx->device));
   const size_t na = 3 * (size_t)cols * (L / 2 + 1);
-  size_t bytes = 2 * kwy_pad(sizeof(double) * na) + kwy_pad(sizeof(int32_t) * (size_t)count);
-  for (int i = 0; i < count; ++i) {
-    const size_t n = kwy_pad(sizeof(double) * (size_t)jobs[i].rows * cols);
-    bytes += (jobs[i].base == jobs[i].x ? 2 : 3) * n;
-  }
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
-  double *dG = kwy_arena<double>(ctx, na), *dN = kwy_arena<double>(ctx, na);
-  int32_t *dstatus = kwy_arena<int32_t>(ctx, (size_t)count);
-  KWY_HIP(hipMemcpyAsync(dG, statsG, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dN, statsN, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "ms_postfilter");
+  double *dG, *dN;
+  int32_t *dstatus;
+  st.in(dG, statsG, na);
+  st.in(dN, statsN, na);
+  st.out(dstatus, status, (size_t)count);
   std::vector<kwy_ms_job> staged(jobs, jobs + count);
   for (int i = 0; i < count; ++i) {
     const size_t n = (size_t)jobs[i].rows * cols;
-    double *dx = kwy_arena<double>(ctx, n), *dbase = dx;
-    if (n > 0) KWY_HIP(hipMemcpyAsync(dx, jobs[i].x, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    if (jobs[i].base != jobs[i].x) {
-      dbase = kwy_arena<double>(ctx, n);
-      if (n > 0) KWY_HIP(hipMemcpyAsync(dbase, jobs[i].base, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    staged[i] = kwy_ms_job{dx, jobs[i].rows, dbase, kwy_arena<double>(ctx, n)};
+    st.in(staged[i].x, jobs[i].x, n);
+    if (jobs[i].base != jobs[i].x) st.in(staged[i].base, jobs[i].base, n);
+    st.out(staged[i].out, jobs[i].out, n);
   }
+  KWY_TRY(st.begin());
+  for (int i = 0; i < count; ++i)
+    if (jobs[i].base == jobs[i].x) staged[i].base = staged[i].x;
   KWY_TRY(ms_launch_filter(ctx, log2h, staged.data(), count, cols, first_col, dG, dN, strength, dstatus));
-  for (int i = 0; i < count; ++i) {
-    const size_t n = (size_t)jobs[i].rows * cols;
-    if (n > 0) KWY_HIP(hipMemcpyAsync(jobs[i].out, staged[i].out, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  if (status) KWY_HIP(hipMemcpyAsync(status, dstatus, sizeof(int32_t) * count, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

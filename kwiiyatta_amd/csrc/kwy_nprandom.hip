@@ -685,14 +685,12 @@ extern "C" int kwy_np_normal(kwy_ctx *ctx, void *state, double loc, double scale
   KWY_TRY(np_check(ctx, state, n, out));
   if (n == 0) return KWY_OK;
   KWY_HIP(hipSetDevice(ctx->device));
-  KWY_TRY(kwy_arena_begin(ctx, np_scratch_bytes(n) + kwy_pad(sizeof(np_state)) + kwy_pad(sizeof(double) * (size_t)n)));
-  np_state *ds = (np_state *)kwy_arena_alloc(ctx, sizeof(np_state));
-  double *dout = kwy_arena<double>(ctx, (size_t)n);
-  KWY_HIP(hipMemcpyAsync(ds, state, sizeof(np_state), hipMemcpyHostToDevice, ctx->stream));
-  double *outs[1] = {dout};
+  kwy_staging st(ctx, "np_normal");
+  np_state *ds;
+  double *outs[1];
+  st.inout(ds, (np_state *)state, 1);
+  st.out(outs[0], out, (size_t)n);
+  KWY_TRY(st.begin(np_scratch_bytes(n)));
   KWY_TRY(np_core(ctx, ds, loc, scale, take_abs, 1, n, outs));
-  KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(state, ds, sizeof(np_state), hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -298,17 +298,12 @@ extern "C" int kwy_pitch_shift(kwy_ctx *ctx, const double *x, int64_t n, int fs,
   const kwy_pitch_job host = {x, n, y, positions};
   KWY_TRY(pitch_check(ctx, &host, 1, fs, rate));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t K = (size_t)kwy_pitch_frames(n, fs, rate);
-  KWY_TRY(kwy_arena_begin(ctx, pitch_bytes(&host, 1, fs, rate) + 2 * kwy_pad(sizeof(double) * (size_t)n) +
-                                   kwy_pad(sizeof(int32_t) * K)));
-  double *dx = kwy_arena<double>(ctx, (size_t)n), *dy = kwy_arena<double>(ctx, (size_t)n);
-  int32_t *dpos = kwy_arena<int32_t>(ctx, K);
-  if (n > 0) KWY_HIP(hipMemcpyAsync(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  const kwy_pitch_job staged = {dx, n, dy, dpos};
+  kwy_staging st(ctx, "pitch_shift");
+  kwy_pitch_job staged = host;
+  st.in(staged.x, x, (size_t)n);
+  st.out(staged.y, y, (size_t)n);
+  st.out(staged.pos, positions, (size_t)kwy_pitch_frames(n, fs, rate));
+  KWY_TRY(st.begin(pitch_bytes(&host, 1, fs, rate)));
   KWY_TRY(pitch_run(ctx, &staged, 1, fs, rate));
-  if (n > 0) KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  if (positions && K > 0)
-    KWY_HIP(hipMemcpyAsync(positions, dpos, sizeof(int32_t) * K, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

@@ -139,16 +139,7 @@ static int stretch_make_plan(kwy_ctx *ctx, int K, int new_K, stretch_plan *p, co
   p->rows = (int)(ST_LDS_DOUBLES / span);
   if (p->rows > ST_MAX_ROWS) p->rows = ST_MAX_ROWS;
   const std::string key = "stretch:" + std::to_string(p->up) + "/" + std::to_string(p->down);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
-    const std::vector<double> h = design_taps(p->numtaps, 1.0 / max_rate, (double)p->up);
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(double) * h.size()));
-    KWY_HIP(hipMemcpy(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  *taps = it->second;
-  return KWY_OK;
+  return kwy_cached_table<double>(ctx, key, [&] { return design_taps(p->numtaps, 1.0 / max_rate, (double)p->up); }, taps);
 }
 
 static int stretch_check(kwy_ctx *ctx, const void *rows, int64_t T, int K, int new_K, const void *out) {
@@ -180,12 +171,11 @@ extern "C" int kwy_stretch_log_dev(kwy_ctx *ctx, const double *rows, int64_t T, 
 extern "C" int kwy_stretch_log(kwy_ctx *ctx, const double *rows, int64_t T, int K, int new_K, double *out) {
   KWY_TRY(stretch_check(ctx, rows, T, K, new_K, out));
   KWY_HIP(hipSetDevice(ctx->device));
-  const size_t bi = kwy_pad(sizeof(double) * (size_t)T * K), bo = kwy_pad(sizeof(double) * (size_t)T * new_K);
-  KWY_TRY(kwy_arena_begin(ctx, bi + bo));
-  double *din = kwy_arena<double>(ctx, (size_t)T * K), *dout = kwy_arena<double>(ctx, (size_t)T * new_K);
-  KWY_HIP(hipMemcpyAsync(din, rows, sizeof(double) * (size_t)T * K, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "stretch_log");
+  double *din, *dout;
+  st.in(din, rows, (size_t)T * K);
+  st.out(dout, out, (size_t)T * new_K);
+  KWY_TRY(st.begin());
   KWY_TRY(kwy_stretch_log_dev(ctx, din, T, K, new_K, dout));
-  KWY_HIP(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)T * new_K, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }

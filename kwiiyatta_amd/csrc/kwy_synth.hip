@@ -1257,8 +1257,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_syn_ola(syn_batch batch, int N)
 // ------------------------------------------------------------------ host side
 static int get_dc_remover(kwy_ctx *ctx, int fft_size, const double **out) {
   std::string key = "dcrem:" + std::to_string(fft_size);
-  auto it = ctx->d_mats.find(key);
-  if (it == ctx->d_mats.end()) {
+  return kwy_cached_table<double>(ctx, key, [&] {
     std::vector<double> h(fft_size);
     double dc_component = 0.0;
     for (int i = 0; i < fft_size / 2; ++i) {
@@ -1270,13 +1269,8 @@ static int get_dc_remover(kwy_ctx *ctx, int fft_size, const double **out) {
       h[i] /= dc_component;
       h[fft_size - i - 1] = h[i];
     }
-    double *d = nullptr;
-    KWY_HIP(hipMalloc((void **)&d, sizeof(double) * fft_size));
-    KWY_HIP(hipMemcpy(d, h.data(), sizeof(double) * fft_size, hipMemcpyHostToDevice));
-    it = ctx->d_mats.emplace(key, d).first;
-  }
-  *out = it->second;
-  return KWY_OK;
+    return h;
+  }, out);
 }
 
 template <int LOG2N>
@@ -1608,16 +1602,13 @@ extern "C" int kwy_synthesize(kwy_ctx *ctx, const double *f0, int64_t T, const d
   for (int64_t i = 0; i < T; ++i)
     if (!(f0[i] >= 0.0 && f0[i] < fs / 12.0)) { ctx->err = "synthesize: f0 must lie in [0, fs/12)"; return KWY_EINVAL; }
   const int K = fft_size / 2 + 1;
-  size_t bf = kwy_pad(sizeof(double) * T), bs = kwy_pad(sizeof(double) * T * K);
-  size_t by = kwy_pad(sizeof(double) * y_length);
-  KWY_TRY(kwy_arena_begin(ctx, syn_scratch_bytes(y_length, fft_size, fs) + bf + 2 * bs + by));
-  double *df0 = kwy_arena<double>(ctx, T), *dsp = kwy_arena<double>(ctx, (size_t)T * K);
-  double *dap = kwy_arena<double>(ctx, (size_t)T * K), *dy = kwy_arena<double>(ctx, y_length);
-  KWY_HIP(hipMemcpyAsync(df0, f0, sizeof(double) * T, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dsp, sp, sizeof(double) * T * K, hipMemcpyHostToDevice, ctx->stream));
-  KWY_HIP(hipMemcpyAsync(dap, ap, sizeof(double) * T * K, hipMemcpyHostToDevice, ctx->stream));
+  kwy_staging st(ctx, "synthesize");
+  double *df0, *dsp, *dap, *dy;
+  st.in(df0, f0, (size_t)T);
+  st.in(dsp, sp, (size_t)T * K);
+  st.in(dap, ap, (size_t)T * K);
+  st.out(dy, y, (size_t)y_length);
+  KWY_TRY(st.begin(syn_scratch_bytes(y_length, fft_size, fs)));
   KWY_TRY(synth_core(ctx, df0, T, dsp, dap, fft_size, frame_period_ms, fs, sp_mul, y_length, dy));
-  KWY_HIP(hipMemcpyAsync(y, dy, sizeof(double) * y_length, hipMemcpyDeviceToHost, ctx->stream));
-  KWY_HIP(hipStreamSynchronize(ctx->stream));
-  return KWY_OK;
+  return st.finish();
 }
