@@ -13,8 +13,14 @@
 #include "kwy_internal.hpp"
 
 // Every workgroup finds the power threshold (max over all frames of c0, minus the offset) for itself -- T loads of
-// an L2-resident column -- and then writes the feature rows of its 8 frames: one launch instead of a reduction
-// kernel followed by a row kernel.
+// an L2-resident column, one cache line each -- and then writes the feature rows of its AL_FEAT_FRAMES frames: one
+// launch instead of a reduction kernel followed by a row kernel.  With 8 frames per workgroup the column reads were
+// the kernel (2.7 GB of cache lines per launch of a wave); measured per launch of 32 utterances of ~2 300 frames:
+// 8 frames 85 us, 32: 37, 64: 29, 128: 32, 256: 42, 1024: 111 -- fewer workgroups leave a CU's loads too few in flight.
+// fmax does not depend on the order: the threshold is the same whatever the split.
+#ifndef AL_FEAT_FRAMES
+#define AL_FEAT_FRAMES 64
+#endif
 __device__ __forceinline__ void align_features_body(const double *__restrict__ mc, int64_t T,
                                                     int ncoef, const double *__restrict__ f0,
                                                     double power_threshold, double power_weight,
@@ -22,6 +28,7 @@ __device__ __forceinline__ void align_features_body(const double *__restrict__ m
   __shared__ double red[KWY_WAVES];
   const int tid = threadIdx.x;
   double mx = -INFINITY;
+#pragma unroll 8
   for (int64_t t = tid; t < T; t += KWY_THREADS) mx = fmax(mx, mc[t * ncoef]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o));
@@ -30,15 +37,25 @@ __device__ __forceinline__ void align_features_body(const double *__restrict__ m
   double m = red[0];
   for (int i = 1; i < KWY_WAVES; ++i) m = fmax(m, red[i]);
   const double thr = m - power_threshold;
-  const int64_t t = (int64_t)blockIdx.x * 8 + (tid >> 5);  // 8 frames per workgroup, 32 lanes per frame
-  if (t >= T) return;
   const int w = ncoef + 1;
-  for (int c = tid & 31; c < w; c += 32) {
+  const int64_t t0 = (int64_t)blockIdx.x * AL_FEAT_FRAMES;
+  const int64_t t1 = t0 + AL_FEAT_FRAMES < T ? t0 + AL_FEAT_FRAMES : T;
+  // the rows of these frames are one contiguous piece of `out`: element by element, every lane busy, and the
+  // (frame, column) of a thread's next element by addition (256 = dq w + dr)
+  const int n = (int)(t1 - t0) * w;
+  const int dq = KWY_THREADS / w, dr = KWY_THREADS % w;
+  int tl = tid / w, c = tid % w;
+  double *__restrict__ dst = out + t0 * w;
+#pragma unroll 4
+  for (int e = tid; e < n; e += KWY_THREADS) {
+    const int64_t t = t0 + tl;
     double v;
     if (c == 0) v = mc[t * ncoef] >= thr ? power_weight : 0.0;
     else if (c == 1) v = f0[t] > 0 ? vuv_weight : 0.0;
     else v = mc[t * ncoef + (c - 1)];
-    out[t * w + c] = v;
+    dst[e] = v;
+    tl += dq; c += dr;
+    if (c >= w) { c -= w; ++tl; }
   }
 }
 
@@ -157,7 +174,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_align_features(al_jobs<kwy_alig
                                                                double power_threshold, double power_weight,
                                                                double vuv_weight) {
   const kwy_align_job &q = b.j[blockIdx.y];
-  if ((int64_t)blockIdx.x * 8 >= q.T) return;
+  if ((int64_t)blockIdx.x * AL_FEAT_FRAMES >= q.T) return;
   align_features_body(q.mc, q.T, ncoef, q.f0, power_threshold, power_weight, vuv_weight, q.out);
 }
 
@@ -203,7 +220,8 @@ extern "C" int kwy_align_features_batch_dev(kwy_ctx *ctx, const kwy_align_job *j
   al_for_batches(jobs, count, [&](const al_jobs<kwy_align_job> &b) {
     int64_t T = 0;
     for (int k = 0; k < b.n; ++k) T = b.j[k].T > T ? b.j[k].T : T;
-    hipLaunchKernelGGL(k_align_features, dim3((unsigned)((T + 7) / 8), b.n), dim3(KWY_THREADS), 0, ctx->stream, b, ncoef,
+    hipLaunchKernelGGL(k_align_features, dim3((unsigned)((T + AL_FEAT_FRAMES - 1) / AL_FEAT_FRAMES), b.n), dim3(KWY_THREADS), 0,
+                       ctx->stream, b, ncoef,
                        power_threshold, power_weight, vuv_weight);
   });
   KWY_HIP(hipGetLastError());

@@ -129,70 +129,141 @@ __device__ __forceinline__ void dtw_window_scan_first(int radius, int len_x, int
 }
 
 // dist(i, j) = || x_i - y_j ||_2 (sequential sum over the dimensions) for every cell of the strips' rectangles that
-// lies in its row's window, +inf for the others.  A workgroup = 16 steps x 64 lanes of one strip: 64 frames of x and
-// the 79 frames of y its cells pair them with, staged in LDS 32 dimensions at a time (the sum keeps its order).
+// lies in its row's window, +inf for the others.  A workgroup = a run of DTW_RUN consecutive steps x 64 lanes of one
+// strip.  Per tile of 32 dimensions: the strip's 64 frames of x pass through LDS into registers (a lane keeps its own
+// row for all of its steps), then the DTW_RUN + 63 frames of y the run pairs them with are staged in the same LDS --
+// one LDS read per cell and dimension.  A thread takes pairs of steps (even, odd): its two values are 16 adjacent
+// bytes of the band, one store.  With more than one tile the running sum waits in the band itself between tiles
+// (the thread that wrote it reads it back), so the sum keeps its order and the common case carries nothing.
+//
+// Runs and workgroups: strip k owns the units from U(k) = soff[k] / (64 DTW_RUN) + k on.  U(k + 1) - U(k) is at
+// least the strip's number of runs (floor(a + b) - floor(a) >= floor(b), plus one for the partial run), so the units
+// of different strips never overlap, a unit finds its strip by a search over soff alone, and the host's bound on
+// the cells bounds the units: cap / (64 DTW_RUN) + strips + 1.  A unit past its strip's last run has nothing to do.
 #define DTW_DT 32                       // dimensions per tile
-#define DTW_DTP (DTW_DT + 1)            // padded row (lane l reads row l, row s - l: 33 doubles apart, no bank conflict)
-#define DTW_DIST_LDS (sizeof(double) * (64 + 80) * DTW_DTP)
-// (unit_first, unit_stride: the units of 1024 cells this workgroup takes; lds: DTW_DIST_LDS bytes)
+#define DTW_DTP (DTW_DT + 1)            // padded row (lane l reads row s + 63 - l: 33 doubles apart, no bank conflict)
+#ifndef DTW_RUN
+#define DTW_RUN 64                      // steps per workgroup (a multiple of 16; 8 * KWY_WAVES pairs of steps)
+#endif
+#define DTW_YROWS (DTW_RUN + 63)
+#define DTW_DIST_ROWS (DTW_YROWS + 1)   // (>= 64: the x rows use the same tile first)
+#define DTW_DIST_LDS (sizeof(double) * DTW_DIST_ROWS * DTW_DTP)
+typedef double dtw_d2 __attribute__((ext_vector_type(2), aligned(16)));
+__host__ __device__ static inline uint64_t dtw_dist_units(uint64_t cells, uint64_t strips) {
+  return cells / (64ull * DTW_RUN) + strips + 1;
+}
+// The cells (lane, s) and (lane, s + 1) over CW dimensions of a tile: xr the lane's row of x, yr the row of y that
+// step s pairs it with (step s + 1: the row after it).  A width that is no multiple of 4 is padded with zeros in both
+// tiles: (0 - 0)^2 added to a sum of squares leaves its bits alone.
+template <int CW>
+__device__ __forceinline__ void dtw_dist_pair(const double (&xr)[DTW_DT], const double *yr, double &a0, double &a1) {
+#pragma unroll
+  for (int c = 0; c < CW; ++c) {
+    // (eight dimensions' reads in flight at a time: with all 32 hoisted the rows of x no longer fit beside them)
+    if (c % 8 == 0) __builtin_amdgcn_sched_barrier(0);
+    const double d0 = xr[c] - yr[c], d1 = xr[c] - yr[DTW_DTP + c];
+    a0 += d0 * d0;
+    a1 += d1 * d1;
+  }
+}
+// (unit_first, unit_stride: the units this workgroup takes; lds: DTW_DIST_LDS bytes)
 __device__ __forceinline__ void dtw_dist_body(const double *x, const double *y, int dim, int len_x, int len_y,
                                               const int32_t *lo, const int32_t *hi, const uint64_t *soff,
                                               double *dist, const int *status, unsigned unit_first,
                                               unsigned unit_stride, unsigned char *lds) {
-  double *xs = (double *)lds, *ys = xs + 64 * DTW_DTP;
-  if (status[0] != 0) return;
+  static_assert(DTW_RUN % 16 == 0 && DTW_RUN / 2 % KWY_WAVES == 0 && DTW_DIST_ROWS >= 64, "the run's thread map");
+  static_assert(KWY_THREADS % DTW_DT == 0 && DTW_DIST_ROWS % (8 * (KWY_THREADS / DTW_DT)) == 0, "the staging map");
+  double *tile = (double *)lds;
+  // Loads that do not depend on each other are issued together, in front of the branch that needs the first of
+  // them: a workgroup has a few microseconds of arithmetic, and under load every round trip to memory costs as much.
   const int nstrips = (len_x + 63) / 64;
-  const uint64_t total = soff[nstrips];
+  const int overflow = status[0];
+  const uint64_t nunits = soff[nstrips] / (64ull * DTW_RUN) + (uint64_t)nstrips;
+  if (overflow != 0) return;
   const int lane = threadIdx.x & 63, sub = threadIdx.x >> 6;
-  constexpr int PER = 16 / (KWY_THREADS / 64);          // steps per wavefront
-  for (uint64_t cell0 = (uint64_t)unit_first * 1024ull; cell0 < total; cell0 += (uint64_t)unit_stride * 1024ull) {
-    int a = 0, b = nstrips - 1;                   // the strip of this unit: the last one that starts at or before it
-    while (a < b) { const int mid = (a + b + 1) >> 1; if (soff[mid] <= cell0) a = mid; else b = mid - 1; }
-    const int k = a;
-    const uint64_t sb = soff[k];
-    const int s0 = (int)((cell0 - sb) >> 6);
+  const int scol = threadIdx.x & (DTW_DT - 1), srow = threadIdx.x / DTW_DT;     // staging: 8 rows of 32 columns a pass
+  constexpr int SROWS = KWY_THREADS / DTW_DT;
+  constexpr int XP = 64 / SROWS, YP = DTW_DIST_ROWS / SROWS;
+  for (uint64_t u = unit_first; u < nunits; u += unit_stride) {
+    // the strip of this unit: the last one whose units start at or before it.  Up to 256 strips (16 384 frames) every
+    // thread looks at one and the workgroup counts: one round of loads instead of a search's dependent chain
+    int a = 0, b = nstrips - 1;
+    while (b - a >= KWY_THREADS) {
+      const int mid = (a + b + 1) >> 1;
+      if (soff[mid] / (64ull * DTW_RUN) + (uint64_t)mid <= u) a = mid; else b = mid - 1;
+    }
+    const int cand = a + (int)threadIdx.x;
+    const int k = a - 1 + __syncthreads_count(cand <= b && soff[cand] / (64ull * DTW_RUN) + (uint64_t)cand <= u);
+    // everything that follows from k alone: the strip's place and steps, its rows' windows
+    const uint64_t sb = soff[k], sb_next = soff[k + 1];
     const int i = 64 * k + lane;
     const bool valid = i < len_x;
     const int jmin = lo[64 * k], l = valid ? lo[i] : 0, h = valid ? hi[i] : -1;
-    const int jbase = jmin + s0 - 63;             // y frame of ys row 0; the cell (lane, step s) uses row s - s0 + 63 - lane
-    bool in[PER];
-    double acc[PER];
-    bool any = false;
+    const int steps16 = (int)((sb_next - sb) >> 6);
+    const int s0 = (int)(u - (sb / (64ull * DTW_RUN) + (uint64_t)k)) * DTW_RUN;
+    if (s0 >= steps16) continue;                  // (the whole workgroup: no barrier is skipped by a part of it)
+    const int nst = min(DTW_RUN, steps16 - s0);   // a multiple of 16
+    const int jbase = jmin + s0 - 63;             // y frame of tile row 0; the cell (lane, step s) uses row s - s0 + 63 - lane
+    dtw_d2 *band = (dtw_d2 *)(dist + sb) + lane;  // band[(s >> 1) * 64]: the steps s, s + 1 (s even) of this lane
+    for (int c0 = 0; c0 < dim; c0 += DTW_DT) {
+      const int cw = min(DTW_DT, dim - c0), cwp = (cw + 3) & ~3;     // columns cw .. cwp - 1 of both tiles: zeros
+      const bool first = c0 == 0, last = c0 + DTW_DT >= dim;
+      // staging: a thread's 8 values of x are in flight together; the rows of y (16 values a thread) follow in two
+      // rounds of 8 while the lanes hold their rows of x -- all at once take more registers than three workgroups
+      // per CU leave
+      double xv[XP];
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int j = jmin + s0 + PER * sub + q - lane;
-      in[q] = j >= l && j <= h;
-      any = any || in[q];
-      acc[q] = 0.0;
-    }
-    if (__syncthreads_or(any)) {
-      for (int c0 = 0; c0 < dim; c0 += DTW_DT) {
-        const int cw = min(DTW_DT, dim - c0);
-        __syncthreads();
-        for (int e = threadIdx.x; e < 64 * cw; e += KWY_THREADS) {
-          const int r = e / cw, c = e - r * cw, ii = 64 * k + r;
-          xs[r * DTW_DTP + c] = ii < len_x ? x[(int64_t)ii * dim + c0 + c] : 0.0;
-        }
-        for (int e = threadIdx.x; e < 79 * cw; e += KWY_THREADS) {
-          const int r = e / cw, c = e - r * cw, jj = jbase + r;
-          ys[r * DTW_DTP + c] = (jj >= 0 && jj < len_y) ? y[(int64_t)jj * dim + c0 + c] : 0.0;
-        }
-        __syncthreads();
+      for (int q = 0; q < XP; ++q) {
+        const int ii = 64 * k + srow + SROWS * q;
+        xv[q] = (scol < cw && ii < len_x) ? x[(int64_t)ii * dim + c0 + scol] : 0.0;
+      }
+      __syncthreads();                            // (the tile is still read by the unit or dimension tile before)
+      if (scol < cwp) {
 #pragma unroll
-        for (int q = 0; q < PER; ++q) {
-          if (in[q]) {
-            const double *xr = xs + lane * DTW_DTP, *yr = ys + (PER * sub + q + 63 - lane) * DTW_DTP;
-            double t = acc[q];
-            for (int c = 0; c < cw; ++c) { const double df = xr[c] - yr[c]; t += df * df; }
-            acc[q] = t;
+        for (int q = 0; q < XP; ++q) tile[(srow + SROWS * q) * DTW_DTP + scol] = xv[q];
+      }
+      __syncthreads();
+      double xr[DTW_DT];
+#pragma unroll
+      for (int c = 0; c < DTW_DT; ++c) xr[c] = tile[lane * DTW_DTP + c];       // (columns from cwp on: never used)
+      __syncthreads();
+      if (scol < cwp) {
+#pragma unroll
+        for (int q0 = 0; q0 < YP; q0 += 8) {
+          double yv[8];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const int r = srow + SROWS * (q0 + q), jj = jbase + r;
+            yv[q] = (scol < cw && r < nst + 63 && jj >= 0 && jj < len_y) ? y[(int64_t)jj * dim + c0 + scol] : 0.0;
           }
+#pragma unroll
+          for (int q = 0; q < 8; ++q) tile[(srow + SROWS * (q0 + q)) * DTW_DTP + scol] = yv[q];
         }
       }
+      __syncthreads();
+      for (int p = sub; 2 * p < nst; p += KWY_WAVES) {
+        const int j0 = jmin + s0 + 2 * p - lane;
+        const bool in0 = j0 >= l && j0 <= h, in1 = j0 + 1 >= l && j0 + 1 <= h;
+        dtw_d2 *cell = band + (size_t)((s0 >> 1) + p) * 64;
+        double a0 = 0.0, a1 = 0.0;
+        if (in0 || in1) {
+          if (!first) { const dtw_d2 v = *cell; a0 = v.x; a1 = v.y; }
+          const double *yr = tile + (2 * p + 63 - lane) * DTW_DTP;
+          switch (cwp) {                          // (straight-line code for the tile's width: the reads pipeline)
+            case 4: dtw_dist_pair<4>(xr, yr, a0, a1); break;
+            case 8: dtw_dist_pair<8>(xr, yr, a0, a1); break;
+            case 12: dtw_dist_pair<12>(xr, yr, a0, a1); break;
+            case 16: dtw_dist_pair<16>(xr, yr, a0, a1); break;
+            case 20: dtw_dist_pair<20>(xr, yr, a0, a1); break;
+            case 24: dtw_dist_pair<24>(xr, yr, a0, a1); break;
+            case 28: dtw_dist_pair<28>(xr, yr, a0, a1); break;
+            default: dtw_dist_pair<32>(xr, yr, a0, a1); break;
+          }
+        }
+        if (last) { a0 = in0 ? sqrt(a0) : INFINITY; a1 = in1 ? sqrt(a1) : INFINITY; }
+        *cell = dtw_d2{a0, a1};
+      }
     }
-#pragma unroll
-    for (int q = 0; q < PER; ++q)
-      dist[dtw_skew_index(sb, s0 + PER * sub + q, lane)] = in[q] ? sqrt(acc[q]) : INFINITY;
-    __syncthreads();        // (the tiles are rewritten by the next unit)
   }
 }
 // (the kernels themselves follow the batch descriptor's helpers: see k_dtw_* below)
@@ -339,7 +410,6 @@ __device__ __forceinline__ bool dtw_make_args(const dtw_batch &b, int pi, int le
 #ifndef DTW_BLK
 #define DTW_BLK 16           // steps between two rounds of bookkeeping (stores of D, boundary row, progress word)
 #endif
-typedef double dtw_d2 __attribute__((ext_vector_type(2), aligned(16)));
 
 template <bool BND_LDS>
 __device__ __forceinline__ void dtw_values_body(const dtw_level_args &a, unsigned char *bt /* boundary rows (BND_LDS) */) {
@@ -995,8 +1065,10 @@ __global__ __launch_bounds__(DTW_WS_NT) void k_dtw_window_scan(dtw_batch b, int 
   dtw_window_scan_first(b.radius, a.len_x, a.len_y, a.lo_w, a.hi_w, a.off_w, a.soff_w, a.cap_rows, a.cap_skew, a.status,
                         tot, sizeof(tot));
 }
-__global__ __launch_bounds__(KWY_THREADS) void k_dtw_dist(dtw_batch b, int lev) {
-  __shared__ double tiles[(64 + 80) * DTW_DTP];
+// (three workgroups per CU: 168 registers, 64 of them a lane's row of x.  Holding them to 128 for a fourth -- the
+// tile's LDS would allow it -- spills a few loop-invariant addresses to scratch.)
+__global__ __launch_bounds__(KWY_THREADS, 3) void k_dtw_dist(dtw_batch b, int lev) {
+  __shared__ double tiles[DTW_DIST_ROWS * DTW_DTP];
   dtw_level_args a;
   if (!dtw_make_args(b, blockIdx.y, lev, true, a)) return;
   dtw_dist_body(a.x, a.y, a.dim, a.len_x, a.len_y, a.lo, a.hi, a.soff, a.dist, a.status, blockIdx.x, gridDim.x,
@@ -1170,9 +1242,10 @@ static int fastdtw_core(kwy_ctx *ctx, const dtw_pair *pairs, int n, int dim, int
     if (first)
       hipLaunchKernelGGL(k_dtw_window_scan, dim3(n), dim3(DTW_WS_NT), 0, ctx->stream, b, l);
     const int nstrips = (len_x + 63) / 64;
-    // a workgroup per 16 steps of a strip; how many there are is known on the device only: as many workgroups as
-    // this level's rectangles can have (the others return at once; more units: the workgroups loop)
-    const uint64_t lv_units = std::min(b.cap_skew, dtw_cap_skew(len_x, len_y, radius, full)) / 1024 + 1;
+    // a workgroup per run of DTW_RUN steps of a strip; how many there are is known on the device only: as many
+    // workgroups as this level's rectangles can have (the others return at once; more units: the workgroups loop)
+    const uint64_t lv_units = std::min<uint64_t>(
+        dtw_dist_units(std::min(b.cap_skew, dtw_cap_skew(len_x, len_y, radius, full)), (uint64_t)nstrips), 0x7fffffffull);
     b.lds_bytes = 0;
     if (!small_dist)
       KWY_PROF(ctx, "k_dtw_dist", hipLaunchKernelGGL(k_dtw_dist, dim3((unsigned)lv_units, n), dim3(KWY_THREADS), 0, ctx->stream, b, l));

@@ -1211,6 +1211,9 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
 
 // y[n] (+)= the responses of this round's pulses that reach sample n, in pulse order.  The pulses of the
 // SYN_TILE-sample tiles within `reach` tiles of the output tile are candidates (tile_off: first pulse of a tile).
+#ifndef SYN_OLA_GROUP
+#define SYN_OLA_GROUP 4
+#endif
 __global__ __launch_bounds__(KWY_THREADS) void k_syn_ola(syn_batch batch, int N) {
   const int utt = batch.find(blockIdx.x);
   const double *__restrict__ resp = batch.u[utt].resp;
@@ -1236,15 +1239,40 @@ __global__ __launch_bounds__(KWY_THREADS) void k_syn_ola(syn_batch batch, int N)
     const int64_t n = n0 + KWY_THREADS * m;
     v[m] = (first_pulse > 0 && n < y_length) ? y[n] : 0.0;
   }
-  for (int pp = p0; pp < p1; ++pp) {
-    const int idx = pidx[pp];
-    if (pidx[min(P - 1, pp + 1)] - idx <= 0) continue;      // the last pulse has no response
-    const double *slot = resp + (size_t)(pp - first_pulse) * N;
-    const int64_t base = (int64_t)idx - H + 1;
+  // The candidates' positions come in coalesced, KWY_THREADS at a time (and the one after them: a pulse's response
+  // ends where the next pulse starts), and the pulses are walked in groups of SYN_OLA_GROUP: all of a group's slot
+  // loads are issued before the first of them is added, so a tile waits for memory once per group and not once per
+  // pulse.  The additions keep the pulse order.
+  __shared__ int32_t s_idx[KWY_THREADS + 1];
+  for (int c0 = p0; c0 < p1; c0 += KWY_THREADS) {
+    const int cn = min(KWY_THREADS, p1 - c0);
+    __syncthreads();
+    if ((int)threadIdx.x < cn) s_idx[threadIdx.x] = pidx[min(P - 1, c0 + (int)threadIdx.x)];
+    if (threadIdx.x == 0) s_idx[cn] = pidx[min(P - 1, c0 + cn)];
+    __syncthreads();
+    for (int g0 = 0; g0 < cn; g0 += SYN_OLA_GROUP) {
+      double r[SYN_OLA_GROUP][SYN_TILE_PER_THREAD];
+      bool on[SYN_OLA_GROUP][SYN_TILE_PER_THREAD];
 #pragma unroll
-    for (int m = 0; m < SYN_TILE_PER_THREAD; ++m) {
-      const int64_t q = n0 + KWY_THREADS * m - base;
-      if (q >= 0 && q < N) v[m] += slot[q];
+      for (int g = 0; g < SYN_OLA_GROUP; ++g) {
+        const int e = min(g0 + g, cn - 1);
+        const int idx = s_idx[e];
+        const bool live = g0 + g < cn && s_idx[e + 1] - idx > 0;     // the last pulse has no response
+        const double *slot = resp + (size_t)(c0 + e - first_pulse) * N;
+        const int64_t base = (int64_t)idx - H + 1;
+#pragma unroll
+        for (int m = 0; m < SYN_TILE_PER_THREAD; ++m) {
+          const int64_t q = n0 + KWY_THREADS * m - base;
+          on[g][m] = live && q >= 0 && q < N;
+          r[g][m] = on[g][m] ? slot[q] : 0.0;
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < SYN_OLA_GROUP; ++g) {
+#pragma unroll
+        for (int m = 0; m < SYN_TILE_PER_THREAD; ++m)
+          if (on[g][m]) v[m] += r[g][m];
+      }
     }
   }
 #pragma unroll
