@@ -856,6 +856,64 @@ int kwy_mcep_filter_fft_dev(kwy_ctx *ctx, const double *x, int64_t n, const doub
 int kwy_mcep_filter_fft_batch_dev(kwy_ctx *ctx, const kwy_mlsa_job *jobs, int count, int order, double alpha,
                                   int hopsize, int fft_size, int ignore_c0);
 
+/* ---- mel-cepstral energy: power-preserving c0 and the formant-emphasis postfilter --------------
+ * The reference has no counterpart (kwiiyatta/convert_voice.py:35-46 synthesises the converter's output as it is).
+ * c0 of a mel-cepstrum is not its power: the energy of a frame is the mean of |H|^2 with log |H| = sum c_m cos(m w~),
+ * so changing c1.. at a fixed c0 moves it.  For a row c of order + 1 coefficients, alpha and N = fft_size:
+ *   w_k = 2 pi k / N,   w~_k = w_k + 2 atan2(alpha sin w_k, 1 - alpha cos w_k)             (as kwy_mcep_filter_fft)
+ *   L_k = sum_{m = 0 .. order} c[m] cos(m w~_k),   m ascending
+ *   E(c) = ( exp(2 L_0) + exp(2 L_{N/2}) + 2 sum_{k = 1 .. N/2 - 1} exp(2 L_k) ) / N
+ * E(c) is the energy of the filter's N-periodic impulse response.  SPTK's mc2e truncates that response at irleng
+ * samples; this takes all of it, so no parity with SPTK is claimed.  No spectrum is stored: the kernel reads a table
+ * of cos(m w~_k), (order + 1) x (N/2 + 1) doubles per (N, alpha, order), kept with the context.
+ * The filter of a row x with strength beta in [0, 1] (the mel-cepstral formant emphasis of the HTS vocoder and SPTK's
+ * mcpf, renormalised by E instead of a truncated response) and a reference row r (absent: r = x):
+ *   b[order] = x[order];  b[m] = x[m] - alpha b[m+1],  m = order-1 .. 0                      (kwy_mc2b)
+ *   if order >= 2:  b[1] = b[1] - (beta alpha) b[2];   b[m] = b[m] (1 + beta),  m = 2 .. order
+ *   y[order] = b[order];  y[m] = b[m] + alpha b[m+1],  m = order-1 .. 0
+ *   y[0] = y[0] + log(E(r) / E(y)) / 2                                (E(y) of y before this line)
+ * evaluated operation by operation as written.  beta == 0: y = x before the last line and no b is formed, so with a
+ * reference the row keeps x[1..] and gets the c0 at which its energy is the reference's (the power-preserving shift);
+ * beta == 0 without a reference copies the row and forms no energy.  out = y, or with a base matrix
+ * out = base + (y - x) element by element (the differential form, as the GV and MS filters have it).  A row where E(r)
+ * or E(y) is not finite or not > 0, or whose correction is not finite, takes y = x: it is copied bit for bit from base
+ * (from x without one) and counted in the matrix's status word; so is every row at beta == 0 without a reference,
+ * uncounted.  The reductions over k have a fixed order: a row's result depends on the row, alpha, N, beta and its
+ * reference alone -- not on the run, nor on the batch, nor on the launch it ran in.  No atomics, nothing accumulated in
+ * memory.
+ * KWY_EINVAL, nothing written: order outside [1, 63], fft_size not a power of two within [512, 8192], |alpha| >= 1,
+ * beta outside [0, 1], a null jobs / x / out pointer (with rows > 0), negative rows or count.  count == 0 is KWY_OK.
+ * out may equal x or base (a workgroup reads its rows before it writes them).  _dev: device pointers, not
+ * synchronised, nothing allocated: legal inside a stream capture once the context holds the table of (fft_size,
+ * alpha, order) and, for a non-NULL status, its count slots (256 KB) -- the first call makes them.  A workgroup writes
+ * the number of rows it copied into a slot of its own and a second kernel adds a matrix's slots up.  _batch_dev: every job equals the single call bit for bit; more jobs than
+ * one launch holds are split.  The host forms stage through HBM and synchronise. */
+typedef struct kwy_energy_job {
+  const double *mc;       /* rows x (order + 1) mel-cepstra */
+  int64_t rows;
+  double *energy;         /* rows doubles, written */
+} kwy_energy_job;
+int kwy_mcep_energy(kwy_ctx *ctx, const double *mc, int64_t T, int order, double alpha, int fft_size, double *energy);
+int kwy_mcep_energy_dev(kwy_ctx *ctx, const double *mc, int64_t T, int order, double alpha, int fft_size,
+                        double *energy);
+int kwy_mcep_energy_batch_dev(kwy_ctx *ctx, const kwy_energy_job *jobs, int count, int order, double alpha,
+                              int fft_size);
+typedef struct kwy_mcpower_job {
+  const double *x;        /* rows x (order + 1): the rows that are filtered */
+  const double *ref;      /* rows x (order + 1): the rows whose energy the output takes, or NULL (x itself) */
+  const double *base;     /* rows x (order + 1), or NULL: out = base + (y - x) */
+  double *out;            /* rows x (order + 1), written (may equal x or base) */
+  int64_t rows;
+} kwy_mcpower_job;
+/* status: one int32 per matrix (or NULL), set to the number of rows that were copied because an energy or the
+ * correction is unusable */
+int kwy_mcep_postfilter(kwy_ctx *ctx, const kwy_mcpower_job *jobs, int count, int order, double alpha, int fft_size,
+                        double beta, int32_t *status);
+int kwy_mcep_postfilter_dev(kwy_ctx *ctx, const double *x, int64_t rows, int order, double alpha, int fft_size,
+                            double beta, const double *ref, const double *base, double *out, int32_t *status);
+int kwy_mcep_postfilter_batch_dev(kwy_ctx *ctx, const kwy_mcpower_job *jobs, int count, int order, double alpha,
+                                  int fft_size, double beta, int32_t *status);
+
 
 /* ---- converter fit: EM building blocks --------------------------------------------------------
  * sklearn.mixture.GaussianMixture(covariance_type='full').fit as used at

@@ -37,6 +37,29 @@ def shift_formants(feature_set, ratio):
     return warped
 
 
+def mcep_energy(mcep):
+    """the energy of every frame of a MelCepstrum record: the mean of |H|^2 over the vocoder's transform length at its
+    sampling rate, without the spectrum (backend.power, kwy_mcpower.hip); one double per frame"""
+    import numpy as np
+    from .backend import power
+    return power.frame_energy(np.ascontiguousarray(mcep.data, dtype=np.float64), mcep.alpha(),
+                              power.energy_fft_size(mcep.fs))
+
+
+def postfilter_mcep(mcep, beta=0.0, power_of=None):
+    """a new MelCepstrum: `mcep` through the mel-cepstral formant emphasis of strength beta (within [0, 1]), every
+    frame's c0 shifted until the frame has the energy of the same frame of `power_of` (a MelCepstrum of the same shape
+    and rate; default: of `mcep` itself, which the emphasis alone would make louder)"""
+    import numpy as np
+    from .backend import power
+    if power_of is not None and (power_of.fs != mcep.fs or np.shape(power_of.data) != np.shape(mcep.data)):
+        raise ValueError('postfilter_mcep: power_of must have the sampling rate and the shape of mcep')
+    ref = None if power_of is None else np.ascontiguousarray(power_of.data, dtype=np.float64)
+    data = power.postfilter(np.ascontiguousarray(mcep.data, dtype=np.float64), beta, ref=ref, alpha=mcep.alpha(),
+                            fft_size=power.energy_fft_size(mcep.fs))
+    return MelCepstrum(mcep.fs, mcep.frame_period, data)
+
+
 name = "kwiiyatta_amd"
 
 __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFileDataset',
@@ -48,4 +71,6 @@ __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFil
            # ... and the waveform pitch shifter in front of a differential conversion across genders (backend/pitch.py)
            'shift_pitch',
            # ... and the formant shift beside it: the envelope of a feature set warped along frequency (backend/formant.py)
-           'shift_formants']
+           'shift_formants',
+           # ... and the energy of a mel-cepstrum with the postfilter that renormalises by it (backend/power.py)
+           'mcep_energy', 'postfilter_mcep']

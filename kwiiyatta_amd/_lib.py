@@ -203,6 +203,12 @@ SIGNATURES = {
     'kwy_mcep_filter_fft': (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_int, c_int, c_int, c_vp]),
     'kwy_mcep_filter_fft_dev': (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_int, c_int, c_int, c_vp]),
     'kwy_mcep_filter_fft_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_int, c_int, c_int]),
+    'kwy_mcep_energy': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_int, c_vp]),
+    'kwy_mcep_energy_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_int, c_vp]),
+    'kwy_mcep_energy_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_int]),
+    'kwy_mcep_postfilter': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_int, c_dbl, c_vp]),
+    'kwy_mcep_postfilter_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp]),
+    'kwy_mcep_postfilter_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_int, c_dbl, c_vp]),
     'kwy_gmm_prepare_dev': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp]),
     'kwy_gmm_mlpg_model_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
     'kwy_convert_mcep_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp]),
@@ -309,6 +315,10 @@ GvJob = _job_struct('GvJob', 'kwy_gv_job: one matrix through the global-variance
                     [('x', c_vp), ('rows', c_i64), ('moments', c_vp), ('base', c_vp), ('out', c_vp)])
 MsJob = _job_struct('MsJob', 'kwy_ms_job: one matrix through the modulation-spectrum postfilter',
                     [('x', c_vp), ('rows', c_i64), ('base', c_vp), ('out', c_vp)])
+EnergyJob = _job_struct('EnergyJob', 'kwy_energy_job: the frame energies of one mel-cepstrum matrix',
+                        [('mc', c_vp), ('rows', c_i64), ('energy', c_vp)])
+McPowerJob = _job_struct('McPowerJob', 'kwy_mcpower_job: one matrix through the formant-emphasis / power filter',
+                         [('x', c_vp), ('ref', c_vp), ('base', c_vp), ('out', c_vp), ('rows', c_i64)])
 PitchJob = _job_struct('PitchJob', 'kwy_pitch_job: one waveform through the pitch shifter',
                        [('x', c_vp), ('n', c_i64), ('y', c_vp), ('pos', c_vp)])
 FormantJob = _job_struct('FormantJob', 'kwy_formant_job: one envelope matrix through the formant shift',

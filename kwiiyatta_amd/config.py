@@ -209,6 +209,17 @@ DIFF_FILTER_OPTION = ('--diff-filter', dict(choices=('mlsa', 'fft'), default='ml
                                                  'frames in parallel, neighbouring frames crossfaded'))
 
 
+POWER_OPTIONS = (
+    ('--postfilter', dict(type=gv_strength, default=0.0, metavar='BETA',
+                          help='Mel-cepstral formant-emphasis postfilter on the converted mel-cepstrum, frame by frame '
+                               '(the beta of the HTS vocoder and of SPTK mcpf), the frame energy kept; BETA within '
+                               '[0, 1], 0 (the default) is off; runs after --ms, --gv and --mlpg-gv')),
+    ('--keep-power', dict(action='store_true',
+                          help='Shift c0 of every converted frame until the frame has the energy of the source frame: '
+                               'c0 is not the power, converting c1.. at a fixed c0 moves it by several dB')),
+)
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -251,6 +262,9 @@ class Config:
 
     def add_diff_filter_argument(self):
         self._declare((DIFF_FILTER_OPTION,))
+
+    def add_power_arguments(self):
+        self._declare(POWER_OPTIONS)
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)

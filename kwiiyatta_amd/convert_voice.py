@@ -43,7 +43,16 @@ kwy_mcep_filter_fft_batch_dev over all frames of a wave's files): the mel-cepstr
 applied to every frame through its frequency response, the outputs of neighbouring frames' filters crossfaded where the
 MLSA filter interpolates their coefficients.  Its time shrinks with the GPU where the MLSA recursion's does not (about
 0.5 us per sample of the longest file, whatever runs beside it).  The default, `mlsa`, is the reference's filter,
-unchanged; the .synth.wav outputs do not depend on the option."""
+unchanged; the .synth.wav outputs do not depend on the option.
+`--keep-power` repairs the loudness of both outputs: the conversion keeps the source's c0, but c0 is not the power --
+a frame's energy is the mean of |H|^2, and the converted c1.. move it by several dB -- so c0 of every converted frame
+is shifted until the frame has the energy of the source frame (`convert(..., keep_power=True)`, backend.power,
+kwy_mcpower.hip; with `--batch` kwy_mcep_postfilter_batch_dev inside the wave).  `--postfilter BETA` (within [0, 1])
+sharpens the over-smoothed envelope frame by frame with the mel-cepstral formant emphasis of the HTS vocoder and SPTK's
+mcpf and keeps the frame's energy -- the source's with `--keep-power`, its own otherwise.  Both run after `--ms`, `--gv`
+and `--mlpg-gv`.  For the .diff.wav output the corrected c0 travels as its difference from the source's c0 in column 0
+of the differential mel-cepstrum, and the differential filter takes that column into account
+(`apply_diff_filter(..., use_c0=True)`).  Neither option writes anything to the converter model."""
 import pathlib
 
 import numpy as np
@@ -52,7 +61,7 @@ OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 
 def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-            formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa'):
+            formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa', postfilter=0.0, keep_power=False):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
@@ -65,16 +74,23 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
     mlpg_gv=N: parameter generation considering the global variance, N steps (converter.convert(mlpg_gv=N), either
     output).
     diff_filter: the filter of the differential output, 'mlsa' (apply_mlsa_filter) or 'fft'
-    (apply_diff_filter(method='fft')); the synthesised output ignores it."""
+    (apply_diff_filter(method='fft')); the synthesised output ignores it.
+    postfilter > 0 / keep_power: the formant emphasis of that beta and / or the source's frame energies on the converted
+    mel-cepstrum (converter.convert(postfilter=..., keep_power=...), either output); the differential filter then runs
+    with use_c0=True, on the change of c0 the conversion hands over in column 0."""
     import kwiiyatta_amd as k
+    if not 0.0 <= postfilter <= 1.0:          # (raises before the file is read)
+        raise ValueError(f'postfilter: beta {postfilter!r} is outside [0, 1]')
+    power = dict(postfilter=postfilter, keep_power=keep_power) if postfilter > 0 or keep_power else {}
     source = analyze_source(conf, converter, src_path)
     converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
                                   **(dict(ms=ms) if ms > 0 else {}), **({} if mlpg_em is None else dict(em=mlpg_em)),
-                                  **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)))
+                                  **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)), **power)
     if diffvc:
+        use_c0 = dict(use_c0=True) if power else {}
         if diff_filter == 'mlsa':
-            return k.apply_mlsa_filter(source, converted)
-        return k.apply_diff_filter(source, converted, method=diff_filter)
+            return k.apply_mlsa_filter(source, converted, **use_c0)
+        return k.apply_diff_filter(source, converted, method=diff_filter, **use_c0)
     rendered = k.feature(source)
     rendered.mel_cepstrum = converted                   # takes over from the analysed envelope
     if convert_f0 or transpose_key != 0:
@@ -126,7 +142,8 @@ class _Pcm16:
 
 
 def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-                        formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa'):
+                        formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa', postfilter=0.0,
+                        keep_power=False):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -144,9 +161,13 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     mlpg_gv=N: both outputs from GV-considering parameter generation (as `convert` does;
     corpus.convert_batch(mlpg_gv=N)).
     diff_filter='fft': the .diff.wav outputs through the frame-parallel FFT filter instead of the MLSA filter
-    (corpus.convert_batch(diff_filter='fft'): all frames of a wave's files in one launch)."""
+    (corpus.convert_batch(diff_filter='fft'): all frames of a wave's files in one launch).
+    postfilter > 0 / keep_power: both outputs from the emphasised / power-corrected mel-cepstra (as `convert` does;
+    corpus.convert_batch(postfilter_beta=..., keep_power=...))."""
     import kwiiyatta_amd as k
     from . import corpus
+    postfilter = corpus._postfilter_beta(postfilter)          # (raises before any file is read)
+    power = dict(postfilter=postfilter, keep_power=keep_power) if postfilter > 0 or keep_power else {}
     if mlpg_gv is not None:
         converter.gv_ascent_statistics()          # (raises before any file is read)
     from ._lib import lib
@@ -163,7 +184,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                 (period is not None and a.frame_period != period):
             out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
                                        transpose_key=transpose_key, gv=gv, ms=ms, formant_shift=formant_shift,
-                                       mlpg_em=mlpg_em, mlpg_gv=mlpg_gv)
+                                       mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, **power)
         else:
             batch.append((path, a))
     if batch:
@@ -182,7 +203,8 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
                                    **({} if mlpg_em is None else dict(mlpg_em=mlpg_em)),
                                    **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv, gv_stats=converter.gv_stats,
                                                                       gv_var=converter.gv_var)),
-                                   **({} if diff_filter == 'mlsa' else dict(diff_filter=diff_filter)))
+                                   **({} if diff_filter == 'mlsa' else dict(diff_filter=diff_filter)),
+                                   **(dict(postfilter_beta=postfilter, keep_power=keep_power) if power else {}))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -215,6 +237,7 @@ def main():
     conf.add_mlpg_em_argument()
     conf.add_mlpg_gv_argument()
     conf.add_diff_filter_argument()
+    conf.add_power_arguments()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
@@ -222,7 +245,8 @@ def main():
     pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, formant_shift=conf.formant_shift)
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
                                   diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                                  mlpg_gv=conf.mlpg_gv, diff_filter=conf.diff_filter, **pitch) if conf.batch else {}
+                                  mlpg_gv=conf.mlpg_gv, diff_filter=conf.diff_filter, postfilter=conf.postfilter,
+                                  keep_power=conf.keep_power, **pitch) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -236,7 +260,7 @@ def main():
                 batched[wav_path, differential].save(out)
             else:
                 convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                        mlpg_gv=conf.mlpg_gv,
+                        mlpg_gv=conf.mlpg_gv, postfilter=conf.postfilter, keep_power=conf.keep_power,
                         **(dict(diff_filter=conf.diff_filter) if differential else pitch)).save(out)
 
 

@@ -323,7 +323,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                              'converter with gv_stats=True on two or more utterances)')
         return mean, var
 
-    def convert(self, mel_cepstrum, gv=0.0, ms=0.0, mlpg_gv=None, gv_weight=1.0, **kwargs):
+    def convert(self, mel_cepstrum, gv=0.0, ms=0.0, mlpg_gv=None, gv_weight=1.0, postfilter=0.0, keep_power=False,
+                **kwargs):
         """a MelCepstrum at the converter's sampling rate: c0 of the input, c1..cN converted.
         gv > 0 (a strength within [0, 1]; needs `gv_stats`): the converted c1..cN through the global-variance
         postfilter, each trajectory stretched about its own mean towards the target's variance.  With diff=True the
@@ -342,9 +343,19 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         global variance instead of the postfilter -- N conjugate-gradient steps on the joint objective of trajectory
         and GV likelihood, from the linearly scaled track (backend.mlpg.MLPG(gv=...)); gv_weight > 0 weighs the GV
         term.  c0 is kept; with diff=True the variance is that of the converted spectrum (differential + source).  It
-        goes with em=N, and with neither gv > 0 (the same repair twice) nor ms > 0 (not composed yet)."""
+        goes with em=N, and with neither gv > 0 (the same repair twice) nor ms > 0 (not composed yet).
+        postfilter > 0 (beta within [0, 1]) / keep_power=True run last, after ms, gv and mlpg_gv, on the ABSOLUTE
+        converted rows -- c0 of the input with the converted c1..cN; with diff=True input + differential, one addition
+        -- through backend.power.postfilter: the mel-cepstral formant emphasis of strength beta, then c0 shifted until
+        the frame has the energy of the input's frame (keep_power) or of the unfiltered converted frame (postfilter
+        alone).  c0 is not the power: converting c1.. at a fixed c0 moves a frame's energy by several dB.  Column 0 of
+        the result is then the corrected c0 -- with diff=True its DIFFERENCE from the input's c0, for a filter that
+        takes c0 into account (apply_diff_filter(use_c0=True)).  With both neutral nothing changes and
+        backend.power is not imported."""
         if mel_cepstrum.order != self.order:
             raise ValueError(f'order is expected to {self.order!s} but {mel_cepstrum.order!s}')
+        if not 0.0 <= postfilter <= 1.0:
+            raise ValueError(f'postfilter: beta {postfilter!r} is outside [0, 1]')
         if mlpg_gv is not None:
             if gv > 0:
                 raise ValueError('mlpg_gv does not go with gv > 0: the postfilter would repair the same variance twice')
@@ -381,5 +392,17 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             if gv > 0:
                 from ..backend import gv as gvfilter
                 converted = gvfilter.postfilter(plain, as_f64(self.gv_stats[1:]), gv, base=converted, first_col=0)
+        if postfilter > 0 or keep_power:
+            from ..backend import power as powerfilter
+            source = np.ascontiguousarray(out.data, dtype=np.float64)
+            options = dict(ref=source if keep_power else None, alpha=out.alpha(),
+                           fft_size=powerfilter.energy_fft_size(self.fs))
+            if kwargs.get('diff'):
+                base = np.hstack((np.zeros_like(source[:, :1]), converted)).astype(np.float64, copy=False)
+                out.data = powerfilter.postfilter(source + base, postfilter, base=base, **options)
+            else:
+                absolute = np.hstack((source[:, :1], converted)).astype(np.float64, copy=False)
+                out.data = powerfilter.postfilter(absolute, postfilter, **options)
+            return out
         out.data = np.hstack((power, converted))
         return out

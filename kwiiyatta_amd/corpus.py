@@ -847,13 +847,20 @@ class ConvertWave:
     differential; non-zero: coefficients left at the maximum-likelihood track).  Not with gv_strength or ms_strength.
     diff_filter='fft' (with diff=True): `wave_diff[i]` through the frame-parallel FFT form of the differential filter
     (kwy_mcep_filter_fft_batch_dev over the MLSA filter's jobs: one workgroup per frame, launched with the wave, so
-    defer_mlsa has nothing to defer) instead of the MLSA recursion; 'mlsa' (default) is that recursion, unchanged."""
+    defer_mlsa has nothing to defer) instead of the MLSA recursion; 'mlsa' (default) is that recursion, unchanged.
+    postfilter_beta > 0 (within [0, 1]) and / or keep_power (with a GMM): the absolute converted mel-cepstra through
+    kwy_mcep_postfilter_batch_dev after every other filter -- the formant emphasis, c0 shifted to the energy of the
+    source frame (keep_power) or of the unfiltered converted frame; the plain conversion in place, the differential one
+    as the base of source + differential, its column 0 then the change of c0, which the differential filters take into
+    account (ignore_c0 = 0).  `power_status` holds a word per utterance (two with diff=True: plain, then differential;
+    non-zero: frames left unfiltered, backend.power.postfilter).  With both neutral no kernel is launched."""
 
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
                  f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
                  ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0,
-                 diff_filter='mlsa'):
+                 diff_filter='mlsa', postfilter_beta=0.0, keep_power=False):
         self.diff_filter = _diff_filter(diff_filter)
+        self.postfilter_beta, self.keep_power = _postfilter_beta(postfilter_beta), bool(keep_power)
         self.mlpg_em = _mlpg_em(mlpg_em) if gmm is not None else None
         self.gvgen = _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order, ls.dev,
                                       on=gmm is not None)
@@ -972,6 +979,22 @@ class ConvertWave:
                 if self.diff:
                     self.j_ms_diff = _lib.job_array(_lib.MsJob, [(conv[i], self.T[i], self.mc_diff_rows[i],
                                                                   self.mc_diff_rows[i]) for i in range(n)])
+            # the formant emphasis / the power-preserving c0 on the ABSOLUTE converted rows, last of the filters: the plain
+            # conversion in place; the differential one as base of source + differential (its column 0 zeroed first: it
+            # then carries the difference of c0, and the differential filter reads it)
+            self.power_status = None
+            if gmm is not None and (self.postfilter_beta > 0 or self.keep_power):
+                self.power_status = torch.zeros((2 if self.diff else 1) * n, dtype=torch.int32, device=dev)
+                ref = env if self.keep_power else [None] * n
+                self.j_power = _lib.job_array(_lib.McPowerJob, [(conv[i], ref[i], None, conv[i], self.T[i])
+                                                                for i in range(n)])
+                if self.diff:
+                    self.mc_abs = torch.empty((self.rows, order + 1), **f64)
+                    absolute = rows.views(self.mc_abs)
+                    self.j_power_diff = _lib.job_array(_lib.McPowerJob, [(absolute[i], ref[i], self.mc_diff_rows[i],
+                                                                          self.mc_diff_rows[i], self.T[i])
+                                                                         for i in range(n)])
+            self.ignore_c0 = 0 if self.power_status is not None else 1
             self.j_render = _lib.synth_job_array([(self.plan[i], spec[i], ap[i], self.wave[i]) for i in range(n)])
             if self.formant_ratio != 1:
                 self.formant_status = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1023,6 +1046,9 @@ class ConvertWave:
                                                             None))
                     chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv, n, cols, 1, _p(self.gv), self.gv_strength,
                                                         _p(self.gv_status)))
+                if self.power_status is not None:
+                    chk(lib.kwy_mcep_postfilter_batch_dev(h, self.j_power, n, order, self.alpha, fft, self.postfilter_beta,
+                                                          _p(self.power_status[:n])))
                 chk(lib.kwy_mc2sp_dev(h, _p(self.mc_conv), self.rows, order, self.alpha, fft, _p(self.sp_conv)))
             if self.formant_status is not None:     # the rows the rendering reads, warped in place
                 rendered = self.sp_all if self.gmm is None else self.sp_conv
@@ -1038,6 +1064,11 @@ class ConvertWave:
                 if self.gv_status is None and self.ms_status is None:           # (with a postfilter it ran above)
                     chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em,
                                             self.gvgen, 1, None if self.gvgen is None else self.gvgen_status[n:]))
+                if self.power_status is not None:
+                    self.mc_diff[:, 0] = 0.0
+                    torch.add(self.mc, self.mc_diff, out=self.mc_abs)
+                    chk(lib.kwy_mcep_postfilter_batch_dev(h, self.j_power_diff, n, order, self.alpha, fft,
+                                                          self.postfilter_beta, _p(self.power_status[n:])))
                 if self.diff_filter == 'fft':       # every frame of every file in one grid: nothing to defer
                     self.run_fft_filter(ls.ctx)
                 elif not self.defer_mlsa:
@@ -1050,13 +1081,14 @@ class ConvertWave:
 
     def run_mlsa(self, ctx):
         chk = lambda rc: _lib.check(ctx, rc)  # noqa: E731
-        chk(lib.kwy_mlsa_filter_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, 4, self.hop, 1))
+        chk(lib.kwy_mlsa_filter_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, 4, self.hop,
+                                          self.ignore_c0))
         self.finish_diff(ctx)
 
     def run_fft_filter(self, ctx):
         """the wave's differential outputs through the frame-parallel FFT filter (the jobs of the MLSA filter as they are)"""
         _lib.check(ctx, lib.kwy_mcep_filter_fft_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, self.hop,
-                                                          self.diff_fft, 1))
+                                                          self.diff_fft, self.ignore_c0))
         self.finish_diff(ctx)
 
     def finish_diff(self, ctx):
@@ -1068,7 +1100,7 @@ class ConvertWave:
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
                     f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
                     ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0,
-                    diff_filter='mlsa'):
+                    diff_filter='mlsa', postfilter_beta=0.0, keep_power=False):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.
     Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
@@ -1078,7 +1110,7 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     if ms_strength:          # (checked and uploaded once: every wave takes the device tensors as they are)
         ms_stats = _ms_on_device(ms_stats, ms_length, ms_strength, order, ls.dev, on=gmm is not None)
     held, status, map_status, gv_status, ms_status, formant_status, waves_diff = [], [], [], [], [], [], []
-    gvgen_status = []
+    gvgen_status, power_status = [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
                          diff=diff, defer_mlsa=diff and diff_filter == 'mlsa', f0_stats=f0_stats,
@@ -1088,7 +1120,9 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
                          **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}),
                          **(dict(mlpg_em=mlpg_em) if mlpg_em is not None else {}),
                          **(dict(mlpg_gv=mlpg_gv, gv_stats=gv_stats, gv_var=gv_var, gv_weight=gv_weight)
-                            if mlpg_gv is not None else {}))
+                            if mlpg_gv is not None else {}),
+                         **(dict(postfilter_beta=postfilter_beta, keep_power=keep_power)
+                            if postfilter_beta or keep_power else {}))
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -1106,6 +1140,8 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             gvgen_status.append(wv.gvgen_status)
         if wv.formant_status is not None:
             formant_status.append(wv.formant_status)
+        if wv.power_status is not None:
+            power_status.append((wv.power_status, wv.n))
         if diff and diff_filter == 'mlsa':
             waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
         held.append(wv)
@@ -1122,7 +1158,7 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
             with torch.cuda.stream((ls.main, ls.side)[k % 2]):
                 chunk = rows[c0:c0 + 64]
                 _lib.check(ctx, lib.kwy_mlsa_filter_batch_dev(ctx.handle, _lib.job_array(_lib.MlsaJob, chunk), len(chunk), order,
-                                                              wv0.alpha, 4, wv0.hop, 1))
+                                                              wv0.alpha, 4, wv0.hop, wv0.ignore_c0))
         ls.main.wait_stream(ls.side)
         with torch.cuda.stream(ls.main):
             for wv in waves_diff:
@@ -1152,6 +1188,10 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     if gvgen_status:
         # (two words per utterance of a wave: the plain conversion's, then the differential one's)
         _check_gvgen_status(torch.cat([v.cpu()[:len(v) // 2] + v.cpu()[len(v) // 2:] for v in gvgen_status]))
+    if power_status:
+        # (with diff=True two words per utterance of a wave: the plain conversion's, then the differential one's)
+        from .backend import power
+        power.check_status(torch.cat([v.cpu().reshape(-1, n).sum(0) for v, n in power_status]))
     return ls
 
 
@@ -1538,6 +1578,14 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
         s_.synchronize()
 
 
+def _postfilter_beta(beta):
+    """the strength of the formant emphasis a driver is asked for, checked"""
+    beta = float(beta)
+    if not 0.0 <= beta <= 1.0:
+        raise ValueError(f'postfilter: beta {beta!r} is outside [0, 1]')
+    return beta
+
+
 def _diff_filter(name):
     """the differential filter a driver is asked for, checked"""
     from .filter import DIFF_FILTERS
@@ -1559,7 +1607,8 @@ def _formant_ratio(formant_ratio, driver, pool, who):
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
                   shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
                   gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0,
-                  mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0, diff_filter='mlsa'):
+                  mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0, diff_filter='mlsa', postfilter_beta=0.0,
+                  keep_power=False):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1585,8 +1634,16 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     after the batch.
     diff_filter (with diff=True): 'mlsa' (default), or 'fft': the differential outputs through the frame-parallel FFT
     form of the filter (kwy_mcep_filter_fft_batch_dev, one grid over all frames of a wave's files, launched with the
-    wave) instead of the MLSA recursions (which wait for the last wave and run side by side, one wavefront per file)."""
+    wave) instead of the MLSA recursions (which wait for the last wave and run side by side, one wavefront per file).
+    postfilter_beta / keep_power (lockstep driver): beta > 0 (within [0, 1]) runs the mel-cepstral formant emphasis on
+    the absolute converted mel-cepstra of both outputs, keep_power shifts every frame's c0 until the frame has the
+    energy of the source frame (ConvertWave; kwy_mcep_postfilter_batch_dev, after every other filter); the differential
+    filters then take c0 into account (ignore_c0 = 0: the coefficients' column 0 is the change of c0).  A frame whose
+    energy is unusable raises ValueError after the batch, a beta outside [0, 1] before anything is put on the device."""
     diff_filter = _diff_filter(diff_filter)
+    postfilter_beta = _postfilter_beta(postfilter_beta)
+    if (postfilter_beta or keep_power) and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
+        raise ValueError('convert_batch: postfilter_beta and keep_power need the lockstep driver')
     formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'convert_batch')
     mlpg_em = _mlpg_em(mlpg_em)
     if mlpg_gv is not None and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
@@ -1605,7 +1662,8 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
                         f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
                         ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio,
-                        mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, gv_var=gv_var, gv_weight=gv_weight, diff_filter=diff_filter)
+                        mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, gv_var=gv_var, gv_weight=gv_weight, diff_filter=diff_filter,
+                        postfilter_beta=postfilter_beta, keep_power=keep_power)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
