@@ -942,7 +942,40 @@ int kwy_gmm_em_finalize_dev(kwy_ctx *ctx, const double *stats, const double *sxx
                             double reg_covar, double *weights, double *covs);
 int kwy_gmm_em_scratch_bytes(int64_t n, int D, int M, int64_t *bytes);
 
-/* The whole fit of ONE rank's rows as one call: GaussianMixture(n_components=M, covariance_type='full', max_iter, tol,
+/* ---- converter fit: block-diagonal covariances ------------------------------------------------
+ * The same EM for a joint-density mixture over z = [x | y] (D = 2 h) whose covariance blocks Sxx, Syy and Sxy = Syx
+ * are diagonal (Toda, Black and Tokuda 2007; sprocket's covtype 'block_diag'): pairing x_i with y_i leaves h
+ * independent 2 x 2 blocks [[a_i, c_i], [c_i, b_i]] per mixture.  covs_bd and sbd are M x 3 x h doubles, laid out
+ * [a | b | c] per mixture.  Per EM iteration a driver runs
+ *   estep_bd -> sums -> [all-reduce stats] -> means -> cov_bd -> [all-reduce sbd] -> finalize_bd
+ * with kwy_gmm_em_sums_dev and kwy_gmm_em_means_dev from above; EM in this family is exact (the M-step's maximum is
+ * the empirical covariance restricted to the pattern).  All pointers are device pointers, nothing
+ * synchronises, the stream is the context's.  1 <= M <= 256, D even with 2 <= D <= 160, n >= 1; anything else, a NULL
+ * pointer included, is KWY_EINVAL with a message in kwy_last_error.
+ *
+ * estep_bd: resp (n x M) and loglik_parts (ceil(n/256) doubles, summed in a fixed order: bit-reproducible) as
+ *   kwy_gmm_em_estep_dev writes them, from log N(z; mu, S) = -1/2 (D log 2pi + sum_i log(a_i b_i - c_i^2)
+ *   + sum_i [b_i dx_i^2 - 2 c_i dx_i dy_i + a_i dy_i^2] / (a_i b_i - c_i^2)).  status_out[0] is set to non-zero when
+ *   some block has a <= 0 or a b - c^2 <= 0 (the block is then evaluated as the unit block: the outputs stay finite
+ *   and mean nothing), and to zero otherwise.
+ * cov_bd: sbd = [sum_t r (x - mux)^2 | sum_t r (y - muy)^2 | sum_t r (x - mux)(y - muy)] over the local shard, summed
+ *   in a fixed order without atomics.  stats (the reduced sums, or NULL) is accepted for symmetry with
+ *   kwy_gmm_em_cov_stats_dev; every frame is summed either way.
+ * finalize_bd: weights as kwy_gmm_em_finalize_dev; a = sa / nk + reg_covar, b = sb / nk + reg_covar, c = sc / nk.
+ * expand_bd: the M x D x D matrices -- the three diagonals copied exactly, +0.0 everywhere else -- which the
+ *   conversion entries (kwy_gmm_prepare_dev, ...) take as they take any full mixture. */
+int kwy_gmm_em_estep_bd_dev(kwy_ctx *ctx, const double *X, int64_t n, int D, int M, const double *weights,
+                            const double *means, const double *covs_bd /* M x 3 x D/2 */, double *resp /* n x M */,
+                            double *loglik_parts /* ceil(n/256) */, int *status_out);
+int kwy_gmm_em_cov_bd_dev(kwy_ctx *ctx, const double *X, int64_t n, int D, int M, const double *resp,
+                          const double *means, const double *stats_or_null, double *sbd /* M x 3 x D/2 */);
+int kwy_gmm_em_finalize_bd_dev(kwy_ctx *ctx, const double *stats, const double *sbd, int D, int M, double reg_covar,
+                               double *weights, double *covs_bd);
+int kwy_gmm_expand_bd_dev(kwy_ctx *ctx, const double *covs_bd, int D, int M, double *covs /* M x D x D */);
+
+/* The one-call fits below are full-covariance only: a block-diagonal fit is driven through the building blocks above.
+ *
+ * The whole fit of ONE rank's rows as one call: GaussianMixture(n_components=M, covariance_type='full', max_iter, tol,
  * reg_covar, random_state=seed).fit(X)                kwiiyatta/converter/gmm.py:14-26
  * -- the k-means initialisation below (numpy's RandomState(seed) draws, scikit-learn's seeding and Lloyd loop) and the
  * EM loop above, run by the library.  X: n x D on the device; weights (M), means (M x D), covs (M x D x D): HOST outputs;

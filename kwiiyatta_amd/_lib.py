@@ -153,6 +153,10 @@ SIGNATURES = {
     'kwy_gmm_em_cov_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     'kwy_gmm_em_cov_stats_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'kwy_gmm_em_finalize_dev': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_vp]),
+    'kwy_gmm_em_estep_bd_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'kwy_gmm_em_cov_bd_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'kwy_gmm_em_finalize_bd_dev': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_vp]),
+    'kwy_gmm_expand_bd_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
     'kwy_gmm_fit_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_dbl, c_dbl, ctypes.c_uint32, c_vp, c_vp, c_vp,
                                 ctypes.POINTER(c_int), ctypes.POINTER(c_dbl), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     'kwy_gmm_em_scratch_bytes': (c_int, [c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),

@@ -82,6 +82,19 @@ CONVERTER_OPTIONS += (
 )
 
 
+COVARIANCE_STRUCTURES = ('full', 'block_diag')
+
+# an addition to the reference's options (its mixtures have full covariances)
+CONVERTER_OPTIONS += (
+    ('--converter-covariance', dict(choices=COVARIANCE_STRUCTURES, default=None,
+                                    help='Structure of the mixture\'s covariances: full matrices, or block_diag -- '
+                                         'diagonal source, target and cross blocks (Toda et al. 2007), 3 D / 2 numbers '
+                                         'per component instead of D (D + 1) / 2, for training sets of a few '
+                                         'sentences; kept in the converter model (default full, as the reference '
+                                         'does)')),
+)
+
+
 # an addition to the reference's options (it has no postfilter)
 CONVERTER_OPTIONS += (
     ('--ms-length', dict(type=int, choices=MS_LENGTHS, default=None, metavar='L',
@@ -289,6 +302,8 @@ class Config:
         chosen = dict(random_state=self.converter_seed, components=self.converter_components)
         if self.mcep_fs is not None:
             chosen['mcep_fs'] = self.mcep_fs
+        if getattr(self, 'converter_covariance', None) is not None:
+            chosen['covariance'] = self.converter_covariance
         return make(**dict(chosen, **kwargs))
 
     def _required_dir(self, flag):
@@ -379,6 +394,11 @@ class Config:
             if asked is not None and asked != converter.align_iterations:
                 self.parser.error(f'{model}: the converter model was trained with --align-iterations '
                                   f'{converter.align_iterations}, not {asked}; retrain it with --align-iterations '
+                                  f'{asked} (a new --converter-model file)')
+            asked = getattr(self, 'converter_covariance', None)
+            if asked is not None and asked != converter.covariance:
+                self.parser.error(f'{model}: the converter model was trained with --converter-covariance '
+                                  f'{converter.covariance}, not {asked}; retrain it with --converter-covariance '
                                   f'{asked} (a new --converter-model file)')
             if f0_stats and converter.f0_stats is None:
                 self.parser.error(f'{model}: the converter model has no f0 statistics; retrain it with '

@@ -9,13 +9,22 @@ from .gmm_fit import GaussianMixtureHIP as GaussianMixture
 
 
 class GMMFeatureConverter(abc.FeatureConverter):
-    def __init__(self, components=64, max_iter=100, random_state=None, **kwargs):
-        self.init_gmm(components, max_iter, random_state, **kwargs)
+    def __init__(self, components=64, max_iter=100, random_state=None, covariance='full', **kwargs):
+        # covariance (an addition): 'full', or 'block_diag' -- diagonal source, target and cross blocks, the
+        # structure of Toda et al.'s mixtures, for training sets too small for 64 full matrices (gmm_fit)
+        self.init_gmm(components, max_iter, random_state, covariance=covariance, **kwargs)
 
-    def init_gmm(self, components, max_iter=100, random_state=None, **kwargs):
+    def init_gmm(self, components, max_iter=100, random_state=None, covariance='full', **kwargs):
         options = dict(verbose=1, covariance_type='full')
+        if covariance not in (None, 'full'):       # (handed on only when asked for: a mixture class without the
+            options['covariance_structure'] = covariance       # argument, scikit-learn's, keeps working)
         options.update(kwargs)
         self.gmm = GaussianMixture(n_components=components, max_iter=max_iter, random_state=random_state, **options)
+
+    @property
+    def covariance(self):
+        """the structure of the mixture's covariances: 'full' or 'block_diag'"""
+        return getattr(self.gmm, 'covariance_structure', 'full')
 
     def _train(self, dataarray, **kwargs):
         self.gmm.fit(dataarray, **kwargs)

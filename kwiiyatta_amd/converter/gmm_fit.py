@@ -27,6 +27,11 @@ the number of ranks beyond the rounding of the sums.
 
 The numerical work is delegated to a ``stats`` object; ``HipStats`` is the product
 implementation, the tests inject a numpy one to exercise the driver without a GPU.
+
+``covariance_structure='block_diag'`` (an addition; ``HipStatsBlockDiag``) fits the mixture over
+[source | target] features with diagonal xx, yy and xy = yx covariance blocks -- the structure of
+Toda, Black and Tokuda (2007) -- through the same driver: EM is exact in that family, and what the
+ranks exchange for the covariances shrinks to 3 M D / 2 doubles per iteration.
 """
 import numpy as np
 
@@ -109,10 +114,13 @@ class HipStats:
         self.ll = torch.empty((self.n + 255) // 256, **f64)
         self.status = torch.zeros(4, dtype=torch.int32, device=self.dev)
         self.stats = torch.empty((self.M, self.D + 1), **f64)
-        self.sxx = torch.empty((self.M, self.D, self.D), **f64)
         self.means = torch.empty((self.M, self.D), **f64)
         self.weights = torch.empty(self.M, **f64)
-        self.covs = torch.empty((self.M, self.D, self.D), **f64)
+        self._allocate_covariances(f64)
+
+    def _allocate_covariances(self, f64):
+        self.sxx = self.torch.empty((self.M, self.D, self.D), **f64)
+        self.covs = self.torch.empty((self.M, self.D, self.D), **f64)
 
     def _p(self, t):
         return self._lib.c_vp(t.data_ptr()) if t is not None else None
@@ -289,6 +297,76 @@ class HipStats:
         d = (self.Xc - centers[self.labels.long()]).pow(2).sum(1)
         v, i = t.topk(d, min(k, self.n))
         return v, i
+
+
+class HipStatsBlockDiag(HipStats):
+    """The statistics of a mixture over [x | y] (D = 2 h) whose covariance blocks xx, yy and xy = yx are diagonal
+    (Toda, Black and Tokuda 2007): h independent 2 x 2 blocks per component, kept as (M, 3, h) = [a | b | c] on the
+    device (kwy_gmm_em_*_bd_dev, csrc/kwy_gmmfit_bd.hip).  Sums, means, k-means and everything the driver exchanges
+    are HipStats's; the parameters go in and come out as full (M, D, D) matrices."""
+
+    def _allocate(self, X, n_components):
+        D = X.shape[1]
+        if D < 2 or D % 2:
+            raise ValueError(f'block_diag covariances pair the two halves of the features: D = {D} is not even')
+        super()._allocate(X, n_components)
+
+    def _allocate_covariances(self, f64):
+        self.sbd = self.torch.empty((self.M, 3, self.D // 2), **f64)
+        self.covs_bd = self.torch.empty((self.M, 3, self.D // 2), **f64)
+
+    def set_params(self, weights, means, covs):
+        """covs: full (M, D, D) matrices, of which the pattern is read (the rest is taken to be zero)"""
+        h = self.D // 2
+        covs = np.asarray(covs, dtype=np.float64)
+        i = np.arange(h)
+        bd = np.stack((covs[:, i, i], covs[:, h + i, h + i], covs[:, i, h + i]), axis=1)
+        for dst, src in ((self.weights, weights), (self.means, means), (self.covs_bd, bd)):
+            dst.copy_(self.torch.from_numpy(np.ascontiguousarray(src, dtype=np.float64)))
+
+    def estep(self):
+        lib = self._lib.lib
+        self._chk(lib.kwy_gmm_em_estep_bd_dev(self.ctx.handle, self._p(self.X), self.n, self.D, self.M,
+                                              self._p(self.weights), self._p(self.means), self._p(self.covs_bd),
+                                              self._p(self.resp), self._p(self.ll), self._p(self.status)))
+        return self.ll.sum().reshape(1)
+
+    def cov(self, stats=None):
+        """(M, 3, h) local [sum r dx^2 | sum r dy^2 | sum r dx dy] around self.means, device tensor"""
+        self._chk(self._lib.lib.kwy_gmm_em_cov_bd_dev(self.ctx.handle, self._p(self.X), self.n, self.D, self.M,
+                                                      self._p(self.resp), self._p(self.means),
+                                                      self._p(stats) if stats is not None else None, self._p(self.sbd)))
+        return self.sbd
+
+    def finalize(self, stats, sbd, reg_covar):
+        self._chk(self._lib.lib.kwy_gmm_em_finalize_bd_dev(self.ctx.handle, self._p(stats), self._p(sbd), self.D,
+                                                           self.M, float(reg_covar), self._p(self.weights),
+                                                           self._p(self.covs_bd)))
+
+    def expanded(self):
+        """the covariances as (M, D, D) device tensor: the three diagonals, zero elsewhere"""
+        covs = self.torch.empty((self.M, self.D, self.D), dtype=self.torch.float64, device=self.dev)
+        self._chk(self._lib.lib.kwy_gmm_expand_bd_dev(self.ctx.handle, self._p(self.covs_bd), self.D, self.M,
+                                                      self._p(covs)))
+        return covs
+
+    def get_params(self):
+        with self.scope():
+            out = (self.weights.cpu().numpy(), self.means.cpu().numpy(), self.expanded().cpu().numpy())
+        self.ctx.sync()
+        return out
+
+
+COVARIANCE_STRUCTURES = ('full', 'block_diag')
+
+
+def check_covariance_structure(structure):
+    """'full' for None; NotImplementedError for a word that names no structure"""
+    structure = 'full' if structure is None else structure
+    if structure not in COVARIANCE_STRUCTURES:
+        raise NotImplementedError(f'covariance structure {structure!r}: GaussianMixtureHIP fits '
+                                  f"{' and '.join(repr(s) for s in COVARIANCE_STRUCTURES)}")
+    return structure
 
 
 LLOYD_BATCH = 16          # Lloyd iterations enqueued per read-back of the device's stopping decision (one shard)
@@ -534,13 +612,18 @@ def library_comm(device_index=0):
 
 
 def fit_one_call(X, n_components, max_iter=100, tol=1e-3, reg_covar=1e-6, random_state=0, device_index=0, ctx=None,
-                 distributed=False):
+                 distributed=False, covariance_structure='full'):
     """The fit of one rank's rows through the library's single entry point `kwy_gmm_fit_dev` (the control flow of this
     module in C++, for binders without a Python driver).  X: (n, D) numpy array or float64 device tensor; an integer
     `random_state`.  distributed=True: `kwy_gmm_fit_comm_dev` with torch.distributed's default group as the
     communicator -- X is this rank's shard and every rank returns the model of all rows.
-    Returns a GaussianMixtureHIP carrying the fitted attributes."""
+    Returns a GaussianMixtureHIP carrying the fitted attributes.  Full covariances only: the library's one-call
+    drivers know no other structure."""
     import ctypes
+    if check_covariance_structure(covariance_structure) != 'full':
+        raise NotImplementedError(f'fit_one_call fits full covariances only (kwy_gmm_fit_dev has no '
+                                  f'{covariance_structure!r} form): use GaussianMixtureHIP(covariance_structure='
+                                  f'{covariance_structure!r}).fit')
     import torch
     from .. import _lib
     dev = torch.device('cuda', device_index)
@@ -572,14 +655,21 @@ def fit_one_call(X, n_components, max_iter=100, tol=1e-3, reg_covar=1e-6, random
 
 class GaussianMixtureHIP:
     """Drop-in for the sklearn GaussianMixture object held by GMMFeatureConverter
-    (full covariance, one initialisation)."""
+    (full covariance, one initialisation).
+    covariance_structure='block_diag' (an addition): the mixture over [x | y] with diagonal xx, yy and xy = yx
+    covariance blocks (HipStatsBlockDiag) -- 3 D / 2 covariance numbers per component instead of D (D + 1) / 2, for
+    training sets too small for the latter.  `covariance_type` stays 'full' either way: it names the shape of
+    `covariances_`, (M, D, D), which is what the conversion reads."""
     covariance_type = 'full'
+    covariance_structure = 'full'
 
     def __init__(self, n_components=1, covariance_type='full', tol=1e-3, reg_covar=1e-6, max_iter=100,
-                 n_init=1, init_params='kmeans', random_state=None, verbose=0, device_index=0, sort_rows=True, **unused):
+                 n_init=1, init_params='kmeans', random_state=None, verbose=0, device_index=0, sort_rows=True,
+                 covariance_structure='full', **unused):
         if covariance_type != 'full' or n_init != 1 or init_params != 'kmeans':
             raise NotImplementedError('GaussianMixtureHIP implements the configuration the reference uses: '
                                       "covariance_type='full', n_init=1, init_params='kmeans'")
+        self.covariance_structure = check_covariance_structure(covariance_structure)
         self.n_components, self.tol, self.reg_covar, self.max_iter = n_components, tol, reg_covar, max_iter
         self.random_state, self.verbose, self.device_index = random_state, verbose, device_index
         self.sort_rows = sort_rows        # group the rows by their k-means cluster before EM (HipStats.sort_rows_by_component)
@@ -589,7 +679,13 @@ class GaussianMixtureHIP:
         assignments of the local rows (skips the k-means run)."""
         import torch
         if stats is None:
-            stats = HipStats(X, self.n_components, device_index=self.device_index)
+            if self.covariance_structure == 'block_diag':
+                if X.shape[1] < 2 or X.shape[1] % 2:         # (before anything is allocated on the device)
+                    raise ValueError(f'block_diag covariances pair the two halves of the features: D = {X.shape[1]} '
+                                     f'is not even')
+                stats = HipStatsBlockDiag(X, self.n_components, device_index=self.device_index)
+            else:
+                stats = HipStats(X, self.n_components, device_index=self.device_index)
         comm = Comm()
         with stats.scope():
             n_total = comm.all_reduce(torch.tensor([float(stats.n)], dtype=torch.float64, device=stats.dev))

@@ -256,7 +256,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         """the trained stack as one .npz: the mixture's parameters and what the outer stages learnt from the
         training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics, the global variance and the
         modulation-spectrum statistics when there are any; the pitch ratio of the source waveforms; the re-alignment passes of the training as
-        `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`)"""
+        `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`; the structure of
+        the covariances as `covariance` when it is not 'full')"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
@@ -267,6 +268,9 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             if self.ms_stats is not None:
                 extra.update(ms_stats_g=np.array(self.ms_stats[0], dtype=np.float64),
                              ms_stats_n=np.array(self.ms_stats[1], dtype=np.float64), ms_length=int(self.ms_length))
+            structure = getattr(gmm, 'covariance_structure', 'full')
+            if structure != 'full':          # (a full model's file is what it was before structures existed)
+                extra['covariance'] = structure
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      source_f0_rate=float(self.source_f0_rate),
@@ -278,7 +282,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
     def load(self, path):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
         the file.  `f0_stats` / `gv_stats` / `ms_stats` are None for a file without them (written without these statistics, or before
-        they existed); `source_f0_rate` is 1.0 for a file without it, `align_iterations` 0 and `align_history` empty"""
+        they existed); `source_f0_rate` is 1.0 for a file without it, `align_iterations` 0 and `align_history` empty,
+        the mixture's `covariance_structure` 'full'"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
@@ -295,6 +300,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             gmm.means_ = np.array(z['means'], dtype=np.float64)
             gmm.covariances_ = np.array(z['covariances'], dtype=np.float64)
             gmm.n_components = len(gmm.weights_)
+            gmm.covariance_structure = str(z['covariance']) if 'covariance' in z.files else 'full'
             gmm.converged_ = True
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
             self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None

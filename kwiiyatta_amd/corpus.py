@@ -430,10 +430,10 @@ def realign_training_matrix(cache, gmm, paths=None):
 def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterations=0, max_iter=100, device_index=0,
                               order=24, radius=32, frame_period=5.0, silence_for=None, rng=None, pairs_before=0,
                               driver=None, lockstep=None, wave_pairs=16, f0_moments=False, gv_moments=False, verbose=0,
-                              keep_matrices=False):
+                              keep_matrices=False, covariance='full'):
     """Training with iterative re-alignment on the device: `build_training_matrix(keep=True)` and `fit_converter`, then
     `align_iterations` times `realign_training_matrix` with the mixture fitted last and `fit_converter` on its rows,
-    from scratch (same components, seed, stopping rule).  The pads are drawn once -- numpy's global generator or the
+    from scratch (same components, seed, stopping rule, `covariance` structure).  The pads are drawn once -- numpy's global generator or the
     device-drawn stream (`rng`, `pairs_before`) advance as they do for align_iterations = 0 -- and the f0 / global
     variance moments are the first pass's.  Returns (mixture, history[, f0 moments][, gv statistic]): history holds a
     dict per fit -- rows, mcd (the alignment's monitor, `_Alignment.monitor`), em_iterations -- and with keep_matrices=True
@@ -453,7 +453,7 @@ def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterati
 
     def fit(X, mcd):
         g = fit_converter(X, components=components, seed=seed, max_iter=max_iter, device_index=device_index,
-                          verbose=verbose)
+                          verbose=verbose, covariance=covariance)
         history.append(dict(rows=int(X.shape[0]), mcd=mcd, em_iterations=int(g.n_iter_),
                             **(dict(X=X) if keep_matrices else {})))
         return g
@@ -1537,11 +1537,12 @@ def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=3
     return X, frames
 
 
-def fit_converter(X, components=64, seed=None, max_iter=100, device_index=0, verbose=0):
-    """GMMFeatureConverter._train on the device-resident matrix (this rank's shard)."""
+def fit_converter(X, components=64, seed=None, max_iter=100, device_index=0, verbose=0, covariance='full'):
+    """GMMFeatureConverter._train on the device-resident matrix (this rank's shard).  covariance: 'full' or
+    'block_diag' (GaussianMixtureHIP's covariance_structure)."""
     from .converter.gmm_fit import GaussianMixtureHIP
     return GaussianMixtureHIP(n_components=components, max_iter=max_iter, random_state=seed, verbose=verbose,
-                              device_index=device_index).fit(X)
+                              device_index=device_index, covariance_structure=covariance).fit(X)
 
 
 def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):

@@ -676,6 +676,13 @@ extern "C" int kwy_gmm_em_scratch_bytes(int64_t n, int D, int M, int64_t *bytes)
   return KWY_OK;
 }
 
+// wlp (n x M weighted log probabilities) -> responsibilities in place, ll_part: ceil(n/256) partial log-likelihoods
+int kwy_fit_resp(kwy_ctx *ctx, double *wlp, int64_t n, int M, double *ll_part) {
+  KWY_PROF(ctx, "k_fit_resp", hipLaunchKernelGGL(k_fit_resp, dim3((unsigned)((n + KWY_THREADS - 1) / KWY_THREADS)), dim3(KWY_THREADS), 0, ctx->stream, wlp, n, M, ll_part));
+  KWY_HIP(hipGetLastError());
+  return KWY_OK;
+}
+
 // E-step on the local shard.  resp: n x M (out).  loglik_parts: ceil(n/256) doubles (out): their sum is
 // sum_t log p(x_t).  status_out (device int): nonzero if a covariance was not positive definite.
 extern "C" int kwy_gmm_em_estep_dev(kwy_ctx *ctx, const double *X, int64_t n, int D, int M,
@@ -707,10 +714,7 @@ extern "C" int kwy_gmm_em_estep_dev(kwy_ctx *ctx, const double *X, int64_t n, in
     case 9: KWY_TRY(fit_lp_launch<9>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
     default: KWY_TRY(fit_lp_launch<10>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
   }
-  hipLaunchKernelGGL(k_fit_resp, dim3((unsigned)((n + KWY_THREADS - 1) / KWY_THREADS)), dim3(KWY_THREADS), 0,
-                     ctx->stream, resp, n, M, loglik_parts);
-  KWY_HIP(hipGetLastError());
-  return KWY_OK;
+  return kwy_fit_resp(ctx, resp, n, M, loglik_parts);
 }
 
 template <int NBLK>

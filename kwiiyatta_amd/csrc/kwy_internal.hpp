@@ -141,6 +141,9 @@ int kwy_get_sp2mc_matrix(kwy_ctx *ctx, int N, int order, double alpha, const dou
 // the one-hot rows of the labels (resp is not read): kwy_gmmfit.hip
 int kwy_fit_sums_gated(kwy_ctx *ctx, const double *X, int64_t n, int D, int M, const double *resp, double *stats,
                        const long long *gate, const int *labels);
+// the log-sum-exp step of the E-step (k_fit_resp, kwy_gmmfit.hip): wlp (n x M) becomes the responsibilities in place,
+// ll_part[ceil(n/256)] the partial sums of the frames' log-likelihoods; shared by the full and the block-diagonal E-step
+int kwy_fit_resp(kwy_ctx *ctx, double *wlp, int64_t n, int M, double *ll_part);
 // [max_c][nthreads] table: row c-1 holds x^(12*c*t) mod P, t < nthreads (chunk of c draws per thread)
 int kwy_get_poly_multi(kwy_ctx *ctx, int max_c, int nthreads, const uint4 **out);
 
