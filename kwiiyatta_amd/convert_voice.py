@@ -54,14 +54,37 @@ and `--mlpg-gv`.  For the .diff.wav output the corrected c0 travels as its diffe
 of the differential mel-cepstrum, and the differential filter takes that column into account
 (`apply_diff_filter(..., use_c0=True)`).  Neither option writes anything to the converter model."""
 import pathlib
+from types import SimpleNamespace
 
 import numpy as np
 
+from ._convert_options import ConvertOptions, filled, takes_options
+
 OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
+# what a command can ask of a conversion, under the names of its arguments (Config), and what it asks by default
+COMMAND_OPTIONS = dict(convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0, formant_shift=0.0, mlpg_em=None, mlpg_gv=None,
+                       diff_filter='mlsa', postfilter=0.0, keep_power=False)
 
-def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-            formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa', postfilter=0.0, keep_power=False):
+
+def driver_options(converter, asked):
+    """the keywords of the device drivers (corpus.ConvertOptions) for what a command `asked` of this converter: its
+    statistics where an option needs them, and of the others those that are not the drivers' defaults"""
+    plain = dict(formant_ratio=2.0 ** (asked.formant_shift / 12), mlpg_em=asked.mlpg_em, mlpg_gv=asked.mlpg_gv,
+                 diff_filter=asked.diff_filter, postfilter_beta=asked.postfilter, keep_power=asked.keep_power)
+    on = {name: v for name, v in plain.items() if v != ConvertOptions.DEFAULTS[name]}
+    on.update(f0_stats=converter.f0_stats if asked.convert_f0 else None, transpose_key=asked.transpose_key)
+    if asked.gv > 0:
+        on.update(gv_stats=converter.gv_stats, gv_strength=asked.gv)
+    if asked.ms > 0:
+        on.update(ms_stats=converter.ms_stats, ms_length=converter.ms_length, ms_strength=asked.ms)
+    if asked.mlpg_gv is not None:
+        on.update(gv_stats=converter.gv_stats, gv_var=converter.gv_var)
+    return on
+
+
+@takes_options(defaults=COMMAND_OPTIONS)
+def convert(conf, converter, src_path, diffvc=True, **options):
     """one converted waveform.  The file is analysed afresh per call, as the reference does.  convert_f0 /
     transpose_key: the f0 of the synthesised output through converter.convert_f0 (the differential output is the
     input waveform filtered, its pitch stays the source's).  gv > 0: the converted mel-cepstrum through the
@@ -79,27 +102,30 @@ def convert(conf, converter, src_path, diffvc=True, convert_f0=False, transpose_
     mel-cepstrum (converter.convert(postfilter=..., keep_power=...), either output); the differential filter then runs
     with use_c0=True, on the change of c0 the conversion hands over in column 0."""
     import kwiiyatta_amd as k
-    if not 0.0 <= postfilter <= 1.0:          # (raises before the file is read)
-        raise ValueError(f'postfilter: beta {postfilter!r} is outside [0, 1]')
-    power = dict(postfilter=postfilter, keep_power=keep_power) if postfilter > 0 or keep_power else {}
+    o = SimpleNamespace(**filled(options, COMMAND_OPTIONS))
+    if not 0.0 <= o.postfilter <= 1.0:          # (raises before the file is read)
+        raise ValueError(f'postfilter: beta {o.postfilter!r} is outside [0, 1]')
+    power = o.postfilter > 0 or o.keep_power
+    # converter.convert's keywords: (value, whether it is on) -- an option that is off is not handed over
+    stages = dict(gv=(o.gv, o.gv > 0), ms=(o.ms, o.ms > 0), em=(o.mlpg_em, o.mlpg_em is not None),
+                  mlpg_gv=(o.mlpg_gv, o.mlpg_gv is not None), postfilter=(o.postfilter, power),
+                  keep_power=(o.keep_power, power))
     source = analyze_source(conf, converter, src_path)
-    converted = converter.convert(source.mel_cepstrum, diff=diffvc, **(dict(gv=gv) if gv > 0 else {}),
-                                  **(dict(ms=ms) if ms > 0 else {}), **({} if mlpg_em is None else dict(em=mlpg_em)),
-                                  **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)), **power)
+    converted = converter.convert(source.mel_cepstrum, diff=diffvc, **{name: v for name, (v, on) in stages.items() if on})
     if diffvc:
         use_c0 = dict(use_c0=True) if power else {}
-        if diff_filter == 'mlsa':
+        if o.diff_filter == 'mlsa':
             return k.apply_mlsa_filter(source, converted, **use_c0)
-        return k.apply_diff_filter(source, converted, method=diff_filter, **use_c0)
+        return k.apply_diff_filter(source, converted, method=o.diff_filter, **use_c0)
     rendered = k.feature(source)
     rendered.mel_cepstrum = converted                   # takes over from the analysed envelope
-    if convert_f0 or transpose_key != 0:
+    if o.convert_f0 or o.transpose_key != 0:
         from .backend import f0 as f0map
-        stats = converter.f0_stats if convert_f0 else None          # (converter.convert_f0 without the statistics)
+        stats = converter.f0_stats if o.convert_f0 else None          # (converter.convert_f0 without the statistics)
         rendered.f0 = f0map.map_f0(np.ascontiguousarray(source.f0, dtype=np.float64), rendered.fs, stats=stats,
-                                   key=transpose_key)
-    if formant_shift != 0:
-        rendered.shift_formants(2.0 ** (formant_shift / 12))
+                                   key=o.transpose_key)
+    if o.formant_shift != 0:
+        rendered.shift_formants(2.0 ** (o.formant_shift / 12))
     return rendered.synthesize()
 
 
@@ -141,9 +167,8 @@ class _Pcm16:
         wavfile.write(wav, self.fs, self.pcm)
 
 
-def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0,
-                        formant_shift=0.0, mlpg_em=None, mlpg_gv=None, diff_filter='mlsa', postfilter=0.0,
-                        keep_power=False):
+@takes_options(defaults=COMMAND_OPTIONS)
+def convert_synth_batch(conf, converter, paths, diffvc=False, **options):
     """{(path, differential?): object with .save(file)} of the .synth.wav outputs -- with diffvc=True of the .diff.wav
     outputs too.  Files whose sampling rate or frame period differ from the converter's go through `convert` one by
     one (the batch path has no resampling stage).  The others go through the device WAV IN -> PCM OUT: the pitch shift of
@@ -166,9 +191,9 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
     corpus.convert_batch(postfilter_beta=..., keep_power=...))."""
     import kwiiyatta_amd as k
     from . import corpus
-    postfilter = corpus._postfilter_beta(postfilter)          # (raises before any file is read)
-    power = dict(postfilter=postfilter, keep_power=keep_power) if postfilter > 0 or keep_power else {}
-    if mlpg_gv is not None:
+    o = SimpleNamespace(**filled(options, COMMAND_OPTIONS))
+    corpus._postfilter_beta(o.postfilter)          # (raises before any file is read)
+    if o.mlpg_gv is not None:
         converter.gv_ascent_statistics()          # (raises before any file is read)
     from ._lib import lib
     from .converter.delta import DeltaFeatureConverter
@@ -178,13 +203,11 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
         a = conf.create_analyzer(path, Analyzer=k.analyze_wav)
         # (the frame count ConvertWave itself takes for a bare waveform -- the same call on the same number of samples,
         # which the pitch shifter keeps -- so a file that passes here fits there)
-        too_long = ms > 0 and converter.ms_length is not None and \
+        too_long = o.ms > 0 and converter.ms_length is not None and \
             lib.kwy_dio_frames(int(a.fs), len(a.wavdata.data), float(a.frame_period)) > converter.ms_length
         if a.fs != converter.fs or a.mel_cepstrum_order != converter.order or too_long or \
                 (period is not None and a.frame_period != period):
-            out[path, False] = convert(conf, converter, path, diffvc=False, convert_f0=convert_f0,
-                                       transpose_key=transpose_key, gv=gv, ms=ms, formant_shift=formant_shift,
-                                       mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, **power)
+            out[path, False] = convert(conf, converter, path, diffvc=False, **options)
         else:
             batch.append((path, a))
     if batch:
@@ -195,16 +218,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, convert_f0=False, 
             waves = shift_waves_dev(waves, fs, rate)
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
                                    frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
-                                   f0_stats=converter.f0_stats if convert_f0 else None, transpose_key=transpose_key,
-                                   **(dict(gv_stats=converter.gv_stats, gv_strength=gv) if gv > 0 else {}),
-                                   **(dict(ms_stats=converter.ms_stats, ms_length=converter.ms_length, ms_strength=ms)
-                                      if ms > 0 else {}),
-                                   **(dict(formant_ratio=2.0 ** (formant_shift / 12)) if formant_shift != 0 else {}),
-                                   **({} if mlpg_em is None else dict(mlpg_em=mlpg_em)),
-                                   **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv, gv_stats=converter.gv_stats,
-                                                                      gv_var=converter.gv_var)),
-                                   **({} if diff_filter == 'mlsa' else dict(diff_filter=diff_filter)),
-                                   **(dict(postfilter_beta=postfilter, keep_power=keep_power) if power else {}))
+                                   **driver_options(converter, o))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:
@@ -242,11 +256,9 @@ def main():
     conf.parse_args()
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
                                      ms_stats=conf.ms > 0, **(dict(gv_var=True) if conf.mlpg_gv is not None else {}))
-    pitch = dict(convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, formant_shift=conf.formant_shift)
-    batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files],
-                                  diffvc=not conf.no_diffvc, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                                  mlpg_gv=conf.mlpg_gv, diff_filter=conf.diff_filter, postfilter=conf.postfilter,
-                                  keep_power=conf.keep_power, **pitch) if conf.batch else {}
+    asked = {name: getattr(conf, name) for name in COMMAND_OPTIONS}
+    batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files], diffvc=not conf.no_diffvc,
+                                  **asked) if conf.batch else {}
     for name in conf.files:
         wav_path = pathlib.Path(name)
         stem = wav_path if conf.result_dir is None else pathlib.Path(conf.result_dir) / wav_path.name
@@ -259,9 +271,7 @@ def main():
             if (wav_path, differential) in batched:
                 batched[wav_path, differential].save(out)
             else:
-                convert(conf, converter, wav_path, diffvc=differential, gv=conf.gv, ms=conf.ms, mlpg_em=conf.mlpg_em,
-                        mlpg_gv=conf.mlpg_gv, postfilter=conf.postfilter, keep_power=conf.keep_power,
-                        **(dict(diff_filter=conf.diff_filter) if differential else pitch)).save(out)
+                convert(conf, converter, wav_path, diffvc=differential, **asked).save(out)
 
 
 if __name__ == '__main__':

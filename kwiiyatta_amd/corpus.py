@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from ._blocks import Ragged, p as _p, to_device
+from ._convert_options import ConvertOptions, takes_options
 from ._lib import lib
 from .pipeline import (PAD_LEN, PIECE_CEILING, POWER_THRESHOLD, POWER_WEIGHT, SAFE_GUARD_MINIMUM, VUV_WEIGHT, DeviceGMM,
                        _Graphed, _Side, draw_silence, f0_jobs)
@@ -477,12 +478,11 @@ class EvalWave(TrainWave):
     counts stay device words).  Nothing is read back here: `measure` writes pair k's figures into row first + k of the
     caller's tensors.  `frame_period` is accepted and ignored, as in TrainWave."""
 
-    def measure(self, pads, gmm, model, tot, first, frames='speech', gv=None, gv_strength=0.0, f0_stats=None,
-                transpose_key=0.0, per_frame=False, mlpg_em=None, gvgen=None):
-        """tot: the _EvalTotals of the corpus; gv / f0_stats: device tensors (order + 1 values / 4 values) or None;
-        mlpg_em: None, or the re-estimations of the EM trajectory conversion (kwy_convert_mcep_em_batch_dev);
-        gvgen: None, or `_gvgen_on_device`'s options of the GV ascent behind the conversion
-        (kwy_convert_mcep_gv_batch_dev; its status words go where the postfilter's would, the two exclude each other)"""
+    def measure(self, pads, gmm, model, tot, first, opts, frames='speech', per_frame=False):
+        """tot: the _EvalTotals of the corpus; opts: the resolved options (`ConvertOptions.upload`) -- of them the f0
+        map, the global-variance postfilter (`_GvFilter`), mlpg_em and the GV ascent, whose status words go where the
+        postfilter's would (the two exclude each other)"""
+        mlpg_em, gvgen = opts.mlpg_em, opts.gvgen
         from .backend import distortion as dist
         a = self.align(pads)
         Tp = a.inputs.Tp
@@ -506,20 +506,18 @@ class EvalWave(TrainWave):
             chk(_convert_mcep_batch(h, _convert_jobs([(src_mc[k], keep[2 * k], conv[k]) for k in range(n)], mlpg_em, gvgen),
                                     n, order, gmm.M, model, mlpg_em, gvgen, 0,
                                     tot.gv_status[first:first + n] if gvgen is not None else None))
-            if gv is not None:
-                self.gv_moments = torch.empty((n, cols, 3), **f64)
-                chk(lib.kwy_column_moments_batch_dev(h, J(_lib.GvMatrix, [(conv[k], keep[2 * k]) for k in range(n)]), n,
-                                                     cols, _p(self.gv_moments)))
-                chk(lib.kwy_gv_postfilter_batch_dev(
-                    h, J(_lib.GvJob, [(conv[k], keep[2 * k], self.gv_moments[k], conv[k], conv[k]) for k in range(n)]),
-                    n, cols, 1, _p(gv), float(gv_strength), _p(tot.gv_status[first:first + n])))
-            if f0_stats is not None or transpose_key != 0:
+            if opts.gv is not None:
+                self.gv_filter = _GvFilter(opts.gv, opts.gv_strength, conv, keep[0::2], None, dev,
+                                           status=tot.gv_status[first:first + n])
+                self.gv_filter.prepare(chk, h)
+                self.gv_filter.launch(chk, h)
+            if opts.f0_map:
                 from .backend.f0 import key_ratio
                 self.f0_mapped = torch.empty(own.total, **f64)
                 mapped = own.views(self.f0_mapped)
                 chk(lib.kwy_f0_map_batch_dev(h, J(_lib.F0MapJob, [(src_f0[k], keep[2 * k], mapped[k]) for k in range(n)]),
-                                             n, fs, None if f0_stats is None else f0_stats.data_ptr(),
-                                             key_ratio(transpose_key), _p(tot.f0_map_status[first:first + n])))
+                                             n, fs, None if opts.f0_stats is None else opts.f0_stats.data_ptr(),
+                                             key_ratio(opts.transpose_key), _p(tot.f0_map_status[first:first + n])))
                 src_f0 = mapped
             self.mcd_frames = [torch.empty(c, **f64) for c in cap] if per_frame else [None] * n
             jobs = []
@@ -698,13 +696,13 @@ class ConvertPipeline(_Graphed):
 
 
 def _mlpg_em(mlpg_em):
-    """the option of the EM trajectory conversion, checked before anything is put on the device: None (one arg-max
-    mixture per frame) or the count of re-estimations as an int within [0, 16] (KWY_MLPG_EM_MAX)"""
-    if mlpg_em is None:
-        return None
-    if isinstance(mlpg_em, bool) or int(mlpg_em) != mlpg_em or not 0 <= int(mlpg_em) <= 16:
-        raise ValueError(f'mlpg_em must be None or an integer within [0, 16], not {mlpg_em!r}')
-    return int(mlpg_em)
+    """the option of the EM trajectory conversion as `ConvertOptions.check` leaves it: None or an int within [0, 16]"""
+    return ConvertOptions(mlpg_em=mlpg_em).check(0).mlpg_em
+
+
+def _postfilter_beta(beta):
+    """the strength of the formant emphasis as `ConvertOptions.check` leaves it: a float within [0, 1]"""
+    return ConvertOptions(postfilter_beta=beta).check(0).postfilter_beta
 
 
 def _convert_jobs(rows, mlpg_em=None, gvgen=None):
@@ -719,7 +717,7 @@ def _convert_jobs(rows, mlpg_em=None, gvgen=None):
 
 def _convert_mcep_batch(handle, jobs, n, order, M, model, mlpg_em=None, gvgen=None, offset=0, status=None):
     """kwy_convert_mcep_batch_dev over `_convert_jobs(rows, mlpg_em, gvgen)`, kwy_convert_mcep_em_batch_dev when mlpg_em
-    is set, kwy_convert_mcep_gv_batch_dev when gvgen (`_gvgen_on_device`) is: -> the return code.  offset: 1 for a
+    is set, kwy_convert_mcep_gv_batch_dev when gvgen (`ConvertOptions.upload`) is: -> the return code.  offset: 1 for a
     model prepared with diff = 1 (the variance is that of trajectory + source); status: n int32 words on the device"""
     if gvgen is not None:
         return lib.kwy_convert_mcep_gv_batch_dev(handle, jobs, n, order, M, _p(model), -1 if mlpg_em is None else mlpg_em,
@@ -730,34 +728,6 @@ def _convert_mcep_batch(handle, jobs, n, order, M, model, mlpg_em=None, gvgen=No
     return lib.kwy_convert_mcep_em_batch_dev(handle, jobs, n, order, M, _p(model), mlpg_em)
 
 
-def _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order, dev, on=True):
-    """the options of the GV-considering parameter generation, checked before anything is put on the device: -> None
-    (mlpg_gv is None, or on=False: no conversion), or dict(iterations, weight, mean, var) with the statistics of
-    c1..cN (`order` values each) as device tensors.  gv_stats / gv_var: the order + 1 values of
-    MelCepstrumFeatureConverter.gv_stats / .gv_var"""
-    if mlpg_gv is None or not on:
-        return None
-    from .backend import gv as gvgen
-    if gv_strength:
-        raise ValueError('mlpg_gv does not go with gv_strength > 0: the postfilter would repair the same variance twice')
-    if ms_strength:
-        raise ValueError('mlpg_gv does not go with ms_strength > 0: composing it with the modulation-spectrum filter is '
-                         'left for later')
-    if gv_stats is None or gv_var is None:
-        raise ValueError('mlpg_gv needs gv_stats and gv_var (retrain the converter with gv_stats=True on two or more '
-                         'utterances)')
-    host = [v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64) for v in (gv_stats, gv_var)]
-    if any(v.shape != (order + 1,) for v in host):
-        raise ValueError(f'mlpg_gv: gv_stats and gv_var must be {order + 1} float64 values each')
-    if not (host[1][1:] > 0).all():
-        raise ValueError('mlpg_gv: the variance of the global variance is not positive everywhere (retrain the converter '
-                         'with gv_stats=True on two or more utterances)')
-    mean, var, iterations, weight = gvgen.ascent_arguments(np.ascontiguousarray(host[0][1:]),
-                                                           np.ascontiguousarray(host[1][1:]), mlpg_gv, gv_weight, order)
-    return dict(iterations=iterations, weight=weight, mean=to_device(mean, dev, dtype=np.float64).to(dev),
-                var=to_device(var, dev, dtype=np.float64).to(dev))
-
-
 def _check_gvgen_status(status):
     bad = [i for i, v in enumerate(status.tolist() if hasattr(status, 'tolist') else status) if v]
     if bad:
@@ -765,45 +735,96 @@ def _check_gvgen_status(status):
                          f'variance is not finite, or a statistic is not finite or not positive there')
 
 
-def _gv_on_device(gv_stats, gv_strength, order, dev, on=True):
-    """the options of the global-variance postfilter, checked before anything is put on the device: -> the order + 1
-    statistics as a device tensor, or None when nothing is filtered (strength 0, or on=False: no conversion)"""
-    if not 0.0 <= float(gv_strength) <= 1.0:
-        raise ValueError(f'global variance: strength {gv_strength!r} is outside [0, 1]')
-    if not (on and gv_strength > 0):
-        return None
-    if gv_stats is None:
-        raise ValueError('global variance: gv_strength > 0 needs gv_stats')
-    gv = to_device(gv_stats, dev, dtype=np.float64).to(dev)     # (.to: a tensor may come from the host)
-    if gv.shape != (order + 1,) or gv.dtype != torch.float64:
-        raise ValueError(f'global variance: gv_stats must be {order + 1} float64 values')
-    return gv
+class _McFilter:
+    """A filter of a wave's converted mel-cepstra `conv` as one unit: its buffers, its jobs over the plain rows and --
+    with `diff_rows`, the rows of the differential conversion -- over those, `words` status words per utterance (the
+    plain conversion's, then the differential one's), `prepare` and `launch` on the main stream.  early: the filter
+    changes the plain rows in place and the differential rows take that change (the jobs' base is `conv`), so they are
+    filtered right before the plain ones; otherwise after the rendering."""
+
+    def prepare(self, chk, h):
+        pass
 
 
-def _ms_on_device(ms_stats, ms_length, ms_strength, order, dev, on=True):
-    """the options of the modulation-spectrum postfilter, checked before anything is put on the device: -> the (G, N)
-    statistics, (order + 1, ms_length / 2 + 1, 3) each, as device tensors, or None when nothing is filtered (strength 0,
-    or on=False: no conversion)"""
-    if not 0.0 <= float(ms_strength) <= 1.0:
-        raise ValueError(f'modulation spectrum: strength {ms_strength!r} is outside [0, 1]')
-    if not (on and ms_strength > 0):
-        return None
-    if ms_stats is None or len(ms_stats) != 2:
-        raise ValueError('modulation spectrum: ms_strength > 0 needs ms_stats, the (G, N) pair of a trained converter')
-    pair = tuple(to_device(v, dev, dtype=np.float64).to(dev).contiguous() for v in ms_stats)
-    length = 2 * (pair[0].shape[1] - 1) if pair[0].dim() == 3 else None
-    if ms_length is not None and int(ms_length) != length:
-        raise ValueError(f'modulation spectrum: ms_stats are of length {length}, not ms_length = {ms_length}')
-    for v in pair:
-        if v.shape != (order + 1, (length or 0) // 2 + 1, 3) or v.dtype != torch.float64:
-            raise ValueError(f'modulation spectrum: ms_stats must be two ({order + 1}, L/2 + 1, 3) float64 arrays')
-    return pair
+class _MsFilter(_McFilter):
+    """The modulation-spectrum postfilter (kwy_ms_postfilter_batch_dev on c1..cN, in place)"""
+    kind, early, words = 'ms', True, 1
+
+    def __init__(self, pair, strength, conv, T, diff_rows, dev):
+        from .backend import ms as msfilter
+        self.pair, self.strength, self.n, self.cols = pair, strength, len(T), pair[0].shape[0]
+        self.length = 2 * (pair[0].shape[1] - 1)
+        msfilter._fits(T, self.length)
+        self.status = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.jobs, self.jobs_diff = (None if out is None else _lib.job_array(
+            _lib.MsJob, [(conv[i], T[i], out[i], out[i]) for i in range(self.n)]) for out in (conv, diff_rows))
+
+    def launch(self, chk, h, differential=False):
+        chk(lib.kwy_ms_postfilter_batch_dev(h, self.jobs_diff if differential else self.jobs, self.n, self.cols, 1,
+                                            self.length, _p(self.pair[0]), _p(self.pair[1]), self.strength,
+                                            None if differential else _p(self.status)))
 
 
-def _f0_stats_on_device(f0_stats, dev):
-    """(mu_src, sigma_src, mu_tgt, sigma_tgt) as 4 doubles on the device (a 4-tuple, or such a tensor already), or None"""
-    return None if f0_stats is None else torch.as_tensor(f0_stats if torch.is_tensor(f0_stats) else list(f0_stats),
-                                                         dtype=torch.float64, device=dev)
+class _GvFilter(_McFilter):
+    """The global-variance postfilter (kwy_column_moments_batch_dev, then kwy_gv_postfilter_batch_dev on c1..cN, in
+    place).  status: the caller's words instead of its own"""
+    kind, early, words = 'gv', True, 1
+
+    def __init__(self, gv, strength, conv, T, diff_rows, dev, status=None):
+        self.gv, self.strength, self.n, self.cols = gv, strength, len(T), gv.numel()
+        self.moments = torch.empty((self.n, self.cols, 3), dtype=torch.float64, device=dev)
+        self.status = status if status is not None else torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.j_mom = _lib.job_array(_lib.GvMatrix, [(conv[i], T[i]) for i in range(self.n)])
+        self.jobs, self.jobs_diff = (None if out is None else _lib.job_array(
+            _lib.GvJob, [(conv[i], T[i], self.moments[i], out[i], out[i]) for i in range(self.n)])
+            for out in (conv, diff_rows))
+
+    def prepare(self, chk, h):
+        chk(lib.kwy_column_moments_batch_dev(h, self.j_mom, self.n, self.cols, _p(self.moments)))
+
+    def launch(self, chk, h, differential=False):
+        chk(lib.kwy_gv_postfilter_batch_dev(h, self.jobs_diff if differential else self.jobs, self.n, self.cols, 1,
+                                            _p(self.gv), self.strength, None if differential else _p(self.status)))
+
+
+class _PowerFilter(_McFilter):
+    """The formant emphasis / the power-preserving c0 on the ABSOLUTE converted rows, last of the filters
+    (kwy_mcep_postfilter_batch_dev).  The plain conversion in place; the differential
+    one as the base of source + differential (`mc` + `mc_diff` into a block of its own, column 0 of `mc_diff` zeroed
+    first: it then carries the difference of c0, and the differential filter reads it).  env: the source's rows, whose
+    frame energies keep_power restores"""
+    kind, early = 'power', False
+
+    def __init__(self, beta, keep_power, conv, env, T, diff_rows, rows, mc, mc_diff, scalars, dev):
+        self.beta, self.n, self.scalars, self.mc, self.mc_diff = beta, len(T), scalars, mc, mc_diff      # scalars: order, alpha, fft
+        self.words = 1 if diff_rows is None else 2
+        self.status = torch.zeros(self.words * self.n, dtype=torch.int32, device=dev)
+        ref = env if keep_power else [None] * self.n
+        self.jobs = _lib.job_array(_lib.McPowerJob, [(conv[i], ref[i], None, conv[i], T[i]) for i in range(self.n)])
+        if diff_rows is not None:
+            self.mc_abs = torch.empty_like(mc)
+            absolute = rows.views(self.mc_abs)
+            self.jobs_diff = _lib.job_array(_lib.McPowerJob, [(absolute[i], ref[i], diff_rows[i], diff_rows[i], T[i])
+                                                              for i in range(self.n)])
+
+    def launch(self, chk, h, differential=False):
+        if differential:
+            self.mc_diff[:, 0] = 0.0
+            torch.add(self.mc, self.mc_diff, out=self.mc_abs)
+        words = self.status[self.n:] if differential else self.status[:self.n]
+        chk(lib.kwy_mcep_postfilter_batch_dev(h, self.jobs_diff if differential else self.jobs, self.n, *self.scalars,
+                                              self.beta, _p(words)))
+
+
+# All that the MLSA pass behind the last wave of a batch reads of a wave: its MlsaJob rows (inputs, differential
+# mel-cepstra, outputs), `finish` -- None, or (the FinishJob array of the outputs, their count, the block of 16-bit samples
+# it points into) -- and the filter's scalars
+_DeferredMlsa = namedtuple('_DeferredMlsa', 'rows finish alpha hop ignore_c0')
+
+
+def _finish_diff(ctx, jobs, n, fs):
+    """Wavdata.save's normalisation of `n` filtered waveforms (a filtered waveform has no synthesis post-step)"""
+    _lib.check(ctx, lib.kwy_finish_pcm16_batch_dev(ctx.handle, jobs, n, fs, 0, PIECE_CEILING, 1, PIECE_CEILING))
 
 
 class ConvertWave:
@@ -820,56 +841,30 @@ class ConvertWave:
     `pcm[i]` int16 views, 2 bytes per sample to download.  diff=True (with a GMM): also the DIFFERENTIAL output of
     every file -- the input waveform through the MLSA filter of the differential conversion, convert(diffvc=True),
     /root/reference/kwiiyatta/convert_voice.py:19,39-40, filter/mlsa.py:9-30 -- as `wave_diff[i]` (and `pcm_diff[i]`:
-    Wavdata.save's normalisation only, a filtered waveform has no synthesis post-step).  f0_stats (mu_src, sigma_src,
-    mu_tgt, sigma_tgt: a 4-tuple or 4 doubles on the device) and / or transpose_key != 0: the synthesis runs on the
-    analysed f0 mapped by kwy_f0_map_batch_dev (into `f0_synth`; CheapTrick and D4C keep the analysed track), and
-    `f0_map_status` holds a word per utterance (non-zero: frames out of range, backend.f0.map_f0's limit).
-    gv_strength > 0 (with a GMM and gv_stats, the order + 1 values of MelCepstrumFeatureConverter.gv_stats as an array
-    or on the device): the converted mel-cepstra through the global-variance postfilter right after the conversion
-    (kwy_column_moments_batch_dev, kwy_gv_postfilter_batch_dev on c1..cN, in place); with diff=True the differential
-    conversion then runs early and takes the filter's change of the plain conversion BEFORE that one is filtered in
-    place.  `gv_status` holds a word per utterance (non-zero: coefficients left unfiltered, backend.gv.postfilter).
-    ms_strength > 0 (with a GMM and ms_stats, the (G, N) pair of MelCepstrumFeatureConverter.ms_stats, of transform
-    length ms_length): the converted mel-cepstra through the modulation-spectrum postfilter between the conversion and
-    the global-variance filter (kwy_ms_postfilter_batch_dev on c1..cN, in place; the differential conversion takes the
-    filter's change of the plain one first, as with gv).  `ms_status` holds a word per utterance (non-zero: bins left
-    unfiltered, backend.ms.postfilter); an utterance of more than ms_length frames is a ValueError.
-    formant_ratio != 1 (within [0.5, 2]): the envelopes the rendering reads -- the converted ones, without a GMM the
-    analysed ones -- warped along frequency right before it, all rows of the wave in ONE in-place call
-    (kwy_formant_shift_dev, backend.formant); `formant_status` holds one word for the wave (non-zero: rows left as they
-    are).  The differential output is not touched.  At 1 no kernel is launched and no buffer added.
-    mlpg_em=N (with a GMM; an integer within [0, 16]): both conversions, plain and differential, are EM trajectory
-    conversions over soft mixture posteriors with N re-estimations (kwy_convert_mcep_em_batch_dev) instead of one
-    arg-max mixture per frame; everything after them runs as it does otherwise.
-    mlpg_gv=N (with a GMM, gv_stats and gv_var; an integer within [0, 256]): both conversions with the GV ascent behind
-    them (kwy_convert_mcep_gv_batch_dev; N conjugate-gradient steps, gv_weight weighs the GV term), the differential
-    one on the variance of differential + source.  `gvgen_status` holds two words per utterance (plain, then
-    differential; non-zero: coefficients left at the maximum-likelihood track).  Not with gv_strength or ms_strength.
-    diff_filter='fft' (with diff=True): `wave_diff[i]` through the frame-parallel FFT form of the differential filter
-    (kwy_mcep_filter_fft_batch_dev over the MLSA filter's jobs: one workgroup per frame, launched with the wave, so
-    defer_mlsa has nothing to defer) instead of the MLSA recursion; 'mlsa' (default) is that recursion, unchanged.
-    postfilter_beta > 0 (within [0, 1]) and / or keep_power (with a GMM): the absolute converted mel-cepstra through
-    kwy_mcep_postfilter_batch_dev after every other filter -- the formant emphasis, c0 shifted to the energy of the
-    source frame (keep_power) or of the unfiltered converted frame; the plain conversion in place, the differential one
-    as the base of source + differential, its column 0 then the change of c0, which the differential filters take into
-    account (ignore_c0 = 0).  `power_status` holds a word per utterance (two with diff=True: plain, then differential;
-    non-zero: frames left unfiltered, backend.power.postfilter).  With both neutral no kernel is launched."""
+    Wavdata.save's normalisation only).  defer_mlsa=True: the caller launches the MLSA recursions of several waves
+    together, from their `deferred()` records.
 
+    **options: the keywords of `ConvertOptions`, which describes each; resolved: `ConvertOptions.upload`'s result instead,
+    as a driver hands it to all its waves.  What the wave adds to them:
+    the mapped f0 is `f0_synth`; the status words to read back -- all None when their option is off -- are
+    `f0_map_status`, `gv_status`, `ms_status` (a word per utterance), `formant_status` (one word for the wave),
+    `gvgen_status` and with diff=True `power_status` (two words per utterance: the plain conversion's, then the
+    differential one's); `status_words()` lists them.
+    The filters of the converted mel-cepstra run in the order MS, GV, power / emphasis (`filters`: a unit each, see
+    `_McFilter`).  The differential conversion has ONE place: right before the first filter that changes the plain
+    conversion in place (MS or GV; it then has no GV ascent and offset 0, and takes those filters' changes of the plain
+    conversion before the plain rows are overwritten), and without such a filter after the rendering (with the ascent
+    options, offset 1).  With formant_ratio = 1, and with the power filter's options both neutral, no kernel is launched
+    and no buffer added."""
+
+    @takes_options()
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
-                 f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                 ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0,
-                 diff_filter='mlsa', postfilter_beta=0.0, keep_power=False):
-        self.diff_filter = _diff_filter(diff_filter)
-        self.postfilter_beta, self.keep_power = _postfilter_beta(postfilter_beta), bool(keep_power)
-        self.mlpg_em = _mlpg_em(mlpg_em) if gmm is not None else None
-        self.gvgen = _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order, ls.dev,
-                                      on=gmm is not None)
-        self.gvgen_status = None
+                 resolved=None, **options):
+        converting = gmm is not None
+        opts = resolved or ConvertOptions(**options).check(order, converting).upload(ls.dev, converting)
+        self.opts, self.mlpg_em, self.gvgen, self.gvgen_status = opts, opts.mlpg_em, opts.gvgen, None
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
-        self.diff = bool(diff) and gmm is not None
-        self.defer_mlsa = bool(defer_mlsa)       # the caller launches the MLSA recursions of several waves together
-        from .backend import formant
-        self.formant_ratio, self.formant_status = formant.check_ratio(formant_ratio), None
+        self.diff, self.defer_mlsa, self.formant_status = bool(diff) and converting, bool(defer_mlsa), None
         self.wav_in = len(utterances) > 0 and not isinstance(utterances[0], (tuple, list))
         dev = ls.dev
         self.fft = lib.kwy_cheaptrick_fft_size(self.fs, 71.0)
@@ -880,7 +875,7 @@ class ConvertWave:
         self.n = n = len(utterances)
         f64 = dict(dtype=torch.float64, device=dev)
         with torch.cuda.stream(ls.main):
-            self.model = gmm.model(diff=False) if gmm is not None else None
+            self.model = gmm.model(diff=False) if converting else None
             both = (ls.main, ls.side)           # the inputs: both streams may use them after the caller has dropped them
             if self.wav_in:
                 self.x = [to_device(u, dev, both) for u in utterances]
@@ -898,7 +893,7 @@ class ConvertWave:
             self.rows = rows.total
             # (with a GMM nothing reads the analysed envelopes but sp2mc: CheapTrick hands over mel-cepstra instead,
             # kwy_cheaptrick_mcep_batch_dev)
-            self.sp_all = torch.empty((self.rows, K), **f64) if gmm is None else None
+            self.sp_all = torch.empty((self.rows, K), **f64) if not converting else None
             self.ap_all = torch.empty((self.rows, K), **f64)
             self.ylen = [int(lib.kwy_synth_length(t, self.frame_period, self.fs)) for t in self.T]
             out = Ragged(self.ylen)
@@ -912,30 +907,29 @@ class ConvertWave:
                                                              for i in range(n)])
             self.plan = [torch.empty(int(lib.kwy_synth_plan_bytes(y)), dtype=torch.uint8, device=dev) for y in self.ylen]
             self.f0_synth, self.f0_map_status = self.f0, None
-            self.transpose_key = float(transpose_key)
-            if f0_stats is not None or self.transpose_key != 0:
-                self.f0_stats = _f0_stats_on_device(f0_stats, dev)
+            if opts.f0_map:
                 self.f0_synth_all = torch.empty(self.rows, **f64)
                 self.f0_synth = rows.views(self.f0_synth_all)
                 self.f0_map_status = torch.zeros(n, dtype=torch.int32, device=dev)
                 self.j_map = _lib.job_array(_lib.F0MapJob, [(self.f0[i], self.T[i], self.f0_synth[i]) for i in range(n)])
-            if gmm is not None:
+            if converting:
                 assert gmm.D2 == 6 * order
                 self.mc = torch.empty((self.rows, order + 1), **f64)
             # CheapTrick's rows (envelopes, or mel-cepstra for the conversion) and the rows the rendering reads
-            env, ap = rows.views(self.sp_all if gmm is None else self.mc), rows.views(self.ap_all)
+            env, ap = rows.views(self.mc if converting else self.sp_all), rows.views(self.ap_all)
             spec = env
             self.j_env = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], env[i]) for i in range(n)])
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], ap[i]) for i in range(n)])
             self.j_plan = _lib.job_array(_lib.SynthPlanJob, [(self.f0_synth[i], self.T[i], self.ylen[i], self.plan[i])
                                                              for i in range(n)])
-            if gmm is not None:
+            if converting:
                 self.mc_conv = torch.empty((self.rows, order + 1), **f64)
                 self.sp_conv = torch.empty((self.rows, K), **f64)
                 conv, spec = rows.views(self.mc_conv), rows.views(self.sp_conv)
                 self.j_conv = _convert_jobs([(env[i], self.T[i], conv[i]) for i in range(n)], self.mlpg_em, self.gvgen)
                 if self.gvgen is not None:
                     self.gvgen_status = torch.zeros(2 * n, dtype=torch.int32, device=dev)
+            self.mc_diff = self.mc_diff_rows = None
             if self.diff:
                 self.model_diff = gmm.model(diff=True)
                 self.mc_diff = torch.empty((self.rows, order + 1), **f64)
@@ -945,10 +939,12 @@ class ConvertWave:
                 samples = Ragged([v.numel() for v in self.x])         # the filtered inputs: as long as the inputs
                 self.wave_diff_all = torch.empty(samples.total, **f64)
                 self.wave_diff = samples.views(self.wave_diff_all)
-                self.j_mlsa = _lib.job_array(_lib.MlsaJob, [(self.x[i], self.x[i].numel(), self.mc_diff_rows[i], self.T[i],
-                                                            self.wave_diff[i]) for i in range(n)])
+                # (as rows too, for ONE launch over the utterances of several waves: a recursion occupies one wavefront
+                # for 0.6 us per sample whatever else runs, so all files of a batch should recurse side by side)
+                self.mlsa = [(self.x[i], self.x[i].numel(), self.mc_diff_rows[i], self.T[i], self.wave_diff[i]) for i in range(n)]
+                self.j_mlsa = _lib.job_array(_lib.MlsaJob, self.mlsa)
                 self.hop = int(self.fs * (self.frame_period * 0.001))
-                if self.diff_filter == 'fft':
+                if opts.diff_filter == 'fft':
                     from .backend import fftfilt
                     self.diff_fft = fftfilt.fft_filter_size(self.fs, self.hop)
                 self.pcm_diff = None
@@ -957,51 +953,34 @@ class ConvertWave:
                     self.pcm_diff = samples.views(self.pcm_diff_all)
                     self.j_fin_diff = _lib.job_array(_lib.FinishJob, [(self.wave_diff[i], self.x[i].numel(), 0, self.pcm_diff[i])
                                                                       for i in range(n)])
-            self.gv_status, self.gv_strength = None, float(gv_strength)
-            self.gv = _gv_on_device(gv_stats, gv_strength, order, dev, on=gmm is not None)
-            if self.gv is not None:
-                self.gv_moments = torch.empty((n, order + 1, 3), **f64)
-                self.gv_status = torch.zeros(n, dtype=torch.int32, device=dev)
-                self.j_gv_mom = _lib.job_array(_lib.GvMatrix, [(conv[i], self.T[i]) for i in range(n)])
-                self.j_gv = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], conv[i], conv[i])
-                                                        for i in range(n)])
-                if self.diff:
-                    self.j_gv_diff = _lib.job_array(_lib.GvJob, [(conv[i], self.T[i], self.gv_moments[i], self.mc_diff_rows[i],
-                                                                  self.mc_diff_rows[i]) for i in range(n)])
-            self.ms_status, self.ms_strength = None, float(ms_strength)
-            self.ms = _ms_on_device(ms_stats, ms_length, ms_strength, order, dev, on=gmm is not None)
-            if self.ms is not None:
-                from .backend import ms as msfilter
-                self.ms_length = 2 * (self.ms[0].shape[1] - 1)
-                msfilter._fits(self.T, self.ms_length)
-                self.ms_status = torch.zeros(n, dtype=torch.int32, device=dev)
-                self.j_ms = _lib.job_array(_lib.MsJob, [(conv[i], self.T[i], conv[i], conv[i]) for i in range(n)])
-                if self.diff:
-                    self.j_ms_diff = _lib.job_array(_lib.MsJob, [(conv[i], self.T[i], self.mc_diff_rows[i],
-                                                                  self.mc_diff_rows[i]) for i in range(n)])
-            # the formant emphasis / the power-preserving c0 on the ABSOLUTE converted rows, last of the filters: the plain
-            # conversion in place; the differential one as base of source + differential (its column 0 zeroed first: it
-            # then carries the difference of c0, and the differential filter reads it)
-            self.power_status = None
-            if gmm is not None and (self.postfilter_beta > 0 or self.keep_power):
-                self.power_status = torch.zeros((2 if self.diff else 1) * n, dtype=torch.int32, device=dev)
-                ref = env if self.keep_power else [None] * n
-                self.j_power = _lib.job_array(_lib.McPowerJob, [(conv[i], ref[i], None, conv[i], self.T[i])
-                                                                for i in range(n)])
-                if self.diff:
-                    self.mc_abs = torch.empty((self.rows, order + 1), **f64)
-                    absolute = rows.views(self.mc_abs)
-                    self.j_power_diff = _lib.job_array(_lib.McPowerJob, [(absolute[i], ref[i], self.mc_diff_rows[i],
-                                                                          self.mc_diff_rows[i], self.T[i])
-                                                                         for i in range(n)])
+            self.filters = []
+            if converting:
+                if opts.ms is not None:
+                    self.filters.append(_MsFilter(opts.ms, opts.ms_strength, conv, self.T, self.mc_diff_rows, dev))
+                if opts.gv is not None:
+                    self.filters.append(_GvFilter(opts.gv, opts.gv_strength, conv, self.T, self.mc_diff_rows, dev))
+                if opts.power:
+                    self.filters.append(_PowerFilter(opts.postfilter_beta, opts.keep_power, conv, env, self.T,
+                                                     self.mc_diff_rows, rows, self.mc, self.mc_diff,
+                                                     (order, self.alpha, self.fft), dev))
+            status = {f.kind: f.status for f in self.filters}
+            self.ms_status, self.gv_status, self.power_status = (status.get(kind) for kind in ('ms', 'gv', 'power'))
+            # the ONE place of the differential conversion: in front of this filter, or (None) after the rendering
+            self.diff_before = next((f for f in self.filters if f.early), None) if self.diff else None
             self.ignore_c0 = 0 if self.power_status is not None else 1
             self.j_render = _lib.synth_job_array([(self.plan[i], spec[i], ap[i], self.wave[i]) for i in range(n)])
-            if self.formant_ratio != 1:
+            if opts.formant_ratio != 1:
                 self.formant_status = torch.zeros(1, dtype=torch.int32, device=dev)
         self.frames = int(sum(self.T))
 
+    def status_words(self):
+        """(kind, device words, words per utterance) of every status the wave's options write"""
+        own = [('dio', self.f0_status, 1), ('f0_map', self.f0_map_status, 1), ('formant', self.formant_status, 1),
+               ('gvgen', self.gvgen_status, 2)] + [(f.kind, f.status, f.words) for f in self.filters]
+        return [item for item in own if item[1] is not None]
+
     def run(self):
-        ls, fs, fft, K, order, n = self.ls, self.fs, self.fft, self.K, self.order, self.n
+        ls, fs, fft, K, order, n, opts = self.ls, self.fs, self.fft, self.K, self.order, self.n, self.opts
         if self.wav_in:
             with torch.cuda.stream(ls.main):
                 _lib.check(ls.ctx, lib.kwy_dio_batch_dev(ls.ctx.handle, self.j_dio, n, fs, 71.0, 800.0, 2.0,
@@ -1014,8 +993,8 @@ class ConvertWave:
             if self.f0_map_status is not None:
                 from .backend.f0 import key_ratio
                 _lib.check(ls.side_ctx, lib.kwy_f0_map_batch_dev(
-                    hs, self.j_map, n, fs, None if self.f0_stats is None else self.f0_stats.data_ptr(),
-                    key_ratio(self.transpose_key), self.f0_map_status.data_ptr()))
+                    hs, self.j_map, n, fs, None if opts.f0_stats is None else opts.f0_stats.data_ptr(),
+                    key_ratio(opts.transpose_key), self.f0_map_status.data_ptr()))
             _lib.check(ls.side_ctx, lib.kwy_synth_plan_batch_dev(hs, self.j_plan, n, fft, self.frame_period, fs))
         with torch.cuda.stream(ls.main):
             h = ls.ctx.handle
@@ -1026,33 +1005,17 @@ class ConvertWave:
                 chk(lib.kwy_cheaptrick_mcep_batch_dev(h, self.j_env, n, fs, -0.15, 71.0, fft, float(fs), order, self.alpha))
                 chk(_convert_mcep_batch(h, self.j_conv, n, order, self.gmm.M, self.model, self.mlpg_em, self.gvgen, 0,
                                         None if self.gvgen is None else self.gvgen_status[:n]))
-                cols = order + 1
-                # the differential coefficients take a filter's change of the plain conversion, which the filter of the
-                # plain conversion (in place) then overwrites: the differential conversion in front of the first filter
-                # that runs, on one stream
-                if self.ms_status is not None:
-                    stats = (self.ms_length, _p(self.ms[0]), _p(self.ms[1]), self.ms_strength)
-                    if self.diff:
-                        chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em))
-                        chk(lib.kwy_ms_postfilter_batch_dev(h, self.j_ms_diff, n, cols, 1, *stats, None))
-                    chk(lib.kwy_ms_postfilter_batch_dev(h, self.j_ms, n, cols, 1, *stats, _p(self.ms_status)))
-                if self.gv_status is not None:
-                    chk(lib.kwy_column_moments_batch_dev(h, self.j_gv_mom, n, cols, _p(self.gv_moments)))
-                    if self.diff:
-                        if self.ms_status is None:
-                            chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff,
-                                                    self.mlpg_em))
-                        chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv_diff, n, cols, 1, _p(self.gv), self.gv_strength,
-                                                            None))
-                    chk(lib.kwy_gv_postfilter_batch_dev(h, self.j_gv, n, cols, 1, _p(self.gv), self.gv_strength,
-                                                        _p(self.gv_status)))
-                if self.power_status is not None:
-                    chk(lib.kwy_mcep_postfilter_batch_dev(h, self.j_power, n, order, self.alpha, fft, self.postfilter_beta,
-                                                          _p(self.power_status[:n])))
+                for f in self.filters:
+                    f.prepare(chk, h)
+                    if self.diff and f.early:
+                        if f is self.diff_before:
+                            self._convert_diff(chk, h, late=False)
+                        f.launch(chk, h, differential=True)
+                    f.launch(chk, h)
                 chk(lib.kwy_mc2sp_dev(h, _p(self.mc_conv), self.rows, order, self.alpha, fft, _p(self.sp_conv)))
             if self.formant_status is not None:     # the rows the rendering reads, warped in place
                 rendered = self.sp_all if self.gmm is None else self.sp_conv
-                chk(lib.kwy_formant_shift_dev(h, _p(rendered), self.rows, K, self.formant_ratio, _p(rendered),
+                chk(lib.kwy_formant_shift_dev(h, _p(rendered), self.rows, K, opts.formant_ratio, _p(rendered),
                                               _p(self.formant_status)))
             ls.main.wait_stream(ls.side)
             chk(lib.kwy_synth_render_batch_dev(h, self.j_render, n, fft, self.frame_period, fs, float(fs)))
@@ -1061,137 +1024,111 @@ class ConvertWave:
             if self.diff:
                 # the differential conversion of the same mel-cepstra, its filter over the INPUT waveforms: all
                 # utterances' recursions side by side (one wavefront each)
-                if self.gv_status is None and self.ms_status is None:           # (with a postfilter it ran above)
-                    chk(_convert_mcep_batch(h, self.j_conv_diff, n, order, self.gmm.M, self.model_diff, self.mlpg_em,
-                                            self.gvgen, 1, None if self.gvgen is None else self.gvgen_status[n:]))
-                if self.power_status is not None:
-                    self.mc_diff[:, 0] = 0.0
-                    torch.add(self.mc, self.mc_diff, out=self.mc_abs)
-                    chk(lib.kwy_mcep_postfilter_batch_dev(h, self.j_power_diff, n, order, self.alpha, fft,
-                                                          self.postfilter_beta, _p(self.power_status[n:])))
-                if self.diff_filter == 'fft':       # every frame of every file in one grid: nothing to defer
-                    self.run_fft_filter(ls.ctx)
-                elif not self.defer_mlsa:
-                    self.run_mlsa(ls.ctx)
+                if self.diff_before is None:
+                    self._convert_diff(chk, h, late=True)
+                for f in self.filters:
+                    if not f.early:
+                        f.launch(chk, h, differential=True)
+                if opts.diff_filter == 'fft' or not self.defer_mlsa:
+                    self.filter_diff(ls.ctx)
 
-    def mlsa_rows(self):
-        """the wave's MLSA jobs as rows (for ONE launch over the utterances of several waves: a recursion occupies one
-        wavefront for 0.6 us per sample whatever else runs, so all files of a batch should recurse side by side)"""
-        return [(self.x[i], self.x[i].numel(), self.mc_diff_rows[i], self.T[i], self.wave_diff[i]) for i in range(self.n)]
+    def _convert_diff(self, chk, h, late):
+        """the differential conversion; late (behind the rendering): with the GV ascent, on the variance of
+        differential + source (offset 1)"""
+        gvgen = self.gvgen if late else None
+        chk(_convert_mcep_batch(h, self.j_conv_diff, self.n, self.order, self.gmm.M, self.model_diff, self.mlpg_em, gvgen,
+                                int(late), None if gvgen is None else self.gvgen_status[self.n:]))
 
-    def run_mlsa(self, ctx):
-        chk = lambda rc: _lib.check(ctx, rc)  # noqa: E731
-        chk(lib.kwy_mlsa_filter_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, 4, self.hop,
-                                          self.ignore_c0))
-        self.finish_diff(ctx)
+    def deferred(self):
+        """what a deferred MLSA pass needs of the wave, and nothing else of it"""
+        return _DeferredMlsa(self.mlsa, None if self.pcm_diff is None else (self.j_fin_diff, self.n, self.pcm_diff_all),
+                             self.alpha, self.hop, self.ignore_c0)
 
-    def run_fft_filter(self, ctx):
-        """the wave's differential outputs through the frame-parallel FFT filter (the jobs of the MLSA filter as they are)"""
-        _lib.check(ctx, lib.kwy_mcep_filter_fft_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, self.hop,
-                                                          self.diff_fft, self.ignore_c0))
-        self.finish_diff(ctx)
-
-    def finish_diff(self, ctx):
+    def filter_diff(self, ctx):
+        """the wave's differential outputs: the MLSA recursions, or the frame-parallel FFT filter over the same jobs
+        (every frame of every file in one grid: nothing to defer), and their post-step"""
+        if self.opts.diff_filter == 'fft':
+            _lib.check(ctx, lib.kwy_mcep_filter_fft_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha,
+                                                              self.hop, self.diff_fft, self.ignore_c0))
+        else:
+            _lib.check(ctx, lib.kwy_mlsa_filter_batch_dev(ctx.handle, self.j_mlsa, self.n, self.order, self.alpha, 4,
+                                                          self.hop, self.ignore_c0))
         if self.pcm_diff is not None:
-            _lib.check(ctx, lib.kwy_finish_pcm16_batch_dev(ctx.handle, self.j_fin_diff, self.n, self.fs, 0, PIECE_CEILING, 1,
-                                                           PIECE_CEILING))
+            _finish_diff(ctx, self.j_fin_diff, self.n, self.fs)
 
 
-def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, wave_size=16, pcm=False, diff=False,
-                    f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None,
-                    ms_strength=0.0, formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0,
-                    diff_filter='mlsa', postfilter_beta=0.0, keep_power=False):
+_STATUS_KINDS = ('dio', 'f0_map', 'gv', 'ms', 'formant', 'gvgen', 'power')
+
+
+def _check_dio_status(status):
+    if bool(status.any()):
+        bad = torch.nonzero(status).flatten().tolist()
+        raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
+
+
+def _check_status_words(items, fs):
+    """The status words of a batch's waves, read back ONCE: items are the waves' (kind, device words, words per
+    utterance) in the order they ran; one concatenation, one copy to the host, then the kinds' checks in the order of
+    `_STATUS_KINDS` (several words per utterance: the plain conversion's of a whole wave, then the differential one's,
+    folded into one)."""
+    if not items:
+        return
+    from .backend import f0, formant, gv, ms, power
+    items = sorted(items, key=lambda item: _STATUS_KINDS.index(item[0]))        # (stable: a kind's waves stay in order)
+    host = torch.cat([w for _, w, _ in items]).cpu().split([w.numel() for _, w, _ in items])
+    folded = {}
+    for (kind, w, per), words in zip(items, host):
+        folded.setdefault(kind, []).append(words.reshape(per, w.numel() // per).sum(0))
+    checks = dict(dio=_check_dio_status, f0_map=lambda w: f0.check_status(w, fs), gv=gv.check_status, ms=ms.check_status,
+                  formant=lambda w: formant.check_status(w, what='wave(s)'), gvgen=_check_gvgen_status,
+                  power=power.check_status)
+    for kind, parts in folded.items():
+        checks[kind](torch.cat(parts))
+
+
+def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, opts, wave_size=16, pcm=False,
+                    diff=False):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
-    view, its pcm view) on the main stream, None for what was not asked for.
-    Bare waveforms get their f0 on the device; the DIO status words of all waves (and those of the f0 map and of the
-    global-variance and modulation-spectrum postfilters and of the formant shift, one per wave) are read back ONCE at the
-    end."""
+    view, its pcm view) on the main stream, None for what was not asked for.  opts: a checked `ConvertOptions`, uploaded
+    here once for all waves.
+    Bare waveforms get their f0 on the device; the status words of all waves are read back ONCE at the end
+    (`_check_status_words`)."""
     ls = ls if ls is not None else _Lockstep(device_index)
-    if ms_strength:          # (checked and uploaded once: every wave takes the device tensors as they are)
-        ms_stats = _ms_on_device(ms_stats, ms_length, ms_strength, order, ls.dev, on=gmm is not None)
-    held, status, map_status, gv_status, ms_status, formant_status, waves_diff = [], [], [], [], [], [], []
-    gvgen_status, power_status = [], []
+    resolved = opts.upload(ls.dev, converting=gmm is not None)
+    defer = bool(diff) and gmm is not None and resolved.diff_filter == 'mlsa'
+    held, deferred, status = [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
-                         diff=diff, defer_mlsa=diff and diff_filter == 'mlsa', f0_stats=f0_stats,
-                         transpose_key=transpose_key, **(dict(diff_filter=diff_filter) if diff_filter != 'mlsa' else {}),
-                         **(dict(gv_stats=gv_stats, gv_strength=gv_strength) if gv_strength else {}),
-                         **(dict(ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength) if ms_strength else {}),
-                         **(dict(formant_ratio=formant_ratio) if formant_ratio != 1 else {}),
-                         **(dict(mlpg_em=mlpg_em) if mlpg_em is not None else {}),
-                         **(dict(mlpg_gv=mlpg_gv, gv_stats=gv_stats, gv_var=gv_var, gv_weight=gv_weight)
-                            if mlpg_gv is not None else {}),
-                         **(dict(postfilter_beta=postfilter_beta, keep_power=keep_power)
-                            if postfilter_beta or keep_power else {}))
+                         diff=diff, defer_mlsa=defer, resolved=resolved)
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
                 keep(w0 + i, wv.wave[i], wv.pcm[i] if pcm else None, wv.wave_diff[i] if wv.diff else None,
                      wv.pcm_diff[i] if wv.diff and pcm else None)
-        if wv.f0_status is not None:
-            status.append(wv.f0_status)
-        if wv.f0_map_status is not None:
-            map_status.append(wv.f0_map_status)
-        if wv.gv_status is not None:
-            gv_status.append(wv.gv_status)
-        if wv.ms_status is not None:
-            ms_status.append(wv.ms_status)
-        if wv.gvgen_status is not None:
-            gvgen_status.append(wv.gvgen_status)
-        if wv.formant_status is not None:
-            formant_status.append(wv.formant_status)
-        if wv.power_status is not None:
-            power_status.append((wv.power_status, wv.n))
-        if diff and diff_filter == 'mlsa':
-            waves_diff.append(wv)            # (kept: its inputs and mel-cepstra feed the filter launch below)
+        status += wv.status_words()
+        if defer:
+            deferred.append(wv.deferred())            # (the wave itself goes when it leaves `held`)
         held.append(wv)
         while len(held) > 2:
             held.pop(0)
-    if waves_diff:
+    if deferred:
         # the differential outputs of ALL files: one pass of launches over every recursion (64 per launch; two contexts
         # alternate so that consecutive launches overlap), then their post-step
-        rows = [r for wv in waves_diff for r in wv.mlsa_rows()]
-        wv0 = waves_diff[0]
+        rows = [r for d in deferred for r in d.rows]
+        d0 = deferred[0]
         ls.side.wait_stream(ls.main)
         for k, c0 in enumerate(range(0, len(rows), 64)):
             ctx = (ls.ctx, ls.side_ctx)[k % 2]
             with torch.cuda.stream((ls.main, ls.side)[k % 2]):
                 chunk = rows[c0:c0 + 64]
                 _lib.check(ctx, lib.kwy_mlsa_filter_batch_dev(ctx.handle, _lib.job_array(_lib.MlsaJob, chunk), len(chunk), order,
-                                                              wv0.alpha, 4, wv0.hop, wv0.ignore_c0))
+                                                              d0.alpha, 4, d0.hop, d0.ignore_c0))
         ls.main.wait_stream(ls.side)
         with torch.cuda.stream(ls.main):
-            for wv in waves_diff:
-                wv.finish_diff(ls.ctx)
+            for jobs, n, _ in (d.finish for d in deferred if d.finish is not None):
+                _finish_diff(ls.ctx, jobs, n, int(fs))
     ls.sync()
-    every = status + map_status + gv_status + ms_status + formant_status
-    words = torch.cat(every).cpu() if every else None
-    n_dio = sum(v.numel() for v in status)
-    n_map = sum(v.numel() for v in map_status)
-    n_gv = sum(v.numel() for v in gv_status)
-    n_ms = sum(v.numel() for v in ms_status)
-    if status and bool(words[:n_dio].any()):
-        bad = torch.nonzero(words[:n_dio]).flatten().tolist()
-        raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
-    if map_status:
-        from .backend.f0 import check_status
-        check_status(words[n_dio:n_dio + n_map], fs)
-    if gv_status:
-        from .backend import gv as gvfilter
-        gvfilter.check_status(words[n_dio + n_map:n_dio + n_map + n_gv])
-    if ms_status:
-        from .backend import ms as msfilter
-        msfilter.check_status(words[n_dio + n_map + n_gv:n_dio + n_map + n_gv + n_ms])
-    if formant_status:
-        from .backend import formant
-        formant.check_status(words[n_dio + n_map + n_gv + n_ms:], what='wave(s)')
-    if gvgen_status:
-        # (two words per utterance of a wave: the plain conversion's, then the differential one's)
-        _check_gvgen_status(torch.cat([v.cpu()[:len(v) // 2] + v.cpu()[len(v) // 2:] for v in gvgen_status]))
-    if power_status:
-        # (with diff=True two words per utterance of a wave: the plain conversion's, then the differential one's)
-        from .backend import power
-        power.check_status(torch.cat([v.cpu().reshape(-1, n).sum(0) for v, n in power_status]))
+    _check_status_words(status, fs)
     return ls
 
 
@@ -1579,37 +1516,9 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
         s_.synchronize()
 
 
-def _postfilter_beta(beta):
-    """the strength of the formant emphasis a driver is asked for, checked"""
-    beta = float(beta)
-    if not 0.0 <= beta <= 1.0:
-        raise ValueError(f'postfilter: beta {beta!r} is outside [0, 1]')
-    return beta
-
-
-def _diff_filter(name):
-    """the differential filter a driver is asked for, checked"""
-    from .filter import DIFF_FILTERS
-    if name not in DIFF_FILTERS:
-        raise ValueError(f'differential filter: {name!r} is not one of {DIFF_FILTERS}')
-    return name
-
-
-def _formant_ratio(formant_ratio, driver, pool, who):
-    """the checked ratio of a batch driver's formant shift, before anything is put on the device: ValueError outside
-    [0.5, 2], and for any ratio but 1 on the stream driver"""
-    from .backend import formant
-    ratio = formant.check_ratio(formant_ratio)
-    if ratio != 1 and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
-        raise ValueError(f'{who}: formant_ratio needs the lockstep driver')
-    return ratio
-
-
+@takes_options()
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
-                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, f0_stats=None, transpose_key=0.0,
-                  gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0, formant_ratio=1.0,
-                  mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0, diff_filter='mlsa', postfilter_beta=0.0,
-                  keep_power=False):
+                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, **options):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1617,67 +1526,26 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     convert_voice.py's .diff.wav): (waveforms, pcm or None, diff waveforms, diff pcm or None).
     driver='lockstep' (default): waves of 16 utterances through the batched entries on two streams (`ConvertWave`);
     'streams': the utterance-per-stream driver, see `_stream_batch` for its scheduling.
-    f0_stats / transpose_key (lockstep driver): the waveforms are synthesised on the mapped f0 (ConvertWave); a frame
-    out of the map's range raises ValueError after the batch.
-    gv_stats / gv_strength (lockstep driver): gv_strength > 0 runs the global-variance postfilter on the converted
-    mel-cepstra of both outputs (ConvertWave); a coefficient it cannot filter raises ValueError after the batch.
-    ms_stats / ms_length / ms_strength (lockstep driver): ms_strength > 0 runs the modulation-spectrum postfilter on
-    them first (ConvertWave); a bin it cannot filter raises ValueError after the batch, an utterance of more than
-    ms_length frames before it.
-    formant_ratio (lockstep driver): a ratio other than 1 warps the converted envelopes along frequency before the
-    synthesis (ConvertWave); the differential outputs are not touched; a row it cannot warp raises ValueError after the
-    batch, a ratio outside [0.5, 2] before anything is put on the device.
-    mlpg_em (lockstep driver): None, or N within [0, 16]: both outputs from EM trajectory conversions over soft mixture
-    posteriors with N re-estimations (ConvertWave; kwy_convert_mcep_em_batch_dev) instead of the arg-max conversion.
-    mlpg_gv (lockstep driver): None, or N within [0, 256], with gv_stats and gv_var (the converter's): both outputs from
-    conversions with the GV ascent behind them (ConvertWave; kwy_convert_mcep_gv_batch_dev), gv_weight weighing the GV
-    term; it goes with mlpg_em, not with gv_strength or ms_strength; a coefficient it cannot process raises ValueError
-    after the batch.
-    diff_filter (with diff=True): 'mlsa' (default), or 'fft': the differential outputs through the frame-parallel FFT
-    form of the filter (kwy_mcep_filter_fft_batch_dev, one grid over all frames of a wave's files, launched with the
-    wave) instead of the MLSA recursions (which wait for the last wave and run side by side, one wavefront per file).
-    postfilter_beta / keep_power (lockstep driver): beta > 0 (within [0, 1]) runs the mel-cepstral formant emphasis on
-    the absolute converted mel-cepstra of both outputs, keep_power shifts every frame's c0 until the frame has the
-    energy of the source frame (ConvertWave; kwy_mcep_postfilter_batch_dev, after every other filter); the differential
-    filters then take c0 into account (ignore_c0 = 0: the coefficients' column 0 is the change of c0).  A frame whose
-    energy is unusable raises ValueError after the batch, a beta outside [0, 1] before anything is put on the device."""
-    diff_filter = _diff_filter(diff_filter)
-    postfilter_beta = _postfilter_beta(postfilter_beta)
-    if (postfilter_beta or keep_power) and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
-        raise ValueError('convert_batch: postfilter_beta and keep_power need the lockstep driver')
-    formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'convert_batch')
-    mlpg_em = _mlpg_em(mlpg_em)
-    if mlpg_gv is not None and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
-        raise ValueError('convert_batch: mlpg_gv needs the lockstep driver')
-    _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, ms_strength, order,
-                     torch.device('cuda', device_index))          # (raises before anything else is put on the device)
+    **options: the keywords of `ConvertOptions`, which describes each (lockstep driver; every value is checked before
+    anything is put on the device)."""
+    opts = ConvertOptions(**options).check(order)
+    driver = driver or ('streams' if pool is not None else 'lockstep')     # (a caller's pool asks for the stream driver)
+    if driver != 'lockstep' and opts.need_lockstep():
+        raise ValueError(f'convert_batch: {opts.need_lockstep()[0]} the lockstep driver')
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     out = [None] * len(utterances)
-    driver = driver or ('streams' if pool is not None else 'lockstep')     # (a caller's pool asks for the stream driver)
     if driver == 'lockstep':
         pcms, dwav, dpcm = ([None] * len(utterances) for _ in range(3))
 
         def keep_view(i, w, p, wd, pd):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
-        _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, pcm=pcm, diff=diff,
-                        f0_stats=f0_stats, transpose_key=transpose_key, gv_stats=gv_stats, gv_strength=gv_strength,
-                        ms_stats=ms_stats, ms_length=ms_length, ms_strength=ms_strength, formant_ratio=formant_ratio,
-                        mlpg_em=mlpg_em, mlpg_gv=mlpg_gv, gv_var=gv_var, gv_weight=gv_weight, diff_filter=diff_filter,
-                        postfilter_beta=postfilter_beta, keep_power=keep_power)
+        _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, opts, pcm=pcm, diff=diff)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
     if pcm or diff or (len(utterances) and not isinstance(utterances[0], (tuple, list))):
         raise ValueError('convert_batch: wav-in utterances and pcm=True need the lockstep driver')
-    if f0_stats is not None or transpose_key != 0:
-        raise ValueError('convert_batch: f0_stats and transpose_key need the lockstep driver')
-    if gv_stats is not None or gv_strength != 0:
-        raise ValueError('convert_batch: gv_stats and gv_strength need the lockstep driver')
-    if ms_stats is not None or ms_strength != 0:
-        raise ValueError('convert_batch: ms_stats and ms_strength need the lockstep driver')
-    if mlpg_em is not None:
-        raise ValueError('convert_batch: mlpg_em needs the lockstep driver')
     if pool is None:
         pool = StreamPool(device_index, streams)
 
@@ -1688,20 +1556,23 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     return out
 
 
+@takes_options(dict(formant_ratio=1.0))
 def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams=16, pool=None, shapes_per_stream=4,
-                       out=None, driver=None, lockstep=None, formant_ratio=1.0):
+                       out=None, driver=None, lockstep=None, **options):
     """BASELINE config 4 on one rank: analyse + resynthesise every utterance ((x, f0, t) triples: numpy arrays or
     device tensors), more utterances than the driver has in flight.  Returns the list of waveforms (device tensors;
     written into `out[i]` instead when a list of preallocated tensors is given) and the number of frames analysed.
     driver='lockstep' (default): waves of 16 through the batched entries; 'streams': a fixed pool of streams.
     formant_ratio (lockstep driver): a ratio other than 1 warps the analysed envelopes along frequency before the
     synthesis (ConvertWave); ValueError for a row it cannot warp after the batch, for a ratio outside [0.5, 2] before."""
-    formant_ratio = _formant_ratio(formant_ratio, driver, pool, 'resynthesize_batch')
+    opts = ConvertOptions(only=dict(formant_ratio=1.0), **options).check(24, converting=False)
+    driver = driver or ('streams' if pool is not None else 'lockstep')
+    if driver != 'lockstep' and opts.need_lockstep():
+        raise ValueError(f'resynthesize_batch: {opts.need_lockstep()[0]} the lockstep driver')
     res = [None] * len(utterances)
     frames = 0
     for u in utterances:
         frames += len(u[1])
-    driver = driver or ('streams' if pool is not None else 'lockstep')
     if driver == 'lockstep':
         def keep_view(i, w, *_):
             if out is not None:
@@ -1709,8 +1580,7 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
                 res[i] = out[i]
             else:
                 res[i] = w
-        _lockstep_batch(utterances, fs, device_index, None, 24, frame_period, lockstep, keep_view,
-                        formant_ratio=formant_ratio)
+        _lockstep_batch(utterances, fs, device_index, None, 24, frame_period, lockstep, keep_view, opts)
         return res, frames
     from .pipeline import UtterancePipeline
     if pool is None:
@@ -1727,9 +1597,13 @@ def resynthesize_batch(utterances, fs, device_index=0, frame_period=5.0, streams
     return res, frames
 
 
-def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_period=5.0, frames='speech', gv_stats=None,
-                   gv_strength=0.0, f0_stats=None, transpose_key=0.0, per_frame=False, converter_fs=None, lockstep=None,
-                   wave_pairs=16, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0):
+_EVALUATED = {name: ConvertOptions.DEFAULTS[name] for name in ('f0_stats', 'transpose_key', 'gv_stats', 'gv_strength',
+                                                               'mlpg_em', 'mlpg_gv', 'gv_var', 'gv_weight')}
+
+
+@takes_options(_EVALUATED)
+def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_period=5.0, frames='speech', per_frame=False,
+                   converter_fs=None, lockstep=None, wave_pairs=16, **options):
     """Objective evaluation of the fitted mixture on parallel pairs, HBM-resident (what
     kwiiyatta_amd.evaluate_voice.evaluate does pair by pair through the Python API): waves of `wave_pairs` pairs
     through `EvalWave`.  pairs: ((x, f0, t), (x, f0, t)) triples as `build_training_matrix` takes them, all at the
@@ -1737,8 +1611,8 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     go through evaluate_voice.evaluate_pair, which resamples.  The silence pads are drawn from numpy's global
     generator in training's order, so under np.random.seed a pair's alignment is the one training would use.
     frames='speech': the distortion over the aligned frames whose target-side binarised power term is set; 'all': over
-    every aligned frame inside both utterances.  gv_stats / gv_strength, f0_stats / transpose_key, mlpg_em, mlpg_gv /
-    gv_var / gv_weight: as in `convert_batch`.  Returns (records, total): a dict per pair and one of the pooled figures -- the triples
+    every aligned frame inside both utterances.  **options: gv_stats / gv_strength, f0_stats / transpose_key, mlpg_em,
+    mlpg_gv / gv_var / gv_weight of `ConvertOptions`, as in `convert_batch`.  Returns (records, total): a dict per pair and one of the pooled figures -- the triples
     mcd_moments, source_moments, f0_moments ((n, mean, M2); merged by kwy_moments_merge_dev for the total), counts
     (VV, VU, UV, UU), aligned (frames of the alignment) and outside (those beyond either utterance) -- read back once,
     after the last wave.  per_frame=True: a record also holds idx_x, idx_y (frame indices into the trimmed utterances)
@@ -1749,10 +1623,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
         raise ValueError(f'evaluate_batch: the pairs are at {fs} Hz, the converter at {converter_fs} Hz; pairs of another '
                          f'sampling rate go through evaluate_voice.evaluate_pair')
     dev = torch.device('cuda', device_index)
-    gv = _gv_on_device(gv_stats, gv_strength, order, dev)       # (raises before anything else is put on the device)
-    stats = _f0_stats_on_device(f0_stats, dev)
-    mlpg_em = _mlpg_em(mlpg_em)
-    gvgen = _gvgen_on_device(mlpg_gv, gv_stats, gv_var, gv_weight, gv_strength, 0.0, order, dev)
+    opts = ConvertOptions(only=_EVALUATED, **options).check(order).upload(dev)
     zero = dict(mcd_moments=(0.0, 0.0, 0.0), source_moments=(0.0, 0.0, 0.0), f0_moments=(0.0, 0.0, 0.0),
                 counts=(0, 0, 0, 0), aligned=0, outside=0)
     if not pairs:
@@ -1773,8 +1644,7 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     for w0 in range(0, len(pairs), wave_pairs):
         wave = EvalWave(ls, fs, pairs[w0:w0 + wave_pairs], order=order, radius=radius, frame_period=frame_period)
         wave.analyse()
-        wave.measure(pads, dg, model, tot, w0, frames=frames, gv=gv, gv_strength=gv_strength, f0_stats=stats,
-                     transpose_key=float(transpose_key), per_frame=per_frame, mlpg_em=mlpg_em, gvgen=gvgen)
+        wave.measure(pads, dg, model, tot, w0, opts, frames=frames, per_frame=per_frame)
         waves.append(wave)
         if not per_frame:
             while len(waves) > 2:
@@ -1785,12 +1655,12 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     if status[:, :3].any():
         from .backend import distortion as dist
         dist.check_status(status[:, :3].sum(axis=1), 'evaluation')
-    if gv is not None:
+    if opts.gv is not None:
         from .backend import gv as gvfilter
         gvfilter.check_status(status[:, 3])
-    if gvgen is not None:
+    if opts.gvgen is not None:
         _check_gvgen_status(status[:, 3])
-    if stats is not None or transpose_key != 0:
+    if opts.f0_map:
         from .backend.f0 import check_status
         check_status(status[:, 4], fs)
 

@@ -21,8 +21,12 @@ import json
 import math
 import pathlib
 import sys
+from types import SimpleNamespace
 
 import numpy as np
+
+from ._convert_options import filled, takes_options
+from .convert_voice import COMMAND_OPTIONS, _stages, driver_options
 
 PAD_LEN = 100             # align_even's silence pads
 FRAMES = ('speech', 'all')
@@ -103,8 +107,11 @@ def _check_options(gv, transpose_key, frames):
         raise ValueError(f'transpose_key {transpose_key!r} is outside [-{KEY_RANGE}, {KEY_RANGE}]')
 
 
-def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose_key=0.0, frames='speech',
-                  per_frame=False, em=None, mlpg_gv=None):
+PAIR_OPTIONS = dict(gv=0.0, convert_f0=False, transpose_key=0.0, frames='speech', per_frame=False, em=None, mlpg_gv=None)
+
+
+@takes_options(defaults=PAIR_OPTIONS)
+def evaluate_pair(converter, source, target, **options):
     """The figures of one parallel pair: two unaligned feature sets (trimmed as training trims them, if the alignment
     is to be the one training would use).  Both are padded and aligned as `align_even` does -- the same pad draws in
     the same order, so a seeded run reproduces training's alignment -- `source.mel_cepstrum` is converted on its own
@@ -120,15 +127,17 @@ def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose
     from .backend import distortion as dist
     from .backend import f0 as f0map
     from .vocoder.align import even_indices, make_feature
+    o = SimpleNamespace(**filled(options, PAIR_OPTIONS))
+    gv, convert_f0, transpose_key, frames = o.gv, o.convert_f0, o.transpose_key, o.frames
     _check_options(gv, transpose_key, frames)
     if convert_f0 and converter.f0_stats is None:
         raise ValueError('f0 conversion: the converter has no statistics (train it with f0_stats=True)')
     a, b = k.pad_silence(source, PAD_LEN), k.pad_silence(target, PAD_LEN)
     xs, ys = even_indices(a, b, PAD_LEN, strict=True)
     idx_x, idx_y = (np.ascontiguousarray(v, dtype=np.int32) for v in (xs, ys))
-    converted = converter.convert(source.mel_cepstrum, **(dict(gv=gv) if gv > 0 else {}),
-                                  **({} if em is None else dict(em=em)),
-                                  **({} if mlpg_gv is None else dict(mlpg_gv=mlpg_gv)))
+    # converter.convert's keywords: (value, whether it is on) -- an option that is off is not handed over
+    stages = dict(gv=(gv, gv > 0), em=(o.em, o.em is not None), mlpg_gv=(o.mlpg_gv, o.mlpg_gv is not None))
+    converted = converter.convert(source.mel_cepstrum, **{name: v for name, (v, on) in stages.items() if on})
     fs = converted.fs
 
     def coefficients(f):
@@ -149,7 +158,7 @@ def evaluate_pair(converter, source, target, gv=0.0, convert_f0=False, transpose
     # the cut of align_even ends where BOTH sides are in their trailing pads: cells with one side in its pad remain,
     # and the kernels pass them over (the f0 kernel counts every other aligned frame)
     outside = len(idx_x) - int(counts.sum())
-    keep = dict(idx_x=idx_x - PAD_LEN, idx_y=idx_y - PAD_LEN, mcd_frames=rows[0]) if per_frame else {}
+    keep = dict(idx_x=idx_x - PAD_LEN, idx_y=idx_y - PAD_LEN, mcd_frames=rows[0]) if o.per_frame else {}
     return Result(m[0], m[1], f0_m, counts, len(idx_x), outside, **keep)
 
 
@@ -245,7 +254,6 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
     waveforms of the batch go through the shifter in one call and are analysed from there on the device"""
     import kwiiyatta_amd as k
     from . import corpus
-    from .convert_voice import _stages
     from .converter.delta import DeltaFeatureConverter
     period = next((s.frame_period for s in _stages(converter) if isinstance(s, DeltaFeatureConverter)), None)
     sides = [pathlib.Path(conf.source), pathlib.Path(conf.target)]
@@ -265,14 +273,12 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
         sources = _shifted_triples([pair[0][0] for _, pair, _ in batch], converter.fs, rate, batch[0][2])
         batch = [(key, (src, pair[1]), period) for (key, pair, period), src in zip(batch, sources)]
     if batch:
+        asked = SimpleNamespace(**dict(COMMAND_OPTIONS, gv=options['gv'], convert_f0=options['convert_f0'],
+                                       transpose_key=options['transpose_key'], mlpg_em=options.get('em'),
+                                       mlpg_gv=options.get('mlpg_gv')))
         records, _ = corpus.evaluate_batch(
             [p for _, p, _ in batch], converter.fs, converter.gmm, order=converter.order, frame_period=batch[0][2],
-            f0_stats=converter.f0_stats if options['convert_f0'] else None, transpose_key=options['transpose_key'],
-            frames=options['frames'], **(dict(gv_stats=converter.gv_stats, gv_strength=options['gv'])
-                                         if options['gv'] > 0 else {}),
-            **({} if options.get('em') is None else dict(mlpg_em=options['em'])),
-            **({} if options.get('mlpg_gv') is None else dict(mlpg_gv=options['mlpg_gv'], gv_stats=converter.gv_stats,
-                                                              gv_var=converter.gv_var)))
+            frames=options['frames'], **driver_options(converter, asked))
         for (key, _, _), rec in zip(batch, records):
             results[key] = Result(rec['mcd_moments'], rec['source_moments'], rec['f0_moments'], rec['counts'],
                                   rec['aligned'], rec['outside'])
@@ -330,10 +336,8 @@ def main():
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
                                      **(dict(gv_var=True) if conf.mlpg_gv is not None else {}))
     options = dict(gv=conf.gv, convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, frames=conf.frames)
-    if conf.mlpg_em is not None:           # (--mlpg-em: EM trajectory conversion, as convert_voice runs it)
-        options['em'] = conf.mlpg_em
-    if conf.mlpg_gv is not None:           # (--mlpg-gv: GV-considering parameter generation, likewise)
-        options['mlpg_gv'] = conf.mlpg_gv
+    # (--mlpg-em, --mlpg-gv: EM trajectory conversion, GV-considering parameter generation, as convert_voice runs them)
+    options.update({name: v for name, v in dict(em=conf.mlpg_em, mlpg_gv=conf.mlpg_gv).items() if v is not None})
     if conf.batch:
         results = _evaluate_batched(conf, converter, dataset, keys, options)
         total = pool(results)

@@ -199,3 +199,22 @@ def test_new_entry_points_are_in_the_ctypes_table():
     assert len(_lib.SIGNATURES['kwy_convert_mcep_em_batch_dev'][1]) == 7
     assert [n for n, _ in _lib.ConvertEmJob._fields_] == ['mc', 'T', 'mc_out', 'loglik']
     assert ctypes.sizeof(_lib.ConvertEmJob) == 32
+
+
+def test_drivers_take_the_options_of_one_record_and_name_a_keyword_they_do_not_know():
+    """the defaults below are those of convert_batch's signature before the options moved into ConvertOptions"""
+    from kwiiyatta_amd import corpus
+    from kwiiyatta_amd._convert_options import ConvertOptions
+    with pytest.raises(TypeError, match='gv_strenght'):
+        corpus.convert_batch([], 16000, None, gv_strenght=1.0)
+    with pytest.raises(TypeError, match='ms_strength'):
+        corpus.evaluate_batch([], 16000, None, ms_strength=1.0)
+    assert ConvertOptions.DEFAULTS == dict(
+        f0_stats=None, transpose_key=0.0, gv_stats=None, gv_strength=0.0, ms_stats=None, ms_length=None, ms_strength=0.0,
+        formant_ratio=1.0, mlpg_em=None, mlpg_gv=None, gv_var=None, gv_weight=1.0, diff_filter='mlsa', postfilter_beta=0.0,
+        keep_power=False)
+    assert all(type(v) is type(w) for v, w in zip(ConvertOptions.DEFAULTS.values(),
+                                                  (None, 0.0, None, 0.0, None, None, 0.0, 1.0, None, None, None, 1.0, 'mlsa',
+                                                   0.0, False)))
+    record = ConvertOptions()
+    assert all(getattr(record, name) is default for name, default in ConvertOptions.DEFAULTS.items())
