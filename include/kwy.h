@@ -758,7 +758,8 @@ int kwy_realign_features_batch_dev(kwy_ctx *ctx, const kwy_realign_job *jobs, in
  *                                        kwiiyatta/vocoder/world.py:98-145
  * ap: T x (fft_size/2+1); coded: T x kwy_aperiodicity_bands(fs) on the coding side.  The
  * decoder takes the number of coded columns explicitly (the reference truncates or extends the
- * coded array when it changes the sampling rate, world.py:121-143). */
+ * coded array when it changes the sampling rate, world.py:121-143), at most kwy_aperiodicity_bands(fs) of them:
+ * with more, the band centres would reach fs/2 and the interpolation grid would not increase (KWY_EINVAL). */
 int kwy_aperiodicity_bands(int fs);
 int kwy_code_aperiodicity(kwy_ctx *ctx, const double *ap, int64_t T, int fs, int fft_size, double *coded);
 int kwy_code_aperiodicity_dev(kwy_ctx *ctx, const double *ap, int64_t T, int fs, int fft_size, double *coded);

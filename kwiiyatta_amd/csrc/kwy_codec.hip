@@ -86,6 +86,12 @@ static int codec_check(kwy_ctx *ctx, const void *a, const void *b, int64_t T, in
     ctx->err = "aperiodicity codec: bad argument";
     return KWY_EINVAL;
   }
+  // more bands than the rate has: the nodes 3 kHz, 6 kHz, ... would reach fs/2, the last node, and the grid would
+  // no longer increase (WORLD derives the count from fs; the reference's caller truncates to the new rate's count)
+  if (nb > codec_num_bands(fs)) {
+    ctx->err = "aperiodicity codec: more bands than the sampling rate has";
+    return KWY_EINVAL;
+  }
   return KWY_OK;
 }
 

@@ -140,7 +140,9 @@ __global__ __launch_bounds__(KWY_THREADS) void k_fin_pieces(fin_plan P) {
     for (int q = wv; q < FIN_MS; q += KWY_WAVES) {
       const int64_t piece = p0 + q;
       if (piece >= U.frame_len) break;
-      const int a = (int)(fs * piece / 1000 - s_lo), b = (int)(fs * (piece + 1) / 1000 - s_lo);
+      const int a = (int)(fs * piece / 1000 - s_lo);
+      int b = (int)(fs * (piece + 1) / 1000 - s_lo);
+      if (b > m) b = m;                  // the last piece may end beyond the waveform: numpy's slice stops at its end
       double pk = 0.0;
       for (int i = a + lane; i < b; i += 64) pk = fmax(pk, fabs(tile[i]));
       pk = kwy_wave_max_f64(pk);

@@ -97,7 +97,9 @@ std::vector<double> design_taps(int numtaps, double cutoff, double gain) {
   std::vector<double> h(numtaps);
   const double alpha = 0.5 * (numtaps - 1);
   const double i0b = bessel_i0(5.0);
-  double dc = 0.0;
+  // The DC gain is summed with compensation (Kahan): scipy normalises by numpy's pairwise sum, and a plain running
+  // sum over 50 000 taps is off by ~1e-14 -- a gain error that shows in the output multiplied by |log value|.
+  double dc = 0.0, lost = 0.0;
   for (int i = 0; i < numtaps; ++i) {
     const double m = i - alpha;
     const double y = M_PI * (cutoff * m == 0.0 ? 1.0e-20 : cutoff * m);     // numpy.sinc
@@ -105,7 +107,9 @@ std::vector<double> design_taps(int numtaps, double cutoff, double gain) {
     const double rel = (i - alpha) / alpha;
     const double w = bessel_i0(5.0 * sqrt(fmax(0.0, 1.0 - rel * rel))) / i0b;
     h[i] = lowpass * w;
-    dc += h[i];
+    const double term = h[i] - lost, next = dc + term;
+    lost = (next - dc) - term;
+    dc = next;
   }
   for (double &v : h) v = v / dc * gain;
   return h;
