@@ -164,27 +164,27 @@ __device__ __forceinline__ void align_project_body(const int32_t *__restrict__ p
   if (lane == 0) *n_out = st[2];
 }
 
-// The three kernels take their jobs by value (up to AL_BATCH per launch, blockIdx.y = job): the pairs of a batch
-// driver share one launch, a single call is a batch of one.
+// The three kernels take up to AL_BATCH jobs per launch (blockIdx.y = job): the pairs of a batch driver share one
+// launch, a single call is a batch of one.
 #define AL_BATCH 64
 template <class JOB>
-struct al_jobs { int n; JOB j[AL_BATCH]; };
+using al_jobs = kwy_group<JOB, AL_BATCH>;
 
 __global__ __launch_bounds__(KWY_THREADS) void k_align_features(al_jobs<kwy_align_job> b, int ncoef,
                                                                double power_threshold, double power_weight,
                                                                double vuv_weight) {
-  const kwy_align_job &q = b.j[blockIdx.y];
+  const kwy_align_job &q = b.u[blockIdx.y];
   if ((int64_t)blockIdx.x * AL_FEAT_FRAMES >= q.T) return;
   align_features_body(q.mc, q.T, ncoef, q.f0, power_threshold, power_weight, vuv_weight, q.out);
 }
 
 __global__ __launch_bounds__(AL_NT) void k_align_project(al_jobs<kwy_project_job> b, int trim_len) {
-  const kwy_project_job &q = b.j[blockIdx.x];
+  const kwy_project_job &q = b.u[blockIdx.x];
   align_project_body(q.path, q.path_len, trim_len, q.idx, q.idx_capacity, q.n_out);
 }
 
 __global__ void k_gather_rows(al_jobs<kwy_gather_job> b, int width) {
-  const kwy_gather_job &q = b.j[blockIdx.y];
+  const kwy_gather_job &q = b.u[blockIdx.y];
   const double *__restrict__ src = q.src;
   const int32_t *__restrict__ idx = q.idx;
   double *__restrict__ dst = q.dst;
@@ -199,15 +199,15 @@ __global__ void k_gather_rows(al_jobs<kwy_gather_job> b, int width) {
   for (int c = threadIdx.x; c < width; c += blockDim.x) d[c] = s[c];
 }
 
+// the caller's jobs are the views; a launch that fails is reported after the last one (hipGetLastError)
 template <class JOB, class LAUNCH>
-static int al_for_batches(const JOB *jobs, int count, LAUNCH launch) {
-  for (int j0 = 0; j0 < count; j0 += AL_BATCH) {
-    al_jobs<JOB> b;
-    b.n = count - j0 < AL_BATCH ? count - j0 : AL_BATCH;
-    for (int k = 0; k < AL_BATCH; ++k) b.j[k] = jobs[j0 + (k < b.n ? k : 0)];
-    launch(b);
-  }
-  return KWY_OK;
+static void al_for_batches(const JOB *jobs, int count, LAUNCH launch) {
+  kwy_for_tables<al_jobs<JOB>>(
+      count, [&](int j) { return jobs[j]; },
+      [&](const al_jobs<JOB> &b, int) {
+        launch(b);
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_align_features_batch_dev(kwy_ctx *ctx, const kwy_align_job *jobs, int count, int ncoef,
@@ -219,7 +219,7 @@ extern "C" int kwy_align_features_batch_dev(kwy_ctx *ctx, const kwy_align_job *j
   KWY_HIP(hipSetDevice(ctx->device));
   al_for_batches(jobs, count, [&](const al_jobs<kwy_align_job> &b) {
     int64_t T = 0;
-    for (int k = 0; k < b.n; ++k) T = b.j[k].T > T ? b.j[k].T : T;
+    for (int k = 0; k < b.n; ++k) T = b.u[k].T > T ? b.u[k].T : T;
     hipLaunchKernelGGL(k_align_features, dim3((unsigned)((T + AL_FEAT_FRAMES - 1) / AL_FEAT_FRAMES), b.n), dim3(KWY_THREADS), 0,
                        ctx->stream, b, ncoef,
                        power_threshold, power_weight, vuv_weight);
@@ -268,7 +268,7 @@ extern "C" int kwy_gather_rows_batch_dev(kwy_ctx *ctx, const kwy_gather_job *job
   KWY_HIP(hipSetDevice(ctx->device));
   al_for_batches(jobs, count, [&](const al_jobs<kwy_gather_job> &b) {
     int64_t n = 0;
-    for (int k = 0; k < b.n; ++k) n = b.j[k].n > n ? b.j[k].n : n;
+    for (int k = 0; k < b.n; ++k) n = b.u[k].n > n ? b.u[k].n : n;
     if (n > 0)
       hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)n, b.n), dim3(width >= 256 ? 256 : 64), 0, ctx->stream, b, width);
   });

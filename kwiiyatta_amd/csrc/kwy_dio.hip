@@ -5,8 +5,8 @@
 // pyworld 0.2.8).  SURVEY.md ranks this producer of the f0 track as 8(f)-1: it
 // sits in front of the hot path, and is here so that wav-in analysis needs no CPU
 // numerics and -- round 5 -- no trip over the host either: kwy_dio_batch_dev /
-// kwy_stonemask_batch_dev take device pointers for up to 16 utterances per pass
-// of launches and do not synchronise.
+// kwy_stonemask_batch_dev take device pointers for up to DIO_BATCH (32) and
+// KWY_BATCH_MAX (16) utterances per pass of launches and do not synchronise.
 //
 // DIO on the CPU filters the whole signal with FFTs of ~2^19 points: a 50 Hz
 // low-cut, then one Nuttall low-pass per half-octave band.  Both are short FIRs

@@ -23,7 +23,7 @@
 
 #include "kwy_internal.hpp"
 
-#define EV_GROUP 16        // utterances per launch: the job views travel by value in the kernel arguments
+#define EV_GROUP 16        // utterances per launch
 #define EV_MAX_COLS 64
 #define EV_DB (10.0 / 2.302585092994045684)      // 10 / ln 10
 #define EV_DBL_MAX 1.79769313486231570815e+308
@@ -38,10 +38,7 @@ struct ev_mcd {
   int32_t *status;         // rows with a coefficient that is not finite (may be NULL)
   int64_t a_rows, a_stride, b_rows, b_stride, off_a, off_b, rows, mask_stride, mask_rows;
 };
-struct ev_mcds {
-  int count;
-  ev_mcd u[EV_GROUP];
-};
+typedef kwy_group<ev_mcd, EV_GROUP> ev_mcds;
 
 struct ev_f0 {
   const double *fa, *fb;
@@ -52,10 +49,7 @@ struct ev_f0 {
   int32_t *status;         // frames with an f0 that is negative or not finite (may be NULL)
   int64_t a_len, b_len, off_a, off_b, rows;
 };
-struct ev_f0s {
-  int count;
-  ev_f0 u[EV_GROUP];
-};
+typedef kwy_group<ev_f0, EV_GROUP> ev_f0s;
 
 // the row count of a job: the host value, or the device word clamped to [0, rows] (rows is then the lists' capacity)
 __device__ __forceinline__ int64_t ev_rows(int64_t rows, const int64_t *n_dev) {
@@ -297,24 +291,20 @@ static int ev_check_mcd(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int co
 
 static int ev_launch_mcd(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int cols, int first_col, double *moments,
                          int32_t *status) {
-  for (int i0 = 0; i0 < count; i0 += EV_GROUP) {
-    ev_mcds B;
-    B.count = count - i0 < EV_GROUP ? count - i0 : EV_GROUP;
-    for (int u = 0; u < EV_GROUP; ++u) {
-      ev_mcd v = {};
-      if (u < B.count) {
-        const kwy_mcd_job &j = jobs[i0 + u];
-        v = ev_mcd{j.a, j.b, j.idx_a, j.idx_b, j.n_dev, j.mask, j.per_row, moments + 3 * (int64_t)(i0 + u),
-                   status ? status + i0 + u : nullptr, j.a_rows, j.a_stride, j.b_rows, j.b_stride, j.off_a, j.off_b,
-                   j.rows, j.mask_stride, j.mask_rows};
-      }
-      B.u[u] = v;
-    }
-    KWY_PROF(ctx, "k_eval_mcd",
-             hipLaunchKernelGGL(k_eval_mcd, dim3(B.count), dim3(KWY_THREADS), 0, ctx->stream, B, cols, first_col));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<ev_mcds>(
+      count,
+      [&](int i) {
+        const kwy_mcd_job &j = jobs[i];
+        return ev_mcd{j.a, j.b, j.idx_a, j.idx_b, j.n_dev, j.mask, j.per_row, moments + 3 * (int64_t)i,
+                      status ? status + i : nullptr, j.a_rows, j.a_stride, j.b_rows, j.b_stride, j.off_a, j.off_b,
+                      j.rows, j.mask_stride, j.mask_rows};
+      },
+      [&](const ev_mcds &B, int) {
+        KWY_PROF(ctx, "k_eval_mcd",
+                 hipLaunchKernelGGL(k_eval_mcd, dim3(B.n), dim3(KWY_THREADS), 0, ctx->stream, B, cols, first_col));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_mcd_batch_dev(kwy_ctx *ctx, const kwy_mcd_job *jobs, int count, int cols, int first_col,
@@ -373,23 +363,18 @@ static int ev_check_f0(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int count, co
 
 static int ev_launch_f0(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int count, int64_t *counts, double *moments,
                         int32_t *status) {
-  for (int i0 = 0; i0 < count; i0 += EV_GROUP) {
-    ev_f0s B;
-    B.count = count - i0 < EV_GROUP ? count - i0 : EV_GROUP;
-    for (int u = 0; u < EV_GROUP; ++u) {
-      ev_f0 v = {};
-      if (u < B.count) {
-        const kwy_f0_error_job &j = jobs[i0 + u];
-        v = ev_f0{j.f0_a, j.f0_b, j.idx_a, j.idx_b, j.n_dev, counts + 4 * (int64_t)(i0 + u),
-                  moments + 3 * (int64_t)(i0 + u), status ? status + i0 + u : nullptr, j.a_length, j.b_length, j.off_a,
-                  j.off_b, j.rows};
-      }
-      B.u[u] = v;
-    }
-    KWY_PROF(ctx, "k_eval_f0", hipLaunchKernelGGL(k_eval_f0, dim3(B.count), dim3(KWY_THREADS), 0, ctx->stream, B));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<ev_f0s>(
+      count,
+      [&](int i) {
+        const kwy_f0_error_job &j = jobs[i];
+        return ev_f0{j.f0_a, j.f0_b, j.idx_a, j.idx_b, j.n_dev, counts + 4 * (int64_t)i, moments + 3 * (int64_t)i,
+                     status ? status + i : nullptr, j.a_length, j.b_length, j.off_a, j.off_b, j.rows};
+      },
+      [&](const ev_f0s &B, int) {
+        KWY_PROF(ctx, "k_eval_f0", hipLaunchKernelGGL(k_eval_f0, dim3(B.n), dim3(KWY_THREADS), 0, ctx->stream, B));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_f0_error_batch_dev(kwy_ctx *ctx, const kwy_f0_error_job *jobs, int count, int64_t *counts,

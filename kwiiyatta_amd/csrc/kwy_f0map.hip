@@ -19,17 +19,14 @@
 
 #include "kwy_internal.hpp"
 
-#define F0M_GROUP 32      // tracks per launch: the job views travel by value in the kernel arguments
+#define F0M_GROUP 32      // tracks per launch
 
 struct f0m_track {
   const double *f0;
   int64_t n;
   double *out;            // (count, mean, M2)
 };
-struct f0m_tracks {
-  int count;
-  f0m_track u[F0M_GROUP];
-};
+typedef kwy_group<f0m_track, F0M_GROUP> f0m_tracks;
 
 struct f0m_map {
   const double *in;
@@ -37,10 +34,7 @@ struct f0m_map {
   double *out;
   int32_t *status;        // frames out of range (may be NULL)
 };
-struct f0m_maps {
-  int count;
-  f0m_map u[F0M_GROUP];
-};
+typedef kwy_group<f0m_map, F0M_GROUP> f0m_maps;
 
 // one workgroup per track: (n, mean, M2) of log f0 over the frames with f0 > 0, in two passes
 __global__ __launch_bounds__(KWY_THREADS) void k_logf0_moments(f0m_tracks B) {
@@ -108,17 +102,14 @@ static int f0m_check_tracks(kwy_ctx *ctx, const kwy_f0_track *tracks, int count,
 }
 
 static int f0m_launch_moments(kwy_ctx *ctx, const kwy_f0_track *tracks, int count, double *moments) {
-  for (int i0 = 0; i0 < count; i0 += F0M_GROUP) {
-    f0m_tracks B;
-    B.count = count - i0 < F0M_GROUP ? count - i0 : F0M_GROUP;
-    for (int u = 0; u < F0M_GROUP; ++u)
-      B.u[u] = u < B.count ? f0m_track{tracks[i0 + u].f0, tracks[i0 + u].length, moments + 3 * (int64_t)(i0 + u)}
-                           : f0m_track{nullptr, 0, nullptr};
-    KWY_PROF(ctx, "k_logf0_moments",
-             hipLaunchKernelGGL(k_logf0_moments, dim3(B.count), dim3(KWY_THREADS), 0, ctx->stream, B));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<f0m_tracks>(
+      count, [&](int i) { return f0m_track{tracks[i].f0, tracks[i].length, moments + 3 * (int64_t)i}; },
+      [&](const f0m_tracks &B, int) {
+        KWY_PROF(ctx, "k_logf0_moments",
+                 hipLaunchKernelGGL(k_logf0_moments, dim3(B.n), dim3(KWY_THREADS), 0, ctx->stream, B));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_logf0_moments_batch_dev(kwy_ctx *ctx, const kwy_f0_track *tracks, int count, double *moments) {
@@ -167,18 +158,15 @@ static int f0m_check_maps(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, i
 static int f0m_launch_map(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, const double *stats,
                           double ratio, int32_t *status) {
   const double limit = fs / 8.0;   // kwy_synth.hip's pulse capacity (y_length / 8 + 16) holds every such track
-  for (int i0 = 0; i0 < count; i0 += F0M_GROUP) {
-    f0m_maps B;
-    B.count = count - i0 < F0M_GROUP ? count - i0 : F0M_GROUP;
-    for (int u = 0; u < F0M_GROUP; ++u)
-      B.u[u] = u < B.count ? f0m_map{jobs[i0 + u].f0_in, jobs[i0 + u].length, jobs[i0 + u].f0_out,
-                                     status ? status + i0 + u : nullptr}
-                           : f0m_map{nullptr, 0, nullptr, nullptr};
-    KWY_PROF(ctx, "k_f0_map",
-             hipLaunchKernelGGL(k_f0_map, dim3(B.count), dim3(KWY_THREADS), 0, ctx->stream, B, stats, ratio, limit));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<f0m_maps>(
+      count,
+      [&](int i) { return f0m_map{jobs[i].f0_in, jobs[i].length, jobs[i].f0_out, status ? status + i : nullptr}; },
+      [&](const f0m_maps &B, int) {
+        KWY_PROF(ctx, "k_f0_map",
+                 hipLaunchKernelGGL(k_f0_map, dim3(B.n), dim3(KWY_THREADS), 0, ctx->stream, B, stats, ratio, limit));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_f0_map_batch_dev(kwy_ctx *ctx, const kwy_f0_map_job *jobs, int count, int fs, const double *stats,

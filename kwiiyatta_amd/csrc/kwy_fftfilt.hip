@@ -23,7 +23,7 @@
 #include "kwy_internal.hpp"
 
 #define FF_MAX_ORDER 62          // what kwy_mlsa_synthesis accepts
-#define FF_JOBS_MAX 64           // signals per launch: the jobs travel by value in the kernel arguments
+#define FF_JOBS_MAX 64           // signals per launch
 #define FF_TAIL 16384            // samples of a zero tail per workgroup
 #define FF_BLOCKS_MAX (1 << 30)  // workgroups per launch
 
@@ -33,11 +33,8 @@ struct ff_job {
   double *y;          // n samples out
   int64_t n, T;
 };
-struct ff_jobs {
-  int count;
-  int start[FF_JOBS_MAX + 1];   // first workgroup of every job
-  ff_job j[FF_JOBS_MAX];
-};
+typedef kwy_batch<ff_job, FF_JOBS_MAX> ff_jobs;
+static_assert(sizeof(ff_jobs) + 48 <= KWY_KERNARG_MAX, "k_fft_filter: the table and seven scalar arguments");
 
 static inline int64_t ff_nproc(int64_t n, int64_t T, int hop) {
   const int64_t f = (n - 1) / hop;
@@ -64,11 +61,11 @@ __global__ __launch_bounds__(KWY_THREADS) void k_fft_filter(ff_jobs J, int m, in
   const int tid = threadIdx.x;
   const int g = blockIdx.x;
   int u = 0;
-  while (u + 1 < J.count && g >= J.start[u + 1]) ++u;   // uniform: a scalar loop
-  const double *__restrict__ x = J.j[u].x;
-  const double *__restrict__ mc = J.j[u].mc;
-  double *__restrict__ y = J.j[u].y;
-  const int64_t n = J.j[u].n, T = J.j[u].T;
+  while (u + 1 < J.n && g >= J.start[u + 1]) ++u;   // uniform: a scalar loop
+  const double *__restrict__ x = J.u[u].x;
+  const double *__restrict__ mc = J.u[u].mc;
+  double *__restrict__ y = J.u[u].y;
+  const int64_t n = J.u[u].n, T = J.u[u].T;
   const int64_t i = g - J.start[u];
   int64_t nproc = (n - 1) / hop;
   if (nproc > T) nproc = T;
@@ -174,14 +171,14 @@ static int ff_launch(kwy_ctx *ctx, const ff_jobs &J, int m, int m0, int hop, con
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
   const size_t lds = sizeof(kwy_c) * (2 * (H + 1) + H / 8) + sizeof(double) * 128;
   KWY_HIP(hipFuncSetAttribute((const void *)k_fft_filter<LOG2N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  KWY_PROF(ctx, "k_fft_filter", hipLaunchKernelGGL(k_fft_filter<LOG2N>, dim3((unsigned)J.start[J.count]), dim3(KWY_THREADS), lds,
+  KWY_PROF(ctx, "k_fft_filter", hipLaunchKernelGGL(k_fft_filter<LOG2N>, dim3((unsigned)J.start[J.n]), dim3(KWY_THREADS), lds,
                                                    ctx->stream, J, m, m0, hop, warp, twH, twP, twN));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
 
 static int ff_core(kwy_ctx *ctx, const ff_jobs &J, int m, int m0, int hop, int N, const kwy_c *warp) {
-  if (J.start[J.count] == 0) return KWY_OK;
+  if (J.start[J.n] == 0) return KWY_OK;
   switch (N) {
     case 1024: return ff_launch<10>(ctx, J, m, m0, hop, warp);
     case 2048: return ff_launch<11>(ctx, J, m, m0, hop, warp);
@@ -190,26 +187,25 @@ static int ff_core(kwy_ctx *ctx, const ff_jobs &J, int m, int m0, int hop, int N
   }
 }
 
-// the jobs in launches of <= FF_JOBS_MAX signals and <= FF_BLOCKS_MAX workgroups (all of them checked already)
+// the jobs in launches of <= FF_JOBS_MAX signals and <= FF_BLOCKS_MAX workgroups (all of them checked already): the
+// second limit also ends a table, so this walk is its own and not kwy_for_tables
 static int ff_run(kwy_ctx *ctx, const kwy_mlsa_job *jobs, int count, int order, double alpha, int hop, int N, int ignore_c0) {
   KWY_HIP(hipSetDevice(ctx->device));
   const kwy_c *warp;
   KWY_TRY(ff_warp_table(ctx, N, alpha, &warp));
-  ff_jobs J;
-  J.count = 0;
-  J.start[0] = 0;
+  ff_jobs J{};
   for (int i = 0; i < count; ++i) {
     const kwy_mlsa_job &q = jobs[i];
     const int64_t nb = ff_blocks(q.x_length, q.T, hop);
-    if (J.count == FF_JOBS_MAX || (int64_t)J.start[J.count] + nb > FF_BLOCKS_MAX) {
+    if (J.n == FF_JOBS_MAX || (int64_t)J.start[J.n] + nb > FF_BLOCKS_MAX) {
       KWY_TRY(ff_core(ctx, J, order, ignore_c0 ? 1 : 0, hop, N, warp));
-      J.count = 0;
+      J = ff_jobs{};
     }
-    J.j[J.count] = ff_job{q.x, q.mc, q.y, q.x_length, q.T};
-    J.start[J.count + 1] = J.start[J.count] + (int)nb;
-    ++J.count;
+    J.u[J.n] = ff_job{q.x, q.mc, q.y, q.x_length, q.T};
+    J.start[J.n + 1] = J.start[J.n] + (int)nb;
+    ++J.n;
   }
-  if (J.count) KWY_TRY(ff_core(ctx, J, order, ignore_c0 ? 1 : 0, hop, N, warp));
+  if (J.n) KWY_TRY(ff_core(ctx, J, order, ignore_c0 ? 1 : 0, hop, N, warp));
   return KWY_OK;
 }
 

@@ -22,7 +22,7 @@
 
 #include "kwy_internal.hpp"
 
-#define FS_GROUP 32                         // jobs per launch: the job views travel by value in the kernel arguments
+#define FS_GROUP 32                         // jobs per launch
 #define FS_THREADS 512                      // lanes of a workgroup
 #define FS_CHUNK 2048                       // doubles of staged logarithms; twice that where a row is longer
 #define FS_MAX_ROWS 64                      // rows per chunk at most
@@ -37,9 +37,7 @@ struct fs_view {
   double *out;
   int32_t *status;         // rows copied unchanged (may be NULL); zero before the launch
 };
-struct fs_views {
-  fs_view u[FS_GROUP];
-};
+typedef kwy_group<fs_view, FS_GROUP> fs_views;
 
 static inline int fs_chunk_rows(int K, int cap) {
   const int r = cap / K;
@@ -159,30 +157,26 @@ static int fs_launch(kwy_ctx *ctx, const kwy_formant_job *jobs, int count, int K
   }
   const int cap = K > FS_CHUNK ? 2 * FS_CHUNK : FS_CHUNK;
   const int R = fs_chunk_rows(K, cap);
-  for (int i0 = 0; i0 < count; i0 += FS_GROUP) {
-    fs_views B;
-    const int n = count - i0 < FS_GROUP ? count - i0 : FS_GROUP;
-    int64_t longest = 0;
-    for (int u = 0; u < FS_GROUP; ++u) {
-      const kwy_formant_job *j = u < n ? jobs + i0 + u : nullptr;
-      B.u[u] = j ? fs_view{j->sp, j->rows, j->out, status ? status + i0 + u : nullptr}
-                 : fs_view{nullptr, 0, nullptr, nullptr};
-      if (j && j->rows > longest) longest = j->rows;
-    }
-    if (longest == 0) continue;
-    int64_t blocks = (longest + R - 1) / R;
-    const int64_t share = FS_BLOCKS / n;
-    blocks = blocks > share ? share : blocks;
-    const dim3 grid((unsigned)blocks, n), block(FS_THREADS);
-    if (cap == FS_CHUNK)
-      KWY_PROF(ctx, "k_formant_shift", hipLaunchKernelGGL((k_formant_shift<FS_CHUNK / FS_THREADS, 6>), grid, block, 0,
-                                                          ctx->stream, B, K, R, rho));
-    else      // (only K = 2049, a 4096-point transform: a row needs the larger buffer)
-      KWY_PROF(ctx, "k_formant_shift", hipLaunchKernelGGL((k_formant_shift<2 * FS_CHUNK / FS_THREADS, 4>), grid, block, 0,
-                                                          ctx->stream, B, K, R, rho));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<fs_views>(
+      count,
+      [&](int i) { return fs_view{jobs[i].sp, jobs[i].rows, jobs[i].out, status ? status + i : nullptr}; },
+      [&](const fs_views &B, int) {
+        int64_t longest = 0;
+        for (int u = 0; u < B.n; ++u) longest = B.u[u].rows > longest ? B.u[u].rows : longest;
+        if (longest == 0) return KWY_OK;
+        int64_t blocks = (longest + R - 1) / R;
+        const int64_t share = FS_BLOCKS / B.n;
+        blocks = blocks > share ? share : blocks;
+        const dim3 grid((unsigned)blocks, B.n), block(FS_THREADS);
+        if (cap == FS_CHUNK)
+          KWY_PROF(ctx, "k_formant_shift", hipLaunchKernelGGL((k_formant_shift<FS_CHUNK / FS_THREADS, 6>), grid, block,
+                                                              0, ctx->stream, B, K, R, rho));
+        else      // (only K = 2049, a 4096-point transform: a row needs the larger buffer)
+          KWY_PROF(ctx, "k_formant_shift", hipLaunchKernelGGL((k_formant_shift<2 * FS_CHUNK / FS_THREADS, 4>), grid,
+                                                              block, 0, ctx->stream, B, K, R, rho));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_formant_shift_batch_dev(kwy_ctx *ctx, const kwy_formant_job *jobs, int count, int K, double rho,

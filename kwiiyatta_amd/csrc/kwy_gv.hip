@@ -19,7 +19,7 @@
 
 #include "kwy_internal.hpp"
 
-#define GV_GROUP 32        // matrices per launch: the job views travel by value in the kernel arguments
+#define GV_GROUP 32        // matrices per launch
 #define GV_MAX_COLS 64
 #define GV_CHUNK 2048      // elements a workgroup of the filter takes per step
 #define GV_MAX_BLOCKS 64   // workgroups per matrix in the filter
@@ -29,10 +29,7 @@ struct gv_mat {
   int64_t rows;
   double *out;             // cols x (n, mean, M2)
 };
-struct gv_mats {
-  int count;
-  gv_mat u[GV_GROUP];
-};
+typedef kwy_group<gv_mat, GV_GROUP> gv_mats;
 
 struct gv_apply {
   const double *x;
@@ -42,10 +39,7 @@ struct gv_apply {
   double *out;
   int32_t *status;         // columns copied for an unusable v or gv (may be NULL)
 };
-struct gv_applies {
-  int count;
-  gv_apply u[GV_GROUP];
-};
+typedef kwy_group<gv_apply, GV_GROUP> gv_applies;
 
 // the row lanes' partials of column slot c (part[lane * slots + c]) added in lane order
 __device__ __forceinline__ double gv_lane_fold(const double *part, int slots, int lanes, int c) {
@@ -185,17 +179,14 @@ static int gv_check_mats(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int
 }
 
 static int gv_launch_moments(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols, double *moments) {
-  for (int i0 = 0; i0 < count; i0 += GV_GROUP) {
-    gv_mats B;
-    B.count = count - i0 < GV_GROUP ? count - i0 : GV_GROUP;
-    for (int u = 0; u < GV_GROUP; ++u)
-      B.u[u] = u < B.count ? gv_mat{mats[i0 + u].x, mats[i0 + u].rows, moments + 3 * (int64_t)cols * (i0 + u)}
-                           : gv_mat{nullptr, 0, nullptr};
-    KWY_PROF(ctx, "k_gv_moments",
-             hipLaunchKernelGGL(k_gv_moments, dim3(B.count), dim3(KWY_THREADS), 0, ctx->stream, B, cols));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<gv_mats>(
+      count, [&](int i) { return gv_mat{mats[i].x, mats[i].rows, moments + 3 * (int64_t)cols * i}; },
+      [&](const gv_mats &B, int) {
+        KWY_PROF(ctx, "k_gv_moments",
+                 hipLaunchKernelGGL(k_gv_moments, dim3(B.n), dim3(KWY_THREADS), 0, ctx->stream, B, cols));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_column_moments_batch_dev(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols,
@@ -277,23 +268,22 @@ static int gv_check_jobs(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int co
 
 static int gv_launch_apply(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col, const double *gv,
                            double strength, int32_t *status) {
-  for (int i0 = 0; i0 < count; i0 += GV_GROUP) {
-    gv_applies B;
-    B.count = count - i0 < GV_GROUP ? count - i0 : GV_GROUP;
-    int64_t longest = 0;
-    for (int u = 0; u < GV_GROUP; ++u) {
-      const kwy_gv_job *j = u < B.count ? jobs + i0 + u : nullptr;
-      B.u[u] = j ? gv_apply{j->x, j->rows, j->moments, j->base, j->out, status ? status + i0 + u : nullptr}
-                 : gv_apply{nullptr, 0, nullptr, nullptr, nullptr, nullptr};
-      if (j && j->rows > longest) longest = j->rows;
-    }
-    int64_t blocks = (longest * cols + GV_CHUNK - 1) / GV_CHUNK;
-    blocks = blocks < 1 ? 1 : (blocks > GV_MAX_BLOCKS ? GV_MAX_BLOCKS : blocks);      // (block 0 writes the status)
-    KWY_PROF(ctx, "k_gv_apply", hipLaunchKernelGGL(k_gv_apply, dim3((unsigned)blocks, B.count), dim3(KWY_THREADS), 0,
-                                                   ctx->stream, B, cols, first_col, gv, strength));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<gv_applies>(
+      count,
+      [&](int i) {
+        const kwy_gv_job &j = jobs[i];
+        return gv_apply{j.x, j.rows, j.moments, j.base, j.out, status ? status + i : nullptr};
+      },
+      [&](const gv_applies &B, int) {
+        int64_t longest = 0;
+        for (int u = 0; u < B.n; ++u) longest = B.u[u].rows > longest ? B.u[u].rows : longest;
+        int64_t blocks = (longest * cols + GV_CHUNK - 1) / GV_CHUNK;
+        blocks = blocks < 1 ? 1 : (blocks > GV_MAX_BLOCKS ? GV_MAX_BLOCKS : blocks);      // (block 0 writes the status)
+        KWY_PROF(ctx, "k_gv_apply", hipLaunchKernelGGL(k_gv_apply, dim3((unsigned)blocks, B.n), dim3(KWY_THREADS), 0,
+                                                       ctx->stream, B, cols, first_col, gv, strength));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_gv_postfilter_batch_dev(kwy_ctx *ctx, const kwy_gv_job *jobs, int count, int cols, int first_col,

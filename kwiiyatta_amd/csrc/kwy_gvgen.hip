@@ -48,10 +48,7 @@ struct gva_job {
   double *objective;
   int32_t *status;
 };
-struct gva_jobs {
-  int n;
-  gva_job u[KWY_BATCH_MAX];
-};
+typedef kwy_group<gva_job, KWY_BATCH_MAX> gva_jobs;
 
 // the butterfly leaves the same bits in every lane (a + b == b + a)
 __device__ __forceinline__ double gva_wave_sum(double s) {
@@ -397,26 +394,30 @@ static int gva_launch_form(kwy_ctx *ctx, const gva_jobs &J, int d, const double 
 
 int kwy_gva_launch(kwy_ctx *ctx, const kwy_gva_view *v, int n, int d, const double *gv_mean, const double *gv_var,
                    double weight, int iterations) {
-  gva_jobs J;
-  J.n = n;
-  int64_t tmax[3] = {0, 0, 0};
-  for (int j = 0; j < n; ++j) {
-    gva_job &q = J.u[j];
-    q = gva_job{v[j].band, v[j].offset, v[j].y, v[j].T, v[j].ldy, v[j].ldo, nullptr, nullptr, v[j].objective,
-                v[j].status};
-    q.work = kwy_arena<double>(ctx, (size_t)d * (iterations + 2));
-    const int form = v[j].T <= GVA_NT * GVA_REG_ROWS ? 0 : (v[j].T <= GVA_LDS_ROWS ? 1 : 2);
-    if (form == 2) q.tracks = kwy_arena<double>(ctx, (size_t)d * 3 * ((size_t)v[j].T + 4));
-    if (!q.work || (form == 2 && !q.tracks)) { ctx->err = "gv_ascent: scratch arena too small"; return KWY_ENOMEM; }
-    tmax[form] = std::max(tmax[form], v[j].T);
-  }
-  for (int j = n; j < KWY_BATCH_MAX; ++j) J.u[j] = J.u[0];
-  if (tmax[0] > 0) KWY_TRY((gva_launch_form<true, true>(ctx, J, d, gv_mean, gv_var, weight, iterations, tmax[0])));
-  if (tmax[1] > 0) KWY_TRY((gva_launch_form<false, true>(ctx, J, d, gv_mean, gv_var, weight, iterations, tmax[1])));
-  if (tmax[2] > 0) KWY_TRY((gva_launch_form<false, false>(ctx, J, d, gv_mean, gv_var, weight, iterations, tmax[2])));
-  hipLaunchKernelGGL(k_gv_fold, dim3(n), dim3(GVA_NT), 0, ctx->stream, J, d, iterations);
-  KWY_HIP(hipGetLastError());
-  return KWY_OK;
+  const auto form = [](int64_t T) { return T <= GVA_NT * GVA_REG_ROWS ? 0 : (T <= GVA_LDS_ROWS ? 1 : 2); };
+  return kwy_for_tables<gva_jobs>(
+      n,
+      [&](int j) {
+        gva_job q{v[j].band, v[j].offset, v[j].y, v[j].T, v[j].ldy, v[j].ldo, nullptr, nullptr, v[j].objective,
+                  v[j].status};
+        q.work = kwy_arena<double>(ctx, (size_t)d * (iterations + 2));
+        if (form(q.T) == 2) q.tracks = kwy_arena<double>(ctx, (size_t)d * 3 * ((size_t)q.T + 4));
+        return q;
+      },
+      [&](const gva_jobs &J, int) {
+        int64_t tmax[3] = {0, 0, 0};
+        for (int j = 0; j < J.n; ++j) {
+          const gva_job &q = J.u[j];
+          if (!q.work || (form(q.T) == 2 && !q.tracks)) { ctx->err = "gv_ascent: scratch arena too small"; return KWY_ENOMEM; }
+          tmax[form(q.T)] = std::max(tmax[form(q.T)], q.T);
+        }
+        if (tmax[0] > 0) KWY_TRY((gva_launch_form<true, true>(ctx, J, d, gv_mean, gv_var, weight, iterations, tmax[0])));
+        if (tmax[1] > 0) KWY_TRY((gva_launch_form<false, true>(ctx, J, d, gv_mean, gv_var, weight, iterations, tmax[1])));
+        if (tmax[2] > 0) KWY_TRY((gva_launch_form<false, false>(ctx, J, d, gv_mean, gv_var, weight, iterations, tmax[2])));
+        hipLaunchKernelGGL(k_gv_fold, dim3(J.n), dim3(GVA_NT), 0, ctx->stream, J, d, iterations);
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 static int gva_check(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int count, int d, const double *gv_mean,
@@ -443,16 +444,12 @@ static int gva_check(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int count, int
 
 static int gva_run(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int count, int d, const double *gv_mean,
                    const double *gv_var, double weight, int iterations, int32_t *status) {
-  for (int j0 = 0; j0 < count; j0 += KWY_BATCH_MAX) {
-    const int n = std::min(KWY_BATCH_MAX, count - j0);
-    kwy_gva_view v[KWY_BATCH_MAX];
-    for (int k = 0; k < n; ++k) {
-      const kwy_gv_ascent_job &q = jobs[j0 + k];
-      v[k] = kwy_gva_view{q.band, q.offset, q.y, q.T, d, d, q.objective, status ? status + j0 + k : nullptr};
-    }
-    KWY_TRY(kwy_gva_launch(ctx, v, n, d, gv_mean, gv_var, weight, iterations));
+  std::vector<kwy_gva_view> v((size_t)count);
+  for (int j = 0; j < count; ++j) {
+    const kwy_gv_ascent_job &q = jobs[j];
+    v[j] = kwy_gva_view{q.band, q.offset, q.y, q.T, d, d, q.objective, status ? status + j : nullptr};
   }
-  return KWY_OK;
+  return kwy_gva_launch(ctx, v.data(), count, d, gv_mean, gv_var, weight, iterations);
 }
 
 static size_t gva_jobs_scratch(const kwy_gv_ascent_job *jobs, int count, int d, int iterations) {

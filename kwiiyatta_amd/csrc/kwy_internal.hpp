@@ -152,25 +152,61 @@ static inline kwy_randn_src kwy_randn(const kwy_ctx *ctx) {
   return kwy_randn_src{ctx->d_randn, ctx->randn_n, ctx->d_pow2};
 }
 
-// --- utterance batches -------------------------------------------------------------
-// The frame-parallel analysis kernels take up to KWY_BATCH_MAX utterances per launch: workgroup g belongs to the
-// utterance u with start[u] <= g < start[u + 1] and handles its frame g - start[u].  The per-utterance pointers travel
-// BY VALUE in the kernel arguments (scalar loads, no descriptor table in device memory, capturable in HIP graphs);
-// one launch over both utterances of a pair -- or over all pairs of a step -- fills the chip where a single
-// utterance's 2 000 frames are 2.2 rounds of resident workgroups.
+// --- job tables ---------------------------------------------------------------------
+// A batched kernel takes the views of up to N jobs (utterances, matrices, signals) per launch, and the views travel BY
+// VALUE in the kernel arguments: scalar loads, no descriptor table in device memory, nothing to upload, capturable in
+// HIP graphs.  A launch's whole argument block must stay under the 4 KB kernel-argument limit: an instantiation near it
+// carries a static_assert on its sizeof where it is declared.
+//   kwy_group<VIEW, N>: the kernel finds its job from the block index alone (u[blockIdx.x], u[blockIdx.y]).
+//   kwy_batch<VIEW, N>: the jobs share one grid dimension: workgroup g belongs to the job u with
+//     start[u] <= g < start[u + 1] and handles its frame (or slice) g - start[u].  One launch over both utterances of a
+//     pair -- or over all pairs of a step -- fills the chip where a single utterance's 2 000 frames are 2.2 rounds of
+//     resident workgroups.
 #define KWY_BATCH_MAX 16
-template <class VIEW>
+#define KWY_KERNARG_MAX 4096
+template <class VIEW, int N>
+struct kwy_group {
+  int n;
+  VIEW u[N];
+};
+template <class VIEW, int N = KWY_BATCH_MAX>
 struct kwy_batch {
   int n;
-  int start[KWY_BATCH_MAX + 1];
-  VIEW u[KWY_BATCH_MAX];
-  // utterance of workgroup g (uniform: scalar loop)
+  int start[N + 1];
+  VIEW u[N];
+  // job of workgroup g (uniform: scalar loop)
   __device__ __forceinline__ int find(int g) const {
     int k = 0;
     while (k + 1 < n && g >= start[k + 1]) ++k;
     return k;
   }
 };
+
+// slot u of a table from job i: view(i) for a group; view(i, blocks) for a batch, which also says how many workgroups
+// the job takes (blocks comes in as 0)
+template <class VIEW, int N, class FILL>
+static inline void kwy_table_fill(kwy_group<VIEW, N> &t, int u, int i, FILL &fill) { t.u[u] = fill(i); }
+template <class VIEW, int N, class FILL>
+static inline void kwy_table_fill(kwy_batch<VIEW, N> &t, int u, int i, FILL &fill) {
+  int blocks = 0;
+  t.u[u] = fill(i, blocks);
+  t.start[u + 1] = t.start[u] + blocks;
+}
+
+// `count` jobs in launches of at most N: every table starts out value-initialised (the slots from n on are zero and
+// null, whatever the kernel), slot u is filled from job i0 + u, and launch(table, i0) -- table.n jobs, the first of them
+// job i0 of the call -- enqueues the kernels; its first return other than KWY_OK ends the walk.
+template <class TABLE, class FILL, class LAUNCH>
+static inline int kwy_for_tables(int count, FILL fill, LAUNCH launch) {
+  constexpr int N = (int)(sizeof(TABLE::u) / sizeof(TABLE::u[0]));
+  for (int i0 = 0; i0 < count; i0 += N) {
+    TABLE t{};
+    t.n = count - i0 < N ? count - i0 : N;
+    for (int u = 0; u < t.n; ++u) kwy_table_fill(t, u, i0 + u, fill);
+    KWY_TRY(launch(t, i0));
+  }
+  return KWY_OK;
+}
 
 // --- GV-considering trajectory generation (kwy_gvgen.hip) ---------------------------------
 // One utterance of the ascent for the conversion entries of kwy_mlpg.hip: the band records of its last solve (a copy:

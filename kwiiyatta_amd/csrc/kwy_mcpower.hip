@@ -21,13 +21,14 @@
 // count slots (the first call makes them): they are legal inside a stream capture from then on.
 #include <math.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "kwy_internal.hpp"
 
 #define MP_ROWS 4                // rows of a matrix per workgroup and step (KWY_THREADS / MP_LD)
 #define MP_NV 8                  // coefficient vectors per step: (reference, filtered) of MP_ROWS rows, or MP_NV rows
 #define MP_LD 64                 // doubles between two vectors in LDS (order <= 63)
-#define MP_JOBS_MAX 64           // matrices per launch: the jobs travel by value in the kernel arguments
+#define MP_JOBS_MAX 64           // matrices per launch
 #define MP_JOB_BLOCKS 1024       // workgroups per matrix; they stride over its rows
 #define MP_SLOTS (MP_JOBS_MAX * MP_JOB_BLOCKS)
 
@@ -40,11 +41,10 @@ struct mp_job {
   double *out;
   int64_t rows;
 };
-struct mp_jobs {
-  int count;
-  int start[MP_JOBS_MAX + 1];   // first workgroup of every job
-  mp_job j[MP_JOBS_MAX];
-};
+typedef kwy_batch<mp_job, MP_JOBS_MAX> mp_jobs;
+static_assert(sizeof(mp_jobs) + 48 <= KWY_KERNARG_MAX, "k_mcpower_filter: the table and six scalar arguments");
+// the table's start[] alone for k_mcpower_status: a kernel that took the whole mp_jobs would find start[] four bytes
+// further on and get 2.8 KB of arguments for 260 bytes it reads
 struct mp_starts {
   int start[MP_JOBS_MAX + 1];
 };
@@ -121,8 +121,8 @@ __global__ __launch_bounds__(KWY_THREADS) void k_mcpower_filter(mp_jobs J, int o
   __shared__ double Es[MP_NV];
   const int tid = threadIdx.x, r = tid / MP_LD, m = tid % MP_LD;
   int u = 0;
-  while (u + 1 < J.count && (int)blockIdx.x >= J.start[u + 1]) ++u;   // uniform: a scalar loop
-  const mp_job &U = J.j[u];
+  while (u + 1 < J.n && (int)blockIdx.x >= J.start[u + 1]) ++u;   // uniform: a scalar loop
+  const mp_job &U = J.u[u];
   const int64_t rows = U.rows;
   const int cols = order + 1;
   const int64_t g = (int)blockIdx.x - J.start[u], G = J.start[u + 1] - J.start[u];
@@ -193,8 +193,8 @@ __global__ __launch_bounds__(KWY_THREADS) void k_mcpower_energy(mp_jobs J, int o
   __shared__ double Es[MP_NV];
   const int tid = threadIdx.x;
   int u = 0;
-  while (u + 1 < J.count && (int)blockIdx.x >= J.start[u + 1]) ++u;
-  const mp_job &U = J.j[u];
+  while (u + 1 < J.n && (int)blockIdx.x >= J.start[u + 1]) ++u;
+  const mp_job &U = J.u[u];
   const int64_t rows = U.rows;
   const int cols = order + 1;
   const int64_t g = (int)blockIdx.x - J.start[u], G = J.start[u + 1] - J.start[u];
@@ -277,52 +277,50 @@ static int mp_run_filter(kwy_ctx *ctx, const kwy_mcpower_job *jobs, int count, i
   int32_t *slots = nullptr;
   KWY_TRY(mp_table(ctx, N, alpha, order, &tab));
   if (status) KWY_TRY(mp_slots(ctx, &slots));
-  for (int i0 = 0; i0 < count; i0 += MP_JOBS_MAX) {
-    mp_jobs J;
-    mp_starts S;
-    J.count = count - i0 < MP_JOBS_MAX ? count - i0 : MP_JOBS_MAX;
-    J.start[0] = 0;
-    for (int u = 0; u < MP_JOBS_MAX; ++u) {
-      const kwy_mcpower_job *q = u < J.count ? jobs + i0 + u : nullptr;
-      J.j[u] = q ? mp_job{q->x, q->ref, q->base, q->out, q->rows} : mp_job{nullptr, nullptr, nullptr, nullptr, 0};
-      J.start[u + 1] = J.start[u] + (q ? mp_blocks(q->rows, MP_ROWS) : 0);
-    }
-    for (int u = 0; u <= MP_JOBS_MAX; ++u) S.start[u] = J.start[u];
-    if (J.start[J.count] > 0) {
-      auto k = N >= 2048 ? k_mcpower_filter<4> : N == 1024 ? k_mcpower_filter<2> : k_mcpower_filter<1>;
-      KWY_PROF(ctx, "k_mcpower_filter", hipLaunchKernelGGL(k, dim3((unsigned)J.start[J.count]), dim3(KWY_THREADS), 0,
-                                                           ctx->stream, J, order, alpha, beta, N / 2, tab, slots));
-      KWY_HIP(hipGetLastError());
-    }
-    if (status) {
-      KWY_PROF(ctx, "k_mcpower_status", hipLaunchKernelGGL(k_mcpower_status, dim3(J.count), dim3(KWY_THREADS), 0,
-                                                           ctx->stream, S, slots, status + i0));
-      KWY_HIP(hipGetLastError());
-    }
-  }
-  return KWY_OK;
+  return kwy_for_tables<mp_jobs>(
+      count,
+      [&](int i, int &blocks) {
+        const kwy_mcpower_job &q = jobs[i];
+        blocks = mp_blocks(q.rows, MP_ROWS);
+        return mp_job{q.x, q.ref, q.base, q.out, q.rows};
+      },
+      [&](const mp_jobs &J, int i0) {
+        if (J.start[J.n] > 0) {
+          auto k = N >= 2048 ? k_mcpower_filter<4> : N == 1024 ? k_mcpower_filter<2> : k_mcpower_filter<1>;
+          KWY_PROF(ctx, "k_mcpower_filter", hipLaunchKernelGGL(k, dim3((unsigned)J.start[J.n]), dim3(KWY_THREADS), 0,
+                                                               ctx->stream, J, order, alpha, beta, N / 2, tab, slots));
+          KWY_HIP(hipGetLastError());
+        }
+        if (status) {
+          mp_starts S;
+          memcpy(S.start, J.start, sizeof(S.start));
+          KWY_PROF(ctx, "k_mcpower_status", hipLaunchKernelGGL(k_mcpower_status, dim3(J.n), dim3(KWY_THREADS), 0,
+                                                               ctx->stream, S, slots, status + i0));
+          KWY_HIP(hipGetLastError());
+        }
+        return KWY_OK;
+      });
 }
 
 static int mp_run_energy(kwy_ctx *ctx, const kwy_energy_job *jobs, int count, int order, double alpha, int N) {
   KWY_HIP(hipSetDevice(ctx->device));
   const double *tab;
   KWY_TRY(mp_table(ctx, N, alpha, order, &tab));
-  for (int i0 = 0; i0 < count; i0 += MP_JOBS_MAX) {
-    mp_jobs J;
-    J.count = count - i0 < MP_JOBS_MAX ? count - i0 : MP_JOBS_MAX;
-    J.start[0] = 0;
-    for (int u = 0; u < MP_JOBS_MAX; ++u) {
-      const kwy_energy_job *q = u < J.count ? jobs + i0 + u : nullptr;
-      J.j[u] = q ? mp_job{q->mc, nullptr, nullptr, q->energy, q->rows} : mp_job{nullptr, nullptr, nullptr, nullptr, 0};
-      J.start[u + 1] = J.start[u] + (q ? mp_blocks(q->rows, MP_NV) : 0);
-    }
-    if (J.start[J.count] == 0) continue;
-    auto k = N >= 2048 ? k_mcpower_energy<4> : N == 1024 ? k_mcpower_energy<2> : k_mcpower_energy<1>;
-    KWY_PROF(ctx, "k_mcpower_energy", hipLaunchKernelGGL(k, dim3((unsigned)J.start[J.count]), dim3(KWY_THREADS), 0,
-                                                         ctx->stream, J, order, N / 2, tab));
-    KWY_HIP(hipGetLastError());
-  }
-  return KWY_OK;
+  return kwy_for_tables<mp_jobs>(
+      count,
+      [&](int i, int &blocks) {
+        const kwy_energy_job &q = jobs[i];
+        blocks = mp_blocks(q.rows, MP_NV);
+        return mp_job{q.mc, nullptr, nullptr, q.energy, q.rows};
+      },
+      [&](const mp_jobs &J, int) {
+        if (J.start[J.n] == 0) return KWY_OK;
+        auto k = N >= 2048 ? k_mcpower_energy<4> : N == 1024 ? k_mcpower_energy<2> : k_mcpower_energy<1>;
+        KWY_PROF(ctx, "k_mcpower_energy", hipLaunchKernelGGL(k, dim3((unsigned)J.start[J.n]), dim3(KWY_THREADS), 0,
+                                                             ctx->stream, J, order, N / 2, tab));
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      });
 }
 
 extern "C" int kwy_mcep_energy_batch_dev(kwy_ctx *ctx, const kwy_energy_job *jobs, int count, int order, double alpha,

@@ -30,7 +30,7 @@ __constant__ double c_pade[21] = {1.0,
                                   1.0, 0.4999273, 0.1067005, 0.01170221, 0.0005656279,
                                   1.0, 0.4999391, 0.1107098, 0.01369984, 0.0009564853, 0.00003041721};
 
-// One signal of a launch: the jobs travel by value in the kernel arguments (capturable, no descriptor in memory).
+// One signal of a launch
 #define MLSA_JOBS_MAX 64
 struct mlsa_job {
   const double *x;    // n samples in
@@ -39,15 +39,13 @@ struct mlsa_job {
   double *y;          // n samples out
   int64_t n, T;
 };
-struct mlsa_jobs {
-  int count;
-  mlsa_job j[MLSA_JOBS_MAX];
-};
+typedef kwy_group<mlsa_job, MLSA_JOBS_MAX> mlsa_jobs;
+static_assert(sizeof(mlsa_jobs) + 24 <= KWY_KERNARG_MAX, "k_mc2b, k_mlsa_filter: the table and three scalar arguments");
 
 // b[m] = c[m]; b[i] = c[i] - a b[i+1]   (pysptk.mc2b, one thread per frame); zero_c0: c[0] is taken as 0
 // (apply_mlsa_filter's `mcep.data[:, 0] = 0`: the filter changes the envelope's shape, not its power)
 __global__ void k_mc2b(mlsa_jobs J, int m, double a, int zero_c0) {
-  const mlsa_job q = J.j[blockIdx.y];
+  const mlsa_job q = J.u[blockIdx.y];
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= q.T) return;
   const double *c = q.mc + t * (m + 1);
@@ -63,10 +61,10 @@ __global__ void k_mc2b(mlsa_jobs J, int m, double a, int zero_c0) {
 // One wavefront (workgroup) per signal of the launch.
 template <int NB, int PD>
 __global__ __launch_bounds__(64) void k_mlsa_filter(mlsa_jobs J, int m, double a, int hop) {
-  const double *__restrict__ x = J.j[blockIdx.x].x;
-  const double *__restrict__ b = J.j[blockIdx.x].b;
-  double *__restrict__ y = J.j[blockIdx.x].y;
-  const int64_t n = J.j[blockIdx.x].n, T = J.j[blockIdx.x].T;
+  const double *__restrict__ x = J.u[blockIdx.x].x;
+  const double *__restrict__ b = J.u[blockIdx.x].b;
+  double *__restrict__ y = J.u[blockIdx.x].y;
+  const int64_t n = J.u[blockIdx.x].n, T = J.u[blockIdx.x].T;
   constexpr int pd = PD;
   constexpr int ML = 8 * NB;
   extern __shared__ double sm[];
@@ -211,12 +209,12 @@ static int mlsa_launch(kwy_ctx *ctx, const mlsa_jobs &J, int m, double a, int pd
   const size_t lds = sizeof(double) * (2 * 72 + 2 * hop);
   void (*kern)(mlsa_jobs, int, double, int) = (pd == 4) ? k_mlsa_filter<NB, 4> : k_mlsa_filter<NB, 5>;
   KWY_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  KWY_PROF(ctx, "k_mlsa_filter", hipLaunchKernelGGL(kern, dim3(J.count), dim3(64), lds, ctx->stream, J, m, a, hop));
+  KWY_PROF(ctx, "k_mlsa_filter", hipLaunchKernelGGL(kern, dim3(J.n), dim3(64), lds, ctx->stream, J, m, a, hop));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
 
-// the filters of J.count signals (J.j[].b: their coefficients), one workgroup each
+// the filters of J.n signals (J.u[].b: their coefficients), one workgroup each
 static int mlsa_core(kwy_ctx *ctx, const mlsa_jobs &J, int m, double a, int pd, int hop) {
   switch ((m - 1 + 7) / 8) {   // links 2..m in blocks of 8
     case 1: return mlsa_launch<1>(ctx, J, m, a, pd, hop);
@@ -231,14 +229,14 @@ static int mlsa_core(kwy_ctx *ctx, const mlsa_jobs &J, int m, double a, int pd, 
 }
 
 static mlsa_jobs mlsa_one(const double *x, int64_t n, const double *mc, double *b, int64_t T, double *y) {
-  mlsa_jobs J;
-  J.count = 1;
-  J.j[0] = mlsa_job{x, mc, b, y, n, T};
+  mlsa_jobs J{};
+  J.n = 1;
+  J.u[0] = mlsa_job{x, mc, b, y, n, T};
   return J;
 }
 
 static int mc2b_launch(kwy_ctx *ctx, const mlsa_jobs &J, int64_t T_max, int order, double alpha, int zero_c0) {
-  hipLaunchKernelGGL(k_mc2b, dim3((unsigned)((T_max + 255) / 256), J.count), dim3(256), 0, ctx->stream, J, order, alpha,
+  hipLaunchKernelGGL(k_mc2b, dim3((unsigned)((T_max + 255) / 256), J.n), dim3(256), 0, ctx->stream, J, order, alpha,
                      zero_c0);
   KWY_HIP(hipGetLastError());
   return KWY_OK;
@@ -286,21 +284,21 @@ extern "C" int kwy_mlsa_filter_batch_dev(kwy_ctx *ctx, const kwy_mlsa_job *jobs,
   }
   KWY_HIP(hipSetDevice(ctx->device));
   KWY_TRY(kwy_arena_begin(ctx, need));
-  for (int i0 = 0; i0 < count; i0 += MLSA_JOBS_MAX) {
-    mlsa_jobs J;
-    J.count = count - i0 < MLSA_JOBS_MAX ? count - i0 : MLSA_JOBS_MAX;
-    int64_t T_max = 0;
-    for (int u = 0; u < J.count; ++u) {
-      const kwy_mlsa_job &q = jobs[i0 + u];
-      double *b = kwy_arena<double>(ctx, (size_t)q.T * (order + 1));
-      if (!b) { ctx->err = "mlsa_filter_batch: scratch arena too small"; return KWY_ENOMEM; }
-      J.j[u] = mlsa_job{q.x, q.mc, b, q.y, q.x_length, q.T};
-      T_max = q.T > T_max ? q.T : T_max;
-    }
-    KWY_TRY(mc2b_launch(ctx, J, T_max, order, alpha, ignore_c0 ? 1 : 0));
-    KWY_TRY(mlsa_core(ctx, J, order, alpha, pd, hopsize));
-  }
-  return KWY_OK;
+  return kwy_for_tables<mlsa_jobs>(
+      count,
+      [&](int i) {
+        const kwy_mlsa_job &q = jobs[i];
+        return mlsa_job{q.x, q.mc, kwy_arena<double>(ctx, (size_t)q.T * (order + 1)), q.y, q.x_length, q.T};
+      },
+      [&](const mlsa_jobs &J, int) {
+        int64_t T_max = 0;
+        for (int u = 0; u < J.n; ++u) {
+          if (!J.u[u].b) { ctx->err = "mlsa_filter_batch: scratch arena too small"; return KWY_ENOMEM; }
+          T_max = J.u[u].T > T_max ? J.u[u].T : T_max;
+        }
+        KWY_TRY(mc2b_launch(ctx, J, T_max, order, alpha, ignore_c0 ? 1 : 0));
+        return mlsa_core(ctx, J, order, alpha, pd, hopsize);
+      });
 }
 
 extern "C" int kwy_mlsa_synthesis(kwy_ctx *ctx, const double *x, int64_t n, const double *b, int64_t T, int order,

@@ -30,7 +30,7 @@
 
 #include "kwy_internal.hpp"
 
-#define MS_GROUP 64        // matrices per launch: the job views travel by value in the kernel arguments
+#define MS_GROUP 64        // matrices per launch
 #define MS_MAX_COLS 64
 
 struct ms_view {
@@ -40,9 +40,8 @@ struct ms_view {
   double *out;             // filter: rows x cols; log-spectra: cols x (L/2 + 1)
   int32_t *status;         // filter: the matrix's word (may be NULL); log-spectra: cols validity words
 };
-struct ms_views {
-  ms_view u[MS_GROUP];
-};
+typedef kwy_group<ms_view, MS_GROUP> ms_views;
+static_assert(sizeof(ms_views) + 64 <= KWY_KERNARG_MAX, "k_ms: the table and eight scalar arguments");
 
 template <int LOG2H>
 struct ms_cfg {
@@ -207,7 +206,7 @@ static int ms_check_rows(kwy_ctx *ctx, int64_t rows, int L, const char *what) {
 }
 
 template <int LOG2H, bool FILTER>
-static int ms_launch_as(kwy_ctx *ctx, const ms_views &B, int count, int cols, int first_col, const double *statsG,
+static int ms_launch_as(kwy_ctx *ctx, const ms_views &B, int cols, int first_col, const double *statsG,
                         const double *statsN, double strength) {
   constexpr int NT = ms_cfg<LOG2H>::NT, H = 1 << LOG2H;
   const kwy_c *twH, *twN, *twP;
@@ -221,21 +220,21 @@ static int ms_launch_as(kwy_ctx *ctx, const ms_views &B, int count, int cols, in
     raised = 1;
   }
   KWY_PROF(ctx, FILTER ? "k_ms_filter" : "k_ms_logspectra",
-           hipLaunchKernelGGL((k_ms<LOG2H, FILTER>), dim3((unsigned)cols, (unsigned)count), dim3(NT), lds, ctx->stream, B,
+           hipLaunchKernelGGL((k_ms<LOG2H, FILTER>), dim3((unsigned)cols, (unsigned)B.n), dim3(NT), lds, ctx->stream, B,
                               cols, first_col, statsG, statsN, strength, twH, twP, twN));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
 
 template <bool FILTER>
-static int ms_launch(kwy_ctx *ctx, int log2h, const ms_views &B, int count, int cols, int first_col,
-                     const double *statsG, const double *statsN, double strength) {
+static int ms_launch(kwy_ctx *ctx, int log2h, const ms_views &B, int cols, int first_col, const double *statsG,
+                     const double *statsN, double strength) {
   switch (log2h) {
-    case 8: return ms_launch_as<8, FILTER>(ctx, B, count, cols, first_col, statsG, statsN, strength);
-    case 9: return ms_launch_as<9, FILTER>(ctx, B, count, cols, first_col, statsG, statsN, strength);
-    case 10: return ms_launch_as<10, FILTER>(ctx, B, count, cols, first_col, statsG, statsN, strength);
-    case 11: return ms_launch_as<11, FILTER>(ctx, B, count, cols, first_col, statsG, statsN, strength);
-    default: return ms_launch_as<12, FILTER>(ctx, B, count, cols, first_col, statsG, statsN, strength);
+    case 8: return ms_launch_as<8, FILTER>(ctx, B, cols, first_col, statsG, statsN, strength);
+    case 9: return ms_launch_as<9, FILTER>(ctx, B, cols, first_col, statsG, statsN, strength);
+    case 10: return ms_launch_as<10, FILTER>(ctx, B, cols, first_col, statsG, statsN, strength);
+    case 11: return ms_launch_as<11, FILTER>(ctx, B, cols, first_col, statsG, statsN, strength);
+    default: return ms_launch_as<12, FILTER>(ctx, B, cols, first_col, statsG, statsN, strength);
   }
 }
 
@@ -254,16 +253,12 @@ static int ms_check_mats(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int
 static int ms_launch_logspectra(kwy_ctx *ctx, int log2h, const kwy_gv_matrix *mats, int count, int cols, double *spectra,
                                 int32_t *valid) {
   const int64_t K = (1 << log2h) + 1;
-  for (int i0 = 0; i0 < count; i0 += MS_GROUP) {
-    ms_views B;
-    const int n = count - i0 < MS_GROUP ? count - i0 : MS_GROUP;
-    for (int u = 0; u < MS_GROUP; ++u)
-      B.u[u] = u < n ? ms_view{mats[i0 + u].x, mats[i0 + u].rows, nullptr, spectra + (int64_t)(i0 + u) * cols * K,
-                               valid + (int64_t)(i0 + u) * cols}
-                     : ms_view{nullptr, 0, nullptr, nullptr, nullptr};
-    KWY_TRY(ms_launch<false>(ctx, log2h, B, n, cols, 0, nullptr, nullptr, 0.0));
-  }
-  return KWY_OK;
+  return kwy_for_tables<ms_views>(
+      count,
+      [&](int i) {
+        return ms_view{mats[i].x, mats[i].rows, nullptr, spectra + (int64_t)i * cols * K, valid + (int64_t)i * cols};
+      },
+      [&](const ms_views &B, int) { return ms_launch<false>(ctx, log2h, B, cols, 0, nullptr, nullptr, 0.0); });
 }
 
 extern "C" int kwy_ms_logspectra_batch_dev(kwy_ctx *ctx, const kwy_gv_matrix *mats, int count, int cols, int L,
@@ -361,17 +356,13 @@ static int ms_check_jobs(kwy_ctx *ctx, const kwy_ms_job *jobs, int count, int co
 static int ms_launch_filter(kwy_ctx *ctx, int log2h, const kwy_ms_job *jobs, int count, int cols, int first_col,
                             const double *statsG, const double *statsN, double strength, int32_t *status) {
   if (status) KWY_HIP(hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)count, ctx->stream));
-  for (int i0 = 0; i0 < count; i0 += MS_GROUP) {
-    ms_views B;
-    const int n = count - i0 < MS_GROUP ? count - i0 : MS_GROUP;
-    for (int u = 0; u < MS_GROUP; ++u) {
-      const kwy_ms_job *j = u < n ? jobs + i0 + u : nullptr;
-      B.u[u] = j ? ms_view{j->x, j->rows, j->base, j->out, status ? status + i0 + u : nullptr}
-                 : ms_view{nullptr, 0, nullptr, nullptr, nullptr};
-    }
-    KWY_TRY(ms_launch<true>(ctx, log2h, B, n, cols, first_col, statsG, statsN, strength));
-  }
-  return KWY_OK;
+  return kwy_for_tables<ms_views>(
+      count,
+      [&](int i) {
+        const kwy_ms_job &j = jobs[i];
+        return ms_view{j.x, j.rows, j.base, j.out, status ? status + i : nullptr};
+      },
+      [&](const ms_views &B, int) { return ms_launch<true>(ctx, log2h, B, cols, first_col, statsG, statsN, strength); });
 }
 
 extern "C" int kwy_ms_postfilter_batch_dev(kwy_ctx *ctx, const kwy_ms_job *jobs, int count, int cols, int first_col,

@@ -24,7 +24,7 @@
 
 #include "kwy_internal.hpp"
 
-#define PITCH_GROUP 64         // job records a table kernel takes by value
+#define PITCH_GROUP 64         // job records per launch of the table kernel
 #define PITCH_MIN_FS 100
 #define PITCH_MAX_FS 128000    // H <= 1280: 6 H doubles of window and template fit 64 KB of LDS
 #define PITCH_MAX_N (1ll << 30)
@@ -38,14 +38,12 @@ struct pitch_rec {
   int32_t *pos;                // K positions (the caller's, or scratch)
   int64_t M, K;
 };
-struct pitch_recs {
-  int count;
-  pitch_rec u[PITCH_GROUP];
-};
+typedef kwy_group<pitch_rec, PITCH_GROUP> pitch_recs;
+static_assert(sizeof(pitch_recs) + 8 <= KWY_KERNARG_MAX, "k_pitch_table: the table and one pointer");
 
 __global__ void k_pitch_table(pitch_recs B, pitch_rec *__restrict__ table) {
   const int i = threadIdx.x;
-  if (i < B.count) table[i] = B.u[i];
+  if (i < B.n) table[i] = B.u[i];
 }
 
 // w[i] = 0.5 - 0.5 cos(2 pi i / L), i < H: the rising half of the Hann window, the weight of the new frame
@@ -251,24 +249,23 @@ static int pitch_run(kwy_ctx *ctx, const kwy_pitch_job *jobs, int count, int fs,
   double *win = kwy_arena<double>(ctx, (size_t)(fs / 100 + 1));
   if (!table || !win) { ctx->err = "pitch_shift: scratch arena too small"; return KWY_EHIP; }
   int64_t longest = 0;
-  for (int i0 = 0; i0 < count; i0 += PITCH_GROUP) {
-    pitch_recs B;
-    B.count = count - i0 < PITCH_GROUP ? count - i0 : PITCH_GROUP;
-    for (int u = 0; u < PITCH_GROUP; ++u) {
-      if (u >= B.count) { B.u[u] = pitch_rec{nullptr, 0, nullptr, nullptr, 0, 0}; continue; }
-      const kwy_pitch_job &j = jobs[i0 + u];
-      const int64_t M = kwy_pitch_stretched_length(j.n, rate), K = kwy_pitch_frames(j.n, fs, rate);
-      int32_t *pos = j.pos;
-      if (!pos) {
-        pos = kwy_arena<int32_t>(ctx, (size_t)K);
-        if (!pos) { ctx->err = "pitch_shift: scratch arena too small"; return KWY_EHIP; }
-      }
-      B.u[u] = pitch_rec{j.x, j.n, j.y, pos, M, K};
-      if (j.n > longest) longest = j.n;
-    }
-    hipLaunchKernelGGL(k_pitch_table, dim3(1), dim3(PITCH_GROUP), 0, ctx->stream, B, table + i0);
-    KWY_HIP(hipGetLastError());
-  }
+  bool starved = false;                // a job's positions did not fit the arena
+  KWY_TRY(kwy_for_tables<pitch_recs>(
+      count,
+      [&](int i) {
+        const kwy_pitch_job &j = jobs[i];
+        const int64_t M = kwy_pitch_stretched_length(j.n, rate), K = kwy_pitch_frames(j.n, fs, rate);
+        int32_t *pos = j.pos ? j.pos : kwy_arena<int32_t>(ctx, (size_t)K);
+        starved = starved || !pos;
+        if (j.n > longest) longest = j.n;
+        return pitch_rec{j.x, j.n, j.y, pos, M, K};
+      },
+      [&](const pitch_recs &B, int i0) {
+        if (starved) { ctx->err = "pitch_shift: scratch arena too small"; return KWY_EHIP; }
+        hipLaunchKernelGGL(k_pitch_table, dim3(1), dim3(PITCH_GROUP), 0, ctx->stream, B, table + i0);
+        KWY_HIP(hipGetLastError());
+        return KWY_OK;
+      }));
   if (longest == 0) return KWY_OK;
   hipLaunchKernelGGL(k_pitch_window, dim3((H + KWY_THREADS - 1) / KWY_THREADS), dim3(KWY_THREADS), 0, ctx->stream, H, win);
   KWY_HIP(hipGetLastError());

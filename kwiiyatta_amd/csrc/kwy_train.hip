@@ -201,19 +201,19 @@ __device__ __forceinline__ void tr_joint_body(const double *__restrict__ xd, con
   if (tid == 0 && n_out) n_out[0] = s_run;
 }
 
-// ---- the kernels: single calls and batches (blockIdx.y or .x = job, descriptors by value) ------------------------
+// ---- the kernels: single calls and batches (blockIdx.y or .x = job) -----------------------------------------------
 #define TR_BATCH 32          // utterances per launch of the small per-utterance kernels
-#define TR_PAIRS 16          // pairs per launch of the row kernels (their views are 128 bytes: 4 KB of arguments at most)
+#define TR_PAIRS 16          // pairs per launch of the row kernels (their views are 128 bytes)
 template <class JOB, int N = TR_BATCH>
-struct tr_jobs { int n; JOB j[N]; };
+using tr_jobs = kwy_group<JOB, N>;
 
 struct tr_trim_view { const double *sp; int64_t T; double *rowsum; int64_t *n_out; };
 __global__ __launch_bounds__(TR_NT) void k_tr_rowsum(tr_jobs<tr_trim_view> b, int K) {
-  const tr_trim_view &q = b.j[blockIdx.y];
+  const tr_trim_view &q = b.u[blockIdx.y];
   tr_rowsum_body(q.sp, q.T, K, q.rowsum);
 }
 __global__ __launch_bounds__(TR_NT) void k_tr_trim(tr_jobs<tr_trim_view> b, double eps) {
-  const tr_trim_view &q = b.j[blockIdx.x];
+  const tr_trim_view &q = b.u[blockIdx.x];
   tr_trim_body(q.rowsum, q.T, eps, q.n_out);
 }
 __global__ __launch_bounds__(TR_NT) void k_tr_align_even(const int32_t *__restrict__ path,
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(TR_NT) void k_tr_joint(const double *__restrict__ x
 //   voiced[t] = WorldSynthesizer.extract_is_voiced on the padded feature (world.py:147-151)
 struct tr_pad_view { const double *f0; int64_t n; double *f0_pad; double *ap_pad; double *voiced; };
 __global__ __launch_bounds__(TR_NT) void k_tr_pad(tr_jobs<tr_pad_view> b, int K, int pad, double lowest_f0) {
-  const tr_pad_view &q = b.j[blockIdx.y];
+  const tr_pad_view &q = b.u[blockIdx.y];
   const int64_t Tp = q.n + 2 * pad;
   const double one = 1.0 - 1e-12;
   // tail rows of the aperiodicity: workgroups 0 .. pad - 1 take one row each
@@ -264,15 +264,16 @@ struct tr_rows_view {
   double *xd, *yd;                   // cap x 3 d
   int64_t cap;
 };
-__global__ __launch_bounds__(TR_NT) void k_tr_rows_align(tr_jobs<tr_rows_view, TR_PAIRS> b, int width, int strict, int use_power,
+typedef tr_jobs<tr_rows_view, TR_PAIRS> tr_rows_table;
+__global__ __launch_bounds__(TR_NT) void k_tr_rows_align(tr_rows_table b, int width, int strict, int use_power,
                                                         int use_vuv, int pad_len) {
-  const tr_rows_view &v = b.j[blockIdx.x];
+  const tr_rows_view &v = b.u[blockIdx.x];
   tr_align_even_body(v.q.path, v.q.path_len, v.q.feat_x, v.q.feat_y, width, strict, use_power, use_vuv, v.q.x_length,
                      v.q.y_length, pad_len, v.pos, v.idx_x, v.idx_y, v.cap, v.n_sel);
 }
 // delta features of the selected rows' static coefficients (c0 dropped), both sides: blockIdx.y = 2 pair + side
-__global__ void k_tr_rows_delta(tr_jobs<tr_rows_view, TR_PAIRS> b, int d) {
-  const tr_rows_view &v = b.j[blockIdx.y >> 1];
+__global__ void k_tr_rows_delta(tr_rows_table b, int d) {
+  const tr_rows_view &v = b.u[blockIdx.y >> 1];
   const int side = blockIdx.y & 1;
   const int64_t n = min(v.n_sel[0], v.cap);
   const int64_t t = blockIdx.x;
@@ -290,27 +291,27 @@ __global__ void k_tr_rows_delta(tr_jobs<tr_rows_view, TR_PAIRS> b, int d) {
     o[2 * d + c] = (1.0 * xm + -2.0 * x0) + 1.0 * xp;
   }
 }
-__global__ __launch_bounds__(TR_NT) void k_tr_rows_count(tr_jobs<tr_rows_view, TR_PAIRS> b, int w, double eps) {
-  const tr_rows_view &v = b.j[blockIdx.x];
+__global__ __launch_bounds__(TR_NT) void k_tr_rows_count(tr_rows_table b, int w, double eps) {
+  const tr_rows_view &v = b.u[blockIdx.x];
   tr_joint_body<false>(v.xd, v.yd, v.n_sel, v.cap, w, eps, nullptr, v.q.n_rows);
 }
 // the pairs' places in the matrix, in pair order behind the cursor; a pair that would not fit is dropped whole and
 // flagged (n_rows = -1 - rows it had)
-__global__ void k_tr_rows_place(tr_jobs<tr_rows_view, TR_PAIRS> b, int64_t *__restrict__ cursor, int64_t capacity_rows,
+__global__ void k_tr_rows_place(tr_rows_table b, int64_t *__restrict__ cursor, int64_t capacity_rows,
                                 int64_t *__restrict__ places) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   int64_t at = cursor[0];
   for (int k = 0; k < b.n; ++k) {
-    const int64_t n = b.j[k].q.n_rows[0];
-    if (at + n > capacity_rows) { places[k] = -1; b.j[k].q.n_rows[0] = -1 - n; continue; }
+    const int64_t n = b.u[k].q.n_rows[0];
+    if (at + n > capacity_rows) { places[k] = -1; b.u[k].q.n_rows[0] = -1 - n; continue; }
     places[k] = at;
     at += n;
   }
   cursor[0] = at;
 }
-__global__ __launch_bounds__(TR_NT) void k_tr_rows_write(tr_jobs<tr_rows_view, TR_PAIRS> b, int w, double eps,
+__global__ __launch_bounds__(TR_NT) void k_tr_rows_write(tr_rows_table b, int w, double eps,
                                                         double *__restrict__ joint, const int64_t *__restrict__ places) {
-  const tr_rows_view &v = b.j[blockIdx.x];
+  const tr_rows_view &v = b.u[blockIdx.x];
   if (places[blockIdx.x] < 0) return;
   tr_joint_body<true>(v.xd, v.yd, v.n_sel, v.cap, w, eps, joint + (size_t)places[blockIdx.x] * 2 * w, nullptr);
 }
@@ -327,20 +328,18 @@ extern "C" int kwy_trim_length_batch_dev(kwy_ctx *ctx, const kwy_trim_job *jobs,
   if (count == 0) return KWY_OK;
   KWY_HIP(hipSetDevice(ctx->device));
   KWY_TRY(kwy_arena_begin(ctx, bytes));
-  for (int j0 = 0; j0 < count; j0 += TR_BATCH) {
-    tr_jobs<tr_trim_view> b;
-    b.n = std::min(TR_BATCH, count - j0);
-    int64_t T = 0;
-    for (int k = 0; k < b.n; ++k) {
-      const kwy_trim_job &q = jobs[j0 + k];
-      b.j[k] = tr_trim_view{q.sp, q.T, kwy_arena<double>(ctx, q.T), q.n_out};
-      if (!b.j[k].rowsum) { ctx->err = "trim_length: scratch"; return KWY_ENOMEM; }
-      T = std::max(T, q.T);
-    }
-    for (int k = b.n; k < TR_BATCH; ++k) b.j[k] = b.j[0];
-    hipLaunchKernelGGL(k_tr_rowsum, dim3((unsigned)((T + 3) / 4), b.n), dim3(TR_NT), 0, ctx->stream, b, K);
-    hipLaunchKernelGGL(k_tr_trim, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, eps);
-  }
+  KWY_TRY(kwy_for_tables<tr_jobs<tr_trim_view>>(
+      count, [&](int j) { return tr_trim_view{jobs[j].sp, jobs[j].T, kwy_arena<double>(ctx, jobs[j].T), jobs[j].n_out}; },
+      [&](const tr_jobs<tr_trim_view> &b, int) {
+        int64_t T = 0;
+        for (int k = 0; k < b.n; ++k) {
+          if (!b.u[k].rowsum) { ctx->err = "trim_length: scratch"; return KWY_ENOMEM; }
+          T = std::max(T, b.u[k].T);
+        }
+        hipLaunchKernelGGL(k_tr_rowsum, dim3((unsigned)((T + 3) / 4), b.n), dim3(TR_NT), 0, ctx->stream, b, K);
+        hipLaunchKernelGGL(k_tr_trim, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, eps);
+        return KWY_OK;
+      }));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
@@ -358,19 +357,16 @@ extern "C" int kwy_train_pad_batch_dev(kwy_ctx *ctx, const kwy_pad_job *jobs, in
   if (count == 0) return KWY_OK;
   KWY_HIP(hipSetDevice(ctx->device));
   const double lowest = fs / ((K - 1) / 2.0) + 1.0;
-  for (int j0 = 0; j0 < count; j0 += TR_BATCH) {
-    tr_jobs<tr_pad_view> b;
-    b.n = std::min(TR_BATCH, count - j0);
-    int64_t Tp = 0;
-    for (int k = 0; k < TR_BATCH; ++k) {
-      const kwy_pad_job &q = jobs[j0 + (k < b.n ? k : 0)];
-      b.j[k] = tr_pad_view{q.f0, q.n, q.f0_pad, q.ap_pad, q.voiced};
-      Tp = std::max(Tp, q.n + 2 * (int64_t)pad_len);
-    }
-    const unsigned g = (unsigned)std::max<int64_t>(pad_len, (Tp + TR_NT - 1) / TR_NT);
-    if (g == 0) continue;              // nothing kept and no pad: nothing to write
-    hipLaunchKernelGGL(k_tr_pad, dim3(g, b.n), dim3(TR_NT), 0, ctx->stream, b, K, pad_len, lowest);
-  }
+  kwy_for_tables<tr_jobs<tr_pad_view>>(
+      count, [&](int j) { return tr_pad_view{jobs[j].f0, jobs[j].n, jobs[j].f0_pad, jobs[j].ap_pad, jobs[j].voiced}; },
+      [&](const tr_jobs<tr_pad_view> &b, int) {
+        int64_t Tp = 0;
+        for (int k = 0; k < b.n; ++k) Tp = std::max(Tp, b.u[k].n + 2 * (int64_t)pad_len);
+        const unsigned g = (unsigned)std::max<int64_t>(pad_len, (Tp + TR_NT - 1) / TR_NT);
+        // (g == 0: nothing kept and no pad, nothing to write)
+        if (g) hipLaunchKernelGGL(k_tr_pad, dim3(g, b.n), dim3(TR_NT), 0, ctx->stream, b, K, pad_len, lowest);
+        return KWY_OK;
+      });
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
@@ -398,32 +394,36 @@ extern "C" int kwy_train_rows_batch_dev(kwy_ctx *ctx, const kwy_train_job *jobs,
   bytes += kwy_pad(sizeof(int64_t) * TR_PAIRS) * (size_t)((count + TR_PAIRS - 1) / TR_PAIRS);
   KWY_HIP(hipSetDevice(ctx->device));
   KWY_TRY(kwy_arena_begin(ctx, bytes));
-  for (int j0 = 0; j0 < count; j0 += TR_PAIRS) {
-    tr_jobs<tr_rows_view, TR_PAIRS> b;
-    b.n = std::min(TR_PAIRS, count - j0);
-    int64_t cap_max = 0;
-    for (int k = 0; k < b.n; ++k) {
-      tr_rows_view &v = b.j[k];
-      v.q = jobs[j0 + k];
-      v.cap = v.q.x_length + v.q.y_length + 4;
-      v.pos = kwy_arena<int32_t>(ctx, v.cap);
-      v.idx_x = kwy_arena<int32_t>(ctx, v.cap);
-      v.idx_y = kwy_arena<int32_t>(ctx, v.cap);
-      v.n_sel = kwy_arena<int64_t>(ctx, 8);
-      v.xd = kwy_arena<double>(ctx, (size_t)v.cap * 3 * d);
-      v.yd = kwy_arena<double>(ctx, (size_t)v.cap * 3 * d);
-      if (!v.pos || !v.idx_x || !v.idx_y || !v.n_sel || !v.xd || !v.yd) { ctx->err = "train_rows: scratch"; return KWY_ENOMEM; }
-      cap_max = std::max(cap_max, v.cap);
-    }
-    for (int k = b.n; k < TR_PAIRS; ++k) b.j[k] = b.j[0];
-    int64_t *places = kwy_arena<int64_t>(ctx, TR_PAIRS);
-    if (!places) { ctx->err = "train_rows: scratch"; return KWY_ENOMEM; }
-    hipLaunchKernelGGL(k_tr_rows_align, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, d + 2, strict, use_power, use_vuv, pad_len);
-    hipLaunchKernelGGL(k_tr_rows_delta, dim3((unsigned)cap_max, 2 * b.n), dim3(64), 0, ctx->stream, b, d);
-    hipLaunchKernelGGL(k_tr_rows_count, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, 3 * d, eps);
-    hipLaunchKernelGGL(k_tr_rows_place, dim3(1), dim3(64), 0, ctx->stream, b, cursor, capacity_rows, places);
-    hipLaunchKernelGGL(k_tr_rows_write, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, 3 * d, eps, joint, places);
-  }
+  KWY_TRY(kwy_for_tables<tr_rows_table>(
+      count,
+      [&](int j) {
+        tr_rows_view v{};
+        v.q = jobs[j];
+        v.cap = v.q.x_length + v.q.y_length + 4;
+        v.pos = kwy_arena<int32_t>(ctx, v.cap);
+        v.idx_x = kwy_arena<int32_t>(ctx, v.cap);
+        v.idx_y = kwy_arena<int32_t>(ctx, v.cap);
+        v.n_sel = kwy_arena<int64_t>(ctx, 8);
+        v.xd = kwy_arena<double>(ctx, (size_t)v.cap * 3 * d);
+        v.yd = kwy_arena<double>(ctx, (size_t)v.cap * 3 * d);
+        return v;
+      },
+      [&](const tr_rows_table &b, int) {
+        int64_t cap_max = 0;
+        for (int k = 0; k < b.n; ++k) {
+          const tr_rows_view &v = b.u[k];
+          if (!v.pos || !v.idx_x || !v.idx_y || !v.n_sel || !v.xd || !v.yd) { ctx->err = "train_rows: scratch"; return KWY_ENOMEM; }
+          cap_max = std::max(cap_max, v.cap);
+        }
+        int64_t *places = kwy_arena<int64_t>(ctx, TR_PAIRS);
+        if (!places) { ctx->err = "train_rows: scratch"; return KWY_ENOMEM; }
+        hipLaunchKernelGGL(k_tr_rows_align, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, d + 2, strict, use_power, use_vuv, pad_len);
+        hipLaunchKernelGGL(k_tr_rows_delta, dim3((unsigned)cap_max, 2 * b.n), dim3(64), 0, ctx->stream, b, d);
+        hipLaunchKernelGGL(k_tr_rows_count, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, 3 * d, eps);
+        hipLaunchKernelGGL(k_tr_rows_place, dim3(1), dim3(64), 0, ctx->stream, b, cursor, capacity_rows, places);
+        hipLaunchKernelGGL(k_tr_rows_write, dim3(b.n), dim3(TR_NT), 0, ctx->stream, b, 3 * d, eps, joint, places);
+        return KWY_OK;
+      }));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }

@@ -275,6 +275,42 @@ def test_f0_error_hand_made_tracks_and_status():
         dist.f0_error(fa.astype(np.float32), fb)
 
 
+EV_GROUP = 16                # utterances per launch (kwy_eval.hip)
+
+
+def test_one_job_more_than_a_launch_holds():
+    """kwy_mcd_batch_dev and kwy_f0_error_batch_dev on EV_GROUP + 1 tiny jobs of unequal size in ONE call each, the
+    job that falls into the second launch without rows: every job equals the same job through the single call,
+    bit for bit, and the words of the last job are written"""
+    import torch
+    from kwiiyatta_amd.backend import distortion as dist
+    rng = np.random.RandomState(41)
+    rows = [1 + i % 5 for i in range(EV_GROUP)] + [0]
+    dev, stream, ctx = _device()
+    up = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)  # noqa: E731
+    pairs = [ec.matrices(rng, n, n, 25) for n in rows]
+    tracks = [ec.f0_tracks(rng, n, n) for n in rows]
+    held = [[up(v) for v in p] for p in pairs + tracks]
+    outs = [torch.full((n,), 7.0, dtype=torch.float64, device=dev) for n in rows]
+    count = len(rows)
+    d_m = torch.full((count, 3), -1.0, dtype=torch.float64, device=dev)
+    d_s = torch.full((count,), -1, dtype=torch.int32, device=dev)
+    dist.mcd_batch_dev(ctx, [dist.mcd_job(a, b, per_row=o) for (a, b), o in zip(held[:count], outs)], 25, d_m, d_s)
+    f_c = torch.full((count, 4), -1, dtype=torch.int64, device=dev)
+    f_m = torch.full((count, 3), -1.0, dtype=torch.float64, device=dev)
+    f_s = torch.full((count,), -1, dtype=torch.int32, device=dev)
+    dist.f0_error_batch_dev(ctx, [dist.f0_error_job(fa, fb) for fa, fb in held[count:]], f_c, f_m, f_s)
+    stream.synchronize()
+    for i, ((a, b), (fa, fb)) in enumerate(zip(pairs, tracks)):
+        m1, s1, r1 = dist.mcd(a, b, per_row=True)
+        assert d_m[i].cpu().numpy().tobytes() == m1.tobytes() and int(d_s[i]) == s1, i
+        assert outs[i].cpu().numpy().tobytes() == r1.tobytes(), i
+        c1, fm1, fs1 = dist.f0_error(fa, fb)
+        assert f_c[i].cpu().numpy().tobytes() == c1.tobytes() and f_m[i].cpu().numpy().tobytes() == fm1.tobytes(), i
+        assert int(f_s[i]) == fs1, i
+    assert d_m[-1].tolist() == [0.0, 0.0, 0.0] and f_c[-1].tolist() == [0, 0, 0, 0]
+
+
 # ---- merging -----------------------------------------------------------------------------------------------------------
 def test_merge_equals_the_fold_and_the_concatenation():
     import torch

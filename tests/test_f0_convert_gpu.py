@@ -173,6 +173,39 @@ def test_out_of_range_sets_the_status_and_raises():
     assert status.cpu().tolist() == [1, 1, 2]
 
 
+F0M_GROUP = 32               # tracks per launch (kwy_f0map.hip)
+
+
+def test_one_track_more_than_a_launch_holds():
+    """kwy_logf0_moments_batch_dev and kwy_f0_map_batch_dev on F0M_GROUP + 1 tiny tracks of unequal length in ONE call
+    each, the track that falls into the second launch without frames: every track equals the same track through the
+    single call, bit for bit, and the words of the last track are written"""
+    import torch
+    from kwiiyatta_amd import _lib
+    from kwiiyatta_amd.backend import f0 as f0map
+    rng = np.random.RandomState(17)
+    tracks = [rng.uniform(70.0, 500.0, size=1 + i % 5) for i in range(F0M_GROUP)] + [np.zeros(0)]
+    for f0 in tracks[::3]:
+        f0[:1] = 0.0
+    stats = (np.log(140.0), 0.2, np.log(190.0), 0.12)
+    dev = torch.device('cuda', 0)
+    stream = torch.cuda.current_stream(dev)
+    ctx = _lib.Context(0, stream=stream.cuda_stream)
+    d_in = [torch.from_numpy(f).to(dev) for f in tracks]
+    d_out = [torch.full_like(t, -1.0) for t in d_in]
+    d_m = torch.full((len(tracks), 3), -1.0, dtype=torch.float64, device=dev)
+    status = torch.full((len(tracks),), -1, dtype=torch.int32, device=dev)
+    f0map.logf0_moments_batch_dev(ctx, d_in, d_m)
+    f0map.map_f0_batch_dev(ctx, d_in, d_out, 16000, stats=torch.tensor(stats, dtype=torch.float64, device=dev), key=3.0,
+                           status=status)
+    stream.synchronize()
+    assert status.cpu().tolist() == [0] * len(tracks)
+    for i, f0 in enumerate(tracks):
+        assert np.array_equal(d_m[i].cpu().numpy(), f0map.logf0_moments([f0])[0]), i
+        assert np.array_equal(d_out[i].cpu().numpy(), f0map.map_f0(f0, 16000, stats=stats, key=3.0)), i
+    assert d_m[-1].tolist() == [0.0, 0.0, 0.0]
+
+
 # ---- the CLIs and the batch path ---------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
 def trained(tmp_path_factory):

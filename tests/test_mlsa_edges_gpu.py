@@ -94,6 +94,36 @@ def test_batch_entry_on_ragged_jobs(ignore_c0):
         assert ratio <= mc.BOUND, (c.name, ratio)
 
 
+MLSA_JOBS_MAX = 64           # signals per launch (kwy_mlsa.hip)
+
+
+def test_batch_entry_on_one_job_more_than_a_launch_holds():
+    """one kwy_mlsa_filter_batch_dev call on MLSA_JOBS_MAX + 1 signals of a few dozen samples and unequal length (the
+    entry takes no empty signal): every job equals kwy_mc2b_dev + kwy_mlsa_synthesis_dev bit for bit"""
+    import torch
+    from kwiiyatta_amd import _lib
+    from kwiiyatta_amd._lib import lib, c_vp
+    ctx = _lib.Context(0)
+    order, alpha, pd, hop = 5, 0.41, 5, 8
+    rng = np.random.default_rng(7)
+    shapes = [(20 + 7 * i % 41, 1 + i % 5) for i in range(MLSA_JOBS_MAX + 1)]        # (samples, frames)
+    dev = [(torch.from_numpy(rng.standard_normal(n) * 0.1).cuda(),
+            torch.from_numpy(rng.standard_normal((T, order + 1)) * 0.05).cuda(),
+            torch.full((n,), float('nan'), dtype=torch.float64, device='cuda')) for n, T in shapes]
+    torch.cuda.synchronize()
+    arr = _lib.job_array(_lib.MlsaJob, [(x, n, m, T, y) for (n, T), (x, m, y) in zip(shapes, dev)])
+    _lib.check(ctx, lib.kwy_mlsa_filter_batch_dev(ctx.handle, arr, len(dev), order, alpha, pd, hop, 0))
+    ctx.sync()
+    for i, ((n, T), (x, m, y)) in enumerate(zip(shapes, dev)):
+        b, y1 = torch.empty_like(m), torch.full_like(y, float('nan'))
+        torch.cuda.synchronize()
+        _lib.check(ctx, lib.kwy_mc2b_dev(ctx.handle, c_vp(m.data_ptr()), T, order, alpha, c_vp(b.data_ptr())))
+        _lib.check(ctx, lib.kwy_mlsa_synthesis_dev(ctx.handle, c_vp(x.data_ptr()), n, c_vp(b.data_ptr()), T, order, alpha,
+                                                   pd, hop, c_vp(y1.data_ptr())))
+        ctx.sync()
+        assert not bool(torch.isnan(y).any()) and torch.equal(y, y1), i
+
+
 @pytest.mark.parametrize('name,change', mc.REFUSALS, ids=[name for name, _ in mc.REFUSALS])
 def test_refusals_leave_the_output_untouched(name, change):
     """KWY_EINVAL from the host entry and from the device entry, nothing written"""

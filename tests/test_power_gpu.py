@@ -179,6 +179,27 @@ def test_forms_batches_runs_and_aliasing_are_bit_equal():
             assert outs[i].cpu().numpy().tobytes() == alone.tobytes(), (count, i)
 
 
+MP_JOBS_MAX = 64             # matrices per launch (kwy_mcpower.hip)
+
+
+def test_energies_of_one_matrix_more_than_a_launch_holds():
+    """kwy_mcep_energy_batch_dev on MP_JOBS_MAX + 1 tiny matrices of unequal rows in ONE call, the matrix that falls
+    into the second launch without rows: every matrix equals the same matrix through the single call, bit for bit"""
+    import torch
+    from kwiiyatta_amd.backend import power
+    order, N, alpha = 24, 1024, 0.41
+    dev, stream, ctx = _device()
+    rng = np.random.default_rng(23)
+    xs = [pc.rows_like_speech(rng, 1 + i % 5, order) for i in range(MP_JOBS_MAX)] + [np.zeros((0, order + 1))]
+    dxs = [torch.from_numpy(x).to(dev) for x in xs]
+    es = [torch.full((len(x) + 1,), -7.0, dtype=torch.float64, device=dev) for x in xs]
+    power.frame_energy_batch_dev(ctx, dxs, es, alpha, N)
+    stream.synchronize()
+    for i, (x, e) in enumerate(zip(xs, es)):
+        got = e.cpu().numpy()
+        assert got[:-1].tobytes() == power.frame_energy(x, alpha, N, ctx=ctx).tobytes() and got[-1] == -7.0, i
+
+
 # ---- rows that cannot be filtered ------------------------------------------------------------------------------------
 def test_status_words_count_the_bad_rows():
     import torch
