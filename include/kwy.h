@@ -768,6 +768,90 @@ int kwy_decode_aperiodicity(kwy_ctx *ctx, const double *coded, int64_t T, int fs
 int kwy_decode_aperiodicity_dev(kwy_ctx *ctx, const double *coded, int64_t T, int fs, int fft_size, int bands,
                                 double *ap);
 
+/* ---- aperiodicity conversion (an addition: the reference renders a converted voice with the source's aperiodicity) ----
+ * The aperiodic component as one more stream of the joint-density GMM conversion (Ohtani et al. 2006: a mixture on band
+ * aperiodicity; sprocket's `codeap` mixture).  B = kwy_aperiodicity_bands(fs) must be >= 1 (fs >= 12 kHz): with B == 0
+ * every entry below returns KWY_EINVAL.
+ *
+ * BAND TRACK of an utterance with aperiodicity ap (T x K, K = fft_size / 2 + 1): S, T x (B + 1).
+ *   c[t, b]    the coded value in dB, k_code_aperiodicity's arithmetic: bit-equal to kwy_code_aperiodicity_dev.
+ *   S[t, 0]    v[t] = 1.0 when (sum_b c[t, b]) / B <= -0.5, else 0.0 -- the sum a left fold, b ascending, compared with
+ *              > -0.5 exactly as k_decode_aperiodicity does: v[t] == 0 exactly for the frames the decoder flattens to
+ *              1 - 1e-12.  D4C writes that row for f0 = 0, so no f0 track is needed; the pad rows of a training item
+ *              (1 - 1e-12) come out unvoiced by themselves.
+ *   S[t, 1..B] c[t, :] for a voiced frame; for an unvoiced one the row of the nearest voiced frame before it, and
+ *              without one that of the nearest voiced frame after it ("hold fill": the delta windows see no 0 dB spike
+ *              at a voicing boundary, in training and in conversion alike).  A track without any voiced frame keeps c.
+ *
+ * TRAINING ROWS of an aligned pair with tracks X, Y and the kept cells (ix[k], iy[k]), k < n -- the lists the
+ * mel-cepstrum rows use (dtw_feature(strict) + align_even's cut): gx[k] = X[ix[k], 1:], gy[k] = Y[iy[k], 1:]; the delta
+ * features of both gathered sequences as kwy_delta_features_dev takes them; row k = [gx, dgx, ddgx | gy, dgy, ddgy][k],
+ * 6 B wide, kept only if X[ix[k], 0] == 1 and Y[iy[k], 0] == 1.  Kept rows go, in order, behind the device cursor
+ * as kwy_train_rows_batch_dev's do; a pair that does not fit is dropped whole with n_rows = -1 - rows.  An index
+ * outside its track reads the track's nearest row.
+ *
+ * CONVERSION: Y^ = kwy_convert_mcep(_batch)_dev(S, d = B, M, model(diff = 0)): arg-max MLPG, column 0 travels through.
+ * Then, IN PLACE over ap: row t with v[t] == 1 becomes the decode of clamp(Y^[t, 1:], -60, -1e-12) with
+ * k_decode_aperiodicity's arithmetic, its flat-row rule included (bit-equal to kwy_decode_aperiodicity_dev on the
+ * clamped row); a row with v[t] == 0 is not written, so an utterance without a voiced frame is left as it is.
+ *
+ * BAND ERROR along an alignment: over the cells voiced on both sides, sqrt(sum_b (a - b)^2 / B) in dB, as the
+ * (n, mean, M2) triples of kwy_mcd_batch_dev (rows, index lists, offsets and n_dev as in kwy_mcd_job; fixed reduction
+ * order).
+ *
+ * The _dev forms allocate nothing and do not synchronise (kwy_bap_rows_batch_dev takes 8 bytes per pair from the
+ * context's scratch arena); the host forms stage through HBM and synchronise. */
+typedef struct kwy_bap_track_job {
+  const double *ap;          /* T x K; a padded training item is one job */
+  int64_t T;
+  double *track;             /* T x (B + 1), written */
+} kwy_bap_track_job;
+int kwy_bap_track(kwy_ctx *ctx, const kwy_bap_track_job *jobs, int count, int fs, int fft_size);
+int kwy_bap_track_dev(kwy_ctx *ctx, const double *ap, int64_t T, int fs, int fft_size, double *track);
+int kwy_bap_track_batch_dev(kwy_ctx *ctx, const kwy_bap_track_job *jobs, int count, int fs, int fft_size);
+typedef struct kwy_bap_rows_job {
+  const double *track_x;     /* x_rows x (B + 1) */
+  int64_t x_rows;
+  const double *track_y;     /* y_rows x (B + 1) */
+  int64_t y_rows;
+  const int32_t *idx_x;      /* capacity cells */
+  const int32_t *idx_y;
+  const int64_t *n_dev;      /* device word with the cell count, clamped to [0, capacity]; NULL: capacity cells (always
+                                NULL in the host form) */
+  int64_t capacity;
+  int64_t *n_rows;           /* 1, written: the rows kept, or -1 - rows for a pair that did not fit */
+} kwy_bap_rows_job;
+/* joint: capacity_rows x 6 B doubles; cursor[0]: rows written so far, read and advanced in job order */
+int kwy_bap_rows(kwy_ctx *ctx, const kwy_bap_rows_job *jobs, int count, int bands, double *joint,
+                 int64_t capacity_rows, int64_t *cursor);
+int kwy_bap_rows_batch_dev(kwy_ctx *ctx, const kwy_bap_rows_job *jobs, int count, int bands, double *joint,
+                           int64_t capacity_rows, int64_t *cursor);
+typedef struct kwy_bap_apply_job {
+  const double *track_src;   /* T x (B + 1): the band track of ap as analysed (its column 0 decides) */
+  const double *track_conv;  /* T x (B + 1): the converted track */
+  int64_t T;
+  double *ap;                /* T x K, voiced rows rewritten in place */
+} kwy_bap_apply_job;
+int kwy_bap_apply(kwy_ctx *ctx, const kwy_bap_apply_job *jobs, int count, int fs, int fft_size);
+int kwy_bap_apply_dev(kwy_ctx *ctx, const double *track_src, const double *track_conv, int64_t T, int fs,
+                      int fft_size, double *ap);
+int kwy_bap_apply_batch_dev(kwy_ctx *ctx, const kwy_bap_apply_job *jobs, int count, int fs, int fft_size);
+typedef struct kwy_bap_error_job {
+  const double *a;           /* a_rows x (B + 1): the track under test */
+  int64_t a_rows;
+  const double *b;           /* b_rows x (B + 1): the track it is measured against */
+  int64_t b_rows;
+  const int32_t *idx_a;      /* as in kwy_mcd_job */
+  const int32_t *idx_b;
+  int64_t off_a, off_b;
+  int64_t rows;
+  const int64_t *n_dev;
+  double *per_row;           /* rows values, written (or NULL): the cell's error, NaN for a cell that does not count */
+} kwy_bap_error_job;
+/* moments: count x 3 doubles, written */
+int kwy_bap_error(kwy_ctx *ctx, const kwy_bap_error_job *jobs, int count, int bands, double *moments);
+int kwy_bap_error_batch_dev(kwy_ctx *ctx, const kwy_bap_error_job *jobs, int count, int bands, double *moments);
+
 /* ---- spectral-axis stretch (another number of bins at the same sampling rate) ------------------------
  * Synthesizer._reshape_feature on log values, as reshape_spectrum_envelope / reshape_aperiodicity call it:
  *   np.exp(scipy.signal.resample_poly(np.hstack((edge x pad, np.log(rows), edge x pad)), new_K, K, axis=1)[:, trim:-trim])

@@ -60,6 +60,25 @@ def postfilter_mcep(mcep, beta=0.0, power_of=None):
     return MelCepstrum(mcep.fs, mcep.frame_period, data)
 
 
+def band_track(feature_or_ap, fs=None):
+    """the band track (frames, B + 1) of a feature set's aperiodicity, or of an aperiodicity matrix (frames, bins) at
+    the sampling rate `fs` (a feature set brings its own): column 0 the voicing flag of the band codec's decoder,
+    columns 1..B the coded bands in dB, unvoiced frames holding the row of the nearest voiced frame (backend.bap,
+    kwy_bap.hip) -- what the converter's band mixture is trained on and converts.  ValueError below 12 kHz"""
+    import numpy as np
+    from .backend import bap
+    if hasattr(feature_or_ap, 'aperiodicity'):
+        if fs is not None and fs != feature_or_ap.fs:
+            raise ValueError(f'band_track: the feature set is at {feature_or_ap.fs} Hz, not at {fs} Hz')
+        fs = feature_or_ap.fs
+        bap.check_rate(fs)
+        feature_or_ap = feature_or_ap.aperiodicity
+    elif fs is None:
+        raise ValueError('band_track: an aperiodicity matrix needs its sampling rate')
+    bap.check_rate(fs)
+    return bap.track(np.ascontiguousarray(feature_or_ap, dtype=np.float64), fs)
+
+
 name = "kwiiyatta_amd"
 
 __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFileDataset',
@@ -73,4 +92,6 @@ __all__ = ['align', 'Config', 'MelCepstrumConverter', 'ParallelDataset', 'WavFil
            # ... and the formant shift beside it: the envelope of a feature set warped along frequency (backend/formant.py)
            'shift_formants',
            # ... and the energy of a mel-cepstrum with the postfilter that renormalises by it (backend/power.py)
-           'mcep_energy', 'postfilter_mcep']
+           'mcep_energy', 'postfilter_mcep',
+           # ... and the band track the aperiodicity conversion works on (backend/bap.py)
+           'band_track']

@@ -192,6 +192,16 @@ SIGNATURES = {
     'kwy_code_aperiodicity_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     'kwy_decode_aperiodicity': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp]),
     'kwy_decode_aperiodicity_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_int, c_vp]),
+    'kwy_bap_track': (c_int, [c_vp, c_vp, c_int, c_int, c_int]),
+    'kwy_bap_track_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    'kwy_bap_track_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int]),
+    'kwy_bap_rows': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp]),
+    'kwy_bap_rows_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp]),
+    'kwy_bap_apply': (c_int, [c_vp, c_vp, c_int, c_int, c_int]),
+    'kwy_bap_apply_dev': (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
+    'kwy_bap_apply_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int]),
+    'kwy_bap_error': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
+    'kwy_bap_error_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_vp]),
     'kwy_stretch_log': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     'kwy_stretch_log_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp]),
     'kwy_np_state_bytes': (c_i64, []),
@@ -334,6 +344,16 @@ McdJob = _job_struct('McdJob', 'kwy_mcd_job: one utterance of a mel-cepstral dis
 F0ErrorJob = _job_struct('F0ErrorJob', 'kwy_f0_error_job: one pair of f0 tracks of an f0 / voicing error call',
                          [('f0_a', c_vp), ('a_length', c_i64), ('f0_b', c_vp), ('b_length', c_i64), ('idx_a', c_vp),
                           ('idx_b', c_vp), ('off_a', c_i64), ('off_b', c_i64), ('rows', c_i64), ('n_dev', c_vp)])
+BapTrackJob = _job_struct('BapTrackJob', 'kwy_bap_track_job: the band track of one aperiodicity matrix',
+                          [('ap', c_vp), ('T', c_i64), ('track', c_vp)])
+BapRowsJob = _job_struct('BapRowsJob', 'kwy_bap_rows_job: the band training rows of one aligned pair',
+                         [('track_x', c_vp), ('x_rows', c_i64), ('track_y', c_vp), ('y_rows', c_i64), ('idx_x', c_vp),
+                          ('idx_y', c_vp), ('n_dev', c_vp), ('capacity', c_i64), ('n_rows', c_vp)])
+BapApplyJob = _job_struct('BapApplyJob', 'kwy_bap_apply_job: converted bands decoded over one aperiodicity matrix',
+                          [('track_src', c_vp), ('track_conv', c_vp), ('T', c_i64), ('ap', c_vp)])
+BapErrorJob = _job_struct('BapErrorJob', 'kwy_bap_error_job: one pair of band tracks of a band error call',
+                          [('a', c_vp), ('a_rows', c_i64), ('b', c_vp), ('b_rows', c_i64), ('idx_a', c_vp), ('idx_b', c_vp),
+                           ('off_a', c_i64), ('off_b', c_i64), ('rows', c_i64), ('n_dev', c_vp), ('per_row', c_vp)])
 SynthPlanJob = _job_struct('SynthPlanJob', 'kwy_synth_plan_job: the pulse placement of one utterance',
                            [('f0', c_vp), ('f0_length', c_i64), ('y_length', c_i64), ('plan', c_vp)])
 

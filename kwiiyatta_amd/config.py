@@ -233,6 +233,32 @@ POWER_OPTIONS = (
 )
 
 
+def ap_components(text):
+    """--ap-components: the components of the band-aperiodicity mixture, a positive integer"""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid component count: {text!r}') from None
+    if n < 1:
+        raise argparse.ArgumentTypeError(f'{text} is not a positive component count')
+    return n
+
+
+# an addition to the reference's options (it renders a converted voice with the source's aperiodicity)
+APERIODICITY_OPTIONS = (
+    ('--convert-aperiodicity', dict(action='store_true',
+                                    help='Convert the aperiodicity as well: a second joint-density mixture on the band '
+                                         'aperiodicity of the voiced frames of the same aligned pairs (Ohtani et al. 2006), '
+                                         'kept in the converter model; the converted bands replace the voiced frames of '
+                                         'the analysed aperiodicity.  Needs a sampling rate of 12 kHz or more.  Only the '
+                                         'synthesised output (.synth.wav) changes: the differential output (.diff.wav) is '
+                                         'a filtered waveform and keeps the source\'s aperiodic component')),
+    ('--ap-components', dict(type=ap_components, default=16, metavar='N',
+                             help='Components of the band-aperiodicity mixture trained with --convert-aperiodicity '
+                                  '(default 16); a loaded converter model decides')),
+)
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -278,6 +304,9 @@ class Config:
 
     def add_power_arguments(self):
         self._declare(POWER_OPTIONS)
+
+    def add_aperiodicity_arguments(self):
+        self._declare(APERIODICITY_OPTIONS)
 
     def add_argument(self, *args, **kwargs):
         self.parser.add_argument(*args, **kwargs)
@@ -374,12 +403,19 @@ class Config:
         sides = [k.WavFileDataset(self.source_path, Analyzer=source), k.WavFileDataset(self.target_path, Analyzer=analyze)]
         return k.align(*sides)
 
-    def train_converter(self, f0_stats=False, gv_stats=False, ms_stats=False, gv_var=False, **kwargs):
+    def train_converter(self, f0_stats=False, gv_stats=False, ms_stats=False, gv_var=False, ap_model=False, **kwargs):
         """f0_stats=True / gv_stats=True / ms_stats=True: training also computes the f0 statistics / the target's global
         variance / the modulation-spectrum statistics at --ms-length (and the model file keeps them); a loaded model
         without them is a parser error.  gv_var=True (--mlpg-gv): gv_stats, and a loaded model must also hold the
-        variance of the global variance"""
+        variance of the global variance.  ap_model=True (--convert-aperiodicity): training also fits the band-aperiodicity
+        mixture of --ap-components components; a loaded model without it is a parser error, and so is a --mcep-fs below
+        12 kHz (no band), before a file is read"""
         gv_stats = gv_stats or gv_var
+        if ap_model and self.mcep_fs is not None:
+            from .backend import bap
+            if bap.bands(self.mcep_fs) < 1:
+                self.parser.error(f'--convert-aperiodicity needs a sampling rate of 12 kHz or more: --mcep-fs '
+                                  f'{self.mcep_fs} has no aperiodicity band')
         converter = self.create_converter(**kwargs)
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
@@ -412,13 +448,16 @@ class Config:
             if ms_stats and converter.ms_stats is None:
                 self.parser.error(f'{model}: the converter model has no modulation spectrum statistics; retrain it '
                                   f'with --ms (a new --converter-model file)')
+            if ap_model and converter.ap_converter is None:
+                self.parser.error(f'{model}: the converter model has no band-aperiodicity mixture; retrain it with '
+                                  f'--convert-aperiodicity (a new --converter-model file)')
             return converter
-        converter = self._train(converter, f0_stats=f0_stats, gv_stats=gv_stats, ms_stats=ms_stats)
+        converter = self._train(converter, f0_stats=f0_stats, gv_stats=gv_stats, ms_stats=ms_stats, ap_model=ap_model)
         if model is not None:
             converter.save(model)
         return converter
 
-    def _train(self, converter, f0_stats=False, gv_stats=False, ms_stats=False):
+    def _train(self, converter, f0_stats=False, gv_stats=False, ms_stats=False, ap_model=False):
         converter.source_f0_rate = self._model_f0_rate = self.resolve_source_f0_rate()
         dataset = self.load_dataset(converter.source_f0_rate)
         keys = sorted(dataset.keys())[slice(self.skip_files, None)]
@@ -429,5 +468,7 @@ class Config:
             extra.update(ms_stats=True, ms_length=getattr(self, 'ms_length', None) or 4096)
         if getattr(self, 'align_iterations', None):
             extra['align_iterations'] = self.align_iterations
+        if ap_model:
+            extra.update(ap_model=True, ap_components=getattr(self, 'ap_components', None) or 16)
         converter.train(dataset, keys[:self.max_files], **extra)
         return converter

@@ -52,7 +52,13 @@ sharpens the over-smoothed envelope frame by frame with the mel-cepstral formant
 mcpf and keeps the frame's energy -- the source's with `--keep-power`, its own otherwise.  Both run after `--ms`, `--gv`
 and `--mlpg-gv`.  For the .diff.wav output the corrected c0 travels as its difference from the source's c0 in column 0
 of the differential mel-cepstrum, and the differential filter takes that column into account
-(`apply_diff_filter(..., use_c0=True)`).  Neither option writes anything to the converter model."""
+(`apply_diff_filter(..., use_c0=True)`).  Neither option writes anything to the converter model.
+`--convert-aperiodicity` renders the .synth.wav outputs on the source's aperiodicity converted to the target speaker's:
+training fits a second mixture (`--ap-components`, kept in the converter model) on the band aperiodicity of the voiced
+frames of the same aligned pairs, and `convert(..., convert_ap=True)` decodes the converted bands over the voiced frames
+of the analysed aperiodicity (converter.convert_aperiodicity, backend.bap, kwy_bap.hip).  It needs a sampling rate of
+12 kHz or more and does not reach the .diff.wav output (a filtered waveform); with `--batch` the three calls run on
+the wave's side stream behind D4C (corpus.convert_batch(ap_gmm=...))."""
 import pathlib
 from types import SimpleNamespace
 
@@ -64,7 +70,7 @@ OUTPUTS = (('diff', True), ('synth', False))          # suffix, differential?
 
 # what a command can ask of a conversion, under the names of its arguments (Config), and what it asks by default
 COMMAND_OPTIONS = dict(convert_f0=False, transpose_key=0.0, gv=0.0, ms=0.0, formant_shift=0.0, mlpg_em=None, mlpg_gv=None,
-                       diff_filter='mlsa', postfilter=0.0, keep_power=False)
+                       diff_filter='mlsa', postfilter=0.0, keep_power=False, convert_ap=False)
 
 
 def driver_options(converter, asked):
@@ -100,11 +106,16 @@ def convert(conf, converter, src_path, diffvc=True, **options):
     (apply_diff_filter(method='fft')); the synthesised output ignores it.
     postfilter > 0 / keep_power: the formant emphasis of that beta and / or the source's frame energies on the converted
     mel-cepstrum (converter.convert(postfilter=..., keep_power=...), either output); the differential filter then runs
-    with use_c0=True, on the change of c0 the conversion hands over in column 0."""
+    with use_c0=True, on the change of c0 the conversion hands over in column 0.
+    convert_ap: the synthesised output on the aperiodicity converted by the converter's band mixture
+    (converter.convert_aperiodicity; needs a converter trained with ap_model=True at 12 kHz or more); the differential
+    output is a filtered waveform and keeps the source's aperiodic component."""
     import kwiiyatta_amd as k
     o = SimpleNamespace(**filled(options, COMMAND_OPTIONS))
     if not 0.0 <= o.postfilter <= 1.0:          # (raises before the file is read)
         raise ValueError(f'postfilter: beta {o.postfilter!r} is outside [0, 1]')
+    if o.convert_ap:                            # (raises before the file is read)
+        check_convert_ap(converter)
     power = o.postfilter > 0 or o.keep_power
     # converter.convert's keywords: (value, whether it is on) -- an option that is off is not handed over
     stages = dict(gv=(o.gv, o.gv > 0), ms=(o.ms, o.ms > 0), em=(o.mlpg_em, o.mlpg_em is not None),
@@ -126,7 +137,18 @@ def convert(conf, converter, src_path, diffvc=True, **options):
                                    key=o.transpose_key)
     if o.formant_shift != 0:
         rendered.shift_formants(2.0 ** (o.formant_shift / 12))
+    if o.convert_ap:
+        rendered.aperiodicity = converter.convert_aperiodicity(source)
     return rendered.synthesize()
+
+
+def check_convert_ap(converter):
+    """what convert_ap needs of a converter, without reading a file: a sampling rate with an aperiodicity band and the
+    band mixture (ValueError otherwise)"""
+    from .backend import bap
+    bap.check_rate(converter.fs)
+    if getattr(converter, 'ap_converter', None) is None:
+        raise ValueError('convert_ap: the converter has no band-aperiodicity mixture (train it with ap_model=True)')
 
 
 def analyze_source(conf, converter, path):
@@ -188,11 +210,14 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, **options):
     diff_filter='fft': the .diff.wav outputs through the frame-parallel FFT filter instead of the MLSA filter
     (corpus.convert_batch(diff_filter='fft'): all frames of a wave's files in one launch).
     postfilter > 0 / keep_power: both outputs from the emphasised / power-corrected mel-cepstra (as `convert` does;
-    corpus.convert_batch(postfilter_beta=..., keep_power=...))."""
+    corpus.convert_batch(postfilter_beta=..., keep_power=...)).
+    convert_ap: the .synth.wav outputs on the converted aperiodicity (as `convert` does; corpus.convert_batch(ap_gmm=...))."""
     import kwiiyatta_amd as k
     from . import corpus
     o = SimpleNamespace(**filled(options, COMMAND_OPTIONS))
     corpus._postfilter_beta(o.postfilter)          # (raises before any file is read)
+    if o.convert_ap:
+        check_convert_ap(converter)               # (raises before any file is read)
     if o.mlpg_gv is not None:
         converter.gv_ascent_statistics()          # (raises before any file is read)
     from ._lib import lib
@@ -218,6 +243,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, **options):
             waves = shift_waves_dev(waves, fs, rate)
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
                                    frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
+                                   ap_gmm=converter.ap_converter.gmm if o.convert_ap else None,
                                    **driver_options(converter, o))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
@@ -252,10 +278,13 @@ def main():
     conf.add_mlpg_gv_argument()
     conf.add_diff_filter_argument()
     conf.add_power_arguments()
+    conf.add_aperiodicity_arguments()
     conf.add_converter_arguments()          # (--source-f0-rate among them)
     conf.parse_args()
+    conf.convert_ap = conf.convert_aperiodicity
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
-                                     ms_stats=conf.ms > 0, **(dict(gv_var=True) if conf.mlpg_gv is not None else {}))
+                                     ms_stats=conf.ms > 0, **(dict(gv_var=True) if conf.mlpg_gv is not None else {}),
+                                     **(dict(ap_model=True) if conf.convert_ap else {}))
     asked = {name: getattr(conf, name) for name in COMMAND_OPTIONS}
     batched = convert_synth_batch(conf, converter, [pathlib.Path(n) for n in conf.files], diffvc=not conf.no_diffvc,
                                   **asked) if conf.batch else {}

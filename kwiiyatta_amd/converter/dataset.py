@@ -82,12 +82,14 @@ class PaddedSide:
     """What re-alignment needs of one padded side of a pair, and nothing else: its mel-cepstrum (frames, order + 1) and
     its voicing decision -- no envelopes.  It answers the questions `vocoder.align.make_feature` asks of a feature set"""
 
-    def __init__(self, feature):
+    def __init__(self, feature, bands=False):
         record = feature.mel_cepstrum
         self.fs, self.frame_period, self.order = feature.fs, feature.frame_period, record.order
         self.mel_cepstrum_data = np.ascontiguousarray(record.data, dtype=np.float64)
         self.is_voiced = np.array(feature.is_voiced, dtype=bool)
         self.frame_len = len(self.is_voiced)
+        # bands=True: also the band track of its aperiodicity (frames, bands + 1), for the band mixture's rows
+        self.band_track = _pkg().band_track(feature) if bands else None
 
     def resample_mel_cepstrum(self, fs):
         if fs != self.fs:
@@ -107,9 +109,10 @@ class PaddedDataset(abc.MapDataset):
     expand_tuple = False
     with_key = True
 
-    def __init__(self, base, pad_len=100):
+    def __init__(self, base, pad_len=100, bands=False):
         super().__init__(base)
         self.pad_len = pad_len
+        self.bands = bands           # keep the sides' band tracks too (`PaddedSide.band_track`)
         self.sides = {}
 
     def function(self, features, key):
@@ -117,7 +120,7 @@ class PaddedDataset(abc.MapDataset):
             raise ValueError(f'PaddedDataset: "{key}" was padded before; its pads are drawn once (read `sides`)')
         pad = _pkg().pad_silence
         pair = tuple(pad(f, self.pad_len) for f in features)
-        self.sides[key] = tuple(PaddedSide(f) for f in pair)
+        self.sides[key] = tuple(PaddedSide(f, bands=self.bands) for f in pair)
         return pair
 
 

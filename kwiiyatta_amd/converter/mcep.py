@@ -84,9 +84,13 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         # the re-alignment passes the training ran (`train(align_iterations=...)`) and its record, a dict per fit
         self.align_iterations = 0
         self.align_history = []
+        # the band-aperiodicity stack (`train(ap_model=True)`: delta stage > joint GMM on the band rows of the aligned
+        # pairs, used by `convert_aperiodicity`) and the rows its fit saw; None / 0 without one
+        self.ap_converter = None
+        self.ap_rows = 0
 
     def train(self, dataset, keys, f0_stats=False, gv_stats=False, align_iterations=0, ms_stats=False, ms_length=4096,
-              **kwargs):
+              ap_model=False, ap_components=16, **kwargs):
         """f0_stats=True: also the voiced log-f0 statistics of both sides (`f0_stats`, used by `convert_f0`).
         gv_stats=True: also the target side's global variance (`gv_stats`, order + 1 values: per coefficient the mean
         over the training utterances of its variance within the utterance; used by `convert(gv=...)`) and `gv_var`, the
@@ -97,14 +101,28 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         3): per coefficient and modulation-frequency bin the count, mean and M2 over the training utterances of the log
         modulation spectrum -- N of the target side's mel-cepstra, G of the source side's converted by the mixture just
         fitted (`convert(..., diff=False)`); used by `convert(ms=...)`).  ms_length: the transform length, which no
-        utterance may exceed (`ms_length`)"""
+        utterance may exceed (`ms_length`)
+        ap_model=True: also a mixture of `ap_components` components (the converter's covariance structure, random
+        state and stopping rule) on the band aperiodicity of the same aligned pairs (`ap_converter`, used by
+        `convert_aperiodicity`; include/kwy.h, "aperiodicity conversion"): the rows pair the two sides' band tracks along
+        the kept cells that are voiced on both sides -- with align_iterations > 0 along the LAST alignment.  It takes the
+        padded-pair path of the re-alignment for any align_iterations (an aligned dataset that pads its pairs itself,
+        both sides at the converter's sampling rate, which must be 12 kHz or more: ValueError otherwise)"""
         if isinstance(align_iterations, bool) or int(align_iterations) != align_iterations or align_iterations < 0:
             raise ValueError(f'align_iterations must be a non-negative integer, not {align_iterations!r}')
         self.align_iterations, self.align_history = int(align_iterations), []
         if ms_stats:
             self._check_ms_lengths(dataset, keys, ms_length)          # (before the fit is paid for)
-        if self.align_iterations > 0:
-            self._train_realigned(dataset, list(keys), self.align_iterations, kwargs)
+        self.ap_converter, self.ap_rows = None, 0
+        if ap_model:
+            if isinstance(ap_components, bool) or int(ap_components) != ap_components or ap_components < 1:
+                raise ValueError(f'ap_components must be a positive integer, not {ap_components!r}')
+            if self.mcep_fs is not None:
+                from ..backend import bap
+                bap.check_rate(self.mcep_fs)                           # (before a file is read)
+        if self.align_iterations > 0 or ap_model:
+            self._train_realigned(dataset, list(keys), self.align_iterations, kwargs,
+                                  ap_components=int(ap_components) if ap_model else None)
         else:
             coefficients = MelCepstrumDataset(dataset, mcep_fs=self.mcep_fs)
             self.base.train(coefficients, keys, **kwargs)
@@ -161,7 +179,46 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                                  f'two frames and with every coefficient varying)')
         self.ms_stats, self.ms_length = (stats_g, stats_n), int(length)
 
-    def _train_realigned(self, dataset, keys, iterations, fit_options):
+    def _band_stack(self, components):
+        """an untrained band stack: delta stage > joint GMM of `components` components with this converter's covariance
+        structure, random state and iteration limit"""
+        from .delta import DeltaFeatureConverter
+        from .gmm import GMMFeatureConverter
+        main = self.gmm
+        return DeltaFeatureConverter(GMMFeatureConverter(
+            components=components, max_iter=getattr(main, 'max_iter', 100), random_state=getattr(main, 'random_state', None),
+            covariance=getattr(main, 'covariance_structure', 'full')))
+
+    def convert_aperiodicity(self, feature):
+        """the aperiodicity (frames, bins) for synthesising a converted voice: a copy of the feature set's whose voiced
+        frames are the decode of its band track converted by the band mixture (arg-max MLPG, no EM / GV / MS; the bands
+        clamped to [-60, -1e-12] dB); unvoiced frames are the feature set's own.  The feature set must be at the
+        converter's sampling rate and frame period"""
+        from ..backend import bap
+        ap = np.array(feature.aperiodicity, dtype=np.float64, order='C')
+        if not len(ap):
+            return ap
+        source, converted = self.convert_band_track(feature, ap=ap)
+        return bap.apply(source, converted, ap, self.fs)
+
+    def convert_band_track(self, feature, ap=None):
+        """(the band track of the feature set's aperiodicity, the converted band track): (frames, B + 1) each, column 0
+        -- the voicing flag -- the same in both, the converted bands clamped to [-60, -1e-12] dB"""
+        from ..backend import bap
+        if self.ap_converter is None:
+            raise ValueError('convert_aperiodicity: the converter has no band mixture (train it with ap_model=True)')
+        if feature.fs != self.fs:
+            raise ValueError(f'convert_aperiodicity: the feature set is at {feature.fs} Hz, the converter at {self.fs} Hz')
+        B = bap.check_rate(self.fs)
+        if self.ap_converter.gmm.means_.shape[1] != 6 * B:
+            raise ValueError(f'convert_aperiodicity: the band mixture does not have the {B} band(s) of {self.fs} Hz')
+        if ap is None:
+            ap = np.ascontiguousarray(feature.aperiodicity, dtype=np.float64)
+        source = bap.track(ap, self.fs)
+        bands = self.ap_converter.convert(np.ascontiguousarray(source[:, 1:]), raw=feature, diff=False)
+        return source, np.ascontiguousarray(np.hstack((source[:, :1], bap.clamp(bands))), dtype=np.float64)
+
+    def _train_realigned(self, dataset, keys, iterations, fit_options, ap_components=None):
         """Iterative re-alignment of the training set (Toda et al.'s joint-feature iterations): fit 0 is the training
         of align_iterations=0 on the same rows -- every pair trimmed, padded (the pads are drawn ONCE, here, in
         today's order) and aligned on the two speakers' own DTW features.  Then, `iterations` times over, every pair
@@ -174,7 +231,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         the path was found with (fit 0: the source's own; fit k: converted by fit k - 1).
         The dataset must be an AlignedDataset chain with silence pads; pairs whose alignment would not run at the
         converter's sampling rate raise ValueError (nothing is resampled here)."""
-        from ..backend import distortion as dist
+        from ..backend import bap, distortion as dist
         from ..backend.mlpg import DELTA_WINDOWS, delta_features
         from ..vocoder.align import even_indices
         from .dataset import AlignedDataset, PaddedDataset, remove_zeros_frames
@@ -182,12 +239,13 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         stage = dataset
         while not isinstance(stage, AlignedDataset) and isinstance(stage, abc.MapDataset):
             stage = stage.base
+        who = 'align_iterations > 0' if iterations > 0 else 'ap_model=True'     # (whichever brought the caller here)
         if not isinstance(stage, AlignedDataset):
-            raise ValueError('align_iterations > 0 needs an aligned dataset (kwiiyatta_amd.align / align_dataset)')
+            raise ValueError(f'{who} needs an aligned dataset (kwiiyatta_amd.align / align_dataset)')
         options = dict(stage.kwargs)
         if not options.pop('pad_silence', True) or options.pop('padded', False):
-            raise ValueError('align_iterations > 0 needs an alignment that pads its pairs with silence itself')
-        padded = PaddedDataset(stage.base, pad_len=options.pop('pad_len', 100))
+            raise ValueError(f'{who} needs an alignment that pads its pairs with silence itself')
+        padded = PaddedDataset(stage.base, pad_len=options.pop('pad_len', 100), bands=ap_components is not None)
         delta_stage = self.base
         while not isinstance(delta_stage, DeltaFeatureConverter) and isinstance(delta_stage, abc.MapFeatureConverter):
             delta_stage = delta_stage.base
@@ -196,7 +254,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         k = _pkg()
         self.order, self.fs = None, self.mcep_fs
         for it in range(iterations + 1):
-            blocks, triples = [], []
+            blocks, triples, band_blocks = [], [], []
             for key in keys:
                 if it == 0:
                     padded[key]                      # draws the pair's pads and keeps its `sides`
@@ -209,6 +267,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                     if x.order != self.order or y.order != self.order:
                         raise ValueError(f'align_iterations: "{key}" has mel-cepstra of order {x.order} and {y.order}, '
                                          f'the converter of order {self.order}')
+                    if ap_components is not None and key == keys[0]:
+                        bap.check_rate(self.fs)
                     if not x.fs == y.fs == self.fs:
                         raise ValueError(f'align_iterations: "{key}" is aligned at {min(x.fs, y.fs)} Hz (source {x.fs} Hz, '
                                          f'target {y.fs} Hz) but the converter works at {self.fs} Hz; re-alignment does '
@@ -232,14 +292,29 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 blocks.append(remove_zeros_frames(np.hstack(sides)))
                 lists = [np.ascontiguousarray(v, dtype=np.int32) for v in (xs, ys)]
                 triples.append(dist.mcd(mapped, y.data, idx_a=lists[0], idx_b=lists[1])[0])
+                if ap_components is not None and it == iterations:        # the band rows follow the last alignment
+                    joint, n, _ = bap.rows(x.band_track, y.band_track, lists[0], lists[1])
+                    band_blocks.append(joint[:n])
             matrix = np.concatenate(blocks)
             self._train(matrix, **fit_options)
+            if band_blocks:
+                band_matrix = np.concatenate(band_blocks)
+                if len(band_matrix) < ap_components:
+                    raise ValueError(f'ap_model: the aligned pairs have {len(band_matrix)} cell(s) voiced on both sides, '
+                                     f'fewer than the {ap_components} components of the band mixture')
+                stack = self._band_stack(ap_components)
+                stack.frame_period = getattr(delta_stage, 'frame_period', x.frame_period)
+                stack._train(band_matrix, **fit_options)
+                self.ap_converter, self.ap_rows = stack, len(band_matrix)
             cells = float(sum(t[0] for t in triples))
             total = 0.0
             for t in triples:
                 total += float(t[0]) * float(t[1])
             self.align_history.append(dict(rows=len(matrix), mcd=total / cells if cells > 0 else float('nan'),
                                            em_iterations=int(getattr(self.gmm, 'n_iter_', 0))))
+        if ap_components is not None and self.ap_converter is None:
+            raise ValueError(f'ap_model: the band rows follow the last alignment (fit {iterations}), which this training '
+                             f'did not reach: no band mixture was fitted')
 
     def convert_f0(self, f0, key=0.0, fs=None):
         """the f0 track for synthesising a converted voice: voiced frames through the log-Gaussian transform of
@@ -257,7 +332,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         training set (mel-cepstrum order, sampling rate, frame period; the f0 statistics, the global variance and the
         modulation-spectrum statistics when there are any; the pitch ratio of the source waveforms; the re-alignment passes of the training as
         `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`; the structure of
-        the covariances as `covariance` when it is not 'full')"""
+        the covariances as `covariance` when it is not 'full'; the band-aperiodicity mixture as `ap_weights`, `ap_means`,
+        `ap_covariances` and `ap_covariance` when there is one)"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
@@ -271,6 +347,10 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             structure = getattr(gmm, 'covariance_structure', 'full')
             if structure != 'full':          # (a full model's file is what it was before structures existed)
                 extra['covariance'] = structure
+            if self.ap_converter is not None:      # (a model without the band mixture has none of these keys)
+                band = self.ap_converter.gmm
+                extra.update(ap_weights=band.weights_, ap_means=band.means_, ap_covariances=band.covariances_,
+                             ap_covariance=getattr(band, 'covariance_structure', 'full'))
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      source_f0_rate=float(self.source_f0_rate),
@@ -310,6 +390,18 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                                   for n in ('ms_stats_g', 'ms_stats_n')) if has_ms else None
             self.ms_length = int(z['ms_length']) if has_ms else None
             self.source_f0_rate = float(z['source_f0_rate']) if 'source_f0_rate' in z.files else 1.0
+            self.ap_converter, self.ap_rows = None, 0
+            if 'ap_weights' in z.files:
+                stack = self._band_stack(len(z['ap_weights']))
+                band = stack.gmm
+                band.weights_ = np.array(z['ap_weights'], dtype=np.float64)
+                band.means_ = np.array(z['ap_means'], dtype=np.float64)
+                band.covariances_ = np.array(z['ap_covariances'], dtype=np.float64)
+                band.covariance_structure = str(z['ap_covariance']) if 'ap_covariance' in z.files else 'full'
+                band.converged_ = True
+                period = float(z['frame_period'])
+                stack.frame_period = int(period) if period.is_integer() else period
+                self.ap_converter = stack
             self.align_iterations = int(z['align_iterations']) if 'align_iterations' in z.files else 0
             mcd = z['align_mcd'] if 'align_mcd' in z.files else ()
             rows = z['align_rows'] if 'align_rows' in z.files else [None] * len(mcd)

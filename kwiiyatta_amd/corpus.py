@@ -171,9 +171,13 @@ class TrainWave:
                       behind the sink's device-side cursor
     `frame_period` is accepted and ignored: the frames come with the f0 tracks."""
 
-    def __init__(self, ls, fs, pairs, order=24, radius=32, frame_period=5.0):
+    def __init__(self, ls, fs, pairs, order=24, radius=32, frame_period=5.0, bands=False):
         self.ls, self.fs, self.order, self.radius = ls, int(fs), int(order), int(radius)
         dev = ls.dev
+        self.bands = 0
+        if bands:                    # the band tracks of the padded items as well (`align`): B + 1 doubles per frame
+            from .backend import bap
+            self.bands = bap.check_rate(self.fs)
         self.fft = lib.kwy_cheaptrick_fft_size(self.fs, 71.0)
         self.K = K = self.fft // 2 + 1
         from .backend import sptk
@@ -195,6 +199,7 @@ class TrainWave:
             self.voiced = torch.empty(rows, **f64)
             self.mc_pad = torch.empty((rows, order + 1), **f64)
             self.feat = torch.empty((rows, order + 2), **f64)
+            self.track = torch.empty((rows, self.bands + 1), **f64) if self.bands else None
             ns = len(sides)
             self.keep_dev = torch.zeros(ns, dtype=torch.int64, device=dev)
             self.keep_host = torch.zeros(ns, dtype=torch.int64).pin_memory()
@@ -219,12 +224,13 @@ class TrainWave:
             self.keep_ready = torch.cuda.Event()
             self.keep_ready.record(ls.main)
 
-    def finish(self, sink, pads, cache=None):
+    def finish(self, sink, pads, cache=None, band_sink=None):
         """pads(rows): fills the wave's pad rows -- a list of 4 n device views (source head, source tail, target
         head, target tail, pair after pair) -- on the main stream.  cache: a TrainCache that takes over the wave's
-        alignment inputs (and its share of the monitor of this first alignment), or None"""
+        alignment inputs (and its share of the monitor of this first alignment), or None.  band_sink: the `_RowSink` of
+        the band matrix (a wave made with bands=True), or None"""
         a = self.align(pads)
-        a.rows_into(sink)
+        a.rows_into(sink, band_sink)
         if cache is not None:
             cache.add(a)
 
@@ -245,20 +251,24 @@ class TrainWave:
             J = _lib.job_array
             chk(lib.kwy_train_pad_batch_dev(h, J(_lib.PadJob, [(self.f0[i], keep[i], reg(self.f0_pad, i), reg(self.ap_pad, i),
                                                                reg(self.voiced, i)) for i in range(ns)]), ns, K, fs, P))
+            if self.bands:       # every padded item is one job: its pad rows (1 - 1e-12) come out unvoiced by themselves
+                chk(lib.kwy_bap_track_batch_dev(h, J(_lib.BapTrackJob, [(reg(self.ap_pad, i), Tp[i], reg(self.track, i))
+                                                                        for i in range(ns)]), ns, fs, self.fft))
             chk(lib.kwy_sp2mc_dev(h, _p(self.sp_pad), self.rows, K, order, self.alpha, _p(self.mc_pad)))
             # make_feature(vuv='voiced', power='binalize', power_pivot='max')
             chk(lib.kwy_align_features_batch_dev(h, J(_lib.AlignJob, [(reg(self.mc_pad, i), reg(self.voiced, i), Tp[i],
                                                                        reg(self.feat, i)) for i in range(ns)]),
                                                  ns, order + 1, POWER_WEIGHT, POWER_THRESHOLD, VUV_WEIGHT))
-        inputs = _AlignInputs(self.n, self.layout, Tp, keep, self.mc_pad, self.feat, self.voiced, order)
+        inputs = _AlignInputs(self.n, self.layout, Tp, keep, self.mc_pad, self.feat, self.voiced, order, self.track)
         self.alignment = _Alignment(ls, inputs, self.radius)
         return self.alignment
 
 
-class _AlignInputs(namedtuple('_AlignInputs', 'n layout Tp keep mc_pad feat voiced order')):
+class _AlignInputs(namedtuple('_AlignInputs', 'n layout Tp keep mc_pad feat voiced order track', defaults=(None,))):
     """What a wave of `n` pairs hands to an alignment, and all a TrainCache keeps of it: the padded mel-cepstra, the DTW
     features and the voicing -- blocks in the wave's ragged `layout`, item 2 k the source, 2 k + 1 the target of pair
-    k --, the padded lengths `Tp` in use and the frames `keep` that TrimmedDataset kept"""
+    k --, the padded lengths `Tp` in use and the frames `keep` that TrimmedDataset kept; `track`: the band tracks of the
+    padded items in the same layout ((B + 1) * 8 bytes per padded frame), or None for a wave made without bands"""
     __slots__ = ()
 
 
@@ -282,9 +292,12 @@ class _Alignment:
                                              self.dist[k:k + 1], self.path[k], self.path_len[k:k + 1]) for k in range(n)]),
                 n, inputs.order + 2, radius))
 
-    def rows_into(self, sink):
+    def rows_into(self, sink, band_sink=None):
         """enqueue dtw_feature(strict=True) + align_even's cut, deltas, hstack + remove_zeros_frames and the append
-        behind the cursor of the `_RowSink` for every pair; `n_rows`: the pairs' row counts, device words"""
+        behind the cursor of the `_RowSink` for every pair; `n_rows`: the pairs' row counts, device words.
+        band_sink: the `_RowSink` of the band matrix: the band rows of the same kept cells (`index_lists`) that are
+        voiced on both sides go behind its cursor (kwy_bap_rows_batch_dev), `n_band_rows` their counts; the inputs must
+        carry the band tracks (ValueError otherwise)"""
         ls, inp, feat = self.ls, self.inputs, self.feat
         Tp, reg = inp.Tp, inp.layout.view
         with torch.cuda.stream(ls.main):
@@ -295,6 +308,18 @@ class _Alignment:
                                                 reg(inp.mc_pad, 2 * k), reg(inp.mc_pad, 2 * k + 1), Tp[2 * k], Tp[2 * k + 1],
                                                 self.n_rows[k:k + 1]) for k in range(inp.n)]),
                 inp.n, inp.order, 1, 1, 1, PAD_LEN, TRIM_EPS, _p(sink.X), sink.X.shape[0], _p(sink.cursor)))
+            if band_sink is not None:
+                from .backend import bap
+                if inp.track is None:
+                    raise ValueError('band rows: this alignment\'s inputs carry no band tracks (the wave, or the cache '
+                                     'it came from, was made without bands=True)')
+                idx_x, idx_y, cap, n_sel = self.index_lists()
+                self.n_band_rows = torch.zeros(inp.n, dtype=torch.int64, device=ls.dev)
+                bap.rows_batch_dev(ls.ctx, [bap.rows_job(reg(inp.track, 2 * k)[:Tp[2 * k]], reg(inp.track, 2 * k + 1)[:Tp[2 * k + 1]],
+                                                         idx_x[k], idx_y[k], self.n_band_rows[k:k + 1], n_dev=n_sel[k:k + 1],
+                                                         capacity=cap[k]) for k in range(inp.n)],
+                                   band_sink.X.shape[1] // 6, band_sink.X, band_sink.cursor)
+                band_sink.take(self.n_band_rows)
 
     def index_lists(self, n_sel=None):
         """enqueue dtw_feature(strict=True) + align_even's cut of every pair: -> (idx_x, idx_y, cap, n_sel), per pair the
@@ -383,7 +408,8 @@ class TrainCache:
 
     pairs = property(lambda self: sum(w.n for w in self.waves))
     frames = property(lambda self: sum(sum(w.Tp) for w in self.waves))
-    nbytes = property(lambda self: sum(t.numel() * 8 for w in self.waves for t in (w.mc_pad, w.feat, w.voiced)))
+    nbytes = property(lambda self: sum(t.numel() * 8 for w in self.waves for t in (w.mc_pad, w.feat, w.voiced, w.track)
+                                       if t is not None))
 
     def add(self, alignment):
         self.waves.append(alignment.inputs)
@@ -392,7 +418,7 @@ class TrainCache:
         alignment.monitor(self.monitor)
 
 
-def realign_training_matrix(cache, gmm, paths=None):
+def realign_training_matrix(cache, gmm, paths=None, bands=False):
     """One re-alignment pass over a cached training set with the fitted mixture `gmm`: -> (X, mcd_mean).
     The mixture is prepared once (kwy_gmm_prepare_dev); then, wave by wave (<= 16 pairs), the sources' padded
     mel-cepstra are converted -- deltas, mixture, MLPG: `MelCepstrumFeatureConverter.convert(..., diff=False)` -- straight
@@ -400,13 +426,19 @@ def realign_training_matrix(cache, gmm, paths=None):
     features stay as they are, power and voicing terms are the source's own), FastDTW runs on them against the targets'
     unchanged features, and the joint rows of the ORIGINAL mel-cepstra along the new paths go behind a device-side
     cursor (kwy_train_rows_batch_dev).  mcd_mean: the monitor of this alignment (`_Alignment.monitor`).  One read-back.
-    paths: a list that receives, pair after pair, the (FastDTW path, its length) device tensors of this pass."""
+    paths: a list that receives, pair after pair, the (FastDTW path, its length) device tensors of this pass.
+    bands=True: -> (X, mcd_mean, band matrix): the band rows along this pass's alignment as well; the cache must hold the
+    band tracks (`build_training_matrix(keep=True, bands=True)`), ValueError otherwise, before anything is enqueued."""
     import struct
+    if bands and any(w.track is None for w in cache.waves):
+        raise ValueError('realign_training_matrix(bands=True): the cache holds no band tracks, so the band rows cannot '
+                         'follow this alignment (build it with build_training_matrix(keep=True, bands=True))')
     ls, order, dev = cache.ls, cache.order, cache.ls.dev
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
     if dg.D2 != 6 * order:
         raise ValueError(f'realign_training_matrix: the mixture has {dg.D2} joint dimensions, the cache order {order}')
     sink = _RowSink(ls, cache.frames, order)      # a pair yields at most one row per cell of its path
+    band_sink = _RowSink(ls, cache.frames, cache.waves[0].track.shape[1] - 1) if bands and cache.waves else None
     with torch.cuda.stream(ls.main):
         model = dg.model(diff=False)
         acc = torch.zeros(2, dtype=torch.float64, device=dev)
@@ -417,7 +449,7 @@ def realign_training_matrix(cache, gmm, paths=None):
                 ls.ctx.handle, _lib.job_array(_lib.RealignJob, [(reg(w.mc_pad, 2 * k), w.Tp[2 * k], reg(feat, 2 * k))
                                                                 for k in range(w.n)]), w.n, order, dg.M, _p(model)))
             a = _Alignment(ls, w, cache.radius, feat=feat)
-            a.rows_into(sink)
+            a.rows_into(sink, band_sink)
             a.monitor(acc)
             sink.take(a.n_rows)
             # (the wave's scratch -- feat, path, ... -- was made on the main stream: freed here, reused there in order)
@@ -425,20 +457,25 @@ def realign_training_matrix(cache, gmm, paths=None):
                 paths.extend((a.path[k], a.path_len[k:k + 1]) for k in range(w.n))
     X, words = sink.close(extra=(acc.view(torch.int64),))
     total, cells = struct.unpack('<2d', struct.pack('<2q', *words))
-    return X, (total / cells if cells > 0 else float('nan'))
+    mcd = total / cells if cells > 0 else float('nan')
+    return (X, mcd, band_sink.close()[0]) if band_sink is not None else (X, mcd)
 
 
 def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterations=0, max_iter=100, device_index=0,
                               order=24, radius=32, frame_period=5.0, silence_for=None, rng=None, pairs_before=0,
                               driver=None, lockstep=None, wave_pairs=16, f0_moments=False, gv_moments=False, verbose=0,
-                              keep_matrices=False, covariance='full'):
+                              keep_matrices=False, covariance='full', ap_components=None):
     """Training with iterative re-alignment on the device: `build_training_matrix(keep=True)` and `fit_converter`, then
     `align_iterations` times `realign_training_matrix` with the mixture fitted last and `fit_converter` on its rows,
     from scratch (same components, seed, stopping rule, `covariance` structure).  The pads are drawn once -- numpy's global generator or the
     device-drawn stream (`rng`, `pairs_before`) advance as they do for align_iterations = 0 -- and the f0 / global
     variance moments are the first pass's.  Returns (mixture, history[, f0 moments][, gv statistic]): history holds a
     dict per fit -- rows, mcd (the alignment's monitor, `_Alignment.monitor`), em_iterations -- and with keep_matrices=True
-    its matrix X.  Lockstep driver only."""
+    its matrix X.  Lockstep driver only.
+    ap_components=N: also the band-aperiodicity mixture of N components (same seed, stopping rule, structure), fitted as
+    it is on the band rows of the LAST alignment (`build_training_matrix(bands=True)` / `realign_training_matrix(bands=
+    True)`); it is the last result.  Those rows exist only once the last pass has run: a pass whose cache holds no band
+    tracks raises the ValueError of `realign_training_matrix`, which says so."""
     n_more = int(align_iterations)
     if n_more < 0:
         raise ValueError(f'align_iterations {align_iterations!r} is negative')
@@ -447,9 +484,10 @@ def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterati
     out = build_training_matrix(pairs, fs, device_index=device_index, order=order, radius=radius, frame_period=frame_period,
                                 silence_for=silence_for, rng=rng, pairs_before=pairs_before, driver=driver,
                                 lockstep=lockstep, wave_pairs=wave_pairs, f0_moments=f0_moments, gv_moments=gv_moments,
-                                keep=n_more > 0)
+                                keep=n_more > 0, bands=ap_components is not None)
     X, rest = out[0], list(out[2:])
     cache = rest.pop(0) if n_more > 0 else None
+    Xb = rest.pop(0) if ap_components is not None else None
     history = []
 
     def fit(X, mcd):
@@ -464,8 +502,12 @@ def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterati
         first = total / cells if cells > 0 else float('nan')
     g = fit(X, first)
     for _ in range(n_more):
-        X, mcd = realign_training_matrix(cache, g)
+        X, mcd, *band = realign_training_matrix(cache, g, bands=ap_components is not None)
+        Xb = band[0] if band else Xb
         g = fit(X, mcd)
+    if ap_components is not None:
+        rest.append(fit_converter(Xb, components=ap_components, seed=seed, max_iter=max_iter, device_index=device_index,
+                                  verbose=verbose, covariance=covariance))
     return (g, history, *rest)
 
 
@@ -478,10 +520,12 @@ class EvalWave(TrainWave):
     counts stay device words).  Nothing is read back here: `measure` writes pair k's figures into row first + k of the
     caller's tensors.  `frame_period` is accepted and ignored, as in TrainWave."""
 
-    def measure(self, pads, gmm, model, tot, first, opts, frames='speech', per_frame=False):
+    def measure(self, pads, gmm, model, tot, first, opts, frames='speech', per_frame=False, ap_gmm=None):
         """tot: the _EvalTotals of the corpus; opts: the resolved options (`ConvertOptions.upload`) -- of them the f0
         map, the global-variance postfilter (`_GvFilter`), mlpg_em and the GV ascent, whose status words go where the
-        postfilter's would (the two exclude each other)"""
+        postfilter's would (the two exclude each other).  ap_gmm (a DeviceGMM; the wave made with bands=True): also the
+        band error of the source's band track, converted (clamped as the rendering clamps it) and unconverted, against
+        the target's along the same index lists, into tot.bap (kwy_bap_error_batch_dev)"""
         mlpg_em, gvgen = opts.mlpg_em, opts.gvgen
         from .backend import distortion as dist
         a = self.align(pads)
@@ -531,16 +575,33 @@ class EvalWave(TrainWave):
             dist.f0_error_batch_dev(ls.ctx, [dist.f0_error_job(src_f0[k], tgt_f0[k], self.idx_x[k], self.idx_y[k], P, P,
                                                                rows=cap[k], n_dev=n_sel[k:k + 1]) for k in range(n)],
                                     tot.counts[first:first + n], tot.f0[first:first + n], tot.f0_status[first:first + n])
+            if ap_gmm is not None:
+                from .backend import bap
+                B = self.bands
+                src_tr = [reg(self.track, 2 * k)[P:P + keep[2 * k]] for k in range(n)]
+                tgt_tr = [reg(self.track, 2 * k + 1)[P:P + keep[2 * k + 1]] for k in range(n)]
+                self.track_conv = torch.empty((own.total, B + 1), **f64)
+                mapped = own.views(self.track_conv)
+                chk(lib.kwy_convert_mcep_batch_dev(h, J(_lib.ConvertJob, [(src_tr[k], keep[2 * k], mapped[k]) for k in range(n)]),
+                                                   n, B, ap_gmm.M, _p(ap_gmm.model(diff=False))))
+                self.track_conv[:, 1:].clamp_(bap.FLOOR, bap.CEILING)
+                jobs = []
+                for k in range(n):
+                    along = dict(idx_a=self.idx_x[k], idx_b=self.idx_y[k], off_a=P, off_b=P, rows=cap[k], n_dev=n_sel[k:k + 1])
+                    jobs.append(bap.error_job(mapped[k], tgt_tr[k], **along))
+                    jobs.append(bap.error_job(src_tr[k], tgt_tr[k], **along))
+                bap.error_batch_dev(ls.ctx, jobs, B, tot.bap[first:first + n].view(-1, 3))
 
 
 class _EvalTotals:
     """the figures of a corpus's pairs in HBM, a row per pair: the (n, mean, M2) triples of the distortion (converted,
     unconverted source) and of the f0 error, the voicing counts, the aligned frames and the status words"""
 
-    def __init__(self, n_pairs, dev):
+    def __init__(self, n_pairs, dev, bands=False):
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         self.mcd = torch.zeros((n_pairs, 2, 3), **f64)
+        self.bap = torch.zeros((n_pairs, 2, 3), **f64) if bands else None     # band error: converted, unconverted source
         self.f0 = torch.zeros((n_pairs, 3), **f64)
         self.counts = torch.zeros((n_pairs, 4), dtype=torch.int64, device=dev)
         self.aligned = torch.zeros(n_pairs, dtype=torch.int64, device=dev)
@@ -549,9 +610,10 @@ class _EvalTotals:
 
     def read(self, ctx):
         """(enqueued behind the waves on ctx's stream) the pooled triples from the merge kernel, then everything to the
-        host: (triples (n_pairs + 1, 3, 3) with the totals last, counts, aligned, status words (n_pairs, 5))"""
+        host: (triples (n_pairs + 1, 3, 3) with the totals last -- (n_pairs + 1, 5, 3) with the band error's two behind
+        them --, counts, aligned, status words (n_pairs, 5))"""
         from .backend import distortion as dist
-        triples = torch.cat((self.mcd, self.f0[:, None]), dim=1).contiguous()
+        triples = torch.cat((self.mcd, self.f0[:, None]) + (() if self.bap is None else (self.bap,)), dim=1).contiguous()
         both = torch.cat((triples, torch.zeros_like(triples[:1])))
         dist.merge_moments_dev(ctx, triples, both[-1])
         status = torch.cat((self.mcd_status, self.f0_status[:, None], self.gv_status[:, None],
@@ -855,12 +917,18 @@ class ConvertWave:
     conversion in place (MS or GV; it then has no GV ascent and offset 0, and takes those filters' changes of the plain
     conversion before the plain rows are overwritten), and without such a filter after the rendering (with the ascent
     options, offset 1).  With formant_ratio = 1, and with the power filter's options both neutral, no kernel is launched
-    and no buffer added."""
+    and no buffer added.
+    ap_gmm (a DeviceGMM over 6 B dimensions, B the aperiodicity bands of fs; None: off, no call, buffer or status word
+    is added): the aperiodicity the rendering reads is converted too -- band track, prepared-model MLPG at d = B and the
+    in-place apply (kwy_bap_track / kwy_convert_mcep / kwy_bap_apply _batch_dev) on the SIDE stream right behind D4C,
+    beside the mel-cepstrum conversion on the main stream; `ap_all` then holds the converted rows.  Independent of
+    `gmm`; the differential outputs do not read the aperiodicity."""
 
     @takes_options()
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
-                 resolved=None, **options):
+                 resolved=None, ap_gmm=None, **options):
         converting = gmm is not None
+        self.ap_gmm = ap_gmm
         opts = resolved or ConvertOptions(**options).check(order, converting).upload(ls.dev, converting)
         self.opts, self.mlpg_em, self.gvgen, self.gvgen_status = opts, opts.mlpg_em, opts.gvgen, None
         self.ls, self.fs, self.order, self.frame_period = ls, int(fs), int(order), float(frame_period)
@@ -922,6 +990,17 @@ class ConvertWave:
             self.j_ap = _lib.utterance_array([(self.x[i], self.t[i], self.f0[i], ap[i]) for i in range(n)])
             self.j_plan = _lib.job_array(_lib.SynthPlanJob, [(self.f0_synth[i], self.T[i], self.ylen[i], self.plan[i])
                                                              for i in range(n)])
+            if ap_gmm is not None:
+                from .backend import bap
+                self.bands = B = bap.check_rate(self.fs)
+                if ap_gmm.D2 != 6 * B:
+                    raise ValueError(f'ap_gmm has {ap_gmm.D2} joint dimensions, {self.fs} Hz has {B} band(s): {6 * B}')
+                self.ap_model = ap_gmm.model(diff=False)
+                self.ap_src, self.ap_conv = (torch.empty((self.rows, B + 1), **f64) for _ in range(2))
+                src, mapped = rows.views(self.ap_src), rows.views(self.ap_conv)
+                self.j_bap = (_lib.job_array(_lib.BapTrackJob, [(ap[i], self.T[i], src[i]) for i in range(n)]),
+                              _lib.job_array(_lib.ConvertJob, [(src[i], self.T[i], mapped[i]) for i in range(n)]),
+                              _lib.job_array(_lib.BapApplyJob, [(src[i], mapped[i], self.T[i], ap[i]) for i in range(n)]))
             if converting:
                 self.mc_conv = torch.empty((self.rows, order + 1), **f64)
                 self.sp_conv = torch.empty((self.rows, K), **f64)
@@ -990,6 +1069,12 @@ class ConvertWave:
         with torch.cuda.stream(ls.side):
             hs = ls.side_ctx.handle
             _lib.check(ls.side_ctx, lib.kwy_d4c_batch_dev(hs, self.j_ap, n, fs, 0.85, fft))
+            if self.ap_gmm is not None:
+                track, convert, apply = self.j_bap
+                _lib.check(ls.side_ctx, lib.kwy_bap_track_batch_dev(hs, track, n, fs, fft))
+                _lib.check(ls.side_ctx, lib.kwy_convert_mcep_batch_dev(hs, convert, n, self.bands, self.ap_gmm.M,
+                                                                       _p(self.ap_model)))
+                _lib.check(ls.side_ctx, lib.kwy_bap_apply_batch_dev(hs, apply, n, fs, fft))
             if self.f0_map_status is not None:
                 from .backend.f0 import key_ratio
                 _lib.check(ls.side_ctx, lib.kwy_f0_map_batch_dev(
@@ -1087,19 +1172,19 @@ def _check_status_words(items, fs):
 
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, opts, wave_size=16, pcm=False,
-                    diff=False):
+                    diff=False, ap_gmm=None):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.  opts: a checked `ConvertOptions`, uploaded
     here once for all waves.
     Bare waveforms get their f0 on the device; the status words of all waves are read back ONCE at the end
-    (`_check_status_words`)."""
+    (`_check_status_words`).  ap_gmm: a DeviceGMM for every wave's aperiodicity conversion (`ConvertWave`), or None."""
     ls = ls if ls is not None else _Lockstep(device_index)
     resolved = opts.upload(ls.dev, converting=gmm is not None)
     defer = bool(diff) and gmm is not None and resolved.diff_filter == 'mlsa'
     held, deferred, status = [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
-                         diff=diff, defer_mlsa=defer, resolved=resolved)
+                         diff=diff, defer_mlsa=defer, resolved=resolved, ap_gmm=ap_gmm)
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -1226,7 +1311,7 @@ def _pair_uploads(pairs, dev):
 
 def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
                           silence_for=None, pool=None, rng=None, pairs_before=0, driver=None, lockstep=None,
-                          wave_pairs=16, f0_moments=False, gv_moments=False, keep=False, gv_variance=False):
+                          wave_pairs=16, f0_moments=False, gv_moments=False, keep=False, gv_variance=False, bands=False):
     """driver='lockstep' (default): waves of `wave_pairs` pairs through the batched entries on two streams
     (`TrainWave`; `lockstep`: a _Lockstep to reuse), rows appended behind a device-side cursor, one read-back per wave;
     driver='streams': the pair-per-stream driver (`TrainPair`, below).  Same matrix either way.
@@ -1239,8 +1324,17 @@ def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_
     gv_variance=True (with gv_moments=True): one more result behind it, the order + 1 values of the variance over the
     pairs of the same per-utterance variance (train(gv_stats=True)'s `gv_var`, for mlpg_gv).
     keep=True (lockstep driver): a third result right behind (X, frames), the `TrainCache` with the alignment inputs of
-    every pair for `realign_training_matrix`; the default keeps nothing, the waves' buffers go as they went before."""
+    every pair for `realign_training_matrix`; the default keeps nothing, the waves' buffers go as they went before.
+    bands=True (lockstep driver; fs of 12 kHz or more, ValueError otherwise before anything is read): one more result
+    right behind (X, frames[, cache]), the band matrix (rows, 6 B) of the aperiodicity conversion -- the band rows of
+    the same kept cells that both sides voice (include/kwy.h, "aperiodicity conversion"), appended behind a cursor of
+    their own; with keep=True the cache holds the band tracks too."""
     driver = driver or ('streams' if pool is not None else 'lockstep')
+    if bands:
+        from .backend import bap
+        if driver != 'lockstep':
+            raise ValueError(f"build_training_matrix(bands=True) needs the lockstep driver, not driver={driver!r}")
+        bap.check_rate(fs)
     if keep and driver != 'lockstep':
         raise ValueError(f"build_training_matrix(keep=True) needs the lockstep driver, not driver={driver!r}")
     if gv_variance and not gv_moments:
@@ -1249,7 +1343,7 @@ def build_training_matrix(pairs, fs, device_index=0, order=24, radius=32, frame_
     gv = _PairGV(len(pairs), order, device_index) if gv_moments else None
     if driver == 'lockstep':
         out = _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng,
-                                              pairs_before, lockstep, wave_pairs, moments, gv, keep)
+                                              pairs_before, lockstep, wave_pairs, moments, gv, keep, bands)
     else:
         out = _build_training_matrix_streams(pairs, fs, device_index, order, radius, frame_period, streams, silence_for,
                                              pool, rng, pairs_before, moments, gv)
@@ -1322,15 +1416,17 @@ class _PairGV:
 
 
 def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, frame_period, silence_for, rng, pairs_before,
-                                    ls, wave_pairs, moments=None, gv=None, keep=False):
+                                    ls, wave_pairs, moments=None, gv=None, keep=False, bands=False):
     dev = torch.device('cuda', device_index)
     ls = ls if ls is not None else _Lockstep(device_index)
     cache = TrainCache(ls, fs, order, radius) if keep else None
     K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
     scale = 2.220446049250313e-16 / fs
     wave_pairs = max(1, min(16, int(wave_pairs)))
+    B = lib.kwy_aperiodicity_bands(int(fs)) if bands else 0
     if not pairs:
-        return (torch.empty((0, 6 * order), dtype=torch.float64, device=dev), 0) + ((cache,) if keep else ())
+        empty = lambda d: torch.empty((0, 6 * d), dtype=torch.float64, device=dev)  # noqa: E731
+        return (empty(order), 0) + ((cache,) if keep else ()) + ((empty(B),) if bands else ())
     if rng is not None and pairs_before:
         with torch.cuda.stream(ls.main):
             sink = [torch.empty((PAD_LEN, K), dtype=torch.float64, device=dev) for _ in range(4 * 16)]
@@ -1359,10 +1455,11 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
 
     try:
         matrix = _RowSink(ls, cap_rows, order)
+        band_matrix = _RowSink(ls, cap_rows, B) if bands else None
         prev, held = None, []           # prev: the wave that waits for its trim lengths, and its first pair
 
         def close(wave, first_pair):
-            wave.finish(matrix, pads, cache)
+            wave.finish(matrix, pads, cache, band_matrix)
             matrix.take(wave.alignment.n_rows)
             with torch.cuda.stream(ls.main):
                 if moments is not None:
@@ -1372,7 +1469,7 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
                                                 for k in range(wave.n)])
         for w0 in range(0, len(pairs), wave_pairs):
             chunk = [uploads.get() for _ in range(len(pairs[w0:w0 + wave_pairs]))]
-            wave = TrainWave(ls, fs, chunk, order=order, radius=radius, frame_period=frame_period)
+            wave = TrainWave(ls, fs, chunk, order=order, radius=radius, frame_period=frame_period, bands=bands)
             wave.analyse()                     # enqueued BEFORE the host waits for the previous wave's lengths
             if prev is not None:
                 close(*prev)
@@ -1383,11 +1480,12 @@ def _build_training_matrix_lockstep(pairs, fs, device_index, order, radius, fram
                 held.pop(0)                    # (its buffers: all uses are ordered on the main stream before reuse)
         close(*prev)
         X, _ = matrix.close()
+        Xb = band_matrix.close()[0] if bands else None
     finally:
         if ahead is not None:
             ahead.stop()
         uploads.stop()
-    return (X, frames) + ((cache,) if keep else ())
+    return (X, frames) + ((cache,) if keep else ()) + ((Xb,) if bands else ())
 
 
 def _build_training_matrix_streams(pairs, fs, device_index=0, order=24, radius=32, frame_period=5.0, streams=16,
@@ -1518,7 +1616,7 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
 
 @takes_options()
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
-                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, **options):
+                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, ap_gmm=None, **options):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1527,20 +1625,29 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     driver='lockstep' (default): waves of 16 utterances through the batched entries on two streams (`ConvertWave`);
     'streams': the utterance-per-stream driver, see `_stream_batch` for its scheduling.
     **options: the keywords of `ConvertOptions`, which describes each (lockstep driver; every value is checked before
-    anything is put on the device)."""
+    anything is put on the device).
+    ap_gmm (lockstep driver): the fitted band-aperiodicity mixture (weights_, means_, covariances_ over 6 B dimensions):
+    the synthesised outputs are rendered on the converted aperiodicity (`ConvertWave`); None: on the analysed one."""
     opts = ConvertOptions(**options).check(order)
     driver = driver or ('streams' if pool is not None else 'lockstep')     # (a caller's pool asks for the stream driver)
     if driver != 'lockstep' and opts.need_lockstep():
         raise ValueError(f'convert_batch: {opts.need_lockstep()[0]} the lockstep driver')
+    if driver != 'lockstep' and ap_gmm is not None:
+        raise ValueError('convert_batch: ap_gmm needs the lockstep driver')
     dev = torch.device('cuda', device_index)
     dg = DeviceGMM(gmm.weights_, gmm.means_, gmm.covariances_, dev)
+    if ap_gmm is not None:
+        from .backend import bap
+        bap.check_rate(fs)
+        ap_gmm = DeviceGMM(ap_gmm.weights_, ap_gmm.means_, ap_gmm.covariances_, dev)
     out = [None] * len(utterances)
     if driver == 'lockstep':
         pcms, dwav, dpcm = ([None] * len(utterances) for _ in range(3))
 
         def keep_view(i, w, p, wd, pd):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
-        _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, opts, pcm=pcm, diff=diff)
+        _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, opts, pcm=pcm, diff=diff,
+                        ap_gmm=ap_gmm)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out
@@ -1603,7 +1710,7 @@ _EVALUATED = {name: ConvertOptions.DEFAULTS[name] for name in ('f0_stats', 'tran
 
 @takes_options(_EVALUATED)
 def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_period=5.0, frames='speech', per_frame=False,
-                   converter_fs=None, lockstep=None, wave_pairs=16, **options):
+                   converter_fs=None, lockstep=None, wave_pairs=16, ap_gmm=None, **options):
     """Objective evaluation of the fitted mixture on parallel pairs, HBM-resident (what
     kwiiyatta_amd.evaluate_voice.evaluate does pair by pair through the Python API): waves of `wave_pairs` pairs
     through `EvalWave`.  pairs: ((x, f0, t), (x, f0, t)) triples as `build_training_matrix` takes them, all at the
@@ -1616,7 +1723,13 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     mcd_moments, source_moments, f0_moments ((n, mean, M2); merged by kwy_moments_merge_dev for the total), counts
     (VV, VU, UV, UU), aligned (frames of the alignment) and outside (those beyond either utterance) -- read back once,
     after the last wave.  per_frame=True: a record also holds idx_x, idx_y (frame indices into the trimmed utterances)
-    and mcd_frames (per aligned frame, nan where not selected).  A value that is not finite raises ValueError."""
+    and mcd_frames (per aligned frame, nan where not selected).  A value that is not finite raises ValueError.
+    ap_gmm: the fitted band-aperiodicity mixture (fs of 12 kHz or more, ValueError otherwise before anything is read):
+    records and total also hold bap_moments and bap_source_moments, the band error of the converted and of the
+    unconverted source's band track against the target's over the aligned frames both sides voice."""
+    if ap_gmm is not None:
+        from .backend import bap
+        bap.check_rate(fs)
     if frames not in ('speech', 'all'):
         raise ValueError(f"frames must be 'speech' or 'all', not {frames!r}")
     if converter_fs is not None and int(converter_fs) != int(fs):
@@ -1635,16 +1748,20 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
     K = lib.kwy_cheaptrick_fft_size(int(fs), 71.0) // 2 + 1
     with torch.cuda.stream(ls.main):
         model = dg.model(diff=False)
-        tot = _EvalTotals(len(pairs), dev)
+        tot = _EvalTotals(len(pairs), dev, bands=ap_gmm is not None)
+        if ap_gmm is not None:
+            ap_gmm = DeviceGMM(ap_gmm.weights_, ap_gmm.means_, ap_gmm.covariances_, dev)
+            ap_gmm.model(diff=False)
 
     def pads(rows):          # the reference's order of draws: source head, source tail, target head, target tail
         for dst in rows:
             dst.copy_(to_device(draw_silence(fs, K), None), non_blocking=True)
     waves = []
     for w0 in range(0, len(pairs), wave_pairs):
-        wave = EvalWave(ls, fs, pairs[w0:w0 + wave_pairs], order=order, radius=radius, frame_period=frame_period)
+        wave = EvalWave(ls, fs, pairs[w0:w0 + wave_pairs], order=order, radius=radius, frame_period=frame_period,
+                        bands=ap_gmm is not None)
         wave.analyse()
-        wave.measure(pads, dg, model, tot, w0, opts, frames=frames, per_frame=per_frame)
+        wave.measure(pads, dg, model, tot, w0, opts, frames=frames, per_frame=per_frame, ap_gmm=ap_gmm)
         waves.append(wave)
         if not per_frame:
             while len(waves) > 2:
@@ -1666,9 +1783,10 @@ def evaluate_batch(pairs, fs, gmm, device_index=0, order=24, radius=32, frame_pe
 
     def record(m, c, n_aligned):
         c = tuple(int(v) for v in c)
+        band = dict(bap_moments=tuple(m[3].tolist()), bap_source_moments=tuple(m[4].tolist())) if len(m) > 3 else {}
         return dict(mcd_moments=tuple(m[0].tolist()), source_moments=tuple(m[1].tolist()), f0_moments=tuple(m[2].tolist()),
                     counts=c,
-                    aligned=int(n_aligned), outside=int(n_aligned) - sum(c))
+                    aligned=int(n_aligned), outside=int(n_aligned) - sum(c), **band)
     records = [record(triples[i], counts[i], aligned[i]) for i in range(len(pairs))]
     if per_frame:
         i = 0

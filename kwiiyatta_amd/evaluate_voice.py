@@ -45,11 +45,16 @@ class Result:
         f0_rmse_cents     over the frames both sides voice;  vuv_error: (VU + UV) / all aligned frames
         vv, vu, uv, uu    source voiced / target voiced, source voiced / target unvoiced, ...
         aligned           aligned frames (the alignment's length);  outside: those of them beyond either utterance
+        bap, bap_source   with convert_ap: mean band-aperiodicity error in dB (sqrt of the mean squared difference over
+                          the bands) of the converted / unconverted source's band track against the target's, over the
+                          bap_frames aligned frames that both sides voice; nan / 0 without convert_ap
     A figure without frames is nan.  idx_x / idx_y (frame indices into the two utterances) and mcd_frames
     (per aligned frame, nan where not selected) are kept when they were asked for."""
 
     def __init__(self, mcd_moments, source_moments, f0_moments, counts, aligned, outside=0, idx_x=None, idx_y=None,
-                 mcd_frames=None):
+                 mcd_frames=None, bap_moments=None, bap_source_moments=None):
+        self.bap_moments, self.bap_source_moments = (None if m is None else tuple(float(v) for v in m)
+                                                     for m in (bap_moments, bap_source_moments))
         self.mcd_moments, self.source_moments, self.f0_moments = (tuple(float(v) for v in m) for m in
                                                                   (mcd_moments, source_moments, f0_moments))
         self.vv, self.vu, self.uv, self.uu = (int(v) for v in counts)
@@ -60,6 +65,11 @@ class Result:
     mcd = property(lambda self: self.mcd_moments[1] if self.mcd_moments[0] > 0 else math.nan)
     mcd_source = property(lambda self: self.source_moments[1] if self.source_moments[0] > 0 else math.nan)
     counts = property(lambda self: (self.vv, self.vu, self.uv, self.uu))
+    convert_ap = property(lambda self: self.bap_moments is not None)
+    bap_frames = property(lambda self: int(self.bap_moments[0]) if self.convert_ap else 0)
+    bap = property(lambda self: self.bap_moments[1] if self.bap_frames > 0 else math.nan)
+    bap_source = property(lambda self: self.bap_source_moments[1] if self.convert_ap and self.bap_source_moments[0] > 0
+                          else math.nan)
 
     @property
     def f0_rmse_cents(self):
@@ -76,11 +86,15 @@ class Result:
         d = dict(frames=self.frames, aligned=self.aligned, outside=self.outside, mcd=self.mcd, mcd_source=self.mcd_source,
                  f0_rmse_cents=self.f0_rmse_cents, f0_frames=int(self.f0_moments[0]), vuv_error=self.vuv_error,
                  counts=dict(vv=self.vv, vu=self.vu, uv=self.uv, uu=self.uu))
+        if self.convert_ap:
+            d.update(bap=self.bap, bap_source=self.bap_source, bap_frames=self.bap_frames)
         return {k: _nan_to_none(v) for k, v in d.items()}
 
     def line(self, name):
+        band = f' band aperiodicity {self.bap:.3f} dB (source {self.bap_source:.3f} dB, {self.bap_frames} frames)' \
+            if self.convert_ap else ''
         return (f'{name}: frames {self.frames} MCD {self.mcd:.3f} dB (source {self.mcd_source:.3f} dB) '
-                f'f0 RMSE {self.f0_rmse_cents:.1f} cents V/UV error {100 * self.vuv_error:.2f} %')
+                f'f0 RMSE {self.f0_rmse_cents:.1f} cents V/UV error {100 * self.vuv_error:.2f} %' + band)
 
 
 def pool(results):
@@ -91,10 +105,13 @@ def pool(results):
     if not results:
         zero = (0.0, 0.0, 0.0)
         return Result(zero, zero, zero, (0, 0, 0, 0), 0)
-    triples = np.array([[r.mcd_moments, r.source_moments, r.f0_moments] for r in results], dtype=np.float64)
+    bands = all(r.convert_ap for r in results)          # (the band error is pooled when every pair has one)
+    triples = np.array([[r.mcd_moments, r.source_moments, r.f0_moments] +
+                        ([r.bap_moments, r.bap_source_moments] if bands else []) for r in results], dtype=np.float64)
     merged = dist.merge_moments(np.ascontiguousarray(triples))
     return Result(merged[0], merged[1], merged[2], [sum(r.counts[i] for r in results) for i in range(4)],
-                  sum(r.aligned for r in results), sum(r.outside for r in results))
+                  sum(r.aligned for r in results), sum(r.outside for r in results),
+                  **(dict(bap_moments=merged[3], bap_source_moments=merged[4]) if bands else {}))
 
 
 def _check_options(gv, transpose_key, frames):
@@ -107,7 +124,8 @@ def _check_options(gv, transpose_key, frames):
         raise ValueError(f'transpose_key {transpose_key!r} is outside [-{KEY_RANGE}, {KEY_RANGE}]')
 
 
-PAIR_OPTIONS = dict(gv=0.0, convert_f0=False, transpose_key=0.0, frames='speech', per_frame=False, em=None, mlpg_gv=None)
+PAIR_OPTIONS = dict(gv=0.0, convert_f0=False, transpose_key=0.0, frames='speech', per_frame=False, em=None, mlpg_gv=None,
+                    convert_ap=False)
 
 
 @takes_options(defaults=PAIR_OPTIONS)
@@ -122,7 +140,11 @@ def evaluate_pair(converter, source, target, **options):
     em=N: the conversion is the EM trajectory conversion over soft mixture posteriors with N re-estimations
     (`converter.convert(..., em=N)`, convert_voice's --mlpg-em); None: one arg-max mixture per frame.
     mlpg_gv=N: parameter generation considering the global variance behind it, N steps
-    (`converter.convert(..., mlpg_gv=N)`, --mlpg-gv); it does not go with gv > 0."""
+    (`converter.convert(..., mlpg_gv=N)`, --mlpg-gv); it does not go with gv > 0.
+    convert_ap: also the band-aperiodicity error (`Result.bap`, `bap_source`, `bap_frames`) of the source's band track
+    converted by the converter's band mixture -- clamped as the rendering clamps it -- and of the unconverted one
+    against the target's, along the same index lists over the frames both sides voice (backend.bap.error); both
+    feature sets must be at the converter's sampling rate (12 kHz or more)."""
     import kwiiyatta_amd as k
     from .backend import distortion as dist
     from .backend import f0 as f0map
@@ -132,6 +154,12 @@ def evaluate_pair(converter, source, target, **options):
     _check_options(gv, transpose_key, frames)
     if convert_f0 and converter.f0_stats is None:
         raise ValueError('f0 conversion: the converter has no statistics (train it with f0_stats=True)')
+    if o.convert_ap:
+        from .convert_voice import check_convert_ap
+        check_convert_ap(converter)
+        if not source.fs == target.fs == converter.fs:
+            raise ValueError(f'convert_ap: the pair is at {source.fs} Hz and {target.fs} Hz, the converter at '
+                             f'{converter.fs} Hz (the band tracks are not resampled)')
     a, b = k.pad_silence(source, PAD_LEN), k.pad_silence(target, PAD_LEN)
     xs, ys = even_indices(a, b, PAD_LEN, strict=True)
     idx_x, idx_y = (np.ascontiguousarray(v, dtype=np.int32) for v in (xs, ys))
@@ -159,6 +187,13 @@ def evaluate_pair(converter, source, target, **options):
     # and the kernels pass them over (the f0 kernel counts every other aligned frame)
     outside = len(idx_x) - int(counts.sum())
     keep = dict(idx_x=idx_x - PAD_LEN, idx_y=idx_y - PAD_LEN, mcd_frames=rows[0]) if o.per_frame else {}
+    if o.convert_ap:
+        from .backend import bap
+        own, mapped = converter.convert_band_track(source)
+        theirs = k.band_track(target)
+        band = bap.error([mapped, own], [theirs, theirs], idx_a=[idx_x, idx_x], idx_b=[idx_y, idx_y], off_a=PAD_LEN,
+                         off_b=PAD_LEN)
+        keep.update(bap_moments=band[0], bap_source_moments=band[1])
     return Result(m[0], m[1], f0_m, counts, len(idx_x), outside, **keep)
 
 
@@ -211,6 +246,7 @@ def make_config():
     conf.add_gv_argument()
     conf.add_mlpg_em_argument()
     conf.add_mlpg_gv_argument()
+    conf.add_aperiodicity_arguments()
     conf.add_converter_arguments()
     return conf
 
@@ -255,6 +291,9 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
     import kwiiyatta_amd as k
     from . import corpus
     from .converter.delta import DeltaFeatureConverter
+    if options.get('convert_ap'):
+        from .convert_voice import check_convert_ap
+        check_convert_ap(converter)               # (raises before any file is read)
     period = next((s.frame_period for s in _stages(converter) if isinstance(s, DeltaFeatureConverter)), None)
     sides = [pathlib.Path(conf.source), pathlib.Path(conf.target)]
     results, batch = {}, []
@@ -278,10 +317,12 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
                                        mlpg_gv=options.get('mlpg_gv')))
         records, _ = corpus.evaluate_batch(
             [p for _, p, _ in batch], converter.fs, converter.gmm, order=converter.order, frame_period=batch[0][2],
-            frames=options['frames'], **driver_options(converter, asked))
+            frames=options['frames'], ap_gmm=converter.ap_converter.gmm if options.get('convert_ap') else None,
+            **driver_options(converter, asked))
         for (key, _, _), rec in zip(batch, records):
+            band = {name: rec[name] for name in ('bap_moments', 'bap_source_moments') if name in rec}
             results[key] = Result(rec['mcd_moments'], rec['source_moments'], rec['f0_moments'], rec['counts'],
-                                  rec['aligned'], rec['outside'])
+                                  rec['aligned'], rec['outside'], **band)
     return [results[key] for key in keys]
 
 
@@ -334,8 +375,13 @@ def main():
         if warning:
             print(warning, file=sys.stderr)
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
-                                     **(dict(gv_var=True) if conf.mlpg_gv is not None else {}))
+                                     **(dict(gv_var=True) if conf.mlpg_gv is not None else {}),
+                                     **(dict(ap_model=True) if conf.convert_aperiodicity else {}))
     options = dict(gv=conf.gv, convert_f0=conf.convert_f0, transpose_key=conf.transpose_key, frames=conf.frames)
+    if conf.convert_aperiodicity:
+        options['convert_ap'] = True
+        print(f'band-aperiodicity mixture: {converter.ap_converter.gmm.n_components} components'
+              + (f', fitted on {converter.ap_rows} rows' if converter.ap_rows else ''))
     # (--mlpg-em, --mlpg-gv: EM trajectory conversion, GV-considering parameter generation, as convert_voice runs them)
     options.update({name: v for name, v in dict(em=conf.mlpg_em, mlpg_gv=conf.mlpg_gv).items() if v is not None})
     if conf.batch:
