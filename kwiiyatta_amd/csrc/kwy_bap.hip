@@ -9,10 +9,7 @@
 //   kwy_bap_apply_*   the converted bands decoded over the voiced rows of the analysed aperiodicity, in place
 //   kwy_bap_error_*   (n, mean, M2) of the per-cell band error over the cells voiced on both sides
 //
-// The coder's and the decoder's arithmetic is that of k_code_aperiodicity / k_decode_aperiodicity (kwy_codec.hip),
-// expression for expression: the library is built with -ffp-contract=off, so the results are bit-equal to
-// kwy_code_aperiodicity_dev / kwy_decode_aperiodicity_dev, which the tests hold it to.  kwy_codec.hip itself is not
-// touched (its device code stays what it was); the two expressions live in bap_code() and bap_decode_bin() below.
+// The band codec's arithmetic is kwy_band_code() / kwy_band_decode_bin() of kwy_device.hpp, which kwy_codec.hip calls too.
 //
 // Nothing here allocates or synchronises in the _dev forms; kwy_bap_rows_batch_dev takes 8 bytes per pair from the
 // context's arena (the pairs' places in the matrix), as kwy_train_rows_batch_dev does.
@@ -22,51 +19,9 @@
 
 #include "kwy_internal.hpp"
 
-#define BAP_SAFE 0.000000000001       // kwy_codec.hip: CODEC_SAFE
-#define BAP_INTERVAL 3000.0           //                CODEC_INTERVAL
-#define BAP_MAX_BANDS 8               //                CODEC_MAX_BANDS
-#define BAP_FLOOR -60.0               // the decoder's node at 0 Hz: the lowest value a converted band may take
 #define BAP_NT KWY_THREADS
 #define BAP_PASS BAP_NT               // frames per pass of the track kernel: one thread per frame in the fill
 #define BAP_GROUP 16                  // jobs per launch
-
-// k_code_aperiodicity's value of band b of a frame: interp1Q(0, fs / fft, 20 log10(row), K, 3000 (b + 1))
-__device__ __forceinline__ double bap_code(const double *__restrict__ row, int K, int fs, int fft_size, int b) {
-  const double shift = (double)fs / fft_size;
-  const double xi = BAP_INTERVAL * (b + 1.0);
-  const int base = (int)((xi - 0) / shift);
-  const double frac = (xi - 0) / shift - base;
-  const double y0 = 20 * log10(row[base]);
-  const double dy = (base >= K - 1) ? 0.0 : 20 * log10(row[base + 1]) - y0;
-  return y0 + dy * frac;
-}
-
-// k_decode_aperiodicity's value of bin k over the nodes {0: coarse[0], 3k (i + 1): coarse[i + 1], fs / 2: coarse[nb + 1]}
-__device__ __forceinline__ double bap_decode_bin(const double *coarse, int fs, int fft_size, int nb, int k) {
-  const int nn = nb + 2;
-  const double xi = (double)fs / fft_size * k;
-  int seg = 0;  // number of nodes <= xi  (WORLD histc)
-  for (int j = 0; j < nn; ++j) {
-    const double xj = (j <= nb) ? j * BAP_INTERVAL : fs / 2.0;
-    if (xj <= xi) seg = j + 1;
-  }
-  if (seg < 1) seg = 1;
-  if (seg > nn - 1) seg = nn - 1;
-  const double xa = (seg - 1 <= nb) ? (seg - 1) * BAP_INTERVAL : fs / 2.0;
-  const double xb = (seg <= nb) ? seg * BAP_INTERVAL : fs / 2.0;
-  const double s = (xi - xa) / (xb - xa);
-  const double v = coarse[seg - 1] + s * (coarse[seg] - coarse[seg - 1]);
-  return pow(10.0, v / 20.0);
-}
-
-// the row count of a job: the host value, or the device word clamped to [0, rows] (rows is then the lists' capacity)
-__device__ __forceinline__ int64_t bap_rows(int64_t rows, const int64_t *n_dev) {
-  if (!n_dev) return rows;
-  const int64_t w = *n_dev;
-  return w < 0 ? 0 : (w < rows ? w : rows);
-}
-
-__device__ __forceinline__ int64_t bap_clamp_row(int64_t r, int64_t rows) { return r < 0 ? 0 : (r >= rows ? rows - 1 : r); }
 
 // ---- band track ------------------------------------------------------------------------------------------------------
 struct bap_track_view { const double *ap; int64_t T; double *track; };
@@ -80,10 +35,10 @@ typedef kwy_group<bap_track_view, BAP_GROUP> bap_track_table;
 // first voiced frame are written as coded and overwritten with that frame's row at the end (the leading run); without
 // any voiced frame they stay as coded.
 __global__ __launch_bounds__(BAP_NT) void k_bap_track(bap_track_table tab, int fs, int fft_size, int B) {
-  __shared__ double s_c[BAP_PASS * BAP_MAX_BANDS];     // the pass's coded values
+  __shared__ double s_c[BAP_PASS * KWY_BAND_MAX];     // the pass's coded values
   __shared__ int s_last[2][BAP_PASS];                  // max-scan buffers: local index of the last voiced frame, or -1
-  __shared__ double s_carry[BAP_MAX_BANDS];            // the row of the last voiced frame of the passes before
-  __shared__ double s_lead[BAP_MAX_BANDS];             // the row of the utterance's first voiced frame
+  __shared__ double s_carry[KWY_BAND_MAX];            // the row of the last voiced frame of the passes before
+  __shared__ double s_lead[KWY_BAND_MAX];             // the row of the utterance's first voiced frame
   __shared__ int s_have_carry;
   __shared__ long long s_first;                        // index of the utterance's first voiced frame, or -1
   const bap_track_view &U = tab.u[blockIdx.x];
@@ -94,7 +49,7 @@ __global__ __launch_bounds__(BAP_NT) void k_bap_track(bap_track_table tab, int f
     const int F = (int)(U.T - t0 < BAP_PASS ? U.T - t0 : BAP_PASS);
     for (int p = tid; p < F * B; p += BAP_NT) {
       const int f = p / B, b = p - f * B;
-      s_c[f * B + b] = bap_code(U.ap + (t0 + f) * K, K, fs, fft_size, b);
+      s_c[f * B + b] = kwy_band_code(U.ap + (t0 + f) * K, K, fs, fft_size, b);
     }
     __syncthreads();
     // the decoder's test (k_decode_aperiodicity): a left fold, b ascending, compared with > -0.5
@@ -155,43 +110,26 @@ struct bap_rows_view {
 };
 typedef kwy_group<bap_rows_view, BAP_GROUP> bap_rows_table;
 
-// exclusive scan of one int per thread over the workgroup; *total = the sum.  sh: BAP_NT / 64 ints
-__device__ __forceinline__ int bap_block_exscan(int v, int *sh, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = (int)kwy_wave_scan_u32((uint32_t)v);
-  __syncthreads();
-  if (lane == 63) sh[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < BAP_NT / 64; ++w) {
-    if (w < wv) base += sh[w];
-    tot += sh[w];
-  }
-  *total = tot;
-  return base + inc - v;
-}
-
 __device__ __forceinline__ bool bap_cell_kept(const bap_rows_view &U, int W, int64_t k) {
-  const int64_t rx = bap_clamp_row(U.ix[k], U.x_rows), ry = bap_clamp_row(U.iy[k], U.y_rows);
+  const int64_t rx = kwy_clamp_row(U.ix[k], U.x_rows), ry = kwy_clamp_row(U.iy[k], U.y_rows);
   return U.tx[rx * W] == 1.0 && U.ty[ry * W] == 1.0;
 }
 
 // Cell k of a pair is kept when both sides are voiced there; WRITE: the kept cells' rows go to `joint` in order, the
-// delta features taken over the gathered sequences of ALL n cells with k_tr_delta's expressions (kwy_train.hip) --
+// delta features taken over the gathered sequences of ALL n cells as k_tr_delta takes them (kwy_delta_windows) --
 // else they are counted into n_rows.  One workgroup per pair, BAP_NT cells a round.
 template <bool WRITE>
 __device__ __forceinline__ void bap_rows_body(const bap_rows_view &U, int B, double *__restrict__ joint) {
   __shared__ int sh[BAP_NT / 64];
   __shared__ int s_dst[BAP_NT];
   const int tid = threadIdx.x, W = B + 1, D = 3 * B;
-  const int64_t n = bap_rows(U.capacity, U.n_dev);
+  const int64_t n = kwy_device_count(U.capacity, U.n_dev);
   int64_t run = 0;
   for (int64_t k0 = 0; k0 < n; k0 += BAP_NT) {
     const int64_t k = k0 + tid;
     const int keep = (k < n && bap_cell_kept(U, W, k)) ? 1 : 0;
     int tot;
-    const int off = bap_block_exscan(keep, sh, &tot);
+    const int off = kwy_block_exscan<BAP_NT>(keep, sh, &tot);
     if (WRITE) {
       s_dst[tid] = keep ? off : -1;
       __syncthreads();
@@ -203,13 +141,12 @@ __device__ __forceinline__ void bap_rows_body(const bap_rows_view &U, int B, dou
         const double *__restrict__ tr = side ? U.ty : U.tx;
         const int32_t *__restrict__ idx = side ? U.iy : U.ix;
         const int64_t rows = side ? U.y_rows : U.x_rows;
-        const double x0 = tr[bap_clamp_row(idx[kk], rows) * W + 1 + b];
-        const double xm = kk > 0 ? tr[bap_clamp_row(idx[kk - 1], rows) * W + 1 + b] : 0.0;
-        const double xp = kk + 1 < n ? tr[bap_clamp_row(idx[kk + 1], rows) * W + 1 + b] : 0.0;
+        const double x0 = tr[kwy_clamp_row(idx[kk], rows) * W + 1 + b];
+        const double xm = kk > 0 ? tr[kwy_clamp_row(idx[kk - 1], rows) * W + 1 + b] : 0.0;
+        const double xp = kk + 1 < n ? tr[kwy_clamp_row(idx[kk + 1], rows) * W + 1 + b] : 0.0;
         double *o = joint + (size_t)(run + s_dst[c]) * 2 * D + side * D;
         o[b] = x0;
-        o[B + b] = (-0.5 * xm + 0.0 * x0) + 0.5 * xp;
-        o[2 * B + b] = (1.0 * xm + -2.0 * x0) + 1.0 * xp;
+        kwy_delta_windows(xm, x0, xp, &o[B + b], &o[2 * B + b]);
       }
       __syncthreads();
     }
@@ -221,19 +158,10 @@ __device__ __forceinline__ void bap_rows_body(const bap_rows_view &U, int B, dou
 __global__ __launch_bounds__(BAP_NT) void k_bap_rows_count(bap_rows_table tab, int B) {
   bap_rows_body<false>(tab.u[blockIdx.x], B, nullptr);
 }
-// the pairs' places in the matrix, in pair order behind the cursor; a pair that would not fit is dropped whole and
-// flagged (n_rows = -1 - rows it had)
 __global__ void k_bap_rows_place(bap_rows_table tab, int64_t *__restrict__ cursor, int64_t capacity_rows,
                                  int64_t *__restrict__ places) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int64_t at = cursor[0];
-  for (int k = 0; k < tab.n; ++k) {
-    const int64_t n = tab.u[k].n_rows[0];
-    if (at + n > capacity_rows) { places[k] = -1; tab.u[k].n_rows[0] = -1 - n; continue; }
-    places[k] = at;
-    at += n;
-  }
-  cursor[0] = at;
+  kwy_place_rows(tab.n, [&](int k) { return tab.u[k].n_rows; }, cursor, capacity_rows, places);
 }
 __global__ __launch_bounds__(BAP_NT) void k_bap_rows_write(bap_rows_table tab, int B, double *__restrict__ joint,
                                                           const int64_t *__restrict__ places) {
@@ -250,7 +178,7 @@ static_assert(sizeof(bap_apply_table) + 64 <= KWY_KERNARG_MAX, "the apply kernel
 // One workgroup per frame of the batch, as k_decode_aperiodicity has it: a frame that is voiced in the source's track
 // becomes the decode of its converted bands, clamped to [-60, -1e-12] dB; any other frame is not touched.
 __global__ __launch_bounds__(BAP_NT) void k_bap_apply(bap_apply_table tab, int fs, int fft_size, int nb) {
-  __shared__ double coarse[BAP_MAX_BANDS + 2];
+  __shared__ double coarse[KWY_BAND_MAX + 2];
   __shared__ int s_unvoiced;
   const int u = tab.find(blockIdx.x);
   const bap_apply_view &U = tab.u[u];
@@ -262,20 +190,20 @@ __global__ __launch_bounds__(BAP_NT) void k_bap_apply(bap_apply_table tab, int f
     double tmp = 0.0;
     for (int i = 0; i < nb; ++i) {
       double v = U.conv[frame * W + 1 + i];
-      v = v < BAP_FLOOR ? BAP_FLOOR : (v > -BAP_SAFE ? -BAP_SAFE : v);
+      v = v < KWY_BAND_FLOOR ? KWY_BAND_FLOOR : (v > -KWY_SAFE ? -KWY_SAFE : v);
       tmp += v;
       coarse[i + 1] = v;
     }
-    coarse[0] = -60.0;
-    coarse[nb + 1] = -BAP_SAFE;
+    coarse[0] = KWY_BAND_FLOOR;
+    coarse[nb + 1] = -KWY_SAFE;
     s_unvoiced = nb <= 0 || (tmp / nb > -0.5);
   }
   __syncthreads();
   if (s_unvoiced) {
-    for (int k = tid; k < K; k += BAP_NT) o[k] = 1.0 - BAP_SAFE;
+    for (int k = tid; k < K; k += BAP_NT) o[k] = 1.0 - KWY_SAFE;
     return;
   }
-  for (int k = tid; k < K; k += BAP_NT) o[k] = bap_decode_bin(coarse, fs, fft_size, nb, k);
+  for (int k = tid; k < K; k += BAP_NT) o[k] = kwy_band_decode_bin(coarse, fs, fft_size, nb, k);
 }
 
 // ---- band error ------------------------------------------------------------------------------------------------------
@@ -295,7 +223,7 @@ __global__ __launch_bounds__(BAP_NT) void k_bap_error(bap_error_table tab, int B
   __shared__ double red[KWY_WAVES];
   const bap_error_view &U = tab.u[blockIdx.x];
   const int tid = threadIdx.x, W = B + 1;
-  const int64_t n = bap_rows(U.rows, U.n_dev);
+  const int64_t n = kwy_device_count(U.rows, U.n_dev);
   double cnt = 0.0, sum = 0.0;
   for (int pass = 0; pass < 2; ++pass) {
     const double mean = cnt > 0.0 ? sum / cnt : 0.0;
@@ -342,13 +270,13 @@ static int bap_check_rate(kwy_ctx *ctx, const char *who, int fs, int fft_size, i
     ctx->err = std::string(who) + ": the sampling rate has no aperiodicity band (it takes 12 kHz or more)";
     return KWY_EINVAL;
   }
-  if (B > BAP_MAX_BANDS) { ctx->err = std::string(who) + ": too many bands"; return KWY_EINVAL; }
+  if (B > KWY_BAND_MAX) { ctx->err = std::string(who) + ": too many bands"; return KWY_EINVAL; }
   *bands = B;
   return KWY_OK;
 }
 
 static int bap_check_bands(kwy_ctx *ctx, const char *who, int B) {
-  if (B < 1 || B > BAP_MAX_BANDS) {
+  if (B < 1 || B > KWY_BAND_MAX) {
     ctx->err = std::string(who) + ": the band count must be within [1, 8] (a rate of 12 kHz or more)";
     return KWY_EINVAL;
   }

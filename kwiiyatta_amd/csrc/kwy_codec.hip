@@ -11,19 +11,7 @@
 
 #include "kwy_internal.hpp"
 
-#define CODEC_SAFE 0.000000000001
-#define CODEC_INTERVAL 3000.0
-#define CODEC_UPPER 15000.0
-#define CODEC_MAX_BANDS 8
-
-static int codec_num_bands(int fs) {
-  double lim = fs / 2.0 - CODEC_INTERVAL;
-  if (lim > CODEC_UPPER) lim = CODEC_UPPER;
-  int n = (int)(lim / CODEC_INTERVAL);
-  return n < 0 ? 0 : n;
-}
-
-extern "C" int kwy_aperiodicity_bands(int fs) { return codec_num_bands(fs); }
+extern "C" int kwy_aperiodicity_bands(int fs) { return kwy_band_count(fs); }
 
 __global__ __launch_bounds__(64) void k_code_aperiodicity(const double *__restrict__ ap, int64_t T, int fs,
                                                          int fft_size, int nb, double *__restrict__ coded) {
@@ -31,21 +19,13 @@ __global__ __launch_bounds__(64) void k_code_aperiodicity(const double *__restri
   const int b = threadIdx.x;
   if (b >= nb) return;
   const int K = fft_size / 2 + 1;
-  const double *row = ap + frame * K;
-  // interp1Q(0, fs/fft, 20 log10(ap), K, 3000 (b+1))
-  const double shift = (double)fs / fft_size;
-  const double xi = CODEC_INTERVAL * (b + 1.0);
-  const int base = (int)((xi - 0) / shift);
-  const double frac = (xi - 0) / shift - base;
-  const double y0 = 20 * log10(row[base]);
-  const double dy = (base >= K - 1) ? 0.0 : 20 * log10(row[base + 1]) - y0;
-  coded[frame * nb + b] = y0 + dy * frac;
+  coded[frame * nb + b] = kwy_band_code(ap + frame * K, K, fs, fft_size, b);
 }
 
 __global__ __launch_bounds__(KWY_THREADS) void k_decode_aperiodicity(const double *__restrict__ coded, int64_t T,
                                                                      int fs, int fft_size, int nb,
                                                                      double *__restrict__ ap) {
-  __shared__ double coarse[CODEC_MAX_BANDS + 2];
+  __shared__ double coarse[KWY_BAND_MAX + 2];
   __shared__ int s_unvoiced;
   const int64_t frame = blockIdx.x;
   const int tid = threadIdx.x, K = fft_size / 2 + 1;
@@ -53,42 +33,27 @@ __global__ __launch_bounds__(KWY_THREADS) void k_decode_aperiodicity(const doubl
   if (tid == 0) {
     double tmp = 0.0;
     for (int i = 0; i < nb; ++i) { tmp += coded[frame * nb + i]; coarse[i + 1] = coded[frame * nb + i]; }
-    coarse[0] = -60.0;
-    coarse[nb + 1] = -CODEC_SAFE;
+    coarse[0] = KWY_BAND_FLOOR;
+    coarse[nb + 1] = -KWY_SAFE;
     s_unvoiced = nb <= 0 || (tmp / nb > -0.5);
   }
   __syncthreads();
   if (s_unvoiced) {
-    for (int k = tid; k < K; k += KWY_THREADS) o[k] = 1.0 - CODEC_SAFE;
+    for (int k = tid; k < K; k += KWY_THREADS) o[k] = 1.0 - KWY_SAFE;
     return;
   }
-  const int nn = nb + 2;
-  for (int k = tid; k < K; k += KWY_THREADS) {
-    const double xi = (double)fs / fft_size * k;
-    int seg = 0;  // number of nodes <= xi  (WORLD histc)
-    for (int j = 0; j < nn; ++j) {
-      const double xj = (j <= nb) ? j * CODEC_INTERVAL : fs / 2.0;
-      if (xj <= xi) seg = j + 1;
-    }
-    if (seg < 1) seg = 1;
-    if (seg > nn - 1) seg = nn - 1;
-    const double xa = (seg - 1 <= nb) ? (seg - 1) * CODEC_INTERVAL : fs / 2.0;
-    const double xb = (seg <= nb) ? seg * CODEC_INTERVAL : fs / 2.0;
-    const double s = (xi - xa) / (xb - xa);
-    const double v = coarse[seg - 1] + s * (coarse[seg] - coarse[seg - 1]);
-    o[k] = pow(10.0, v / 20.0);
-  }
+  for (int k = tid; k < K; k += KWY_THREADS) o[k] = kwy_band_decode_bin(coarse, fs, fft_size, nb, k);
 }
 
 static int codec_check(kwy_ctx *ctx, const void *a, const void *b, int64_t T, int fs, int fft_size, int nb) {
   if (!ctx) return KWY_EINVAL;
-  if (!a || !b || T <= 0 || fs <= 0 || fft_size < 4 || (fft_size & 1) || nb < 0 || nb > CODEC_MAX_BANDS) {
+  if (!a || !b || T <= 0 || fs <= 0 || fft_size < 4 || (fft_size & 1) || nb < 0 || nb > KWY_BAND_MAX) {
     ctx->err = "aperiodicity codec: bad argument";
     return KWY_EINVAL;
   }
   // more bands than the rate has: the nodes 3 kHz, 6 kHz, ... would reach fs/2, the last node, and the grid would
   // no longer increase (WORLD derives the count from fs; the reference's caller truncates to the new rate's count)
-  if (nb > codec_num_bands(fs)) {
+  if (nb > kwy_band_count(fs)) {
     ctx->err = "aperiodicity codec: more bands than the sampling rate has";
     return KWY_EINVAL;
   }
@@ -97,7 +62,7 @@ static int codec_check(kwy_ctx *ctx, const void *a, const void *b, int64_t T, in
 
 extern "C" int kwy_code_aperiodicity_dev(kwy_ctx *ctx, const double *ap, int64_t T, int fs, int fft_size,
                                          double *coded) {
-  const int nb = codec_num_bands(fs);
+  const int nb = kwy_band_count(fs);
   KWY_TRY(codec_check(ctx, ap, coded, T, fs, fft_size, nb));
   KWY_HIP(hipSetDevice(ctx->device));
   if (nb == 0) return KWY_OK;
@@ -118,7 +83,7 @@ extern "C" int kwy_decode_aperiodicity_dev(kwy_ctx *ctx, const double *coded, in
 
 extern "C" int kwy_code_aperiodicity(kwy_ctx *ctx, const double *ap, int64_t T, int fs, int fft_size,
                                      double *coded) {
-  const int nb = codec_num_bands(fs);
+  const int nb = kwy_band_count(fs);
   KWY_TRY(codec_check(ctx, ap, coded, T, fs, fft_size, nb));
   KWY_HIP(hipSetDevice(ctx->device));
   if (nb == 0) return KWY_OK;

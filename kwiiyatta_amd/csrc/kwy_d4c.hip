@@ -25,10 +25,8 @@
 
 #include "kwy_internal.hpp"
 
-#define D4C_SAFE 0.000000000001
 #define D4C_FLOOR_F0 47.0
 #define D4C_FREQ_INTERVAL 3000.0
-#define D4C_UPPER_LIMIT 15000.0
 #define D4C_MAX_BANDS 8
 
 enum { D4C_HANNING = 1, D4C_BLACKMAN = 2 };
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(NT) void k_d4c_lovetrain(
     if (i < wl) {
       double w = walk.value(D4C_BLACKMAN);
       int idx = min(x_length - 1, max(0, origin + i - half));
-      v = __builtin_fma(kwy_randn_from_raw(raw[r]), D4C_SAFE, x[idx] * w);
+      v = __builtin_fma(kwy_randn_from_raw(raw[r]), KWY_SAFE, x[idx] * w);
       Bd[i] = w;
       s1 += v; s2 += w;
     }
@@ -388,7 +386,7 @@ __device__ __forceinline__ void d4c_frame_window(const double *__restrict__ x, i
         if (wmode == 1) wcos[slot] = c1;
       }
       const double w = type == D4C_HANNING ? 0.5 * c1 + 0.5 : 0.42 + 0.5 * c1 + 0.08 * (2.0 * c1 * c1 - 1.0);
-      v = __builtin_fma(kwy_randn_from_raw(raw[r]), D4C_SAFE, xv[r] * w);
+      v = __builtin_fma(kwy_randn_from_raw(raw[r]), KWY_SAFE, xv[r] * w);
       Bd[i] = w;                       // kept for the DC removal below (only this thread reads it)
       s1 += v; s2 += w;
     }
@@ -540,7 +538,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   const double f0v = kwy_uniform(batch.u[utt].f0[frame]);
   double *o = batch.u[utt].out + frame * p.K;
   if (f0v == 0.0 || kwy_uniform(batch.u[utt].ap0[frame]) <= p.threshold) {
-    for (int k = tid; k < p.K; k += NT) o[k] = 1.0 - D4C_SAFE;
+    for (int k = tid; k < p.K; k += NT) o[k] = 1.0 - KWY_SAFE;
     return;
   }
   const double cf0 = kwy_uniform(f0v > D4C_FLOOR_F0 ? f0v : D4C_FLOOR_F0);
@@ -946,7 +944,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 2 : 4) void k_d
   D4C_STAMP(21);
   if (tid == 0) {
     coarse[0] = -60.0;
-    coarse[p.nbands + 1] = -D4C_SAFE;
+    coarse[p.nbands + 1] = -KWY_SAFE;
   }
   __syncthreads();
   // ---- interp1 of the (nbands+2)-point contour onto the K output bins
@@ -1038,13 +1036,6 @@ static int d4c_fft_size(int fs) {
   return (int)pow(2.0, 1.0 + (int)(log(4.0 * fs / D4C_FLOOR_F0 + 1) / 0.69314718055994529));
 }
 
-static int d4c_nbands(int fs) {
-  double lim = fs / 2.0 - D4C_FREQ_INTERVAL;
-  if (lim > D4C_UPPER_LIMIT) lim = D4C_UPPER_LIMIT;
-  const int nb = (int)(lim / D4C_FREQ_INTERVAL);
-  return nb < 0 ? 0 : nb;
-}
-
 // The band windows (2 hw + 1 taps around bin (int)(3000 (b + 1) N / fs), hw = (int)(3000 N / fs)) read the bins
 // [0, (int)(3000 nbands N / fs) + hw] of the static group delay: 1537 of 2049 at 48 kHz.
 static int d4c_dv_len(int fs, int n4, int nbands) {
@@ -1056,7 +1047,7 @@ static int d4c_dv_len(int fs, int n4, int nbands) {
 
 static size_t d4c_scratch_bytes(int64_t T, int fs) {
   const int n4 = d4c_fft_size(fs);
-  const size_t stride = (size_t)((d4c_dv_len(fs, n4, d4c_nbands(fs)) + 1) & ~1);
+  const size_t stride = (size_t)((d4c_dv_len(fs, n4, kwy_band_count(fs)) + 1) & ~1);
   return kwy_pad(sizeof(double) * (size_t)T * (stride > 0 ? stride : 2)) + 2 * kwy_pad(sizeof(uint64_t) * (T + 1)) +
          kwy_pad(sizeof(uint64_t) * 3 * T) + kwy_pad(sizeof(double) * T);
 }
@@ -1075,10 +1066,7 @@ static int d4c_core(kwy_ctx *ctx, d4c_batch &b, int fs, double threshold, int ff
   p.fs = fs;
   p.fft_size = fft_size;
   p.K = fft_size / 2 + 1;
-  double lim = fs / 2.0 - D4C_FREQ_INTERVAL;
-  if (lim > D4C_UPPER_LIMIT) lim = D4C_UPPER_LIMIT;
-  p.nbands = (int)(lim / D4C_FREQ_INTERVAL);
-  if (p.nbands < 0) p.nbands = 0;
+  p.nbands = kwy_band_count(fs);
   if (p.nbands > 5) { ctx->err = "d4c: too many bands"; return KWY_EINVAL; }
   p.window_length = (int)(D4C_FREQ_INTERVAL * n4 / fs) * 2 + 1;
   p.dv_len = d4c_dv_len(fs, n4, p.nbands);

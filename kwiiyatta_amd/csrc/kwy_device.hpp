@@ -2,6 +2,7 @@
 //   * WORLD's xorshift128 "randn" stream with GF(2) jump-ahead, so that every
 //     frame / pulse draws exactly the numbers the serial CPU algorithm would
 //   * block-wide f64 reductions and scans (64-wide wavefronts)
+//   * the small routines that several kernels must compute bit for bit alike (band codec, delta windows, row placement)
 //   * LDS-resident double-precision Stockham FFTs (radix-4 + one radix-2 pass)
 //     and the half-length real-FFT packing around them
 // Written for CDNA4 only (wave64, 160 KB LDS); no portability layer.
@@ -13,6 +14,9 @@
 #define KWY_THREADS 256
 #define KWY_WAVES (KWY_THREADS / 64)
 #define KWY_PI 3.1415926535897932384
+#define KWY_SAFE 0.000000000001                    // WORLD's safe guard (world/constantnumbers.h)
+#define KWY_DBL_MAX 1.79769313486231570815e+308
+static_assert(1.0 - KWY_SAFE == 1.0 - 1e-12, "the two spellings of the safe guard are one double");
 
 // ---------------------------------------------------------------- xorshift128
 struct kwy_rng {
@@ -527,6 +531,108 @@ __device__ __forceinline__ void kwy_block_sum2(double a, double b, double *red, 
 #pragma unroll
   for (int i = 1; i < NT / 64; ++i) { sa += red[i]; sb += red[NT / 64 + i]; }
   *ta = sa; *tb = sb;
+}
+
+// exclusive scan of one int per thread over the block of NT threads; *total = the sum.  sh: NT / 64 ints of LDS.
+template <int NT = KWY_THREADS>
+__device__ __forceinline__ int kwy_block_exscan(int v, int *sh, int *total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int inc = (int)kwy_wave_scan_u32((uint32_t)v);
+  __syncthreads();
+  if (lane == 63) sh[wv] = inc;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    if (w < wv) base += sh[w];
+    tot += sh[w];
+  }
+  *total = tot;
+  return base + inc - v;
+}
+
+// --------------------------------------------------- routines that kernels share bit for bit
+// Where two kernels must produce the same bits (the band track and the codec, the band rows and
+// kwy_delta_features_dev) they call ONE routine; the library is built with -ffp-contract=off, so
+// an expression here rounds the same wherever it is inlined.  (Left apart on purpose: k_delta of
+// kwy_mlpg.hip, the interp1Q variants with D4C's decode, the two-pass moments kernels: DESIGN.md.)
+
+// finite, and of the sign a site asks for (the three forms differ for negative values and zero)
+__host__ __device__ __forceinline__ bool kwy_finite(double v) { return fabs(v) <= KWY_DBL_MAX; }
+__host__ __device__ __forceinline__ bool kwy_finite_pos(double v) { return v > 0.0 && v <= KWY_DBL_MAX; }
+__host__ __device__ __forceinline__ bool kwy_finite_nonneg(double v) { return v >= 0.0 && v <= KWY_DBL_MAX; }
+
+// WORLD's aperiodicity bands (codec.cpp): centres at 3 kHz, 6 kHz, ... below fs / 2 - 3 kHz, at most 15 kHz
+#define KWY_BAND_INTERVAL 3000.0
+#define KWY_BAND_UPPER 15000.0
+#define KWY_BAND_MAX 8
+#define KWY_BAND_FLOOR -60.0                       // the decoder's node at 0 Hz
+__host__ inline int kwy_band_count(int fs) {
+  double lim = fs / 2.0 - KWY_BAND_INTERVAL;
+  if (lim > KWY_BAND_UPPER) lim = KWY_BAND_UPPER;
+  const int n = (int)(lim / KWY_BAND_INTERVAL);
+  return n < 0 ? 0 : n;
+}
+
+// the coder's value of band b of a frame: interp1Q(0, fs / fft, 20 log10(row), K, 3000 (b + 1))
+__device__ __forceinline__ double kwy_band_code(const double *__restrict__ row, int K, int fs, int fft_size, int b) {
+  const double shift = (double)fs / fft_size;
+  const double xi = KWY_BAND_INTERVAL * (b + 1.0);
+  const int base = (int)((xi - 0) / shift);
+  const double frac = (xi - 0) / shift - base;
+  const double y0 = 20 * log10(row[base]);
+  const double dy = (base >= K - 1) ? 0.0 : 20 * log10(row[base + 1]) - y0;
+  return y0 + dy * frac;
+}
+
+// the decoder's value of bin k over the nodes {0: coarse[0], 3k (i + 1): coarse[i + 1], fs / 2: coarse[nb + 1]}
+__device__ __forceinline__ double kwy_band_decode_bin(const double *coarse, int fs, int fft_size, int nb, int k) {
+  const int nn = nb + 2;
+  const double xi = (double)fs / fft_size * k;
+  int seg = 0;  // number of nodes <= xi  (WORLD histc)
+  for (int j = 0; j < nn; ++j) {
+    const double xj = (j <= nb) ? j * KWY_BAND_INTERVAL : fs / 2.0;
+    if (xj <= xi) seg = j + 1;
+  }
+  if (seg < 1) seg = 1;
+  if (seg > nn - 1) seg = nn - 1;
+  const double xa = (seg - 1 <= nb) ? (seg - 1) * KWY_BAND_INTERVAL : fs / 2.0;
+  const double xb = (seg <= nb) ? seg * KWY_BAND_INTERVAL : fs / 2.0;
+  const double s = (xi - xa) / (xb - xa);
+  const double v = coarse[seg - 1] + s * (coarse[seg] - coarse[seg - 1]);
+  return pow(10.0, v / 20.0);
+}
+
+// the reference's DELTA_WINDOWS [-0.5, 0, 0.5] and [1, -2, 1] on three neighbours (np.correlate: the products are
+// summed in tap order; a neighbour outside the sequence is passed as 0.0)
+__device__ __forceinline__ void kwy_delta_windows(double xm, double x0, double xp, double *d1, double *d2) {
+  *d1 = (-0.5 * xm + 0.0 * x0) + 0.5 * xp;
+  *d2 = (1.0 * xm + -2.0 * x0) + 1.0 * xp;
+}
+
+// the row count of a job: the host value, or the device word clamped to [0, rows] (rows is then the lists' capacity)
+__device__ __forceinline__ int64_t kwy_device_count(int64_t rows, const int64_t *n_dev) {
+  if (!n_dev) return rows;
+  const int64_t w = *n_dev;
+  return w < 0 ? 0 : (w < rows ? w : rows);
+}
+
+__device__ __forceinline__ int64_t kwy_clamp_row(int64_t r, int64_t rows) { return r < 0 ? 0 : (r >= rows ? rows - 1 : r); }
+
+// One thread: the places of n jobs' rows in a matrix of capacity_rows, in job order behind the cursor; rows_word(k)
+// is job k's row count.  A job that would not fit is dropped whole and flagged (count = -1 - rows it had).
+template <class F>
+__device__ __forceinline__ void kwy_place_rows(int n, F rows_word, int64_t *__restrict__ cursor, int64_t capacity_rows,
+                                               int64_t *__restrict__ places) {
+  int64_t at = cursor[0];
+  for (int k = 0; k < n; ++k) {
+    int64_t *word = rows_word(k);
+    const int64_t r = word[0];
+    if (at + r > capacity_rows) { places[k] = -1; word[0] = -1 - r; continue; }
+    places[k] = at;
+    at += r;
+  }
+  cursor[0] = at;
 }
 
 // Sum of the m smallest of n non-negative doubles, and the sum of all of them, without sorting.  Thread t holds the

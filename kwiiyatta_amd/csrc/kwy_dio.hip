@@ -34,7 +34,6 @@
 
 #include "kwy_internal.hpp"
 
-#define DIO_SAFE 0.000000000001
 #define DIO_MAXVAL 100000.0
 #define DIO_CUTOFF 50.0
 #define DIO_MAX_BANDS 16
@@ -316,7 +315,7 @@ __global__ void k_dio_candidates(dio_plan P) {
     if (c > bf || c < bf / 2.0 || c > P.f0_ceil || c < P.f0_floor) { c = 0.0; sc = DIO_MAXVAL; }
   }
   P.at<double>(utt, P.off_cand)[(int64_t)b * P.T_max + j] = c;
-  P.at<double>(utt, P.off_score)[(int64_t)b * P.T_max + j] = sc / (c + DIO_SAFE);
+  P.at<double>(utt, P.off_score)[(int64_t)b * P.T_max + j] = sc / (c + KWY_SAFE);
 }
 
 // ---- best contour + WORLD FixF0Contour -----------------------------------------------------------
@@ -395,7 +394,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_dio_fix(dio_plan p) {
     double v = 0.0;
     if (i >= vrm) {
       double fb = base(i);
-      v = fabs((fb - base(i - 1)) / (DIO_SAFE + fb)) < p.allowed_range ? fb : 0.0;
+      v = fabs((fb - base(i - 1)) / (KWY_SAFE + fb)) < p.allowed_range ? fb : 0.0;
     }
     w2[i] = v;
   }
@@ -615,7 +614,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_stonemask(sm_batch batch, int f
         denominator += amp * (h + 1);
       }
     }
-    const double est = numerator / (denominator + DIO_SAFE);
+    const double est = numerator / (denominator + KWY_SAFE);
     __syncthreads();
     if (pass == 0) {
       if (est <= 0.0 || est > initial_f0 * 2) { mean_f0 = 0.0; break; }

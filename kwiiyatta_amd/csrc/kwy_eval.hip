@@ -26,7 +26,6 @@
 #define EV_GROUP 16        // utterances per launch
 #define EV_MAX_COLS 64
 #define EV_DB (10.0 / 2.302585092994045684)      // 10 / ln 10
-#define EV_DBL_MAX 1.79769313486231570815e+308
 
 struct ev_mcd {
   const double *a, *b;
@@ -50,13 +49,6 @@ struct ev_f0 {
   int64_t a_len, b_len, off_a, off_b, rows;
 };
 typedef kwy_group<ev_f0, EV_GROUP> ev_f0s;
-
-// the row count of a job: the host value, or the device word clamped to [0, rows] (rows is then the lists' capacity)
-__device__ __forceinline__ int64_t ev_rows(int64_t rows, const int64_t *n_dev) {
-  if (!n_dev) return rows;
-  const int64_t w = *n_dev;
-  return w < 0 ? 0 : (w < rows ? w : rows);
-}
 
 // sum over the SLOTS lanes that share a row (a whole wavefront, or one of its halves); each of them gets the result
 template <int SLOTS>
@@ -112,7 +104,7 @@ __device__ __forceinline__ void ev_mcd_pass(const ev_mcd &U, int64_t n, int cols
 #pragma unroll
     for (int q = 0; q < EV_AHEAD; ++q) {
       const int64_t t = t0 + q * G + g;
-      const bool odd = !(fabs(x[q]) <= EV_DBL_MAX && fabs(y[q]) <= EV_DBL_MAX);      // a coefficient that is not finite
+      const bool odd = !(kwy_finite(x[q]) && kwy_finite(y[q]));      // a coefficient that is not finite
       const double d = x[q] - y[q];
       const double s = ev_slot_sum<SLOTS>(odd ? 0.0 : d * d);
       const unsigned long long odd_lanes = __ballot(odd);
@@ -152,7 +144,7 @@ template <int SLOTS>
 __device__ __forceinline__ void ev_mcd_job(const ev_mcd &U, int cols, int first_col, double *part) {
   constexpr int G = KWY_THREADS / SLOTS;
   const int c = threadIdx.x % SLOTS, g = threadIdx.x / SLOTS;
-  const int64_t n = ev_rows(U.rows, U.n_dev);
+  const int64_t n = kwy_device_count(U.rows, U.n_dev);
   double sum = 0.0, cnt = 0.0, m2 = 0.0, none = 0.0;
   int left_out = 0, unused = 0;
   ev_mcd_pass<SLOTS, false>(U, n, cols, first_col, 0.0, sum, cnt, left_out);
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_eval_f0(ev_f0s B) {
   __shared__ double red[KWY_WAVES];
   const ev_f0 &U = B.u[blockIdx.x];
   const int tid = threadIdx.x;
-  const int64_t n = ev_rows(U.rows, U.n_dev);
+  const int64_t n = kwy_device_count(U.rows, U.n_dev);
   double vv = 0.0, vu = 0.0, uv = 0.0, uu = 0.0, bad = 0.0, sum = 0.0;
   for (int pass = 0; pass < 2; ++pass) {
     const double mean = vv > 0.0 ? sum / vv : 0.0;        // (second pass: of the first pass's totals)
@@ -193,7 +185,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_eval_f0(ev_f0s B) {
       const int64_t ra = (U.ia ? (int64_t)U.ia[t] : t) - U.off_a, rb = (U.ib ? (int64_t)U.ib[t] : t) - U.off_b;
       if (!(ra >= 0 && ra < U.a_len && rb >= 0 && rb < U.b_len)) continue;      // beyond either track: not a frame
       const double fa = U.fa[ra], fb = U.fb[rb];
-      if (!(fa >= 0.0 && fa <= EV_DBL_MAX && fb >= 0.0 && fb <= EV_DBL_MAX)) { c_bad += 1.0; continue; }
+      if (!(fa >= 0.0 && fa <= KWY_DBL_MAX && fb >= 0.0 && fb <= KWY_DBL_MAX)) { c_bad += 1.0; continue; }
       const bool va = fa > 0.0, vb = fb > 0.0;
       if (va && vb) {
         const double cents = 1200.0 * log2(fa / fb);

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_f0_map(f0m_maps B, const double
     else y = f * ratio;
     U.out[i] = y;
     // negative or non-finite input, or an output at or beyond the limit (a NaN output fails `y < limit`)
-    if (!(f >= 0.0 && f <= 1.79769313486231570815e+308) || !(y < limit)) bad += 1.0;
+    if (!kwy_finite_nonneg(f) || !(y < limit)) bad += 1.0;
   }
   bad = kwy_block_sum(bad, red);
   if (tid == 0 && U.status) *U.status = (int32_t)fmin(bad, 2147483647.0);

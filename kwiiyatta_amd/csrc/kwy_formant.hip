@@ -94,7 +94,7 @@ __global__ __launch_bounds__(FS_THREADS, W) void k_formant_shift(fs_views B, int
       const int i = tid + q * NT;
       if (i < count) {
         lg[i] = kwy_log(v[q]);
-        if (!(v[q] > 0.0 && v[q] <= 1.79769313486231570815e+308)) bad[par][tap[q] >> 16] = 1;
+        if (!kwy_finite_pos(v[q])) bad[par][tap[q] >> 16] = 1;
       }
     }
     __syncthreads();

@@ -129,8 +129,8 @@ __global__ __launch_bounds__(KWY_THREADS) void k_gv_apply(gv_applies B, int cols
     const double n = U.moments[3 * tid], g = gv[tid];
     if (tid >= first_col) {
       const double v = n > 0.0 ? U.moments[3 * tid + 2] / n : 0.0;       // (no rows: nothing to stretch)
-      const bool v_ok = v >= 0.0 && v <= 1.79769313486231570815e+308;
-      const bool g_ok = g > 0.0 && g <= 1.79769313486231570815e+308;
+      const bool v_ok = v >= 0.0 && v <= KWY_DBL_MAX;
+      const bool g_ok = g > 0.0 && g <= KWY_DBL_MAX;
       if (!v_ok || !g_ok) bad = 1;
       else if (v > 0.0) k = strength * (sqrt(g / v) - 1.0);
     }

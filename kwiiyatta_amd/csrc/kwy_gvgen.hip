@@ -35,7 +35,6 @@
 #define GVA_NS 5             // sums of the widest reduction
 #define GVA_RED (2 * (GVA_NT / 64) * GVA_NS + 8)   // two buffers, used in turn: one barrier per reduction
 #define GVA_MAX_COLS 64
-#define GVA_DBL_MAX 1.79769313486231570815e+308
 
 struct gva_job {
   const double *band;
@@ -108,7 +107,7 @@ __device__ double gva_root(double c0, double c1, double c2, double c3) {
     hi = lo + h;
     int it = 0;
     while (f(hi) > 0.0) {
-      if (++it > 2100 || !(hi <= GVA_DBL_MAX)) return -1.0;
+      if (++it > 2100 || !(hi <= KWY_DBL_MAX)) return -1.0;
       lo = hi;
       h *= 2.0;
       hi = lo + h;
@@ -144,7 +143,7 @@ __global__ __launch_bounds__(GVA_NT) void k_gv_ascent(gva_jobs J, int d, const d
     for (int k = tid; k <= N; k += GVA_NT) qo[k] = 0.0;
     if (tid == 0) qo[N + 1] = flag;
   };
-  if (!(mu > 0.0 && mu <= GVA_DBL_MAX && var > 0.0 && var <= GVA_DBL_MAX)) { leave(1.0); return; }
+  if (!(mu > 0.0 && mu <= KWY_DBL_MAX && var > 0.0 && var <= KWY_DBL_MAX)) { leave(1.0); return; }
 
   double *red = (double *)gva_smem;
   double *trk = LDSTRK ? red + GVA_RED : U.tracks + (size_t)c * 3 * ((size_t)T + 4);
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(GVA_NT) void k_gv_ascent(gva_jobs J, int d, const d
 
   double zbar, v;
   double Q = evaluate(yt, false, 0.0, zbar, v);
-  if (!(v >= 0.0 && v <= GVA_DBL_MAX)) { leave(1.0); return; }
+  if (!kwy_finite_nonneg(v)) { leave(1.0); return; }
   if (v == 0.0) { leave(0.0); return; }
   {
     const double a = sqrt(mu / v);
@@ -276,7 +275,7 @@ __global__ __launch_bounds__(GVA_NT) void k_gv_ascent(gva_jobs J, int d, const d
       }
       double gp = gg + beta * s5[4];
       if (!(gp > 0.0)) { beta = 0.0; gp = gg; }
-      if (!(gp > 0.0 && gp <= GVA_DBL_MAX)) {
+      if (!kwy_finite_pos(gp)) {
         frozen = true;
       } else {
         const double pr = s5[2] + beta * s5[3];      // p.(b - P y)
@@ -305,7 +304,7 @@ __global__ __launch_bounds__(GVA_NT) void k_gv_ascent(gva_jobs J, int d, const d
         const double c2 = -6.0 * kap * cov * vp;
         const double c3 = -2.0 * kap * vp * vp;
         const double alpha = gva_root(c0, c1, c2, c3);
-        if (!(alpha > 0.0 && alpha <= GVA_DBL_MAX)) {
+        if (!kwy_finite_pos(alpha)) {
           frozen = true;
         } else {
           double zbar1, v1;
@@ -426,7 +425,7 @@ static int gva_check(kwy_ctx *ctx, const kwy_gv_ascent_job *jobs, int count, int
     ctx->err = "gv_ascent: bad argument";
     return KWY_EINVAL;
   }
-  if (!(weight > 0.0 && weight <= GVA_DBL_MAX)) {
+  if (!kwy_finite_pos(weight)) {
     ctx->err = "gv_ascent: weight must be positive and finite";
     return KWY_EINVAL;
   }

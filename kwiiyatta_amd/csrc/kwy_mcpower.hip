@@ -111,7 +111,6 @@ __device__ __forceinline__ void mp_energies(const double *coef, int order, int H
   __syncthreads();
 }
 
-__device__ __forceinline__ bool mp_usable(double e) { return e > 0.0 && e <= 1.79769313486231570815e+308; }
 
 template <int BPT>
 __global__ __launch_bounds__(KWY_THREADS) void k_mcpower_filter(mp_jobs J, int order, double alpha, double beta, int H,
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_mcpower_filter(mp_jobs J, int o
       __syncthreads();
       mp_energies<BPT>(coef, order, H, tab, red, Es);
       const double corr = log(Es[2 * r] / Es[2 * r + 1]) / 2.0;
-      failed = !(mp_usable(Es[2 * r]) && mp_usable(Es[2 * r + 1]) && fabs(corr) <= 1.79769313486231570815e+308);
+      failed = !(kwy_finite_pos(Es[2 * r]) && kwy_finite_pos(Es[2 * r + 1]) && kwy_finite(corr));
       if (!failed) {
         double yv = coef[m * MP_NV + 2 * r + 1];
         if (m == 0) yv = yv + corr;

@@ -149,6 +149,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_gmm_prep(const double *__restri
 // DELTA_WINDOWS (kwiiyatta/converter/delta.py:8-12): [1], [-0.5, 0, 0.5], [1, -2, 1]
 // x rows are ldx doubles apart.  keep_in / keep_out (may be null): one more column that is copied through
 // unchanged (the power coefficient c0 of a mel-cepstrum, kwiiyatta/converter/mcep.py:57-59), ldx / ldy apart.
+// NOT kwy_delta_windows: this sums from 0.0 and skips outside taps, which signs some zeros differently (recorded bits).
 __global__ void k_delta(ml_batch b, ml_dims dm, double *__restrict__ X) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= dm.T * dm.d) return;
@@ -1284,7 +1285,7 @@ static int ml_check(kwy_ctx *ctx, const ml_job &q, int d, int M, const ml_mixtur
   }
   if (o.gv) {
     if (!o.gv->mean || !o.gv->var) { ctx->err = "gmm_mlpg_gv: bad argument"; return KWY_EINVAL; }
-    if (!(o.gv->weight > 0.0 && o.gv->weight <= 1.79769313486231570815e+308)) {
+    if (!kwy_finite_pos(o.gv->weight)) {
       ctx->err = "gmm_mlpg_gv: weight must be positive and finite";
       return KWY_EINVAL;
     }

@@ -48,7 +48,6 @@ struct ms_cfg {
   static constexpr int NT = LOG2H == 12 ? 512 : 256;
 };
 
-__device__ __forceinline__ bool ms_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 template <int LOG2H, bool FILTER>
 __global__ __launch_bounds__(ms_cfg<LOG2H>::NT) void k_ms(ms_views B, int cols, int first_col,
@@ -133,14 +132,14 @@ __global__ __launch_bounds__(ms_cfg<LOG2H>::NT) void k_ms(ms_views B, int cols, 
     const double *__restrict__ g3 = statsG + 3 * ((int64_t)c * K + f), *__restrict__ n3 = statsN + 3 * ((int64_t)c * K + f);
     const double nG = g3[0], muG = g3[1], nN = n3[0], muN = n3[1];
     double g = 1.0;
-    bool ok = nG >= 2.0 && nN >= 2.0 && ms_finite(muG) && ms_finite(muN);
+    bool ok = nG >= 2.0 && nN >= 2.0 && kwy_finite(muG) && kwy_finite(muN);
     if (ok) {
       const double sG = sqrt(g3[2] / nG), sN = sqrt(n3[2] / nN);
-      ok = ms_finite(sG) && sG > 0.0 && ms_finite(sN) && sN >= 0.0;
+      ok = kwy_finite(sG) && sG > 0.0 && kwy_finite(sN) && sN >= 0.0;
       if (ok) {
         const double sp = (1.0 - strength) * s + strength * (sN / sG * (s - muG) + muN);
         g = exp((sp - s) / 2.0);
-        ok = ms_finite(g);
+        ok = kwy_finite(g);
       }
     }
     if (!ok) {

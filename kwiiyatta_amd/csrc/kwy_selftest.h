@@ -20,6 +20,10 @@ int kwy_debug_select_paths512_dev(void *stream, const double *values, int proble
                                   double *out_new);
 /* kwy_log(x) and kwy_sincos_medium(x) of kwy_device.hpp for every element of x (n doubles, device). */
 int kwy_debug_devmath_dev(void *stream, const double *x, int n, double *log_out, double *sin_out, double *cos_out);
+/* kwy_block_exscan of kwy_device.hpp, one workgroup of 256 threads per problem.  values, offsets: problems x 256 ints
+ * (device), offsets[i] = the sum of the problem's values before i; totals: problems ints (device), as the last thread
+ * of the workgroup received them. */
+int kwy_debug_block_exscan_dev(void *stream, const int *values, int problems, int *offsets, int *totals);
 /* The real FFT of rows of 2^log2n samples through both closing passes of the LDS transform: the stored one and the
  * one drained into registers (kwy_fft_tail4_drain).  x: problems x 2^log2n doubles (device); out_old / out_new:
  * problems x (2^(log2n-1) + 1) x {re, im} (device), twice the bins 0 .. N/2.  log2n = 12 is the only size with a

@@ -23,7 +23,6 @@
 
 #include "kwy_internal.hpp"
 
-#define SYN_SAFE 0.000000000001
 #define SYN_DEFAULT_F0 500.0
 #define SYN_TILE_PER_THREAD 4
 #define SYN_TILE (KWY_THREADS * SYN_TILE_PER_THREAD)
@@ -80,27 +79,6 @@ __device__ __forceinline__ double syn_increment(const double *__restrict__ f0, c
   if (v == 0.0) f = SYN_DEFAULT_F0;
   *vuv_out = v;
   return 2.0 * KWY_PI * f / p.fs;
-}
-
-__device__ __forceinline__ int syn_block_exscan_int(int v, int *sh, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int u = __shfl_up(inc, o);
-    if (lane >= o) inc += u;
-  }
-  __syncthreads();
-  if (lane == 63) sh[wv] = inc;
-  __syncthreads();
-  int woff = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < KWY_WAVES; ++i) {
-    if (i < wv) woff += sh[i];
-    tot += sh[i];
-  }
-  *total = tot;
-  return woff + (inc - v);
 }
 
 __device__ __forceinline__ void syn_scan_counts_body(int *__restrict__ cnt, int nt,
@@ -706,7 +684,7 @@ __device__ __forceinline__ void syn_pulse_count_body(const double *__restrict__ 
 #pragma unroll
   for (int j = 0; j < SYN_TILE_PER_THREAD; ++j) c += syn_is_pulse(wrap, base + j, y_length) ? 1 : 0;
   int tot;
-  (void)syn_block_exscan_int(c, sh, &tot);
+  (void)kwy_block_exscan(c, sh, &tot);
   if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
 }
 
@@ -722,7 +700,7 @@ __device__ __forceinline__ void syn_pulse_emit_body(const double *__restrict__ w
 #pragma unroll
   for (int j = 0; j < SYN_TILE_PER_THREAD; ++j) c += syn_is_pulse(wrap, base + j, y_length) ? 1 : 0;
   int tot;
-  int pos = tile_off[blockIdx.x] + syn_block_exscan_int(c, sh, &tot);
+  int pos = tile_off[blockIdx.x] + kwy_block_exscan(c, sh, &tot);
 #pragma unroll
   for (int j = 0; j < SYN_TILE_PER_THREAD; ++j) {
     int64_t n = base + j;
@@ -1007,7 +985,7 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
         const int k = tid + NT * r;
         if (k <= H) {
           lap[k] = kwy_log((current_vuv != 0.0) ? evs[r] * rts[r] : evs[r]) / 2.0;
-          if (has_periodic) L[k] = kwy_log(evs[r] * (1.0 - rts[r]) + SYN_SAFE) / 2.0;
+          if (has_periodic) L[k] = kwy_log(evs[r] * (1.0 - rts[r]) + KWY_SAFE) / 2.0;
         }
       }
     }

@@ -20,22 +20,9 @@
 
 #define TR_NT 256
 
-// exclusive scan of one int per thread over the workgroup; *total = sum.  sh: TR_NT/64 + 1 ints
-__device__ __forceinline__ int tr_block_exscan(int v, int *sh, int *total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = (int)kwy_wave_scan_u32((uint32_t)v);
-  __syncthreads();
-  if (lane == 63) sh[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < TR_NT / 64; ++w) {
-    if (w < wv) base += sh[w];
-    tot += sh[w];
-  }
-  *total = tot;
-  return base + inc - v;
-}
+// WorldSynthesizer.extract_is_voiced (kwiiyatta/vocoder/world.py:147-151) of one frame, and its lowest f0
+__device__ __forceinline__ bool tr_voiced(double f0, double ap0, double lowest_f0) { return f0 >= lowest_f0 && ap0 <= 0.999; }
+static double tr_lowest_f0(int fs, int K) { return fs / ((K - 1) / 2.0) + 1.0; }
 
 // rowsum[t] = sum_k |sp[t][k]|   (one wavefront per row)
 __device__ __forceinline__ void tr_rowsum_body(const double *__restrict__ sp, int64_t T, int K,
@@ -68,7 +55,7 @@ __global__ void k_tr_is_voiced(const double *__restrict__ f0, const double *__re
                                double lowest_f0, double *__restrict__ out) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
-  out[t] = (f0[t] >= lowest_f0 && ap[t * K] <= 0.999) ? 1.0 : 0.0;
+  out[t] = tr_voiced(f0[t], ap[t * K], lowest_f0) ? 1.0 : 0.0;
 }
 
 // The reference's `check` (align.py:73-80, with its y_feature[y, 0] in the voicing test kept as written) on the
@@ -104,7 +91,7 @@ __device__ __forceinline__ void tr_align_even_body(const int32_t *__restrict__ p
     const int64_t v = v0 + tid;
     const int k = (v < Lv && keep(v)) ? 1 : 0;
     int tot;
-    const int off = tr_block_exscan(k, sh, &tot);
+    const int off = kwy_block_exscan<TR_NT>(k, sh, &tot);
     const int run = s_run;
     if (v < Lv) pos[v] = k ? run + off : -1;
     __syncthreads();
@@ -152,8 +139,7 @@ __global__ void k_tr_delta(const double *__restrict__ x, const int64_t *__restri
     const double xm = t > 0 ? x[(t - 1) * d + c] : 0.0, x0 = x[t * d + c], xp = t + 1 < n ? x[(t + 1) * d + c] : 0.0;
     double *o = out + t * 3 * d;
     o[c] = x0;
-    o[d + c] = (-0.5 * xm + 0.0 * x0) + 0.5 * xp;
-    o[2 * d + c] = (1.0 * xm + -2.0 * x0) + 1.0 * xp;
+    kwy_delta_windows(xm, x0, xp, &o[d + c], &o[2 * d + c]);
   }
 }
 
@@ -182,7 +168,7 @@ __device__ __forceinline__ void tr_joint_body(const double *__restrict__ xd, con
       if (lane == r) k = (t < n && !(s < eps)) ? 1 : 0;
     }
     int tot;
-    const int off = tr_block_exscan(k, sh, &tot);   // thread (wv, lane) <-> row t0 + 64 wv + lane = t0 + tid
+    const int off = kwy_block_exscan<TR_NT>(k, sh, &tot);   // thread (wv, lane) <-> row t0 + 64 wv + lane = t0 + tid
     const int run = s_run;
     s_dst[tid] = k ? run + off : -1;
     __syncthreads();
@@ -239,7 +225,7 @@ struct tr_pad_view { const double *f0; int64_t n; double *f0_pad; double *ap_pad
 __global__ __launch_bounds__(TR_NT) void k_tr_pad(tr_jobs<tr_pad_view> b, int K, int pad, double lowest_f0) {
   const tr_pad_view &q = b.u[blockIdx.y];
   const int64_t Tp = q.n + 2 * pad;
-  const double one = 1.0 - 1e-12;
+  const double one = 1.0 - KWY_SAFE;
   // tail rows of the aperiodicity: workgroups 0 .. pad - 1 take one row each
   if ((int)blockIdx.x < pad) {
     double *row = q.ap_pad + (size_t)(pad + q.n + blockIdx.x) * K;
@@ -251,7 +237,7 @@ __global__ __launch_bounds__(TR_NT) void k_tr_pad(tr_jobs<tr_pad_view> b, int K,
     q.f0_pad[t] = f;
     if (q.voiced) {
       const double a0 = in ? q.ap_pad[(size_t)t * K] : one;
-      q.voiced[t] = (f >= lowest_f0 && a0 <= 0.999) ? 1.0 : 0.0;
+      q.voiced[t] = tr_voiced(f, a0, lowest_f0) ? 1.0 : 0.0;
     }
   }
 }
@@ -281,33 +267,23 @@ __global__ void k_tr_rows_delta(tr_rows_table b, int d) {
   const double *__restrict__ mc = side ? v.q.mc_y : v.q.mc_x;
   const int32_t *__restrict__ idx = side ? v.idx_y : v.idx_x;
   const int64_t rows = side ? v.q.y_length : v.q.x_length;
-  auto row = [&](int64_t tt) { int64_t r = idx[tt]; r = r < 0 ? 0 : (r >= rows ? rows - 1 : r); return mc + r * (d + 1) + 1; };
+  auto row = [&](int64_t tt) { return mc + kwy_clamp_row(idx[tt], rows) * (d + 1) + 1; };
   const double *r0 = row(t), *rm = t > 0 ? row(t - 1) : r0, *rp = t + 1 < n ? row(t + 1) : r0;
   double *o = (side ? v.yd : v.xd) + t * 3 * d;
   for (int c = threadIdx.x; c < d; c += blockDim.x) {
     const double xm = t > 0 ? rm[c] : 0.0, x0 = r0[c], xp = t + 1 < n ? rp[c] : 0.0;
     o[c] = x0;
-    o[d + c] = (-0.5 * xm + 0.0 * x0) + 0.5 * xp;
-    o[2 * d + c] = (1.0 * xm + -2.0 * x0) + 1.0 * xp;
+    kwy_delta_windows(xm, x0, xp, &o[d + c], &o[2 * d + c]);
   }
 }
 __global__ __launch_bounds__(TR_NT) void k_tr_rows_count(tr_rows_table b, int w, double eps) {
   const tr_rows_view &v = b.u[blockIdx.x];
   tr_joint_body<false>(v.xd, v.yd, v.n_sel, v.cap, w, eps, nullptr, v.q.n_rows);
 }
-// the pairs' places in the matrix, in pair order behind the cursor; a pair that would not fit is dropped whole and
-// flagged (n_rows = -1 - rows it had)
 __global__ void k_tr_rows_place(tr_rows_table b, int64_t *__restrict__ cursor, int64_t capacity_rows,
                                 int64_t *__restrict__ places) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  int64_t at = cursor[0];
-  for (int k = 0; k < b.n; ++k) {
-    const int64_t n = b.u[k].q.n_rows[0];
-    if (at + n > capacity_rows) { places[k] = -1; b.u[k].q.n_rows[0] = -1 - n; continue; }
-    places[k] = at;
-    at += n;
-  }
-  cursor[0] = at;
+  kwy_place_rows(b.n, [&](int k) { return b.u[k].q.n_rows; }, cursor, capacity_rows, places);
 }
 __global__ __launch_bounds__(TR_NT) void k_tr_rows_write(tr_rows_table b, int w, double eps,
                                                         double *__restrict__ joint, const int64_t *__restrict__ places) {
@@ -356,7 +332,7 @@ extern "C" int kwy_train_pad_batch_dev(kwy_ctx *ctx, const kwy_pad_job *jobs, in
     if (!jobs[j].f0 || !jobs[j].f0_pad || !jobs[j].ap_pad || jobs[j].n < 0) { ctx->err = "train_pad: bad argument"; return KWY_EINVAL; }
   if (count == 0) return KWY_OK;
   KWY_HIP(hipSetDevice(ctx->device));
-  const double lowest = fs / ((K - 1) / 2.0) + 1.0;
+  const double lowest = tr_lowest_f0(fs, K);
   kwy_for_tables<tr_jobs<tr_pad_view>>(
       count, [&](int j) { return tr_pad_view{jobs[j].f0, jobs[j].n, jobs[j].f0_pad, jobs[j].ap_pad, jobs[j].voiced}; },
       [&](const tr_jobs<tr_pad_view> &b, int) {
@@ -433,7 +409,7 @@ extern "C" int kwy_is_voiced_dev(kwy_ctx *ctx, const double *f0, const double *a
   if (!ctx) return KWY_EINVAL;
   if (!f0 || !ap || !voiced || T <= 0 || K < 2 || fs <= 0) { ctx->err = "is_voiced: bad argument"; return KWY_EINVAL; }
   KWY_HIP(hipSetDevice(ctx->device));
-  const double lowest = fs / ((K - 1) / 2.0) + 1.0;
+  const double lowest = tr_lowest_f0(fs, K);
   hipLaunchKernelGGL(k_tr_is_voiced, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, ctx->stream, f0, ap, T, K, lowest,
                      voiced);
   KWY_HIP(hipGetLastError());

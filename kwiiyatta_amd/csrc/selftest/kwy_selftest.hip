@@ -265,6 +265,23 @@ extern "C" int kwy_debug_devmath_dev(void *stream, const double *x, int n, doubl
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// ---- diagnostic: kwy_block_exscan, one workgroup of 256 threads per problem ------------------------------------
+__global__ __launch_bounds__(KWY_THREADS) void k_block_exscan_selftest(const int *__restrict__ v,
+                                                                      int *__restrict__ offsets, int *__restrict__ totals) {
+  __shared__ int sh[KWY_WAVES];
+  const int i = blockIdx.x * KWY_THREADS + threadIdx.x;
+  int tot;
+  offsets[i] = kwy_block_exscan(v[i], sh, &tot);
+  if (threadIdx.x == KWY_THREADS - 1) totals[blockIdx.x] = tot;
+}
+
+extern "C" int kwy_debug_block_exscan_dev(void *stream, const int *values, int problems, int *offsets, int *totals) {
+  if (!values || !offsets || !totals || problems <= 0) return -1;
+  hipLaunchKernelGGL(k_block_exscan_selftest, dim3(problems), dim3(KWY_THREADS), 0, (hipStream_t)stream, values,
+                     offsets, totals);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 // ---- diagnostic: the real transform of N = 4096 samples through the stored and the drained closing pass ----------
 // (one 256-thread workgroup per row; both paths return TWICE the bins 0 .. H, (H + 1) x {re, im} per row, formed by
 // kwy_rfft_bin2_w resp. its register form with the same twiddle expressions the D4C kernels use: W^k of a bin below
