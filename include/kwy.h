@@ -200,8 +200,9 @@ typedef struct kwy_synth_plan_job {
 } kwy_synth_plan_job;
 int kwy_synth_plan_batch_dev(kwy_ctx *ctx, const kwy_synth_plan_job *jobs, int count, int fft_size,
                              double frame_period_ms, int fs);
-/* ... for a batch of utterances: one pass of launches renders the pulses of all of them (every utterance a slice of
- * the grids), as kwy_cheaptrick_batch_dev / kwy_d4c_batch_dev analyse them.  What Synthesizer.synthesize does file
+/* ... for a batch of utterances: a pass of launches renders the pulses of up to KWY_BATCH_MAX = 16 of them (dealt to
+ * the workgroups from one queue; the passes of a call share one pool of response slots, 116 MB per 10 s utterance at
+ * 48 kHz), as kwy_cheaptrick_batch_dev / kwy_d4c_batch_dev analyse them.  What Synthesizer.synthesize does file
  * after file (kwiiyatta/vocoder/world.py:63-80, resynthesize_voice.py:46-79).  Every job's waveform equals
  * kwy_synth_render_dev's bit for bit. */
 typedef struct kwy_synth_job {

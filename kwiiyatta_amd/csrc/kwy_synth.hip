@@ -878,7 +878,7 @@ __device__ __forceinline__ double syn_safe_ap(double x) {
 // of the periodic response (H samples and a scalar) takes the place of the aperiodic log-spectrum when that moves
 // into the FFT buffer; the minimum-phase spectrum waits in registers while the noise is transformed.
 // One utterance of a rendering launch (descriptors by value in the kernel arguments, as for the analysis kernels):
-// a launch renders the pulses of up to KWY_BATCH_MAX utterances, each with its own slice of the grid.
+// a launch renders the pulses of up to KWY_BATCH_MAX utterances, dealt to the workgroups from one queue.
 struct syn_view {
   const double *sp, *ap;
   syn_params p;
@@ -895,24 +895,26 @@ template <int LOG2N, bool DIRECT>
 __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2N == 12 ? 2 : 1)) void k_syn_pulse(
     syn_batch batch, kwy_randn_src rs, const uint4 *__restrict__ poly,
     const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP, const kwy_c *__restrict__ twN,
-    const double *__restrict__ dc_remover, long long *__restrict__ dbg) {
+    const double *__restrict__ dc_remover, unsigned *__restrict__ head, long long *__restrict__ dbg) {
   constexpr int NT = syn_pulse_nt<LOG2N>::value, V = KWY_THREADS / NT;
   // diagnostic stamps (tools/syn_pulse_stamps.py): the first voiced pulse that a workgroup from dbg[63] on reaches
   bool stamping = false;
 #define SYN_STAMP(n) do { if (stamping && threadIdx.x == 0) dbg[n] = clock64(); } while (0)
-  const int utt = batch.find(blockIdx.x);
-  const int lblock = (int)blockIdx.x - batch.start[utt], lgrid = batch.start[utt + 1] - batch.start[utt];
+  // The utterance at hand.  DIRECT: the workgroup's own, for good.  The slots' round: the one that owns the workgroup's
+  // current ticket -- a workgroup's tickets only grow, so its utterance only moves forward, and the views (by value:
+  // scalar loads) are read again only when it does.  Tickets [base, end) are the utterance's pulses 0 .. end - base.
+  int utt = DIRECT ? (int)blockIdx.x : 0, base = 0;
   const double *__restrict__ sp = batch.u[utt].sp, *__restrict__ ap = batch.u[utt].ap;
-  const syn_params p = batch.u[utt].p;
+  syn_params p = batch.u[utt].p;
   const int32_t *__restrict__ pidx = batch.u[utt].pidx;
   const double *__restrict__ pshift = batch.u[utt].pshift;
   const unsigned char *__restrict__ vuv8 = batch.u[utt].vuv8;
-  const int *__restrict__ npulse = batch.u[utt].npulse;
-  const int cap = batch.u[utt].cap;
   // the slots' round (every pulse its own slot), or the pulses beyond them (DIRECT: one workgroup, in order, onto y)
-  const int first_pulse = DIRECT ? batch.u[utt].slots : 0, slots = DIRECT ? cap : batch.u[utt].slots;
+  const int first_pulse = DIRECT ? batch.u[utt].slots : 0;
   double *__restrict__ resp = batch.u[utt].resp;
   double *__restrict__ y = batch.u[utt].y;
+  int P = min(batch.u[utt].npulse[0], batch.u[utt].cap);
+  int end = DIRECT ? P : min(P, batch.u[utt].slots);      // this round's pulses (of utterance 0 so far)
   constexpr int N = 1 << LOG2N, H = N / 2, K = H + 1;
   constexpr int C = N / NT;                // draws / output samples per thread: sample tid + NT m
   constexpr int RK = (H + 1 + NT - 1) / NT;
@@ -934,14 +936,43 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
   kwy_c twb[V];
 #pragma unroll
   for (int g = 0; g < V; ++g) twb[g] = twN[tid + NT * g];
-  const int P = min(npulse[0], cap);
-  const int pend = min(P, first_pulse + slots);    // this round's pulses
-  for (int pp = first_pulse + lblock; pp < pend; pp += lgrid) {
+  // The slots' round deals its pulses from a queue: one ticket per pulse, from a returning atomic add on `head` (zero
+  // at launch: k_syn_zero), the pass's utterances one after the other in ticket order.  Thread 0 pulls, the ticket
+  // crosses LDS
+  // (tick[par], in the half of `red` that the block sums leave alone) behind the barrier that opens a pulse, and the
+  // next ticket is pulled as soon as this one is read: it has a whole pulse to arrive (tick[par ^ 1]: the other wave
+  // may still be reading tick[par]).  Holding the ticket in a register to store it later costs a spill and was
+  // measured slower (profiles/synq_variants_serial.txt).  No workgroup waits for another: whatever the grid and
+  // however few of it are resident, every ticket below the total is rendered by whoever drew it, and a workgroup
+  // leaves with the first ticket beyond.  What a pulse computes and where it goes depend on the pulse alone.
+  static_assert(KWY_THREADS / 64 <= 4, "the block sums use red[0 .. 4), the tickets live in red[4]");
+  int *tick = (int *)(red + 4);
+  if constexpr (!DIRECT) {
+    if (tid == 0) tick[0] = (int)atomicAdd(head, 1u);
+  }
+  for (int pp = first_pulse - 1, par = 1;;) {
     const int tid = kwy_tid_opaque();  // keeps address arithmetic local to the pulse (no spills across the FFTs)
+    if constexpr (DIRECT) {
+      if (++pp >= end) return;
+    } else {
+      par ^= 1;
+      __syncthreads();
+      const int ticket = __builtin_amdgcn_readfirstlane(tick[par]);
+      while (ticket >= end) {
+        if (++utt >= batch.n) return;
+        sp = batch.u[utt].sp; ap = batch.u[utt].ap; p = batch.u[utt].p;
+        pidx = batch.u[utt].pidx; pshift = batch.u[utt].pshift; vuv8 = batch.u[utt].vuv8; resp = batch.u[utt].resp;
+        P = min(batch.u[utt].npulse[0], batch.u[utt].cap);
+        base = end;
+        end += min(P, batch.u[utt].slots);
+      }
+      pp = ticket - base;
+      if (tid == 0) tick[par ^ 1] = (int)atomicAdd(head, 1u);
+    }
     const int idx = pidx[pp];
     const int nxt = pidx[min(P - 1, pp + 1)];
     const int noise_size = nxt - idx;
-    __syncthreads();
+    if constexpr (DIRECT) __syncthreads();
     if (noise_size <= 0) continue;  // last pulse: zero response
     const int ns_used = min(noise_size, N);
     const double current_vuv = vuv8[idx] ? 1.0 : 0.0;
@@ -1260,6 +1291,15 @@ __global__ __launch_bounds__(KWY_THREADS) void k_syn_ola(syn_batch batch, int N)
   }
 }
 
+// Zeroes by a launch: the head word of the pulse queue in front of a pass, and the waveform of a job with nothing to
+// place.  (Not memset nodes: in a replayed graph one of them -- 640 bytes at an address that is no multiple of 16 --
+// was seen to fill its aligned middle with a stale 16-byte pattern, tests/test_syn_queue_gpu.py.)
+__global__ __launch_bounds__(KWY_THREADS) void k_syn_zero(double *__restrict__ y, int64_t n, unsigned *__restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * KWY_THREADS + threadIdx.x;
+  if (i < n) y[i] = 0.0;
+  if (head && i == 0) *head = 0u;
+}
+
 // ------------------------------------------------------------------ host side
 static int get_dc_remover(kwy_ctx *ctx, int fft_size, const double **out) {
   std::string key = "dcrem:" + std::to_string(fft_size);
@@ -1280,7 +1320,7 @@ static int get_dc_remover(kwy_ctx *ctx, int fft_size, const double **out) {
 }
 
 template <int LOG2N>
-static int launch_pulse(kwy_ctx *ctx, syn_batch &batch) {
+static int launch_pulse(kwy_ctx *ctx, syn_batch &batch, unsigned *head) {
   constexpr int N = 1 << LOG2N, H = N / 2, K = H + 1;
   const kwy_c *twH, *twN, *twP;
   const uint4 *poly;
@@ -1297,22 +1337,30 @@ static int launch_pulse(kwy_ctx *ctx, syn_batch &batch) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_HIP(hipFuncSetAttribute((const void *)k_syn_pulse<LOG2N, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // every utterance its slice of a persistent grid (a pulse's slot does not depend on the slice: the waveform
-  // is the same whatever the batch)
-  const int share = batch.n > 1 ? std::max(64, 4096 / batch.n) : 2048;
-  int g = 0;
-  for (int u = 0; u < batch.n; ++u) { batch.start[u] = g; g += std::max(1, std::min(batch.u[u].slots, share)); }
-  batch.start[batch.n] = g;
+  // One grid for the pass, as many workgroups as the chip holds at once (or as there can be pulses, if fewer): they
+  // pull the pass's pulses one at a time from the queue at `head` until it runs dry.  The grid is a matter of speed
+  // alone -- any number of workgroups renders every pulse, each into its own slot: the waveform is the same whatever
+  // the batch and whatever the grid.
+  int64_t &resident = ctx->i_vals[std::string("syn_resident_") + std::to_string(LOG2N)];
+  if (!resident) {
+    int cus = 0, per_cu = 0;
+    KWY_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    KWY_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_syn_pulse<LOG2N, false>, NT, lds));
+    resident = (int64_t)std::max(1, cus) * std::max(1, per_cu);
+  }
+  int64_t most = 0;
+  for (int u = 0; u < batch.n; ++u) most += std::min(batch.u[u].slots, batch.u[u].cap);
+  int g = (int)std::max<int64_t>(1, std::min(most, resident));
+  hipLaunchKernelGGL(k_syn_zero, dim3(1), dim3(KWY_THREADS), 0, ctx->stream, (double *)nullptr, (int64_t)0, head);
   KWY_PROF(ctx, "k_syn_pulse", hipLaunchKernelGGL((k_syn_pulse<LOG2N, false>), dim3(g), dim3(NT), lds, ctx->stream, batch,
-                     kwy_randn(ctx), poly, twH, twP, twN, dcrem, (long long *)ctx->dbg));
+                     kwy_randn(ctx), poly, twH, twP, twN, dcrem, head, (long long *)ctx->dbg));
   g = 0;
   for (int u = 0; u < batch.n; ++u) { batch.start[u] = g; g += batch.u[u].nt; }
   batch.start[batch.n] = g;
   KWY_PROF(ctx, "k_syn_ola", hipLaunchKernelGGL(k_syn_ola, dim3(g), dim3(KWY_THREADS), 0, ctx->stream, batch, N));
   // pulses beyond the slots (none for speech): one workgroup per utterance, serial, same order
-  for (int u = 0; u <= batch.n; ++u) batch.start[u] = u;
   KWY_PROF(ctx, "k_syn_pulse_more", hipLaunchKernelGGL((k_syn_pulse<LOG2N, true>), dim3(batch.n), dim3(NT), lds, ctx->stream,
-                     batch, kwy_randn(ctx), poly, twH, twP, twN, dcrem, (long long *)nullptr));
+                     batch, kwy_randn(ctx), poly, twH, twP, twN, dcrem, (unsigned *)nullptr, (long long *)nullptr));
   KWY_HIP(hipGetLastError());
   return KWY_OK;
 }
@@ -1321,8 +1369,13 @@ static int syn_pulse_cap(int64_t y_length) { return (int)(y_length / 8 + 16); }
 
 static size_t syn_plan_bytes(int64_t y_length);
 static size_t syn_plan_scratch_bytes(int64_t y_length);
+// the response slots of one utterance, and the head word of the pulse queue that a call's passes share
+static size_t syn_slot_bytes(int64_t y_length, int fft_size, int fs) {
+  return kwy_pad(sizeof(double) * (size_t)SYN_SLOTS(y_length, fs) * fft_size);
+}
+static size_t syn_head_bytes() { return kwy_pad(sizeof(unsigned)); }
 static size_t syn_render_scratch_bytes(int64_t y_length, int fft_size, int fs) {
-  return kwy_pad(sizeof(double) * (size_t)SYN_SLOTS(y_length, fs) * fft_size) + kwy_pad(64);
+  return syn_slot_bytes(y_length, fft_size, fs) + syn_head_bytes();
 }
 static size_t syn_scratch_bytes(int64_t y_length, int fft_size, int fs) {
   return syn_plan_bytes(y_length) + syn_plan_scratch_bytes(y_length) + syn_render_scratch_bytes(y_length, fft_size, fs);
@@ -1430,15 +1483,15 @@ static int syn_fill_view(kwy_ctx *ctx, const syn_plan &pl, const double *sp, con
   return KWY_OK;
 }
 
-static int syn_launch(kwy_ctx *ctx, syn_batch &batch, int log2n) {
+static int syn_launch(kwy_ctx *ctx, syn_batch &batch, int log2n, unsigned *head) {
   switch (log2n) {
-    case 9: return launch_pulse<9>(ctx, batch);
-    case 10: return launch_pulse<10>(ctx, batch);
-    case 11: return launch_pulse<11>(ctx, batch);
-    case 12: return launch_pulse<12>(ctx, batch);
+    case 9: return launch_pulse<9>(ctx, batch, head);
+    case 10: return launch_pulse<10>(ctx, batch, head);
+    case 11: return launch_pulse<11>(ctx, batch, head);
+    case 12: return launch_pulse<12>(ctx, batch, head);
     // 8192: features resampled up to 96 kHz (3078 bins -> 4097, kwiiyatta/vocoder/world.py:71-78); rare, runs
     // with the 256-thread layout of the shorter transforms (register spills accepted)
-    default: return launch_pulse<13>(ctx, batch);
+    default: return launch_pulse<13>(ctx, batch, head);
   }
 }
 
@@ -1446,8 +1499,10 @@ static int synth_render(kwy_ctx *ctx, const syn_plan &pl, const double *sp, cons
                         int log2n, double *y) {
   syn_batch batch;
   batch.n = 1;
+  unsigned *head = kwy_arena<unsigned>(ctx, 1);
+  if (!head) { ctx->err = "synthesize: scratch arena too small"; return KWY_ENOMEM; }
   KWY_TRY(syn_fill_view(ctx, pl, sp, ap, p, y, &batch.u[0]));
-  return syn_launch(ctx, batch, log2n);
+  return syn_launch(ctx, batch, log2n, head);
 }
 
 static int synth_core(kwy_ctx *ctx, const double *f0, int64_t T, const double *sp, const double *ap,
@@ -1551,12 +1606,21 @@ extern "C" int kwy_synth_render_dev(kwy_ctx *ctx, const void *plan, int64_t T, c
   return synth_render(ctx, syn_plan_carve(const_cast<void *>(plan), y_length), sp, ap, p, log2n, y);
 }
 
-// The rendering of several utterances (include/kwy.h).  A pass of launches takes SYN_RENDER_GROUP utterances -- four
-// 10 s utterances are ~9 000 pulses: a dozen rounds of the chip's resident workgroups -- and the passes of a call share
-// ONE pool of response slots (the launches of a stream run one after the other: a pass's responses are dead when the
-// next pass writes its own).  Until round 4 a call held the slots of all its utterances at once: 116 MB per 10 s
-// utterance, 3.7 GB for the 32 pairs of the benchmark; now 0.46 GB per context whatever the number of utterances.
-#define SYN_RENDER_GROUP 4
+// The rendering of several utterances (include/kwy.h).  A pass of launches takes SYN_RENDER_GROUP utterances, and the
+// passes of a call share ONE pool of response slots (the launches of a stream run one after the other: a pass's
+// responses are dead when the next pass writes its own) and one head word in front of it.  The pool is 116 MB per
+// 10 s utterance at 48 kHz: 1.86 GB per context at 16 utterances a pass, whatever the number of utterances of the call
+// (0.46 GB at 4, the pass size until the pulse queue; 3.7 GB when a call of 32 held all its slots at once).  A pass
+// ends with the stragglers of its last round of pulses while the rest of the chip idles, and the queue cannot deal
+// pulses across the passes' boundary (k_syn_ola stands between), so fewer and longer passes are what shortens a wave:
+// the three launches of a pass summed over a wave of 16 target tracks take 1.82 ms at 4, 1.67 ms at 8 and 1.57 ms at
+// 16 utterances a pass (profiles/synq_variants_serial.txt; the slices of before: 1.84, 1.79, 1.76) -- although a pass
+// of 16 keeps 0.6 GB of responses alive, more than the 256 MB last-level cache: k_syn_ola's time per wave hardly
+// changes (0.136 -> 0.140 - 0.150 ms).  -DSYN_RENDER_GROUP=n (n <= KWY_BATCH_MAX) rebuilds the smaller passes.
+#ifndef SYN_RENDER_GROUP
+#define SYN_RENDER_GROUP KWY_BATCH_MAX
+#endif
+static_assert(SYN_RENDER_GROUP >= 1 && SYN_RENDER_GROUP <= KWY_BATCH_MAX, "a pass is one job table");
 extern "C" int kwy_synth_render_batch_dev(kwy_ctx *ctx, const kwy_synth_job *jobs, int count, int fft_size,
                                           double frame_period_ms, int fs, double sp_mul) {
   if (!ctx) return KWY_EINVAL;
@@ -1570,11 +1634,14 @@ extern "C" int kwy_synth_render_batch_dev(kwy_ctx *ctx, const kwy_synth_job *job
                       q.y_length, q.y));
     if (!q.plan) { ctx->err = "synth_render_batch: bad argument"; return KWY_EINVAL; }
     if (q.y_length < 2 || q.f0_length < 2) continue;
-    group += syn_render_scratch_bytes(q.y_length, fft_size, fs);
+    group += syn_slot_bytes(q.y_length, fft_size, fs);
     if (++in_group == SYN_RENDER_GROUP) { bytes = std::max(bytes, group); group = 0; in_group = 0; }
   }
   bytes = std::max(bytes, group);
-  KWY_TRY(kwy_arena_begin(ctx, bytes));
+  KWY_TRY(kwy_arena_begin(ctx, syn_head_bytes() + bytes));
+  unsigned *head = kwy_arena<unsigned>(ctx, 1);      // in front of the slot pool; k_syn_zero in front of every pass
+  if (!head) { ctx->err = "synth_render_batch: scratch arena too small"; return KWY_ENOMEM; }
+  const size_t pool = ctx->arena_off;
   syn_batch batch;
   batch.n = 0;
   int log2n = 0;
@@ -1584,18 +1651,20 @@ extern "C" int kwy_synth_render_batch_dev(kwy_ctx *ctx, const kwy_synth_job *job
     syn_params p;
     KWY_TRY(syn_make_params(ctx, q.f0_length, fft_size, frame_period_ms, fs, sp_mul, q.y_length, &p, &log2n));
     if (q.y_length < 2 || q.f0_length < 2) {
-      KWY_HIP(hipMemsetAsync(q.y, 0, sizeof(double) * q.y_length, ctx->stream));
+      hipLaunchKernelGGL(k_syn_zero, dim3((unsigned)((q.y_length + KWY_THREADS - 1) / KWY_THREADS)), dim3(KWY_THREADS), 0,
+                         ctx->stream, q.y, (int64_t)q.y_length, (unsigned *)nullptr);
+      KWY_HIP(hipGetLastError());
       continue;
     }
     KWY_TRY(syn_fill_view(ctx, syn_plan_carve(const_cast<void *>(q.plan), q.y_length), q.spectrogram, q.aperiodicity, p,
                           q.y, &batch.u[batch.n]));
     if (++batch.n == SYN_RENDER_GROUP) {
-      KWY_TRY(syn_launch(ctx, batch, log2n));
+      KWY_TRY(syn_launch(ctx, batch, log2n, head));
       batch.n = 0;
-      ctx->arena_off = 0;               // the next pass takes the same slots
+      ctx->arena_off = pool;            // the next pass takes the same slots
     }
   }
-  if (batch.n > 0) KWY_TRY(syn_launch(ctx, batch, log2n));
+  if (batch.n > 0) KWY_TRY(syn_launch(ctx, batch, log2n, head));
   return KWY_OK;
 }
 
