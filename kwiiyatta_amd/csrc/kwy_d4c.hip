@@ -559,6 +559,12 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   const uint64_t dpos0 = dbase + offs3[3 * frame], dpos1 = dbase + offs3[3 * frame + 1], dpos2 = dbase + offs3[3 * frame + 2];
   // (the window cosine cache lives in A0, where a frame beyond the noise table builds its jump table: no cache then)
   const bool cache = dpos2 + (uint64_t)(2 * kwy_matlab_round(4.0 * p.fs / cf0 / 2.0) + 1) <= rs.n;
+  // Half frames: a window of wl <= N/2 + 1 samples (f0 >= 8 fs / N: 93.75 Hz at 48 kHz) leaves the packed points above
+  // H/2 of all five transforms zero.  One block-uniform flag: where it holds, the fills store the thread's elements
+  // r < E/2 and point H/2 (its value or zero -- B holds the smoothing scratch or the previous transform there), no
+  // zeros, and the first radix-8 pass takes its half-input form (kwy_fft_inplace_sel_w), which reads no more than that
+  // and stores all H points.  Everything behind the first pass is shared; the bins are the dense transform's.
+  const bool zh = 2 * kwy_matlab_round(4.0 * p.fs / cf0 / 2.0) + 1 <= H + 1;
 
   D4C_STAMP(1);
   // ---- static centroid: two temporal centroids at pos -+ 0.25/f0, each Re(X2 conj X1) of the
@@ -583,14 +589,17 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
                               A0, cache ? 1 + which : 0);
       __syncthreads();      // (the window code keeps per-thread values in Bd until here)
       // even samples: z[m] = a[2m] + j b[2m] -- sample i = tid + NT r has the parity of tid
+      // (half frame: samples below H, and sample H = point H/2, thread 0's element E/2)
       if (!(tid & 1)) {
 #pragma unroll
-        for (int r = 0; r < E; ++r) { const int i = tid + NT * r; Bd[i] = av[r]; Bd[i + 1] = av[r] * (i + 1.0); }
+        for (int r = 0; r < E; ++r) {
+          if (r < E / 2 || !zh || (r == E / 2 && tid == 0)) { const int i = tid + NT * r; Bd[i] = av[r]; Bd[i + 1] = av[r] * (i + 1.0); }
+        }
       }
       __syncthreads();
       D4C_STAMP(2 + which * 2);
       D4C_BODY_TW4();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
+      kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP, zh);
       kwy_c Ek[RP], Eh[RP];
       if constexpr (DRAIN) {
         // slot r holds the pair of bin p = kwy_drain_bin(r, tid) instead of p = tid + NT r (the centroid sums go to
@@ -609,13 +618,18 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
         if (tid == 0) { mid[0] = B[H / 2].x; mid[1] = B[H / 2].y; }
       }
       __syncthreads();
+      // (half frame: the odd samples end below H, point H/2 is zero)
       if (tid & 1) {
 #pragma unroll
-        for (int r = 0; r < E; ++r) { const int i = tid + NT * r; Bd[i - 1] = av[r]; Bd[i] = av[r] * (i + 1.0); }
+        for (int r = 0; r < E; ++r) {
+          if (r < E / 2 || !zh) { const int i = tid + NT * r; Bd[i - 1] = av[r]; Bd[i] = av[r] * (i + 1.0); }
+        }
+      } else if (zh && tid == 0) {
+        B[H / 2] = kwy_c{0.0, 0.0};
       }
       __syncthreads();
       D4C_BODY_TW4();
-      kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
+      kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP, zh);
       kwy_c Od[DRAIN ? 4 : 1], Odh[DRAIN ? 4 : 1], twa = {0.0, 0.0}, twc = {0.0, 0.0};
       if constexpr (DRAIN) {
         kwy_c Om;
@@ -663,13 +677,16 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
     D4C_STAMP(6);
     // ---- smoothed power spectrum (the centroid sum waits in registers)
     d4c_frame_window<N, NT>(x, x_length, p, cf0, pos, D4C_HANNING, dpos2, rs, poly, e, jtab, Bd, false, red, av, A0, cache ? 2 : 0);
+    // (half frame: point H/2 is sample H, thread 0's element E/2, beside the zero of sample H + 1)
 #pragma unroll
-    for (int r = 0; r < E; ++r) Bd[tid + NT * r] = av[r];
+    for (int r = 0; r < E; ++r)
+      if (r < E / 2 || !zh) Bd[tid + NT * r] = av[r];
+    if (zh && tid == 0) { Bd[H] = av[E / 2]; Bd[H + 1] = 0.0; }
     __syncthreads();
   }
   D4C_STAMP(7);
   D4C_BODY_TW4();
-  kwy_fft_inplace_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP);
+  kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP, zh);
   D4C_STAMP(8);
   double pv[RK];
   if constexpr (DRAIN) {

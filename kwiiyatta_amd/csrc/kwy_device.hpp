@@ -1244,6 +1244,44 @@ __device__ __forceinline__ void kwy_fft_pass8_first_half_core(kwy_c *z, TW tw) {
   __syncthreads();
 }
 
+// The first pass of a kernel that meets both kinds of input: `half` (block-uniform) picks the loads and the butterfly of
+// kwy_fft_pass8_first_half_core, else those of the dense pass (one butterfly per thread); the factors, their powers and
+// the stores are one piece of code, so a kernel at its register budget carries one set of them.
+template <int LOG2H, int NT, bool INV, class TW>
+__device__ __forceinline__ void kwy_fft_pass8_first_sel_core(kwy_c *z, TW tw, bool half) {
+  constexpr int H = 1 << LOG2H, Q = H / 8;
+  static_assert(Q <= NT && Q >= 8, "one butterfly per thread");
+  const int j = kwy_tid_opaque();
+  kwy_c a[8];
+  if (j < Q) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) a[m] = z[j + m * Q];
+    if (half) {
+      a[4] = {0.0, 0.0};
+      if (j == 0) a[4] = z[H / 2];
+      kwy_dft8_low5<INV>(a);
+    } else {
+#pragma unroll
+      for (int m = 4; m < 8; ++m) a[m] = z[j + m * Q];
+      kwy_dft8<INV>(a);
+    }
+    kwy_c w1 = tw(j);
+    if (INV) w1.y = -w1.y;
+    const kwy_c w2 = cmulf(w1, w1), w4 = cmulf(w2, w2);
+    const kwy_c w3 = cmulf(w1, w2), w5 = cmulf(w4, w1), w6 = cmulf(w4, w2);
+    const kwy_c w7 = cmulf(w4, w3);
+    a[1] = cmulf(w1, a[1]); a[2] = cmulf(w2, a[2]); a[3] = cmulf(w3, a[3]);
+    a[4] = cmulf(w4, a[4]); a[5] = cmulf(w5, a[5]); a[6] = cmulf(w6, a[6]);
+    a[7] = cmulf(w7, a[7]);
+  }
+  __syncthreads();
+  if (j < Q) {
+#pragma unroll
+    for (int m = 0; m < 8; ++m) z[8 * j + (m ^ (j & 7))] = a[m];
+  }
+  __syncthreads();
+}
+
 template <int LOG2H, int TAIL, int NT, bool INV>
 __device__ __forceinline__ void kwy_fft_tail(kwy_c *z);
 
@@ -1328,6 +1366,22 @@ __device__ inline void kwy_fft_inplace_w(kwy_c *z, const kwy_c (&w)[4], const kw
   static_assert(LOG2H >= 8 && LOG2H <= 12, "unsupported in-place FFT length");
   kwy_fft_pass8_core<LOG2H, 0, NT, INV>(z, kwy_tw_reg{w[0]});
   kwy_fft_inplace_rest_w<LOG2H, NT, INV, TAIL>(z, w, pw);
+}
+// The same transform for a kernel whose input may be zero from z[H/2 + 1] on: where `half` (block-uniform) says so, the
+// caller has filled z[0 .. H/2] -- point H/2 itself too, with its value or zero, whatever the buffer held before -- and
+// nothing above is read; the first pass stores all H points, and the bins are those of kwy_fft_inplace_w on the
+// zero-padded input (a zero may come out with the other sign).  Only the first pass's loads and butterfly branch;
+// half = false is kwy_fft_inplace_w.
+template <int LOG2H, int NT, bool INV, bool TAIL = true>
+__device__ inline void kwy_fft_inplace_sel_w(kwy_c *z, const kwy_c (&w)[4], const kwy_c *__restrict__ pw, bool half) {
+  static_assert(LOG2H >= 9 && LOG2H <= 12, "unsupported in-place FFT length");
+  kwy_fft_pass8_first_sel_core<LOG2H, NT, INV>(z, kwy_tw_reg{w[0]}, half);
+  kwy_fft_inplace_rest_w<LOG2H, NT, INV, TAIL>(z, w, pw);
+}
+// ... and where the zero half is known at compile time
+template <int LOG2H, int NT, bool INV, bool TAIL = true>
+__device__ inline void kwy_fft_inplace_half_w(kwy_c *z, const kwy_c (&w)[4], const kwy_c *__restrict__ pw) {
+  kwy_fft_inplace_sel_w<LOG2H, NT, INV, TAIL>(z, w, pw, true);
 }
 
 // exp(-2 pi i (t + r*NT) / N) from base = exp(-2 pi i t / N): base times a 16th root of unity,

@@ -526,3 +526,79 @@ extern "C" int kwy_debug_syn_first_passes_dev(void *stream, const double *x, int
   (void)hipFree(tw);
   return rc;
 }
+
+// ---- diagnostic: the transform on thread-held factors, dense and with the half-input first pass -----------------------
+// (one NT-thread workgroup per row of H complex, the shapes of k_d4c_body: H = 1024 and 2048 with 256 threads, 4096 with
+// 512.  The half path copies points 0 .. H/2 of the row and puts `stale` -- whatever the caller likes, NaNs included --
+// where the dense path has the row's upper points, which the half transform must not read.  TAIL = false stops both
+// paths in front of the closing radix-4 / radix-2 pass.)
+template <int LOG2H, int NT, bool INV, bool TAIL>
+__global__ __launch_bounds__(NT) void k_fft_half_w_selftest(const kwy_c *__restrict__ x, const kwy_c *__restrict__ stale,
+                                                            const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP,
+                                                            kwy_c *__restrict__ out_dense, kwy_c *__restrict__ out_half) {
+  constexpr int H = 1 << LOG2H;
+  extern __shared__ double smem[];
+  kwy_c *B = (kwy_c *)smem;          // H complex
+  const int tid = threadIdx.x;
+  const kwy_c *row = x + (size_t)blockIdx.x * H, *old = stale + (size_t)blockIdx.x * H;
+  kwy_c tw4[4];
+  kwy_fft_thread_twiddles<LOG2H, NT>(twH, tw4);
+#pragma nounroll
+  for (int path = 0; path < 2; ++path) {
+    kwy_c *o = (path == 0 ? out_dense : out_half) + (size_t)blockIdx.x * H;
+    for (int i = tid; i < H; i += NT) B[i] = (path == 0 || i <= H / 2) ? row[i] : old[i];
+    __syncthreads();
+    if (path == 0) kwy_fft_inplace_w<LOG2H, NT, INV, TAIL>(B, tw4, twP);
+    else kwy_fft_inplace_half_w<LOG2H, NT, INV, TAIL>(B, tw4, twP);
+    for (int i = tid; i < H; i += NT) o[i] = B[i];
+    __syncthreads();
+  }
+}
+
+template <int LOG2H, int NT, bool INV, bool TAIL>
+static int fft_half_w_launch(hipStream_t stream, const kwy_c *x, const kwy_c *stale, int problems, const kwy_c *twH,
+                             const kwy_c *twP, kwy_c *out_dense, kwy_c *out_half) {
+  const size_t lds = sizeof(kwy_c) * (1 << LOG2H);
+  auto kern = k_fft_half_w_selftest<LOG2H, NT, INV, TAIL>;
+  if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+  hipLaunchKernelGGL(kern, dim3(problems), dim3(NT), lds, stream, x, stale, twH, twP, out_dense, out_half);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+template <int LOG2H, int NT>
+static int fft_half_w_pick(hipStream_t s, bool inv, bool tail, const kwy_c *x, const kwy_c *stale, int problems,
+                           const kwy_c *twH, const kwy_c *twP, kwy_c *od, kwy_c *oh) {
+  if (inv) return tail ? fft_half_w_launch<LOG2H, NT, true, true>(s, x, stale, problems, twH, twP, od, oh)
+                       : fft_half_w_launch<LOG2H, NT, true, false>(s, x, stale, problems, twH, twP, od, oh);
+  return tail ? fft_half_w_launch<LOG2H, NT, false, true>(s, x, stale, problems, twH, twP, od, oh)
+              : fft_half_w_launch<LOG2H, NT, false, false>(s, x, stale, problems, twH, twP, od, oh);
+}
+
+extern "C" int kwy_debug_fft_half_w_dev(void *stream, const double *x, const double *stale, int problems, int log2h,
+                                        int inverse, int tail, double *out_dense, double *out_half) {
+  if (!x || !stale || !out_dense || !out_half || problems <= 0) return -1;
+  if (log2h < 10 || log2h > 12) return -1;
+  const int H = 1 << log2h, entries = H / 512;
+  std::vector<kwy_c> h(H / 8);
+  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * M_PI * (double)k / (double)H; h[k] = {cos(a), sin(a)}; }
+  kwy_c *tw = nullptr;                 // exp(-2 pi i k / H), k < H/8, and the powers table behind it
+  if (hipMalloc((void **)&tw, sizeof(kwy_c) * (H / 8 + KWY_TWP_ENTRY * entries)) != hipSuccess) return -2;
+  int rc = 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * (H / 8), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  if (rc == 0) {
+    kwy_c *tp = tw + H / 8;
+    // (the fill kernel reads tw[64 u], u < H/512: inside the H/8 factors)
+    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, tp, entries);
+    if (hipGetLastError() != hipSuccess) rc = -2;
+    const kwy_c *cx = (const kwy_c *)x, *cs = (const kwy_c *)stale;
+    kwy_c *od = (kwy_c *)out_dense, *oh = (kwy_c *)out_half;
+    if (rc == 0) {
+      if (log2h == 10) rc = fft_half_w_pick<10, 256>(s, inverse != 0, tail != 0, cx, cs, problems, tw, tp, od, oh);
+      else if (log2h == 11) rc = fft_half_w_pick<11, 256>(s, inverse != 0, tail != 0, cx, cs, problems, tw, tp, od, oh);
+      else rc = fft_half_w_pick<12, 512>(s, inverse != 0, tail != 0, cx, cs, problems, tw, tp, od, oh);
+    }
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
+  (void)hipFree(tw);
+  return rc;
+}
