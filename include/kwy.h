@@ -204,14 +204,20 @@ int kwy_synth_plan_batch_dev(kwy_ctx *ctx, const kwy_synth_plan_job *jobs, int c
  * the workgroups from one queue; the passes of a call share one pool of response slots, 116 MB per 10 s utterance at
  * 48 kHz), as kwy_cheaptrick_batch_dev / kwy_d4c_batch_dev analyse them.  What Synthesizer.synthesize does file
  * after file (kwiiyatta/vocoder/world.py:63-80, resynthesize_voice.py:46-79).  Every job's waveform equals
- * kwy_synth_render_dev's bit for bit. */
+ * kwy_synth_render_dev's bit for bit.
+ * ap_rows (optional): the aperiodicity through a row index, as an alignment leaves it.  `aperiodicity` is then a
+ * matrix of ap_src_rows rows and frame t reads its row clamp(ap_rows[t], 0, ap_src_rows - 1) -- kwy_gather_rows_dev's
+ * clamp, so the waveform equals, bit for bit, the one rendered from the rows gathered beforehand, without the copy.
+ * NULL: row t is row t (ap_src_rows is ignored). */
 typedef struct kwy_synth_job {
   const void *plan;             /* kwy_synth_plan_dev's output for this utterance */
   const double *spectrogram;    /* f0_length x (fft_size/2+1) */
-  const double *aperiodicity;   /* f0_length x (fft_size/2+1) */
+  const double *aperiodicity;   /* f0_length (with ap_rows: ap_src_rows) x (fft_size/2+1) */
   int64_t f0_length;
   int64_t y_length;
   double *y;                    /* y_length samples */
+  const int32_t *ap_rows;       /* f0_length row numbers into `aperiodicity`, or NULL */
+  int64_t ap_src_rows;          /* rows of `aperiodicity` when ap_rows is set (> 0) */
 } kwy_synth_job;
 int kwy_synth_render_batch_dev(kwy_ctx *ctx, const kwy_synth_job *jobs, int count, int fft_size,
                                double frame_period_ms, int fs, double sp_mul);

@@ -274,16 +274,21 @@ def utterance_array(items):
 class SynthJob(ctypes.Structure):
     """kwy_synth_job (include/kwy.h): one utterance of a batched rendering call"""
     _fields_ = [('plan', c_vp), ('spectrogram', c_vp), ('aperiodicity', c_vp), ('f0_length', c_i64),
-                ('y_length', c_i64), ('y', c_vp)]
+                ('y_length', c_i64), ('y', c_vp), ('ap_rows', c_vp), ('ap_src_rows', c_i64)]
 
 
 def synth_job_array(items):
     """items: (plan, sp, ap, y) device tensors per utterance (sp, ap: T x K; y: the waveform) -> a ctypes array of
-    kwy_synth_job"""
+    kwy_synth_job.  (plan, sp, ap, y, ap_rows): the aperiodicity through a row index -- ap is the matrix the int32
+    tensor ap_rows (>= T entries) points into, all of its rows; None is the four-item form."""
     arr = (SynthJob * len(items))()
-    for q, (plan, sp, ap, y) in zip(arr, items):
+    for q, (plan, sp, ap, y, *rows) in zip(arr, items):
         q.plan, q.spectrogram, q.aperiodicity = plan.data_ptr(), sp.data_ptr(), ap.data_ptr()
         q.f0_length, q.y_length, q.y = sp.shape[0], y.numel(), y.data_ptr()
+        if rows and rows[0] is not None:
+            if rows[0].dtype.is_floating_point or rows[0].element_size() != 4 or rows[0].numel() < sp.shape[0]:
+                raise ValueError('synth_job_array: ap_rows must be int32, one entry per frame')
+            q.ap_rows, q.ap_src_rows = rows[0].data_ptr(), ap.shape[0]
     return arr
 
 

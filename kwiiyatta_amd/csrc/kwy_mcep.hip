@@ -167,7 +167,14 @@ typedef double mc_v4f64 __attribute__((ext_vector_type(4)));
 // coefficients, B = G2, order + 1 padded to a multiple of 4 in the k direction), exp applied to the accumulators.
 // Used for every length, power of two or not: at K = 1025 the product is 113 MFLOP and G2 (205 KB) stays in L2;
 // 15 us for 2201 frames against 35 us of the LDS-FFT form it replaced in round 2.  Lane map: A[row l&15][k l>>4], B[k l>>4][col l&15], D[row (l>>4)+4r][col l&15].
+// A wavefront holds MC2_TILES neighbouring products of its 16 frames at once -- as many independent chains of operand
+// loads, MFMAs and exp, with a[] loaded once for all -- and stores them a row at a time through LDS.  With one product
+// in flight and the accumulators stored as they lie the kernel wrote 1.6 TB/s (0.175 ms per 35 216 frames at K = 1025);
+// four products stored row by row from the registers: 0.140; through LDS: 0.118 (profiles/apx_variants_serial.txt).
+// Every value is the same exp of the same sum in the same order, whoever computes it: tests/test_mc2sp_bits_gpu.py.
 #define MC2_KSTEPS ((MC_MAX_ORDER + 4) / 4)
+#define MC2_TILES 4                      // neighbouring 16-bin products a wavefront has in flight: 64 bins of 16 frames
+#define MC2_STAGE_STRIDE (64 + 16)       // doubles per staged row: rows ak, ak + 1 land on different halves of the banks
 __global__ __launch_bounds__(KWY_THREADS) void k_mc2sp_mfma(const double *__restrict__ mc, int64_t T, int order,
                                                            int K, const double *__restrict__ G2,
                                                            double *__restrict__ sp) {
@@ -181,23 +188,45 @@ __global__ __launch_bounds__(KWY_THREADS) void k_mc2sp_mfma(const double *__rest
     const int j = 4 * ks + ak;
     a[ks] = (ks < ksteps && j <= order && t0 + ar < T) ? mc[(t0 + ar) * (order + 1) + j] : 0.0;
   }
-  const int ntile = (K + 15) / 16;
-  for (int bt = blockIdx.y * KWY_WAVES + wv; bt < ntile; bt += gridDim.y * KWY_WAVES) {
-    const int b0 = bt * 16;
-    mc_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+  const int ntile = (K + 15) / 16, ngroup = (ntile + MC2_TILES - 1) / MC2_TILES;
+  __shared__ double stage[KWY_WAVES][16][MC2_STAGE_STRIDE];
+  for (int g = blockIdx.y * KWY_WAVES + wv; g < ngroup; g += gridDim.y * KWY_WAVES) {
+    const int g0 = g * (16 * MC2_TILES);
+    mc_v4f64 acc[MC2_TILES];
+#pragma unroll
+    for (int q = 0; q < MC2_TILES; ++q) acc[q] = mc_v4f64{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int ks = 0; ks < MC2_KSTEPS; ++ks) {
       if (ks < ksteps) {
         const int j = 4 * ks + ak;
-        const double b = (j <= order && b0 + ar < K) ? G2[(size_t)j * K + b0 + ar] : 0.0;
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], b, acc, 0, 0, 0);
+        double b[MC2_TILES];
+#pragma unroll
+        for (int q = 0; q < MC2_TILES; ++q)
+          b[q] = (j <= order && g0 + 16 * q + ar < K) ? G2[(size_t)j * K + g0 + 16 * q + ar] : 0.0;
+#pragma unroll
+        for (int q = 0; q < MC2_TILES; ++q) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], b[q], acc[q], 0, 0, 0);
       }
     }
+    // D[row ak + 4 r][col ar] of the four products -> the wavefront's own 16 x 64 block of LDS -> a row per store:
+    // 512 contiguous bytes an instruction (in the accumulators' own layout a store is four 128-byte pieces of four
+    // rows, none line-aligned at a row stride of 8 K bytes).  The block is the wavefront's alone: no workgroup barrier.
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t t = t0 + ak + 4 * r;
-      if (t < T && b0 + ar < K) sp[t * K + b0 + ar] = exp(acc[r]);
-    }
+    for (int q = 0; q < MC2_TILES; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) stage[wv][ak + 4 * r][16 * q + ar] = exp(acc[q][r]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    static_assert(16 * MC2_TILES == 64, "a lane per bin of the group");
+    double v[16];
+#pragma unroll
+    for (int row = 0; row < 16; ++row) v[row] = stage[wv][row][lane];
+#pragma unroll
+    for (int row = 0; row < 16; ++row)
+      if (t0 + row < T && g0 + lane < K) sp[(t0 + row) * K + g0 + lane] = v[row];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
 }
 

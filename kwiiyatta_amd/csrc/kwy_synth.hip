@@ -881,6 +881,8 @@ __device__ __forceinline__ double syn_safe_ap(double x) {
 // a launch renders the pulses of up to KWY_BATCH_MAX utterances, dealt to the workgroups from one queue.
 struct syn_view {
   const double *sp, *ap;
+  const int32_t *ap_rows;   // the aperiodicity through a row index (kwy_synth_job), or NULL: row t is row t
+  int ap_last;              // ... whose entries are clamped to [0, ap_last], as k_gather_rows clamps them
   syn_params p;
   const int32_t *pidx;
   const double *pshift;
@@ -986,7 +988,15 @@ __global__ __launch_bounds__(syn_pulse_nt<LOG2N>::value, LOG2N <= 11 ? 3 : (LOG2
     if (ce > p.T - 1) ce = (int)p.T - 1;
     const double interpolation = current_time / p.frame_period - fl;
     const double *s0 = sp + (int64_t)fl * K, *s1 = sp + (int64_t)ce * K;
-    const double *a0 = ap + (int64_t)fl * K, *a1 = ap + (int64_t)ce * K;
+    // (through the job's row index, if it has one: two scalar loads per pulse, read from the view where they are
+    // needed -- nothing more is held across the transforms)
+    int fa = fl, ca = ce;
+    if (const int32_t *__restrict__ rows = batch.u[utt].ap_rows) {
+      const int last = batch.u[utt].ap_last;
+      fa = min(max(rows[__builtin_amdgcn_readfirstlane(fl)], 0), last);
+      ca = min(max(rows[__builtin_amdgcn_readfirstlane(ce)], 0), last);
+    }
+    const double *a0 = ap + (int64_t)fa * K, *a1 = ap + (int64_t)ca * K;
     double rv0 = syn_safe_ap(a0[0]);
     if (fl != ce) rv0 = (1.0 - interpolation) * rv0 + interpolation * syn_safe_ap(a1[0]);
     const bool has_periodic = current_vuv > 0.5 && !(rv0 * rv0 > 0.999);
@@ -1469,10 +1479,11 @@ static int synth_plan(kwy_ctx *ctx, const double *f0, const syn_params &p, const
   return synth_plan_launch(ctx, b);
 }
 
-static int syn_fill_view(kwy_ctx *ctx, const syn_plan &pl, const double *sp, const double *ap, const syn_params &p,
-                         double *y, syn_view *v) {
+static int syn_fill_view(kwy_ctx *ctx, const syn_plan &pl, const double *sp, const double *ap, const int32_t *ap_rows,
+                         int64_t ap_src_rows, const syn_params &p, double *y, syn_view *v) {
   const int64_t y_length = p.y_length;
   v->sp = sp; v->ap = ap; v->p = p;
+  v->ap_rows = ap_rows; v->ap_last = ap_rows ? (int)(ap_src_rows - 1) : 0;
   v->pidx = pl.pidx; v->pshift = pl.pshift; v->vuv8 = pl.vuv8; v->npulse = pl.npulse; v->tile_off = pl.tile_cnt;
   v->cap = syn_pulse_cap(y_length);
   v->slots = SYN_SLOTS(y_length, p.fs);
@@ -1501,7 +1512,7 @@ static int synth_render(kwy_ctx *ctx, const syn_plan &pl, const double *sp, cons
   batch.n = 1;
   unsigned *head = kwy_arena<unsigned>(ctx, 1);
   if (!head) { ctx->err = "synthesize: scratch arena too small"; return KWY_ENOMEM; }
-  KWY_TRY(syn_fill_view(ctx, pl, sp, ap, p, y, &batch.u[0]));
+  KWY_TRY(syn_fill_view(ctx, pl, sp, ap, nullptr, 0, p, y, &batch.u[0]));
   return syn_launch(ctx, batch, log2n, head);
 }
 
@@ -1522,11 +1533,13 @@ static int synth_core(kwy_ctx *ctx, const double *f0, int64_t T, const double *s
   return synth_render(ctx, pl, sp, ap, p, log2n, y);
 }
 
+// ap_rows / ap_src_rows: kwy_synth_job's row index of the aperiodicity (NULL: none, the row count is not looked at)
 static int syn_check(kwy_ctx *ctx, const void *f0, int64_t T, const void *sp, const void *ap,
-                     int fft_size, double frame_period_ms, int fs, int64_t y_length, const void *y) {
+                     int fft_size, double frame_period_ms, int fs, int64_t y_length, const void *y,
+                     const void *ap_rows = nullptr, int64_t ap_src_rows = 0) {
   if (!ctx) return KWY_EINVAL;
   if (!f0 || !sp || !ap || !y || T <= 0 || fs <= 0 || fft_size <= 0 || !(frame_period_ms > 0) ||
-      y_length < 0 || y_length > 0x7fffffff) {
+      y_length < 0 || y_length > 0x7fffffff || (ap_rows && (ap_src_rows <= 0 || ap_src_rows > 0x7fffffff))) {
     ctx->err = "synthesize: bad argument";
     return KWY_EINVAL;
   }
@@ -1631,7 +1644,7 @@ extern "C" int kwy_synth_render_batch_dev(kwy_ctx *ctx, const kwy_synth_job *job
   for (int j = 0; j < count; ++j) {
     const kwy_synth_job &q = jobs[j];
     KWY_TRY(syn_check(ctx, q.spectrogram, q.f0_length, q.spectrogram, q.aperiodicity, fft_size, frame_period_ms, fs,
-                      q.y_length, q.y));
+                      q.y_length, q.y, q.ap_rows, q.ap_src_rows));
     if (!q.plan) { ctx->err = "synth_render_batch: bad argument"; return KWY_EINVAL; }
     if (q.y_length < 2 || q.f0_length < 2) continue;
     group += syn_slot_bytes(q.y_length, fft_size, fs);
@@ -1656,8 +1669,8 @@ extern "C" int kwy_synth_render_batch_dev(kwy_ctx *ctx, const kwy_synth_job *job
       KWY_HIP(hipGetLastError());
       continue;
     }
-    KWY_TRY(syn_fill_view(ctx, syn_plan_carve(const_cast<void *>(q.plan), q.y_length), q.spectrogram, q.aperiodicity, p,
-                          q.y, &batch.u[batch.n]));
+    KWY_TRY(syn_fill_view(ctx, syn_plan_carve(const_cast<void *>(q.plan), q.y_length), q.spectrogram, q.aperiodicity,
+                          q.ap_rows, q.ap_src_rows, p, q.y, &batch.u[batch.n]));
     if (++batch.n == SYN_RENDER_GROUP) {
       KWY_TRY(syn_launch(ctx, batch, log2n, head));
       batch.n = 0;

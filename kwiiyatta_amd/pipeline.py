@@ -394,7 +394,6 @@ class _Wave:
             self.Tt = Tt
             al = Ragged(Tt)
             arows = al.total
-            self.ap_al = torch.empty((arows, K), **f64)
             self.mc_al = torch.empty((arows, order + 1), **f64)
             self.mc_conv = torch.empty((arows, order + 1), **f64)
             self.sp_conv = torch.empty((arows, K), **f64)
@@ -416,7 +415,7 @@ class _Wave:
             self.plan = [torch.empty(lib.kwy_synth_plan_bytes(y), dtype=torch.uint8, device=dev) for y in self.ylen]
             # the per-pair words (distance, path length, gathered rows) as one-element views, the aligned blocks per pair
             dist, path_len, n_idx = (Ragged([1] * self.n).views(a) for a in (self.dist, self.path_len, self.n_idx))
-            ap_al, mc_al, mc_conv, sp_conv = (al.views(b) for b in (self.ap_al, self.mc_al, self.mc_conv, self.sp_conv))
+            mc_al, mc_conv, sp_conv = (al.views(b) for b in (self.mc_al, self.mc_conv, self.sp_conv))
             J = _lib.job_array
             both = range(ns)
             env_out = pl.views(self.mc_pad, P, P) if fused else self.sp
@@ -427,13 +426,13 @@ class _Wave:
                                           dist[k], self.path[k], path_len[k]) for k in range(self.n)])
             self.j_proj = J(_lib.ProjectJob, [(self.path[k], path_len[k], self.idx[k], self.Tp[2 * k + 1], n_idx[k])
                                               for k in range(self.n)])
-            self.j_gap = J(_lib.GatherJob, [(self.ap_p[2 * k], self.Tp[2 * k], self.idx[k], Tt[k], ap_al[k])
-                                            for k in range(self.n)])
             self.j_gmc = J(_lib.GatherJob, [(self.mc_p[2 * k], self.Tp[2 * k], self.idx[k], Tt[k], mc_al[k])
                                             for k in range(self.n)])
             self.j_conv = J(_lib.ConvertJob, [(mc_al[k], Tt[k], mc_conv[k]) for k in range(self.n)])
             self.j_plan = J(_lib.SynthPlanJob, [(self.f0[2 * k + 1], Tt[k], self.ylen[k], self.plan[k]) for k in range(self.n)])
-            self.j_render = _lib.synth_job_array([(self.plan[k], sp_conv[k], ap_al[k], self.wave[k]) for k in range(self.n)])
+            # the aperiodicity is not gathered: the renderer reads the source's padded rows through the alignment index
+            self.j_render = _lib.synth_job_array([(self.plan[k], sp_conv[k], self.ap_p[2 * k], self.wave[k], self.idx[k])
+                                                  for k in range(self.n)])
         self.rows, self.arows = rows, arows
         self.frames = sum(self.T[0::2])
 
@@ -447,7 +446,7 @@ class PairBatchPipeline(_Graphed):
     N times the frames.  A wave (<= 16 pairs: the batch limit of one launch) uses two streams:
 
         main   CheapTrick of both sides -> [pads] -> sp2mc -> DTW features -> FastDTW -> projection
-               -> [aperiodicity] -> gathers -> conversion -> mc2sp -> [plan] -> rendering
+               -> gather -> conversion -> mc2sp -> [aperiodicity, plan] -> rendering
         side   D4C of both sides (waveform, f0 and frame times only) -> pulse placement (target f0 only)
 
     and `waves` waves run side by side (default 2: four streams, the number of hardware queues the HIP runtime creates
@@ -575,8 +574,6 @@ class PairBatchPipeline(_Graphed):
                     pads = torch.cuda.Event()
                     pads.record(wv.side)
                 _lib.check(wv.side_ctx, lib.kwy_d4c_batch_dev(hs, wv.j_ap, 2 * n, fs, 0.85, fft))
-                ap_done = torch.cuda.Event()
-                ap_done.record(wv.side)
                 _lib.check(wv.side_ctx, lib.kwy_synth_plan_batch_dev(hs, wv.j_plan, n, fft, self.frame_period, fs))
             with torch.cuda.stream(wv.stream):
                 chk = lambda rc, c=wv.ctx: _lib.check(c, rc)  # noqa: E731
@@ -595,12 +592,10 @@ class PairBatchPipeline(_Graphed):
                                                      VUV_WEIGHT))
                 chk(lib.kwy_fastdtw_batch_dev(h, wv.j_dtw, n, order + 2, self.radius))
                 chk(lib.kwy_align_project_batch_dev(h, wv.j_proj, n, PAD_LEN))
-                wv.stream.wait_event(ap_done)
-                chk(lib.kwy_gather_rows_batch_dev(h, wv.j_gap, n, K))
                 chk(lib.kwy_gather_rows_batch_dev(h, wv.j_gmc, n, order + 1))
                 chk(lib.kwy_convert_mcep_batch_dev(h, wv.j_conv, n, order, self.gmm.M, _p(self.gmm_model)))
                 chk(lib.kwy_mc2sp_dev(h, _p(wv.mc_conv), wv.arows, order, self.alpha, fft, _p(wv.sp_conv)))
-                wv.stream.wait_stream(wv.side)                      # join: the plans are there
+                wv.stream.wait_stream(wv.side)                      # join: the aperiodicity and the plans are there
                 chk(lib.kwy_synth_render_batch_dev(h, wv.j_render, n, fft, self.frame_period, fs, float(fs)))
                 if self.pcm:
                     chk(lib.kwy_finish_pcm16_batch_dev(h, wv.j_fin, n, fs, 1, PIECE_CEILING, 1, PIECE_CEILING))
