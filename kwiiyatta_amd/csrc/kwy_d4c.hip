@@ -488,6 +488,28 @@ struct d4c_nt { static constexpr int value = LOG2N >= 13 ? 512 : 256; };
 // re-read.  The other sizes have another thread / point ratio, a radix-2 tail or none, and keep the stored form.
 template <int LOG2N>
 struct d4c_drain { static constexpr bool value = LOG2N == 12; };
+// ... and k_d4c_body runs them in the wave-local form (kwy_device.hpp, kwy_fftwl_*): the same butterflies, two workgroup
+// barriers per transform in front of the drain instead of six.  k_d4c_bands keeps the Stockham chain: its exchange of
+// powers stores to Z[2 NT - tid] and Z[4 NT - tid] right behind the drain's loads, which in the wave-local layout hold
+// other wavefronts' operands -- with the barrier that takes, the kernel measured no faster.
+template <int LOG2N>
+struct d4c_body_wl { static constexpr bool value = LOG2N == 12; };
+// the transform up to the drain and the drain, in either form (t: the opaque thread index of the factor fetch)
+template <int LOG2H, int NT, bool WL>
+__device__ __forceinline__ void d4c_thread_twiddles(const kwy_c *__restrict__ twH, int t, kwy_c (&w)[4]) {
+  if constexpr (WL) kwy_fftwl_thread_twiddles(twH, t, w);
+  else kwy_fft_thread_twiddles<LOG2H, NT>(twH + (t - (int)threadIdx.x), w);
+}
+template <int LOG2H, int NT, bool WL>
+__device__ __forceinline__ void d4c_fft_sel(kwy_c *z, const kwy_c (&w)[4], const kwy_c *__restrict__ pw, bool half) {
+  if constexpr (WL) { kwy_fftwl_first_sel<false>(z, kwy_tw_reg{w[0]}, half); kwy_fftwl_rest<false>(z, kwy_tw_reg{w[1]}, pw); }
+  else kwy_fft_inplace_sel_w<LOG2H, NT, false, false>(z, w, pw, half);
+}
+template <int LOG2H, int NT, bool WL>
+__device__ __forceinline__ void d4c_fft_drain(const kwy_c *z, kwy_c (&lo)[4], kwy_c (&hi)[4], kwy_c &mid) {
+  if constexpr (WL) kwy_fftwl_tail4_drain<false>(z, lo, hi, mid);
+  else kwy_fft_tail4_drain<LOG2H, NT, false>(z, lo, hi, mid);
+}
 // the slot twiddles of the drained form: twN[tid] and twN[(NT - tid) mod NT], fetched where they are used
 #define D4C_DRAIN_TWC(twN, NT, tid) (twN)[((NT) - (tid)) & ((NT) - 1)]
 template <int LOG2N>
@@ -513,6 +535,8 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   constexpr int HEX = 16 * NT / N;           // 16th-root index step of the bin twiddles
   static_assert(HEX >= 1, "workgroup narrower than N/16");
   constexpr bool DRAIN = d4c_drain<LOG2N>::value;
+  constexpr bool WL = d4c_body_wl<LOG2N>::value;
+  static_assert(!WL || DRAIN, "the wave-local transform ends in the drained pass");
 #define D4C_STAMP(n) do { if (dbg && threadIdx.x == 0 && blockIdx.x == (unsigned)dbg[63]) dbg[n] = clock64(); } while (0)
   extern __shared__ double smem[];
   double *tot = smem;                        // NT
@@ -551,7 +575,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   // pass factors do not stay in registers across those phases: every transform fetches them again (three 16-byte
   // loads from L1 / L2 through the opaque thread index, as k_d4c_bands does per band).
 #define D4C_BODY_TW4() do { if constexpr (DRAIN) { const int ot = kwy_tid_opaque(); \
-    kwy_fft_thread_twiddles<LOG2N - 1, NT>(twH + (ot - (int)threadIdx.x), tw4); } } while (0)
+    d4c_thread_twiddles<LOG2N - 1, NT, WL>(twH, ot, tw4); } } while (0)
   // exp(-2 pi i k / N) of "my" spectrum bins k = tid + NT*r is this times a 16th root of unity
   const kwy_c twb = twN[tid];
   // stream positions of the frame's three windows: the body's noise continues where the LoveTrain pass stopped
@@ -599,14 +623,15 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
       __syncthreads();
       D4C_STAMP(2 + which * 2);
       D4C_BODY_TW4();
-      kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP, zh);
+      if constexpr (DRAIN) d4c_fft_sel<LOG2N - 1, NT, WL>(B, tw4, twP, zh);
+      else kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, true>(B, tw4, twP, zh);
       kwy_c Ek[RP], Eh[RP];
       if constexpr (DRAIN) {
         // slot r holds the pair of bin p = kwy_drain_bin(r, tid) instead of p = tid + NT r (the centroid sums go to
         // LDS by bin index further down: which thread forms a bin does not matter)
         static_assert(RP == 4, "four pairs per thread");
         kwy_c Em;
-        kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, Ek, Eh, Em);
+        d4c_fft_drain<LOG2N - 1, NT, WL>(B, Ek, Eh, Em);
         if (tid == 0) { mid[0] = Em.x; mid[1] = Em.y; }
       } else {
 #pragma unroll
@@ -629,11 +654,12 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
       }
       __syncthreads();
       D4C_BODY_TW4();
-      kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP, zh);
+      if constexpr (DRAIN) d4c_fft_sel<LOG2N - 1, NT, WL>(B, tw4, twP, zh);
+      else kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, true>(B, tw4, twP, zh);
       kwy_c Od[DRAIN ? 4 : 1], Odh[DRAIN ? 4 : 1], twa = {0.0, 0.0}, twc = {0.0, 0.0};
       if constexpr (DRAIN) {
         kwy_c Om;
-        kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, Od, Odh, Om);
+        d4c_fft_drain<LOG2N - 1, NT, WL>(B, Od, Odh, Om);
         if (tid == 0) { mid[3] = Om.x; mid[4] = Om.y; }     // (parked like E[H/2]: four registers less across the products)
         // (both twiddle bases are fetched here, through the opaque thread index, instead of living in registers
         // from the head of the kernel: at this register budget they would be spilled)
@@ -686,7 +712,8 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
   }
   D4C_STAMP(7);
   D4C_BODY_TW4();
-  kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, !DRAIN>(B, tw4, twP, zh);
+  if constexpr (DRAIN) d4c_fft_sel<LOG2N - 1, NT, WL>(B, tw4, twP, zh);
+  else kwy_fft_inplace_sel_w<LOG2N - 1, NT, false, true>(B, tw4, twP, zh);
   D4C_STAMP(8);
   double pv[RK];
   if constexpr (DRAIN) {
@@ -694,7 +721,7 @@ __global__ __launch_bounds__(d4c_nt<LOG2N>::value, LOG2N >= 13 ? 1 : 3) void k_d
     static_assert(RK == 9, "four pairs per thread and the self-paired bin");
     const int tid = kwy_tid_opaque();
     kwy_c lo[4], hi[4], md;
-    kwy_fft_tail4_drain<LOG2N - 1, NT, false>(B, lo, hi, md);
+    d4c_fft_drain<LOG2N - 1, NT, WL>(B, lo, hi, md);
     const kwy_c twa = twN[tid], twc = D4C_DRAIN_TWC(twN, NT, tid);
 #pragma unroll
     for (int s = 0; s < 4; ++s) {

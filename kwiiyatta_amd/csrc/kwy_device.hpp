@@ -1674,15 +1674,11 @@ __device__ __forceinline__ void kwy_rfft_pair_power2_dc(kwy_c Z0, double *pk, do
 // NT], HEX (k div NT)) that the k = tid + NT q mapping forms, so that the bits of every bin stay what they were.
 // Reads z only; the caller has a barrier in front (the last radix-8 pass ends with one) and puts one behind before
 // anything is stored to z.
-template <int LOG2H, int NT, bool INV>
-__device__ __forceinline__ void kwy_fft_tail4_drain(const kwy_c *z, kwy_c (&lo)[4], kwy_c (&hi)[4], kwy_c &mid) {
-  constexpr int H = 1 << LOG2H, Q = H / 4;
-  static_assert(LOG2H % 3 == 2 && NT == Q / 2, "radix-4 tail, two butterflies per thread");
-  const int t = kwy_tid_opaque();
-  const int jb = t ? Q - t : Q / 2;
-  kwy_c a[4], b[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) { a[m] = z[t + m * Q]; b[m] = z[jb + m * Q]; }
+// (first the two butterflies and the hand-over on operands already in registers -- a: butterfly j = t, b: butterfly
+// j = Q - t resp. Q/2 -- which the loads of the natural order and those of the wave-local layout below share)
+template <bool INV>
+__device__ __forceinline__ void kwy_tail4_drain_pairs(kwy_c (&a)[4], kwy_c (&b)[4], bool t0, kwy_c (&lo)[4],
+                                                      kwy_c (&hi)[4], kwy_c &mid) {
   {
     const kwy_c apc = cadd(a[0], a[2]), amc = csub(a[0], a[2]);
     const kwy_c bpd = cadd(a[1], a[3]), jq = kwy_rot90<INV>(csub(a[1], a[3]));
@@ -1693,12 +1689,22 @@ __device__ __forceinline__ void kwy_fft_tail4_drain(const kwy_c *z, kwy_c (&lo)[
     const kwy_c bpd = cadd(b[1], b[3]), jq = kwy_rot90<INV>(csub(b[1], b[3]));
     b[0] = cadd(apc, bpd); b[1] = cadd(amc, jq); b[2] = csub(apc, bpd); b[3] = csub(amc, jq);
   }
-  const bool t0 = t == 0;
   lo[0] = a[0]; hi[0] = t0 ? a[0] : b[3];
   lo[1] = a[1]; hi[1] = t0 ? a[3] : b[2];
   lo[2] = b[0]; hi[2] = t0 ? b[3] : a[3];
   lo[3] = b[1]; hi[3] = t0 ? b[2] : a[2];
   mid = a[2];
+}
+template <int LOG2H, int NT, bool INV>
+__device__ __forceinline__ void kwy_fft_tail4_drain(const kwy_c *z, kwy_c (&lo)[4], kwy_c (&hi)[4], kwy_c &mid) {
+  constexpr int H = 1 << LOG2H, Q = H / 4;
+  static_assert(LOG2H % 3 == 2 && NT == Q / 2, "radix-4 tail, two butterflies per thread");
+  const int t = kwy_tid_opaque();
+  const int jb = t ? Q - t : Q / 2;
+  kwy_c a[4], b[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) { a[m] = z[t + m * Q]; b[m] = z[jb + m * Q]; }
+  kwy_tail4_drain_pairs<INV>(a, b, t == 0, lo, hi, mid);
 }
 // the bin k of slot s (see above); Q = H/4
 template <int LOG2H>
@@ -1722,6 +1728,169 @@ __device__ __forceinline__ kwy_c kwy_drain_tw(int s, kwy_c twa, kwy_c twc) {
     case 2: return kwy_tw_hex(twc, HEX);
     default: return kwy_tw_hex(twc, 3 * HEX);
   }
+}
+
+// ------------------------------------------------------- the 2048-point transform with two wave-local passes
+// (H = 2048 on 256 threads: the 4096-point D4C frames.)  The Stockham chain above permutes the buffer in every pass, so
+// each pass has a workgroup barrier between its loads and its stores and one behind its stores: six per transform in
+// front of the drained closing pass.  The data flow needs two.  Call a point of the transform after the first pass
+// (s, n): s = 0..7 the sub-transform (the output residue mod 8), n = 0..255 the first-pass butterfly that made it, and
+// let every later butterfly store its results to the eight places it read (decimation in frequency, in place):
+//   first pass    thread j reads x[j + 256 m] (natural order, as the callers fill it), stores result m as (m, j)
+//   stride 8      butterfly (s, j1), j1 = 0..31: points n = j1 + 32 m, m = 0..7; factor twH[8 j1]; result m1 back to
+//                 (s, j1 + 32 m1), which is point s + 8 m1 + 64 j1 of the Stockham order
+//   stride 64     butterfly (s, m1, j2), j2 = 0..3: points n = j2 + 4 m + 32 m1, m = 0..7; factors: entry j2 of the
+//                 powers table; result m2 back to (s, j2 + 4 m2 + 32 m1): Stockham point s + 8 m1 + 64 m2 + 512 j2
+//   radix-4 tail  butterfly j = s + 8 m1 + 64 m2: points n = j2 + 4 m2 + 32 m1, j2 = 0..3 -> X[j + 512 m3]
+// Wavefront w runs the stride-8 butterflies with j1 mod 4 = w and the stride-64 butterflies with j2 = w: both touch
+// exactly the points with n mod 4 = w, so the stride-64 pass reads what its own wavefront wrote, and between the two
+// the wavefront only waits for its own stores (the LDS executes one wavefront's instructions in order; all 64 lanes
+// are live).  Two exchanges cross wavefronts -- first pass to stride-8 pass, stride-64 pass to tail -- and those are
+// the transform's two workgroup barriers.  Same butterflies on the same operands with the same factors as the chain
+// above, formed by the same expressions: only which thread runs a butterfly and where its points lie differ, so every
+// bin keeps its bits.
+// Layout: (s, n) lies at 256 s + (n ^ sw(s) ^ (((n >> 5) & 1) << 3)), sw(s) = s ^ ((s & 4) << 1).  A 16-byte load is
+// served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 -- over the sixteen
+// 16-byte slots of a 256-byte row, a 16-byte store in eight groups of 8 consecutive lanes over eight slots.  A lane is
+// (s, h) = (t & 7, (t >> 3) & 7), and the points of one access of either wave-local pass or of the tail differ in s and
+// h only, n carrying h in its bits 2..4 (stride 8) or 5..7 (stride 64, tail): a load group holds the lanes with equal
+// h2 and equal s2 ^ h0 ^ h1, so s has to reach slot bits 0..2 (which also spreads the eight s of a store group), s2 slot
+// bit 3 as well, and n5 slot bit 3.  Counted over those groups, every load and store of the transform is free of
+// conflicts except the tail's second butterfly (j = 512 - t), at 16 extra LDS cycles per transform.  The place differs
+// from the natural one, n + 256 s, in bits 0..3 only: the first pass's stores land in the 64 columns its own wavefront
+// read, so the write-after-read hazard stays inside the wavefront and that pass needs no barrier between its loads and
+// its stores either.
+// orders a wavefront's LDS loads behind its own LDS stores: kwy_lds_barrier() without the rendezvous
+__device__ __forceinline__ void kwy_lds_wave_fence() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+// the thread's factors: w[0] = twH[t] for the first pass, w[1] = twH[8 j1] of its stride-8 butterfly (t: the thread
+// index, opaque where the fetch is to stay at its use)
+__device__ __forceinline__ void kwy_fftwl_thread_twiddles(const kwy_c *__restrict__ twH, int t, kwy_c (&w)[4]) {
+  w[0] = twH[t];
+  w[1] = twH[32 * ((t >> 3) & 7) + 8 * ((t >> 6) & 3)];
+  w[2] = w[3] = kwy_c{1.0, 0.0};
+}
+// first-pass stores: result m of thread j to (m, j)
+__device__ __forceinline__ void kwy_fftwl_store_first(kwy_c *z, int j, const kwy_c (&a)[8]) {
+  const int c = j ^ (((j >> 5) & 1) << 3);
+#pragma unroll
+  for (int m = 0; m < 8; ++m) z[256 * m + (c ^ (m ^ ((m & 4) << 1)))] = a[m];
+}
+// the factor's 2nd .. 7th powers and the products, by the expressions of kwy_fft_pass8_core
+template <bool INV>
+__device__ __forceinline__ void kwy_fftwl_twiddle(kwy_c (&a)[8], kwy_c w1) {
+  if (INV) w1.y = -w1.y;
+  const kwy_c w2 = cmulf(w1, w1), w4 = cmulf(w2, w2);
+  const kwy_c w3 = cmulf(w1, w2), w5 = cmulf(w4, w1), w6 = cmulf(w4, w2);
+  const kwy_c w7 = cmulf(w4, w3);
+  a[1] = cmulf(w1, a[1]); a[2] = cmulf(w2, a[2]); a[3] = cmulf(w3, a[3]);
+  a[4] = cmulf(w4, a[4]); a[5] = cmulf(w5, a[5]); a[6] = cmulf(w6, a[6]);
+  a[7] = cmulf(w7, a[7]);
+}
+// First pass, dense or (block-uniform `half`) with the loads and the butterfly of kwy_fft_pass8_first_half_core.  The
+// caller has a barrier between filling z and this call; ends with a barrier.
+template <bool INV>
+__device__ __forceinline__ void kwy_fftwl_first_sel(kwy_c *z, kwy_tw_reg tw, bool half) {
+  constexpr int H = 2048, Q = 256;
+  const int j = kwy_tid_opaque();
+  kwy_c a[8];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) a[m] = z[j + m * Q];
+  if (half) {
+    a[4] = {0.0, 0.0};
+    if (j == 0) a[4] = z[H / 2];
+    kwy_dft8_low5<INV>(a);
+  } else {
+#pragma unroll
+    for (int m = 4; m < 8; ++m) a[m] = z[j + m * Q];
+    kwy_dft8<INV>(a);
+  }
+  kwy_fftwl_twiddle<INV>(a, tw(j));
+  kwy_fftwl_store_first(z, j, a);
+  __syncthreads();
+}
+// First pass of an input that is zero except for x[0 .. 256]: kwy_fft_pass8_first_sparse_core in this layout (thread j
+// supplies x[j] in a0, thread 0 also x[256] in a1; nothing is read, the buffer itself must be free).  Ends with a barrier.
+// (k_d4c_bands, the kernel with this kind of input, keeps the chain -- kwy_d4c.hip; the self-test holds this to its bits.)
+template <bool INV>
+__device__ __forceinline__ void kwy_fftwl_first_sparse(kwy_c *z, kwy_tw_reg tw, kwy_c a0, kwy_c a1) {
+  const int j = kwy_tid_opaque();
+  kwy_c a[8];
+  if (j == 0) {
+    a[0] = a0; a[1] = a1;
+#pragma unroll
+    for (int m = 2; m < 8; ++m) a[m] = {0.0, 0.0};
+    kwy_dft8<INV>(a);
+  } else {
+    kwy_c w1 = tw(j);
+    if (INV) w1.y = -w1.y;
+    const kwy_c w2 = cmulf(w1, w1), w4 = cmulf(w2, w2);
+    const kwy_c w3 = cmulf(w1, w2), w5 = cmulf(w4, w1), w6 = cmulf(w4, w2);
+    const kwy_c w7 = cmulf(w4, w3);
+    a[0] = a0; a[1] = cmulf(w1, a0); a[2] = cmulf(w2, a0); a[3] = cmulf(w3, a0);
+    a[4] = cmulf(w4, a0); a[5] = cmulf(w5, a0); a[6] = cmulf(w6, a0); a[7] = cmulf(w7, a0);
+  }
+  kwy_fftwl_store_first(z, j, a);
+  __syncthreads();
+}
+// The two wave-local passes behind a first pass; ends with a barrier, in front of the drained tail.
+// w1: twH[8 j1] of this thread (kwy_fftwl_thread_twiddles); pw: the powers table.
+template <bool INV>
+__device__ __forceinline__ void kwy_fftwl_rest(kwy_c *z, kwy_tw_reg tw1, const kwy_c *__restrict__ pw) {
+  const int t = kwy_tid_opaque();
+  const int s = t & 7, hi3 = (t >> 3) & 7, wv = (t >> 6) & 3;
+  const int sw = s ^ ((s & 4) << 1);
+  kwy_c a[8];
+  {   // stride 8: butterfly (s, j1 = 4 hi3 + wv), points n = j1 + 32 m at 256 s + 32 m + (j1 ^ sw ^ ((m & 1) << 3))
+    const int c = 256 * s + ((4 * hi3 + wv) ^ sw);
+    const int at[2] = {c, c ^ 8};
+#pragma unroll
+    for (int m = 0; m < 8; ++m) a[m] = z[at[m & 1] + 32 * m];
+    kwy_dft8<INV>(a);
+    kwy_fftwl_twiddle<INV>(a, tw1(0));
+#pragma unroll
+    for (int m = 0; m < 8; ++m) z[at[m & 1] + 32 * m] = a[m];
+  }
+  kwy_lds_wave_fence();
+  {   // stride 64: butterfly (s, m1 = hi3, j2 = wv), points n = wv + 4 m + 32 m1 at
+      // 256 s + 32 m1 + ((wv + 4 m) ^ k), k = sw ^ ((m1 & 1) << 3)
+    const int k = sw ^ ((hi3 & 1) << 3);
+    const int c = 256 * s + 32 * hi3 + (wv ^ (k & 3));
+    int at[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) at[q] = c + 4 * (q ^ (k >> 2));
+#pragma unroll
+    for (int m = 0; m < 8; ++m) a[m] = z[at[m & 3] + 4 * (m & 4)];
+    kwy_dft8<INV>(a);
+    const kwy_c *__restrict__ pe = pw + KWY_TWP_ENTRY * __builtin_amdgcn_readfirstlane(t >> 6);
+#pragma unroll
+    for (int m = 1; m < 8; ++m) {
+      kwy_c w = pe[m];
+      if (INV) w.y = -w.y;
+      a[m] = cmulf(w, a[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < 8; ++m) z[at[m & 3] + 4 * (m & 4)] = a[m];
+  }
+  __syncthreads();
+}
+// the place of operand j2 of the tail's butterfly j = s + 8 m1 + 64 m2, j < 512
+__device__ __forceinline__ int kwy_fftwl_tail_at(int j, int j2) {
+  const int s = j & 7, m1 = (j >> 3) & 7, m2 = (j >> 6) & 7;
+  const int k = s ^ ((s & 4) << 1) ^ ((m1 & 1) << 3);
+  return 256 * s + 32 * m1 + ((4 * m2) ^ (k & 12)) + (j2 ^ (k & 3));
+}
+// kwy_fft_tail4_drain<11, 256, INV> on this layout: the same butterflies, pairs and slots
+template <bool INV>
+__device__ __forceinline__ void kwy_fftwl_tail4_drain(const kwy_c *z, kwy_c (&lo)[4], kwy_c (&hi)[4], kwy_c &mid) {
+  constexpr int Q = 512;
+  const int t = kwy_tid_opaque();
+  const int jb = t ? Q - t : Q / 2;
+  kwy_c a[4], b[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) { a[m] = z[kwy_fftwl_tail_at(t, m)]; b[m] = z[kwy_fftwl_tail_at(jb, m)]; }
+  kwy_tail4_drain_pairs<INV>(a, b, t == 0, lo, hi, mid);
 }
 
 template <int LOG2H>

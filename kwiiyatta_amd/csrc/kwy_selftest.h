@@ -55,6 +55,16 @@ int kwy_debug_syn_first_passes_dev(void *stream, const double *x, int problems, 
  * -2 (HIP failure). */
 int kwy_debug_fft_half_w_dev(void *stream, const double *x, const double *stale, int problems, int log2h, int inverse,
                              int tail, double *out_dense, double *out_half);
+/* The 2048-point transform of the 4096-point D4C frames (256 threads) up to and including the drained closing pass,
+ * twice on every row: the Stockham chain (kwy_fft_inplace_w / kwy_fft_inplace_sel_w / kwy_fft_pass8_first_sparse_core +
+ * kwy_fft_inplace_rest_w, then kwy_fft_tail4_drain: out_old) and the wave-local form (kwy_fftwl_*: out_new).  Before
+ * either runs, the whole buffer (2049 points) is filled with the row of `stale`.  kind: 0 dense (all 2048 points of the
+ * row), 1 half (points 0 .. 1024 of the row, the half first pass), 2 half with point 1024 stored as zero, 3 sparse
+ * (points 0 .. 256 of the row, from registers).  x: problems x 2048 x {re, im}; stale: problems x 2049 x {re, im};
+ * out_old, out_new: problems x 256 threads x 9 x {re, im}: lo[0..3], hi[0..3], mid of kwy_fft_tail4_drain (all device).
+ * Synchronises the stream.  Returns 0, -1 (arguments) or -2 (HIP failure). */
+int kwy_debug_fft_wave_local_dev(void *stream, const double *x, const double *stale, int problems, int kind,
+                                 double *out_old, double *out_new);
 #ifdef __cplusplus
 }
 #endif

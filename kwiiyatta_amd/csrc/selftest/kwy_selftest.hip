@@ -602,3 +602,81 @@ extern "C" int kwy_debug_fft_half_w_dev(void *stream, const double *x, const dou
   (void)hipFree(tw);
   return rc;
 }
+
+// ---- diagnostic: the 2048-point transform up to the drained pairs, Stockham chain against the wave-local form --------
+// (one 256-thread workgroup per row, the shape of k_d4c_body<12> / k_d4c_bands<12>.  Both paths start from a buffer that
+// holds the row of `stale` in all H + 1 points -- what the previous transform, the smoothing or the select left there --
+// and fill what their kind of input fills: see kwy_selftest.h.)
+template <bool SPARSE>
+__global__ __launch_bounds__(256) void k_fft_wave_local_selftest(const kwy_c *__restrict__ x, const kwy_c *__restrict__ stale,
+                                                                 const kwy_c *__restrict__ twH, const kwy_c *__restrict__ twP,
+                                                                 int kind, kwy_c *__restrict__ out_old,
+                                                                 kwy_c *__restrict__ out_new) {
+  constexpr int LOG2H = 11, H = 1 << LOG2H, NT = 256;
+  extern __shared__ double smem[];
+  kwy_c *B = (kwy_c *)smem;          // H + 1 complex
+  const int tid = threadIdx.x;
+  const kwy_c *row = x + (size_t)blockIdx.x * H, *old = stale + (size_t)blockIdx.x * (H + 1);
+  const bool half = kind == 1 || kind == 2;
+#pragma nounroll
+  for (int path = 0; path < 2; ++path) {
+    kwy_c *o = (path == 0 ? out_old : out_new) + ((size_t)blockIdx.x * NT + tid) * 9;
+    for (int i = tid; i <= H; i += NT) B[i] = old[i];
+    __syncthreads();
+    if (!SPARSE) {
+      const int n = half ? H / 2 + 1 : H;
+      for (int i = tid; i < n; i += NT) B[i] = (kind == 2 && i == H / 2) ? kwy_c{0.0, 0.0} : row[i];
+      __syncthreads();
+    }
+    kwy_c tw4[4], lo[4], hi[4], md;
+    if (path == 0) {
+      kwy_fft_thread_twiddles<LOG2H, NT>(twH, tw4);
+      if constexpr (SPARSE) {
+        kwy_fft_pass8_first_sparse_core<LOG2H, NT, false>(B, kwy_tw_reg{tw4[0]}, row[tid], tid == 0 ? row[H / 8] : kwy_c{0.0, 0.0});
+        kwy_fft_inplace_rest_w<LOG2H, NT, false, false>(B, tw4, twP);
+      } else {
+        kwy_fft_inplace_sel_w<LOG2H, NT, false, false>(B, tw4, twP, half);
+      }
+      kwy_fft_tail4_drain<LOG2H, NT, false>(B, lo, hi, md);
+    } else {
+      kwy_fftwl_thread_twiddles(twH, tid, tw4);
+      if constexpr (SPARSE) kwy_fftwl_first_sparse<false>(B, kwy_tw_reg{tw4[0]}, row[tid], tid == 0 ? row[H / 8] : kwy_c{0.0, 0.0});
+      else kwy_fftwl_first_sel<false>(B, kwy_tw_reg{tw4[0]}, half);
+      kwy_fftwl_rest<false>(B, kwy_tw_reg{tw4[1]}, twP);
+      kwy_fftwl_tail4_drain<false>(B, lo, hi, md);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { o[s] = lo[s]; o[4 + s] = hi[s]; }
+    o[8] = md;
+    __syncthreads();
+  }
+}
+
+extern "C" int kwy_debug_fft_wave_local_dev(void *stream, const double *x, const double *stale, int problems, int kind,
+                                            double *out_old, double *out_new) {
+  if (!x || !stale || !out_old || !out_new || problems <= 0 || kind < 0 || kind > 3) return -1;
+  constexpr int LOG2H = 11, H = 1 << LOG2H, entries = KWY_TWP_ENTRIES(LOG2H);
+  std::vector<kwy_c> h(H / 8);
+  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * M_PI * (double)k / (double)H; h[k] = {cos(a), sin(a)}; }
+  kwy_c *tw = nullptr;                 // exp(-2 pi i k / H), k < H/8, and the powers table behind it
+  if (hipMalloc((void **)&tw, sizeof(kwy_c) * (H / 8 + KWY_TWP_ENTRY * entries)) != hipSuccess) return -2;
+  int rc = 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * (H / 8), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  if (rc == 0) {
+    kwy_c *tp = tw + H / 8;
+    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, tp, entries);
+    if (hipGetLastError() != hipSuccess) rc = -2;
+    const size_t lds = sizeof(kwy_c) * (H + 1);
+    auto kern = kind == 3 ? k_fft_wave_local_selftest<true> : k_fft_wave_local_selftest<false>;
+    if (rc == 0 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) rc = -2;
+    if (rc == 0) {
+      hipLaunchKernelGGL(kern, dim3(problems), dim3(256), lds, s, (const kwy_c *)x, (const kwy_c *)stale, (const kwy_c *)tw,
+                         (const kwy_c *)tp, kind, (kwy_c *)out_old, (kwy_c *)out_new);
+      if (hipGetLastError() != hipSuccess) rc = -2;
+    }
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
+  (void)hipFree(tw);
+  return rc;
+}
