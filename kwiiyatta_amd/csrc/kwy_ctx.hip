@@ -286,7 +286,7 @@ int kwy_table_upload(kwy_ctx *ctx, const std::string &key, const void *host, siz
   return KWY_OK;
 }
 
-// The powers table of the stride-64 pass (kwy_device.hpp: kwy_tw_powers), filled on the device with the expressions the
+// The powers table of the stride-64 pass (kwy_fft.hpp: kwy_tw_powers), filled on the device with the expressions the
 // per-lane pass uses, under the same -ffp-contract=off (k_twiddle_powers_fill): entry u holds the bits every lane of a
 // wavefront with j >> 6 == u would form from tw[64 u].
 int kwy_get_twiddles(kwy_ctx *ctx, int log2n, const kwy_c **out) {

@@ -13,7 +13,7 @@
 //                     of the smallest power bins against the sum of all (a histogram
 //                     select, no sort) and the energy ratio; finally the band values are
 //                     interpolated to the K output bins.
-// The stride-64 pass of every transform takes its factors from the context's powers table (twP; kwy_device.hpp:
+// The stride-64 pass of every transform takes its factors from the context's powers table (twP; kwy_fft.hpp:
 // kwy_tw_powers).  The noise of the windows comes from the process-wide randn table (kwy_device.hpp).  The
 // 4096-point frames (32 .. 48 kHz) drain the closing pass of every transform into
 // registers (d4c_drain below).
@@ -488,7 +488,7 @@ struct d4c_nt { static constexpr int value = LOG2N >= 13 ? 512 : 256; };
 // re-read.  The other sizes have another thread / point ratio, a radix-2 tail or none, and keep the stored form.
 template <int LOG2N>
 struct d4c_drain { static constexpr bool value = LOG2N == 12; };
-// ... and k_d4c_body runs them in the wave-local form (kwy_device.hpp, kwy_fftwl_*): the same butterflies, two workgroup
+// ... and k_d4c_body runs them in the wave-local form (kwy_fft.hpp, kwy_fftwl_*): the same butterflies, two workgroup
 // barriers per transform in front of the drain instead of six.  k_d4c_bands keeps the Stockham chain: its exchange of
 // powers stores to Z[2 NT - tid] and Z[4 NT - tid] right behind the drain's loads, which in the wave-local layout hold
 // other wavefronts' operands -- with the barrier that takes, the kernel measured no faster.

@@ -15,7 +15,7 @@
 //   * cos / sin of w~_k: one table per (N, alpha), kept with the context (built on the host on first use)
 //   * e^{-j m w~_k}: the rotation recurrence from m = 0 upwards, the two frames' sums side by side on one rotation;
 //     separate multiplications and additions in a fixed order (the library is built with -ffp-contract=off)
-//   * one real transform in, two spectral products, two real transforms out: the LDS FFTs of kwy_device.hpp, in two
+//   * one real transform in, two spectral products, two real transforms out: the LDS FFTs of kwy_fft.hpp, in two
 //     buffers of N/2 + 1 complex
 #include <math.h>
 #include <stdio.h>

@@ -10,7 +10,7 @@
 #include <vector>
 
 #include "../../include/kwy.h"
-#include "kwy_device.hpp"
+#include "kwy_fft.hpp"      // (and kwy_device.hpp through it: kwy_c is the element type of the twiddle tables)
 
 struct kwy_ctx {
   int device = 0;
@@ -130,7 +130,7 @@ static inline int kwy_cached_table(kwy_ctx *ctx, const std::string &key, BUILD b
 }
 
 int kwy_get_twiddles(kwy_ctx *ctx, int log2n, const kwy_c **out);
-// w^1 .. w^7 of every factor w the stride-64 radix-8 pass of a 2^log2h-point LDS transform uses (kwy_device.hpp:
+// w^1 .. w^7 of every factor w the stride-64 radix-8 pass of a 2^log2h-point LDS transform uses (kwy_fft.hpp:
 // kwy_tw_powers), KWY_TWP_ENTRY complex per factor; made together with the twiddles of that length.  Transforms below
 // 1024 points have no such pass: *out = NULL.
 int kwy_get_twiddle_powers(kwy_ctx *ctx, int log2h, const kwy_c **out);

@@ -48,7 +48,7 @@ int kwy_debug_syn_first_passes_dev(void *stream, const double *x, int problems, 
                                    double *out_half, double *fold_ref, double *fold_new);
 /* The complex LDS transform on thread-held pass factors in the shapes of k_d4c_body (2^log2h = 1024 or 2048 points with
  * 256 threads, 4096 with 512), forward or inverse, twice on every row: kwy_fft_inplace_w on the whole row (out_dense),
- * and kwy_fft_inplace_half_w on a buffer that holds points 0 .. H/2 of the row and, above them, the same points of
+ * and kwy_fft_inplace_sel_w with half = true on a buffer that holds points 0 .. H/2 of the row and, above them, the same points of
  * `stale` (out_half) -- the half transform takes the points above H/2 as zero and must not read them.  tail = 0 stops
  * both in front of the closing radix-4 / radix-2 pass (what the callers of kwy_fft_tail4_drain do).  x, stale,
  * out_dense, out_half: problems x 2^log2h x {re, im} (device).  Synchronises the stream.  Returns 0, -1 (arguments) or

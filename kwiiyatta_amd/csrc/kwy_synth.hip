@@ -789,7 +789,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_syn_pulse_emit(syn_plan_batch b
 // -- every wavefront works in every pass, and the registers of the idle half buy two more workgroups per CU -- but
 // keeps the arithmetic of the 256-thread form it replaced, bit for bit: thread t stands for the V = 256/NT "virtual"
 // threads t + NT g.  Pair twiddles: exp(-2 pi i k / N) for k = t + NT r as base[r % V] times an 8th root of unity,
-// base[g] = exp(-2 pi i (t + NT g) / N) (syn_pair_twiddle, kwy_device.hpp); block sums: the partial sums of the virtual
+// base[g] = exp(-2 pi i (t + NT g) / N) (syn_pair_twiddle, kwy_fft.hpp); block sums: the partial sums of the virtual
 // threads, wavefront by wavefront (syn_block_sum_v).
 template <int LOG2N>
 struct syn_pulse_nt { static constexpr int value = LOG2N <= 10 ? 64 : (LOG2N == 11 ? 128 : 256); };
@@ -820,27 +820,22 @@ __device__ inline void syn_rfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, 
 template <int LOG2H, int NT, int V>
 __device__ inline void syn_irfft_inplace(kwy_c *z, const kwy_c *__restrict__ tw, const kwy_c *__restrict__ pw, const kwy_c (&base)[V],
                                          const kwy_c *__restrict__ twN) {
-  constexpr int H = 1 << LOG2H, N = 2 * H;
-  constexpr bool TABLE = 8 * (NT * V) / N < 1;
+  constexpr int H = 1 << LOG2H;
   const int tid = kwy_tid_opaque();
   __syncthreads();
 #pragma unroll
-  for (int r = 0; r * NT <= H / 2; ++r) {
+  for (int r = 0; r * NT <= H / 2; ++r) {   // kwy_irfft_inplace's loop with the pair twiddles of the virtual threads
     const int k = tid + NT * r;
     if (k > H / 2) continue;
     if (k == 0) {
       const double ar = z[0].x, br = z[H].x;
       z[0] = {ar + br, ar - br};
     } else {
-      kwy_c w;
-      if constexpr (TABLE) w = twN[k]; else w = syn_pair_twiddle<LOG2H, NT, V>(base, r);
-      const kwy_c A = z[k], Bc = z[H - k];
-      const double er = A.x + Bc.x, ei = A.y - Bc.y;
-      const double dr = A.x - Bc.x, di = A.y + Bc.y;
-      const double wr = w.x, wi = -w.y;
-      const double orr = __builtin_fma(dr, wr, -(di * wi)), oi = __builtin_fma(dr, wi, di * wr);
-      z[k] = {er - oi, ei + orr};
-      if (k != H - k) z[H - k] = {er + oi, -(ei - orr)};
+      const kwy_c w = syn_pair_twiddle<LOG2H, NT, V>(base, twN, k, r);
+      kwy_c bk, bm;
+      kwy_irsplit_pair(z[k], z[H - k], w, bk, bm);
+      z[k] = bk;
+      if (k != H - k) z[H - k] = bm;
     }
   }
   __syncthreads();

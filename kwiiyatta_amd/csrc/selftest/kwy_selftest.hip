@@ -1,5 +1,5 @@
 // libkwy_selftest.so -- NOT part of the product: entry points that let tests drive device-side building blocks of
-// kwy_device.hpp on caller data.  Built beside libkwy.so by build.sh, loaded only by tests (test_select_gpu.py,
+// kwy_device.hpp and kwy_fft.hpp on caller data.  Built beside libkwy.so by build.sh, loaded only by tests (test_select_gpu.py,
 // test_select_paths_gpu.py, test_devmath_gpu.py, test_fft_regs_gpu.py).
 #include <hip/hip_runtime.h>
 
@@ -8,7 +8,7 @@
 
 #include <vector>
 
-#include "../kwy_device.hpp"
+#include "../kwy_fft.hpp"
 #include "../kwy_selftest.h"
 
 #define D4C_NT 256   // the 256-thread select of the 16..48 kHz band kernel
@@ -282,6 +282,31 @@ extern "C" int kwy_debug_block_exscan_dev(void *stream, const int *values, int p
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// ---- the twiddle tables of the FFT diagnostics below, on the device for the lifetime of the object -------------------
+// twH: exp(-2 pi i k / H), k < nh; twN (where asked): exp(-2 pi i k / N), k < N = 2H; twP: the powers table of an H-point
+// transform's stride-64 pass, filled on `s` by the library's own fill kernel from twH (which reads twH[64 u], u < H/512:
+// inside the H/8 factors every caller asks for) -- behind the tables, or in `powers_out` where the caller wants to see it.
+struct fft_tables {
+  kwy_c *buf = nullptr;
+  const kwy_c *twH = nullptr, *twN = nullptr, *twP = nullptr;
+  int rc = 0;
+  fft_tables(hipStream_t s, int log2h, int nh, bool with_n, kwy_c *powers_out = nullptr) {
+    const int H = 1 << log2h, N = 2 * H, nn = with_n ? N : 0, entries = H / 512;
+    std::vector<kwy_c> h(nh + nn);
+    for (int k = 0; k < nh; ++k) { const double a = -2.0 * KWY_PI * k / H; h[k] = {cos(a), sin(a)}; }
+    for (int k = 0; k < nn; ++k) { const double a = -2.0 * KWY_PI * k / N; h[nh + k] = {cos(a), sin(a)}; }
+    if (hipMalloc((void **)&buf, sizeof(kwy_c) * (h.size() + KWY_TWP_ENTRY * entries)) != hipSuccess ||
+        hipMemcpy(buf, h.data(), sizeof(kwy_c) * h.size(), hipMemcpyHostToDevice) != hipSuccess) { rc = -2; return; }
+    kwy_c *pw = powers_out ? powers_out : buf + h.size();
+    twH = buf; twN = with_n ? buf + nh : nullptr; twP = pw;
+    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, twH, pw, entries);
+    if (hipGetLastError() != hipSuccess) rc = -2;
+  }
+  ~fft_tables() { (void)hipFree(buf); }
+  fft_tables(const fft_tables &) = delete;
+  fft_tables &operator=(const fft_tables &) = delete;
+};
+
 // ---- diagnostic: the real transform of N = 4096 samples through the stored and the drained closing pass ----------
 // (one 256-thread workgroup per row; both paths return TWICE the bins 0 .. H, (H + 1) x {re, im} per row, formed by
 // kwy_rfft_bin2_w resp. its register form with the same twiddle expressions the D4C kernels use: W^k of a bin below
@@ -336,27 +361,17 @@ extern "C" int kwy_debug_rfft_paths_dev(void *stream, const double *x, int probl
   if (!x || !out_old || !out_new || problems <= 0) return -1;
   if (log2n != 12) return -1;        // the one size with a drained closing pass
   constexpr int LOG2N = 12, NT = 256, N = 1 << LOG2N, H = N / 2;
-  constexpr int TWP = KWY_TWP_ENTRY * KWY_TWP_ENTRIES(LOG2N - 1);    // the powers table behind the two twiddle tables
-  std::vector<kwy_c> h(H / 8 + N + TWP);
-  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * KWY_PI * k / H; h[k] = {cos(a), sin(a)}; }
-  for (int k = 0; k < N; ++k) { const double a = -2.0 * KWY_PI * k / N; h[H / 8 + k] = {cos(a), sin(a)}; }
-  kwy_c *tw = nullptr;
-  if (hipMalloc((void **)&tw, sizeof(kwy_c) * h.size()) != hipSuccess) return -2;
-  int rc = 0;
-  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * h.size(), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  hipStream_t s = (hipStream_t)stream;
+  fft_tables t(s, LOG2N - 1, H / 8, true);
+  int rc = t.rc;
+  const size_t lds = sizeof(kwy_c) * (H + 1);
+  auto kern = k_rfft_paths_selftest<LOG2N, NT>;
+  if (rc == 0 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) rc = -2;
   if (rc == 0) {
-    const size_t lds = sizeof(kwy_c) * (H + 1);
-    auto kern = k_rfft_paths_selftest<LOG2N, NT>;
-    if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) rc = -2;
-    if (rc == 0) {
-      hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, (hipStream_t)stream, (const kwy_c *)tw,
-                         tw + H / 8 + N, KWY_TWP_ENTRIES(LOG2N - 1));
-      hipLaunchKernelGGL(kern, dim3(problems), dim3(NT), lds, (hipStream_t)stream, x, tw, tw + H / 8 + N, tw + H / 8, (kwy_c *)out_old,
-                         (kwy_c *)out_new);
-      if (hipGetLastError() != hipSuccess || hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = -2;
-    }
+    hipLaunchKernelGGL(kern, dim3(problems), dim3(NT), lds, s, x, t.twH, t.twP, t.twN, (kwy_c *)out_old, (kwy_c *)out_new);
+    if (hipGetLastError() != hipSuccess) rc = -2;
   }
-  hipFree(tw);
+  if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
   return rc;
 }
 
@@ -424,20 +439,15 @@ extern "C" int kwy_debug_fft_powers_dev(void *stream, const double *x, int probl
   if (!x || !out_lane || !out_table || !tab || !tab_ref || !tab_ref_conj || problems <= 0) return -1;
   if (!((log2h == 10 && (nt == 128 || nt == 256)) || (log2h == 11 && nt == 256) || (log2h == 12 && nt == 512))) return -1;
   const int H = 1 << log2h, entries = H / 512;
-  std::vector<kwy_c> h(H);
-  for (int k = 0; k < H; ++k) { const double a = -2.0 * M_PI * (double)k / (double)H; h[k] = {cos(a), sin(a)}; }
-  kwy_c *tw = nullptr;
-  if (hipMalloc((void **)&tw, sizeof(kwy_c) * H) != hipSuccess) return -2;
-  int rc = 0;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * H, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  fft_tables t(s, log2h, H, false, (kwy_c *)tab);    // (the per-lane stride-64 pass reads the whole table)
+  int rc = t.rc;
   if (rc == 0) {
-    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, (kwy_c *)tab, entries);
-    hipLaunchKernelGGL(k_twiddle_powers_ref, dim3(1), dim3(1), 0, s, (const kwy_c *)tw, entries, (kwy_c *)tab_ref, (kwy_c *)tab_ref_conj);
+    hipLaunchKernelGGL(k_twiddle_powers_ref, dim3(1), dim3(1), 0, s, t.twH, entries, (kwy_c *)tab_ref, (kwy_c *)tab_ref_conj);
     if (hipGetLastError() != hipSuccess) rc = -2;
   }
   if (rc == 0) {
-    const kwy_c *cx = (const kwy_c *)x, *tp = (const kwy_c *)tab;
+    const kwy_c *cx = (const kwy_c *)x, *tw = t.twH, *tp = t.twP;
     kwy_c *ol = (kwy_c *)out_lane, *ot = (kwy_c *)out_table;
     if (log2h == 10 && nt == 128) rc = fft_powers_launch<10, 128>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
     else if (log2h == 10) rc = fft_powers_launch<10, 256>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
@@ -445,7 +455,6 @@ extern "C" int kwy_debug_fft_powers_dev(void *stream, const double *x, int probl
     else rc = fft_powers_launch<12, 512>(s, cx, problems, inverse != 0, tw, tp, ol, ot);
   }
   if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
-  hipFree(tw);
   return rc;
 }
 
@@ -503,27 +512,17 @@ __global__ __launch_bounds__(128) void k_syn_first_passes_selftest(const kwy_c *
 extern "C" int kwy_debug_syn_first_passes_dev(void *stream, const double *x, int problems, double *out_dense,
                                               double *out_sparse, double *out_half, double *fold_ref, double *fold_new) {
   if (!x || !out_dense || !out_sparse || !out_half || !fold_ref || !fold_new || problems <= 0) return -1;
-  constexpr int LOG2H = 10, H = 1 << LOG2H, N = 2 * H;
-  constexpr int TWP = KWY_TWP_ENTRY * KWY_TWP_ENTRIES(LOG2H);        // the powers table behind the two twiddle tables
-  std::vector<kwy_c> h(H / 8 + N + TWP);
-  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * KWY_PI * k / H; h[k] = {cos(a), sin(a)}; }
-  for (int k = 0; k < N; ++k) { const double a = -2.0 * KWY_PI * k / N; h[H / 8 + k] = {cos(a), sin(a)}; }
-  kwy_c *tw = nullptr;
-  if (hipMalloc((void **)&tw, sizeof(kwy_c) * h.size()) != hipSuccess) return -2;
-  int rc = 0;
+  constexpr int LOG2H = 10, H = 1 << LOG2H;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * h.size(), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  fft_tables t(s, LOG2H, H / 8, true);
+  int rc = t.rc;
   if (rc == 0) {
     const size_t lds = sizeof(kwy_c) * (H + 1);
-    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, tw + H / 8 + N,
-                       KWY_TWP_ENTRIES(LOG2H));
-    hipLaunchKernelGGL(k_syn_first_passes_selftest<0>, dim3(problems), dim3(128), lds, s, (const kwy_c *)x, (const kwy_c *)tw,
-                       (const kwy_c *)(tw + H / 8 + N), (const kwy_c *)(tw + H / 8), (kwy_c *)out_dense, (kwy_c *)out_sparse,
-                       (kwy_c *)out_half, fold_ref, fold_new);
+    hipLaunchKernelGGL(k_syn_first_passes_selftest<0>, dim3(problems), dim3(128), lds, s, (const kwy_c *)x, t.twH, t.twP, t.twN,
+                       (kwy_c *)out_dense, (kwy_c *)out_sparse, (kwy_c *)out_half, fold_ref, fold_new);
     if (hipGetLastError() != hipSuccess) rc = -2;
   }
   if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
-  (void)hipFree(tw);
   return rc;
 }
 
@@ -549,7 +548,7 @@ __global__ __launch_bounds__(NT) void k_fft_half_w_selftest(const kwy_c *__restr
     for (int i = tid; i < H; i += NT) B[i] = (path == 0 || i <= H / 2) ? row[i] : old[i];
     __syncthreads();
     if (path == 0) kwy_fft_inplace_w<LOG2H, NT, INV, TAIL>(B, tw4, twP);
-    else kwy_fft_inplace_half_w<LOG2H, NT, INV, TAIL>(B, tw4, twP);
+    else kwy_fft_inplace_sel_w<LOG2H, NT, INV, TAIL>(B, tw4, twP, true);
     for (int i = tid; i < H; i += NT) o[i] = B[i];
     __syncthreads();
   }
@@ -577,29 +576,18 @@ extern "C" int kwy_debug_fft_half_w_dev(void *stream, const double *x, const dou
                                         int inverse, int tail, double *out_dense, double *out_half) {
   if (!x || !stale || !out_dense || !out_half || problems <= 0) return -1;
   if (log2h < 10 || log2h > 12) return -1;
-  const int H = 1 << log2h, entries = H / 512;
-  std::vector<kwy_c> h(H / 8);
-  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * M_PI * (double)k / (double)H; h[k] = {cos(a), sin(a)}; }
-  kwy_c *tw = nullptr;                 // exp(-2 pi i k / H), k < H/8, and the powers table behind it
-  if (hipMalloc((void **)&tw, sizeof(kwy_c) * (H / 8 + KWY_TWP_ENTRY * entries)) != hipSuccess) return -2;
-  int rc = 0;
+  const int H = 1 << log2h;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * (H / 8), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  fft_tables t(s, log2h, H / 8, false);
+  int rc = t.rc;
   if (rc == 0) {
-    kwy_c *tp = tw + H / 8;
-    // (the fill kernel reads tw[64 u], u < H/512: inside the H/8 factors)
-    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, tp, entries);
-    if (hipGetLastError() != hipSuccess) rc = -2;
     const kwy_c *cx = (const kwy_c *)x, *cs = (const kwy_c *)stale;
     kwy_c *od = (kwy_c *)out_dense, *oh = (kwy_c *)out_half;
-    if (rc == 0) {
-      if (log2h == 10) rc = fft_half_w_pick<10, 256>(s, inverse != 0, tail != 0, cx, cs, problems, tw, tp, od, oh);
-      else if (log2h == 11) rc = fft_half_w_pick<11, 256>(s, inverse != 0, tail != 0, cx, cs, problems, tw, tp, od, oh);
-      else rc = fft_half_w_pick<12, 512>(s, inverse != 0, tail != 0, cx, cs, problems, tw, tp, od, oh);
-    }
+    if (log2h == 10) rc = fft_half_w_pick<10, 256>(s, inverse != 0, tail != 0, cx, cs, problems, t.twH, t.twP, od, oh);
+    else if (log2h == 11) rc = fft_half_w_pick<11, 256>(s, inverse != 0, tail != 0, cx, cs, problems, t.twH, t.twP, od, oh);
+    else rc = fft_half_w_pick<12, 512>(s, inverse != 0, tail != 0, cx, cs, problems, t.twH, t.twP, od, oh);
   }
   if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
-  (void)hipFree(tw);
   return rc;
 }
 
@@ -655,28 +643,18 @@ __global__ __launch_bounds__(256) void k_fft_wave_local_selftest(const kwy_c *__
 extern "C" int kwy_debug_fft_wave_local_dev(void *stream, const double *x, const double *stale, int problems, int kind,
                                             double *out_old, double *out_new) {
   if (!x || !stale || !out_old || !out_new || problems <= 0 || kind < 0 || kind > 3) return -1;
-  constexpr int LOG2H = 11, H = 1 << LOG2H, entries = KWY_TWP_ENTRIES(LOG2H);
-  std::vector<kwy_c> h(H / 8);
-  for (int k = 0; k < H / 8; ++k) { const double a = -2.0 * M_PI * (double)k / (double)H; h[k] = {cos(a), sin(a)}; }
-  kwy_c *tw = nullptr;                 // exp(-2 pi i k / H), k < H/8, and the powers table behind it
-  if (hipMalloc((void **)&tw, sizeof(kwy_c) * (H / 8 + KWY_TWP_ENTRY * entries)) != hipSuccess) return -2;
-  int rc = 0;
+  constexpr int LOG2H = 11, H = 1 << LOG2H;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpy(tw, h.data(), sizeof(kwy_c) * (H / 8), hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+  fft_tables t(s, LOG2H, H / 8, false);
+  int rc = t.rc;
+  const size_t lds = sizeof(kwy_c) * (H + 1);
+  auto kern = kind == 3 ? k_fft_wave_local_selftest<true> : k_fft_wave_local_selftest<false>;
+  if (rc == 0 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) rc = -2;
   if (rc == 0) {
-    kwy_c *tp = tw + H / 8;
-    hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, s, (const kwy_c *)tw, tp, entries);
+    hipLaunchKernelGGL(kern, dim3(problems), dim3(256), lds, s, (const kwy_c *)x, (const kwy_c *)stale, t.twH, t.twP, kind,
+                       (kwy_c *)out_old, (kwy_c *)out_new);
     if (hipGetLastError() != hipSuccess) rc = -2;
-    const size_t lds = sizeof(kwy_c) * (H + 1);
-    auto kern = kind == 3 ? k_fft_wave_local_selftest<true> : k_fft_wave_local_selftest<false>;
-    if (rc == 0 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) rc = -2;
-    if (rc == 0) {
-      hipLaunchKernelGGL(kern, dim3(problems), dim3(256), lds, s, (const kwy_c *)x, (const kwy_c *)stale, (const kwy_c *)tw,
-                         (const kwy_c *)tp, kind, (kwy_c *)out_old, (kwy_c *)out_new);
-      if (hipGetLastError() != hipSuccess) rc = -2;
-    }
   }
   if (hipStreamSynchronize(s) != hipSuccess) rc = -2;
-  (void)hipFree(tw);
   return rc;
 }

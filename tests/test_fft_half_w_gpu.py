@@ -1,4 +1,5 @@
-"""kwy_fft_inplace_half_w, the LDS transform whose first radix-8 pass knows that the packed points above H/2 are zero
+"""kwy_fft_inplace_sel_w with half = true (kwy_fft.hpp), the LDS transform whose first radix-8 pass knows that the
+packed points above H/2 are zero
 (the windows of k_d4c_body at f0 >= 8 fs / N), against kwy_fft_inplace_w on the zero-padded row, side by side in
 libkwy_selftest.so: every bin equal (adding exact zeros changes no value; np.array_equal takes -0 for +0), in the
 three shapes of the body (1024 and 2048 points on 256 threads, 4096 on 512), forward and inverse, with the closing pass

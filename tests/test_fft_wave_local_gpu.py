@@ -1,4 +1,4 @@
-"""The wave-local form of the 2048-point LDS transform (kwy_fftwl_* in kwy_device.hpp: in-place decimation in frequency
+"""The wave-local form of the 2048-point LDS transform (kwy_fftwl_* in kwy_fft.hpp: in-place decimation in frequency
 behind the first pass, two workgroup barriers per transform) against the Stockham chain it replaces in k_d4c_body<12>
 and k_d4c_bands<12>, side by side in libkwy_selftest.so on the same rows: the drained pairs lo[0..3], hi[0..3], mid of
 every thread are the same numbers (np.array_equal, which takes -0 for +0; both paths take the same first pass for a kind

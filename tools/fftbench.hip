@@ -4,7 +4,7 @@
 #include <stdlib.h>
 #include <math.h>
 #include <vector>
-#include "../kwiiyatta_amd/csrc/kwy_device.hpp"
+#include "../kwiiyatta_amd/csrc/kwy_fft.hpp"
 
 // ---------------------------------------------------------------------------------------------------------------
 // Round 4 experiment, measured and NOT adopted: a wave-local 2048-point transform with two
@@ -506,7 +506,7 @@ int main() {
   const int L = 11, H = 1 << L;
   std::vector<kwy_c> h(H);
   for (int k = 0; k < H; ++k) { double a = -2.0 * M_PI * k / H; h[k].x = cos(a); h[k].y = sin(a); }
-  // every twiddle table is followed by the powers table of its length's stride-64 pass (kwy_device.hpp: kwy_tw_powers)
+  // every twiddle table is followed by the powers table of its length's stride-64 pass (kwy_fft.hpp: kwy_tw_powers)
   kwy_c *tw; CK(hipMalloc(&tw, sizeof(kwy_c) * (H + KWY_TWP_ENTRY * KWY_TWP_ENTRIES(L)))); CK(hipMemcpy(tw, h.data(), sizeof(kwy_c) * H, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_twiddle_powers_fill<0>, dim3(1), dim3(64), 0, 0, (const kwy_c *)tw, tw + H, KWY_TWP_ENTRIES(L));
   {
