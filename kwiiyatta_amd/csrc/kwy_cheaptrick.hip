@@ -15,6 +15,7 @@
 // loads its draws from the device's table of it (jump-ahead beyond the table;
 // see kwy_device.hpp, kwy_ctx.hip).
 #include "kwy_internal.hpp"
+#include "kwy_mfma.hpp"
 
 #define CT_EPS 0.00000000000000022204460492503131
 #define CT_DEFAULT_F0 500.0
@@ -316,7 +317,6 @@ __global__ __launch_bounds__(KWY_THREADS, LOG2N <= 11 ? 5 : 4) void k_cheaptrick
 // mc[t][j] = sum_n cep[t][n] F[n][j]: pysptk's frequency transform (freqt) of the cepstra as an f64 matrix product, one
 // wavefront per 16 frames (v_mfma_f64_16x16x4_f64; A = 16 frames x 4 cepstral indices, B = F, 16 coefficients per
 // block).  F: [ncut][64] (kwy_mcep.hip), L2-resident.  Row t of the launch belongs to the utterance batch.find(t).
-typedef double ct_v4f64 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(KWY_THREADS) void k_cep2mc(ct_batch batch, ct_mcep mcep, int order,
                                                        const double *__restrict__ F) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -326,9 +326,9 @@ __global__ __launch_bounds__(KWY_THREADS) void k_cep2mc(ct_batch batch, ct_mcep 
   if (t0 >= rows) return;
   const int nblk = (order + 16) / 16;                  // 16-coefficient blocks: <= 4
   const double *__restrict__ crow = mcep.cep + (size_t)min(t0 + ar, rows - 1) * mcep.ncs;
-  ct_v4f64 acc[4];
+  kwy_v4f64 acc[4];
 #pragma unroll
-  for (int b = 0; b < 4; ++b) acc[b] = ct_v4f64{0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < 4; ++b) acc[b] = kwy_v4f64{0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
   for (int ks = 0; ks < mcep.ncs / 4; ++ks) {
     const int n = 4 * ks + ak;

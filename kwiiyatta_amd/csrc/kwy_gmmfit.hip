@@ -18,9 +18,8 @@
 // rate of gfx950 equals its f64 vector rate).
 #include <math.h>
 
-#include <type_traits>
-
 #include "kwy_internal.hpp"
+#include "kwy_mfma.hpp"
 
 
 __host__ __device__ static inline size_t fit_tri(int D) { return (size_t)D * (D + 1) / 2; }
@@ -100,8 +99,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_fit_prec(const double *__restri
 // sub-tiles (2 x 36 doubles per lane), and every B fragment it reads feeds two MFMAs.  Per 16-column
 // block of Z only the k-steps up to the block's diagonal are issued (180 instead of 324 fragments for
 // D = 144).  The second wavefront of each SIMD computes while the first one waits for its rows.
-// Lane map: A[row l&15][k l>>4], B[k l>>4][col l&15], D[row (l>>4)+4r][col l&15].
-typedef double fit_v4f64 __attribute__((ext_vector_type(4)));
+// The tile's parts and the lane map: kwy_mfma.hpp.
 #define FIT_LP_NT 512
 #define FIT_LP_COLS 3   // feature columns per lane when staging a row (k_fit_cov): D <= 192
 
@@ -111,10 +109,10 @@ __global__ __launch_bounds__(FIT_LP_NT) void k_fit_logprob(const double *__restr
                                                           const double *__restrict__ Zp,
                                                           const double *__restrict__ cst,
                                                           double *__restrict__ wlp) {
-  constexpr int KS = 4 * NBLK, NFRAG = 2 * NBLK * (NBLK + 1);
-  extern __shared__ double sm[];
-  double *zf = sm;                  // NFRAG x 64: fragment (nb, ks), ks < 4 nb + 4, at 2 nb (nb + 1) + ks
-  double *cs = zf + NFRAG * 64;     // 16 NBLK: Z mu
+  constexpr int KS = 4 * NBLK;
+  extern __shared__ double sm[];               // kwy_tri_lds_doubles(NBLK)
+  double *zf = sm;                             // the fragments of Z
+  double *cs = zf + kwy_tri_frags(NBLK) * 64;  // 16 NBLK: Z mu
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int ar = lane & 15, ak = lane >> 4;
   int m, split;
@@ -128,14 +126,7 @@ __global__ __launch_bounds__(FIT_LP_NT) void k_fit_logprob(const double *__restr
   }
   const int nt = (int)fit_tri(D);
   const double *zp = Zp + (size_t)m * nt, *mu = means + (size_t)m * D;
-  for (int idx = tid; idx < NFRAG * 64; idx += FIT_LP_NT) {
-    const int f = idx >> 6, l = idx & 63;
-    int nb = 0;
-    while (2 * (nb + 1) * (nb + 2) <= f) ++nb;
-    const int ks = f - 2 * nb * (nb + 1);
-    const int j = 16 * nb + (l & 15), i = 4 * ks + (l >> 4);
-    zf[idx] = (j < D && i <= j) ? zp[tri(j, i)] : 0.0;
-  }
+  kwy_tri_fill<NBLK, FIT_LP_NT>(zf, D, tid, [&](int j, int i) { return zp[tri(j, i)]; });
   for (int j = tid; j < 16 * NBLK; j += FIT_LP_NT) {
     double c = 0.0;
     if (j < D)
@@ -167,7 +158,7 @@ __global__ __launch_bounds__(FIT_LP_NT) void k_fit_logprob(const double *__restr
     double q0[4] = {0.0, 0.0, 0.0, 0.0}, q1[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int nb = 0; nb < NBLK; ++nb) {
-      fit_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+      kwy_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
       const double *frag = zf + (2 * nb * (nb + 1)) * 64 + lane;
 #pragma unroll
       for (int ks = 0; ks < 4 * nb + 4; ++ks) {
@@ -184,14 +175,7 @@ __global__ __launch_bounds__(FIT_LP_NT) void k_fit_logprob(const double *__restr
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double v = q0[r], w = q1[r];
-      v += kwy_dpp_f64<0x111>(v); w += kwy_dpp_f64<0x111>(w);
-      v += kwy_dpp_f64<0x112>(v); w += kwy_dpp_f64<0x112>(w);
-      v += kwy_dpp_f64<0x114>(v); w += kwy_dpp_f64<0x114>(w);
-      v += kwy_dpp_f64<0x118>(v); w += kwy_dpp_f64<0x118>(w);
-      q0[r] = v; q1[r] = w;
-    }
+    for (int r = 0; r < 4; ++r) kwy_row_sum15(q0[r], q1[r]);
     if (ar == 15) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -207,14 +191,6 @@ __global__ __launch_bounds__(FIT_LP_NT) void k_fit_logprob(const double *__restr
 // per-block sums of the frame log-likelihoods go to ll_part[blockIdx.x].
 // Sixteen lanes (one DPP row) share a frame, lane c of the row holds mixtures c, c+16, ...: a
 // wavefront's loads cover four whole rows of wlp, and max and sum are rotations within the row.
-template <class OP>
-__device__ __forceinline__ double fit_row_allreduce(double v, OP op) {
-  v = op(v, kwy_dpp_f64<0x121>(v));   // row_ror:1
-  v = op(v, kwy_dpp_f64<0x122>(v));
-  v = op(v, kwy_dpp_f64<0x124>(v));
-  v = op(v, kwy_dpp_f64<0x128>(v));
-  return v;
-}
 #define FIT_RESP_Q 16   // mixtures per lane: M <= 256
 
 __global__ __launch_bounds__(KWY_THREADS) void k_fit_resp(double *__restrict__ wlp, int64_t n, int M,
@@ -234,12 +210,12 @@ __global__ __launch_bounds__(KWY_THREADS) void k_fit_resp(double *__restrict__ w
       v[q] = (live && m < M) ? w[m] : -INFINITY;
       mx = fmax(mx, v[q]);
     }
-    mx = fit_row_allreduce(mx, [](double a, double b) { return fmax(a, b); });
+    mx = kwy_row_allreduce(mx, [](double a, double b) { return fmax(a, b); });
     double sm = 0.0;
 #pragma unroll
     for (int q = 0; q < FIT_RESP_Q; ++q)
       if (16 * q < M) sm += exp(v[q] - mx);
-    sm = fit_row_allreduce(sm, [](double a, double b) { return a + b; });
+    sm = kwy_row_allreduce(sm, [](double a, double b) { return a + b; });
     const double lse = mx + log(sm);
 #pragma unroll
     for (int q = 0; q < FIT_RESP_Q; ++q) {
@@ -274,9 +250,9 @@ __global__ __launch_bounds__(KWY_THREADS) void k_fit_sums(const double *__restri
   const int mrow = min(16 * rb + ar, M - 1);
   const bool mok = 16 * rb + ar < M;
   const int clast = min(16 * (NBLK - 1) + ar, D - 1);
-  fit_v4f64 acc[NBLK];
+  kwy_v4f64 acc[NBLK];
 #pragma unroll
-  for (int b = 0; b < NBLK; ++b) acc[b] = fit_v4f64{0.0, 0.0, 0.0, 0.0};
+  for (int b = 0; b < NBLK; ++b) acc[b] = kwy_v4f64{0.0, 0.0, 0.0, 0.0};
   double sumr = 0.0;
   const int64_t nks = (r1 - r0 + 3) / 4;
   double xs[FIT_SUM_PF][NBLK], as[FIT_SUM_PF];
@@ -351,18 +327,9 @@ constexpr bool fit_blk_uses(int nblk, int w, int b, bool as_row) {
   return false;
 }
 
-// compile-time loop: f(std::integral_constant<int, I>) for I in [I0, I1)
-template <int I0, int I1, class F>
-__device__ __forceinline__ void fit_static_for(F &&f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    fit_static_for<I0 + 1, I1>(f);
-  }
-}
-
 template <int NBLK, int W, int CMAX>
 __device__ __forceinline__ void fit_cov_tile(const double *__restrict__ tile, const double *__restrict__ rt, int ZS,
-                                             int ar, int ak, double r_min, fit_v4f64 (&acc)[CMAX]) {
+                                             int ar, int ak, double r_min, kwy_v4f64 (&acc)[CMAX]) {
   constexpr int E0 = fit_blk_lo(NBLK, W), E1 = fit_blk_lo(NBLK, W + 1);
 #pragma unroll 2
   for (int ks = 0; ks < FIT_COV_TILE / 4; ++ks) {
@@ -376,13 +343,13 @@ __device__ __forceinline__ void fit_cov_tile(const double *__restrict__ tile, co
     // this sense -- most frames belong to one or two of the 64 components.
     if (__ballot(rr >= r_min) == 0) continue;
     double dv[NBLK], av[NBLK];
-    fit_static_for<0, NBLK>([&](auto bc) {
+    kwy_static_for<0, NBLK>([&](auto bc) {
       constexpr int b = decltype(bc)::value;
       constexpr bool as_row = fit_blk_uses(NBLK, W, b, true), as_col = fit_blk_uses(NBLK, W, b, false);
       if constexpr (as_row || as_col) dv[b] = drow[16 * b];
       if constexpr (as_row) av[b] = rr * dv[b];
     });
-    fit_static_for<E0, E1>([&](auto ec) {
+    kwy_static_for<E0, E1>([&](auto ec) {
       constexpr int e = decltype(ec)::value;
       constexpr int I = fit_blk_row(e), J = fit_blk_col(e);
       acc[e - E0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[I], dv[J], acc[e - E0], 0, 0, 0);
@@ -392,9 +359,9 @@ __device__ __forceinline__ void fit_cov_tile(const double *__restrict__ tile, co
 
 template <int NBLK, int W, int CMAX>
 __device__ __forceinline__ void fit_cov_store(double *__restrict__ out, int D, int ar, int ak,
-                                              const fit_v4f64 (&acc)[CMAX]) {
+                                              const kwy_v4f64 (&acc)[CMAX]) {
   constexpr int E0 = fit_blk_lo(NBLK, W), E1 = fit_blk_lo(NBLK, W + 1);
-  fit_static_for<E0, E1>([&](auto ec) {
+  kwy_static_for<E0, E1>([&](auto ec) {
     constexpr int e = decltype(ec)::value;
     constexpr int I = fit_blk_row(e), J = fit_blk_col(e);
 #pragma unroll
@@ -497,9 +464,9 @@ __global__ __launch_bounds__(KWY_THREADS, 2) void k_fit_cov(const double *__rest
   double muv[FIT_LP_COLS];
 #pragma unroll
   for (int c = 0; c < FIT_LP_COLS; ++c) muv[c] = (lane + 64 * c < D) ? mu[lane + 64 * c] : 0.0;
-  fit_v4f64 acc[CMAX];
+  kwy_v4f64 acc[CMAX];
 #pragma unroll
-  for (int a = 0; a < CMAX; ++a) acc[a] = fit_v4f64{0.0, 0.0, 0.0, 0.0};
+  for (int a = 0; a < CMAX; ++a) acc[a] = kwy_v4f64{0.0, 0.0, 0.0, 0.0};
   // this wavefront stages rows ROWS*w .. ROWS*w+ROWS-1 of every tile: fetched one tile ahead into registers
   double xv[ROWS][FIT_LP_COLS], rv = 0.0;
   // tile j of the mixture = the listed groups 8 j .. 8 j + 7 (four frames each; entries beyond the list: no frames)
@@ -642,7 +609,7 @@ static int fit_lp_splits(int64_t n, int M) {
 template <int NBLK>
 static int fit_lp_launch(kwy_ctx *ctx, const double *X, int64_t n, int D, int M, int nsplit, const double *means,
                          const double *Zp, const double *cst, double *wlp) {
-  const size_t lds = sizeof(double) * ((size_t)2 * NBLK * (NBLK + 1) * 64 + 16 * NBLK);
+  const size_t lds = sizeof(double) * kwy_tri_lds_doubles(NBLK);
   KWY_HIP(hipFuncSetAttribute((const void *)k_fit_logprob<NBLK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_PROF(ctx, "k_fit_logprob", hipLaunchKernelGGL(k_fit_logprob<NBLK>, dim3((unsigned)(M * nsplit)), dim3(FIT_LP_NT), lds, ctx->stream, X, n, D, M, nsplit, means, Zp, cst, wlp));
   return KWY_OK;
@@ -702,18 +669,9 @@ extern "C" int kwy_gmm_em_estep_dev(kwy_ctx *ctx, const double *X, int64_t n, in
   hipLaunchKernelGGL(k_fit_prec, dim3(M), dim3(KWY_THREADS), lds_prec, ctx->stream, weights, covs, D, Zp, cst,
                      status_out);
   const int nsplit = fit_lp_splits(n, M);
-  switch ((D + 15) / 16) {
-    case 1: KWY_TRY(fit_lp_launch<1>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 2: KWY_TRY(fit_lp_launch<2>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 3: KWY_TRY(fit_lp_launch<3>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 4: KWY_TRY(fit_lp_launch<4>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 5: KWY_TRY(fit_lp_launch<5>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 6: KWY_TRY(fit_lp_launch<6>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 7: KWY_TRY(fit_lp_launch<7>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 8: KWY_TRY(fit_lp_launch<8>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    case 9: KWY_TRY(fit_lp_launch<9>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-    default: KWY_TRY(fit_lp_launch<10>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp)); break;
-  }
+  KWY_TRY(kwy_with_blocks<10>((D + 15) / 16, [&](auto nb) {
+    return fit_lp_launch<decltype(nb)::value>(ctx, X, n, D, M, nsplit, means, Zp, cst, resp);
+  }));
   return kwy_fit_resp(ctx, resp, n, M, loglik_parts);
 }
 
@@ -735,18 +693,9 @@ int kwy_fit_sums_gated(kwy_ctx *ctx, const double *X, int64_t n, int D, int M, c
   KWY_TRY(kwy_arena_begin(ctx, kwy_pad(sizeof(double) * (size_t)nchunks * len)));
   double *part = kwy_arena<double>(ctx, (size_t)nchunks * len);
   if (!part) { ctx->err = "gmm_em_sums: scratch"; return KWY_ENOMEM; }
-  switch ((D + 15) / 16) {
-    case 1: fit_sums_launch<1>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 2: fit_sums_launch<2>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 3: fit_sums_launch<3>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 4: fit_sums_launch<4>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 5: fit_sums_launch<5>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 6: fit_sums_launch<6>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 7: fit_sums_launch<7>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 8: fit_sums_launch<8>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    case 9: fit_sums_launch<9>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-    default: fit_sums_launch<10>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels); break;
-  }
+  kwy_with_blocks<10>((D + 15) / 16, [&](auto nb) {
+    fit_sums_launch<decltype(nb)::value>(ctx, X, resp, n, D, M, rows_per_chunk, nchunks, part, gate, labels);
+  });
   hipLaunchKernelGGL(k_fit_reduce, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, part, nchunks, len,
                      stats, gate);
   KWY_HIP(hipGetLastError());
@@ -816,18 +765,9 @@ extern "C" int kwy_gmm_em_cov_stats_dev(kwy_ctx *ctx, const double *X, int64_t n
                      (size_t)M * FIT_ACT_GROUPS, ctx->stream, resp, n, D, M, stats, ntiles, act);
   hipLaunchKernelGGL(k_fit_active_list, dim3((unsigned)M), dim3(KWY_THREADS), 0, ctx->stream, act, ntiles, list, count);
   KWY_HIP(hipGetLastError());
-  switch ((D + 15) / 16) {
-    case 1: KWY_TRY(fit_cov_launch<1>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 2: KWY_TRY(fit_cov_launch<2>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 3: KWY_TRY(fit_cov_launch<3>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 4: KWY_TRY(fit_cov_launch<4>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 5: KWY_TRY(fit_cov_launch<5>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 6: KWY_TRY(fit_cov_launch<6>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 7: KWY_TRY(fit_cov_launch<7>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 8: KWY_TRY(fit_cov_launch<8>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    case 9: KWY_TRY(fit_cov_launch<9>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-    default: KWY_TRY(fit_cov_launch<10>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit)); break;
-  }
+  KWY_TRY(kwy_with_blocks<10>((D + 15) / 16, [&](auto nb) {
+    return fit_cov_launch<decltype(nb)::value>(ctx, X, resp, n, D, M, means, stats, list, count, ntiles, cpart, nsplit);
+  }));
   hipLaunchKernelGGL(k_fit_reduce_sym, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, cpart, nsplit, D,
                      M, sxx);
   KWY_HIP(hipGetLastError());

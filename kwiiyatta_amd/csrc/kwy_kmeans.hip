@@ -22,22 +22,12 @@
 #include <math.h>
 
 #include "kwy_internal.hpp"
-
-typedef double km_v4f64 __attribute__((ext_vector_type(4)));
+#include "kwy_mfma.hpp"
 
 #define KM_COLS 3          // columns per lane, one wavefront per row: D <= 192
 #define KM_K16 12          // columns per lane, 16 lanes per row:      D <= 192
 #define KM_MAXL 8          // candidates per k-means++ step (2 + ln(n_clusters): n_clusters <= 403)
 #define KM_CHUNK 2048      // elements per workgroup in the chunk sums
-
-template <class OP>
-__device__ __forceinline__ double km_row_allreduce(double v, OP op) {   // over the 16 lanes of a DPP row
-  v = op(v, kwy_dpp_f64<0x121>(v));   // row_ror:1
-  v = op(v, kwy_dpp_f64<0x122>(v));
-  v = op(v, kwy_dpp_f64<0x124>(v));
-  v = op(v, kwy_dpp_f64<0x128>(v));
-  return v;
-}
 
 // part[chunk][0][i] = sum_t (x[t][i] - shift[i]), part[chunk][1][i] = sum_t (x[t][i] - shift[i])^2
 __global__ __launch_bounds__(KWY_THREADS) void k_km_colstats(const double *__restrict__ X, int64_t n, int D,
@@ -155,7 +145,7 @@ __global__ __launch_bounds__(KWY_THREADS) void k_km_pp_dist(const double *__rest
           const int i = ar + 16 * k;
           if (i < D) dot += x[k] * y[c * D + i];
         }
-        dot = km_row_allreduce(dot, [](double a, double b) { return a + b; });
+        dot = kwy_row_allreduce(dot, [](double a, double b) { return a + b; });
         double d = (-2.0 * dot + ysq[c]) + xs;
         d = fmax(d, 0.0);
         d = fmin(cl, d);
@@ -276,7 +266,7 @@ __global__ __launch_bounds__(KM_AS_NT) void k_km_assign(const double *__restrict
     centers += (size_t)(state[1] & 1) * M * D;
   }
   constexpr int KS = 4 * NBLK;
-  extern __shared__ double sm[];
+  extern __shared__ double sm[];    // kwy_km_lds_doubles(NBLK)
   double *cf = sm;                  // 4 x KS x 64
   double *cn = cf + 4 * KS * 64;    // 64: |c|^2, +inf beyond M
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -323,7 +313,7 @@ __global__ __launch_bounds__(KM_AS_NT) void k_km_assign(const double *__restrict
 #pragma unroll
     for (int r = 0; r < 4; ++r) { bv0[r] = bv1[r] = INFINITY; bi0[r] = bi1[r] = 0x7fffffff; }
     for (int mb = 0; mb < nmb; ++mb) {
-      km_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+      kwy_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
       const double *frag = cf + (size_t)mb * KS * 64 + lane;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
@@ -343,23 +333,10 @@ __global__ __launch_bounds__(KM_AS_NT) void k_km_assign(const double *__restrict
     // over the 16 lanes of the row: (value, centre) lexicographic minimum
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        double ov0, ov1;
-        int oi0, oi1;
-        switch (s) {
-          case 0: ov0 = kwy_dpp_f64<0x121>(bv0[r]); oi0 = (int)kwy_dpp_u32<0x121>((uint32_t)bi0[r]);
-                  ov1 = kwy_dpp_f64<0x121>(bv1[r]); oi1 = (int)kwy_dpp_u32<0x121>((uint32_t)bi1[r]); break;
-          case 1: ov0 = kwy_dpp_f64<0x122>(bv0[r]); oi0 = (int)kwy_dpp_u32<0x122>((uint32_t)bi0[r]);
-                  ov1 = kwy_dpp_f64<0x122>(bv1[r]); oi1 = (int)kwy_dpp_u32<0x122>((uint32_t)bi1[r]); break;
-          case 2: ov0 = kwy_dpp_f64<0x124>(bv0[r]); oi0 = (int)kwy_dpp_u32<0x124>((uint32_t)bi0[r]);
-                  ov1 = kwy_dpp_f64<0x124>(bv1[r]); oi1 = (int)kwy_dpp_u32<0x124>((uint32_t)bi1[r]); break;
-          default: ov0 = kwy_dpp_f64<0x128>(bv0[r]); oi0 = (int)kwy_dpp_u32<0x128>((uint32_t)bi0[r]);
-                   ov1 = kwy_dpp_f64<0x128>(bv1[r]); oi1 = (int)kwy_dpp_u32<0x128>((uint32_t)bi1[r]); break;
-        }
-        if (ov0 < bv0[r] || (ov0 == bv0[r] && oi0 < bi0[r])) { bv0[r] = ov0; bi0[r] = oi0; }
-        if (ov1 < bv1[r] || (ov1 == bv1[r] && oi1 < bi1[r])) { bv1[r] = ov1; bi1[r] = oi1; }
-      }
+      const kwy_val_idx b0 = kwy_row_allreduce(kwy_val_idx{bv0[r], bi0[r]}, kwy_lex_min);
+      const kwy_val_idx b1 = kwy_row_allreduce(kwy_val_idx{bv1[r], bi1[r]}, kwy_lex_min);
+      bv0[r] = b0.v; bi0[r] = b0.i;
+      bv1[r] = b1.v; bi1[r] = b1.i;
     }
     if (ar == 0) {
 #pragma unroll
@@ -531,7 +508,7 @@ extern "C" int kwy_km_pp_pick_dev(kwy_ctx *ctx, const double *v, int64_t n, cons
 template <int NBLK>
 static int km_assign_launch(kwy_ctx *ctx, const double *X, int64_t n, int D, int M, int nsplit, const double *centers,
                             double *pv, int *pi, const long long *state) {
-  const size_t lds = sizeof(double) * ((size_t)4 * 4 * NBLK * 64 + 64);
+  const size_t lds = sizeof(double) * kwy_km_lds_doubles(NBLK);
   KWY_HIP(hipFuncSetAttribute((const void *)k_km_assign<NBLK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int ngroups = (M + 63) / 64;
   KWY_PROF(ctx, "k_km_assign", hipLaunchKernelGGL(k_km_assign<NBLK>, dim3((unsigned)(ngroups * nsplit)), dim3(KM_AS_NT), lds, ctx->stream, X, n, D, M, nsplit, centers, pv, pi, state));
@@ -557,18 +534,9 @@ static int km_assign_core(kwy_ctx *ctx, const double *X, int64_t n, int D, const
   const int64_t ntiles = (n + 255) / 256;
   int nsplit = (int)min(ntiles, (int64_t)((512 + ngroups - 1) / ngroups));
   if (nsplit < 1) nsplit = 1;
-  switch ((D + 15) / 16) {
-    case 1: KWY_TRY(km_assign_launch<1>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 2: KWY_TRY(km_assign_launch<2>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 3: KWY_TRY(km_assign_launch<3>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 4: KWY_TRY(km_assign_launch<4>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 5: KWY_TRY(km_assign_launch<5>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 6: KWY_TRY(km_assign_launch<6>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 7: KWY_TRY(km_assign_launch<7>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 8: KWY_TRY(km_assign_launch<8>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    case 9: KWY_TRY(km_assign_launch<9>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-    default: KWY_TRY(km_assign_launch<10>(ctx, X, n, D, M, nsplit, centers, pv, pi, state)); break;
-  }
+  KWY_TRY(kwy_with_blocks<10>((D + 15) / 16, [&](auto nb) {
+    return km_assign_launch<decltype(nb)::value>(ctx, X, n, D, M, nsplit, centers, pv, pi, state);
+  }));
   KWY_HIP(hipMemsetAsync(changed, 0, sizeof(unsigned long long), ctx->stream));   // (a stopped loop has its count in state[2])
   hipLaunchKernelGGL(k_km_labels, dim3((unsigned)((n + KWY_THREADS - 1) / KWY_THREADS)), dim3(KWY_THREADS), 0,
                      ctx->stream, pv, pi, ngroups, n, M, labels, resp, changed, state);

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "kwy_internal.hpp"
+#include "kwy_mfma.hpp"
 
 #define MC_MAX_ORDER 63  // order+1 <= 64 coefficients
 
@@ -161,7 +162,6 @@ __global__ __launch_bounds__(KWY_THREADS) void k_sp2mc_dense(const double *__res
   }
 }
 
-typedef double mc_v4f64 __attribute__((ext_vector_type(4)));
 // mc2sp: G2 is [order+1][K].
 // The dense map as one f64 MFMA product per 16 frames x 16 bins (v_mfma_f64_16x16x4_f64: A = the frames'
 // coefficients, B = G2, order + 1 padded to a multiple of 4 in the k direction), exp applied to the accumulators.
@@ -192,9 +192,9 @@ __global__ __launch_bounds__(KWY_THREADS) void k_mc2sp_mfma(const double *__rest
   __shared__ double stage[KWY_WAVES][16][MC2_STAGE_STRIDE];
   for (int g = blockIdx.y * KWY_WAVES + wv; g < ngroup; g += gridDim.y * KWY_WAVES) {
     const int g0 = g * (16 * MC2_TILES);
-    mc_v4f64 acc[MC2_TILES];
+    kwy_v4f64 acc[MC2_TILES];
 #pragma unroll
-    for (int q = 0; q < MC2_TILES; ++q) acc[q] = mc_v4f64{0.0, 0.0, 0.0, 0.0};
+    for (int q = 0; q < MC2_TILES; ++q) acc[q] = kwy_v4f64{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int ks = 0; ks < MC2_KSTEPS; ++ks) {
       if (ks < ksteps) {

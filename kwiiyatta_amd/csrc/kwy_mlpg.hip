@@ -10,7 +10,7 @@
 //                A = S_yx S_xx^-1 and its transpose, diagonal conditional variance, log-normaliser
 //   k_delta      static + delta + delta-delta features (3-tap correlations)
 //   k_gmm_logp_frag  (frame tile x mixture) workgroups: ||L^-1 (x - mu)||^2 on the f64 MFMA, L^-1 in fragment order in
-//                LDS, the frames in registers (k_gmm_logp: both operands from LDS, for features wider than 96)
+//                LDS, the frames in registers (profiled as "k_gmm_logp")
 //   k_gmm_cond   four frames per wavefront: arg-max mixture, conditional mean E (from A transposed) and variance D
 //   k_mlpg_build per (frame, dim): the pentadiagonal normal equations W'PW, W'P mu
 //   k_mlpg_chunks / k_mlpg_finish  per static dim: banded Cholesky, partitioned into chunks (nested dissection)
@@ -24,12 +24,10 @@
 
 #include <algorithm>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "kwy_internal.hpp"
-
-#define ML_TILE 64  // frames per k_gmm_logp workgroup
+#include "kwy_mfma.hpp"
 
 struct ml_dims { int d, D, M; int64_t T; };
 
@@ -178,147 +176,35 @@ __global__ void k_delta(ml_batch b, ml_dims dm, double *__restrict__ X) {
 }
 
 // ---- log p(x_t | m) up to the shared constant -------------------------------------------
-// || Z_m (x_t - mu_m) ||^2 for a tile of 64 frames and one mixture is a 64 x D times D x D
-// (lower-triangular) product: the one MFMA-shaped piece of the conversion path.  One workgroup
-// keeps Z_m (zero above the diagonal, rows padded) in LDS and walks over frame tiles; wavefront w
-// owns frames 16w..16w+15 and, per 16-column block of Z, runs v_mfma_f64_16x16x4_f64 over the
-// k-steps that reach the block's diagonal (58 instead of 90 MFMAs per wavefront and tile for D = 72).
-// Lane map of that instruction: A[row l&15][k l>>4], B[k l>>4][col l&15], D[row (l>>4)+4r][col l&15].
-typedef double ml_v4f64 __attribute__((ext_vector_type(4)));
+// || Z_m (x_t - mu_m) ||^2 for a tile of frames and one mixture is a frames x D times D x D (lower-triangular) product:
+// the one MFMA-shaped piece of the arg-max conversion path, with the frame operand in registers (the form of
+// k_fit_logprob, kwy_gmmfit.hip; fed from LDS alone the MFMA is LDS-bound).  Z_m (zero above the diagonal) is expanded
+// once per workgroup into MFMA-fragment order (kwy_mfma.hpp: one conflict-free 512-byte read per operand, 29 KB for
+// D = 72).  A wavefront takes 32 frames: x - mu_x of two 16-frame sub-tiles goes straight from global memory into the A
+// registers (2 x Kp/4 doubles per lane), and every B fragment feeds two independent accumulator chains.  Per
+// logp[t][m]: per 16-column block nb the k-steps min(Kp/4, 4 (nb + 1)) that reach the block's diagonal, from a zero
+// accumulator (58 instead of 90 MFMAs per 16 frames for D = 72), the squares summed in ascending nb, then the row sum.
+// NBLK = column blocks (D <= 16 NBLK), NW = wavefronts per workgroup.
+__host__ __device__ constexpr int ml_kp(int D) { return (D + 3) & ~3; }
+__host__ __device__ constexpr int ml_np(int D) { return (D + 15) & ~15; }
 
-__host__ __device__ static inline int ml_kp(int D) { return (D + 3) & ~3; }
-__host__ __device__ static inline int ml_np(int D) { return (D + 15) & ~15; }
-
-// NW wavefronts per workgroup, 16 frames each (round 4: eight where the LDS allows -- a workgroup fills a CU alone, so
-// its wavefronts are all the latency hiding there is: 0.68 -> see DESIGN.md section 5 for a wave of 35 216 frames)
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void k_gmm_logp(const double *__restrict__ X, ml_dims dm,
-                                                         const double *__restrict__ model,
-                                                         double *__restrict__ logp) {
-  extern __shared__ double smem[];
-  const int D = dm.D, Kp = ml_kp(D), NP = ml_np(D), ZS = Kp + 1;
-  double *Zs = smem;             // NP x ZS
-  constexpr int TILE = 16 * NW;
-  double *dts = Zs + NP * ZS;    // TILE x ZS
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, m = blockIdx.y;
-  const double *mod = model + (size_t)m * ml_model_stride(D);
-  const double *mZ = mod, *mux = mod + 2 * D * D;
-  const double cst = mod[2 * D * D + 3 * D];
-  for (int jb = 4 * wv; jb < NP; jb += 4 * NW) {  // four rows per wavefront and step, loads batched
-    double z0[4], z1[4];
-    const int i0 = lane, i1 = lane + 64;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = jb + r;
-      z0[r] = (j < D && i0 <= j) ? mZ[j * D + i0] : 0.0;
-      z1[r] = (j < D && i1 <= j) ? mZ[j * D + i1] : 0.0;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = jb + r;
-      if (j < NP) {
-        if (i0 < Kp) Zs[j * ZS + i0] = z0[r];
-        if (i1 < Kp) Zs[j * ZS + i1] = z1[r];
-        for (int i = lane + 128; i < Kp; i += 64) Zs[j * ZS + i] = (j < D && i <= j) ? mZ[j * D + i] : 0.0;
-      }
-    }
-  }
-  const int ar = lane & 15, ak = lane >> 4;
-  const int64_t ntiles = (dm.T + TILE - 1) / TILE;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t t0 = tile * TILE;
-    __syncthreads();  // the previous tile has been consumed (and Zs is complete)
-    // every wavefront stages the 16 frames it multiplies itself
-    {
-      // all loads of the wavefront's 16 rows in flight before the first store (two columns per lane)
-      const int i0 = lane, i1 = lane + 64;
-      const double mu0 = i0 < D ? mux[i0] : 0.0, mu1 = i1 < D ? mux[i1] : 0.0;
-      double v0[16], v1[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t t = t0 + 16 * wv + r;
-        v0[r] = (t < dm.T && i0 < D) ? X[t * D + i0] : mu0;
-        v1[r] = (t < dm.T && i1 < D) ? X[t * D + i1] : mu1;
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        double *row = dts + (16 * wv + r) * ZS;
-        if (i0 < Kp) row[i0] = v0[r] - mu0;
-        if (i1 < Kp) row[i1] = v1[r] - mu1;
-      }
-      for (int i = lane + 128; i < Kp; i += 64)   // wider features: the remaining columns, plainly
-        for (int r = 0; r < 16; ++r) {
-          const int64_t t = t0 + 16 * wv + r;
-          dts[(16 * wv + r) * ZS + i] = (t < dm.T && i < D) ? X[t * D + i] - mux[i] : 0.0;
-        }
-    }
-    __syncthreads();
-    double q[4] = {0.0, 0.0, 0.0, 0.0};
-    const double *arow = dts + (16 * wv + ar) * ZS + ak;
-    for (int nt = 0; nt < NP / 16; ++nt) {
-      ml_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-      const int ksteps = min(Kp / 4, 4 * (nt + 1));
-      const double *brow = Zs + (16 * nt + ar) * ZS + ak;
-      // (built with -mllvm -amdgpu-mfma-vgpr-form=1: the accumulator stays in VGPRs across the loop
-      // instead of being copied to and from AGPRs around every MFMA)
-#pragma unroll 4
-      for (int ks = 0; ks < ksteps; ++ks)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(arow[4 * ks], brow[4 * ks], acc, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) q[r] += acc[r] * acc[r];
-    }
-    // sum over the 16 columns held by the lanes of one row group: lane 15 of the group ends up with the total
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double v = q[r];
-      v += kwy_dpp_f64<0x111>(v);
-      v += kwy_dpp_f64<0x112>(v);
-      v += kwy_dpp_f64<0x114>(v);
-      v += kwy_dpp_f64<0x118>(v);
-      q[r] = v;
-    }
-    if (ar == 15) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t t = t0 + 16 * wv + ak + 4 * r;
-        if (t < dm.T) logp[t * dm.M + m] = cst - 0.5 * q[r];
-      }
-    }
-  }
-}
-
-// The same product with the frame operand in registers (the form of k_fit_logprob, kwy_gmmfit.hip): fed from LDS alone
-// the MFMA is LDS-bound.  Z_m is expanded once per workgroup into MFMA-fragment order -- fragment (nb, ks), ks < 4 nb + 4,
-// at 2 nb (nb + 1) + ks holds the 64 lane values of the B operand of column block nb and k-step ks, zeros above the
-// diagonal: one conflict-free 512-byte read per operand, 29 KB for D = 72 instead of 121 KB of rows.  A wavefront takes
-// 32 frames: x - mu_x of two 16-frame sub-tiles goes straight from global memory into the A registers (2 x Kp/4
-// doubles per lane), and every B fragment feeds two independent accumulator chains.  Per logp[t][m] the operations and
-// their order are those of k_gmm_logp: the same k-steps min(Kp/4, 4 (nb + 1)) from a zero accumulator, the squares
-// summed in ascending nb, the same row sum.  NBLK = column blocks (D <= 16 NBLK), NW = wavefronts per workgroup.
 #define ML_FRAG_MAXBLK 6    // D <= 96.  The fragments would fit the LDS up to nine blocks (D = 144, 92 KB), but k_gmm_prep
-                            // holds three D x D matrices in LDS and admits D <= 82: wider instances could not be reached or tested
+                            // holds three D x D matrices in LDS and admits D <= 82 (checked where ml_prep_lds is defined)
 template <int NBLK, int NW>
 __global__ __launch_bounds__(64 * NW) void k_gmm_logp_frag(const double *__restrict__ X, ml_dims dm,
                                                           const double *__restrict__ model,
                                                           double *__restrict__ logp) {
-  constexpr int KS = 4 * NBLK, NFRAG = 2 * NBLK * (NBLK + 1), TILE = 32 * NW;
-  extern __shared__ double smem[];
-  double *zf = smem;                // NFRAG x 64
-  double *mus = zf + NFRAG * 64;    // 16 NBLK: mu_x, zero beyond D
+  constexpr int KS = 4 * NBLK, TILE = 32 * NW;
+  extern __shared__ double smem[];              // kwy_tri_lds_doubles(NBLK)
+  double *zf = smem;                            // the fragments of Z_m
+  double *mus = zf + kwy_tri_frags(NBLK) * 64;  // 16 NBLK: mu_x, zero beyond D
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, m = blockIdx.y;
   const int ar = lane & 15, ak = lane >> 4;
   const int D = dm.D, kp4 = ml_kp(D) / 4;      // 4 (NBLK - 1) < kp4 <= 4 NBLK
   const double *mod = model + (size_t)m * ml_model_stride(D);
   const double *mZ = mod, *mux = mod + 2 * D * D;
   const double cst = mod[2 * D * D + 3 * D];
-  for (int idx = tid; idx < NFRAG * 64; idx += 64 * NW) {
-    const int f = idx >> 6, l = idx & 63;
-    int nb = 0;
-    while (2 * (nb + 1) * (nb + 2) <= f) ++nb;
-    const int ks = f - 2 * nb * (nb + 1);
-    const int j = 16 * nb + (l & 15), i = 4 * ks + (l >> 4);
-    zf[idx] = (j < D && i <= j) ? mZ[j * D + i] : 0.0;
-  }
+  kwy_tri_fill<NBLK, 64 * NW>(zf, D, tid, [&](int j, int i) { return mZ[j * D + i]; });
   for (int c = tid; c < 16 * NBLK; c += 64 * NW) mus[c] = c < D ? mux[c] : 0.0;
   __syncthreads();
   const int64_t ntiles = (dm.T + TILE - 1) / TILE;
@@ -345,7 +231,7 @@ __global__ __launch_bounds__(64 * NW) void k_gmm_logp_frag(const double *__restr
     double q0[4] = {0.0, 0.0, 0.0, 0.0}, q1[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int nb = 0; nb < NBLK; ++nb) {
-      ml_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+      kwy_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
       const double *frag = zf + (2 * nb * (nb + 1)) * 64 + lane;
 #pragma unroll
       for (int ks = 0; ks < 4 * nb + 4; ++ks) {
@@ -363,14 +249,7 @@ __global__ __launch_bounds__(64 * NW) void k_gmm_logp_frag(const double *__restr
       }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      double v = q0[r], w = q1[r];
-      v += kwy_dpp_f64<0x111>(v); w += kwy_dpp_f64<0x111>(w);
-      v += kwy_dpp_f64<0x112>(v); w += kwy_dpp_f64<0x112>(w);
-      v += kwy_dpp_f64<0x114>(v); w += kwy_dpp_f64<0x114>(w);
-      v += kwy_dpp_f64<0x118>(v); w += kwy_dpp_f64<0x118>(w);
-      q0[r] = v; q1[r] = w;
-    }
+    for (int r = 0; r < 4; ++r) kwy_row_sum15(q0[r], q1[r]);
     if (ar == 15) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -902,44 +781,22 @@ __global__ __launch_bounds__(ML_FIN_NT) void k_mlpg_finish(const double *__restr
 // ---- host side: launch geometry ---------------------------------------------------------------------------------------
 #define ML_LDS_MAX (160 * 1024)   // bytes of LDS a workgroup can have
 
-// f(std::integral_constant<int, N>) for the block count nblk = N of 1 .. 6: the kernels with one code path per number
-// of 16-column blocks are templates over it
-template <class F>
-static int ml_with_blocks(int nblk, F f) {
-  switch (nblk) {
-    case 1: return f(std::integral_constant<int, 1>());
-    case 2: return f(std::integral_constant<int, 2>());
-    case 3: return f(std::integral_constant<int, 3>());
-    case 4: return f(std::integral_constant<int, 4>());
-    case 5: return f(std::integral_constant<int, 5>());
-    default: return f(std::integral_constant<int, 6>());
-  }
+// k_gmm_prep keeps three D x D matrices in LDS: that bounds the feature dimension of every conversion entry (D <= 82),
+// and with it the column blocks of the kernels that are templates over them
+static constexpr size_t ml_prep_lds(int D) { return sizeof(double) * 3 * D * D; }
+static constexpr bool ml_lds_fits(int D) { return ml_prep_lds(D) <= ML_LDS_MAX; }
+static constexpr int ml_widest_d() {
+  int D = 1;
+  while (ml_lds_fits(D + 1)) ++D;
+  return D;
 }
+static constexpr int ml_frag_blocks(int D) { return ml_np(D) / 16; }
+static_assert(ml_frag_blocks(ml_widest_d()) <= ML_FRAG_MAXBLK, "a D that k_gmm_prep admits has no k_gmm_logp_frag instance");
+static_assert(sizeof(double) * kwy_tri_lds_doubles(ML_FRAG_MAXBLK) <= ML_LDS_MAX, "k_gmm_logp_frag: fragments beyond the LDS");
 
-// frame-tile walkers per mixture: enough workgroups for every CU (one fits per CU), not more than tiles
-static int ml_logp_waves(int D) {      // wavefronts per workgroup of k_gmm_logp: eight if Z_m and 128 frames fit the LDS
-  return sizeof(double) * (size_t)(ml_np(D) + 128) * (ml_kp(D) + 1) <= 150 * 1024 ? 8 : 4;
-}
-static size_t ml_logp_lds(int D) {
-  return sizeof(double) * (size_t)(ml_np(D) + 16 * ml_logp_waves(D)) * (ml_kp(D) + 1);
-}
-static int ml_logp_splits(int64_t T, int M, int D) {
-  const int tile = 16 * ml_logp_waves(D);
-  const int64_t ntiles = (T + tile - 1) / tile;
-  int64_t s = (256 + M - 1) / M;
-  if (s > ntiles) s = ntiles;
-  return (int)(s < 1 ? 1 : s);
-}
-
-// the fragment form: eight wavefronts, 256 frames per tile
+// log-densities: eight wavefronts, 256 frames per tile; frame-tile walkers per mixture, not more than tiles
 #define ML_FRAG_NW 8
 #define ML_FRAG_WGS 1024  // workgroups of a launch: measured 0.341 / 0.306 / 0.296 ms with 256 / 512 / 1024 (D = 72, 35 216 frames)
-static int ml_frag_blocks(int D) { return ml_np(D) / 16; }
-static bool ml_logp_frag(int D) { return ml_frag_blocks(D) <= ML_FRAG_MAXBLK; }
-static size_t ml_frag_lds(int D) {
-  const int nblk = ml_frag_blocks(D);
-  return sizeof(double) * ((size_t)2 * nblk * (nblk + 1) * 64 + 16 * nblk);
-}
 static int ml_frag_splits(int64_t T, int M) {
   const int64_t ntiles = (T + 32 * ML_FRAG_NW - 1) / (32 * ML_FRAG_NW);
   int64_t s = (ML_FRAG_WGS + M - 1) / M;
@@ -947,34 +804,18 @@ static int ml_frag_splits(int64_t T, int M) {
   return (int)(s < 1 ? 1 : s);
 }
 
-template <int NBLK>
-static int ml_launch_frag(kwy_ctx *ctx, const double *X, const ml_dims &dm, const double *model, double *logp) {
-  const size_t lds = ml_frag_lds(dm.D);
-  const dim3 grid((unsigned)ml_frag_splits(dm.T, dm.M), dm.M);
-  KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_logp_frag<NBLK, ML_FRAG_NW>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  KWY_PROF(ctx, "k_gmm_logp", hipLaunchKernelGGL((k_gmm_logp_frag<NBLK, ML_FRAG_NW>), grid, dim3(64 * ML_FRAG_NW), lds,
-                                                 ctx->stream, X, dm, model, logp));
-  return KWY_OK;
-}
-
+// (the callers have checked ml_lds_fits(dm.D))
 static int ml_launch_logp(kwy_ctx *ctx, const double *X, const ml_dims &dm, const double *model, double *logp) {
-  if (ml_logp_frag(dm.D)) {
-    return ml_with_blocks(ml_frag_blocks(dm.D), [&](auto nb) {
-      return ml_launch_frag<decltype(nb)::value>(ctx, X, dm, model, logp);
-    });
-  }
-  // wider features: rows of Z_m and the frame tile in LDS
-  const size_t lds = ml_logp_lds(dm.D);
-  const dim3 grid((unsigned)ml_logp_splits(dm.T, dm.M, dm.D), dm.M);
-  if (ml_logp_waves(dm.D) == 8) {
-    KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_logp<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    KWY_PROF(ctx, "k_gmm_logp", hipLaunchKernelGGL(k_gmm_logp<8>, grid, dim3(512), lds, ctx->stream, X, dm, model, logp));
-  } else {
-    KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_logp<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    KWY_PROF(ctx, "k_gmm_logp", hipLaunchKernelGGL(k_gmm_logp<4>, grid, dim3(256), lds, ctx->stream, X, dm, model, logp));
-  }
-  return KWY_OK;
+  return kwy_with_blocks<ML_FRAG_MAXBLK>(ml_frag_blocks(dm.D), [&](auto nb) -> int {
+    constexpr int NBLK = decltype(nb)::value;
+    const size_t lds = sizeof(double) * kwy_tri_lds_doubles(NBLK);
+    const dim3 grid((unsigned)ml_frag_splits(dm.T, dm.M), dm.M);
+    KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_logp_frag<NBLK, ML_FRAG_NW>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    KWY_PROF(ctx, "k_gmm_logp", hipLaunchKernelGGL((k_gmm_logp_frag<NBLK, ML_FRAG_NW>), grid, dim3(64 * ML_FRAG_NW), lds,
+                                                   ctx->stream, X, dm, model, logp));
+    return KWY_OK;
+  });
 }
 
 // chunks of the partitioned solve of a T-row system: 64/d per wavefront, at least 16 rows each
@@ -1128,13 +969,13 @@ __global__ __launch_bounds__(64 * ML_EM_NW) void k_em_estep(const double *__rest
     const double lcm = lc[m];
     // NBLK independent accumulator chains (one per column block) under every k-step: a chain alone leaves the matrix
     // core waiting for its own result
-    ml_v4f64 acc[NBLK];
+    kwy_v4f64 acc[NBLK];
     double ivc[NBLK], q[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int nb = 0; nb < NBLK; ++nb) {
       const double my = vec[NP + 16 * nb + ar];
       ivc[nb] = vec[2 * NP + 16 * nb + ar];
-      acc[nb] = ml_v4f64{my, my, my, my};
+      acc[nb] = kwy_v4f64{my, my, my, my};
     }
     // the operands of k-step ks + 1 are read from LDS before the products of k-step ks are issued (one wavefront per
     // SIMD: nothing else hides the LDS latency in front of every product)
@@ -1351,11 +1192,6 @@ static size_t ml_pass_bytes(const int64_t *Ts, int n, int d, int M, const ml_mix
   return a.bytes + (o.gv ? kwy_gva_scratch_bytes(Ts, n, d, o.gv->iterations) : 0);
 }
 
-// k_gmm_prep keeps three D x D matrices in LDS, the log-density kernels Z_m or its fragments and a frame tile
-static size_t ml_prep_lds(int D) { return sizeof(double) * 3 * D * D; }
-static bool ml_lds_fits(int D) {
-  return ml_prep_lds(D) <= ML_LDS_MAX && (ml_logp_frag(D) ? ml_frag_lds(D) : ml_logp_lds(D)) <= ML_LDS_MAX;
-}
 // the preparation of the mixture over D dimensions per side: its LDS attribute, and the launch
 static int ml_prep_attr(kwy_ctx *ctx, int D) {
   KWY_HIP(hipFuncSetAttribute((const void *)k_gmm_prep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml_prep_lds(D)));
@@ -1403,13 +1239,13 @@ static int ml_convert_core(kwy_ctx *ctx, const char *who, ml_batch &bt, const in
   if (lds_solve > ML_LDS_MAX) { ctx->err = std::string(who) + ": static dimension too large"; return KWY_EINVAL; }
   KWY_HIP(hipFuncSetAttribute((const void *)k_mlpg_finish, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_solve));
   if (em)
-    KWY_TRY(ml_with_blocks(nblk, [&](auto nb) -> int {
+    KWY_TRY(kwy_with_blocks<ML_EM_MAXBLK>(nblk, [&](auto nb) -> int {
       KWY_HIP(hipFuncSetAttribute((const void *)k_em_estep<decltype(nb)::value>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml_em_lds(decltype(nb)::value)));
       return KWY_OK;
     }));
   auto estep = [&](int first) {
-    ml_with_blocks(nblk, [&](auto nb) -> int {
+    kwy_with_blocks<ML_EM_MAXBLK>(nblk, [&](auto nb) -> int {
       constexpr int NBLK = decltype(nb)::value;
       KWY_PROF(ctx, "k_em_estep", hipLaunchKernelGGL(k_em_estep<NBLK>, dim3((unsigned)((T + ML_EM_TILE - 1) / ML_EM_TILE)),
                                                      dim3(64 * ML_EM_NW), ml_em_lds(NBLK), ctx->stream, w.X, dm, bt, w.model,

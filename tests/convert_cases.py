@@ -25,9 +25,10 @@ FRAMES = tuple((6, M, T_SEAMS) for M in MIXTURES) + ((72, 1, T_SHORT), (72, 3, T
 # d = 6, 11, 16, 20, 27: two, three (ragged and full), four and six column blocks.
 MCEP = tuple((2, M, T_SEAMS) for M in MIXTURES) + ((24, 3, T_SEAMS), (24, 1, (17, 33)), (24, 64, (17, 33, 257)),
                                                     (27, 3, (17, 33))) + tuple((d, 3, (33,)) for d in (6, 11, 16, 20))
-# D = 144 and D = 150, the shapes on either side of the log-density kernels' dispatch boundary (nine column blocks /
-# more): k_gmm_prep holds three D x D matrices in LDS, so the library refuses both (KWY_EINVAL) before any kernel runs,
-# in every build so far.  The fixture records that return code, and the tests hold the tree to it.
+# D = 144 and D = 150, nine column blocks and more: wider than any mixture the library prepares.  k_gmm_prep holds three
+# D x D matrices in LDS (D <= 82, six column blocks -- all the log-density kernel is built for), so the library refuses
+# both (KWY_EINVAL) before any kernel runs, in every build so far.  The fixture records that return code, and the tests
+# hold the tree to it.
 REFUSED = ((48, 3, 17), (50, 3, 17))
 BATCH = (24, 3, (17, 256, 33))
 MC2SP = ((2048, (1, 16, 17)), (1024, (1, 16, 17)))       # K = 1025 and K = 513

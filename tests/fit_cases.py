@@ -8,7 +8,8 @@ numpy_em_stats.py: a hand-written Cholesky and forward substitution, log-sum-exp
 |c|^2 - 2 <x, c> distances.  numpy_em_stats.NumpyStats is the FLOAT64 restatement: its error against these references
 is what the GPU tolerances are built from (`bound`), never the kernels' own output.
 
-test_fit_cases.py checks the inputs and references on the CPU; test_fit_kernels_gpu.py runs the kernels."""
+test_fit_cases.py checks the inputs and references on the CPU; test_fit_kernels_gpu.py runs the kernels.  Section 5 holds
+the calls whose output BYTES tools/record_fit_bits.py records and test_fit_bits_gpu.py compares."""
 import functools
 import math
 
@@ -656,3 +657,96 @@ def tie_case():
         a.setflags(write=False)
     return dict(n=n, D=D, M=M, Xc=Xc, centres=centres, same=same, near=near, dist=dist,
                 labels=dist.argmin(1).astype(np.int32))
+
+
+# ---- 5: the bits of the fit and k-means entries (tests/golden/fit_bits_parent.npz) ------------------------------------
+# tools/record_fit_bits.py records what the functions below return on the build the bits are held to;
+# test_fit_bits_gpu.py calls them on the build under test and compares bytes.  The cases sit on the seams of one, two,
+# nine and ten column blocks, of the 16 / 32 / 256-row tiles and of the 64-centre groups.
+BITS_ESTEP = ('d1_m1_n1', 'd16_m2_n31', 'd17_m16_n32', 'd144_m17_n33', 'd160_m2_n255', 'd16_m65_n256')
+BITS_STATS = ('d1_m1_n1', 'd16_m3_n3', 'd17_m16_n4', 'd33_m17_n5', 'd97_m3_n33')      # kept as arrays
+BITS_STATS_DIGEST = ('d144_m16_n257', 'd160_m17_n257')                               # megabytes: SHA-256 only
+BITS_KM = ('n1_d1_m1', 'n5_d16_m16', 'n255_d17_m17', 'n256_d160_m64', 'n257_d16_m65', 'n5_d17_m256')
+
+
+def digest(a):
+    """SHA-256 of an array's bytes, as a string array an .npz holds"""
+    import hashlib
+    return np.array(hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest())
+
+
+def tril_pack(sxx):
+    """(M, D, D) -> (M, D (D + 1) / 2): the lower triangles, row by row (the fixture keeps these: the covariance
+    statistics are symmetric to the bit, and `tril_unpack` gives the whole array back)"""
+    i, j = np.tril_indices(sxx.shape[1])
+    return np.ascontiguousarray(sxx[:, i, j])
+
+
+def tril_unpack(packed, D):
+    i, j = np.tril_indices(D)
+    out = np.empty((packed.shape[0], D, D), dtype=packed.dtype)
+    out[:, i, j] = packed
+    out[:, j, i] = packed
+    return out
+
+
+def _hip_stats(X, M, ctx):
+    from kwiiyatta_amd.converter.gmm_fit import HipStats
+    return HipStats(np.array(X), M, ctx=ctx)
+
+
+def _to(hs, a):
+    import torch
+    return torch.from_numpy(np.array(a, dtype=np.float64)).to(hs.dev)
+
+
+def bits_estep(ctx, name):
+    """kwy_gmm_em_estep_dev (k_fit_prec, k_fit_logprob, k_fit_resp) on estep_case(name):
+    responsibilities (n, M), log-likelihood parts, status word"""
+    c = estep_case(name)
+    hs = _hip_stats(c['X'], c['M'], ctx)
+    with hs.scope():
+        hs.set_params(np.array(c['weights']), np.array(c['means']), np.array(c['covs']))
+        hs.estep()
+        return hs.resp.cpu().numpy(), hs.ll.cpu().numpy(), hs.status.cpu().numpy()[:1]
+
+
+def bits_stats(ctx, name):
+    """kwy_gmm_em_sums_dev (k_fit_sums, k_fit_reduce) and kwy_gmm_em_cov_dev (k_fit_active .. k_fit_cov,
+    k_fit_reduce_sym) on soft_case(name): sums (M, 1 + D), sxx (M, D, D) without the sums (what kwy_gmm_em_cov_dev
+    computes), sxx with the case's sums handed over (kwy_gmm_em_cov_stats_dev)"""
+    c = soft_case(name)
+    hs = _hip_stats(c['X'], c['M'], ctx)
+    with hs.scope():
+        hs.resp.copy_(_to(hs, c['resp']))
+        hs.means.copy_(_to(hs, c['means']))
+        sums = hs.sums().cpu().numpy()
+        cov = hs.cov(None).cpu().numpy()
+        st = sums.copy()
+        st[:, 0] = c['nk']
+        cov_stats = hs.cov(_to(hs, st)).cpu().numpy()
+    return sums, cov, cov_stats
+
+
+def _bits_assign(ctx, X, mean, centres, M):
+    hs = _hip_stats(X, M, ctx)
+    with hs.scope():
+        hs.km_begin(_to(hs, mean))
+        cd = _to(hs, centres)
+        first = int(hs.km_assign(cd).item())               # from -1 everywhere
+        labels = hs.labels.cpu().numpy()
+        again = int(hs.km_assign(cd).item())               # the same centres
+        hs.km_end()
+    return labels, np.array([first, again], dtype=np.int64)
+
+
+def bits_km(ctx, name):
+    """kwy_km_assign_dev (k_km_assign, k_km_labels) on km_case(name): labels, [changed from -1, changed again]"""
+    c = km_case(name)
+    return _bits_assign(ctx, c['X'], c['mean'], c['centres'], c['M'])
+
+
+def bits_tie(ctx):
+    """... on tie_case(), centred on zero"""
+    c = tie_case()
+    return _bits_assign(ctx, c['Xc'], np.zeros(c['D']), c['centres'], c['M'])

@@ -11,10 +11,10 @@
     wins.
 
 Frame counts sit on the seams of the kernels' maps (16-frame sub-tiles, 32 frames per wavefront, 256 per workgroup
-tile), feature widths on one to six 16-column blocks -- D = 82 is the widest mixture the library prepares.  The issue's
-D = 144 and D = 150 (the dispatch boundary between the fragment kernel and the row kernel) cannot reach a log-density
-kernel: k_gmm_prep needs 3 D^2 doubles of LDS, so the library refuses them with KWY_EINVAL, as the parent build does;
-the fixture holds the parent's return codes and the tree has to give the same.
+tile), feature widths on one to six 16-column blocks -- D = 82 is the widest mixture the library prepares, and six
+blocks are all the log-density kernel is built for.  D = 144 and D = 150 (nine blocks and more) cannot reach a
+log-density kernel: k_gmm_prep needs 3 D^2 doubles of LDS, so the library refuses them with KWY_EINVAL, as the recorded
+build does; the fixture holds that build's return codes and the tree has to give the same.
 """
 import os
 
@@ -97,8 +97,8 @@ def test_ragged_batch_bits_and_values(ctx, golden):
 
 @pytest.mark.parametrize('d,M,T', cc.REFUSED)
 def test_widths_the_preparation_cannot_hold_are_refused_as_before(ctx, golden, d, M, T):
-    """D = 144 (nine column blocks, the fragment kernel's last shape) and D = 150 (the row kernel's side of the
-    dispatch): both builds refuse them before a kernel runs."""
+    """D = 144 (nine column blocks) and D = 150 (ten): wider than k_gmm_prep admits (D <= 82), so the recorded build
+    and the tree refuse them before a kernel runs."""
     from kwiiyatta_amd import _lib
     w, mu, cov = cc.mixture(3 * d, M, 0)
     rc, model = cc.prepare(ctx, d, w, mu, cov)
