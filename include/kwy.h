@@ -501,7 +501,8 @@ int kwy_moments_accumulate_dev(kwy_ctx *ctx, const double *moments, int count, d
 
 /* ---- mel-cepstrum ---------------------------------------------------------------- */
 /* pysptk.sp2mc(spec, order, alpha) row-wise          kwiiyatta/vocoder/mcep.py:71
- * sp: T x K (K = fftlen/2+1), mc: T x (order+1). */
+ * sp: T x K (K = fftlen/2+1), mc: T x (order+1).  Accepted: T >= 1, 2 <= K <= 4097 (any even fftlen),
+ * 1 <= order <= min(63, fftlen/2) and |alpha| < 1, every combination of them; anything else is KWY_EINVAL. */
 int kwy_sp2mc(kwy_ctx *ctx, const double *sp, int64_t T, int K, int order, double alpha,
               double *mc);
 int kwy_sp2mc_dev(kwy_ctx *ctx, const double *sp, int64_t T, int K, int order, double alpha,

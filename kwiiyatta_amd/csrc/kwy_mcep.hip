@@ -256,16 +256,25 @@ int kwy_get_sp2mc_matrix(kwy_ctx *ctx, int N, int order, double alpha, const dou
   return KWY_OK;
 }
 
+// LDS of k_sp2mc for an N-point transform whose matrix keeps ncut cepstral indices: the FFT buffer, its twiddles,
+// the partial sums and MC_FR cepstra.  ncut grows with |alpha| and the order up to N; beyond KWY_SP2MC_LDS_MAX
+// the call takes the dense form, which needs no more than 139 KB at any length (kwy_sp2mc_dev).
+#define KWY_SP2MC_LDS_MAX (160 * 1024)
+static size_t sp2mc_lds(int N, int ncut) {
+  const int H = N / 2;
+  return sizeof(kwy_c) * ((H + 1) + (H / 8 > 1 ? H / 8 : 1)) + sizeof(double) * (size_t)MC_FR * (256 + ncut);
+}
+
 template <int LOG2N>
 static int launch_sp2mc(kwy_ctx *ctx, const double *sp, int64_t T, int order, const double *F, int ncut,
                         double *mc) {
-  constexpr int N = 1 << LOG2N, H = N / 2;
+  constexpr int N = 1 << LOG2N;
   const kwy_c *twH, *twN, *twP;
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N - 1, &twH));
   KWY_TRY(kwy_get_twiddle_powers(ctx, LOG2N - 1, &twP));
   KWY_TRY(kwy_get_twiddles(ctx, LOG2N, &twN));
-  size_t lds = sizeof(kwy_c) * ((H + 1) + (H / 8 > 1 ? H / 8 : 1)) + sizeof(double) * (size_t)MC_FR * (256 + ncut);
-  if (lds > 160 * 1024) { ctx->err = "sp2mc: transform too long for the LDS"; return KWY_EINVAL; }
+  const size_t lds = sp2mc_lds(N, ncut);
+  if (lds > KWY_SP2MC_LDS_MAX) { ctx->err = "sp2mc: transform too long for the LDS"; return KWY_EINVAL; }
   KWY_HIP(hipFuncSetAttribute((const void *)k_sp2mc<LOG2N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   KWY_PROF(ctx, "k_sp2mc", hipLaunchKernelGGL(k_sp2mc<LOG2N>, dim3((unsigned)((T + MC_FR - 1) / MC_FR)), dim3(KWY_THREADS), lds, ctx->stream, sp, T, order, F,
                      ncut, twH, twP, twN, mc));
@@ -394,6 +403,8 @@ extern "C" int kwy_sp2mc_dev(kwy_ctx *ctx, const double *sp, int64_t T, int K, i
   const double *F;
   int ncut;
   KWY_TRY(kwy_get_sp2mc_matrix(ctx, 1 << l, order, alpha, &F, &ncut));
+  // a warp whose cepstra do not fit beside the transform: the same map as one dense matrix
+  if (sp2mc_lds(1 << l, ncut) > KWY_SP2MC_LDS_MAX) return launch_sp2mc_dense(ctx, sp, T, K, order, alpha, mc);
   switch (l) {
     case 9: return launch_sp2mc<9>(ctx, sp, T, order, F, ncut, mc);
     case 10: return launch_sp2mc<10>(ctx, sp, T, order, F, ncut, mc);
