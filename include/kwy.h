@@ -26,6 +26,7 @@
 #ifndef KWY_H_
 #define KWY_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1153,6 +1154,38 @@ int kwy_km_lloyd_dev(kwy_ctx *ctx, const double *Xc, int64_t n, int D, double *c
  * scikit-learn's `resp` of the k-means initialisation (sklearn/mixture/_base.py:_initialize_parameters) asks for it
  * once, after the loop. */
 int kwy_km_onehot_dev(kwy_ctx *ctx, const int32_t *labels, int64_t n, int M, double *resp);
+
+/* ---- non-parallel training: all-pairs nearest-neighbour search ---------------------------------------
+ * The search of INCA (Erro, Moreno, Bonafonte 2010: every source frame paired with its nearest target frame and the
+ * other way round, the mixture fitted on those pairs, the source converted, the search repeated).  The reference
+ * trains on parallel data only and has no counterpart.
+ * Q: nq x D queries, C: nc x D candidates, row-major doubles; 1 <= D <= 160 (the k-means limit), nc <= 2^31 - 1.
+ *   score     s(t, j) = |c_j|^2 - 2 <q_t, c_j>: |c_j|^2 summed over the columns in ascending order, the product on
+ *             v_mfma_f64_16x16x4_f64 with the k-steps ascending (kwy_km_assign_dev's arithmetic).  The score of a pair
+ *             is the same bits in whatever tile, slice or launch the pair lands.
+ *   idx[t]    the j of the lexicographic minimum of (s(t, j), j): of equal scores the lower index
+ *   dist2[t]  sum_k (q_tk - c_jk)^2 for that j, recomputed directly, k ascending, no contraction (NOT s + |q|^2)
+ *   A comparison with a score that is not finite is never "less": a query without any finite score gets idx = -1 and
+ *   dist2 = NaN and is counted in status[0] (set, not accumulated; status may be NULL).
+ *   splits    0: the entry chooses (enough slices to fill the chip when the queries are few); 1 .. KWY_NN_MAX_SPLITS:
+ *             that many slices of the candidate range, slice s = [s L, min(nc, (s + 1) L)) with
+ *             L = kwy_nn_slice(nc, splits) = ceil(nc / splits) rounded up to a multiple of 64.  A slice without
+ *             candidates contributes (+inf, INT_MAX).  The results are bit for bit independent of `splits`.
+ *   Rows beyond nc and columns beyond D are padding inside the kernel and cannot win (a padded row scores +inf).
+ * KWY_EINVAL, nothing written: D outside [1, 160], nq < 0, splits outside [0, KWY_NN_MAX_SPLITS], and with nq > 0:
+ * nc < 1 or beyond the limit, a null Q, C, idx or dist2.  nq = 0 is KWY_OK and writes nothing.
+ * The _dev form does not synchronise and does not allocate once the context's scratch holds
+ * kwy_nn_scratch_bytes(nq, splits) bytes (kwy_ctx_reserve; splits = 0: the bound for every choice of the entry) --
+ * the slices' partial results ([splits][nq] scores and indices) live there -- so it is legal in a stream capture.
+ * It uses no atomics. */
+#define KWY_NN_MAX_SPLITS 64
+int kwy_nn_search(kwy_ctx *ctx, const double *Q, int64_t nq, const double *C, int64_t nc, int D, int splits,
+                  int32_t *idx, double *dist2, int32_t *status);
+int kwy_nn_search_dev(kwy_ctx *ctx, const double *Q, int64_t nq, const double *C, int64_t nc, int D, int splits,
+                      int32_t *idx, double *dist2, int32_t *status);
+/* pure host arithmetic, no device needed; 0 for nq <= 0, and for kwy_nn_slice with an argument out of range */
+size_t kwy_nn_scratch_bytes(int64_t nq, int splits);
+int64_t kwy_nn_slice(int64_t nc, int splits);
 
 /* ---- training-set path (device-resident) ---------------------------------------------------------
  * What the reference does per parallel pair before the converter fit (Config.load_dataset ->

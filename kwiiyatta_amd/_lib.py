@@ -182,6 +182,10 @@ SIGNATURES = {
     'kwy_km_onehot_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp]),
     'kwy_km_lloyd_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_dbl, c_int, c_i64,
                          c_vp, c_vp]),
+    'kwy_nn_search': (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    'kwy_nn_search_dev': (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
+    'kwy_nn_scratch_bytes': (ctypes.c_size_t, [c_i64, c_int]),
+    'kwy_nn_slice': (c_i64, [c_i64, c_int]),
     'kwy_gmm_mlpg': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     'kwy_gmm_mlpg_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     'kwy_gmm_convert_frames': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),

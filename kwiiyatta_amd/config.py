@@ -82,6 +82,35 @@ CONVERTER_OPTIONS += (
 )
 
 
+NONPARALLEL_RANGE = (0, 64)      # MelCepstrumFeatureConverter.NONPARALLEL_RANGE
+NONPARALLEL_DEFAULT = 6          # MelCepstrumFeatureConverter.NONPARALLEL_DEFAULT
+
+
+def nonparallel(text):
+    """--nonparallel: the INCA iterations of a training without parallel data, an integer within [0, 64]"""
+    try:
+        n = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid iteration count: {text!r}') from None
+    lo, hi = NONPARALLEL_RANGE
+    if not lo <= n <= hi:
+        raise argparse.ArgumentTypeError(f'{text} is outside [{lo}, {hi}]')
+    return n
+
+
+# an addition to the reference's options (it trains on parallel data only)
+CONVERTER_OPTIONS += (
+    ('--nonparallel', dict(type=nonparallel, nargs='?', const=NONPARALLEL_DEFAULT, default=None, metavar='N',
+                           help='Train without parallel data (INCA, Erro et al. 2010): --source and --target need no '
+                                'common file names, --skip-files / --max-files pick the training files of each '
+                                'directory on its own.  Every speech frame of one side is paired with its nearest '
+                                'frame of the other (static and delta mel-cepstrum, voicing), the mixture fitted on '
+                                'the pairs, the source converted and the search repeated N times (within [0, 64], '
+                                f'{NONPARALLEL_DEFAULT} when omitted); kept in the converter model.  Goes with neither '
+                                '--align-iterations nor --convert-aperiodicity')),
+)
+
+
 COVARIANCE_STRUCTURES = ('full', 'block_diag')
 
 # an addition to the reference's options (its mixtures have full covariances)
@@ -320,6 +349,13 @@ class Config:
             if getattr(self, 'ms', 0.0) > 0:
                 self.parser.error('--mlpg-gv does not go with --ms: composing it with the modulation-spectrum filter is '
                                   'left for later')
+        if getattr(self, 'nonparallel', None) is not None:
+            if getattr(self, 'align_iterations', None) is not None:
+                self.parser.error('--nonparallel does not go with --align-iterations: there are no pairs to align '
+                                  'again')
+            if getattr(self, 'convert_aperiodicity', False):
+                self.parser.error('--nonparallel does not go with --convert-aperiodicity: band rows along the '
+                                  'nearest-neighbour pairs are left for later')
 
     # ---- factories --------------------------------------------------------------------------------------
     def create_analyzer(self, *args, Analyzer=None, **kwargs):
@@ -368,6 +404,8 @@ class Config:
         keys = self._training_keys(sides[0].keys() & sides[1].keys())
         means = []
         for flag, side in zip(('source', 'target'), sides):
+            if getattr(self, 'nonparallel', None) is not None:       # each side's own training files
+                keys = self._training_keys(side.keys())
             tracks = [np.ascontiguousarray(side[key].f0, dtype=np.float64) for key in keys]
             n, mean, _ = f0map.merge_moments(f0map.logf0_moments(tracks)) if tracks else (0, 0, 0)
             if not n > 0:
@@ -403,6 +441,15 @@ class Config:
         sides = [k.WavFileDataset(self.source_path, Analyzer=source), k.WavFileDataset(self.target_path, Analyzer=analyze)]
         return k.align(*sides)
 
+    def nonparallel_sides(self, source_f0_rate=None):
+        """(source, target): the two directories as data sets of their own for --nonparallel, which pairs no files;
+        the source side through `analyze_source` as in `load_dataset`"""
+        k = _pkg()
+        rate = self.resolve_source_f0_rate() if source_f0_rate is None else source_f0_rate
+        analyze = functools.partial(self.create_analyzer, Analyzer=k.analyze_wav)
+        return (k.WavFileDataset(self.source_path, Analyzer=lambda path: self.analyze_source(path, rate)),
+                k.WavFileDataset(self.target_path, Analyzer=analyze))
+
     def train_converter(self, f0_stats=False, gv_stats=False, ms_stats=False, gv_var=False, ap_model=False, **kwargs):
         """f0_stats=True / gv_stats=True / ms_stats=True: training also computes the f0 statistics / the target's global
         variance / the modulation-spectrum statistics at --ms-length (and the model file keeps them); a loaded model
@@ -431,6 +478,12 @@ class Config:
                 self.parser.error(f'{model}: the converter model was trained with --align-iterations '
                                   f'{converter.align_iterations}, not {asked}; retrain it with --align-iterations '
                                   f'{asked} (a new --converter-model file)')
+            asked = getattr(self, 'nonparallel', None)
+            if asked is not None and asked != converter.nonparallel:
+                was = ('on parallel data' if converter.nonparallel is None
+                       else f'with --nonparallel {converter.nonparallel}')
+                self.parser.error(f'{model}: the converter model was trained {was}, not with --nonparallel {asked}; '
+                                  f'retrain it with --nonparallel {asked} (a new --converter-model file)')
             asked = getattr(self, 'converter_covariance', None)
             if asked is not None and asked != converter.covariance:
                 self.parser.error(f'{model}: the converter model was trained with --converter-covariance '
@@ -459,13 +512,18 @@ class Config:
 
     def _train(self, converter, f0_stats=False, gv_stats=False, ms_stats=False, ap_model=False):
         converter.source_f0_rate = self._model_f0_rate = self.resolve_source_f0_rate()
-        dataset = self.load_dataset(converter.source_f0_rate)
-        keys = sorted(dataset.keys())[slice(self.skip_files, None)]
         extra = dict(f0_stats=True) if f0_stats else {}
         if gv_stats:
             extra['gv_stats'] = True
         if ms_stats:
             extra.update(ms_stats=True, ms_length=getattr(self, 'ms_length', None) or 4096)
+        if getattr(self, 'nonparallel', None) is not None:
+            sides = self.nonparallel_sides(converter.source_f0_rate)
+            converter.train_nonparallel(*sides, *(self._training_keys(side.keys()) for side in sides),
+                                        iterations=self.nonparallel, **extra, **(dict(ap_model=True) if ap_model else {}))
+            return converter
+        dataset = self.load_dataset(converter.source_f0_rate)
+        keys = sorted(dataset.keys())[slice(self.skip_files, None)]
         if getattr(self, 'align_iterations', None):
             extra['align_iterations'] = self.align_iterations
         if ap_model:

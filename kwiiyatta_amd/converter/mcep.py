@@ -88,6 +88,10 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         # pairs, used by `convert_aperiodicity`) and the rows its fit saw; None / 0 without one
         self.ap_converter = None
         self.ap_rows = 0
+        # the INCA iterations of a non-parallel training (`train_nonparallel(iterations=...)`; None: trained on
+        # parallel data) and its record, a dict per fit
+        self.nonparallel = None
+        self.nonparallel_history = []
 
     def train(self, dataset, keys, f0_stats=False, gv_stats=False, align_iterations=0, ms_stats=False, ms_length=4096,
               ap_model=False, ap_components=16, **kwargs):
@@ -111,6 +115,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         if isinstance(align_iterations, bool) or int(align_iterations) != align_iterations or align_iterations < 0:
             raise ValueError(f'align_iterations must be a non-negative integer, not {align_iterations!r}')
         self.align_iterations, self.align_history = int(align_iterations), []
+        self.nonparallel, self.nonparallel_history = None, []
         if ms_stats:
             self._check_ms_lengths(dataset, keys, ms_length)          # (before the fit is paid for)
         self.ap_converter, self.ap_rows = None, 0
@@ -164,14 +169,18 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                              'two frames)')
 
     def _train_ms(self, dataset, keys, length):
+        self._train_ms_sides(lambda: _side_mel_cepstra(dataset, keys, self.order, self.fs, 0),
+                             _target_mel_cepstra(dataset, keys, self.order, self.fs), length)
+
+    def _train_ms_sides(self, sources, natural, length):
+        """sources: a callable that gives the source side's MelCepstrum records (called after the target's statistics
+        are made); natural: the target side's (frames, order + 1) matrices"""
         from ..backend import ms as msfilter
         as_f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
-        natural = _target_mel_cepstra(dataset, keys, self.order, self.fs)
         if not natural:
             raise ValueError('modulation spectrum statistics: no training files')
         stats_n = msfilter.statistics(natural, length)
-        converted = [as_f64(self.convert(source, diff=False).data)
-                     for source in _side_mel_cepstra(dataset, keys, self.order, self.fs, 0)]
+        converted = [as_f64(self.convert(source, diff=False).data) for source in sources()]
         stats_g = msfilter.statistics(converted, length)
         for name, stats in (('target', stats_n), ('converted source', stats_g)):
             if stats[1:, 1:, 0].min() < 2:
@@ -316,6 +325,128 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             raise ValueError(f'ap_model: the band rows follow the last alignment (fit {iterations}), which this training '
                              f'did not reach: no band mixture was fitted')
 
+    NONPARALLEL_RANGE = (0, 64)
+    NONPARALLEL_DEFAULT = 6
+
+    def train_nonparallel(self, source, target, source_keys, target_keys, iterations=None, f0_stats=False,
+                          gv_stats=False, ms_stats=False, ms_length=4096, ap_model=False, **fit_options):
+        """Training without parallel data: INCA (Erro, Moreno, Bonafonte 2010).  `source` and `target` are datasets of
+        feature sets (WavFileDataset) that need no common keys; `source_keys` / `target_keys` name the utterances of
+        each, in the order their frames take in the matrices.
+        Of every utterance the SPEECH frames take part: those whose power term `vocoder.align.make_feature` sets with
+        its defaults (what --frames speech means); an utterance without one contributes nothing.  Its delta features
+        are `delta_features(c1..cN, DELTA_WINDOWS)` over ALL its frames, the rows selected afterwards, and the search
+        row of a speech frame is [voicing term of make_feature | c1..cN | delta c1..cN]: D = 2 order + 1.
+        Fit i = 0 .. iterations: the source search rows take their static and delta columns from X' -- fit 0: the
+        source's own mel-cepstra; fit i: `convert(utterance, diff=False)` by fit i - 1, the deltas recomputed from it;
+        the voicing term stays the source's own.  p = nearest(S, T), q = nearest(T, S) (backend.nn); the joint matrix is
+        [x_k | y_p(k)] for k in source order followed by [x_q(j) | y_j] for j in target order, x ALWAYS the original
+        source delta features; the mixture is fitted on it from scratch (same components, random_state, stopping rule,
+        covariance structure).  `nonparallel_history` gets one record per fit: rows, em_iterations and mcd, the
+        monitor -- the mean distortion in dB over c1..cN across all joint rows between the static columns the search
+        used.  Order, sampling rate and frame period are checked as `_train_realigned` checks them (nothing is
+        resampled).  f0_stats / gv_stats / ms_stats as in `train`, each side's statistics over its own utterances;
+        ap_model raises ValueError: band rows along the nearest-neighbour pairs are left for later."""
+        from ..backend import distortion as dist, nn
+        from ..backend.mlpg import DELTA_WINDOWS, delta_features
+        from ..vocoder.align import make_feature
+        from .delta import DeltaFeatureConverter
+        if ap_model:
+            raise ValueError('ap_model: non-parallel training pairs no band-aperiodicity rows (left for later)')
+        if iterations is None:
+            iterations = self.NONPARALLEL_DEFAULT
+        lo, hi = self.NONPARALLEL_RANGE
+        if isinstance(iterations, bool) or int(iterations) != iterations or not lo <= iterations <= hi:
+            raise ValueError(f'iterations must be an integer within [{lo}, {hi}], not {iterations!r}')
+        iterations = int(iterations)
+        delta_stage = self.base
+        while not isinstance(delta_stage, DeltaFeatureConverter) and isinstance(delta_stage, abc.MapFeatureConverter):
+            delta_stage = delta_stage.base
+        if not isinstance(delta_stage, DeltaFeatureConverter):
+            raise ValueError('non-parallel training searches on delta features: the stack needs a delta stage '
+                             '(use_delta=True)')
+        if ms_stats:
+            from ..backend import ms as msfilter
+            msfilter._length(ms_length)
+        as_f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
+        k = _pkg()
+        self.order, self.fs = None, self.mcep_fs
+        sides = []
+        for name, dataset, keys in (('source', source, list(source_keys)), ('target', target, list(target_keys))):
+            utterances = []
+            for key in keys:
+                feature = dataset[key]
+                record = feature.mel_cepstrum
+                if self.order is None:
+                    self.order = record.order
+                if self.fs is None:
+                    self.fs = record.fs
+                if not utterances and name == 'source':
+                    delta_stage.frame_period = record.frame_period
+                if record.order != self.order:
+                    raise ValueError(f'nonparallel: {name} "{key}" has mel-cepstra of order {record.order}, the converter '
+                                     f'of order {self.order}')
+                if record.fs != self.fs:
+                    raise ValueError(f'nonparallel: {name} "{key}" is at {record.fs} Hz but the converter works at '
+                                     f'{self.fs} Hz; non-parallel training does not resample')
+                if record.frame_period != delta_stage.frame_period:
+                    raise ValueError(f'frame_period of {name} "{key}" is {record.frame_period!r} but others are '
+                                     f'{delta_stage.frame_period!r}')
+                terms = make_feature(feature, record.fs)[:, :2]
+                if ms_stats:
+                    msfilter._fits([len(terms)], msfilter._length(ms_length))
+                speech = np.flatnonzero(terms[:, 0] > 0)
+                data = as_f64(record.data)
+                utterances.append(dict(record=k.MelCepstrum(record.fs, record.frame_period, data), speech=speech,
+                                       voicing=terms[speech, 1], f0=as_f64(feature.f0),
+                                       delta=delta_features(as_f64(data[:, 1:]), DELTA_WINDOWS)[speech]))
+            if not utterances:
+                raise ValueError(f'nonparallel: no {name} files')
+            sides.append(utterances)
+        order = self.order
+        xd, yd = (np.concatenate([u['delta'] for u in side]) for side in sides)
+        vx, vy = (np.concatenate([u['voicing'] for u in side]) for side in sides)
+        if not len(xd) or not len(yd):
+            raise ValueError(f'nonparallel: no speech frames ({len(xd)} on the source side, {len(yd)} on the target side)')
+        T = as_f64(np.hstack((vy[:, None], yd[:, :2 * order])))
+        self.align_iterations, self.align_history = 0, []
+        self.ap_converter, self.ap_rows = None, 0
+        self.nonparallel, self.nonparallel_history = iterations, []
+        for it in range(iterations + 1):
+            if it == 0:
+                mapped = xd[:, :2 * order]
+            else:
+                mapped = np.concatenate([
+                    delta_features(as_f64(self.convert(u['record'], diff=False).data[:, 1:]),
+                                   DELTA_WINDOWS)[u['speech'], :2 * order] for u in sides[0]])
+            S = as_f64(np.hstack((vx[:, None], mapped)))
+            # (the rows as they are, as the device driver searches them, corpus.train_converter_nonparallel: with a
+            # voicing term of 9 and mel-cepstra of a few units the bound of the search, 4 (D + 1) 2^-53 (|q|^2 + |c|^2),
+            # is some 1e-12 on squared distances of order 1 -- centring has nothing to repair here)
+            p, q = nn.nearest(S, T, center=False)[0], nn.nearest(T, S, center=False)[0]
+            matrix = np.vstack((np.hstack((xd, yd[p])), np.hstack((xd[q], yd))))
+            self._train(matrix, **fit_options)
+            own = np.arange(len(S), dtype=np.int32), np.arange(len(T), dtype=np.int32)
+            moments = dist.mcd(as_f64(S[:, 1:order + 1]), as_f64(T[:, 1:order + 1]),
+                               idx_a=np.concatenate((own[0], q)), idx_b=np.concatenate((p, own[1])), first_col=0)[0]
+            self.nonparallel_history.append(dict(rows=len(matrix), mcd=float(moments[1]),
+                                                 em_iterations=int(getattr(self.gmm, 'n_iter_', 0))))
+        self.f0_stats = None
+        if f0_stats:
+            from ..backend import f0 as f0map
+            self.f0_stats = f0map.stats_from_moments(*(
+                f0map.merge_moments(f0map.logf0_moments([u['f0'] for u in side])) for side in sides))
+        self.gv_stats, self.gv_var = None, None
+        if gv_stats:
+            from ..backend import gv as gvfilter
+            moments = gvfilter.column_moments([u['record'].data for u in sides[1]])
+            self.gv_stats = gvfilter.gv_from_moments(moments)
+            self.gv_var = gvfilter.gv_statistics(moments)[1]
+        self.ms_stats, self.ms_length = None, None
+        if ms_stats:
+            self._train_ms_sides(lambda: [u['record'] for u in sides[0]], [u['record'].data for u in sides[1]],
+                                 ms_length)
+
     def convert_f0(self, f0, key=0.0, fs=None):
         """the f0 track for synthesising a converted voice: voiced frames through the log-Gaussian transform of
         `f0_stats` (when trained with them), then transposed by `key` semitones; unvoiced frames stay 0.  fs: the
@@ -333,7 +464,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         modulation-spectrum statistics when there are any; the pitch ratio of the source waveforms; the re-alignment passes of the training as
         `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`; the structure of
         the covariances as `covariance` when it is not 'full'; the band-aperiodicity mixture as `ap_weights`, `ap_means`,
-        `ap_covariances` and `ap_covariance` when there is one)"""
+        `ap_covariances` and `ap_covariance` when there is one; for a converter trained by `train_nonparallel` the
+        iterations as `nonparallel` and a row (rows, monitor, EM iterations) per fit as `nonparallel_history`)"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
@@ -351,6 +483,10 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 band = self.ap_converter.gmm
                 extra.update(ap_weights=band.weights_, ap_means=band.means_, ap_covariances=band.covariances_,
                              ap_covariance=getattr(band, 'covariance_structure', 'full'))
+            if self.nonparallel is not None:       # (a model trained on parallel data has neither key)
+                extra.update(nonparallel=int(self.nonparallel), nonparallel_history=np.array(
+                    [[r['rows'], r['mcd'], -1 if r['em_iterations'] is None else r['em_iterations']]
+                     for r in self.nonparallel_history], dtype=np.float64).reshape(-1, 3))
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      source_f0_rate=float(self.source_f0_rate),
@@ -363,7 +499,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
         the file.  `f0_stats` / `gv_stats` / `ms_stats` are None for a file without them (written without these statistics, or before
         they existed); `source_f0_rate` is 1.0 for a file without it, `align_iterations` 0 and `align_history` empty,
-        the mixture's `covariance_structure` 'full'"""
+        the mixture's `covariance_structure` 'full', `nonparallel` None and `nonparallel_history` empty"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
@@ -407,6 +543,10 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             rows = z['align_rows'] if 'align_rows' in z.files else [None] * len(mcd)
             self.align_history = [dict(rows=None if n is None else int(n), mcd=float(v), em_iterations=None)
                                   for n, v in zip(rows, mcd)]
+            self.nonparallel = int(z['nonparallel']) if 'nonparallel' in z.files else None
+            history = z['nonparallel_history'] if 'nonparallel_history' in z.files else ()
+            self.nonparallel_history = [dict(rows=int(n), mcd=float(v), em_iterations=None if e < 0 else int(e))
+                                        for n, v, e in history]
         return self
 
     def gv_ascent_statistics(self):

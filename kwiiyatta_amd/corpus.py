@@ -511,6 +511,168 @@ def train_converter_realigned(pairs, fs, components=64, seed=None, align_iterati
     return (g, history, *rest)
 
 
+class _NonparallelSide:
+    """One side of a non-parallel training set in HBM: the utterances analysed in waves of <= 16 through the batched
+    entries (CheapTrick, D4C, sp2mc, voicing, the DTW feature rows whose power and voicing terms pick and mark the speech
+    frames: what `Analyzer` and `make_feature` do file by file), then per utterance the mel-cepstrum `mc` (T x
+    (order + 1)), the int32 list `speech` of its speech frames and the f0 track, and over all its speech frames in
+    utterance order `delta` (rows x 3 order: delta features of c1..cN over ALL frames, rows selected afterwards) and
+    `voicing` (rows).  The envelopes and aperiodicities of a wave go when the wave is done."""
+
+    def __init__(self, ls, utterances, fs, order, wave=16):
+        self.ls, self.order = ls, int(order)
+        dev, fs = ls.dev, int(fs)
+        f64 = dict(dtype=torch.float64, device=dev)
+        fft = lib.kwy_cheaptrick_fft_size(fs, 71.0)
+        K = fft // 2 + 1
+        from .backend import sptk
+        alpha = sptk.mcepalpha(fs)
+        h, J = ls.ctx.handle, _lib.job_array
+        chk = lambda rc: _lib.check(ls.ctx, rc)  # noqa: E731
+        self.mc, self.speech, self.f0, deltas, voicing = [], [], [], [], []
+        with torch.cuda.stream(ls.main):
+            for w0 in range(0, len(utterances), wave):
+                items = [[to_device(a, dev, (ls.main,)) for a in u] for u in utterances[w0:w0 + wave]]
+                x, f0, t = ([s[k] for s in items] for k in range(3))
+                n, layout = len(items), Ragged([len(v) for v in f0])
+                sp, ap = torch.empty((layout.total, K), **f64), torch.empty((layout.total, K), **f64)
+                mc = torch.empty((layout.total, order + 1), **f64)
+                feat = torch.empty((layout.total, order + 2), **f64)
+                voiced = torch.empty(layout.total, **f64)
+                sp_v, ap_v = layout.views(sp), layout.views(ap)
+                chk(lib.kwy_cheaptrick_batch_dev(h, _lib.utterance_array([(x[i], t[i], f0[i], sp_v[i]) for i in range(n)]),
+                                                 n, fs, -0.15, 71.0, fft, float(fs)))
+                chk(lib.kwy_d4c_batch_dev(h, _lib.utterance_array([(x[i], t[i], f0[i], ap_v[i]) for i in range(n)]), n, fs,
+                                          0.85, fft))
+                chk(lib.kwy_sp2mc_dev(h, _p(sp), layout.total, K, order, alpha, _p(mc)))
+                for i in range(n):
+                    chk(lib.kwy_is_voiced_dev(h, _p(f0[i]), _p(ap_v[i]), len(f0[i]), K, fs, _p(layout.view(voiced, i))))
+                # make_feature(vuv='voiced', power='binalize', power_pivot='max')
+                chk(lib.kwy_align_features_batch_dev(h, J(_lib.AlignJob, [(layout.view(mc, i), layout.view(voiced, i),
+                                                                           len(f0[i]), layout.view(feat, i))
+                                                                          for i in range(n)]),
+                                                     n, order + 1, POWER_WEIGHT, POWER_THRESHOLD, VUV_WEIGHT))
+                for i in range(n):
+                    rows = layout.view(feat, i)
+                    speech = torch.nonzero(rows[:, 0] > 0).flatten().to(torch.int32)
+                    self.mc.append(layout.view(mc, i))
+                    self.speech.append(speech)
+                    self.f0.append(f0[i])
+                    voicing.append(rows[:, 1][speech.long()])
+                    deltas.append(self.delta_rows(layout.view(mc, i), speech))
+            self.delta = torch.cat(deltas) if deltas else torch.empty((0, 3 * order), **f64)
+            self.voicing = torch.cat(voicing) if voicing else torch.empty(0, **f64)
+        self.rows = int(self.delta.shape[0])
+
+    def delta_rows(self, mc, speech):
+        """delta_features(c1..cN of `mc`, DELTA_WINDOWS)[speech] on the device (enqueued on the main stream)"""
+        ls, order, T = self.ls, self.order, int(mc.shape[0])
+        out = torch.empty((len(speech), 3 * order), dtype=torch.float64, device=ls.dev)
+        if T == 0 or len(speech) == 0:
+            return out
+        static = mc[:, 1:].contiguous()
+        count = torch.full((1,), T, dtype=torch.int64, device=ls.dev)
+        full = torch.empty((T, 3 * order), dtype=torch.float64, device=ls.dev)
+        _lib.check(ls.ctx, lib.kwy_delta_features_dev(ls.ctx.handle, _p(static), _p(count), T, order, _p(full)))
+        _lib.check(ls.ctx, lib.kwy_gather_rows_dev(ls.ctx.handle, _p(full), T, 3 * order, _p(speech), len(speech), _p(out)))
+        return out
+
+
+def train_converter_nonparallel(source, target, fs, components=64, seed=None, iterations=None, max_iter=100,
+                                device_index=0, order=24, lockstep=None, f0_moments=False, gv_moments=False, verbose=0,
+                                keep_matrices=False, covariance='full', splits=0):
+    """Non-parallel training (INCA) on the device: `MelCepstrumFeatureConverter.train_nonparallel` with the features in
+    HBM across the iterations.  source, target: lists of (x, f0, t) utterances that need not correspond.  Both sides are
+    analysed once (`_NonparallelSide`); mel-cepstra, delta features, search rows [voicing term | c1..cN | delta c1..cN]
+    and speech-frame index lists stay on the device.  Fit i = 0 .. iterations: kwy_convert_mcep_batch_dev on the source
+    utterances with the mixture fitted last (fit 0: their own mel-cepstra), kwy_delta_features_dev, two
+    kwy_nn_search_dev, kwy_gather_rows_dev into the joint matrix [x_k | y_p(k)] ; [x_q(j) | y_j], `fit_converter` from
+    scratch, and ONE read-back: the monitor (mean distortion over c1..cN across the joint rows between the static columns
+    the search used) with the searches' status words.
+    Returns (mixture, history[, f0 moments][, gv statistic]): history holds a dict per fit -- rows, mcd, em_iterations,
+    seconds (wall clock of the whole iteration, the fit included) and with keep_matrices=True its matrix X; the moments are the merged voiced log-f0 triples of (source, target), the
+    statistic the target's global variance."""
+    from .backend import distortion as dist, nn
+    from .converter.mcep import MelCepstrumFeatureConverter as _M
+    if iterations is None:
+        iterations = _M.NONPARALLEL_DEFAULT
+    lo, hi = _M.NONPARALLEL_RANGE
+    if isinstance(iterations, bool) or int(iterations) != iterations or not lo <= iterations <= hi:
+        raise ValueError(f'iterations must be an integer within [{lo}, {hi}], not {iterations!r}')
+    if not len(source) or not len(target):
+        raise ValueError(f'nonparallel: no {"source" if not len(source) else "target"} files')
+    ls = lockstep if lockstep is not None else _Lockstep(device_index)
+    dev, ctx, h = ls.dev, ls.ctx, ls.ctx.handle
+    f64 = dict(dtype=torch.float64, device=dev)
+    src, tgt = (_NonparallelSide(ls, side, fs, order) for side in (source, target))
+    ns, nt = src.rows, tgt.rows
+    if not ns or not nt:
+        raise ValueError(f'nonparallel: no speech frames ({ns} on the source side, {nt} on the target side)')
+    history, g = [], None
+    with torch.cuda.stream(ls.main):
+        T = torch.cat((tgt.voicing[:, None], tgt.delta[:, :2 * order]), dim=1).contiguous()
+        p, q = (torch.empty(n, dtype=torch.int32, device=dev) for n in (ns, nt))
+        d2 = torch.empty(max(ns, nt), **f64)
+        own = torch.arange(max(ns, nt), dtype=torch.int32, device=dev)
+        words = torch.zeros(5, **f64)            # the monitor's (n, mean, M2), then the two searches' status words
+        status = torch.zeros(3, dtype=torch.int32, device=dev)
+        _lib.check(ctx, lib.kwy_ctx_reserve(h, nn.scratch_bytes(max(ns, nt), splits)))
+    import time
+    for it in range(int(iterations) + 1):
+        started = time.perf_counter()
+        with torch.cuda.stream(ls.main):
+            if g is None:
+                mapped = src.delta[:, :2 * order]
+            else:
+                dg = DeviceGMM(g.weights_, g.means_, g.covariances_, dev)
+                outs = [torch.empty_like(mc) for mc in src.mc]
+                _lib.check(ctx, lib.kwy_convert_mcep_batch_dev(
+                    h, _lib.job_array(_lib.ConvertJob, [(mc, mc.shape[0], out) for mc, out in zip(src.mc, outs)]),
+                    len(outs), order, dg.M, _p(dg.model(diff=False))))
+                mapped = torch.cat([src.delta_rows(out, sp) for out, sp in zip(outs, src.speech)])[:, :2 * order]
+            S = torch.cat((src.voicing[:, None], mapped), dim=1).contiguous()
+            nn.nearest_dev(ctx, S, T, p, d2, status[0:1], splits=splits)
+            nn.nearest_dev(ctx, T, S, q, d2, status[1:2], splits=splits)
+            X = torch.empty((ns + nt, 6 * order), **f64)
+            half = torch.empty((max(ns, nt), 3 * order), **f64)
+            X[:ns, :3 * order] = src.delta
+            X[ns:, 3 * order:] = tgt.delta
+            _lib.check(ctx, lib.kwy_gather_rows_dev(h, _p(tgt.delta), nt, 3 * order, _p(p), ns, _p(half)))
+            X[:ns, 3 * order:] = half[:ns]
+            _lib.check(ctx, lib.kwy_gather_rows_dev(h, _p(src.delta), ns, 3 * order, _p(q), nt, _p(half)))
+            X[ns:, :3 * order] = half[:nt]
+            idx_a, idx_b = torch.cat((own[:ns], q)), torch.cat((p, own[:nt]))
+            dist.mcd_batch_dev(ctx, [dist.mcd_job(S[:, 1:order + 1], T[:, 1:order + 1], idx_a, idx_b)], order,
+                               words[:3].view(1, 3), status[2:3], first_col=0)
+            words[3:] = status[:2]
+            n, mean, _, bad_p, bad_q = words.cpu().tolist()          # (the one read-back of the iteration; it synchronises)
+        if bad_p or bad_q:
+            nn.check_status([int(bad_p) + int(bad_q)], 'nonparallel')
+        ls.sync()
+        g = fit_converter(X, components=components, seed=seed, max_iter=max_iter, device_index=device_index,
+                          verbose=verbose, covariance=covariance)
+        history.append(dict(rows=int(X.shape[0]), mcd=float(mean) if n > 0 else float('nan'),
+                            em_iterations=int(g.n_iter_), seconds=time.perf_counter() - started,
+                            **(dict(X=X) if keep_matrices else {})))
+    rest = []
+    if f0_moments:
+        from .backend import f0 as f0map
+        with torch.cuda.stream(ls.main):
+            merged = torch.empty((2, 3), **f64)
+            for k, side in enumerate((src, tgt)):
+                rows = torch.empty((len(side.f0), 3), **f64)
+                f0map.logf0_moments_batch_dev(ctx, side.f0, rows)
+                f0map.merge_moments_dev(ctx, rows, merged[k])
+            rest.append(merged.cpu().numpy())
+    if gv_moments:
+        gv = _PairGV(len(tgt.mc), order, device_index)
+        with torch.cuda.stream(ls.main):
+            gv.add(ctx, 0, tgt.mc)
+        ls.sync()
+        rest.append(gv.statistic())
+    return (g, history, *rest)
+
+
 class EvalWave(TrainWave):
     """<= 16 parallel pairs -> their evaluation figures (kwiiyatta_amd.evaluate_voice), in lockstep: analysed, trimmed,
     padded and aligned exactly as TrainWave does it (`analyse`, `align`: the same pad rows in the same order), the

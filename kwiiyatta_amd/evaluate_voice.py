@@ -269,7 +269,13 @@ def overlap_warning(trained, evaluated):
 def training_record_lines(converter):
     """the record of a training with --align-iterations, a line per fit: the rows of its joint matrix and the monitor,
     the mean distortion along the training alignment between the target and the source coefficients that alignment was
-    found with (fit 0: the source's own, fit k: converted by fit k - 1).  Nothing for a converter aligned once"""
+    found with (fit 0: the source's own, fit k: converted by fit k - 1).  Nothing for a converter aligned once.
+    For a training with --nonparallel: a line per fit of `nonparallel_history` instead"""
+    if getattr(converter, 'nonparallel', None) is not None:
+        # a training with --nonparallel: the rows are the speech frames of both sides, the monitor runs across the
+        # nearest-neighbour pairs of the fit
+        return [f'non-parallel fit {it}: rows {r["rows"]} monitor MCD {r["mcd"]:.3f} dB'
+                for it, r in enumerate(converter.nonparallel_history)]
     history = getattr(converter, 'align_history', None) or []
     if not getattr(converter, 'align_iterations', 0):
         return []
@@ -371,7 +377,12 @@ def main():
         conf.parser.error('no files to evaluate: --eval-skip-files / --eval-max-files leave none of the '
                           f'{len(dataset.keys())} common files of --source and --target')
     if training:
-        warning = overlap_warning(file_slice(dataset.keys(), conf.skip_files, conf.max_files), keys)
+        if conf.nonparallel is not None:           # either side's training files, picked per directory
+            trained = set().union(*(file_slice(side.keys(), conf.skip_files, conf.max_files)
+                                    for side in conf.nonparallel_sides(1.0)))
+        else:
+            trained = file_slice(dataset.keys(), conf.skip_files, conf.max_files)
+        warning = overlap_warning(trained, keys)
         if warning:
             print(warning, file=sys.stderr)
     converter = conf.train_converter(use_delta=True, f0_stats=conf.convert_f0, gv_stats=conf.gv > 0,
