@@ -1187,6 +1187,46 @@ int kwy_nn_search_dev(kwy_ctx *ctx, const double *Q, int64_t nq, const double *C
 size_t kwy_nn_scratch_bytes(int64_t nq, int splits);
 int64_t kwy_nn_slice(int64_t nc, int splits);
 
+/* ---- exemplar-based conversion: KL-NMF activations over coupled dictionaries --------------------------
+ * The exemplar converter (Takashima et al. 2012; Wu, Virtanen, Chng, Li 2014): the aligned training frames are the
+ * model, a source frame is explained as a sparse non-negative combination of source exemplars, and the same
+ * activations applied to the paired target exemplars are the converted frame.  The reference has no counterpart.
+ * Row-major doubles:  S: A x B source atoms, Tg: A x B target atoms, X: T x B frames.  Every entry is finite and > 0,
+ * and every atom of S and Tg and every frame of X has unit sum over its B bins (the caller's preparation: the
+ * entry does not scale and does not check the sums).
+ *   H (T x A) starts at all ones, or at h0 (T x A, entries finite and >= 0) when h0 is not NULL.  For n = 1 .. N:
+ *       R = H S                      (T x B)
+ *       Q = X / max(R, DBL_MIN)      element by element
+ *       G = Q S^T                    (T x A)
+ *       H <- (H * G) / (1 + lambda)  element by element; atom sums are 1, so the usual denominator S^T 1 + lambda
+ *                                    is this constant
+ *   Y = H Tg (T x B); H itself (T x A); objective[t] = sum_b (x log(x / max(r, DBL_MIN)) - x + r) + lambda sum_a h
+ *   with r = H S of the final H.  Each of Y, H, objective may be NULL; Tg and Y are given together or both NULL.
+ *   Frames never interact: a frame's outputs depend on its own row of X (and of h0) only, not on T nor on the other
+ *   rows.  The result after n updates does not depend on N: N updates are the first N of any longer run.
+ *   Every element of every product is one v_mfma_f64_16x16x4_f64 accumulator chain over its k (atoms for R and Y,
+ *   bins for G) in ascending order starting from zero, four k per step; nothing is contracted.  The order is fixed
+ *   within one build: a call is bit-reproducible from run to run, and H after n updates is the same bits whether
+ *   one call ran n updates or n calls of one update were chained through h0.  It uses no atomics.
+ *   status[0] (may be NULL; set, not accumulated): the number of entries of S, Tg and X that are not finite and > 0
+ *   plus those of h0 that are not finite and >= 0.  The outputs are written all the same, from the values as given,
+ *   and mean nothing when the status is not zero; nothing aborts on the device.
+ * KWY_EINVAL, nothing written and nothing launched: A outside [1, 8192], B outside [2, 2049], T < 0 or above
+ * 2^31 - 1, N outside [0, 1000], lambda negative or not finite, and with T > 0: a null S or X, Tg without Y or Y
+ * without Tg, no output asked for, and for the _dev form a scratch buffer that is NULL or smaller than
+ * kwy_nmf_scratch_bytes(A, B, T).  T = 0 is KWY_OK and writes nothing.
+ * The _dev form takes device pointers, runs on the context's stream, does not synchronise and allocates nothing:
+ * its scratch (zero-padded copies of S, Tg, X, and Q and H) is the caller's buffer.  A ragged batch of utterances
+ * is one call with T the sum of their frames. */
+int kwy_nmf_convert(kwy_ctx *ctx, const double *S, const double *Tg, const double *X, int A, int B, int64_t T,
+                    int iterations, double sparsity, const double *h0, double *Y, double *H, double *objective,
+                    int32_t *status);
+int kwy_nmf_convert_dev(kwy_ctx *ctx, const double *S, const double *Tg, const double *X, int A, int B, int64_t T,
+                        int iterations, double sparsity, const double *h0, double *Y, double *H, double *objective,
+                        int32_t *status, void *scratch, size_t scratch_bytes);
+/* pure host arithmetic, no device needed; 0 for T <= 0 and for sizes outside the limits */
+size_t kwy_nmf_scratch_bytes(int A, int B, int64_t T);
+
 /* ---- training-set path (device-resident) ---------------------------------------------------------
  * What the reference does per parallel pair before the converter fit (Config.load_dataset ->
  * align_dataset -> MelCepstrumDataset -> DeltaFeatureDataset -> make_dataset_to_array,

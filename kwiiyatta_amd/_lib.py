@@ -186,6 +186,10 @@ SIGNATURES = {
     'kwy_nn_search_dev': (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp]),
     'kwy_nn_scratch_bytes': (ctypes.c_size_t, [c_i64, c_int]),
     'kwy_nn_slice': (c_i64, [c_i64, c_int]),
+    'kwy_nmf_convert': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'kwy_nmf_convert_dev': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, ctypes.c_size_t]),
+    'kwy_nmf_scratch_bytes': (ctypes.c_size_t, [c_int, c_int, c_i64]),
     'kwy_gmm_mlpg': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     'kwy_gmm_mlpg_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     'kwy_gmm_convert_frames': (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),

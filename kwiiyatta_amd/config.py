@@ -12,6 +12,11 @@ import numpy as np
 
 from .backend.ms import LENGTHS as MS_LENGTHS
 
+class _Unset(int):
+    """the default of an option whose presence on the command line matters: the number it stands for, told apart
+    from a typed one by its class"""
+
+
 VOCODER_OPTIONS = (
     ('--frame-period', dict(type=int, default=5, help='Frame period milli-seconds of vocoder')),
     ('--mcep-order', dict(type=int, default=24, help='Mel-cepstrum order for spectrum envelope')),
@@ -22,7 +27,7 @@ CONVERTER_OPTIONS = (
     ('--max-files', dict(type=int, help='File num to train feature converter')),
     ('--skip-files', dict(type=int, help='Skip file num to train feature converter')),
     ('--mcep-fs', dict(type=int, help='Sampling rate of training mel cepstrum')),
-    ('--converter-components', dict(type=int, default=64, help='Components num for feature converter')),
+    ('--converter-components', dict(type=int, default=_Unset(64), help='Components num for feature converter')),
     ('--converter-seed', dict(type=int, help='Random seed for feature converter')),
     # an addition to the reference's options: keep the trained converter between runs
     ('--converter-model', dict(type=str, help='File of the trained converter: loaded when it exists (no training, '
@@ -288,6 +293,73 @@ APERIODICITY_OPTIONS = (
 )
 
 
+CONVERTERS = ('gmm', 'exemplar')
+EXEMPLAR_FFT_SIZES = (256, 512, 1024, 2048, 4096)        # converter.exemplar.FFT_SIZES
+EXEMPLARS_RANGE = (1, 8192)                              # backend.nmf.MAX_ATOMS
+EXEMPLAR_ITERATIONS_RANGE = (0, 1000)                    # backend.nmf.MAX_ITERATIONS
+
+
+def _int_within(lo, hi, what):
+    def parse(text):
+        try:
+            n = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f'invalid {what}: {text!r}') from None
+        if not lo <= n <= hi:
+            raise argparse.ArgumentTypeError(f'{text} is outside [{lo}, {hi}]')
+        return n
+    return parse
+
+
+def exemplar_sparsity(text):
+    """--exemplar-sparsity: the weight of the L1 term of the activations, finite and >= 0"""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f'invalid sparsity: {text!r}') from None
+    if not (value >= 0 and math.isfinite(value)):
+        raise argparse.ArgumentTypeError(f'{text} is not a finite sparsity >= 0')
+    return value
+
+
+# an addition to the reference's options (its converter is the joint-density mixture)
+CONVERTER_OPTIONS += (
+    ('--converter', dict(choices=CONVERTERS, default='gmm',
+                         help='The spectral converter: gmm, the joint-density mixture with MLPG of the reference, or '
+                              'exemplar -- the aligned training frames themselves as two coupled dictionaries, a source '
+                              'frame explained as a sparse non-negative combination of source exemplars (KL-NMF '
+                              'activations) and the same activations applied to the paired target exemplars; nothing '
+                              'is fitted, there is no component count; kept in the converter model.  exemplar goes '
+                              'with none of --mlpg-em, --mlpg-gv, --converter-covariance, --converter-components, '
+                              '--convert-aperiodicity, --nonparallel and --batch')),
+    ('--exemplars', dict(type=_int_within(*EXEMPLARS_RANGE, 'exemplar count'), default=None, metavar='A',
+                         help='Exemplars the dictionary keeps at the most (within [1, 8192]): of R > A aligned training '
+                              'rows the rows floor(i R / A); a loaded converter model decides')),
+    ('--exemplar-iterations', dict(type=_int_within(*EXEMPLAR_ITERATIONS_RANGE, 'iteration count'), default=None,
+                                   metavar='N', help='Multiplicative updates of the activations (within [0, 1000]); a '
+                                                     'loaded converter model decides')),
+    ('--exemplar-sparsity', dict(type=exemplar_sparsity, default=None, metavar='L',
+                                 help='Weight of the L1 term on the activations (>= 0); a loaded converter model '
+                                      'decides')),
+    ('--exemplar-fft', dict(type=int, choices=EXEMPLAR_FFT_SIZES, default=None,
+                            help='Transform length of the envelopes the activations work on (FFT / 2 + 1 bins); a '
+                                 'loaded converter model decides')),
+)
+
+# what does not go with --converter exemplar: (attribute, whether it is asked for, flag, why)
+EXEMPLAR_CONFLICTS = (
+    ('mlpg_em', lambda v: v is not None, '--mlpg-em', 'it re-estimates the posteriors of a mixture'),
+    ('mlpg_gv', lambda v: v is not None, '--mlpg-gv', 'it ascends the likelihood of a mixture\'s trajectory'),
+    ('converter_covariance', lambda v: v is not None, '--converter-covariance', 'there are no covariances'),
+    ('converter_components', lambda v: v is not None and not isinstance(v, _Unset), '--converter-components',
+     'there are no components'),
+    ('convert_aperiodicity', bool, '--convert-aperiodicity', 'the band conversion is a mixture'),
+    ('nonparallel', lambda v: v is not None, '--nonparallel', 'its search runs on the delta features of a mixture stack'),
+    ('batch', bool, '--batch', 'the lockstep drivers take a mixture; the exemplar stage is not wired into them yet'),
+)
+EXEMPLAR_OPTIONS = ('exemplars', 'exemplar_iterations', 'exemplar_sparsity', 'exemplar_fft')
+
+
 def _pkg():
     import kwiiyatta_amd
     return kwiiyatta_amd
@@ -349,6 +421,14 @@ class Config:
             if getattr(self, 'ms', 0.0) > 0:
                 self.parser.error('--mlpg-gv does not go with --ms: composing it with the modulation-spectrum filter is '
                                   'left for later')
+        if getattr(self, 'converter', 'gmm') == 'exemplar':
+            for name, asked, flag, why in EXEMPLAR_CONFLICTS:
+                if asked(getattr(self, name, None)):
+                    self.parser.error(f'{flag} does not go with --converter exemplar: {why}')
+        else:
+            for name in EXEMPLAR_OPTIONS:
+                if getattr(self, name, None) is not None:
+                    self.parser.error(f'--{name.replace("_", "-")} needs --converter exemplar')
         if getattr(self, 'nonparallel', None) is not None:
             if getattr(self, 'align_iterations', None) is not None:
                 self.parser.error('--nonparallel does not go with --align-iterations: there are no pairs to align '
@@ -364,7 +444,12 @@ class Config:
 
     def create_converter(self, Converter=None, **kwargs):
         make = Converter or _pkg().MelCepstrumConverter
-        chosen = dict(random_state=self.converter_seed, components=self.converter_components)
+        if getattr(self, 'converter', 'gmm') == 'exemplar':
+            chosen = dict(converter='exemplar', **{name: getattr(self, name, None) for name in EXEMPLAR_OPTIONS})
+            if self.mcep_fs is not None:
+                chosen['mcep_fs'] = self.mcep_fs
+            return make(**dict(chosen, **kwargs))
+        chosen = dict(random_state=self.converter_seed, components=int(self.converter_components))
         if self.mcep_fs is not None:
             chosen['mcep_fs'] = self.mcep_fs
         if getattr(self, 'converter_covariance', None) is not None:
@@ -466,6 +551,12 @@ class Config:
         converter = self.create_converter(**kwargs)
         model = getattr(self, 'converter_model', None)
         if model is not None and pathlib.Path(model).is_file():
+            with np.load(model, allow_pickle=False) as z:
+                kind = str(z['converter']) if 'converter' in z.files else 'gmm'
+            mine = getattr(converter, 'kind', 'gmm')
+            if kind != mine:
+                self.parser.error(f'{model}: the converter model was trained with --converter {kind}, not {mine}; '
+                                  f'retrain it with --converter {mine} (a new --converter-model file)')
             converter.load(model)
             asked = getattr(self, 'source_f0_rate', None)
             if isinstance(asked, float) and asked != converter.source_f0_rate:

@@ -132,6 +132,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             coefficients = MelCepstrumDataset(dataset, mcep_fs=self.mcep_fs)
             self.base.train(coefficients, keys, **kwargs)
             self.order, self.fs = coefficients.order, coefficients.fs
+            self._bind_rate()
         self.f0_stats = None
         if f0_stats:
             from ..backend import f0 as f0map
@@ -305,6 +306,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                     joint, n, _ = bap.rows(x.band_track, y.band_track, lists[0], lists[1])
                     band_blocks.append(joint[:n])
             matrix = np.concatenate(blocks)
+            self._bind_rate()
             self._train(matrix, **fit_options)
             if band_blocks:
                 band_matrix = np.concatenate(band_blocks)
@@ -447,6 +449,21 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             self._train_ms_sides(lambda: [u['record'] for u in sides[0]], [u['record'].data for u in sides[1]],
                                  ms_length)
 
+    @property
+    def kind(self):
+        """'gmm', or 'exemplar' for a stack on an ExemplarFeatureConverter: what a model file's `converter` names"""
+        try:
+            return self.base.kind
+        except AttributeError:
+            return 'gmm'
+
+    def _bind_rate(self):
+        """hand the sampling rate to an innermost stage that works on spectra (the exemplar converter needs the
+        all-pass constant); the mixture stages have no use for it"""
+        bind = getattr(self.base, 'bind_rate', None)
+        if bind is not None:
+            bind(self.fs)
+
     def convert_f0(self, f0, key=0.0, fs=None):
         """the f0 track for synthesising a converted voice: voiced frames through the log-Gaussian transform of
         `f0_stats` (when trained with them), then transposed by `key` semitones; unvoiced frames stay 0.  fs: the
@@ -465,10 +482,17 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         `align_iterations` with the monitor and row count of every fit as `align_mcd` / `align_rows`; the structure of
         the covariances as `covariance` when it is not 'full'; the band-aperiodicity mixture as `ap_weights`, `ap_means`,
         `ap_covariances` and `ap_covariance` when there is one; for a converter trained by `train_nonparallel` the
-        iterations as `nonparallel` and a row (rows, monitor, EM iterations) per fit as `nonparallel_history`)"""
+        iterations as `nonparallel` and a row (rows, monitor, EM iterations) per fit as `nonparallel_history`).
+        A stack on the exemplar converter writes `converter: 'exemplar'` and, in the mixture's place, its dictionaries
+        and settings: `exemplar_source`, `exemplar_target`, `exemplar_fft`, `exemplar_iterations`, `exemplar_sparsity`
+        (and `exemplar_rows`); a file without `converter` is a mixture's"""
         gmm = self.gmm
         with open(path, 'wb') as fh:        # a file object: np.savez would append '.npz' to a bare name
             extra = {} if self.f0_stats is None else dict(f0_stats=np.array(self.f0_stats, dtype=np.float64))
+            if self.kind == 'exemplar':     # the dictionaries in the mixture's place (a mixture's file has no `converter`)
+                model = dict(converter='exemplar', **self.base.model_arrays())
+            else:
+                model = dict(weights=gmm.weights_, means=gmm.means_, covariances=gmm.covariances_)
             if self.gv_stats is not None:
                 extra['gv_stats'] = np.array(self.gv_stats, dtype=np.float64)
             if self.gv_var is not None:
@@ -493,7 +517,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                      align_iterations=int(self.align_iterations),
                      align_mcd=np.array([r['mcd'] for r in self.align_history], dtype=np.float64),
                      align_rows=np.array([r['rows'] for r in self.align_history], dtype=np.int64),
-                     weights=gmm.weights_, means=gmm.means_, covariances=gmm.covariances_, **extra)
+                     **model, **extra)
 
     def load(self, path):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
@@ -503,6 +527,9 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
+            kind = str(z['converter']) if 'converter' in z.files else 'gmm'
+            if kind != self.kind:
+                raise ValueError(f'{path!s}: a model of the {kind} converter, not of the {self.kind} converter')
             self.order, self.fs = int(z['order']), int(z['fs'])
             from .delta import DeltaFeatureConverter
             stage = self.base
@@ -511,13 +538,17 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                     period = float(z['frame_period'])
                     stage.frame_period = int(period) if period.is_integer() else period
                 stage = stage.base
-            gmm = self.gmm
-            gmm.weights_ = np.array(z['weights'], dtype=np.float64)
-            gmm.means_ = np.array(z['means'], dtype=np.float64)
-            gmm.covariances_ = np.array(z['covariances'], dtype=np.float64)
-            gmm.n_components = len(gmm.weights_)
-            gmm.covariance_structure = str(z['covariance']) if 'covariance' in z.files else 'full'
-            gmm.converged_ = True
+            if kind == 'exemplar':
+                self.base.load_arrays(z)
+                self._bind_rate()
+            else:
+                gmm = self.gmm
+                gmm.weights_ = np.array(z['weights'], dtype=np.float64)
+                gmm.means_ = np.array(z['means'], dtype=np.float64)
+                gmm.covariances_ = np.array(z['covariances'], dtype=np.float64)
+                gmm.n_components = len(gmm.weights_)
+                gmm.covariance_structure = str(z['covariance']) if 'covariance' in z.files else 'full'
+                gmm.converged_ = True
             self.f0_stats = tuple(float(v) for v in z['f0_stats']) if 'f0_stats' in z.files else None
             self.gv_stats = np.array(z['gv_stats'], dtype=np.float64) if 'gv_stats' in z.files else None
             self.gv_var = np.array(z['gv_var'], dtype=np.float64) if 'gv_var' in z.files else None

@@ -8,7 +8,7 @@ mkdir -p obj
 PIDS=()
 for f in $SRCS; do
   o=obj/${f%.hip}.o
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ kwy_device.hpp -nt "$o" ] || [ kwy_fft.hpp -nt "$o" ] || [ kwy_mfma.hpp -nt "$o" ] || [ kwy_internal.hpp -nt "$o" ] || [ ../../include/kwy.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ kwy_device.hpp -nt "$o" ] || [ kwy_fft.hpp -nt "$o" ] || [ kwy_mfma.hpp -nt "$o" ] || [ kwy_internal.hpp -nt "$o" ] || [ kwy_nmf_args.hpp -nt "$o" ] || [ ../../include/kwy.h -nt "$o" ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 -c "$f" -o "$o" &
     PIDS+=($!)
   fi

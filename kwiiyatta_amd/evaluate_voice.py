@@ -271,6 +271,15 @@ def training_record_lines(converter):
     the mean distortion along the training alignment between the target and the source coefficients that alignment was
     found with (fit 0: the source's own, fit k: converted by fit k - 1).  Nothing for a converter aligned once.
     For a training with --nonparallel: a line per fit of `nonparallel_history` instead"""
+    if getattr(converter, 'kind', 'gmm') == 'exemplar':
+        stage = converter.base
+        size = [f'exemplar dictionary: {len(stage.source)} exemplars of {stage.rows} training rows, '
+                f'{stage.fft // 2 + 1} bins, {stage.iterations} iterations, sparsity {stage.sparsity:g}']
+        history = getattr(converter, 'align_history', None) or []
+        if not getattr(converter, 'align_iterations', 0):
+            return size
+        return size + [f'training alignment {it}: rows {"?" if r["rows"] is None else r["rows"]} monitor MCD '
+                       f'{r["mcd"]:.3f} dB' for it, r in enumerate(history)]
     if getattr(converter, 'nonparallel', None) is not None:
         # a training with --nonparallel: the rows are the speech frames of both sides, the monitor runs across the
         # nearest-neighbour pairs of the fit
