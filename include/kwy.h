@@ -170,6 +170,77 @@ int kwy_stonemask_dev(kwy_ctx *ctx, const double *x, int64_t x_length, int fs,
 /* utterances[i].out: the refined f0 (f0_length values); .f0: the initial track */
 int kwy_stonemask_batch_dev(kwy_ctx *ctx, const kwy_utterance *utterances, int count, int fs);
 
+/* ---- probabilistic YIN: the second f0 estimator (Mauch & Dixon 2014) --------------------------------------
+ * A coarse f0 track on DIO's frame grid (kwy_dio_frames frames, t_i = i frame_period), refined by StoneMask like
+ * DIO's.  Voicing and pitch are decided jointly by a Viterbi pass over the utterance.  The reference has no
+ * counterpart.  Parameters (the defaults of the Python front-end): f0_floor 71, f0_ceil 800, p_a 0.01, switch
+ * probability 0.01, maximal pitch rate 35.92 octaves / s; KWY_PYIN_BINS_PER_OCTAVE pitch bins an octave (10 cents).
+ *   tau_min = floor(fs / f0_ceil), tau_max = ceil(fs / f0_floor), W = tau_max + 1
+ *   nb = kwy_pyin_bins     = ceil(120 log2(f0_ceil / f0_floor))                      (420 at the defaults)
+ *   R  = kwy_pyin_radius   = ceil(max_rate 120 frame_period / 1000)                  (22 at 5 ms)
+ *   N  = kwy_pyin_fft_size = the smallest power of two >= 2 W and >= 1024            (1024 at 16 kHz, 2048 at 48 kHz)
+ * 1 frame        c = floor(t_i fs + 0.5); the frame is x[c - W .. c + W), zeros outside the signal.
+ * 2 difference   d(tau) = sum_{j < W} (x_j - x_{j + tau})^2 for tau <= tau_max + 1, formed as e(0) + e(tau) - 2 r(tau):
+ *                r the correlation of the first W samples with the whole frame (two real transforms of length N, a
+ *                product, one inverse), e the sliding energy from a prefix sum.  A value below
+ *                2^-40 (e(0) + e(tau)) counts as 0: a constant or silent frame has no candidates.
+ * 3 normalise    d'(0) = 1; d'(tau) = d(tau) tau / sum_{j = 1 .. tau} d(j), and 1 where that sum is 0.
+ * 4 candidates   every tau in [max(tau_min, 1), tau_max] with d'(tau) < d'(tau - 1) and d'(tau) <= d'(tau + 1); with
+ *                a = d'(tau - 1), b = d'(tau), c = d'(tau + 1) and a - 2 b + c > 0 the parabola gives the offset
+ *                (a - c) / (2 (a - 2 b + c)) and the trough value v = max(b - (a - c) offset / 4, 0); else 0 and b.
+ * 5 prior        Beta(2, 18) over a CONTINUOUS threshold, F(v) = 1 - (1 - v)^18 (1 + 18 v) on [0, 1] (no probability
+ *                jumps with a rounding error of v; the paper has 100 discrete thresholds).  The candidates are walked
+ *                in ascending tau with a running minimum m = 1: one with v < m receives F(m) - F(v) and sets m = v;
+ *                the last one that set m also receives p_a F(m).
+ * 6 observation  a candidate of frequency f = fs / (tau + offset) falls into bin floor(120 log2(f / f0_floor));
+ *                outside [0, nb) it is dropped.  p_b: the masses of bin b, added in ascending tau.  The stage writes
+ *                L (T x (nb + 1) doubles): L[t][b] = log max(p_b, 1e-300), L[t][nb] = log max((1 - sum p_b) / nb,
+ *                1e-300), the value of every unvoiced state.
+ * 7 decoding     2 nb states (voiced bin b, unvoiced bin b), uniform start.  A step from bin s to bin s + k, |k| <= R,
+ *                weighs (R + 1 - |k|) / (R + 1)^2 (NOT renormalised at the ends of the bin range), times 1 - switch
+ *                where the voicing stays and times switch where it changes.  trans: the 2 (2 R + 1) logarithms of
+ *                those, [kept | changed][k + R], formed on the host; the device adds and compares only
+ *                (delta' = max(delta + trans) + L, nothing contracted).  Of equal predecessors the one of the same
+ *                voicing wins, within each voicing the lowest bin; at the end the lowest state.  freq[b]: the track's
+ *                value for voiced bin b, f0_floor 2^((b + 1/2) / 120); an unvoiced state gives 0.
+ * 8 status       a non-finite sample sets the utterance's status word (cleared by the call otherwise) and makes its
+ *                track all zero; the entries on host pointers return KWY_EINVAL.  No other utterance of a batch is
+ *                touched by it.
+ * KWY_EINVAL, nothing written: N > 4096 (the frame no longer fits one workgroup's transform: 96 kHz is the highest
+ * rate at f0_floor 71), 2 nb > 1024 (one thread per state), R > 8191, p_a outside [0, 1], switch outside (0, 1), and
+ * what kwy_dio refuses.
+ * Scratch: L and the 16-bit back-pointers (T x 2 nb) live in the context's arena; the _dev entries do not allocate
+ * once it holds kwy_pyin_scratch_bytes(frames of the longest utterance, nb, count) bytes (kwy_ctx_reserve), and all
+ * launches of a call are enqueued without a host round trip.  The batch form takes <= 32 utterances per pass of
+ * launches and is a drop-in for kwy_dio_batch_dev; every job's result equals the single entries' bit for bit. */
+#define KWY_PYIN_BINS_PER_OCTAVE 120
+/* pure host arithmetic, no device needed; 0 (kwy_pyin_radius: -1) for an argument out of range */
+int kwy_pyin_fft_size(int fs, double f0_floor);
+int kwy_pyin_bins(double f0_floor, double f0_ceil);
+int kwy_pyin_radius(double frame_period_ms, double max_rate);
+size_t kwy_pyin_scratch_bytes(int64_t frames, int nb, int count);
+int kwy_pyin(kwy_ctx *ctx, const double *x, int64_t x_length, int fs, double f0_floor, double f0_ceil,
+             double frame_period_ms, double p_a, double switch_prob, double max_rate, double *temporal_positions,
+             double *f0);
+int kwy_pyin_dev(kwy_ctx *ctx, const double *x, int64_t x_length, int fs, double f0_floor, double f0_ceil,
+                 double frame_period_ms, double p_a, double switch_prob, double max_rate, double *temporal_positions,
+                 double *f0, int32_t *status);
+int kwy_pyin_batch_dev(kwy_ctx *ctx, const kwy_f0_job *jobs, int count, int fs, double f0_floor, double f0_ceil,
+                       double frame_period_ms, double p_a, double switch_prob, double max_rate);
+/* steps 1 - 6 alone: L, kwy_dio_frames(...) x (kwy_pyin_bins(...) + 1).  status (may be NULL): set for a non-finite
+ * sample that one of the FRAMES reads (it counts as 0 there); unlike the whole estimator, which looks through the whole
+ * waveform in front of the decoding, this entry does not see a sample between the frames of a window narrower than
+ * the frame period (2 W < frame_period fs / 1000: an f0_floor above 400 Hz at 5 ms). */
+int kwy_pyin_observe(kwy_ctx *ctx, const double *x, int64_t x_length, int fs, double f0_floor, double f0_ceil,
+                     double frame_period_ms, double p_a, double *L);
+int kwy_pyin_observe_dev(kwy_ctx *ctx, const double *x, int64_t x_length, int fs, double f0_floor, double f0_ceil,
+                         double frame_period_ms, double p_a, double *L, int32_t *status);
+/* step 7 alone on the caller's L (T x (nb + 1)), trans (2 (2 R + 1)) and freq (nb): f0, T values */
+int kwy_pyin_decode(kwy_ctx *ctx, const double *L, int64_t T, int nb, const double *trans, int R, const double *freq,
+                    double *f0);
+int kwy_pyin_decode_dev(kwy_ctx *ctx, const double *L, int64_t T, int nb, const double *trans, int R,
+                        const double *freq, double *f0);
+
 /* ---- WORLD synthesis ------------------------------------------------------------ */
 /* pyworld.synthesize(f0, sp, ap, fs, frame_period)   kwiiyatta/vocoder/world.py:86-92
  * sp_mul: every spectrogram value is multiplied by this before use (pass fs to

@@ -89,6 +89,17 @@ SIGNATURES = {
     'kwy_dio_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_dbl]),
     'kwy_stonemask_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp]),
     'kwy_stonemask_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int]),
+    'kwy_pyin_fft_size': (c_int, [c_int, c_dbl]),
+    'kwy_pyin_bins': (c_int, [c_dbl, c_dbl]),
+    'kwy_pyin_radius': (c_int, [c_dbl, c_dbl]),
+    'kwy_pyin_scratch_bytes': (ctypes.c_size_t, [c_i64, c_int, c_int]),
+    'kwy_pyin': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp]),
+    'kwy_pyin_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp, c_vp]),
+    'kwy_pyin_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl]),
+    'kwy_pyin_observe': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_vp]),
+    'kwy_pyin_observe_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_vp, c_vp]),
+    'kwy_pyin_decode': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp]),
+    'kwy_pyin_decode_dev': (c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp]),
     'kwy_finish_pcm16_batch_dev': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_dbl, c_int, c_dbl]),
     'kwy_finish_scratch_bytes': (c_i64, [c_i64]),
     'kwy_logf0_moments': (c_int, [c_vp, c_vp, c_int, c_vp]),

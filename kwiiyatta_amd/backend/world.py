@@ -9,6 +9,7 @@ import numpy as np
 
 from .. import _lib
 from .._lib import lib, ptr
+from .pyin import pyin, pyin_batch_dev  # noqa: F401  (the second f0 estimator, beside dio / dio_batch_dev)
 
 default_frame_period = 5.0
 default_f0_floor = 71.0

@@ -20,6 +20,10 @@ class _Unset(int):
 VOCODER_OPTIONS = (
     ('--frame-period', dict(type=int, default=5, help='Frame period milli-seconds of vocoder')),
     ('--mcep-order', dict(type=int, default=24, help='Mel-cepstrum order for spectrum envelope')),
+    # an addition to the reference's options: the coarse f0 track that StoneMask refines
+    ('--f0-estimator', dict(choices=('dio', 'pyin'), default='dio',
+                            help='Coarse f0 estimator of the analysis: dio (WORLD\'s), or pyin, probabilistic YIN with '
+                                 'a Viterbi pass over the utterance; a converter model keeps the one it was trained with')),
 )
 CONVERTER_OPTIONS = (
     ('--source', dict(type=str, help='Source data-set path of voice conversion')),
@@ -440,6 +444,8 @@ class Config:
     # ---- factories --------------------------------------------------------------------------------------
     def create_analyzer(self, *args, Analyzer=None, **kwargs):
         make = Analyzer or _pkg().Analyzer
+        if getattr(self, 'f0_estimator', 'dio') != 'dio':       # (the analyzers of the default take what they always took)
+            kwargs = dict(kwargs, f0_estimator=self.f0_estimator)
         return make(*args, **dict(kwargs, frame_period=self.frame_period, mcep_order=self.mcep_order))
 
     def create_converter(self, Converter=None, **kwargs):
@@ -575,6 +581,12 @@ class Config:
                        else f'with --nonparallel {converter.nonparallel}')
                 self.parser.error(f'{model}: the converter model was trained {was}, not with --nonparallel {asked}; '
                                   f'retrain it with --nonparallel {asked} (a new --converter-model file)')
+            asked = getattr(self, 'f0_estimator', 'dio')
+            if asked != converter.f0_estimator:
+                self.parser.error(f'{model}: the converter model was trained with --f0-estimator '
+                                  f'{converter.f0_estimator}, not {asked}: its voicing term and f0 statistics were learnt '
+                                  f'on the other tracks; retrain it with --f0-estimator {asked} (a new --converter-model '
+                                  f'file)')
             asked = getattr(self, 'converter_covariance', None)
             if asked is not None and asked != converter.covariance:
                 self.parser.error(f'{model}: the converter model was trained with --converter-covariance '
@@ -603,6 +615,7 @@ class Config:
 
     def _train(self, converter, f0_stats=False, gv_stats=False, ms_stats=False, ap_model=False):
         converter.source_f0_rate = self._model_f0_rate = self.resolve_source_f0_rate()
+        converter.f0_estimator = getattr(self, 'f0_estimator', 'dio')
         extra = dict(f0_stats=True) if f0_stats else {}
         if gv_stats:
             extra['gv_stats'] = True

@@ -244,7 +244,7 @@ def convert_synth_batch(conf, converter, paths, diffvc=False, **options):
         res = corpus.convert_batch(waves, fs, converter.gmm, order=converter.order,
                                    frame_period=float(batch[0][1].frame_period), pcm=True, diff=diffvc,
                                    ap_gmm=converter.ap_converter.gmm if o.convert_ap else None,
-                                   **driver_options(converter, o))
+                                   f0_estimator=getattr(conf, 'f0_estimator', 'dio'), **driver_options(converter, o))
         for k, (path, a) in enumerate(batch):
             out[path, False] = _Pcm16(fs, res[1][k].cpu().numpy())
             if diffvc:

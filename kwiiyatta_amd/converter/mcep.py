@@ -92,6 +92,9 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         # parallel data) and its record, a dict per fit
         self.nonparallel = None
         self.nonparallel_history = []
+        # the f0 estimator behind the training set's tracks ('dio' or 'pyin': the voicing term of the alignment and the
+        # f0 statistics were learnt on them): set by whoever prepares the training set, kept in the model file
+        self.f0_estimator = 'dio'
 
     def train(self, dataset, keys, f0_stats=False, gv_stats=False, align_iterations=0, ms_stats=False, ms_length=4096,
               ap_model=False, ap_components=16, **kwargs):
@@ -511,6 +514,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
                 extra.update(nonparallel=int(self.nonparallel), nonparallel_history=np.array(
                     [[r['rows'], r['mcd'], -1 if r['em_iterations'] is None else r['em_iterations']]
                      for r in self.nonparallel_history], dtype=np.float64).reshape(-1, 3))
+            if self.f0_estimator != 'dio':         # (a model trained on DIO's tracks has no such key)
+                extra['f0_estimator'] = str(self.f0_estimator)
             np.savez(fh, format=self.MODEL_FORMAT, order=self.order, fs=self.fs,
                      frame_period=getattr(self, 'frame_period', -1),     # (forwarded to the delta stage)
                      source_f0_rate=float(self.source_f0_rate),
@@ -523,7 +528,8 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
         """the state written by `save` into this (untrained) stack; component count and dimensions come from
         the file.  `f0_stats` / `gv_stats` / `ms_stats` are None for a file without them (written without these statistics, or before
         they existed); `source_f0_rate` is 1.0 for a file without it, `align_iterations` 0 and `align_history` empty,
-        the mixture's `covariance_structure` 'full', `nonparallel` None and `nonparallel_history` empty"""
+        the mixture's `covariance_structure` 'full', `nonparallel` None and `nonparallel_history` empty, `f0_estimator`
+        'dio'"""
         with np.load(path, allow_pickle=False) as z:
             if str(z['format']) != self.MODEL_FORMAT:
                 raise ValueError(f'{path!s}: not a converter model of format {self.MODEL_FORMAT}')
@@ -575,6 +581,7 @@ class MelCepstrumFeatureConverter(abc.MapFeatureConverter):
             self.align_history = [dict(rows=None if n is None else int(n), mcd=float(v), em_iterations=None)
                                   for n, v in zip(rows, mcd)]
             self.nonparallel = int(z['nonparallel']) if 'nonparallel' in z.files else None
+            self.f0_estimator = str(z['f0_estimator']) if 'f0_estimator' in z.files else 'dio'
             history = z['nonparallel_history'] if 'nonparallel_history' in z.files else ()
             self.nonparallel_history = [dict(rows=int(n), mcd=float(v), em_iterations=None if e < 0 else int(e))
                                         for n, v, e in history]

@@ -35,7 +35,7 @@ from ._blocks import Ragged, p as _p, to_device
 from ._convert_options import ConvertOptions, takes_options
 from ._lib import lib
 from .pipeline import (PAD_LEN, PIECE_CEILING, POWER_THRESHOLD, POWER_WEIGHT, SAFE_GUARD_MINIMUM, VUV_WEIGHT, DeviceGMM,
-                       _Graphed, _Side, draw_silence, f0_jobs)
+                       _Graphed, _Side, check_f0_estimator, check_f0_status, coarse_f0_batch_dev, draw_silence, f0_jobs)
 
 TRIM_EPS = 1e-7       # nnmnkwii trim_zeros_frames / remove_zeros_frames
 
@@ -1088,8 +1088,9 @@ class ConvertWave:
 
     @takes_options()
     def __init__(self, ls, fs, utterances, gmm=None, order=24, frame_period=5.0, pcm=False, diff=False, defer_mlsa=False,
-                 resolved=None, ap_gmm=None, **options):
+                 resolved=None, ap_gmm=None, f0_estimator='dio', **options):
         converting = gmm is not None
+        self.f0_estimator = check_f0_estimator(f0_estimator)     # of bare waveforms: 'dio' or 'pyin' in front of StoneMask
         self.ap_gmm = ap_gmm
         opts = resolved or ConvertOptions(**options).check(order, converting).upload(ls.dev, converting)
         self.opts, self.mlpg_em, self.gvgen, self.gvgen_status = opts, opts.mlpg_em, opts.gvgen, None
@@ -1216,7 +1217,7 @@ class ConvertWave:
 
     def status_words(self):
         """(kind, device words, words per utterance) of every status the wave's options write"""
-        own = [('dio', self.f0_status, 1), ('f0_map', self.f0_map_status, 1), ('formant', self.formant_status, 1),
+        own = [(self.f0_estimator, self.f0_status, 1), ('f0_map', self.f0_map_status, 1), ('formant', self.formant_status, 1),
                ('gvgen', self.gvgen_status, 2)] + [(f.kind, f.status, f.words) for f in self.filters]
         return [item for item in own if item[1] is not None]
 
@@ -1224,8 +1225,7 @@ class ConvertWave:
         ls, fs, fft, K, order, n, opts = self.ls, self.fs, self.fft, self.K, self.order, self.n, self.opts
         if self.wav_in:
             with torch.cuda.stream(ls.main):
-                _lib.check(ls.ctx, lib.kwy_dio_batch_dev(ls.ctx.handle, self.j_dio, n, fs, 71.0, 800.0, 2.0,
-                                                         self.frame_period, 1, 0.1))
+                coarse_f0_batch_dev(ls.ctx, self.f0_estimator, self.j_dio, n, fs, self.frame_period, lib=lib)
                 _lib.check(ls.ctx, lib.kwy_stonemask_batch_dev(ls.ctx.handle, self.j_sm, n, fs))
         ls.side.wait_stream(ls.main)
         with torch.cuda.stream(ls.side):
@@ -1304,7 +1304,7 @@ class ConvertWave:
             _finish_diff(ctx, self.j_fin_diff, self.n, self.fs)
 
 
-_STATUS_KINDS = ('dio', 'f0_map', 'gv', 'ms', 'formant', 'gvgen', 'power')
+_STATUS_KINDS = ('dio', 'pyin', 'f0_map', 'gv', 'ms', 'formant', 'gvgen', 'power')
 
 
 def _check_dio_status(status):
@@ -1326,7 +1326,7 @@ def _check_status_words(items, fs):
     folded = {}
     for (kind, w, per), words in zip(items, host):
         folded.setdefault(kind, []).append(words.reshape(per, w.numel() // per).sum(0))
-    checks = dict(dio=_check_dio_status, f0_map=lambda w: f0.check_status(w, fs), gv=gv.check_status, ms=ms.check_status,
+    checks = dict(dio=_check_dio_status, pyin=lambda w: check_f0_status('pyin', w), f0_map=lambda w: f0.check_status(w, fs), gv=gv.check_status, ms=ms.check_status,
                   formant=lambda w: formant.check_status(w, what='wave(s)'), gvgen=_check_gvgen_status,
                   power=power.check_status)
     for kind, parts in folded.items():
@@ -1334,7 +1334,7 @@ def _check_status_words(items, fs):
 
 
 def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, keep, opts, wave_size=16, pcm=False,
-                    diff=False, ap_gmm=None):
+                    diff=False, ap_gmm=None, f0_estimator='dio'):
     """utterances in waves of `wave_size` through ConvertWave; keep(i, waveform view, pcm view, differential waveform
     view, its pcm view) on the main stream, None for what was not asked for.  opts: a checked `ConvertOptions`, uploaded
     here once for all waves.
@@ -1346,7 +1346,7 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     held, deferred, status = [], [], []
     for w0 in range(0, len(utterances), wave_size):
         wv = ConvertWave(ls, fs, utterances[w0:w0 + wave_size], gmm=gmm, order=order, frame_period=frame_period, pcm=pcm,
-                         diff=diff, defer_mlsa=defer, resolved=resolved, ap_gmm=ap_gmm)
+                         diff=diff, defer_mlsa=defer, resolved=resolved, ap_gmm=ap_gmm, f0_estimator=f0_estimator)
         wv.run()
         with torch.cuda.stream(ls.main):
             for i in range(wv.n):
@@ -1778,7 +1778,8 @@ def _stream_batch(make_pipeline, utterances, pool, shapes_per_stream, keep):
 
 @takes_options()
 def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.0, streams=16, pool=None,
-                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, ap_gmm=None, **options):
+                  shapes_per_stream=4, driver=None, lockstep=None, pcm=False, diff=False, ap_gmm=None, f0_estimator='dio',
+                  **options):
     """Convert this rank's utterances with the fitted mixture: list of waveforms (device tensors).
     Lockstep driver only: an utterance may be a bare waveform (its f0 is then extracted on the device), and pcm=True
     returns (waveforms, int16 tensors of the post-processed samples) -- wav in, 16-bit PCM out without the host;
@@ -1789,8 +1790,12 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
     **options: the keywords of `ConvertOptions`, which describes each (lockstep driver; every value is checked before
     anything is put on the device).
     ap_gmm (lockstep driver): the fitted band-aperiodicity mixture (weights_, means_, covariances_ over 6 B dimensions):
-    the synthesised outputs are rendered on the converted aperiodicity (`ConvertWave`); None: on the analysed one."""
+    the synthesised outputs are rendered on the converted aperiodicity (`ConvertWave`); None: on the analysed one.
+    f0_estimator (lockstep driver): 'dio' or 'pyin', the coarse f0 track of bare waveforms in front of StoneMask
+    (kwy_dio_batch_dev / kwy_pyin_batch_dev); with 'pyin' a sample that is not finite is a ValueError after the batch."""
     opts = ConvertOptions(**options).check(order)
+    if check_f0_estimator(f0_estimator) != 'dio' and (driver or ('streams' if pool is not None else 'lockstep')) != 'lockstep':
+        raise ValueError("convert_batch: f0_estimator='pyin' needs the lockstep driver")
     driver = driver or ('streams' if pool is not None else 'lockstep')     # (a caller's pool asks for the stream driver)
     if driver != 'lockstep' and opts.need_lockstep():
         raise ValueError(f'convert_batch: {opts.need_lockstep()[0]} the lockstep driver')
@@ -1809,7 +1814,7 @@ def convert_batch(utterances, fs, gmm, device_index=0, order=24, frame_period=5.
         def keep_view(i, w, p, wd, pd):
             out[i], pcms[i], dwav[i], dpcm[i] = w, p, wd, pd      # (views of their wave's blocks, which live as long as the views)
         _lockstep_batch(utterances, fs, device_index, dg, order, frame_period, lockstep, keep_view, opts, pcm=pcm, diff=diff,
-                        ap_gmm=ap_gmm)
+                        ap_gmm=ap_gmm, f0_estimator=f0_estimator)
         if diff:
             return out, (pcms if pcm else None), dwav, (dpcm if pcm else None)
         return (out, pcms) if pcm else out

@@ -324,7 +324,8 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
             batch.append((key, (source, _triple(pair[1])), float(pair[0].frame_period)))
     rate = getattr(converter, 'source_f0_rate', 1.0)
     if batch and rate != 1:
-        sources = _shifted_triples([pair[0][0] for _, pair, _ in batch], converter.fs, rate, batch[0][2])
+        sources = _shifted_triples([pair[0][0] for _, pair, _ in batch], converter.fs, rate, batch[0][2],
+                                   f0_estimator=getattr(conf, 'f0_estimator', 'dio'))
         batch = [(key, (src, pair[1]), period) for (key, pair, period), src in zip(batch, sources)]
     if batch:
         asked = SimpleNamespace(**dict(COMMAND_OPTIONS, gv=options['gv'], convert_f0=options['convert_f0'],
@@ -341,9 +342,10 @@ def _evaluate_batched(conf, converter, dataset, keys, options):
     return [results[key] for key in keys]
 
 
-def _shifted_triples(waves, fs, rate, frame_period, group=16):
+def _shifted_triples(waves, fs, rate, frame_period, group=16, f0_estimator='dio'):
     """(x, f0, t) device tensors per waveform: the waveforms through ONE kwy_pitch_shift_batch_dev call
-    (convert_voice.shift_waves_dev), then DIO + StoneMask on the device, as Analyzer.extract_f0 runs them"""
+    (convert_voice.shift_waves_dev), then DIO (or, with f0_estimator='pyin', pYIN) + StoneMask on the device, as
+    Analyzer.extract_f0 runs them"""
     import torch
     from . import _lib
     from .backend import world
@@ -354,13 +356,14 @@ def _shifted_triples(waves, fs, rate, frame_period, group=16):
     ts, coarse, f0 = ([torch.empty(n, dtype=torch.float64, device=xs[0].device) for n in frames] for _ in range(3))
     status = torch.zeros(len(xs), dtype=torch.int32, device=xs[0].device)
     torch.cuda.current_stream(xs[0].device).synchronize()
+    from .pipeline import check_f0_status, coarse_f0_batch_dev, f0_jobs
     for g in range(0, len(xs), group):
         sl = slice(g, g + group)
-        world.dio_batch_dev(ctx, xs[sl], fs, ts[sl], coarse[sl], status=status[sl], frame_period=frame_period)
+        jobs, _ = f0_jobs(xs[sl], ts[sl], coarse[sl], f0[sl], status[sl])
+        coarse_f0_batch_dev(ctx, f0_estimator, jobs, len(xs[sl]), int(fs), float(frame_period))
         world.stonemask_batch_dev(ctx, xs[sl], ts[sl], coarse[sl], fs, f0[sl])
     ctx.sync()
-    if status.any().item():
-        raise RuntimeError('dio: zero-crossing buffer overflow')
+    check_f0_status(f0_estimator, status.cpu().numpy())
     return list(zip(xs, f0, ts))
 
 

@@ -28,6 +28,7 @@ import torch
 from . import _lib
 from ._blocks import Ragged, p as _p, to_device
 from ._lib import lib
+from .backend.pyin import F0_ESTIMATORS, check_estimator as check_f0_estimator      # noqa: F401 (names of this module)
 
 EPS = 2.220446049250313e-16
 SAFE_GUARD_MINIMUM = 1e-12
@@ -303,6 +304,31 @@ class PairPipeline(_Graphed):
         self.ctx.sync()
 
 
+def coarse_f0_batch_dev(ctx, estimator, jobs, n, fs, frame_period, lib=lib):
+    """THE estimator dispatch of the device drivers: the coarse f0 tracks of the n utterances of a kwy_f0_job table,
+    enqueued on the context's stream: DIO's (kwy_dio_batch_dev) or pYIN's (kwy_pyin_batch_dev), each at the analyzers'
+    defaults.  The status words mean an overflow of DIO's zero-crossing buffers, or for pYIN a sample that is not
+    finite.  lib: the binding the calls go through (a driver module passes its own, which its tests may stand in for).
+    (The estimator is a keyword of the drivers, not a field of ConvertOptions: that record is the set of CONVERSION
+    options, pinned name by name by tests/test_em_cases.py, and this one belongs to the analysis in front of it.)"""
+    from .backend import pyin
+    if estimator == 'pyin':
+        _lib.check(ctx, lib.kwy_pyin_batch_dev(ctx.handle, jobs, n, fs, pyin.default_f0_floor, pyin.default_f0_ceil,
+                                               frame_period, pyin.default_p_a, pyin.default_switch_prob,
+                                               pyin.default_max_rate))
+    else:
+        _lib.check(ctx, lib.kwy_dio_batch_dev(ctx.handle, jobs, n, fs, 71.0, 800.0, 2.0, frame_period, 1, 0.1))
+
+
+def check_f0_status(estimator, status):
+    """raise for the non-zero status words of `coarse_f0_batch_dev` (a host array, one word per utterance)"""
+    bad = [i for i, s in enumerate(status) if int(s)]
+    if bad and estimator == 'pyin':
+        raise ValueError(f'pyin: a sample of the signal is not finite in utterance(s) {bad}')
+    if bad:
+        raise RuntimeError(f'dio: zero-crossing buffer overflow in utterance(s) {bad} (signal too noisy for the band filters)')
+
+
 def f0_jobs(x, t, f0_dio, f0, status):
     """The job arrays of the f0 extraction of a wave of bare waveforms `x` (lists of per-utterance views): DIO's
     (kwy_dio_batch_dev: frame times into `t`, its track into `f0_dio`, one word of `status` per utterance) and
@@ -478,10 +504,12 @@ class PairBatchPipeline(_Graphed):
 
     def __init__(self, device_index, fs, pairs, gmm, order=24, radius=32, frame_period=5.0, waves=2, rng=None,
                  silence=None, rng_place='side', serial=False, max_wave=16, wav_in=False, pcm=False, fused_mcep=True,
+                 f0_estimator='dio',
                  chain_priority=False):
         self.dev = torch.device('cuda', device_index)
         self.chain_priority = bool(chain_priority)
         self.wav_in, self.pcm, self.fused_mcep = bool(wav_in), bool(pcm), bool(fused_mcep)
+        self.f0_estimator = check_f0_estimator(f0_estimator)
         self.fs, self.order, self.radius, self.frame_period = int(fs), int(order), int(radius), float(frame_period)
         self.fft = lib.kwy_cheaptrick_fft_size(self.fs, 71.0)
         self.K = self.fft // 2 + 1
@@ -559,8 +587,7 @@ class PairBatchPipeline(_Graphed):
                 # tools/capture_probe.py.  The kernels are chip-wide anyway.)
                 c0 = self.waves[0].ctx
                 for wv in self.waves:
-                    _lib.check(c0, lib.kwy_dio_batch_dev(c0.handle, wv.j_dio, 2 * wv.n, fs, 71.0, 800.0, 2.0,
-                                                         self.frame_period, 1, 0.1))
+                    coarse_f0_batch_dev(c0, self.f0_estimator, wv.j_dio, 2 * wv.n, fs, self.frame_period)
                     _lib.check(c0, lib.kwy_stonemask_batch_dev(c0.handle, wv.j_sm, 2 * wv.n, fs))
             for wv in self.waves:
                 if wv.stream is not origin:

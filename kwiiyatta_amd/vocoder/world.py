@@ -11,13 +11,16 @@ import numpy as np
 import scipy.interpolate
 
 from ..backend import world as pyworld
+from ..backend.pyin import F0_ESTIMATORS, check_estimator
 from ..wavfile import Wavdata
 from . import abc
 
 
 class WorldAnalyzer(abc.Analyzer):
-    def __init__(self, *args, **kwargs):
+    def __init__(self, *args, f0_estimator='dio', **kwargs):
         super().__init__(*args, **kwargs)
+        self.f0_estimator = check_estimator(f0_estimator)
+        self._f0_from = None           # the estimator behind the track in `_f0`, once `extract_f0` has made it
         self._data = np.ascontiguousarray(self._data)      # pyworld's contract: C-contiguous float64
         self._timeaxis = None
 
@@ -26,9 +29,17 @@ class WorldAnalyzer(abc.Analyzer):
         samples = self.data.shape[0]
         return samples * 1000 // self.fs // self.frame_period + 1      # integer arithmetic throughout
 
-    def extract_f0(self, **kwargs):
+    def extract_f0(self, estimator=None, **kwargs):
+        """the f0 track: the coarse track of `estimator` -- 'dio' (the reference's) or 'pyin' (probabilistic YIN);
+        default: the analyzer's `f0_estimator`, 'dio' unless it was made with another -- refined by StoneMask; kwargs
+        go to the estimator.  The track is made once: asking for another estimator's afterwards is a ValueError"""
+        estimator = check_estimator(estimator or self.f0_estimator)
+        if self._f0 is not None and self._f0_from not in (None, estimator):
+            raise ValueError(f"extract_f0: this analyzer holds {self._f0_from}'s track already, not {estimator}'s")
         if self._f0 is None:
-            coarse, self._timeaxis = pyworld.dio(self.data, self.fs, frame_period=self.frame_period, **kwargs)
+            self._f0_from = estimator
+            coarse_track = pyworld.pyin if estimator == 'pyin' else pyworld.dio
+            coarse, self._timeaxis = coarse_track(self.data, self.fs, frame_period=self.frame_period, **kwargs)
             self._f0 = pyworld.stonemask(self.data, coarse, self._timeaxis, self.fs)
         return self._f0
 
