@@ -1340,6 +1340,13 @@ def _lockstep_batch(utterances, fs, device_index, gmm, order, frame_period, ls, 
     here once for all waves.
     Bare waveforms get their f0 on the device; the status words of all waves are read back ONCE at the end
     (`_check_status_words`).  ap_gmm: a DeviceGMM for every wave's aperiodicity conversion (`ConvertWave`), or None."""
+    if gmm is not None and opts.ms_strength > 0:
+        # an utterance longer than the transform is a ValueError BEFORE the batch (`ConvertOptions`): every frame count is
+        # known here, and the per-wave check of `_MsFilter` would fire with the earlier waves already enqueued
+        from .backend import ms as msfilter
+        bare = len(utterances) > 0 and not isinstance(utterances[0], (tuple, list))
+        msfilter._fits([int(lib.kwy_dio_frames(int(fs), len(u), float(frame_period))) if bare else len(u[1])
+                        for u in utterances], 2 * (np.shape(opts.ms_stats[0])[1] - 1))
     ls = ls if ls is not None else _Lockstep(device_index)
     resolved = opts.upload(ls.dev, converting=gmm is not None)
     defer = bool(diff) and gmm is not None and resolved.diff_filter == 'mlsa'
